@@ -2,6 +2,7 @@
 """Benchmark of the hot path: ADMM iterations/sec on synthetic n x d data.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--rows R] [--cols D] [--config NAME] [--storage f32|f64]
+                    [--full] [--dump-outputs DIR]
 
 Workload at N=1 (BASELINE.json configs[1], "C2"): SRM, erm weights, binary cross entropy,
 l1_reg = 0.01, synthetic 6 000 000 x 1 000 generated on the device, D stored fp32
@@ -14,9 +15,14 @@ GPUs (strong scaling, one rank per GPU, launched by torch.distributed.run): erm 
 all-reduce of 2 ld + 3 doubles per iteration; rank-weighted ones add the distributed z-step's exchanges
 (`config.collectives_per_iteration` / `config.host_syncs_per_iteration` in the N > 1 line say how many).
 
-Prints ONE JSON line with the contract fields plus
+A plain run sets up, warms up, times K steps and prints ONE JSON line with the contract fields (`value` = K / the
+wall-clock of the K timed steps, `ms_per_step` its inverse in ms) and the step counters in `config`.
+--dump-outputs DIR then writes what the timed path computed in its last step (`get_state()` and the step's
+statistics) to DIR/*.npy, see dump_outputs().  --full adds the records below, each of which costs time of its own
+(--no-gap, --no-c1, --no-cpu-baseline leave single ones out):
   roofline:     algorithmic HBM bytes of the dominant sweep kernel / its average launch
-                duration (HIP events on the library's stream, inside the timed region)
+                duration (HIP events on the library's stream, inside the timed region), beside the box's measured
+                device-to-device copy rate
   cpu_baseline: the reference-faithful CPU restatement (oracle, "port") timed on this
                 box's host cores on a bounded sample of the same workload (rank 0, N=1); one-time setup
                 (D, D^T D) and the first iterations are timed separately from the per-iteration rate
@@ -292,6 +298,98 @@ def c1_record(rbl, device):
                               "source": "table/erm_synthetic_6000x1000_l1_binary_cross_entropy.xlsx (BASELINE.md section 1)"}}
 
 
+DUMP_ROWS = 1_000_000    # z and lambda rows written by dump_outputs (2 x 48 MB in full at C2 would pass the 64 MB cap)
+
+
+def dump_outputs(s, last, out_dir, row_offset):
+    """What a caller of the timed path receives after its last step, as float64 .npy files in out_dir:
+      w.npy          the iterate w_k (d entries, in full)
+      z.npy, lam.npy z and lambda at the rows listed in row_index.npy: all rows up to DUMP_ROWS, otherwise a fixed
+                     sample of DUMP_ROWS rows (seed 0, sorted); with N > 1 ranks, rank 0's rows
+      row_index.npy  the global row numbers of those entries
+      last_step.npy  the step's statistics: iteration, primal residual, dual residual, rho, rho of the next iteration
+    Together at most 3 x 8 MB + 8 d bytes.  get_state() waits for the device and runs after the timed region."""
+    import numpy as np
+    st = s.get_state()
+    n = s.n
+    if n <= DUMP_ROWS:
+        idx = np.arange(n)
+    else:
+        idx = np.sort(np.random.default_rng(0).choice(n, size=DUMP_ROWS, replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"w": st["w"], "z": st["z"][idx], "lam": st["lam"][idx], "row_index": idx + row_offset,
+              "last_step": [last.iter, last.primal, last.dual, last.rho, last.rho_next]}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.asarray(a, dtype=np.float64))
+
+
+def roofline_record(torch, _lib, s, a, world, local_rank, n_local, n_total, d, t_steps):
+    """--full: the dominant sweep kernel's HIP-event times over the timed steps against the HBM peak and the box's
+    measured device copy rate (runs after the timed region)."""
+    # the box's own device-to-device copy rate, AFTER the timed region (measured before it - 16 GB allocated and freed
+    # ahead of the data - the sweep ran 1-1.5 % slower for the whole run: interleaved on one box 277.9 / 278.3 against
+    # 282.0 / 281.6 it/s; physical placement of the 24 GB matrix)
+    copy_gbs = (device_copy_rate(torch, torch.device("cuda", local_rank))
+                if world == 1 and os.environ.get("RBL_BENCH_NO_COPY") != "1" else None)
+    esz = 4 if a.storage == "f32" else 8
+    kt = {}
+    for name, kid in (("gemv", _lib.KERNEL_GEMV), ("gemvt", _lib.KERNEL_GEMVT), ("sweep_erm", _lib.KERNEL_SWEEP_ERM)):
+        ms, cnt = s.kernel_time(kid)
+        kt[name] = dict(avg_ms=ms / max(cnt, 1), launches=cnt, total_ms=ms, samples=s.kernel_samples(kid))
+    dom = max(kt, key=lambda k: kt[k]["total_ms"])     # the kernel the timed region spends most time in
+    bytes_per_launch = n_local * d * esz            # algorithmic: every element of this rank's D read once
+    achieved = bytes_per_launch / (kt[dom]["avg_ms"] * 1e-3) / 1e9 if kt[dom]["avg_ms"] > 0 else 0.0
+    # One record shows both ends of the timed region (VERDICT r2 item 2): the first and the last timed launch of
+    # the dominant kernel, and a steady-state sub-record = the median over the LAST THIRD of the timed launches
+    # (kernel) and of the timed steps (wall clock between the returns of consecutive step() calls).  `value`,
+    # `ms_per_step`, `achieved` and `frac` stay the means over all K timed steps.
+    import statistics
+    smp = [float(x) for x in kt[dom]["samples"]]
+    third = smp[len(smp) - max(1, len(smp) // 3):] if smp else []
+    k_med = statistics.median(third) if third else 0.0
+    dts = [t_steps[i] - t_steps[i - 1] for i in range(1, len(t_steps))]
+    dts_third = dts[len(dts) - max(1, len(dts) // 3):] if dts else []
+    step_med = statistics.median(dts_third) if dts_third else 0.0
+    steady = {"launches": len(third), "kernel_ms_median": round(k_med, 4),
+              "achieved": (bytes_per_launch / (k_med * 1e-3) / 1e9) if k_med > 0 else 0.0,
+              "frac": (bytes_per_launch / (k_med * 1e-3) / 1e9 / HBM_PEAK_GBS) if k_med > 0 else 0.0,
+              "ms_per_step_median": round(step_med * 1e3, 4),
+              "iterations_per_s": (1.0 / step_med) if step_med > 0 else 0.0,
+              "window": "median over the last third of the timed launches / timed steps"}
+    # HBM traffic cannot be counted from inside this process (PMC counters need rocprofv3 passes of their own,
+    # MI355X_MICROARCH.md): the figure is READ from the committed summary of such passes over this same
+    # command (tools/profile_round.sh -> profiles/traffic_latest.json) and labelled with its source; null
+    # when no summary matches the workload
+    traffic, traffic_source = None, None
+    tpath = os.path.join(ROOT, "profiles", "traffic_latest.json")
+    if os.path.exists(tpath) and world == 1:
+        try:
+            tj = json.load(open(tpath))
+            if tj.get("rows") == n_total and tj.get("cols") == d and tj.get("storage") == a.storage:
+                traffic = tj.get("kernels", {}).get(dom, {}).get("hbm_bytes_per_launch")
+                if traffic is not None:
+                    traffic_source = ("profiles/traffic_latest.json: rocprofv3 --pmc passes (FETCH_SIZE, WRITE_SIZE) of "
+                                      "this command in an EARLIER run on another box (%s), not measured in this run"
+                                      % tj.get("source", "see tools/profile_round.sh"))
+        except Exception:
+            traffic = None
+    prof_every = 1 if world == 1 else (4 if a.steps >= 16 else 1)
+    return {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+            "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_source,
+            "kernel": "k_" + dom,
+            "device_copy_GBs": round(copy_gbs, 1) if copy_gbs else None,
+            "achieved_over_device_copy": round(achieved / copy_gbs, 3) if copy_gbs else None,
+            "bytes_per_launch": bytes_per_launch, "timed_every": prof_every,
+            "kernel_ms_first": round(smp[0], 4) if smp else None,
+            "kernel_ms_last": round(smp[-1], 4) if smp else None,
+            "kernel_ms_min": round(min(smp), 4) if smp else None,
+            "kernel_ms_max": round(max(smp), 4) if smp else None,
+            "steady_state": steady,
+            "kernels": {k: {"avg_ms": round(v["avg_ms"], 4), "launches": v["launches"],
+                            "GBps": round(bytes_per_launch / (v["avg_ms"] * 1e-3) / 1e9, 1)
+                            if v["avg_ms"] > 0 else 0.0} for k, v in kt.items()}}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -301,9 +399,14 @@ def main():
     ap.add_argument("--rows", type=int, default=0)
     ap.add_argument("--cols", type=int, default=0)
     ap.add_argument("--storage", default="f32", choices=["f32", "f64"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-gap", action="store_true", help="skip the wall-clock-to-1e-6-gap run (and its F* run)")
-    ap.add_argument("--no-c1", action="store_true", help="skip the C1 (6000x1000 reference data) sub-record")
+    ap.add_argument("--full", action="store_true",
+                    help="also the records beyond the headline figure: kernel events + roofline, the device copy rate, "
+                         "the F* / time-to-gap run, C1 and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/*.npy (float64, see dump_outputs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-gap", action="store_true", help="with --full: skip the wall-clock-to-1e-6-gap run (and its F* run)")
+    ap.add_argument("--no-c1", action="store_true", help="with --full: skip the C1 (6000x1000 reference data) sub-record")
     ap.add_argument("--phase-times", action="store_true",
                     help="HIP events around every phase (config.phase_ms_last); costs ~5 us of stream time per event")
     ap.add_argument("--seed", type=int, default=17)
@@ -311,6 +414,8 @@ def main():
                     help="N=1 only: run the multi-GPU driver (ShardedADMM over a 1-rank RCCL group) instead of the "
                          "single handle, to measure the driver's own per-iteration cost")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
 
     import torch
     import torch.distributed as dist
@@ -369,12 +474,15 @@ def main():
     # the timed region, the first half of round 3 had them between the set-up and the warm-up; now the device goes
     # Gram product -> warm-up -> timed steps without a host-side pause.
     import gc
+    # the kernel events feed the roofline record of --full; a plain run's iterations carry none
+    profiled = a.full or a.phase_times
 
     def quiet_host():
-        s.profile_kernels(2 if a.phase_times else 1)
-        # HIP events around every launch of the sweep kernels at N = 1 (two event records cost ~11 us of stream
-        # time, 0.3 % of a 4 ms pass); every 4th one with several GPUs, where a rank's pass is 0.55 ms
-        s.profile_sampling(1 if world == 1 else (4 if a.steps >= 16 else 1))
+        if profiled:
+            s.profile_kernels(2 if a.phase_times else 1)
+            # HIP events around every launch of the sweep kernels at N = 1 (two event records cost ~11 us of stream
+            # time, 0.3 % of a 4 ms pass); every 4th one with several GPUs, where a rank's pass is 0.55 ms
+            s.profile_sampling(1 if world == 1 else (4 if a.steps >= 16 else 1))
         gc.collect()
         gc.disable()      # no collector pause inside the timed region (with N ranks the slowest one sets the pace)
 
@@ -392,10 +500,10 @@ def main():
         step = lambda: s.step(False)
     torch.cuda.synchronize()
     t_setup = time.perf_counter() - t_setup
-    prof_every = 1 if world == 1 else (4 if a.steps >= 16 else 1)
     for _ in range(a.warmup):
         step()
-    s.reset_kernel_times()      # host bookkeeping only: the device goes straight from the warm-up into the timed steps
+    if profiled:
+        s.reset_kernel_times()      # host bookkeeping only: the device goes straight from the warm-up into the timed steps
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
@@ -422,54 +530,8 @@ def main():
         t = torch.tensor([dt], dtype=torch.float64, device="cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
-
-    # the box's own device-to-device copy rate, AFTER the timed region (measured before it - 16 GB allocated and freed
-    # ahead of the data - the sweep ran 1-1.5 % slower for the whole run: interleaved on one box 277.9 / 278.3 against
-    # 282.0 / 281.6 it/s; physical placement of the 24 GB matrix)
-    copy_gbs = (device_copy_rate(torch, torch.device("cuda", local_rank))
-                if world == 1 and os.environ.get("RBL_BENCH_NO_COPY") != "1" else None)
-    esz = 4 if a.storage == "f32" else 8
-    kt = {}
-    for name, kid in (("gemv", _lib.KERNEL_GEMV), ("gemvt", _lib.KERNEL_GEMVT), ("sweep_erm", _lib.KERNEL_SWEEP_ERM)):
-        ms, cnt = s.kernel_time(kid)
-        kt[name] = dict(avg_ms=ms / max(cnt, 1), launches=cnt, total_ms=ms, samples=s.kernel_samples(kid))
-    dom = max(kt, key=lambda k: kt[k]["total_ms"])     # the kernel the timed region spends most time in
-    bytes_per_launch = n_local * d * esz            # algorithmic: every element of this rank's D read once
-    achieved = bytes_per_launch / (kt[dom]["avg_ms"] * 1e-3) / 1e9 if kt[dom]["avg_ms"] > 0 else 0.0
-    # One record shows both ends of the timed region: the first and the last timed launch of
-    # the dominant kernel, and a steady-state sub-record = the median over the LAST THIRD of the timed launches
-    # (kernel) and of the timed steps (wall clock between the returns of consecutive step() calls).  `value`,
-    # `ms_per_step`, `achieved` and `frac` stay the means over all K timed steps.
-    import statistics
-    smp = [float(x) for x in kt[dom]["samples"]]
-    third = smp[len(smp) - max(1, len(smp) // 3):] if smp else []
-    k_med = statistics.median(third) if third else 0.0
-    dts = [t_steps[i] - t_steps[i - 1] for i in range(1, len(t_steps))]
-    dts_third = dts[len(dts) - max(1, len(dts) // 3):] if dts else []
-    step_med = statistics.median(dts_third) if dts_third else 0.0
-    steady = {"launches": len(third), "kernel_ms_median": round(k_med, 4),
-              "achieved": (bytes_per_launch / (k_med * 1e-3) / 1e9) if k_med > 0 else 0.0,
-              "frac": (bytes_per_launch / (k_med * 1e-3) / 1e9 / HBM_PEAK_GBS) if k_med > 0 else 0.0,
-              "ms_per_step_median": round(step_med * 1e3, 4),
-              "iterations_per_s": (1.0 / step_med) if step_med > 0 else 0.0,
-              "window": "median over the last third of the timed launches / timed steps"}
-    # HBM traffic cannot be counted from inside this process (PMC counters need rocprofv3 passes of their own,
-    # MI355X_MICROARCH.md): the figure is READ from the committed summary of such passes over this same
-    # command (tools/profile_round.sh -> profiles/traffic_latest.json) and labelled with its source; null
-    # when no summary matches the workload
-    traffic, traffic_source = None, None
-    tpath = os.path.join(ROOT, "profiles", "traffic_latest.json")
-    if os.path.exists(tpath) and world == 1:
-        try:
-            tj = json.load(open(tpath))
-            if tj.get("rows") == n_total and tj.get("cols") == d and tj.get("storage") == a.storage:
-                traffic = tj.get("kernels", {}).get(dom, {}).get("hbm_bytes_per_launch")
-                if traffic is not None:
-                    traffic_source = ("profiles/traffic_latest.json: rocprofv3 --pmc passes (FETCH_SIZE, WRITE_SIZE) of "
-                                      "this command in an EARLIER run on another box (%s), not measured in this run"
-                                      % tj.get("source", "see tools/profile_round.sh"))
-        except Exception:
-            traffic = None
+    if a.dump_outputs and rank == 0:
+        dump_outputs(s, last, a.dump_outputs, off)
 
     if rank == 0:
         out = {
@@ -490,22 +552,10 @@ def main():
                        "collectives_per_iteration": round(n_coll / a.steps, 2),
                        "driver_syncs_per_iteration": round(n_drv_sync / a.steps, 2),
                        "host_syncs_per_iteration": round(n_lib_sync / a.steps, 2)},
-            "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_source,
-                         "kernel": "k_" + dom,
-                         "device_copy_GBs": round(copy_gbs, 1) if copy_gbs else None,
-                         "achieved_over_device_copy": round(achieved / copy_gbs, 3) if copy_gbs else None,
-                         "bytes_per_launch": bytes_per_launch, "timed_every": prof_every,
-                         "kernel_ms_first": round(smp[0], 4) if smp else None,
-                         "kernel_ms_last": round(smp[-1], 4) if smp else None,
-                         "kernel_ms_min": round(min(smp), 4) if smp else None,
-                         "kernel_ms_max": round(max(smp), 4) if smp else None,
-                         "steady_state": steady,
-                         "kernels": {k: {"avg_ms": round(v["avg_ms"], 4), "launches": v["launches"],
-                                         "GBps": round(bytes_per_launch / (v["avg_ms"] * 1e-3) / 1e9, 1)
-                                         if v["avg_ms"] > 0 else 0.0} for k, v in kt.items()}},
         }
-        if world == 1 and not a.no_gap:
+        if a.full:
+            out["roofline"] = roofline_record(torch, _lib, s, a, world, local_rank, n_local, n_total, d, t_steps)
+        if a.full and world == 1 and not a.no_gap:
             try:
                 # F* from a separate tightened run: fp64 storage when a second copy of D fits beside this one
                 fs_storage = "f64" if n_total * d * 8 <= 110e9 else a.storage
@@ -522,13 +572,13 @@ def main():
                 out["config"]["time_to_gap"] = time_to_gap(s, cfg, n_total, d, fs["F_star"])
             except Exception as e:      # the second half of the metric is informative, never fatal
                 out["config"]["time_to_gap"] = {"error": repr(e)[:200]}
-        if world == 1 and not a.no_c1 and a.config == "C2" and not a.rows and not a.cols:
+        if a.full and world == 1 and not a.no_c1 and a.config == "C2" and not a.rows and not a.cols:
             try:
                 s.close()
                 out["config"]["c1"] = c1_record(rbl, local_rank)
             except Exception as e:
                 out["config"]["c1"] = {"error": repr(e)[:200]}
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(cfg)
         sys.stdout.flush()
         if saved_stdout is not None:

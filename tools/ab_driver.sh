@@ -9,7 +9,7 @@ for rep in 1 2; do
     i=$((i+1))
     f=$out/drv_s${i}_r${rep}
     if [ "$setting" = "-" ]; then envs=""; else envs="$setting"; fi
-    env $envs timeout -k 10 300 python bench.py --sharded-driver --rows 750000 --steps 200 --no-gap --no-cpu-baseline --no-c1 > $f.json 2> $f.err || { echo "FAILED: $setting"; tail -3 $f.err; exit 1; }
+    env $envs timeout -k 10 300 python bench.py --full --sharded-driver --rows 750000 --steps 200 --no-gap --no-cpu-baseline --no-c1 > $f.json 2> $f.err || { echo "FAILED: $setting"; tail -3 $f.err; exit 1; }
     python - $f.json "$setting" <<'PY'
 import json, sys
 j = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

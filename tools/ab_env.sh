@@ -7,7 +7,7 @@ for cfg in "$@"; do
   for rep in 1 2; do
     for mode in new old; do
       if [ $mode = old ]; then export "$kv"; else unset "${kv%%=*}"; fi
-      timeout -k 10 300 python bench.py --config $cfg --no-gap --no-cpu-baseline --no-c1 --steps 50 \
+      timeout -k 10 300 python bench.py --full --config $cfg --no-gap --no-cpu-baseline --no-c1 --steps 50 \
           > $out/${cfg}_${mode}_r${rep}.json 2> $out/${cfg}_${mode}_r${rep}.err || exit 1
       python - $out/${cfg}_${mode}_r${rep}.json $cfg $mode "$kv" <<'PY'
 import json, sys

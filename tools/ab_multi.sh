@@ -11,7 +11,7 @@ for rep in 1 2; do
     i=$((i+1))
     f=$out/${cfg}_s${i}_r${rep}
     if [ "$setting" = "-" ]; then envs=""; else envs="$setting"; fi
-    env $envs timeout -k 10 300 python bench.py --config $cfg $AB_ARGS --no-gap --no-cpu-baseline --no-c1 --steps 50 > $f.json 2> $f.err || { echo "FAILED: $setting"; tail -3 $f.err; exit 1; }
+    env $envs timeout -k 10 300 python bench.py --full --config $cfg $AB_ARGS --no-gap --no-cpu-baseline --no-c1 --steps 50 > $f.json 2> $f.err || { echo "FAILED: $setting"; tail -3 $f.err; exit 1; }
     python - $f.json $cfg "$setting" <<'PY'
 import json, sys
 j = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

@@ -7,7 +7,7 @@ mkdir -p $out
 for cfg in $cfgs; do
   for rep in 1 2; do
     for mode in 1 0; do
-      RBL_WSTEP_PERSIST=$mode timeout -k 10 300 python bench.py --config $cfg --no-gap --no-cpu-baseline --no-c1 --steps 50 \
+      RBL_WSTEP_PERSIST=$mode timeout -k 10 300 python bench.py --full --config $cfg --no-gap --no-cpu-baseline --no-c1 --steps 50 \
           > $out/${cfg}_p${mode}_r${rep}.json 2> $out/${cfg}_p${mode}_r${rep}.err || exit 1
       python - $out/${cfg}_p${mode}_r${rep}.json $cfg $mode <<'PY'
 import json, sys

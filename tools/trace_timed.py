@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Per-launch durations of the dominant sweep kernel in a rocprofv3 kernel trace of `bench.py --steps K --warmup W`,
+"""Per-launch durations of the dominant sweep kernel in a rocprofv3 kernel trace of `bench.py --full --steps K --warmup W`,
 and the mean over the K timed launches - the figure bench.py's HIP events report (the *_kernel_stats.csv beside it
 averages the W warm-up launches in as well).
     python tools/trace_timed.py <x_kernel_trace.csv> <K> [kernel-name substring] [bench line of that run (json)] \
