@@ -114,7 +114,7 @@ struct rbl_solver {
     // (m32_ready); the sort's verdict - no run of equal keys too long to repair - arrives in pinned memory like the
     // sort-free z-step's and is settled by the same entries (zb_resolve): not certified = redone with 64-bit keys
     struct {
-        bool enabled = false, m_ready = false, used = false, q_done = false;
+        bool m_ready = false, used = false, q_done = false;
         u64* mm = nullptr;       // range of m (device)
         int* flag = nullptr;     // device: 1 = a run too long
         int* pin = nullptr;      // pinned: [0] sequence number (written last), [1] flag
@@ -718,10 +718,6 @@ int rbl_create(const rbl_config* cfg, rbl_solver** out) {
                 CK(dev_alloc(&h->s32.flag, 1));
                 CKH(hipHostMalloc((void**)&h->s32.pin, 64, hipHostMallocDefault));
                 for (int i = 0; i < 16; ++i) h->s32.pin[i] = 0;
-                {
-                    const char* e = getenv("RBL_SORT32");     // =0: 64-bit keys always (round 2), for comparison
-                    h->s32.enabled = !(e && e[0] == '0');
-                }
                 CK(alloc_prefix(&h->locx_a, &h->chunk_a, &h->cph_a, &h->cpl_a, nt));
                 if (cfg->weight_function == RBL_W_EHRM)
                     CK(alloc_prefix(&h->locx_b, &h->chunk_b, &h->cph_b, &h->cpl_b, nt));
@@ -826,12 +822,6 @@ int zb_resolve(rbl_solver* h, bool* redone = nullptr) {
     h->zb.backoff = h->zb.backoff < 2 ? 2 : (h->zb.backoff >= 32 ? 64 : 2 * h->zb.backoff);
     h->zb.skip_until = h->iter + 1 + h->zb.backoff;
     h->zb.mode = 2;
-    static const bool zb_debug = [] {
-        const char* e = getenv("RBL_ZBAND_DEBUG");
-        return e && e[0] == '1';
-    }();
-    if (zb_debug) fprintf(stderr, "[rbl] iteration %lld: banded z-step not certified (status %d), redone with the sort\n",
-                          (long long)h->iter, (int)pin[1]);
     const bool q_done = h->zb.q_done;
     h->zb.c_ready = h->zb.q_done = false;
     RBL_TRY(z_step_sorted(h, h->m, h->step_rho, false));
@@ -1215,7 +1205,7 @@ int rbl_phase_m(rbl_solver* h) {
         // which z-step will follow on a single handle: the sort-free one (banded weights), else the sort - with 32-bit
         // keys from the second iteration on (iteration 0 starts from equal m: one run) unless a step was not certified
         const bool banded_next = h->zb.enabled && h->nt == h->n && h->iter > 0 && h->iter >= h->zb.skip_until;
-        const bool s32 = h->s32.enabled && h->s32.pin && h->nt == h->n && h->n >= 2 && h->iter > 0 &&
+        const bool s32 = h->s32.pin && h->nt == h->n && h->n >= 2 && h->iter > 0 &&
                          h->iter >= h->s32.skip_until && !banded_next;
         h->s32.m_ready = false;
         if (s32) {

@@ -152,13 +152,6 @@ __device__ inline double block_value(double ssig, double sm, double cnt, double 
 // ---------------------------------------------------------------- one seam merge
 // Accessors: where u and the prefix sums of sigma / m live.  Global memory for the upper
 // levels, LDS (tile-local indices and plain tile-local prefixes) for the bottom levels.
-struct GlobalAcc {
-    const double* u;
-    Prefix pa, pm;
-    __device__ inline double val(long long i) const { return u[i]; }
-    __device__ inline double sum_a(long long s, long long e1) const { return range_sum(pa, s, e1); }
-    __device__ inline double sum_m(long long s, long long e1) const { return range_sum(pm, s, e1); }
-};
 struct LdsAcc {
     const double* u;   // tile values
     const double* pa;  // exclusive prefix of sigma inside the tile (C+1 entries)
@@ -548,15 +541,13 @@ __global__ __launch_bounds__(PV_THREADS) void k_pav_bottom(const double* __restr
                                                             const double* __restrict__ sb, const int* __restrict__ branch,
                                                             double rho, long long n, double* u_out,
                                                             u32* __restrict__ merge_counter, const double* u0a,
-                                                            const double* u0b, int bflags, int skip_if_branch,
+                                                            const double* u0b, int skip_if_branch,
                                                             double B, int spec, double* __restrict__ fpart) {
     // u0a / u0b != NULL (EHRM, distributed z-step): level 0 was computed by k_ehrm_fvals; u0a may alias u_out (a block
     // reads and writes only its own tile).  skip_if_branch >= 0: nothing to do when *branch says so (see above).
     // SPEC: sa / sb / B / spec as described above, fpart[2 * block + {0, 1}] receive this tile's share of f1 / f2.
     if (!SPEC && skip_if_branch >= 0 && branch && *branch == skip_if_branch) return;
     PAV_LAB_STAMP(0);
-    const int wave_top = bflags & 1;
-    const bool seq_levels = !(bflags & 2);
     __shared__ double su[PB_TILE];
     __shared__ double spa[PB_TILE + 1];
     __shared__ double spm[PB_TILE + 1];
@@ -665,39 +656,37 @@ __global__ __launch_bounds__(PV_THREADS) void k_pav_bottom(const double* __restr
     u32 merges = 0;
     // Levels 1-3: sequential PAV over the thread's own PB_PER positions (see the header comment).  `starts`: bit j set
     // = position j of the segment starts a block; all positions of a block hold its value.
-    if (seq_levels) {
-        const int b0 = tid * PB_PER;
-        const int cnt = (int)(nt - b0 < PB_PER ? nt - b0 : PB_PER);
-        u32 starts = cnt > 0 ? 1u : 0u;
-        if (cnt > 1) {
-            double cur = su[b0];
-            int cur_s = 0;
-            for (int i = 1; i < cnt; ++i) {
-                const double xi = su[b0 + i];
-                if (cur <= xi) {                     // pav.py:105: only a strict decrease violates
-                    starts |= 1u << i;
-                    cur = xi;
-                    cur_s = i;
-                    continue;
-                }
-                int s0 = cur_s;
-                double x = block_value<LOSS>(spa[b0 + i + 1] - spa[b0 + s0], spm[b0 + i + 1] - spm[b0 + s0], (double)(i + 1 - s0), rho);
-                ++merges;
-                while (s0 > 0) {
-                    const int ps0 = 31 - __clz((int)(starts & ((1u << s0) - 1u)));   // start of the block before
-                    if (su[b0 + ps0] <= x) break;
-                    starts &= ~(1u << s0);
-                    s0 = ps0;
-                    x = block_value<LOSS>(spa[b0 + i + 1] - spa[b0 + s0], spm[b0 + i + 1] - spm[b0 + s0], (double)(i + 1 - s0), rho);
-                    ++merges;
-                }
-                for (int j = s0; j <= i; ++j) su[b0 + j] = x;
-                cur = x;
-                cur_s = s0;
+    const int b0 = tid * PB_PER;
+    const int cnt = (int)(nt - b0 < PB_PER ? nt - b0 : PB_PER);
+    u32 starts = cnt > 0 ? 1u : 0u;
+    if (cnt > 1) {
+        double cur = su[b0];
+        int cur_s = 0;
+        for (int i = 1; i < cnt; ++i) {
+            const double xi = su[b0 + i];
+            if (cur <= xi) {                     // pav.py:105: only a strict decrease violates
+                starts |= 1u << i;
+                cur = xi;
+                cur_s = i;
+                continue;
             }
+            int s0 = cur_s;
+            double x = block_value<LOSS>(spa[b0 + i + 1] - spa[b0 + s0], spm[b0 + i + 1] - spm[b0 + s0], (double)(i + 1 - s0), rho);
+            ++merges;
+            while (s0 > 0) {
+                const int ps0 = 31 - __clz((int)(starts & ((1u << s0) - 1u)));   // start of the block before
+                if (su[b0 + ps0] <= x) break;
+                starts &= ~(1u << s0);
+                s0 = ps0;
+                x = block_value<LOSS>(spa[b0 + i + 1] - spa[b0 + s0], spm[b0 + i + 1] - spm[b0 + s0], (double)(i + 1 - s0), rho);
+                ++merges;
+            }
+            for (int j = s0; j <= i; ++j) su[b0 + j] = x;
+            cur = x;
+            cur_s = s0;
         }
-        __syncthreads();
     }
+    __syncthreads();
     PAV_LAB_STAMP(2);
     // Levels with short segments: the thread that merged a seam writes the pooled range itself.
     // From PB_COOP on (at most PB_TILE / (2 PB_COOP) seams per level) the pooled ranges get long
@@ -706,10 +695,10 @@ __global__ __launch_bounds__(PV_THREADS) void k_pav_bottom(const double* __restr
     constexpr int PB_COOP = 32;
     __shared__ int rec_s[PB_TILE / (2 * PB_COOP)], rec_e[PB_TILE / (2 * PB_COOP)];
     __shared__ double rec_x[PB_TILE / (2 * PB_COOP)];
-    for (int half = seq_levels ? PB_PER : 1; half < PB_TILE; half <<= 1) {
+    for (int half = PB_PER; half < PB_TILE; half <<= 1) {
         const int nseams = PB_TILE / (2 * half);
         const bool coop = half >= PB_COOP;
-        if (wave_top && nseams <= PV_THREADS / 64) {
+        if (nseams <= PV_THREADS / 64) {
             // top levels of the tile: one WAVE per seam, 64-ary searches in LDS
             const int k = wave;
             if (k < nseams) {
@@ -770,31 +759,6 @@ __global__ __launch_bounds__(PV_THREADS) void k_pav_bottom(const double* __restr
 }
 
 // ---------------------------------------------------------------- upper levels, global memory
-// One thread per seam of a level.  half = 2^(L-1) >= PB_TILE.
-template <int LOSS>
-__global__ __launch_bounds__(PV_THREADS) void k_pav_seam(double* __restrict__ u, long long n, long long half,
-                                                          Prefix pa_, Prefix pb_, Prefix pm, const int* branch,
-                                                          double rho, SeamRec* __restrict__ recs,
-                                                          long long nseams, u32* __restrict__ merge_counter) {
-    const long long k = (long long)blockIdx.x * PV_THREADS + threadIdx.x;
-    if (k >= nseams) return;
-    const long long seam = (2 * k + 1) * half;
-    if (seam >= n || u[seam - 1] <= u[seam]) {  // pav.py:105 - only a strict decrease is a violation
-        recs[k].s = -1;
-        return;
-    }
-    const GlobalAcc ac{u, (branch && *branch) ? pb_ : pa_, pm};
-    long long R1 = seam + half;
-    if (R1 > n) R1 = n;
-    long long s_star, e_star;
-    double x;
-    seam_merge<LOSS>(ac, seam - half, seam, R1, rho, s_star, e_star, x);
-    atomicAdd(merge_counter, 1u);
-    recs[k].s = s_star;
-    recs[k].e = e_star;
-    recs[k].x = x;
-}
-
 // One WAVE per seam (the levels where seams are few and long): see WaveAcc.
 template <int LOSS>
 __global__ __launch_bounds__(PV_THREADS) void k_pav_seam_wave(double* __restrict__ u, long long n, long long half,
@@ -815,24 +779,19 @@ __global__ __launch_bounds__(PV_THREADS) void k_pav_seam_wave(double* __restrict
     if (R1 > n) R1 = n;
     long long s_star, e_star;
     double x;
-    long long hs = -1, he = -1;
+    // what this seam pooled in the previous iteration (wave-uniform loads)
+    const long long hs = hints[k].s, he = hints[k].e;
     double hx = __builtin_nan("");
-    if (hints) {   // what this seam pooled in the previous iteration (wave-uniform loads)
-        hs = hints[k].s;
-        he = hints[k].e;
-        if (hs >= 0) hx = hints[k].x;
-    }
+    if (hs >= 0) hx = hints[k].x;
     seam_merge<LOSS>(ac, seam - half, seam, R1, rho, s_star, e_star, x, hs, he, hx);
     if (lane == 0) {
         atomicAdd(merge_counter, 1u);
         recs[k].s = s_star;
         recs[k].e = e_star;
         recs[k].x = x;
-        if (hints) {
-            hints[k].s = s_star;
-            hints[k].e = e_star;
-            hints[k].x = x;
-        }
+        hints[k].s = s_star;
+        hints[k].e = e_star;
+        hints[k].x = x;
     }
 }
 
@@ -870,7 +829,7 @@ constexpr long long PU_DIRECT_FILL = 8192;    // positions a merging wave writes
 constexpr int PU_BIG_CAP = 4096;              // capacity of the cooperative-fill list
 
 struct PavUpperArgs {
-    SeamRec* hints;        // per level, concatenated (NULL: cold searches)
+    SeamRec* hints;        // per level, concatenated
     SeamRec* big;          // cooperative-fill list
     u32* counters;         // [0] merges, [1] dirty levels, [2] entries of `big`, [3] status (1: a wait gave up / list overflow)
     unsigned* bar;
@@ -905,7 +864,7 @@ __global__ __launch_bounds__(PV_THREADS) void k_pav_upper(double* __restrict__ u
     long long hint_off = 0;
     for (int l = 0; ok && l < A.nlevels; ++l) {
         const long long half = (long long)PB_TILE << l, nseams = (n + 2 * half - 1) / (2 * half);
-        SeamRec* hints = A.hints ? A.hints + hint_off : nullptr;
+        SeamRec* hints = A.hints + hint_off;
         hint_off += nseams;
         if (!((mask >> l) & 1u)) continue;
         for (long long k = wave_id; k < nseams; k += nwaves) {
@@ -914,21 +873,16 @@ __global__ __launch_bounds__(PV_THREADS) void k_pav_upper(double* __restrict__ u
             long long R1 = seam + half;
             if (R1 > n) R1 = n;
             const long long L0 = seam - half;
-            long long s_star, e_star, hs = -1, he = -1;
+            long long s_star, e_star;
+            const long long hs = hints[k].s, he = hints[k].e;
             double x, hx = __builtin_nan("");
-            if (hints) {
-                hs = hints[k].s;
-                he = hints[k].e;
-                if (hs >= 0) hx = hints[k].x;
-            }
+            if (hs >= 0) hx = hints[k].x;
             seam_merge<LOSS>(ac, L0, seam, R1, rho, s_star, e_star, x, hs, he, hx);
             if (lane == 0) {
                 ++merges;
-                if (hints) {
-                    hints[k].s = s_star;
-                    hints[k].e = e_star;
-                    hints[k].x = x;
-                }
+                hints[k].s = s_star;
+                hints[k].e = e_star;
+                hints[k].x = x;
                 // a pooled range that reaches an end of its segment changes the value next to a higher level's seam
                 u32 up = 0;
                 if (s_star == L0 && L0 > 0) up |= 1u << __builtin_ctzll((unsigned long long)(L0 >> PB_TILE_LOG));
@@ -1408,19 +1362,10 @@ int launch_pav_tree(int loss, int64_t n, double rho, const double* ms, const dou
                     hipStream_t s, const double* u0a, const double* u0b, PavExtras* ex) {
     RBL_HIP(hipMemsetAsync(merge_counter, 0, 4 * sizeof(u32), s));   // merges | dirty levels | long fills | status
     if (n <= 0) return RBL_OK;
-    static const bool thread_seams = [] {
-        const char* e = getenv("RBL_PAV_THREAD_SEAMS");   // one thread per seam everywhere, for comparison
-        return e && e[0] == '1';
-    }();
-    static const bool no_seq = [] {
-        const char* e = getenv("RBL_PAV_NO_SEQ");          // tree merges from segments of one position on (round 2), for comparison
-        return e && e[0] == '1';
-    }();
     static const bool no_upper = [] {
-        const char* e = getenv("RBL_PAV_UPPER_PERSIST");   // =0: two launches per upper level (round 2), for comparison
+        const char* e = getenv("RBL_PAV_UPPER_PERSIST");   // =0: two launches per upper level (round 2)
         return e && e[0] == '0';
     }();
-    const int bflags = (thread_seams ? 0 : 1) | (no_seq ? 2 : 0);
     // levels 0 .. log2(PB_TILE): prox + in-LDS merges, one tile per workgroup
     const unsigned tiles = (unsigned)((n + PB_TILE - 1) / PB_TILE);
     if (ex && ex->fpart && loss == RBL_LOSS_BCE && branch) {
@@ -1428,26 +1373,22 @@ int launch_pav_tree(int loss, int64_t n, double rho, const double* ms, const dou
         // exact test, and the other branch's tree only if the test says so (a no-op launch otherwise)
         int* br = const_cast<int*>(branch);
         hipLaunchKernelGGL((k_pav_bottom<0, true>), dim3(tiles), dim3(PV_THREADS), 0, s, ms, sa, sb, (const int*)nullptr, rho,
-                           (long long)n, u, merge_counter, (const double*)nullptr, (const double*)nullptr, bflags, -1, ex->B,
+                           (long long)n, u, merge_counter, (const double*)nullptr, (const double*)nullptr, -1, ex->B,
                            ex->spec, ex->fpart);
         hipLaunchKernelGGL(k_ehrm_pick, dim3(1), dim3(256), 0, s, (const double*)ex->fpart, (int)tiles, -1, br);
         hipLaunchKernelGGL((k_pav_bottom<0, false>), dim3(tiles), dim3(PV_THREADS), 0, s, ms, sa, sb, branch, rho, (long long)n, u,
-                           merge_counter, (const double*)nullptr, (const double*)nullptr, bflags, ex->spec, 0.0, 0,
+                           merge_counter, (const double*)nullptr, (const double*)nullptr, ex->spec, 0.0, 0,
                            (double*)nullptr);
     } else if (loss == RBL_LOSS_BCE) {
         hipLaunchKernelGGL((k_pav_bottom<0, false>), dim3(tiles), dim3(PV_THREADS), 0, s, ms, sa, sb, branch, rho, (long long)n, u,
-                           merge_counter, u0a, u0b, bflags, -1, 0.0, 0, (double*)nullptr);
+                           merge_counter, u0a, u0b, -1, 0.0, 0, (double*)nullptr);
     } else {
         hipLaunchKernelGGL((k_pav_bottom<1, false>), dim3(tiles), dim3(PV_THREADS), 0, s, ms, sa, sb, branch, rho, (long long)n, u,
-                           merge_counter, u0a, u0b, bflags, -1, 0.0, 0, (double*)nullptr);
+                           merge_counter, u0a, u0b, -1, 0.0, 0, (double*)nullptr);
     }
     // upper levels: one WAVE per seam (64-ary inner searches)
-    static const bool no_hints = [] {
-        const char* e = getenv("RBL_PAV_NO_HINTS");       // cold searches every iteration, for comparison
-        return e && e[0] == '1';
-    }();
-    SeamRec* hint_base = no_hints ? nullptr : recs + pav_level_recs(n);
-    if (ex && ex->bar && ex->big && !thread_seams && !no_upper && (long long)PB_TILE < n) {
+    SeamRec* hint_base = recs + pav_level_recs(n);
+    if (ex && ex->bar && ex->big && !no_upper && (long long)PB_TILE < n) {
         // ... all of them in one persistent launch (k_pav_upper): at most one block per CU
         PavUpperArgs A;
         A.hints = hint_base;
@@ -1473,24 +1414,14 @@ int launch_pav_tree(int loss, int64_t n, double rho, const double* ms, const dou
     for (long long half = PB_TILE; half < n; half <<= 1, ++level) {
         const long long nseams = (n + 2 * half - 1) / (2 * half);
         SeamRec* hints = hint_base;
-        if (hint_base) hint_base += nseams;
-        if (thread_seams) {
-            const unsigned grid = pv_grid(nseams, PV_THREADS, 1LL << 30);
-            if (loss == RBL_LOSS_BCE)
-                hipLaunchKernelGGL(k_pav_seam<0>, dim3(grid), dim3(PV_THREADS), 0, s, u, (long long)n, half, pa, pb, pm,
-                                   branch, rho, recs, nseams, merge_counter);
-            else
-                hipLaunchKernelGGL(k_pav_seam<1>, dim3(grid), dim3(PV_THREADS), 0, s, u, (long long)n, half, pa, pb, pm,
-                                   branch, rho, recs, nseams, merge_counter);
-        } else {
-            const unsigned grid = pv_grid(nseams * 64, PV_THREADS, 1LL << 30);
-            if (loss == RBL_LOSS_BCE)
-                hipLaunchKernelGGL(k_pav_seam_wave<0>, dim3(grid), dim3(PV_THREADS), 0, s, u, (long long)n, half, pa, pb,
-                                   pm, branch, rho, recs, nseams, merge_counter, hints);
-            else
-                hipLaunchKernelGGL(k_pav_seam_wave<1>, dim3(grid), dim3(PV_THREADS), 0, s, u, (long long)n, half, pa, pb,
-                                   pm, branch, rho, recs, nseams, merge_counter, hints);
-        }
+        hint_base += nseams;
+        const unsigned grid = pv_grid(nseams * 64, PV_THREADS, 1LL << 30);
+        if (loss == RBL_LOSS_BCE)
+            hipLaunchKernelGGL(k_pav_seam_wave<0>, dim3(grid), dim3(PV_THREADS), 0, s, u, (long long)n, half, pa, pb,
+                               pm, branch, rho, recs, nseams, merge_counter, hints);
+        else
+            hipLaunchKernelGGL(k_pav_seam_wave<1>, dim3(grid), dim3(PV_THREADS), 0, s, u, (long long)n, half, pa, pb,
+                               pm, branch, rho, recs, nseams, merge_counter, hints);
         hipLaunchKernelGGL(k_pav_fill, dim3((unsigned)((n + PF_CHUNK - 1) / PF_CHUNK)), dim3(256), 0, s, u, (long long)n, level,
                            recs);
     }

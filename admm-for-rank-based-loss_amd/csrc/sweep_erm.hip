@@ -44,27 +44,13 @@ constexpr int SE_THREADS = 256;
 
 // Row-wise stores of the single-sweep kernels (lambda, v, z': 8 bytes per row and array, whole 128-byte lines per
 // super-batch) are WRITE-THROUGH (sc1).  They are 0.4 % of the pass's bytes but cost 8 % of its time as plain stores
-// (tools/sweep_lab.hip, 6M x 1000 fp32: v-only pass 3.81 ms, 3.39 without them, 3.40 when they go to a ring that stays
-// in L2 - so it is not their issue but their way to HBM: dirty lines evicted from the write-back L2 by the streaming
-// reads); written through they leave in order: 3.59 ms (nt 3.70; sc0 / sc1 nt / buffer-store forms the same as sc1).
-// The EXP bits 256 / 512 / 2048 / 4096 exist for tools/sweep_lab.hip only (256: into a 1024-row ring, 512: non-temporal,
-// 2048 + aux in bits 13-17: raw buffer store with that cache-policy field, 4096: plain stores as in round 2).
-template <int EXP>
+// (round 3's lab build, 6M x 1000 fp32: v-only pass 3.81 ms, 3.39 without them, 3.40 when they went to a ring that
+// stays in L2 - so it is not their issue but their way to HBM: dirty lines evicted from the write-back L2 by the
+// streaming reads); written through they leave in order: 3.59 ms (nt 3.70; sc0 / sc1 nt / buffer-store forms the same
+// as sc1).
 __device__ inline void row_store(double* __restrict__ base, long long row, double x) {
-    if (EXP & 256) row &= 1023;
-    if (EXP & 2048) {
-        typedef unsigned v2u __attribute__((ext_vector_type(2)));
-        const unsigned long long b = __builtin_bit_cast(unsigned long long, x);
-        v2u val;
-        val.x = (unsigned)b;
-        val.y = (unsigned)(b >> 32);
-        const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(base, 0, 0x7fffffff, 0x00020000);
-        __builtin_amdgcn_raw_buffer_store_b64(val, rs, (int)(row * 8), 0, (EXP >> 13) & 31);
-    } else if (EXP & 512) __builtin_nontemporal_store(x, base + row);
-    else if (EXP & 4096) base[row] = x;
-    else
-        __hip_atomic_store(reinterpret_cast<unsigned long long*>(base + row), __builtin_bit_cast(unsigned long long, x), __ATOMIC_RELAXED,
-                           __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(reinterpret_cast<unsigned long long*>(base + row), __builtin_bit_cast(unsigned long long, x), __ATOMIC_RELAXED,
+                       __HIP_MEMORY_SCOPE_AGENT);
 }
 
 // fp32 storage: hide the packets from the optimiser between the dot phase and the accumulation
@@ -80,23 +66,23 @@ __device__ inline void opaque(u32x4 (&buf)[R][P]) {
 }
 
 // pred[0] = rho_{k+1} (predicted), read on the device so no host round trip is needed
-// EXP selects what is left out.  The library instantiates EXP == 0 (everything) and
-// EXP == SE_VONLY (rank-weighted problems: v = D w, the lambda update and the primal residual
-// only - the z-step needs the global sort and q a second pass); the other values exist for
-// tools/sweep_lab.hip (ablation timings: which phase costs what).
-constexpr int SE_VONLY = 2 | 4 | 128;   // no accumulation phase, no prox, no z' / slab output
-// q = D^T c alone (round 3; replaces k_gemvt where the row width fits): the row's coefficient is READ (c = z + lambda/rho,
+// MODE selects the pass:
+//   SE_FUSED  erm weights: everything above.
+//   SE_VONLY  rank-weighted problems: v = D w, the lambda update and the primal residual only (the z-step needs the
+//             global sort and q a second pass) - no accumulation phase, no prox, no z' / slab output.
+//   SE_QONLY  q = D^T c alone (round 3; replaces k_gemvt where the row width fits): the row's coefficient is READ (c = z + lambda/rho,
 // passed in the z_old slot) instead of computed - no dot product, no wave reduction, no prox, no row-wise stores, no
 // residual sums; the same loads in the same order, the same accumulation into per-lane column sums, one slab row per
 // block.  The thread-per-column-packet k_gemvt reads the same bytes at 6.0 TB/s, this kernel at the single-sweep
 // kernel's 6.2-6.5 (buffer loads through scalar row descriptors, a whole sub-batch of rows in flight per wave).
-constexpr int SE_QONLY = 1 | 4 | 8 | 16 | 64;
-template <typename T, int LOSS, int P, int R, int S, bool WL, int EXP = 0, bool ONE = false, int OCC = 2>
+enum : int { SE_FUSED = 0, SE_VONLY = 1, SE_QONLY = 2 };
+template <typename T, int LOSS, int P, int R, int S, bool WL, int MODE, int OCC>
 __global__ __launch_bounds__(SE_THREADS, OCC) void k_sweep_erm(
     const T* __restrict__ D, long long n, long long ld, const double* __restrict__ w, const double* __restrict__ z_old,
     double* __restrict__ lam, double* __restrict__ v, double* __restrict__ z_new, double sigma0, double rho,
     const double* __restrict__ pred, double* __restrict__ slab, double* __restrict__ partials) {
     constexpr int E = Pk<T>::E;
+    constexpr bool VONLY = MODE == SE_VONLY, QONLY = MODE == SE_QONLY;
     // The wave index goes through readfirstlane: super-batch numbers, row numbers and the row
     // descriptors are then scalar registers, and a load is buffer_load(SGPR descriptor, 32-bit
     // per-lane offset) - no 64-bit per-lane addresses, which is what keeps two R x P packet
@@ -104,7 +90,7 @@ __global__ __launch_bounds__(SE_THREADS, OCC) void k_sweep_erm(
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int PK = (int)(ld / E);
     const unsigned row_bytes = (unsigned)ld * (unsigned)sizeof(T);
-    const double rho_next = (EXP & (128 | 64)) ? 1.0 : pred[0];
+    const double rho_next = (VONLY || QONLY) ? 1.0 : pred[0];
 
     // w: in registers, or (WL) in LDS, one copy per block, laid out [p][lane][k] so that a
     // lane's E values are contiguous - frees 2*P*E VGPRs for a second pair of row buffers
@@ -136,7 +122,7 @@ __global__ __launch_bounds__(SE_THREADS, OCC) void k_sweep_erm(
     // register buffers alternating); lane l < S*R owns row q*S*R + l of super-batch q, so the
     // row-wise reads (z_old, lambda) and writes (lambda, v, z') of a super-batch are S*R*8
     // contiguous bytes per array - 128 B for S*R = 16 - instead of R*8-byte fragments (partial
-    // cache-line writes cost ~8% of the pass, tools/sweep_lab.hip).
+    // cache-line writes cost ~8% of the pass, measured in round 3).
     // Super-batch numbers are 32-bit (n < 2^31 * S*R rows) so that all the loop control is SALU:
     // there is no scalar 64-bit compare.
     constexpr int SR = S * R;
@@ -150,10 +136,10 @@ __global__ __launch_bounds__(SE_THREADS, OCC) void k_sweep_erm(
     // load issued later than the prefetch would drain it).
     auto load_side = [&](int q, double& zo, double& lm) {
         const int live = q == nsuper - 1 ? live_last : SR;
-        const bool mine = lane < live && !(EXP & 32);
+        const bool mine = lane < live;
         const long long myrow = (long long)q * SR + lane;
         zo = mine ? z_old[myrow] : 0.0;
-        lm = (mine && !(EXP & 64)) ? lam[myrow] : 0.0;
+        lm = (mine && !QONLY) ? lam[myrow] : 0.0;
     };
     auto load_rows = [&](int q, int sub, u32x4 (&buf)[R][P]) {
         const int live = q == nsuper - 1 ? live_last : SR;
@@ -173,14 +159,14 @@ __global__ __launch_bounds__(SE_THREADS, OCC) void k_sweep_erm(
     auto process = [&](int live, int sub, u32x4 (&buf)[R][P], double zo, double lm) {
         double dot[R];
 #pragma unroll
-        for (int r = 0; r < R; ++r) dot[r] = (EXP & 16) ? Pk<T>::at(buf[r][0], 0) : 0.0;
+        for (int r = 0; r < R; ++r) dot[r] = QONLY ? Pk<T>::at(buf[r][0], 0) : 0.0;
         // the LDS offset is made opaque so that the (loop-invariant) reads of w are not hoisted
         // back into 2*P*E registers
         int woff = lane * E;
         if (WL) asm volatile("" : "+v"(woff));
 #pragma unroll
         for (int p = 0; p < P; ++p) {
-            if (EXP & 16) break;
+            if (QONLY) break;   // no dot product
             double wv[E];
 #pragma unroll
             for (int k = 0; k < E; ++k) wv[k] = WL ? sw[p * 64 * E + woff + k] : wr[WL ? 0 : p][k];
@@ -191,12 +177,12 @@ __global__ __launch_bounds__(SE_THREADS, OCC) void k_sweep_erm(
         }
 #pragma unroll
         for (int r = 0; r < R; ++r)
-            if (!(EXP & 8)) dot[r] = rbl::wave_sum_all(dot[r]);   // DPP butterfly + readlanes: no LDS trips
+            if (!QONLY) dot[r] = rbl::wave_sum_all(dot[r]);   // DPP butterfly + readlanes: no LDS trips
         double myv = 0.0;
 #pragma unroll
         for (int r = 0; r < R; ++r) myv = (lane == sub * R + r) ? dot[r] : myv;
         double c = 0.0;
-        if (EXP & 64) {
+        if (QONLY) {
             if (lane >= sub * R && lane < sub * R + R && lane < live) c = zo;    // the coefficient was read, not computed
         } else if (lane >= sub * R && lane < sub * R + R && lane < live) {
             const double res = zo - myv;
@@ -204,7 +190,7 @@ __global__ __launch_bounds__(SE_THREADS, OCC) void k_sweep_erm(
             s_prim += res * res;                                   // algorithms.py:135
             const double lr = l / rho_next;
             const double m = myv - lr;                             // algorithms.py:89 (next iteration)
-            const double zn = (EXP & 4) ? m : ((LOSS == 0) ? rbl::prox_bce_warm(sigma0, rho_next, m, zo) : rbl::prox_hinge(sigma0, rho_next, m));
+            const double zn = VONLY ? m : ((LOSS == 0) ? rbl::prox_bce_warm(sigma0, rho_next, m, zo) : rbl::prox_hinge(sigma0, rho_next, m));
             s_zz += zn * zn;
             l_out = l;
             v_out = myv;
@@ -212,7 +198,7 @@ __global__ __launch_bounds__(SE_THREADS, OCC) void k_sweep_erm(
             c = zn + lr;
         }
         opaque<T>(buf);
-        if (EXP & 2) {
+        if (VONLY) {   // no accumulation phase
             s_zz += c;
             return;
         }
@@ -229,83 +215,48 @@ __global__ __launch_bounds__(SE_THREADS, OCC) void k_sweep_erm(
     u32x4 bufA[R][P], bufB[R][P];
     double zo = 0.0, lm = 0.0, zoN = 0.0, lmN = 0.0;
     int q = gw, sub = 0;
-    if (ONE) {
-        // One copy of the row-wise code, as in k_sweep_erm_wide: every load lands in bufB; at the
-        // top of an iteration bufB (issued one whole process() earlier) is moved to bufA, the next
-        // sub-batch is requested into bufB and the arithmetic runs on bufA, whose registers are
-        // never the target of a load - nothing in process() waits for the prefetch in flight.
-        if (q < nsuper) {
-            load_side(q, zoN, lmN);
-            load_rows(q, 0, bufB);
-        }
-#pragma clang loop unroll(disable)
-        while (q < nsuper) {
-            const int live = q == nsuper - 1 ? live_last : SR;
-#pragma unroll
-            for (int r = 0; r < R; ++r)
-#pragma unroll
-                for (int p = 0; p < P; ++p) bufA[r][p] = bufB[r][p];
-            if (sub == 0) {
-                zo = zoN;
-                lm = lmN;
-            }
-            const bool last = sub + 1 == S;
-            const int qn = last ? q + GW : q;
-            const int subn = last ? 0 : sub + 1;
-            __builtin_amdgcn_sched_barrier(0);
-            if (qn < nsuper) {
-                if (last) load_side(qn, zoN, lmN);
-                load_rows(qn, subn, bufB);
-            }
-            __builtin_amdgcn_sched_barrier(0);   // the prefetch stays above the arithmetic
-            process(live, sub, bufA, zo, lm);
-            if (last && lane < live && !(EXP & 1)) {
-                const long long row = (long long)q * SR + lane;
-                row_store<EXP>(lam, row, l_out);
-                if (v) row_store<EXP>(v, row, v_out);   // NULL: nobody reads v before the next pass (no objective logging)
-                if (!(EXP & 128)) row_store<EXP>(z_new, row, z_out);
-            }
-            q = qn;
-            sub = subn;
-        }
-    } else {
+    // One copy of the row-wise code, as in k_sweep_erm_wide: every load lands in bufB; at the top of
+    // an iteration bufB (issued one whole process() earlier) is moved to bufA, the next sub-batch is
+    // requested into bufB and the arithmetic runs on bufA, whose registers are never the target of a
+    // load - nothing in process() waits for the prefetch in flight.
     if (q < nsuper) {
-        load_side(q, zo, lm);
-        load_rows(q, 0, bufA);
+        load_side(q, zoN, lmN);
+        load_rows(q, 0, bufB);
     }
-    // one flat loop over pairs of sub-batches ((q, sub) in bufA, (q, sub+1) in bufB); q and sub
-    // are scalar registers.  (A nested "for sub" loop lets the compiler hoist the next
-    // super-batch's load addresses out of it and spill them.)
+#pragma clang loop unroll(disable)
     while (q < nsuper) {
         const int live = q == nsuper - 1 ? live_last : SR;
-        load_rows(q, sub + 1, bufB);
-        process(live, sub, bufA, zo, lm);
-        const bool last = sub + 2 == S;
-        const int qn = last ? q + GW : q;
-        const int subn = last ? 0 : sub + 2;
-        if (qn < nsuper) {
-            if (last) load_side(qn, zoN, lmN);
-            load_rows(qn, subn, bufA);
-        }
-        process(live, sub + 1, bufB, zo, lm);
-        if (last) {
-            if (lane < live && !(EXP & 1)) {
-                const long long row = (long long)q * SR + lane;
-                lam[row] = l_out;
-                if (v) v[row] = v_out;   // NULL: nobody reads v before the next pass (no objective logging)
-                if (!(EXP & 128)) z_new[row] = z_out;
-            }
+#pragma unroll
+        for (int r = 0; r < R; ++r)
+#pragma unroll
+            for (int p = 0; p < P; ++p) bufA[r][p] = bufB[r][p];
+        if (sub == 0) {
             zo = zoN;
             lm = lmN;
+        }
+        const bool last = sub + 1 == S;
+        const int qn = last ? q + GW : q;
+        const int subn = last ? 0 : sub + 1;
+        __builtin_amdgcn_sched_barrier(0);
+        if (qn < nsuper) {
+            if (last) load_side(qn, zoN, lmN);
+            load_rows(qn, subn, bufB);
+        }
+        __builtin_amdgcn_sched_barrier(0);   // the prefetch stays above the arithmetic
+        process(live, sub, bufA, zo, lm);
+        if (last && lane < live && !QONLY) {
+            const long long row = (long long)q * SR + lane;
+            row_store(lam, row, l_out);
+            if (v) row_store(v, row, v_out);   // NULL: nobody reads v before the next pass (no objective logging)
+            if (!VONLY) row_store(z_new, row, z_out);
         }
         q = qn;
         sub = subn;
     }
-    }
 
     // fold the 4 waves' column sums in LDS, one slab row per block
-    __shared__ double red[(EXP & 128) ? 1 : SE_THREADS / 64][(EXP & 128) ? 1 : 64 * P * E];
-    if (!(EXP & 128)) {
+    __shared__ double red[VONLY ? 1 : SE_THREADS / 64][VONLY ? 1 : 64 * P * E];
+    if (!VONLY) {
 #pragma unroll
         for (int p = 0; p < P; ++p)
 #pragma unroll
@@ -322,7 +273,7 @@ __global__ __launch_bounds__(SE_THREADS, OCC) void k_sweep_erm(
         }
         __syncthreads();
     }
-    if (EXP & 64) return;                  // q-only: no residual sums
+    if (QONLY) return;                     // no residual sums
     double sums[3] = {s_prim, 0.0, s_zz};   // slot 1: the loss sum, filled by k_loss_sum when wanted
     __shared__ double smem[3 * SE_THREADS / 64];
     rbl::block_sum<3, SE_THREADS>(sums, smem);
@@ -345,12 +296,13 @@ __global__ __launch_bounds__(SE_THREADS, OCC) void k_sweep_erm(
 // the column sums: R is the largest number of rows whose two buffers fit (launch_T).
 constexpr int SEW_THREADS = 512;
 
-template <typename T, int LOSS, int PT, int R, int S, int NT = SEW_THREADS>
-__global__ __launch_bounds__(NT, 1) void k_sweep_erm_wide(
+template <typename T, int LOSS, int PT, int R, int S>
+__global__ __launch_bounds__(SEW_THREADS, 1) void k_sweep_erm_wide(
     const T* __restrict__ D, long long n, long long ld, const double* __restrict__ w, const double* __restrict__ z_old,
     double* __restrict__ lam, double* __restrict__ v, double* __restrict__ z_new, double sigma0, double rho,
     const double* __restrict__ pred, double* __restrict__ slab, double* __restrict__ partials) {
     constexpr int E = Pk<T>::E;
+    constexpr int NT = SEW_THREADS;
     constexpr int NW = NT / 64;
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int PK = (int)(ld / E);
@@ -506,9 +458,9 @@ __global__ __launch_bounds__(NT, 1) void k_sweep_erm_wide(
         if (last) {
             if (tid < live) {
                 const long long row = (long long)q * SR + tid;
-                row_store<0>(lam, row, rw_l[tid]);
-                if (v) row_store<0>(v, row, rw_v[tid]);   // NULL: nobody reads v before the next pass (no objective logging)
-                row_store<0>(z_new, row, rw_z[tid]);
+                row_store(lam, row, rw_l[tid]);
+                if (v) row_store(v, row, rw_v[tid]);   // NULL: nobody reads v before the next pass (no objective logging)
+                row_store(z_new, row, rw_z[tid]);
             }
         }
         q = qn;
@@ -629,12 +581,12 @@ __global__ __launch_bounds__(256) void k_sumsq(long long n, const double* __rest
     if (threadIdx.x == 0) partials[blockIdx.x] = a[0];
 }
 
-template <typename T, int LOSS, int P, int R, int S, bool WL, int OCC = 2>
+template <typename T, int LOSS, int P, int R, int S, bool WL, int OCC>
 int launch_one(const T* D, long long n, long long ld, const double* w, const double* z_old, double* lam, double* v,
                double* z_new, double sigma0, double rho, const double* pred, double* slab, double* partials, int grid,
                hipStream_t s) {
-    hipLaunchKernelGGL((k_sweep_erm<T, LOSS, P, R, S, WL, 0, true, OCC>), dim3(grid), dim3(SE_THREADS), 0, s, D, n, ld, w, z_old, lam, v,
-                       z_new, sigma0, rho, pred, slab, partials);
+    hipLaunchKernelGGL((k_sweep_erm<T, LOSS, P, R, S, WL, SE_FUSED, OCC>), dim3(grid), dim3(SE_THREADS), 0, s, D, n, ld, w, z_old,
+                       lam, v, z_new, sigma0, rho, pred, slab, partials);
     RBL_HIP(hipGetLastError());
     return RBL_OK;
 }
@@ -648,74 +600,46 @@ int launch_T(const T* D, long long n, long long ld, const double* w, const doubl
     *used = grid;
     // 3-4 (fp64 storage: 5-8) packets per lane: ONE block of 4 waves per CU, four (two) rows per sub-batch and two
     // sub-batch buffers - 32 KB of loads in flight per wave - with w in LDS.  Round 2's shape (two rows per sub-batch,
-    // two blocks per CU, w in registers) is 5 % slower at 6M x 1000 and ramps over its first ~25 launches after an idle
+    // two blocks per CU, w in registers) was 5 % slower at 6M x 1000 and ramped over its first ~25 launches after an idle
     // gap (3.93 -> 3.66 ms; this shape 3.57 -> 3.48): interleaved on one box, C2 266-271 it/s against 281-283
     // (profiles/r03_sweep_shapes.txt).  Fewer waves, each with more rows in flight, stream better than more waves:
-    // with 8 waves per CU the same rows-in-flight give 276-278.  RBL_SWEEP_SHAPE=0 is round 2's shape, 1 the
-    // two-blocks-per-CU form of the default, 8 eight rows per sub-batch (same speed as the default).
-    static const int shape = [] {
-        const char* e = getenv("RBL_SWEEP_SHAPE");
-        return e ? atoi(e) : -1;
-    }();
-    static const int bpc1 = [] {
-        const char* e = getenv("RBL_SWEEP_BLOCKS_PER_CU");
-        const int v = e ? atoi(e) : 1;
-        return (v >= 1 && v <= 2) ? v : 1;
-    }();
+    // with 8 waves per CU (two blocks per CU) the same rows-in-flight gave 276-278; eight rows per sub-batch ran at
+    // the same speed as four.
 #define RBL_ONE(P_, R_, S_, WL_)                                                                                              \
     do {                                                                                                                      \
-        *used = num_cu * bpc1;                                                                                                \
+        *used = num_cu;                                                                                                       \
         return launch_one<T, LOSS, P_, R_, S_, WL_, 1>(D, n, ld, w, z_old, lam, v, z_new, sigma0, rho, pred, slab, partials, \
-                                                       num_cu * bpc1, s);                                                     \
+                                                       num_cu, s);                                                            \
     } while (0)
     // 1 and 2 packets per lane (fp32 storage: d <= 256 / 512).  One packet: the per-row work (wave reduction, prox on one
     // lane) weighs most, more waves hide it - 16 rows per sub-batch, still two blocks per CU: 24M x 250 201.5 -> 224 it/s
     // (one block per CU: 184-189).  Two packets: 8 rows per sub-batch, super-batches of 64 rows (512-byte row-wise
     // segments), one block per CU: 12M x 500 255.5 -> 269 (profiles/r03_sweep_shapes.txt block 8).
-    if (passes == 1) {
-        if (shape == 0) return launch_one<T, LOSS, 1, 8, 2, false>(D, n, ld, w, z_old, lam, v, z_new, sigma0, rho, pred, slab, partials, grid, s);
-        return launch_one<T, LOSS, 1, 16, 2, false>(D, n, ld, w, z_old, lam, v, z_new, sigma0, rho, pred, slab, partials, grid, s);
-    }
-    if (passes == 2) {
-        if (shape == 0) return launch_one<T, LOSS, 2, 4, 4, false>(D, n, ld, w, z_old, lam, v, z_new, sigma0, rho, pred, slab, partials, grid, s);
-        RBL_ONE(2, 8, 8, false);
-    }
-    if (passes <= 4) {
-        if (shape == 0) return launch_one<T, LOSS, 4, 2, 8, false>(D, n, ld, w, z_old, lam, v, z_new, sigma0, rho, pred, slab, partials, grid, s);
-        if (shape == 1) return launch_one<T, LOSS, 4, 4, 4, true>(D, n, ld, w, z_old, lam, v, z_new, sigma0, rho, pred, slab, partials, grid, s);
-        if (shape == 8) RBL_ONE(4, 8, 2, true);
-        RBL_ONE(4, 4, 4, true);
-    }
-    if (passes <= 8) {
-        // 5-8 packets per lane and row (fp64 storage d <= 1024, fp32 storage d <= 2048).  fp64, d = 1000: four rows of 8
-        // packets per sub-batch (64 KB in flight per wave) 143.7 it/s against round 2's one row per sub-batch with two
-        // blocks per CU 136.4-138.6 (RBL_SWEEP_SHAPE=0), two rows 140.5-143.5.  fp32 storage took the workgroup-per-row
-        // kernel from d = 1025 on until round 3 (4M x 2000: 171.8 it/s, 5.5 TB/s); RBL_SWEEP_SHAPE=0 keeps that.
-        if constexpr (sizeof(T) == 8) {
-            if (shape == 0) return launch_one<T, LOSS, 8, 1, 8, false>(D, n, ld, w, z_old, lam, v, z_new, sigma0, rho, pred, slab, partials, grid, s);
-        }
-        if (sizeof(T) == 8 || shape != 0) {
-            if (shape == 9) RBL_ONE(8, 2, 8, true);
-            RBL_ONE(8, 4, 4, true);
-        }
-    }
+    if (passes == 1)
+        return launch_one<T, LOSS, 1, 16, 2, false, 2>(D, n, ld, w, z_old, lam, v, z_new, sigma0, rho, pred, slab, partials, grid, s);
+    if (passes == 2) RBL_ONE(2, 8, 8, false);
+    if (passes <= 4) RBL_ONE(4, 4, 4, true);
+    // 5-8 packets per lane and row (fp64 storage d <= 1024, fp32 storage d <= 2048).  fp64, d = 1000: four rows of 8
+    // packets per sub-batch (64 KB in flight per wave) 143.7 it/s against round 2's one row per sub-batch with two
+    // blocks per CU 136.4-138.6, two rows 140.5-143.5.  fp32 storage took the workgroup-per-row kernel from d = 1025 on
+    // until round 3 (4M x 2000: 171.8 it/s, 5.5 TB/s).
+    if (passes <= 8) RBL_ONE(8, 4, 4, true);
 #undef RBL_ONE
     // wider rows: one workgroup of 512 threads per row batch (grid = one workgroup per CU)
     const long long pt = (PK + SEW_THREADS - 1) / SEW_THREADS;
     const int wgrid = grid / 2;
     *used = wgrid;
-#define RBL_WIDE(PT_, R_, S_) RBL_WIDE_NT(PT_, R_, S_, SEW_THREADS)
-#define RBL_WIDE_NT(PT_, R_, S_, NT_)                                                                                  \
+#define RBL_WIDE(PT_, R_, S_)                                                                                          \
     do {                                                                                                               \
-        auto kfn = k_sweep_erm_wide<T, LOSS, PT_, R_, S_, NT_>;                                                        \
-        const size_t lds = (size_t)PT_ * NT_ * Pk<T>::E * sizeof(double);                                              \
+        auto kfn = k_sweep_erm_wide<T, LOSS, PT_, R_, S_>;                                                             \
+        const size_t lds = (size_t)PT_ * SEW_THREADS * Pk<T>::E * sizeof(double);                                      \
         static bool attr_set = false;                                                                                  \
         if (!attr_set) {                                                                                               \
             RBL_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, \
                                         (int)lds));                                                                    \
             attr_set = true;                                                                                           \
         }                                                                                                              \
-        hipLaunchKernelGGL(kfn, dim3(wgrid), dim3(NT_), lds, s, D, n, ld, w, z_old, lam, v, z_new, sigma0, rho,          \
+        hipLaunchKernelGGL(kfn, dim3(wgrid), dim3(SEW_THREADS), lds, s, D, n, ld, w, z_old, lam, v, z_new, sigma0, rho,  \
                            pred, slab, partials);                                                                      \
         RBL_HIP(hipGetLastError());                                                                                    \
         return RBL_OK;                                                                                                 \
@@ -725,35 +649,15 @@ int launch_T(const T* D, long long n, long long ld, const double* w, const doubl
     // per pass, it/s (profiles/r03_sweep_shapes.txt):  d = 4000: 4 rows 177.5, 6 rows 196.5, 8 rows 204.1;  d = 6000:
     // 4 rows 203.2, 5 rows 208.0, 6 rows 210.6;  d = 8000: 2 rows 178.7, 3 rows 200.4, 4 rows 209.8;  d = 10 000: 1 row
     // 80.0, 2 rows 124.6, 3 rows 132.3 (4 rows spill: 68);  d = 12 000: 1 row 130.7, 2 rows 200.6;  d = 16 000: 1 row
-    // 147.1 (two spill).  RBL_WIDE_SHAPE=2: round 2's shapes.
-    static const int wshape = [] {
-        const char* e = getenv("RBL_WIDE_SHAPE");
-        return e ? atoi(e) : 0;
-    }();
+    // 147.1 (two spill).
     if (pt <= 1) RBL_WIDE(1, 16, 1);   // (fp32 storage reaches this kernel from 9 packets per lane on: pt >= 2)
-    if (pt <= 2) {
-        if (wshape == 2) RBL_WIDE(2, 4, 4);
-        RBL_WIDE(2, 8, 2);
-    }
-    if (pt <= 3) {
-        if (wshape == 2) RBL_WIDE(3, 4, 4);
-        RBL_WIDE(3, 6, 4);
-    }
-    if (pt <= 4) {
-        if (wshape == 2) RBL_WIDE(4, 2, 8);
-        RBL_WIDE(4, 4, 4);
-    }
-    if (pt <= 5) {
-        if (wshape == 2) RBL_WIDE(5, 2, 8);
-        RBL_WIDE(5, 3, 8);
-    }
-    if (pt <= 6) {
-        if (wshape == 2) RBL_WIDE(6, 1, 16);
-        RBL_WIDE(6, 2, 8);
-    }
+    if (pt <= 2) RBL_WIDE(2, 8, 2);
+    if (pt <= 3) RBL_WIDE(3, 6, 4);
+    if (pt <= 4) RBL_WIDE(4, 4, 4);
+    if (pt <= 5) RBL_WIDE(5, 3, 8);
+    if (pt <= 6) RBL_WIDE(6, 2, 8);
     if (pt <= 8) RBL_WIDE(8, 1, 16);   // (two rows spill with fp32 storage)
 #undef RBL_WIDE
-#undef RBL_WIDE_NT
     rbl_set_error("single-sweep kernel: d=%lld too wide", (long long)ld);
     return RBL_ERR_INVALID;
 }
@@ -770,19 +674,6 @@ bool sweep_erm_supported(int storage, int64_t ld) {
 // block per CU (launch_T) use the first half
 int sweep_erm_blocks(int num_cu) { return num_cu * 2; }
 int sweep_erm_slab_rows(int num_cu) { return sweep_erm_blocks(num_cu) + CR_SLICES; }
-// the v-only and q-only passes (one half of the fused pass each) run best with ONE block of 4 waves per CU: interleaved
-// on one box C2sq 134.6 -> 137.4 it/s (the fused pass with two rows per sub-batch the other way round, 270 it/s with two
-// blocks and 236 with one; with four rows per sub-batch it too runs best with one block, launch_T);
-// RBL_SWEEPVQ_BLOCKS_PER_CU=2 for experiments
-static int sweep_vq_blocks(int num_cu) {
-    static const int per_cu = [] {
-        const char* e = getenv("RBL_SWEEPVQ_BLOCKS_PER_CU");
-        const int v = e ? atoi(e) : 1;
-        return (v == 1 || v == 2) ? v : 1;
-    }();
-    return num_cu * per_cu;
-}
-
 int launch_sweep_erm(int storage, int loss, const void* D, int64_t n, int64_t ld, const double* w, const double* z_old,
                      double* lam, double* v, double* z_new, double sigma0, double rho, const double* pred_dev,
                      double* slab, double* partials, double* q, double* red, double* zz_out, int num_cu, hipStream_t s,
@@ -832,23 +723,21 @@ int launch_v_T(const T* D, long long n, long long ld, const double* w, const dou
                double* partials, int grid, hipStream_t s) {
     const long long PK = ld / Pk<T>::E;
     const long long passes = (PK + 63) / 64;
-#define RBL_V(P_, R_, S_) RBL_V2(P_, R_, S_, false, 2)
-#define RBL_V2(P_, R_, S_, WL_, OCC_)                                                                               \
+#define RBL_V(P_, R_, S_, WL_, OCC_)                                                                                \
     do {                                                                                                            \
-        hipLaunchKernelGGL((k_sweep_erm<T, 1, P_, R_, S_, WL_, SE_VONLY, true, OCC_>), dim3(grid), dim3(SE_THREADS), 0, s, D, n, \
+        hipLaunchKernelGGL((k_sweep_erm<T, 1, P_, R_, S_, WL_, SE_VONLY, OCC_>), dim3(grid), dim3(SE_THREADS), 0, s, D, n, \
                            ld, w, z, lam, v, (double*)nullptr, 0.0, rho, (const double*)nullptr, (double*)nullptr,  \
                            partials);                                                                               \
         RBL_HIP(hipGetLastError());                                                                                 \
         return RBL_OK;                                                                                              \
     } while (0)
-    if (passes == 1) RBL_V(1, 8, 2);
-    if (passes == 2) RBL_V(2, 4, 4);
-    if (passes <= 4) RBL_V(4, 2, 8);   // (four rows per sub-batch: no gain here, 3.50 against 3.46-3.50 ms at 6M x 1000)
+    if (passes == 1) RBL_V(1, 8, 2, false, 2);
+    if (passes == 2) RBL_V(2, 4, 4, false, 2);
+    if (passes <= 4) RBL_V(4, 2, 8, false, 2);   // (four rows per sub-batch: no gain here, 3.50 against 3.46-3.50 ms at 6M x 1000)
     // 5-8 packets per lane (fp64 d <= 1024, fp32 d <= 2048): two rows per sub-batch, w in LDS, the one block per CU may
     // use up to 512 registers per lane
-    if (passes <= 8) RBL_V2(8, 2, 8, true, 1);
+    if (passes <= 8) RBL_V(8, 2, 8, true, 1);
 #undef RBL_V
-#undef RBL_V2
     return RBL_ERR_INVALID;
 }
 }  // namespace
@@ -860,9 +749,12 @@ bool sweep_v_supported(int storage, int64_t ld) {
     return PK > 32 && PK <= 512;
 }
 
+// the v-only and q-only passes (one half of the fused pass each) run best with ONE block of 4 waves per CU: interleaved
+// on one box C2sq 134.6 -> 137.4 it/s (the fused pass with two rows per sub-batch the other way round, 270 it/s with two
+// blocks and 236 with one; with four rows per sub-batch it too runs best with one block, launch_T)
 int launch_sweep_v(int storage, const void* D, int64_t n, int64_t ld, const double* w, const double* z, double* lam,
                    double* v, double rho, double* partials, double* red, int num_cu, hipStream_t s, hipEvent_t main_done) {
-    const int grid = sweep_vq_blocks(num_cu);
+    const int grid = num_cu;
     if (storage == RBL_STORE_F32)
         RBL_TRY(launch_v_T<float>((const float*)D, n, ld, w, z, lam, v, rho, partials, grid, s));
     else
@@ -887,37 +779,27 @@ template <typename T>
 int launch_q_T(const T* D, long long n, long long ld, const double* c, double* slab, int grid, hipStream_t s) {
     const long long PK = ld / Pk<T>::E;
     const long long passes = (PK + 63) / 64;
-#define RBL_Q(P_, R_, S_) RBL_Q2(P_, R_, S_, 2)
-#define RBL_Q2(P_, R_, S_, OCC_)                                                                                     \
+#define RBL_Q(P_, R_, S_, OCC_)                                                                                      \
     do {                                                                                                             \
-        hipLaunchKernelGGL((k_sweep_erm<T, 1, P_, R_, S_, false, SE_QONLY, true, OCC_>), dim3(grid), dim3(SE_THREADS), 0, s, D, n,  \
+        hipLaunchKernelGGL((k_sweep_erm<T, 1, P_, R_, S_, false, SE_QONLY, OCC_>), dim3(grid), dim3(SE_THREADS), 0, s, D, n,  \
                            ld, (const double*)nullptr, c, (double*)nullptr, (double*)nullptr, (double*)nullptr, 0.0, 1.0,     \
                            (const double*)nullptr, slab, (double*)nullptr);                                          \
         RBL_HIP(hipGetLastError());                                                                                  \
         return RBL_OK;                                                                                               \
     } while (0)
-    if (passes == 1) RBL_Q(1, 8, 2);
-    if (passes == 2) RBL_Q(2, 4, 4);
-    if (passes <= 4) RBL_Q(4, 2, 8);
-    if (passes <= 8) RBL_Q2(8, 2, 8, 1);
+    if (passes == 1) RBL_Q(1, 8, 2, 2);
+    if (passes == 2) RBL_Q(2, 4, 4, 2);
+    if (passes <= 4) RBL_Q(4, 2, 8, 2);
+    if (passes <= 8) RBL_Q(8, 2, 8, 1);
 #undef RBL_Q
-#undef RBL_Q2
     return RBL_ERR_INVALID;
 }
 }  // namespace
 
 // q = D^T c through the single-sweep kernel's loads (SE_QONLY); same widths as launch_sweep_v
-bool sweep_q_supported(int storage, int64_t ld) {
-    static const bool on = [] {
-        const char* e = getenv("RBL_GEMVT_SWEEP");     // =0: k_gemvt everywhere (round 2), for comparison
-        return !(e && e[0] == '0');
-    }();
-    return on && sweep_v_supported(storage, ld);
-}
-
 int launch_sweep_q(int storage, const void* D, int64_t n, int64_t ld, const double* c, double* slab, double* q, int num_cu,
                    hipStream_t s, hipEvent_t main_done) {
-    const int grid = sweep_vq_blocks(num_cu);
+    const int grid = num_cu;   // one block per CU (see launch_sweep_v)
     if (storage == RBL_STORE_F32)
         RBL_TRY(launch_q_T<float>((const float*)D, n, ld, c, slab, grid, s));
     else

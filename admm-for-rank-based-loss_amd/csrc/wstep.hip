@@ -528,11 +528,7 @@ bool ncg_persist_try(const double* G, int64_t ld, const double* q, NcgParams P, 
 int run_ncg(const double* G, int64_t ld, const double* q, double rho, double reg, double smooth_t, double L, double tol,
             int max_inner, double* w, WstepWorkspace& ws, int* iters_host, hipStream_t s, bool want_Gw) {
     const unsigned sg = symv_grid(ld);
-    static const int ncg_active = [] {
-        const char* e = getenv("RBL_NCG_ACTIVE");     // =0: the nonlinear CG alone (comparison)
-        return (e && e[0] == '0') ? 0 : 1;
-    }();
-    NcgParams P{rho, reg, smooth_t, tol, ncg_active};
+    NcgParams P{rho, reg, smooth_t, tol, 1};
     {
         // one persistent launch (k_ncg_persist) where the row width allows it
         int status = 0, it = 0, rc = RBL_OK;
@@ -746,9 +742,8 @@ __global__ __launch_bounds__(WP_THREADS) void k_cg_persist(const double* __restr
                                                             double rho, double reg, double tol, int max_iter,
                                                             double* __restrict__ w, unsigned long long* x0, unsigned long long* x1,
                                                             unsigned tag_base, double* __restrict__ Gw_out, unsigned* abort_word,
-                                                            int* pin, long long* dbg) {
+                                                            int* pin) {
     extern __shared__ __attribute__((aligned(16))) double wp_lds[];
-    if (dbg && blockIdx.x == 0 && threadIdx.x == 0) dbg[0] = (long long)wall_clock64();
     double* xs = wp_lds;                       // ld
     double* red = wp_lds + ld;                 // 16 (block sums)
     double* ybuf = red + 16;                   // WP_RPB
@@ -764,13 +759,11 @@ __global__ __launch_bounds__(WP_THREADS) void k_cg_persist(const double* __restr
         if (j < ld) xs[j] = wj[k];
     }
     __syncthreads();
-    if (dbg && blockIdx.x == 0 && threadIdx.x == 0) dbg[1] = (long long)wall_clock64();
     wp_matvec<GLDS>(G, gs, ld, r0, r1, xs, rho, reg, ybuf);          // A w
     int iters = 0, done = 0, ok = 1;
     double rr = 0.0, thr = 0.0;
     ++xn;
     if (!wp_exchange<PER>(tag_base + xn, ybuf, x0, ld, aj, abort_word)) ok = 0;
-    if (dbg && blockIdx.x == 0 && threadIdx.x == 0) dbg[2] = (long long)wall_clock64();
     if (ok) {
         double acc[2] = {0.0, 0.0};
 #pragma unroll
@@ -823,7 +816,6 @@ __global__ __launch_bounds__(WP_THREADS) void k_cg_persist(const double* __restr
         ++iters;
         done = (rr <= thr || alpha == 0.0) ? 1 : 0;
     }
-    if (dbg && blockIdx.x == 0 && threadIdx.x == 0) dbg[3] = (long long)wall_clock64();
     if (ok && Gw_out) {
         __syncthreads();
 #pragma unroll
@@ -845,9 +837,7 @@ __global__ __launch_bounds__(WP_THREADS) void k_cg_persist(const double* __restr
             }
         }
         __syncthreads();
-        if (dbg && threadIdx.x == 0) dbg[4] = (long long)wall_clock64();
         if (threadIdx.x == 0) wp_publish(pin, ok ? done : -2, iters);
-        if (dbg && threadIdx.x == 0) dbg[5] = (long long)wall_clock64();
     }
 }
 
@@ -1152,22 +1142,11 @@ struct WpPlan {
 // launch shape of the persistent w-step: WP_RPB rows per block, G rows in LDS when they fit
 WpPlan wp_plan(int64_t ld) {
     WpPlan p{false, false, 0, 0, 0};
-    static const int enabled = [] {
-        const char* e = getenv("RBL_WSTEP_PERSIST");
-        return (e && e[0] == '0') ? 0 : 1;
-    }();
-    if (!enabled || ld > WSTEP_PERSIST_MAX_LD || ld < 4) return p;
-    {
-        // several handles of this process on one device (threads as ranks, the test rigs): two persistent kernels side by
-        // side can each hold some CUs and wait for blocks the other keeps out - the batched launches serve there.
-        // RBL_WSTEP_PERSIST=2 keeps the persistent form regardless (lab).
-        static const int force = [] {
-            const char* e = getenv("RBL_WSTEP_PERSIST");
-            return (e && e[0] == '2') ? 1 : 0;
-        }();
-        int dev = 0;
-        if (!force && (hipGetDevice(&dev) != hipSuccess || rbl_live_handles(dev) > 1)) return p;
-    }
+    if (ld > WSTEP_PERSIST_MAX_LD || ld < 4) return p;
+    // several handles of this process on one device (threads as ranks, the test rigs): two persistent kernels side by
+    // side can each hold some CUs and wait for blocks the other keeps out - the batched launches serve there
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || rbl_live_handles(dev) > 1) return p;
     static const int cus = [] {
         int dev = 0, c = 256;
         if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&c, hipDeviceAttributeMultiprocessorCount, dev);
@@ -1191,89 +1170,65 @@ int wp_set_lds(K kernel, size_t bytes) {
     return RBL_OK;
 }
 
-// returns RBL_OK with *status = 1 converged / 0 iteration cap / -1 launch failure / -2 a wait gave up
-int run_cg_persist(const WpPlan& pl, const double* G, int64_t ld, const double* q, double rho, double reg, double tol,
-                   int max_iter, double* w, WstepWorkspace& ws, bool want_Gw, int* status, int* iters, hipStream_t s) {
-    int* pin = ws.pin + 4;
+// One launch of a persistent w-step kernel and the host's wait for its status.  kern[glds][wide] are the kernel's
+// <GLDS, PER> instantiations (G rows in LDS or not; PER = 4 up to ld = 4 * WP_THREADS, 8 above); `args` builds the
+// kernel's argument list from the shared part: the exchange tags of this launch (tag_base + 1 ...), the iteration cap
+// (12 bits of exchange number), G w's destination (or NULL) and the two exchange buffers.  pin[0] = -1 is the sentinel
+// the kernel's publish overwrites.  Returns RBL_OK with *status = 1 converged / 0 iteration cap / -1 launch failure /
+// -2 a wait gave up, and *iters.
+template <typename K, typename Args>
+int wp_run(const WpPlan& pl, int64_t ld, K const (&kern)[2][2], int* pin, int max_iter, WstepWorkspace& ws, bool want_Gw,
+           int* status, int* iters, hipStream_t s, Args args) {
     pin[0] = -1;
     ws.launch_seq = (ws.launch_seq + 1) & 0xfffff;
     if (ws.launch_seq == 0) ws.launch_seq = 1;
     const unsigned tag_base = (unsigned)ws.launch_seq << 12;          // exchange tags of this launch: tag_base + 1 ...
     if (max_iter > 4000) max_iter = 4000;                             // (12 bits of exchange number)
     double* gw = want_Gw ? ws.Gy : nullptr;
-    unsigned long long *x0 = reinterpret_cast<unsigned long long*>(ws.xch),
-                       *x1 = reinterpret_cast<unsigned long long*>(ws.xch) + WSTEP_XCH_GRANULES;
-    // RBL_WPERSIST_DEBUG=1: block 0 leaves 100 MHz wall-clock stamps (start | rows staged | first exchange | loop done |
-    // G w written | published) behind the second exchange buffer; printed to stderr after the kernel
-    static const bool dbg_on = [] {
-        const char* e = getenv("RBL_WPERSIST_DEBUG");
-        return e && e[0] == '1';
-    }();
-    long long* dbg = dbg_on ? reinterpret_cast<long long*>(ws.xch) + 2 * WSTEP_XCH_GRANULES : nullptr;
-#define RBL_CG_PERSIST(GL, PR)                                                                                           \
-    do {                                                                                                                 \
-        static size_t lds_set = 0; /* (one attribute call per instantiation and size, not per launch) */                 \
-        if (lds_set < pl.lds_bytes) {                                                                                    \
-            RBL_TRY(wp_set_lds(k_cg_persist<GL, PR>, pl.lds_bytes));                                                     \
-            lds_set = pl.lds_bytes;                                                                                      \
-        }                                                                                                                \
-        hipLaunchKernelGGL((k_cg_persist<GL, PR>), dim3(pl.nblocks), dim3(WP_THREADS), pl.lds_bytes, s, G, (int)ld, q, rho, \
-                           reg, tol, max_iter, w, x0, x1, tag_base, gw, ws.bar, pin, dbg);                               \
-    } while (0)
-    const bool narrow = ld <= 4 * WP_THREADS;
-    if (pl.glds && narrow) RBL_CG_PERSIST(true, 4);
-    else if (pl.glds) RBL_CG_PERSIST(true, 8);
-    else if (narrow) RBL_CG_PERSIST(false, 4);
-    else RBL_CG_PERSIST(false, 8);
-#undef RBL_CG_PERSIST
-    RBL_HIP(hipGetLastError());
+    unsigned long long *x0 = reinterpret_cast<unsigned long long*>(ws.xch), *x1 = x0 + WSTEP_XCH_GRANULES;
+    const int g = pl.glds ? 1 : 0, wide = ld <= 4 * WP_THREADS ? 0 : 1;
+    static size_t lds_set[2][2] = {};   // (one attribute call per instantiation and size, not per launch)
+    if (lds_set[g][wide] < pl.lds_bytes) {
+        RBL_TRY(wp_set_lds(kern[g][wide], pl.lds_bytes));
+        lds_set[g][wide] = pl.lds_bytes;
+    }
+    RBL_TRY(args(kern[g][wide], tag_base, max_iter, gw, x0, x1));
     rbl_spin_wait(pin, -1, s);
     const volatile int* st = pin;
     *status = st[0];
     *iters = st[1];
-    if (dbg) {
-        long long t[6];
-        RBL_HIP(hipMemcpy(t, dbg, sizeof(t), hipMemcpyDeviceToHost));
-        fprintf(stderr, "[rbl] k_cg_persist: %d iterations; staged %.2f us, first exchange %.2f, loop %.2f, G w %.2f, publish %.2f\n",
-                st[1], (t[1] - t[0]) * 0.01, (t[2] - t[1]) * 0.01, (t[3] - t[2]) * 0.01, (t[4] - t[3]) * 0.01, (t[5] - t[4]) * 0.01);
-    }
     return RBL_OK;
+}
+
+int run_cg_persist(const WpPlan& pl, const double* G, int64_t ld, const double* q, double rho, double reg, double tol,
+                   int max_iter, double* w, WstepWorkspace& ws, bool want_Gw, int* status, int* iters, hipStream_t s) {
+    static decltype(&k_cg_persist<true, 4>) const kern[2][2] = {{k_cg_persist<false, 4>, k_cg_persist<false, 8>},
+                                                                 {k_cg_persist<true, 4>, k_cg_persist<true, 8>}};
+    int* pin = ws.pin + 4;
+    return wp_run(pl, ld, kern, pin, max_iter, ws, want_Gw, status, iters, s,
+                  [&](auto k, unsigned tag_base, int cap, double* gw, unsigned long long* x0, unsigned long long* x1) {
+                      hipLaunchKernelGGL(k, dim3(pl.nblocks), dim3(WP_THREADS), pl.lds_bytes, s, G, (int)ld, q, rho, reg, tol,
+                                         cap, w, x0, x1, tag_base, gw, ws.bar, pin);
+                      RBL_HIP(hipGetLastError());
+                      return RBL_OK;
+                  });
 }
 
 int run_ncg_persist(const WpPlan& pl, const double* G, int64_t ld, const double* q, NcgParams P, int max_iter, double* w,
                     WstepWorkspace& ws, bool want_Gw, int* status, int* iters, hipStream_t s) {
+    static decltype(&k_ncg_persist<true, 4>) const kern[2][2] = {{k_ncg_persist<false, 4>, k_ncg_persist<false, 8>},
+                                                                  {k_ncg_persist<true, 4>, k_ncg_persist<true, 8>}};
     int* pin = ws.pin + 8;
-    pin[0] = -1;
     pin[2] = -1;
     if (ws.ncg_skip > 0) P.active = 0;
-    ws.launch_seq = (ws.launch_seq + 1) & 0xfffff;
-    if (ws.launch_seq == 0) ws.launch_seq = 1;
-    const unsigned tag_base = (unsigned)ws.launch_seq << 12;
-    if (max_iter > 4000) max_iter = 4000;
-    double* gw = want_Gw ? ws.Gy : nullptr;
-    unsigned long long *x0 = reinterpret_cast<unsigned long long*>(ws.xch),
-                       *x1 = reinterpret_cast<unsigned long long*>(ws.xch) + WSTEP_XCH_GRANULES;
-#define RBL_NCG_PERSIST(GL, PR)                                                                                          \
-    do {                                                                                                                 \
-        static size_t lds_set = 0;                                                                                       \
-        if (lds_set < pl.lds_bytes) {                                                                                    \
-            RBL_TRY(wp_set_lds(k_ncg_persist<GL, PR>, pl.lds_bytes));                                                    \
-            lds_set = pl.lds_bytes;                                                                                      \
-        }                                                                                                                \
-        hipLaunchKernelGGL((k_ncg_persist<GL, PR>), dim3(pl.nblocks), dim3(WP_THREADS), pl.lds_bytes, s, G, (int)ld, q, P, \
-                           max_iter, w, x0, x1, tag_base, gw, ws.bar, pin);                                              \
-    } while (0)
-    const bool narrow = ld <= 4 * WP_THREADS;
-    if (pl.glds && narrow) RBL_NCG_PERSIST(true, 4);
-    else if (pl.glds) RBL_NCG_PERSIST(true, 8);
-    else if (narrow) RBL_NCG_PERSIST(false, 4);
-    else RBL_NCG_PERSIST(false, 8);
-#undef RBL_NCG_PERSIST
-    RBL_HIP(hipGetLastError());
-    rbl_spin_wait(pin, -1, s);
+    RBL_TRY(wp_run(pl, ld, kern, pin, max_iter, ws, want_Gw, status, iters, s,
+                   [&](auto k, unsigned tag_base, int cap, double* gw, unsigned long long* x0, unsigned long long* x1) {
+                       hipLaunchKernelGGL(k, dim3(pl.nblocks), dim3(WP_THREADS), pl.lds_bytes, s, G, (int)ld, q, P, cap, w, x0,
+                                          x1, tag_base, gw, ws.bar, pin);
+                       RBL_HIP(hipGetLastError());
+                       return RBL_OK;
+                   }));
     const volatile int* st = pin;
-    *status = st[0];
-    *iters = st[1];
     // the linear first phase pays where the Huber pattern is stable between ADMM iterations (6M x 1000: 252 -> 270 it/s)
     // and costs its iterations where it is not (a few thousand rows: +10-40 % inner iterations if tried every time):
     // after a dropped attempt the next 1, 2, 4, ... 16 w-steps run the nonlinear CG alone
@@ -1379,11 +1334,6 @@ int run_wstep(int wstep, const double* G, int64_t ld, const double* q, double rh
         bool fell_back = false;
         return finish_wstep_l1(G, ld, q, rho, reg, L, tol, max_inner, w, ws, iters_host, s, &fell_back);
     }
-    static const bool smooth_fista = [] {      // RBL_SMOOTH_FISTA=1: the round-1 solver, for comparisons
-        const char* e = getenv("RBL_SMOOTH_FISTA");
-        return e && e[0] == '1';
-    }();
-    if (smooth_fista) return run_fista(1, G, ld, q, rho, reg, smooth_t, L, tol, max_inner, w, ws, iters_host, s);
     return run_ncg(G, ld, q, rho, reg, smooth_t, L, tol, max_inner, w, ws, iters_host, s, want_Gw);
 }
 

@@ -15,7 +15,7 @@ X, y = problems.make_problem(3000, 16, seed=5)
 
 
 def run(env, wstep=1, nit=4):
-    for k in ("RBL_NO_ZBAND", "RBL_ZBAND_MIN_N", "RBL_SORT32", "RBL_PAV_UPPER_PERSIST", "RBL_PAV_NO_SEQ"):
+    for k in ("RBL_NO_ZBAND", "RBL_ZBAND_MIN_N", "RBL_PAV_UPPER_PERSIST"):
         os.environ.pop(k, None)
     os.environ.update(env)
     s = R.Solver(3000, 16, "aorr", "binary_cross_entropy", reg=1e-4, wstep=wstep, args=[0.45, 0.55], tol=0.0, storage="f64")
@@ -30,9 +30,8 @@ def run(env, wstep=1, nit=4):
     return out
 
 
-for name, env in [("nozband s32", {"RBL_NO_ZBAND": "1"}), ("nozband s32 again", {"RBL_NO_ZBAND": "1"}),
-                  ("nozband s64", {"RBL_NO_ZBAND": "1", "RBL_SORT32": "0"}),
-                  ("nozband s64 oldpav", {"RBL_NO_ZBAND": "1", "RBL_SORT32": "0", "RBL_PAV_UPPER_PERSIST": "0", "RBL_PAV_NO_SEQ": "1"}),
-                  ("zband s32", {"RBL_ZBAND_MIN_N": "16"}), ("zband s64", {"RBL_ZBAND_MIN_N": "16", "RBL_SORT32": "0"})]:
+for name, env in [("nozband", {"RBL_NO_ZBAND": "1"}), ("nozband again", {"RBL_NO_ZBAND": "1"}),
+                  ("nozband 2-launch pav", {"RBL_NO_ZBAND": "1", "RBL_PAV_UPPER_PERSIST": "0"}),
+                  ("zband", {"RBL_ZBAND_MIN_N": "16"})]:
     for wstep in (1, 2):
         print("%-20s wstep %d  %s" % (name, wstep, "  ".join(run(env, wstep))))

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""Inner iterations of the smoothed-l1 w-step over 45 sADMM iterations of a small problem (the oracle's generator), for
-comparing RBL_NCG_ACTIVE=0 (nonlinear CG alone) with the default (linear first phase, csrc/wstep.hip):
+"""Inner iterations of the smoothed-l1 w-step (csrc/wstep.hip: the nonlinear CG with its linear first phase) over 45
+sADMM iterations of a small problem (the oracle's generator):
     python tests/diag_sadmm_inner.py ROWS COLS T0"""
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -15,4 +15,4 @@ tot = 0; inn = []
 for i in range(45):
     st = s._s.step(want_objective=True)
     tot += st.inner_iters; inn.append(st.inner_iters)
-print("n", n, "d", d, "t0", t0, "RBL_NCG_ACTIVE", os.environ.get("RBL_NCG_ACTIVE"), "total inner", tot, inn)
+print("n", n, "d", d, "t0", t0, "total inner", tot, inn)

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Generic interleaved A/B of one environment switch on ONE box:  tools/ab_env.sh OUT_DIR VAR=VALUE config [config ...]
-#   "new" = the variable unset (defaults), "old" = VAR=VALUE (e.g. RBL_GEMVT_SWEEP=0, RBL_WSTEP_PERSIST=0)
+#   "new" = the variable unset (defaults), "old" = VAR=VALUE (e.g. RBL_PAV_UPPER_PERSIST=0, RBL_EHRM_SPEC=-1)
 out=$1; kv=$2; shift 2
 mkdir -p $out
 for cfg in "$@"; do

@@ -2,7 +2,7 @@
 """The linear first phase of the smoothed-l1 w-step (csrc/wstep.hip: k_ncg_persist, phase A) emulated on the host with the
 device's G, q, w, rho and t of an sADMM run at C2smooth's size: per selected ADMM iteration the number of coordinates
 outside the assumed Huber pattern and the residual after every CG step, next to the inner iterations the device's
-nonlinear CG took (run with RBL_NCG_ACTIVE=0 for that comparison).  This is the evidence behind the rules in the kernel
+w-step took.  This is the evidence behind the rules in the kernel
 (round 3): crossings in the first steps come back, a wrong pattern shows by the 6th step.
     python tools/ncg_probe.py [rows]"""
 import os, sys

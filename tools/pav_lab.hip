@@ -40,23 +40,22 @@ int main(int argc, char** argv) {
     (void)hipMemcpy(dsg, sg.data(), n * 8, hipMemcpyHostToDevice);
     (void)hipMemcpy(dsa, sga.data(), n * 8, hipMemcpyHostToDevice);
     const unsigned tiles = (unsigned)((n + PB_TILE - 1) / PB_TILE);
-    for (int flags = 0; flags < 6; ++flags) {       // bit 0: one wave per seam at the top levels, bit 1: no sequential stage; 4, 5: the speculating EHRM form
+    for (int spec = 0; spec < 2; ++spec) {           // 0: the plain kernel, 1: the speculating EHRM form
         for (int rep = 0; rep < 3; ++rep) {
             (void)hipMemset(dmc, 0, 4);
-            if (flags >= 4)
+            if (spec)
                 hipLaunchKernelGGL((k_pav_bottom<0, true>), dim3(tiles), dim3(PV_THREADS), 0, 0, dms, dsa, dsg, (const int*)nullptr, rho, n, du,
-                                   dmc, (const double*)nullptr, (const double*)nullptr, flags & 1, -1, -5.0, 1, dfp);
+                                   dmc, (const double*)nullptr, (const double*)nullptr, -1, -5.0, 1, dfp);
             else
                 hipLaunchKernelGGL((k_pav_bottom<0, false>), dim3(tiles), dim3(PV_THREADS), 0, 0, dms, dsa, dsg, (const int*)dbr, rho, n, du,
-                                   dmc, (const double*)nullptr, (const double*)nullptr, flags, -1, 0.0, 0, (double*)nullptr);
+                                   dmc, (const double*)nullptr, (const double*)nullptr, -1, 0.0, 0, (double*)nullptr);
             (void)hipDeviceSynchronize();
         }
         long long st[8 * 32];
         (void)hipMemcpyFromSymbol(st, HIP_SYMBOL(pav_lab_stamps), sizeof(st));
         u32 mc = 0;
         (void)hipMemcpy(&mc, dmc, 4, hipMemcpyDeviceToHost);
-        printf("flags %d (speculating form %d, wave_top %d, no_seq %d): merges in all tiles %u; block 0 = the last tile, us per stage (100 MHz clock):\n", flags, flags >= 4, flags & 1,
-               flags >= 4 ? 0 : (flags >> 1) & 1, mc);
+        printf("speculating form %d: merges in all tiles %u; block 0 = the last tile, us per stage (100 MHz clock):\n", spec, mc);
         const long long* s = st;
         printf("  level 0 + prefixes %.1f | sequential stage %.1f |", (s[1] - s[0]) / 100.0, (s[2] - s[1]) / 100.0);
         long long prev = s[2];
