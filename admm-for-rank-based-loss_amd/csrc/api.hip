@@ -35,6 +35,7 @@ static std::atomic<int> g_live[64];
 int rbl_live_handles(int device) { return device >= 0 && device < 64 ? g_live[device].load(std::memory_order_relaxed) : 2; }
 
 struct rbl_solver {
+    DevArena mem;   // every device and pinned buffer of the handle
     rbl_config cfg;
     bool counted = false;
     int64_t n = 0, d = 0, ld = 0, nt = 0, off = 0;
@@ -58,9 +59,7 @@ struct rbl_solver {
 
     SortWorkspace sw{};
     PavWorkspace pw{};
-    double *locx_a = nullptr, *chunk_a = nullptr, *cph_a = nullptr, *cpl_a = nullptr;
-    double *locx_b = nullptr, *chunk_b = nullptr, *cph_b = nullptr, *cpl_b = nullptr;
-    Prefix pa{}, pb{}, pm{};
+    PrefixBufs pfx_a, pfx_b;   // prefix sums of sigma_a / sigma_b (pfx_b = pfx_a unless EHRM)
     WstepWorkspace ww{};
     double L = 0.0;
 
@@ -83,7 +82,6 @@ struct rbl_solver {
 
     // single-sweep erm iteration (sweep_erm.hip)
     bool fused_ok = false, z_ready = false, p_valid = false, p_pending = false, pred_valid = false, fused_ran = false;
-    bool red_owned = false;
     // distributed z-step (rbl_zd_*): this rank's chunk of the globally sorted order
     double* zd_small = nullptr;      // samples | bounds | fvals | candidates | partial sums | seam sums
     ZdSeam* zd_seam = nullptr;
@@ -91,9 +89,7 @@ struct rbl_solver {
     long long* zd_bounds_dev = nullptr;
     long long* zd_counts_dev = nullptr;   // RBL_BUF_ZD_COUNTS: per-destination counts of the sample sort (64 x int64)
     u32* zd_zids = nullptr;          // row ids received back (n)
-    double *zd_locx_a = nullptr, *zd_chunk_a = nullptr, *zd_cph_a = nullptr, *zd_cpl_a = nullptr;
-    double *zd_locx_b = nullptr, *zd_chunk_b = nullptr, *zd_cph_b = nullptr, *zd_cpl_b = nullptr;
-    Prefix zpa{}, zpb{};
+    PrefixBufs zd_a, zd_b;           // prefix sums of the chunk's slice of sigma_a / sigma_b (zd_b = zd_a unless EHRM)
     int64_t zd_n = 0, zd_off = 0;    // chunk length and its offset in the sorted order
     int zd_world = 0;
     bool fuse_v = false;   // rank-weighted problems: v = D w fused with the lambda update (sweep_erm.hip, SE_VONLY)
@@ -157,23 +153,22 @@ void rbl_spin_wait(const volatile int* word, int sentinel, hipStream_t stream) {
     }
 }
 
-namespace {
-
-template <typename T>
-int dev_alloc(T** p, size_t count) {
-    *p = nullptr;
-    if (count == 0) count = 1;
-    hipError_t e = hipMalloc((void**)p, count * sizeof(T));
-    if (e != hipSuccess) {
-        rbl_set_error("hipMalloc of %zu bytes failed: %s", count * sizeof(T), hipGetErrorString(e));
-        return RBL_ERR_NOMEM;
+int alloc_sort(DevArena& mem, SortWorkspace& sw, int64_t n, bool with_vals, hipStream_t s) {
+    RBL_TRY(mem.alloc(&sw.keys[0], (size_t)n));
+    RBL_TRY(mem.alloc(&sw.keys[1], (size_t)n));
+    if (with_vals) {
+        RBL_TRY(mem.alloc(&sw.vals[0], (size_t)n));
+        RBL_TRY(mem.alloc(&sw.vals[1], (size_t)n));
     }
+    RBL_TRY(mem.alloc((unsigned char**)&sw.spine, sort_spine_bytes()));
+    RBL_TRY(mem.alloc(&sw.bin_total, 256));
+    RBL_TRY(mem.alloc(&sw.bin_base, 256));
+    RBL_TRY(mem.alloc((unsigned char**)&sw.ghist, sort_ghist_bytes()));
+    RBL_HIP(hipMemsetAsync(sw.ghist, 0, sort_ghist_bytes(), s));
     return RBL_OK;
 }
 
-void dev_free(void* p) {
-    if (p) (void)hipFree(p);
-}
+namespace {
 
 int check_device(int* count_out) {
     int cnt = 0;
@@ -206,105 +201,51 @@ int fill_const(double* p, int64_t count, double val, hipStream_t s) {
     return RBL_OK;
 }
 
-int alloc_sort(SortWorkspace& sw, int64_t n, bool with_vals) {
-    RBL_TRY(dev_alloc(&sw.keys[0], (size_t)n));
-    RBL_TRY(dev_alloc(&sw.keys[1], (size_t)n));
-    if (with_vals) {
-        RBL_TRY(dev_alloc(&sw.vals[0], (size_t)n));
-        RBL_TRY(dev_alloc(&sw.vals[1], (size_t)n));
-    }
-    RBL_TRY(dev_alloc((unsigned char**)&sw.spine, sort_spine_bytes()));
-    RBL_TRY(dev_alloc(&sw.bin_total, 256));
-    RBL_TRY(dev_alloc(&sw.bin_base, 256));
-    RBL_TRY(dev_alloc((unsigned char**)&sw.ghist, sort_ghist_bytes()));
-    RBL_HIP(hipMemset(sw.ghist, 0, sort_ghist_bytes()));
+int alloc_prefix(DevArena& mem, PrefixBufs& p, int64_t n) {
+    const int64_t nc = pav_num_chunks(n);
+    RBL_TRY(mem.alloc(&p.locx, (size_t)n + 1));
+    RBL_TRY(mem.alloc(&p.chunk, (size_t)nc));
+    RBL_TRY(mem.alloc(&p.cph, (size_t)nc));
+    RBL_TRY(mem.alloc(&p.cpl, (size_t)nc));
     return RBL_OK;
 }
 
-void free_sort(SortWorkspace& sw) {
-    dev_free(sw.keys[0]); dev_free(sw.keys[1]); dev_free(sw.vals[0]); dev_free(sw.vals[1]);
-    dev_free(sw.spine); dev_free(sw.bin_total); dev_free(sw.bin_base); dev_free(sw.ghist);
-    sw = SortWorkspace{};
-}
-
-int alloc_pav(PavWorkspace& pw, int64_t n) {
-    const int64_t nc = pav_num_chunks(n);
-    RBL_TRY(dev_alloc(&pw.ms, (size_t)n));
-    RBL_TRY(dev_alloc(&pw.u, (size_t)n));
-    RBL_TRY(dev_alloc(&pw.locx_m, (size_t)n + 1));
-    RBL_TRY(dev_alloc(&pw.chunk_m, (size_t)nc));
-    RBL_TRY(dev_alloc(&pw.cph_m, (size_t)nc));
-    RBL_TRY(dev_alloc(&pw.cpl_m, (size_t)nc));
-    RBL_TRY(dev_alloc(&pw.recs, (size_t)pav_num_recs(n)));
-    RBL_HIP(hipMemset(pw.recs, 0xff, sizeof(SeamRec) * (size_t)pav_num_recs(n)));   // s = -1: no hint from a previous iteration
-    RBL_TRY(dev_alloc(&pw.counters, 4));
-    RBL_HIP(hipMemset(pw.counters, 0, 4 * sizeof(u32)));   // (read by every iteration's statistics, also when the caller supplied z)
-    RBL_TRY(dev_alloc(&pw.partials, (size_t)reduce_blocks() * 4));
-    RBL_TRY(dev_alloc(&pw.branch, 1));
+int alloc_pav(DevArena& mem, PavWorkspace& pw, int64_t n, hipStream_t s) {
+    RBL_TRY(mem.alloc(&pw.ms, (size_t)n));
+    RBL_TRY(mem.alloc(&pw.u, (size_t)n));
+    RBL_TRY(alloc_prefix(mem, pw.pm, n));
+    RBL_TRY(mem.alloc(&pw.recs, (size_t)pav_num_recs(n)));
+    RBL_HIP(hipMemsetAsync(pw.recs, 0xff, sizeof(SeamRec) * (size_t)pav_num_recs(n), s));   // s = -1: no hint from a previous iteration
+    RBL_TRY(mem.alloc(&pw.counters, 4));
+    RBL_HIP(hipMemsetAsync(pw.counters, 0, 4 * sizeof(u32), s));   // (read by every iteration's statistics, also when the caller supplied z)
+    RBL_TRY(mem.alloc(&pw.partials, (size_t)reduce_blocks() * 4));
+    RBL_TRY(mem.alloc(&pw.branch, 1));
     pw.ex = PavExtras{};
-    RBL_TRY(dev_alloc(&pw.ex.bar, pav_bar_uints()));
-    RBL_HIP(hipMemset(pw.ex.bar, 0, sizeof(unsigned) * pav_bar_uints()));
-    RBL_TRY(dev_alloc(&pw.ex.big, (size_t)pav_big_recs()));
-    RBL_TRY(dev_alloc(&pw.ex.fpart, (size_t)pav_fpart_doubles(n)));
+    RBL_TRY(mem.alloc(&pw.ex.bar, pav_bar_uints()));
+    RBL_HIP(hipMemsetAsync(pw.ex.bar, 0, sizeof(unsigned) * pav_bar_uints(), s));
+    RBL_TRY(mem.alloc(&pw.ex.big, (size_t)pav_big_recs()));
+    RBL_TRY(mem.alloc(&pw.ex.fpart, (size_t)pav_fpart_doubles(n)));
     pw.ex.spec = 1;   // EHRM: branch b on every ADMM trajectory seen; corrected by the first exact test
     return RBL_OK;
 }
 
-void free_pav(PavWorkspace& pw) {
-    dev_free(pw.ms); dev_free(pw.u); dev_free(pw.locx_m); dev_free(pw.chunk_m); dev_free(pw.cph_m);
-    dev_free(pw.cpl_m); dev_free(pw.recs); dev_free(pw.counters); dev_free(pw.partials); dev_free(pw.branch);
-    dev_free(pw.ex.bar); dev_free(pw.ex.big); dev_free(pw.ex.fpart);
-    pw = PavWorkspace{};
-}
-
-int alloc_prefix(double** locx, double** chunk, double** cph, double** cpl, int64_t n) {
-    const int64_t nc = pav_num_chunks(n);
-    RBL_TRY(dev_alloc(locx, (size_t)n + 1));
-    RBL_TRY(dev_alloc(chunk, (size_t)nc));
-    RBL_TRY(dev_alloc(cph, (size_t)nc));
-    RBL_TRY(dev_alloc(cpl, (size_t)nc));
-    return RBL_OK;
-}
-
-// the status blocks of the lasso kernel and of the CG batches live in pinned host memory the device
-// writes directly (status word last): the host spins on the word - no copy, no stream-wide wait
-int alloc_wstep_pin(WstepWorkspace& ww) {
-    void* pin = nullptr;
-    RBL_HIP(hipHostMalloc(&pin, 64, hipHostMallocCoherent));
-    ww.pin = (int*)pin;
+int alloc_wstep(DevArena& mem, WstepWorkspace& ww, int64_t ld, hipStream_t s) {
+    RBL_TRY(mem.alloc(&ww.yk, (size_t)ld));
+    RBL_TRY(mem.alloc(&ww.Gy, (size_t)ld));
+    RBL_TRY(mem.alloc(&ww.wn, (size_t)ld));
+    RBL_TRY(mem.alloc(&ww.r, (size_t)ld));
+    RBL_TRY(mem.alloc(&ww.p, (size_t)ld));
+    RBL_TRY(mem.alloc(&ww.scal, 8));
+    RBL_TRY(mem.alloc(&ww.flags, 8));
+    RBL_TRY(mem.alloc(&ww.bar, (size_t)WSTEP_BAR_UINTS));
+    RBL_HIP(hipMemsetAsync(ww.bar, 0, sizeof(unsigned) * WSTEP_BAR_UINTS, s));
+    RBL_TRY(mem.alloc(&ww.xch, (size_t)WSTEP_XCH_DOUBLES));
+    RBL_HIP(hipMemsetAsync(ww.xch, 0, sizeof(double) * WSTEP_XCH_DOUBLES, s));   // tag 0 is never used
+    // the status blocks of the lasso kernel and of the CG batches live in pinned host memory the device
+    // writes directly (status word last): the host spins on the word - no copy, no stream-wide wait
+    RBL_TRY(mem.pinned(&ww.pin, 16, hipHostMallocCoherent));
     for (int i = 0; i < 16; ++i) ww.pin[i] = 0;
     return RBL_OK;
-}
-
-void free_wstep_pin(WstepWorkspace& ww) {
-    if (ww.pin) (void)hipHostFree(ww.pin);
-    ww.pin = nullptr;
-}
-
-int alloc_wstep(WstepWorkspace& ww, int64_t ld) {
-    RBL_TRY(dev_alloc(&ww.yk, (size_t)ld));
-    RBL_TRY(dev_alloc(&ww.Gy, (size_t)ld));
-    RBL_TRY(dev_alloc(&ww.wn, (size_t)ld));
-    RBL_TRY(dev_alloc(&ww.r, (size_t)ld));
-    RBL_TRY(dev_alloc(&ww.p, (size_t)ld));
-    RBL_TRY(dev_alloc(&ww.scal, 8));
-    RBL_TRY(dev_alloc(&ww.flags, 8));
-    RBL_TRY(dev_alloc(&ww.bar, (size_t)WSTEP_BAR_UINTS));
-    RBL_HIP(hipMemset(ww.bar, 0, sizeof(unsigned) * WSTEP_BAR_UINTS));
-    RBL_TRY(dev_alloc(&ww.xch, (size_t)WSTEP_XCH_DOUBLES));
-    RBL_HIP(hipMemset(ww.xch, 0, sizeof(double) * WSTEP_XCH_DOUBLES));   // tag 0 is never used
-    RBL_TRY(alloc_wstep_pin(ww));
-    return RBL_OK;
-}
-
-void free_wstep(WstepWorkspace& ww) {
-    dev_free(ww.eig_Vt); dev_free(ww.eig_V); dev_free(ww.eig_lambda);
-    dev_free(ww.yk); dev_free(ww.Gy); dev_free(ww.wn); dev_free(ww.r); dev_free(ww.p); dev_free(ww.scal);
-    dev_free(ww.flags);
-    dev_free(ww.bar);
-    dev_free(ww.xch);
-    free_wstep_pin(ww);
-    ww = WstepWorkspace{};
 }
 
 int validate(const rbl_config* c) {
@@ -371,14 +312,8 @@ int validate(const rbl_config* c) {
 
 int build_sigma_prefix(rbl_solver* h) {
     // sigma is static: its prefix sums are built once (pav.hip uses them every iteration)
-    RBL_TRY(launch_prefix(h->sigma_a, h->nt, h->locx_a, h->chunk_a, h->cph_a, h->cpl_a, h->stream));
-    h->pa = Prefix{h->locx_a, h->cph_a, h->cpl_a};
-    h->pb = h->pa;
-    if (h->cfg.weight_function == RBL_W_EHRM) {
-        RBL_TRY(launch_prefix(h->sigma_b, h->nt, h->locx_b, h->chunk_b, h->cph_b, h->cpl_b, h->stream));
-        h->pb = Prefix{h->locx_b, h->cph_b, h->cpl_b};
-    }
-    h->pm = Prefix{h->pw.locx_m, h->pw.cph_m, h->pw.cpl_m};
+    RBL_TRY(launch_prefix(h->sigma_a, h->nt, h->pfx_a, h->stream));
+    if (h->cfg.weight_function == RBL_W_EHRM) RBL_TRY(launch_prefix(h->sigma_b, h->nt, h->pfx_b, h->stream));
     return RBL_OK;
 }
 
@@ -419,14 +354,14 @@ int z_step_sorted(rbl_solver* h, const double* msrc, double rho, bool allow32 = 
         RBL_HIP(hipGetLastError());
         h->s32.used = true;
         h->s32.q_done = false;
-        RBL_TRY(launch_prefix(h->pw.ms, nt, h->pw.locx_m, h->pw.chunk_m, h->pw.cph_m, h->pw.cpl_m, s));
+        RBL_TRY(launch_prefix(h->pw.ms, nt, h->pw.pm, s));
         perm = h->sw.vals[1];
         h->sort_passes += 4;
     } else {
         // rbl_phase_m already formed the keys with m when it covers the whole problem (one pass instead of two)
         if (!(h->keys_ready && msrc == h->m && nt == h->n)) RBL_TRY(launch_keys_from_m(nt, msrc, h->sw.keys[0], h->sw.vals[0], s));
         RBL_TRY(launch_radix_sort(h->sw, nt, true, s));
-        RBL_TRY(launch_unflip_prefix(h->sw.keys[0], nt, h->pw.ms, h->pw.locx_m, h->pw.chunk_m, h->pw.cph_m, h->pw.cpl_m, s));
+        RBL_TRY(launch_unflip_prefix(h->sw.keys[0], nt, h->pw.ms, h->pw.pm, s));
         h->sort_passes += 8;
     }
     h->keys_ready = false;   // the sort consumes its input
@@ -451,8 +386,8 @@ int z_step_sorted(rbl_solver* h, const double* msrc, double rho, bool allow32 = 
     if (ehrm && !spec)
         RBL_TRY(launch_ehrm_branch(nt, h->sigma_a, h->sigma_b, h->cfg.B, rho, h->pw.ms, h->pw.partials, h->pw.branch,
                                    -1, s, u0a, u0b));
-    RBL_TRY(launch_pav_tree(h->cfg.loss, nt, rho, h->pw.ms, h->sigma_a, h->sigma_b, h->pw.u, h->pa, h->pb, h->pm,
-                            ehrm ? h->pw.branch : nullptr, h->pw.recs, h->pw.counters, s, u0a, u0b, &ex));
+    RBL_TRY(launch_pav_tree(h->cfg.loss, nt, rho, h->pw.ms, h->sigma_a, h->sigma_b, h->pw.u, h->pfx_a.view(), h->pfx_b.view(),
+                            h->pw.pm.view(), ehrm ? h->pw.branch : nullptr, h->pw.recs, h->pw.counters, s, u0a, u0b, &ex));
     h->pw.ex.bar_parity = ex.bar_parity;
     RBL_TRY(launch_scatter_z(nt, h->pw.u, perm, ehrm ? h->pw.branch : nullptr, h->cfg.B, ehrm ? 1 : 0, rho,
                              h->lam, h->z, nullptr, h->off, h->n, s));
@@ -472,22 +407,23 @@ int zb_setup(rbl_solver* h) {
     // collectives in between - rbl_zbd_*)
     if (!h->sorted_path || h->cfg.weight_function == RBL_W_EHRM || h->nt < min_n || h->nt < 16) return RBL_OK;
     constexpr int CAP = 16;
-    long long* pos_dev = nullptr;
-    int* cnt_dev = nullptr;
-    RBL_TRY(dev_alloc(&pos_dev, (size_t)CAP));
-    RBL_TRY(dev_alloc(&cnt_dev, (size_t)1));
-    int rc = launch_zb_edges(h->sigma_a, h->nt, pos_dev, cnt_dev, CAP, h->stream);
     long long pos[CAP];
     int cnt = 0;
-    if (rc == RBL_OK && (hipMemcpyAsync(&cnt, cnt_dev, sizeof(int), hipMemcpyDeviceToHost, h->stream) != hipSuccess ||
-                         hipMemcpyAsync(pos, pos_dev, sizeof(pos), hipMemcpyDeviceToHost, h->stream) != hipSuccess ||
-                         hipStreamSynchronize(h->stream) != hipSuccess))
-        rc = RBL_ERR_HIP;
-    dev_free(pos_dev);
-    dev_free(cnt_dev);
-    if (rc != RBL_OK) {
-        rbl_set_error("zband setup: reading the edges of sigma failed");
-        return rc;
+    {
+        DevArena tmp;   // the edge buffers, freed once read back
+        long long* pos_dev = nullptr;
+        int* cnt_dev = nullptr;
+        RBL_TRY(tmp.alloc(&pos_dev, (size_t)CAP));
+        RBL_TRY(tmp.alloc(&cnt_dev, (size_t)1));
+        int rc = launch_zb_edges(h->sigma_a, h->nt, pos_dev, cnt_dev, CAP, h->stream);
+        if (rc == RBL_OK && (hipMemcpyAsync(&cnt, cnt_dev, sizeof(int), hipMemcpyDeviceToHost, h->stream) != hipSuccess ||
+                             hipMemcpyAsync(pos, pos_dev, sizeof(pos), hipMemcpyDeviceToHost, h->stream) != hipSuccess ||
+                             hipStreamSynchronize(h->stream) != hipSuccess))
+            rc = RBL_ERR_HIP;
+        if (rc != RBL_OK) {
+            rbl_set_error("zband setup: reading the edges of sigma failed");
+            return rc;
+        }
     }
     if (cnt < 1 || cnt > ZB_MAX_BANDS - 1) return RBL_OK;   // constant weights never come here (erm); smooth families: sort
     std::sort(pos, pos + cnt);
@@ -529,15 +465,15 @@ int zb_setup(rbl_solver* h) {
         ++c.nclusters;
         L = j;
     }
-    RBL_TRY(dev_alloc(&h->zb.st, (size_t)1));
-    RBL_HIP(hipMemset(h->zb.st, 0, sizeof(ZbState)));
-    RBL_TRY(dev_alloc((unsigned char**)&h->zb.hist, zb_hist_bytes()));
-    RBL_TRY(dev_alloc((unsigned char**)&h->zb.part, zb_partials_bytes()));
-    RBL_TRY(dev_alloc(&h->zb.tot, (size_t)(4 * ZB_C)));
-    RBL_TRY(dev_alloc(&h->zb.pack, (size_t)(ZB_GCAP + 1)));
-    RBL_HIP(hipHostMalloc((void**)&h->zb.pin, 64, hipHostMallocDefault));
+    RBL_TRY(h->mem.alloc(&h->zb.st, (size_t)1));
+    RBL_HIP(hipMemsetAsync(h->zb.st, 0, sizeof(ZbState), h->stream));
+    RBL_TRY(h->mem.alloc((unsigned char**)&h->zb.hist, zb_hist_bytes()));
+    RBL_TRY(h->mem.alloc((unsigned char**)&h->zb.part, zb_partials_bytes()));
+    RBL_TRY(h->mem.alloc(&h->zb.tot, (size_t)(4 * ZB_C)));
+    RBL_TRY(h->mem.alloc(&h->zb.pack, (size_t)(ZB_GCAP + 1)));
+    RBL_TRY(h->mem.pinned(&h->zb.pin, 16, hipHostMallocDefault));
     for (int i = 0; i < 16; ++i) h->zb.pin[i] = 0;
-    h->zb.enabled = true;
+    h->zb.enabled = true;   // set last: the buffers above are all there
     return RBL_OK;
 }
 
@@ -579,33 +515,118 @@ int rbl_destroy(rbl_solver* h) {
     if (!h) return RBL_OK;
     (void)hipSetDevice(h->cfg.device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
-    dev_free(h->D); dev_free(h->w); dev_free(h->w_prev); dev_free(h->q); dev_free(h->G); dev_free(h->w_tmp);
-    dev_free(h->z); dev_free(h->lam); dev_free(h->v); dev_free(h->m); dev_free(h->c);
-    dev_free(h->sigma_a); dev_free(h->sigma_b); dev_free(h->slab); dev_free(h->partials);
-    if (h->red_owned) dev_free(h->red);
-    dev_free(h->red2); dev_free(h->ysign); dev_free(h->colstats); dev_free(h->z_next); dev_free(h->p); dev_free(h->p_alt); dev_free(h->pred);
-    if (h->hstat) (void)hipHostFree(h->hstat);
-    dev_free(h->zd_small); dev_free(h->zd_seam); dev_free(h->zd_err); dev_free(h->zd_bounds_dev); dev_free(h->zd_counts_dev); dev_free(h->zd_zids);
-    dev_free(h->zd_locx_a); dev_free(h->zd_chunk_a); dev_free(h->zd_cph_a); dev_free(h->zd_cpl_a);
-    dev_free(h->zd_locx_b); dev_free(h->zd_chunk_b); dev_free(h->zd_cph_b); dev_free(h->zd_cpl_b);
-    free_sort(h->sw);
-    free_pav(h->pw);
-    dev_free(h->zb.st); dev_free(h->zb.hist); dev_free(h->zb.part); dev_free(h->zb.tot); dev_free(h->zb.pack);
-    if (h->zb.pin) (void)hipHostFree(h->zb.pin);
-    if (h->s32.pin) (void)hipHostFree(h->s32.pin);
-    dev_free(h->s32.mm);
-    dev_free(h->s32.flag);
-    dev_free(h->locx_a); dev_free(h->chunk_a); dev_free(h->cph_a); dev_free(h->cpl_a);
-    dev_free(h->locx_b); dev_free(h->chunk_b); dev_free(h->cph_b); dev_free(h->cpl_b);
-    free_wstep(h->ww);
     for (auto& e : h->ev) if (e) (void)hipEventDestroy(e);
     for (auto& e : h->kev) if (e) (void)hipEventDestroy(e);
     for (auto& e : h->ev_spec) if (e) (void)hipEventDestroy(e);
     if (h->own_stream) (void)hipStreamDestroy(h->own_stream);
     if (h->counted) g_live[h->cfg.device].fetch_sub(1, std::memory_order_relaxed);
-    delete h;
+    delete h;   // h->mem frees every buffer
     return RBL_OK;
 }
+
+}  // extern "C"
+
+// everything rbl_create sets up past the checks of its arguments; on failure the caller destroys h
+static int create_setup(rbl_solver* h) {
+    const rbl_config* cfg = &h->cfg;
+    h->n = cfg->n;
+    h->d = cfg->d;
+    h->ld = round_up(cfg->d, 4);
+    h->nt = cfg->n_total;
+    h->off = cfg->row_offset;
+    h->storage = cfg->storage;
+    h->esz = cfg->storage == RBL_STORE_F32 ? 4 : 8;
+    h->sorted_path = cfg->weight_function != RBL_W_ERM;
+    // tol is taken literally, as the reference does (algorithms.py:137): tol <= 0 never reports convergence
+    if (h->cfg.w_tol <= 0.0) h->cfg.w_tol = 1e-13;
+    if (h->cfg.max_iter <= 0) h->cfg.max_iter = 200;
+    hipDeviceProp_t prop;
+    RBL_HIP(hipGetDeviceProperties(&prop, cfg->device));
+    h->num_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
+    RBL_HIP(hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking));
+    h->stream = h->own_stream;
+    for (auto& e : h->ev) RBL_HIP(hipEventCreate(&e));
+    for (auto& e : h->kev) RBL_HIP(hipEventCreate(&e));
+    for (auto& e : h->ev_spec) RBL_HIP(hipEventCreate(&e));
+    DevArena& mem = h->mem;
+    RBL_TRY(mem.pinned(&h->hstat, 16, hipHostMallocCoherent));
+    const int64_t n = h->n, ld = h->ld, nt = h->nt;
+    const size_t dbytes = (size_t)(n > 0 ? n : 1) * ld * h->esz;
+    if (mem.alloc((unsigned char**)&h->D, dbytes) != RBL_OK) {
+        rbl_set_error("hipMalloc of the %lld x %lld matrix (%zu bytes) failed: %s", (long long)n, (long long)ld, dbytes,
+                      hipGetErrorString(hipGetLastError()));
+        return RBL_ERR_NOMEM;
+    }
+    RBL_TRY(mem.alloc(&h->w, (size_t)ld));
+    RBL_TRY(mem.alloc(&h->w_tmp, (size_t)ld));
+    RBL_TRY(mem.alloc(&h->v, (size_t)n));
+    RBL_TRY(mem.alloc(&h->m, (size_t)n));
+    RBL_TRY(mem.alloc(&h->sigma_a, (size_t)nt));
+    RBL_TRY(mem.alloc(&h->sigma_b, (size_t)nt));
+    RBL_TRY(mem.alloc(&h->partials, (size_t)reduce_blocks() * 4));
+    if (cfg->objective_only) RBL_TRY(mem.alloc(&h->red, 8));
+    RBL_TRY(mem.alloc(&h->red2, 8));
+    RBL_TRY(mem.alloc(&h->ysign, (size_t)n));
+    RBL_TRY(mem.alloc(&h->colstats, (size_t)ld * 4));
+    h->slab_bytes = (size_t)gemvt_slab_rows(h->num_cu) * ld * sizeof(double) * 2;
+    if (!cfg->objective_only) {
+        size_t gb = gram_slab_bytes(ld, h->num_cu, n > 0 ? n : 1);
+        if (gb > h->slab_bytes) h->slab_bytes = gb;
+        RBL_TRY(mem.alloc(&h->w_prev, (size_t)ld));
+        // one exchange buffer, summed over ranks in at most one collective per iteration:
+        // [q (ld) | D^T lambda seed (ld) | ||z||^2 | primal^2 | sum loss]
+        RBL_TRY(mem.alloc(&h->q, (size_t)ld * 2 + 3));
+        h->red = h->q + 2 * ld + 1;
+        RBL_TRY(mem.alloc(&h->G, (size_t)ld * ld));
+        RBL_TRY(mem.alloc(&h->z, (size_t)n));
+        RBL_TRY(mem.alloc(&h->lam, (size_t)n));
+        RBL_TRY(mem.alloc(&h->c, (size_t)n));
+        RBL_TRY(alloc_wstep(mem, h->ww, ld, h->stream));
+    }
+    RBL_TRY(mem.alloc((unsigned char**)&h->slab, h->slab_bytes));
+    if (h->sorted_path) {
+        RBL_TRY(alloc_sort(mem, h->sw, nt, !cfg->objective_only, h->stream));
+        if (!cfg->objective_only) {
+            RBL_TRY(alloc_pav(mem, h->pw, nt, h->stream));
+            RBL_TRY(mem.alloc(&h->s32.mm, (size_t)s32_range_words()));
+            RBL_TRY(mem.alloc(&h->s32.flag, 1));
+            RBL_TRY(mem.pinned(&h->s32.pin, 16, hipHostMallocDefault));
+            for (int i = 0; i < 16; ++i) h->s32.pin[i] = 0;
+            RBL_TRY(alloc_prefix(mem, h->pfx_a, nt));
+            h->pfx_b = h->pfx_a;
+            if (cfg->weight_function == RBL_W_EHRM) RBL_TRY(alloc_prefix(mem, h->pfx_b, nt));
+        }
+    }
+    // sigma (objective.py:46-54): alphas, betas (= alphas unless ehrm)
+    RBL_TRY(launch_weights(cfg->weight_function, nt, cfg->weight_args, h->sigma_a, h->sigma_b, h->stream));
+    h->sigma0 = 1.0 / (double)nt;
+    if (h->sorted_path && !cfg->objective_only) RBL_TRY(build_sigma_prefix(h));
+    // initial state, algorithms.py:32-52 (n = num_row of the WHOLE problem)
+    RBL_HIP(hipMemsetAsync(h->w, 0, sizeof(double) * ld, h->stream));
+    RBL_HIP(hipMemsetAsync(h->w_tmp, 0, sizeof(double) * ld, h->stream));
+    if (!cfg->objective_only) {
+        const double reg = cfg->reg;
+        RBL_TRY(fill_const(h->lam, n, 0.1 * reg / (double)nt, h->stream));
+        RBL_TRY(fill_const(h->z, n, 0.1 * reg / (double)nt, h->stream));
+        RBL_TRY(fill_const(h->w, h->d, 0.001 * reg / (double)h->d / (double)nt, h->stream));
+        RBL_HIP(hipMemsetAsync(h->q, 0, sizeof(double) * (ld * 2 + 3), h->stream));
+        const char* nf = getenv("RBL_NO_FUSE");
+        h->fused_ok = !h->sorted_path && !(nf && nf[0] == '1') && sweep_erm_supported(h->storage, ld);
+        h->fuse_v = !h->fused_ok && !(nf && nf[0] == '1') && n > 0 && sweep_v_supported(h->storage, ld);
+        if (h->fused_ok) {
+            RBL_TRY(mem.alloc(&h->z_next, (size_t)n));
+            RBL_TRY(mem.alloc(&h->p, (size_t)ld));
+            RBL_TRY(mem.alloc(&h->p_alt, (size_t)ld));
+            RBL_TRY(mem.alloc(&h->pred, 2));
+        }
+        h->rho = cfg->rho0 > 0.0 ? cfg->rho0 : default_rho(cfg->weight_function);
+        h->smooth_t = cfg->smooth_t > 0.0 ? cfg->smooth_t : 1.0;
+    }
+    RBL_HIP(hipStreamSynchronize(h->stream));
+    return RBL_OK;
+}
+
+extern "C" {
 
 int rbl_create(const rbl_config* cfg, rbl_solver** out) {
     if (!out) {
@@ -627,140 +648,13 @@ int rbl_create(const rbl_config* cfg, rbl_solver** out) {
         g_live[cfg->device].fetch_add(1, std::memory_order_relaxed);
         h->counted = true;
     }
-    h->n = cfg->n;
-    h->d = cfg->d;
-    h->ld = round_up(cfg->d, 4);
-    h->nt = cfg->n_total;
-    h->off = cfg->row_offset;
-    h->storage = cfg->storage;
-    h->esz = cfg->storage == RBL_STORE_F32 ? 4 : 8;
-    h->sorted_path = cfg->weight_function != RBL_W_ERM;
-    // tol is taken literally, as the reference does (algorithms.py:137): tol <= 0 never reports convergence
-    if (h->cfg.w_tol <= 0.0) h->cfg.w_tol = 1e-13;
-    if (h->cfg.max_iter <= 0) h->cfg.max_iter = 200;
-    hipDeviceProp_t prop;
-    int rc = RBL_OK;
-#define CK(x)                        \
-    do {                             \
-        rc = (x);                    \
-        if (rc != RBL_OK) goto fail; \
-    } while (0)
-#define CKH(x)                                                                          \
-    do {                                                                                \
-        hipError_t e_ = (x);                                                            \
-        if (e_ != hipSuccess) {                                                         \
-            rbl_set_error("%s:%d: %s -> %s", __FILE__, __LINE__, #x, hipGetErrorString(e_)); \
-            rc = RBL_ERR_HIP;                                                           \
-            goto fail;                                                                  \
-        }                                                                               \
-    } while (0)
-    CKH(hipGetDeviceProperties(&prop, cfg->device));
-    h->num_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-    CKH(hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking));
-    h->stream = h->own_stream;
-    for (auto& e : h->ev) CKH(hipEventCreate(&e));
-    for (auto& e : h->kev) CKH(hipEventCreate(&e));
-    for (auto& e : h->ev_spec) CKH(hipEventCreate(&e));
-    {
-        void* hs = nullptr;
-        CKH(hipHostMalloc(&hs, 16 * sizeof(double), hipHostMallocCoherent));
-        h->hstat = (double*)hs;
+    const int rc = create_setup(h);
+    if (rc != RBL_OK) {
+        rbl_destroy(h);
+        return rc;
     }
-    {
-        const int64_t n = h->n, ld = h->ld, nt = h->nt;
-        void* Dp = nullptr;
-        {
-            size_t bytes = (size_t)(n > 0 ? n : 1) * ld * h->esz;
-            hipError_t e = hipMalloc(&Dp, bytes);
-            if (e != hipSuccess) {
-                rbl_set_error("hipMalloc of the %lld x %lld matrix (%zu bytes) failed: %s", (long long)n,
-                              (long long)ld, bytes, hipGetErrorString(e));
-                rc = RBL_ERR_NOMEM;
-                goto fail;
-            }
-        }
-        h->D = Dp;
-        CK(dev_alloc(&h->w, (size_t)ld));
-        CK(dev_alloc(&h->w_tmp, (size_t)ld));
-        CK(dev_alloc(&h->v, (size_t)n));
-        CK(dev_alloc(&h->m, (size_t)n));
-        CK(dev_alloc(&h->sigma_a, (size_t)nt));
-        CK(dev_alloc(&h->sigma_b, (size_t)nt));
-        CK(dev_alloc(&h->partials, (size_t)reduce_blocks() * 4));
-        if (cfg->objective_only) {
-            CK(dev_alloc(&h->red, 8));
-            h->red_owned = true;
-        }
-        CK(dev_alloc(&h->red2, 8));
-        CK(dev_alloc(&h->ysign, (size_t)n));
-        CK(dev_alloc(&h->colstats, (size_t)ld * 4));
-        h->slab_bytes = (size_t)gemvt_slab_rows(h->num_cu) * ld * sizeof(double) * 2;
-        if (!cfg->objective_only) {
-            size_t gb = gram_slab_bytes(ld, h->num_cu, n > 0 ? n : 1);
-            if (gb > h->slab_bytes) h->slab_bytes = gb;
-            CK(dev_alloc(&h->w_prev, (size_t)ld));
-            // one exchange buffer, summed over ranks in at most one collective per iteration:
-            // [q (ld) | D^T lambda seed (ld) | ||z||^2 | primal^2 | sum loss]
-            CK(dev_alloc(&h->q, (size_t)ld * 2 + 3));
-            h->red = h->q + 2 * ld + 1;
-            CK(dev_alloc(&h->G, (size_t)ld * ld));
-            CK(dev_alloc(&h->z, (size_t)n));
-            CK(dev_alloc(&h->lam, (size_t)n));
-            CK(dev_alloc(&h->c, (size_t)n));
-            CK(alloc_wstep(h->ww, ld));
-        }
-        CK(dev_alloc((unsigned char**)&h->slab, h->slab_bytes));
-        if (h->sorted_path) {
-            CK(alloc_sort(h->sw, nt, !cfg->objective_only));
-            if (!cfg->objective_only) {
-                CK(alloc_pav(h->pw, nt));
-                CK(dev_alloc(&h->s32.mm, (size_t)s32_range_words()));
-                CK(dev_alloc(&h->s32.flag, 1));
-                CKH(hipHostMalloc((void**)&h->s32.pin, 64, hipHostMallocDefault));
-                for (int i = 0; i < 16; ++i) h->s32.pin[i] = 0;
-                CK(alloc_prefix(&h->locx_a, &h->chunk_a, &h->cph_a, &h->cpl_a, nt));
-                if (cfg->weight_function == RBL_W_EHRM)
-                    CK(alloc_prefix(&h->locx_b, &h->chunk_b, &h->cph_b, &h->cpl_b, nt));
-            }
-        }
-        // sigma (objective.py:46-54): alphas, betas (= alphas unless ehrm)
-        CK(launch_weights(cfg->weight_function, nt, cfg->weight_args, h->sigma_a, h->sigma_b, h->stream));
-        h->sigma0 = 1.0 / (double)nt;
-        if (h->sorted_path && !cfg->objective_only) CK(build_sigma_prefix(h));
-        // initial state, algorithms.py:32-52 (n = num_row of the WHOLE problem)
-        CKH(hipMemsetAsync(h->w, 0, sizeof(double) * ld, h->stream));
-        CKH(hipMemsetAsync(h->w_tmp, 0, sizeof(double) * ld, h->stream));
-        if (!cfg->objective_only) {
-            const double reg = cfg->reg;
-            CK(fill_const(h->lam, n, 0.1 * reg / (double)nt, h->stream));
-            CK(fill_const(h->z, n, 0.1 * reg / (double)nt, h->stream));
-            CK(fill_const(h->w, h->d, 0.001 * reg / (double)h->d / (double)nt, h->stream));
-            CKH(hipMemsetAsync(h->q, 0, sizeof(double) * (ld * 2 + 3), h->stream));
-            {
-                const char* nf = getenv("RBL_NO_FUSE");
-                h->fused_ok = !h->sorted_path && !(nf && nf[0] == '1') && sweep_erm_supported(h->storage, ld);
-                h->fuse_v = !h->fused_ok && !(nf && nf[0] == '1') && n > 0 && sweep_v_supported(h->storage, ld);
-                if (h->fused_ok) {
-                    CK(dev_alloc(&h->z_next, (size_t)n));
-                    CK(dev_alloc(&h->p, (size_t)ld));
-                    CK(dev_alloc(&h->p_alt, (size_t)ld));
-                    CK(dev_alloc(&h->pred, 2));
-                    size_t sb = (size_t)sweep_erm_blocks(h->num_cu) * ld * sizeof(double);
-                    (void)sb;
-                }
-            }
-            h->rho = cfg->rho0 > 0.0 ? cfg->rho0 : default_rho(cfg->weight_function);
-            h->smooth_t = cfg->smooth_t > 0.0 ? cfg->smooth_t : 1.0;
-        }
-        CKH(hipStreamSynchronize(h->stream));
-    }
-#undef CK
-#undef CKH
     *out = h;
     return RBL_OK;
-fail:
-    rbl_destroy(h);
-    return rc;
 }
 
 // Entry of the functions that advance the iteration (phases, step, solve) or only read handle
@@ -885,60 +779,62 @@ int rbl_set_data(rbl_solver* h, const double* X, const double* y, int64_t ldx) {
         const size_t xbytes = sizeof(double) * (size_t)n * (size_t)ldx;
         const bool pinned = hipHostRegister(const_cast<double*>(X), xbytes, hipHostRegisterDefault) == hipSuccess;
         if (!pinned) (void)hipGetLastError();
-        double *Xd[2] = {nullptr, nullptr}, *yd = nullptr;
-        hipStream_t copy_stream = nullptr;
-        hipEvent_t copied[2] = {nullptr, nullptr}, formed[2] = {nullptr, nullptr};
         int rc = RBL_OK;
-        auto cleanup = [&]() {
-            dev_free(Xd[0]); dev_free(Xd[1]); dev_free(yd);
-            for (int k = 0; k < 2; ++k) {
-                if (copied[k]) (void)hipEventDestroy(copied[k]);
-                if (formed[k]) (void)hipEventDestroy(formed[k]);
+        {
+            DevArena tmp;   // the staging buffers, freed at the end of this block (after the last stream wait)
+            double *Xd[2] = {nullptr, nullptr}, *yd = nullptr;
+            hipStream_t copy_stream = nullptr;
+            hipEvent_t copied[2] = {nullptr, nullptr}, formed[2] = {nullptr, nullptr};
+            auto cleanup = [&]() {
+                for (int k = 0; k < 2; ++k) {
+                    if (copied[k]) (void)hipEventDestroy(copied[k]);
+                    if (formed[k]) (void)hipEventDestroy(formed[k]);
+                }
+                if (copy_stream) (void)hipStreamDestroy(copy_stream);
+                if (pinned) (void)hipHostUnregister(const_cast<double*>(X));
+            };
+            if (tmp.alloc(&Xd[0], (size_t)chunk * ldx) != RBL_OK || tmp.alloc(&Xd[1], (size_t)chunk * ldx) != RBL_OK ||
+                tmp.alloc(&yd, (size_t)n) != RBL_OK) {
+                cleanup();
+                return RBL_ERR_NOMEM;
             }
-            if (copy_stream) (void)hipStreamDestroy(copy_stream);
-            if (pinned) (void)hipHostUnregister(const_cast<double*>(X));
-        };
-        if (dev_alloc(&Xd[0], (size_t)chunk * ldx) != RBL_OK || dev_alloc(&Xd[1], (size_t)chunk * ldx) != RBL_OK ||
-            dev_alloc(&yd, (size_t)n) != RBL_OK) {
+            bool ok = hipStreamCreateWithFlags(&copy_stream, hipStreamNonBlocking) == hipSuccess;
+            for (int k = 0; k < 2 && ok; ++k)
+                ok = hipEventCreateWithFlags(&copied[k], hipEventDisableTiming) == hipSuccess &&
+                     hipEventCreateWithFlags(&formed[k], hipEventDisableTiming) == hipSuccess;
+            ok = ok && hipMemcpyAsync(yd, y, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, h->stream) == hipSuccess;
+            ok = ok && hipStreamSynchronize(h->stream) == hipSuccess;
+            if (!ok) {
+                rbl_set_error("set_data: stream / event / label upload failed: %s", hipGetErrorString(hipGetLastError()));
+                cleanup();
+                return RBL_ERR_HIP;
+            }
+            int64_t k = 0;
+            for (int64_t r0 = 0; r0 < n && rc == RBL_OK; r0 += chunk, ++k) {
+                const int64_t rows = n - r0 < chunk ? n - r0 : chunk;
+                const int b = (int)(k & 1);
+                hipError_t e = hipSuccess;
+                if (k >= 2) e = hipStreamWaitEvent(copy_stream, formed[b], 0);   // staging buffer b has been consumed
+                if (e == hipSuccess)
+                    e = hipMemcpyAsync(Xd[b], X + r0 * ldx, sizeof(double) * rows * ldx, hipMemcpyHostToDevice, copy_stream);
+                if (e == hipSuccess) e = hipEventRecord(copied[b], copy_stream);
+                if (e == hipSuccess) e = hipStreamWaitEvent(h->stream, copied[b], 0);
+                if (e != hipSuccess) {
+                    rbl_set_error("set_data: upload failed: %s", hipGetErrorString(e));
+                    rc = RBL_ERR_HIP;
+                    break;
+                }
+                rc = launch_form_D(h->storage, h->D, h->ld, r0, Xd[b], ldx, yd + r0, rows, d, h->stream);
+                if (rc == RBL_OK && hipEventRecord(formed[b], h->stream) != hipSuccess) rc = RBL_ERR_HIP;
+            }
+            if (hipStreamSynchronize(copy_stream) != hipSuccess || hipStreamSynchronize(h->stream) != hipSuccess) {
+                if (rc == RBL_OK) {
+                    rbl_set_error("set_data: %s", hipGetErrorString(hipGetLastError()));
+                    rc = RBL_ERR_HIP;
+                }
+            }
             cleanup();
-            return RBL_ERR_NOMEM;
         }
-        bool ok = hipStreamCreateWithFlags(&copy_stream, hipStreamNonBlocking) == hipSuccess;
-        for (int k = 0; k < 2 && ok; ++k)
-            ok = hipEventCreateWithFlags(&copied[k], hipEventDisableTiming) == hipSuccess &&
-                 hipEventCreateWithFlags(&formed[k], hipEventDisableTiming) == hipSuccess;
-        ok = ok && hipMemcpyAsync(yd, y, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, h->stream) == hipSuccess;
-        ok = ok && hipStreamSynchronize(h->stream) == hipSuccess;
-        if (!ok) {
-            rbl_set_error("set_data: stream / event / label upload failed: %s", hipGetErrorString(hipGetLastError()));
-            cleanup();
-            return RBL_ERR_HIP;
-        }
-        int64_t k = 0;
-        for (int64_t r0 = 0; r0 < n && rc == RBL_OK; r0 += chunk, ++k) {
-            const int64_t rows = n - r0 < chunk ? n - r0 : chunk;
-            const int b = (int)(k & 1);
-            hipError_t e = hipSuccess;
-            if (k >= 2) e = hipStreamWaitEvent(copy_stream, formed[b], 0);   // staging buffer b has been consumed
-            if (e == hipSuccess)
-                e = hipMemcpyAsync(Xd[b], X + r0 * ldx, sizeof(double) * rows * ldx, hipMemcpyHostToDevice, copy_stream);
-            if (e == hipSuccess) e = hipEventRecord(copied[b], copy_stream);
-            if (e == hipSuccess) e = hipStreamWaitEvent(h->stream, copied[b], 0);
-            if (e != hipSuccess) {
-                rbl_set_error("set_data: upload failed: %s", hipGetErrorString(e));
-                rc = RBL_ERR_HIP;
-                break;
-            }
-            rc = launch_form_D(h->storage, h->D, h->ld, r0, Xd[b], ldx, yd + r0, rows, d, h->stream);
-            if (rc == RBL_OK && hipEventRecord(formed[b], h->stream) != hipSuccess) rc = RBL_ERR_HIP;
-        }
-        if (hipStreamSynchronize(copy_stream) != hipSuccess || hipStreamSynchronize(h->stream) != hipSuccess) {
-            if (rc == RBL_OK) {
-                rbl_set_error("set_data: %s", hipGetErrorString(hipGetLastError()));
-                rc = RBL_ERR_HIP;
-            }
-        }
-        cleanup();
         RBL_TRY(rc);
         std::vector<signed char> ys((size_t)n);
         for (int64_t i = 0; i < n; ++i) ys[(size_t)i] = y[i] > 0 ? 1 : -1;
@@ -1068,20 +964,24 @@ int rbl_gram_finish(rbl_solver* h) {
     if (h->cfg.wstep == RBL_WSTEP_L2 && h->ld <= 2048 && ridge_eig) {
         const size_t nn = (size_t)h->ld * (size_t)h->ld;
         if (!h->ww.eig_Vt) {
-            RBL_TRY(dev_alloc(&h->ww.eig_Vt, nn));
-            RBL_TRY(dev_alloc(&h->ww.eig_V, nn));
-            RBL_TRY(dev_alloc(&h->ww.eig_lambda, (size_t)h->ld));
+            double *Vt = nullptr, *V = nullptr, *lambda = nullptr;
+            RBL_TRY(h->mem.alloc(&Vt, nn));
+            RBL_TRY(h->mem.alloc(&V, nn));
+            RBL_TRY(h->mem.alloc(&lambda, (size_t)h->ld));
+            h->ww.eig_V = V;
+            h->ww.eig_lambda = lambda;
+            h->ww.eig_Vt = Vt;   // set last: it says the basis buffers are there
         }
-        double* Bt = nullptr;
-        unsigned long long* off = nullptr;
-        RBL_TRY(dev_alloc(&Bt, nn));
-        int rc = dev_alloc(&off, 1);
-        int sweeps = 0;
-        if (rc == RBL_OK)
+        int rc = RBL_OK, sweeps = 0;
+        {
+            DevArena tmp;   // Jacobi scratch, freed after the stream wait
+            double* Bt = nullptr;
+            unsigned long long* off = nullptr;
+            RBL_TRY(tmp.alloc(&Bt, nn));
+            RBL_TRY(tmp.alloc(&off, 1));
             rc = launch_eig_jacobi(h->G, h->ld, h->d, Bt, h->ww.eig_Vt, h->ww.eig_V, h->ww.eig_lambda, off, h->stream, &sweeps);
-        (void)hipStreamSynchronize(h->stream);
-        dev_free(Bt);
-        dev_free(off);
+            (void)hipStreamSynchronize(h->stream);
+        }
         RBL_TRY(rc);
         h->ww.eig_ok = sweeps > 0;
         h->eig_sweeps = sweeps;
@@ -1099,19 +999,17 @@ int rbl_get_D(rbl_solver* h, double* out) {
     const int64_t n = h->n, d = h->d;
     int64_t chunk = (64LL << 20) / (8 * d);
     if (chunk < 1) chunk = 1;
+    DevArena mem;   // the conversion buffer, freed on return
     double* tmp = nullptr;
-    RBL_TRY(dev_alloc(&tmp, (size_t)chunk * d));
-    int rc = RBL_OK;
-    for (int64_t r0 = 0; r0 < n && rc == RBL_OK; r0 += chunk) {
+    RBL_TRY(mem.alloc(&tmp, (size_t)chunk * d));
+    for (int64_t r0 = 0; r0 < n; r0 += chunk) {
         const int64_t rows = n - r0 < chunk ? n - r0 : chunk;
-        rc = launch_D_to_f64(h->storage, (const char*)h->D + (size_t)r0 * h->ld * h->esz, h->ld, rows, d, tmp, h->stream);
-        if (rc == RBL_OK &&
-            hipMemcpyAsync(out + r0 * d, tmp, sizeof(double) * rows * d, hipMemcpyDeviceToHost, h->stream) != hipSuccess)
-            rc = RBL_ERR_HIP;
-        if (rc == RBL_OK && hipStreamSynchronize(h->stream) != hipSuccess) rc = RBL_ERR_HIP;
+        RBL_TRY(launch_D_to_f64(h->storage, (const char*)h->D + (size_t)r0 * h->ld * h->esz, h->ld, rows, d, tmp, h->stream));
+        if (hipMemcpyAsync(out + r0 * d, tmp, sizeof(double) * rows * d, hipMemcpyDeviceToHost, h->stream) != hipSuccess ||
+            hipStreamSynchronize(h->stream) != hipSuccess)
+            return RBL_ERR_HIP;
     }
-    dev_free(tmp);
-    return rc;
+    return RBL_OK;
 }
 
 int rbl_get_state(rbl_solver* h, double* w, double* z, double* lam, double* rho, int64_t* iter, double* smooth_t) {
@@ -1754,20 +1652,19 @@ int zd_ensure(rbl_solver* h) {
         rbl_set_error("distributed z-step: only for rank-weighted solver handles");
         return RBL_ERR_STATE;
     }
-    RBL_TRY(dev_alloc(&h->zd_small, ZD_SMALL_DOUBLES));
-    RBL_TRY(dev_alloc(&h->zd_seam, 1));
-    RBL_TRY(dev_alloc(&h->zd_err, 1));
-    RBL_TRY(dev_alloc(&h->zd_bounds_dev, 80));
-    RBL_TRY(dev_alloc(&h->zd_counts_dev, 64));
-    RBL_TRY(dev_alloc(&h->zd_zids, (size_t)h->n));
-    RBL_TRY(alloc_prefix(&h->zd_locx_a, &h->zd_chunk_a, &h->zd_cph_a, &h->zd_cpl_a, h->nt));
-    h->zpa = Prefix{h->zd_locx_a, h->zd_cph_a, h->zd_cpl_a};
-    h->zpb = h->zpa;
-    if (h->cfg.weight_function == RBL_W_EHRM) {
-        RBL_TRY(alloc_prefix(&h->zd_locx_b, &h->zd_chunk_b, &h->zd_cph_b, &h->zd_cpl_b, h->nt));
-        h->zpb = Prefix{h->zd_locx_b, h->zd_cph_b, h->zd_cpl_b};
-    }
+    DevArena& mem = h->mem;
+    double* small = nullptr;
+    RBL_TRY(mem.alloc(&small, ZD_SMALL_DOUBLES));
+    RBL_TRY(mem.alloc(&h->zd_seam, 1));
+    RBL_TRY(mem.alloc(&h->zd_err, 1));
+    RBL_TRY(mem.alloc(&h->zd_bounds_dev, 80));
+    RBL_TRY(mem.alloc(&h->zd_counts_dev, 64));
+    RBL_TRY(mem.alloc(&h->zd_zids, (size_t)h->n));
+    RBL_TRY(alloc_prefix(mem, h->zd_a, h->nt));
+    h->zd_b = h->zd_a;
+    if (h->cfg.weight_function == RBL_W_EHRM) RBL_TRY(alloc_prefix(mem, h->zd_b, h->nt));
     RBL_HIP(hipMemsetAsync(h->zd_err, 0, sizeof(int), h->stream));
+    h->zd_small = small;   // set last: it says the group is there
     return RBL_OK;
 }
 }  // namespace
@@ -1867,12 +1764,12 @@ int rbl_zd_prepare(rbl_solver* h, int64_t nrecv, int64_t sigma_off) {
     h->zd_n = nrecv;
     h->zd_off = sigma_off;
     RBL_TRY(launch_radix_sort(h->sw, nrecv, true, s));   // runs arrive in rank order: stable => ties in row order
-    RBL_TRY(launch_unflip_prefix(h->sw.keys[0], nrecv, h->pw.ms, h->pw.locx_m, h->pw.chunk_m, h->pw.cph_m, h->pw.cpl_m, s));
-    RBL_TRY(launch_prefix(h->sigma_a + sigma_off, nrecv, h->zd_locx_a, h->zd_chunk_a, h->zd_cph_a, h->zd_cpl_a, s));
+    RBL_TRY(launch_unflip_prefix(h->sw.keys[0], nrecv, h->pw.ms, h->pw.pm, s));
+    RBL_TRY(launch_prefix(h->sigma_a + sigma_off, nrecv, h->zd_a, s));
     const bool ehrm = h->cfg.weight_function == RBL_W_EHRM;
     double* fv = h->zd_small + ZD_OFF_FV;
     if (ehrm) {
-        RBL_TRY(launch_prefix(h->sigma_b + sigma_off, nrecv, h->zd_locx_b, h->zd_chunk_b, h->zd_cph_b, h->zd_cpl_b, s));
+        RBL_TRY(launch_prefix(h->sigma_b + sigma_off, nrecv, h->zd_b, s));
         RBL_TRY(launch_ehrm_fvals(nrecv, h->sigma_a + sigma_off, h->sigma_b + sigma_off, h->cfg.B, h->step_rho, h->pw.ms,
                                   h->pw.partials, fv, s, h->pw.u, (double*)h->sw.keys[1]));
     } else {
@@ -1886,12 +1783,12 @@ int rbl_zd_pav(rbl_solver* h, const void* fvals_total_dev) {
     hipStream_t s = h->stream;
     const bool ehrm = h->cfg.weight_function == RBL_W_EHRM;
     if (ehrm) RBL_TRY(launch_ehrm_pick((const double*)fvals_total_dev, h->pw.branch, s));
-    const Prefix pm{h->pw.locx_m, h->pw.cph_m, h->pw.cpl_m};
     PavExtras ex = h->pw.ex;      // the chunk's upper levels in one launch; the branch comes from the sums over ALL ranks
     ex.num_cu = h->num_cu;
     ex.fpart = nullptr;
     RBL_TRY(launch_pav_tree(h->cfg.loss, h->zd_n, h->step_rho, h->pw.ms, h->sigma_a + h->zd_off, h->sigma_b + h->zd_off,
-                            h->pw.u, h->zpa, h->zpb, pm, ehrm ? h->pw.branch : nullptr, h->pw.recs, h->pw.counters, s,
+                            h->pw.u, h->zd_a.view(), h->zd_b.view(), h->pw.pm.view(), ehrm ? h->pw.branch : nullptr, h->pw.recs,
+                            h->pw.counters, s,
                             ehrm ? h->pw.u : nullptr, ehrm ? (const double*)h->sw.keys[1] : nullptr, &ex));
     h->pw.ex.bar_parity = ex.bar_parity;
     return RBL_OK;
@@ -1920,8 +1817,8 @@ int rbl_zd_seam_eval(rbl_solver* h, int K, const void* cand_all_dev) {
     RBL_ENTER_ITER(h);
     if (K < 1 || K > 64 || K * h->zd_world > ZD_MAX_CAND) return RBL_ERR_INVALID;
     const bool ehrm = h->cfg.weight_function == RBL_W_EHRM;
-    const Prefix pm{h->pw.locx_m, h->pw.cph_m, h->pw.cpl_m};
-    return launch_zd_eval(h->zd_seam, h->pw.u, h->zpa, h->zpb, pm, ehrm ? h->pw.branch : nullptr, K, h->zd_world,
+    return launch_zd_eval(h->zd_seam, h->pw.u, h->zd_a.view(), h->zd_b.view(), h->pw.pm.view(), ehrm ? h->pw.branch : nullptr, K,
+                          h->zd_world,
                           (const double*)cand_all_dev, h->zd_small + ZD_OFF_PART, h->stream);
 }
 
@@ -1931,8 +1828,7 @@ int rbl_zd_seam_sums(rbl_solver* h, int K, const void* cand_all_prev, const void
     RBL_TRY(launch_zd_update_propose(h->cfg.loss, h->zd_seam, h->pw.u, K, h->zd_world, (const double*)cand_all_prev,
                                      (const double*)part_sum_prev, h->step_rho, nullptr, h->stream));
     const bool ehrm = h->cfg.weight_function == RBL_W_EHRM;
-    const Prefix pm{h->pw.locx_m, h->pw.cph_m, h->pw.cpl_m};
-    return launch_zd_pooled(h->zd_seam, h->zpa, h->zpb, pm, ehrm ? h->pw.branch : nullptr, nseams,
+    return launch_zd_pooled(h->zd_seam, h->zd_a.view(), h->zd_b.view(), h->pw.pm.view(), ehrm ? h->pw.branch : nullptr, nseams,
                             h->zd_small + ZD_OFF_SUMS, h->zd_err, h->stream);
 }
 
@@ -2187,28 +2083,25 @@ int rbl_fair_statistics(rbl_solver* h, const double* w, const double* group, dou
         rbl_set_error("fair_statistics: no data or NULL argument");
         return RBL_ERR_STATE;
     }
-    double* gd = nullptr;
-    RBL_TRY(dev_alloc(&gd, (size_t)h->n));
-    int rc = RBL_OK;
     double c[14];
-    do {
+    {
+        DevArena mem;   // the group vector, freed after the readback
+        double* gd = nullptr;
+        RBL_TRY(mem.alloc(&gd, (size_t)h->n));
         if (hipMemcpyAsync(gd, group, sizeof(double) * h->n, hipMemcpyHostToDevice, h->stream) != hipSuccess ||
             hipMemcpyAsync(h->w_tmp, w, sizeof(double) * h->d, hipMemcpyHostToDevice, h->stream) != hipSuccess) {
             rbl_set_error("fair_statistics: upload failed");
-            rc = RBL_ERR_HIP;
-            break;
+            return RBL_ERR_HIP;
         }
-        if ((rc = launch_gemv(h->storage, h->D, h->n, h->ld, h->w_tmp, h->m, h->num_cu, h->stream)) != RBL_OK) break;
+        RBL_TRY(launch_gemv(h->storage, h->D, h->n, h->ld, h->w_tmp, h->m, h->num_cu, h->stream));
         double* out14 = h->slab;  // scratch (>= 14 doubles)
-        if ((rc = launch_fair_counts(h->n, h->m, h->ysign, gd, threshold, h->partials, out14, h->stream)) != RBL_OK) break;
+        RBL_TRY(launch_fair_counts(h->n, h->m, h->ysign, gd, threshold, h->partials, out14, h->stream));
         if (hipMemcpyAsync(c, out14, sizeof(double) * 14, hipMemcpyDeviceToHost, h->stream) != hipSuccess ||
             hipStreamSynchronize(h->stream) != hipSuccess) {
             rbl_set_error("fair_statistics: readback failed");
-            rc = RBL_ERR_HIP;
+            return RBL_ERR_HIP;
         }
-    } while (0);
-    dev_free(gd);
-    RBL_TRY(rc);
+    }
     // fair_metric.py:11-41, group 0 = G1, group 1 = G2
     const double G1P = c[1] / c[0], G2P = c[7] / c[6];
     const double G1TP = c[2], G1FN = c[3], G1TN = c[4], G1FP = c[5];
@@ -2251,26 +2144,19 @@ int rbl_info(rbl_solver* h, int64_t* ld, int* num_cu, double* lipschitz) {
 }  // extern "C"
 
 // =================================================== kernel-level entry points (host buffers)
+// They run on the same workspace allocators as the solver handle (alloc_sort, alloc_pav, alloc_prefix, alloc_wstep).
 namespace {
-struct Scratch {
-    std::vector<void*> ptrs;
+struct Scratch {   // the buffers and the stream of one call
+    DevArena mem;
     hipStream_t s = nullptr;
     ~Scratch() {
-        for (void* p : ptrs) dev_free(p);
         if (s) (void)hipStreamDestroy(s);
     }
     template <typename T>
-    T* alloc(size_t count) {
-        T* p = nullptr;
-        if (dev_alloc(&p, count) != RBL_OK) return nullptr;
-        ptrs.push_back(p);
-        return p;
-    }
-    template <typename T>
-    T* upload(const T* host, size_t count) {
-        T* p = alloc<T>(count);
-        if (p && count && hipMemcpy(p, host, count * sizeof(T), hipMemcpyHostToDevice) != hipSuccess) return nullptr;
-        return p;
+    int upload(T** p, const T* host, size_t count) {
+        RBL_TRY(mem.alloc(p, count));
+        if (count) RBL_HIP(hipMemcpy(*p, host, count * sizeof(T), hipMemcpyHostToDevice));
+        return RBL_OK;
     }
 };
 
@@ -2287,14 +2173,6 @@ int scratch_begin(Scratch& sc, int* num_cu) {
     return RBL_OK;
 }
 
-#define SC_CHECK(p)                                          \
-    do {                                                     \
-        if (!(p)) {                                          \
-            rbl_set_error("scratch allocation/upload failed"); \
-            return RBL_ERR_NOMEM;                            \
-        }                                                    \
-    } while (0)
-
 // D (host fp64 n x d) -> device storage with ld padding
 int upload_matrix(Scratch& sc, int storage, int64_t n, int64_t d, const double* D, void** Dd, int64_t* ld_out) {
     const int64_t ld = round_up(d, 4);
@@ -2305,9 +2183,7 @@ int upload_matrix(Scratch& sc, int storage, int64_t n, int64_t d, const double* 
             if (storage == RBL_STORE_F32) ((float*)host.data())[r * ld + j] = (float)D[r * d + j];
             else ((double*)host.data())[r * ld + j] = D[r * d + j];
         }
-    unsigned char* p = sc.upload<unsigned char>(host.data(), host.size());
-    SC_CHECK(p);
-    *Dd = p;
+    RBL_TRY(sc.upload((unsigned char**)Dd, host.data(), host.size()));
     *ld_out = ld;
     return RBL_OK;
 }
@@ -2319,10 +2195,10 @@ int rbl_k_prox(int loss, int64_t n, const double* sigma, double rho, const doubl
     Scratch sc;
     RBL_TRY(scratch_begin(sc, nullptr));
     if (n <= 0) return RBL_OK;
-    double* ds = sc.upload(sigma, (size_t)n);
-    double* dm = sc.upload(m, (size_t)n);
-    double* dout = sc.alloc<double>((size_t)n);
-    SC_CHECK(ds && dm && dout);
+    double *ds = nullptr, *dm = nullptr, *dout = nullptr;
+    RBL_TRY(sc.upload(&ds, sigma, (size_t)n));
+    RBL_TRY(sc.upload(&dm, m, (size_t)n));
+    RBL_TRY(sc.mem.alloc(&dout, (size_t)n));
     RBL_TRY(launch_prox(loss, n, ds, rho, dm, dout, sc.s));
     RBL_HIP(hipMemcpyAsync(out, dout, sizeof(double) * n, hipMemcpyDeviceToHost, sc.s));
     RBL_HIP(hipStreamSynchronize(sc.s));
@@ -2333,20 +2209,11 @@ int rbl_k_sort(int64_t n, const double* keys, double* sorted_keys, uint32_t* per
     Scratch sc;
     RBL_TRY(scratch_begin(sc, nullptr));
     if (n <= 0) return RBL_OK;
-    double* dk = sc.upload(keys, (size_t)n);
-    SC_CHECK(dk);
+    double *dk = nullptr, *ms = nullptr;
+    RBL_TRY(sc.upload(&dk, keys, (size_t)n));
     SortWorkspace sw{};
-    sw.keys[0] = sc.alloc<u64>((size_t)n);
-    sw.keys[1] = sc.alloc<u64>((size_t)n);
-    sw.vals[0] = sc.alloc<u32>((size_t)n);
-    sw.vals[1] = sc.alloc<u32>((size_t)n);
-    sw.spine = (u32*)sc.alloc<unsigned char>(sort_spine_bytes());
-    sw.bin_total = sc.alloc<u32>(256);
-    sw.bin_base = sc.alloc<u32>(256);
-    sw.ghist = (u32*)sc.alloc<unsigned char>(sort_ghist_bytes());
-    double* ms = sc.alloc<double>((size_t)n);
-    SC_CHECK(sw.keys[0] && sw.keys[1] && sw.vals[0] && sw.vals[1] && sw.spine && sw.bin_total && sw.bin_base && sw.ghist && ms);
-    RBL_HIP(hipMemset(sw.ghist, 0, sort_ghist_bytes()));
+    RBL_TRY(alloc_sort(sc.mem, sw, n, true, sc.s));
+    RBL_TRY(sc.mem.alloc(&ms, (size_t)n));
     RBL_TRY(launch_keys_from_m(n, dk, sw.keys[0], sw.vals[0], sc.s));
     RBL_TRY(launch_radix_sort(sw, n, true, sc.s));
     RBL_TRY(launch_unflip_keys(n, sw.keys[0], ms, sc.s));
@@ -2362,34 +2229,18 @@ static int k_pav_common(int loss, int64_t n, const double* sigma_a, const double
     Scratch sc;
     RBL_TRY(scratch_begin(sc, nullptr));
     if (n <= 0) return RBL_OK;
-    const int64_t nc = pav_num_chunks(n);
-    double* sa = sc.upload(sigma_a, (size_t)n);
-    double* sb = ehrm ? sc.upload(sigma_b, (size_t)n) : sa;
-    double* ms = sc.upload(m_sorted, (size_t)n);
-    double* u = sc.alloc<double>((size_t)n);
-    SC_CHECK(sa && sb && ms && u);
-    double* lx[3];
-    double* ch[3];
-    double* cph[3];
-    double* cpl[3];
-    for (int k = 0; k < 3; ++k) {
-        lx[k] = sc.alloc<double>((size_t)n + 1);
-        ch[k] = sc.alloc<double>((size_t)nc);
-        cph[k] = sc.alloc<double>((size_t)nc);
-        cpl[k] = sc.alloc<double>((size_t)nc);
-        SC_CHECK(lx[k] && ch[k] && cph[k] && cpl[k]);
-    }
-    SeamRec* recs = sc.alloc<SeamRec>((size_t)pav_num_recs(n));
-    u32* counters = sc.alloc<u32>(4);
-    double* partials = sc.alloc<double>((size_t)reduce_blocks() * 4);
-    int* branch = sc.alloc<int>(1);
-    SC_CHECK(recs && counters && partials && branch);
-    PavExtras ex{};
-    ex.bar = sc.alloc<unsigned>(pav_bar_uints());
-    ex.big = sc.alloc<SeamRec>((size_t)pav_big_recs());
-    ex.fpart = sc.alloc<double>((size_t)pav_fpart_doubles(n));
-    SC_CHECK(ex.bar && ex.big && ex.fpart);
-    RBL_HIP(hipMemset(ex.bar, 0, sizeof(unsigned) * pav_bar_uints()));
+    double *sa = nullptr, *sb = nullptr;
+    RBL_TRY(sc.upload(&sa, sigma_a, (size_t)n));
+    if (ehrm) RBL_TRY(sc.upload(&sb, sigma_b, (size_t)n));
+    else sb = sa;
+    PavWorkspace pw{};   // the sorted m goes to pw.ms, its prefix sums to pw.pm
+    RBL_TRY(alloc_pav(sc.mem, pw, n, sc.s));
+    RBL_HIP(hipMemcpy(pw.ms, m_sorted, sizeof(double) * n, hipMemcpyHostToDevice));
+    PrefixBufs pa, pb;
+    RBL_TRY(alloc_prefix(sc.mem, pa, n));
+    pb = pa;
+    if (ehrm) RBL_TRY(alloc_prefix(sc.mem, pb, n));
+    PavExtras ex = pw.ex;
     {
         int dev = 0, cus = 0;
         RBL_HIP(hipGetDevice(&dev));
@@ -2397,7 +2248,6 @@ static int k_pav_common(int loss, int64_t n, const double* sigma_a, const double
         ex.num_cu = cus;
     }
     ex.B = B;
-    ex.spec = 1;
     {
         const char* e = getenv("RBL_EHRM_SPEC");   // 0 / 1: the speculated branch; -1: round 2's separate pass
         if (e && (atoi(e) == 0 || atoi(e) == 1)) ex.spec = atoi(e);
@@ -2405,26 +2255,25 @@ static int k_pav_common(int loss, int64_t n, const double* sigma_a, const double
         // through the speculation inside the bottom kernel
         if (!ehrm || branch_in >= 0 || (e && atoi(e) == -1)) ex.fpart = nullptr;
     }
-    RBL_HIP(hipMemset(recs, 0xff, sizeof(SeamRec) * (size_t)pav_num_recs(n)));   // no hints
-    RBL_TRY(launch_prefix(sa, n, lx[0], ch[0], cph[0], cpl[0], sc.s));
-    RBL_TRY(launch_prefix(sb, n, lx[1], ch[1], cph[1], cpl[1], sc.s));
-    RBL_TRY(launch_prefix(ms, n, lx[2], ch[2], cph[2], cpl[2], sc.s));
-    Prefix pa{lx[0], cph[0], cpl[0]}, pb{lx[1], cph[1], cpl[1]}, pm{lx[2], cph[2], cpl[2]};
-    if (ehrm && !ex.fpart) RBL_TRY(launch_ehrm_branch(n, sa, sb, B, rho, ms, partials, branch, branch_in, sc.s));
-    RBL_TRY(launch_pav_tree(loss, n, rho, ms, sa, sb, u, pa, pb, pm, ehrm ? branch : nullptr, recs, counters, sc.s, nullptr,
-                            nullptr, &ex));
+    RBL_TRY(launch_prefix(sa, n, pa, sc.s));
+    if (ehrm) RBL_TRY(launch_prefix(sb, n, pb, sc.s));
+    RBL_TRY(launch_prefix(pw.ms, n, pw.pm, sc.s));
+    if (ehrm && !ex.fpart) RBL_TRY(launch_ehrm_branch(n, sa, sb, B, rho, pw.ms, pw.partials, pw.branch, branch_in, sc.s));
+    RBL_TRY(launch_pav_tree(loss, n, rho, pw.ms, sa, sb, pw.u, pa.view(), pb.view(), pw.pm.view(), ehrm ? pw.branch : nullptr,
+                            pw.recs, pw.counters, sc.s, nullptr, nullptr, &ex));
     // identity permutation scatter applies the EHRM clip
     std::vector<u32> idh((size_t)n);
     for (int64_t i = 0; i < n; ++i) idh[(size_t)i] = (u32)i;
-    u32* idd = sc.upload(idh.data(), (size_t)n);
-    double* zz = sc.alloc<double>((size_t)n);
-    SC_CHECK(idd && zz);
-    RBL_TRY(launch_scatter_z(n, u, idd, ehrm ? branch : nullptr, B, ehrm, rho, nullptr, zz, nullptr, 0, n, sc.s));
+    u32* idd = nullptr;
+    double* zz = nullptr;
+    RBL_TRY(sc.upload(&idd, idh.data(), (size_t)n));
+    RBL_TRY(sc.mem.alloc(&zz, (size_t)n));
+    RBL_TRY(launch_scatter_z(n, pw.u, idd, ehrm ? pw.branch : nullptr, B, ehrm, rho, nullptr, zz, nullptr, 0, n, sc.s));
     RBL_HIP(hipMemcpyAsync(out, zz, sizeof(double) * n, hipMemcpyDeviceToHost, sc.s));
     unsigned mc4[4] = {0, 0, 0, 0};
     int br = -1;
-    RBL_HIP(hipMemcpyAsync(mc4, counters, sizeof(mc4), hipMemcpyDeviceToHost, sc.s));
-    if (ehrm) RBL_HIP(hipMemcpyAsync(&br, branch, sizeof(int), hipMemcpyDeviceToHost, sc.s));
+    RBL_HIP(hipMemcpyAsync(mc4, pw.counters, sizeof(mc4), hipMemcpyDeviceToHost, sc.s));
+    if (ehrm) RBL_HIP(hipMemcpyAsync(&br, pw.branch, sizeof(int), hipMemcpyDeviceToHost, sc.s));
     RBL_HIP(hipStreamSynchronize(sc.s));
     if (mc4[3] != 0) {
         rbl_set_error("PAV: the upper-level kernel did not complete (a wait gave up or its fill list overflowed)");
@@ -2456,9 +2305,9 @@ int rbl_k_gemv(int storage, int64_t n, int64_t d, const double* D, const double*
     RBL_TRY(upload_matrix(sc, storage, n, d, D, &Dd, &ld));
     std::vector<double> wp((size_t)ld, 0.0);
     for (int64_t j = 0; j < d; ++j) wp[(size_t)j] = w[j];
-    double* dw = sc.upload(wp.data(), (size_t)ld);
-    double* dv = sc.alloc<double>((size_t)n);
-    SC_CHECK(dw && dv);
+    double *dw = nullptr, *dv = nullptr;
+    RBL_TRY(sc.upload(&dw, wp.data(), (size_t)ld));
+    RBL_TRY(sc.mem.alloc(&dv, (size_t)n));
     RBL_TRY(launch_gemv(storage, Dd, n, ld, dw, dv, num_cu, sc.s));
     RBL_HIP(hipMemcpyAsync(v, dv, sizeof(double) * n, hipMemcpyDeviceToHost, sc.s));
     RBL_HIP(hipStreamSynchronize(sc.s));
@@ -2472,10 +2321,10 @@ int rbl_k_gemvt(int storage, int64_t n, int64_t d, const double* D, const double
     void* Dd = nullptr;
     int64_t ld = 0;
     RBL_TRY(upload_matrix(sc, storage, n > 0 ? n : 0, d, D, &Dd, &ld));
-    double* dc = sc.upload(c, (size_t)n);
-    double* slab = sc.alloc<double>((size_t)gemvt_slab_rows(num_cu) * ld);
-    double* dq = sc.alloc<double>((size_t)ld);
-    SC_CHECK(dc && slab && dq);
+    double *dc = nullptr, *slab = nullptr, *dq = nullptr;
+    RBL_TRY(sc.upload(&dc, c, (size_t)n));
+    RBL_TRY(sc.mem.alloc(&slab, (size_t)gemvt_slab_rows(num_cu) * ld));
+    RBL_TRY(sc.mem.alloc(&dq, (size_t)ld));
     RBL_TRY(launch_gemvt(storage, Dd, n, ld, dc, slab, dq, num_cu, sc.s));
     RBL_HIP(hipMemcpyAsync(q, dq, sizeof(double) * d, hipMemcpyDeviceToHost, sc.s));
     RBL_HIP(hipStreamSynchronize(sc.s));
@@ -2489,9 +2338,9 @@ int rbl_k_gram(int storage, int64_t n, int64_t d, const double* D, double* G) {
     void* Dd = nullptr;
     int64_t ld = 0;
     RBL_TRY(upload_matrix(sc, storage, n, d, D, &Dd, &ld));
-    double* slab = (double*)sc.alloc<unsigned char>(gram_slab_bytes(ld, num_cu, n > 0 ? n : 1));
-    double* dG = sc.alloc<double>((size_t)ld * ld);
-    SC_CHECK(slab && dG);
+    double *slab = nullptr, *dG = nullptr;
+    RBL_TRY(sc.mem.alloc((unsigned char**)&slab, gram_slab_bytes(ld, num_cu, n > 0 ? n : 1)));
+    RBL_TRY(sc.mem.alloc(&dG, (size_t)ld * ld));
     RBL_TRY(launch_gram(storage, Dd, n, ld, d, slab, dG, num_cu, sc.s));
     std::vector<double> hG((size_t)ld * ld);
     RBL_HIP(hipMemcpyAsync(hG.data(), dG, sizeof(double) * ld * ld, hipMemcpyDeviceToHost, sc.s));
@@ -2512,28 +2361,12 @@ int rbl_k_wstep(int wstep, int64_t d, const double* G, const double* q, double r
         hq[(size_t)i] = q[i];
         hw[(size_t)i] = w0 ? w0[i] : 0.0;
     }
-    double* dG = sc.upload(hG.data(), hG.size());
-    double* dq = sc.upload(hq.data(), hq.size());
-    double* dw = sc.upload(hw.data(), hw.size());
-    SC_CHECK(dG && dq && dw);
+    double *dG = nullptr, *dq = nullptr, *dw = nullptr;
+    RBL_TRY(sc.upload(&dG, hG.data(), hG.size()));
+    RBL_TRY(sc.upload(&dq, hq.data(), hq.size()));
+    RBL_TRY(sc.upload(&dw, hw.data(), hw.size()));
     WstepWorkspace ww{};
-    ww.yk = sc.alloc<double>((size_t)ld);
-    ww.Gy = sc.alloc<double>((size_t)ld);
-    ww.wn = sc.alloc<double>((size_t)ld);
-    ww.r = sc.alloc<double>((size_t)ld);
-    ww.p = sc.alloc<double>((size_t)ld);
-    ww.scal = sc.alloc<double>(8);
-    ww.flags = sc.alloc<int>(8);
-    ww.bar = sc.alloc<unsigned>((size_t)WSTEP_BAR_UINTS);
-    ww.xch = sc.alloc<double>((size_t)WSTEP_XCH_DOUBLES);
-    SC_CHECK(ww.yk && ww.Gy && ww.wn && ww.r && ww.p && ww.scal && ww.flags && ww.bar && ww.xch);
-    RBL_HIP(hipMemsetAsync(ww.xch, 0, sizeof(double) * WSTEP_XCH_DOUBLES, sc.s));
-    RBL_HIP(hipMemsetAsync(ww.bar, 0, sizeof(unsigned) * WSTEP_BAR_UINTS, sc.s));
-    RBL_TRY(alloc_wstep_pin(ww));
-    struct PinGuard {
-        WstepWorkspace& w;
-        ~PinGuard() { free_wstep_pin(w); }
-    } pin_guard{ww};
+    RBL_TRY(alloc_wstep(sc.mem, ww, ld, sc.s));
     double lam = 0.0;
     RBL_TRY(launch_power_iteration(dG, ld, ww.yk, ww.Gy, ww.scal, 100, &lam, sc.s));
     double L = 1.02 * lam;
@@ -2561,9 +2394,9 @@ int rbl_k_weights(int weight_function, int64_t n, const double* args, int n_args
         }
     }
     double a2[2] = {args && n_args > 0 ? args[0] : 0.0, args && n_args > 1 ? args[1] : 0.0};
-    double* da = sc.alloc<double>((size_t)n);
-    double* db = sc.alloc<double>((size_t)n);
-    SC_CHECK(da && db);
+    double *da = nullptr, *db = nullptr;
+    RBL_TRY(sc.mem.alloc(&da, (size_t)n));
+    RBL_TRY(sc.mem.alloc(&db, (size_t)n));
     RBL_TRY(launch_weights(weight_function, n, a2, da, db, sc.s));
     if (alphas) RBL_HIP(hipMemcpyAsync(alphas, da, sizeof(double) * n, hipMemcpyDeviceToHost, sc.s));
     if (betas) RBL_HIP(hipMemcpyAsync(betas, db, sizeof(double) * n, hipMemcpyDeviceToHost, sc.s));

@@ -32,6 +32,7 @@ struct rbl_baseline {
     float* rands = nullptr;
     size_t idx_cap = 0;
     SortWorkspace sw{};
+    DevArena mem;   // every device buffer of the handle
 };
 
 namespace {
@@ -201,25 +202,49 @@ __global__ __launch_bounds__(BL_THREADS) void k_bl_lsvrg_steps(const double* __r
     }
 }
 
-template <typename T>
-int bl_alloc(T** p, size_t count) {
-    *p = nullptr;
-    if (hipMalloc((void**)p, (count ? count : 1) * sizeof(T)) != hipSuccess) {
-        rbl_set_error("baselines: hipMalloc of %zu bytes failed", count * sizeof(T));
-        return RBL_ERR_NOMEM;
-    }
+int bl_ensure_idx(rbl_baseline* h, size_t count) {
+    if (count <= h->idx_cap) return RBL_OK;
+    if (h->idx) h->mem.release(h->idx);
+    if (h->rands) h->mem.release(h->rands);
+    h->idx = nullptr;
+    h->rands = nullptr;
+    RBL_TRY(h->mem.alloc(&h->idx, count));
+    RBL_TRY(h->mem.alloc(&h->rands, count));
+    h->idx_cap = count;
     return RBL_OK;
 }
 
-int bl_ensure_idx(rbl_baseline* h, size_t count) {
-    if (count <= h->idx_cap) return RBL_OK;
-    if (h->idx) (void)hipFree(h->idx);
-    if (h->rands) (void)hipFree(h->rands);
-    h->idx = nullptr;
-    h->rands = nullptr;
-    RBL_TRY(bl_alloc(&h->idx, count));
-    RBL_TRY(bl_alloc(&h->rands, count));
-    h->idx_cap = count;
+// everything rbl_bl_create sets up past the checks of its arguments; on failure the caller destroys h
+int bl_setup(rbl_baseline* h, const double* X, const double* y01) {
+    hipDeviceProp_t prop;
+    if (hipGetDeviceProperties(&prop, h->device) != hipSuccess || hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) {
+        rbl_set_error("baselines: device set-up failed");
+        return RBL_ERR_HIP;
+    }
+    h->num_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
+    const size_t nn = (size_t)h->n, ld = (size_t)h->ld;
+    DevArena& mem = h->mem;
+    RBL_TRY(mem.alloc(&h->X, nn * ld));
+    RBL_TRY(mem.alloc(&h->y01, nn));
+    RBL_TRY(mem.alloc(&h->w, ld));
+    RBL_TRY(mem.alloc(&h->w_chk, ld));
+    RBL_TRY(mem.alloc(&h->g_chk, ld));
+    RBL_TRY(mem.alloc(&h->z, nn));
+    RBL_TRY(mem.alloc(&h->c, nn));
+    RBL_TRY(mem.alloc(&h->alphas, nn));
+    RBL_TRY(mem.alloc(&h->betas, nn));
+    RBL_TRY(mem.alloc(&h->ab, (size_t)BL_MAX_BATCH));
+    RBL_TRY(mem.alloc(&h->bb, (size_t)BL_MAX_BATCH));
+    RBL_TRY(mem.alloc(&h->slab, (size_t)gemvt_slab_rows(h->num_cu) * ld * 2));
+    RBL_TRY(alloc_sort(mem, h->sw, h->n, true, h->stream));
+    bool ok = hipMemset(h->w, 0, sizeof(double) * ld) == hipSuccess && hipMemset(h->X, 0, sizeof(double) * nn * ld) == hipSuccess;
+    ok = ok && hipMemcpy2D(h->X, sizeof(double) * ld, X, sizeof(double) * (size_t)h->d, sizeof(double) * (size_t)h->d, nn,
+                           hipMemcpyHostToDevice) == hipSuccess;
+    ok = ok && hipMemcpy(h->y01, y01, sizeof(double) * nn, hipMemcpyHostToDevice) == hipSuccess;
+    if (!ok) {
+        rbl_set_error("baselines: upload failed: %s", hipGetErrorString(hipGetLastError()));
+        return RBL_ERR_HIP;
+    }
     return RBL_OK;
 }
 
@@ -231,13 +256,8 @@ int rbl_bl_destroy(rbl_baseline* h) {
     if (!h) return RBL_OK;
     (void)hipSetDevice(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
-    void* ptrs[] = {h->X, h->y01, h->w, h->w_chk, h->g_chk, h->z, h->c, h->alphas, h->betas, h->slab, h->ab, h->bb, h->idx,
-                    h->rands, h->sw.keys[0], h->sw.keys[1], h->sw.vals[0], h->sw.vals[1], h->sw.spine, h->sw.bin_total,
-                    h->sw.bin_base, h->sw.ghist};
-    for (void* p : ptrs)
-        if (p) (void)hipFree(p);
     if (h->stream) (void)hipStreamDestroy(h->stream);
-    delete h;
+    delete h;   // h->mem frees every buffer
     return RBL_OK;
 }
 
@@ -269,35 +289,7 @@ int rbl_bl_create(int64_t n, int64_t d, const double* X, const double* y01, int 
     h->l2 = l2_reg;
     h->l1 = l1_reg;
     h->device = device;
-    hipDeviceProp_t prop;
-    int rc = RBL_OK;
-    do {
-        if (hipGetDeviceProperties(&prop, device) != hipSuccess || hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) {
-            rbl_set_error("baselines: device set-up failed");
-            rc = RBL_ERR_HIP;
-            break;
-        }
-        h->num_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-        const size_t nn = (size_t)n, ld = (size_t)h->ld;
-        if ((rc = bl_alloc(&h->X, nn * ld)) || (rc = bl_alloc(&h->y01, nn)) || (rc = bl_alloc(&h->w, ld)) ||
-            (rc = bl_alloc(&h->w_chk, ld)) || (rc = bl_alloc(&h->g_chk, ld)) || (rc = bl_alloc(&h->z, nn)) ||
-            (rc = bl_alloc(&h->c, nn)) || (rc = bl_alloc(&h->alphas, nn)) || (rc = bl_alloc(&h->betas, nn)) ||
-            (rc = bl_alloc(&h->ab, (size_t)BL_MAX_BATCH)) || (rc = bl_alloc(&h->bb, (size_t)BL_MAX_BATCH)) ||
-            (rc = bl_alloc(&h->slab, (size_t)gemvt_slab_rows(h->num_cu) * ld * 2)) || (rc = bl_alloc(&h->sw.keys[0], nn)) ||
-            (rc = bl_alloc(&h->sw.keys[1], nn)) || (rc = bl_alloc(&h->sw.vals[0], nn)) || (rc = bl_alloc(&h->sw.vals[1], nn)) ||
-            (rc = bl_alloc((unsigned char**)&h->sw.spine, sort_spine_bytes())) || (rc = bl_alloc(&h->sw.bin_total, (size_t)256)) ||
-            (rc = bl_alloc(&h->sw.bin_base, (size_t)256)) || (rc = bl_alloc((unsigned char**)&h->sw.ghist, sort_ghist_bytes())))
-            break;
-        bool ok = hipMemset(h->sw.ghist, 0, sort_ghist_bytes()) == hipSuccess && hipMemset(h->w, 0, sizeof(double) * ld) == hipSuccess &&
-                  hipMemset(h->X, 0, sizeof(double) * nn * ld) == hipSuccess;
-        ok = ok && hipMemcpy2D(h->X, sizeof(double) * ld, X, sizeof(double) * (size_t)d, sizeof(double) * (size_t)d, nn,
-                               hipMemcpyHostToDevice) == hipSuccess;
-        ok = ok && hipMemcpy(h->y01, y01, sizeof(double) * nn, hipMemcpyHostToDevice) == hipSuccess;
-        if (!ok) {
-            rbl_set_error("baselines: upload failed: %s", hipGetErrorString(hipGetLastError()));
-            rc = RBL_ERR_HIP;
-        }
-    } while (0);
+    const int rc = bl_setup(h, X, y01);
     if (rc != RBL_OK) {
         rbl_bl_destroy(h);
         return rc;

@@ -1274,23 +1274,21 @@ int64_t pav_num_chunks(int64_t n) { return n / PAV_CHUNK + 1; }
 static int64_t pav_level_recs(int64_t n) { return n / (2 * PB_TILE) + 2; }
 int64_t pav_num_recs(int64_t n) { return 3 * pav_level_recs(n) + 64; }
 
-int launch_prefix(const double* x, int64_t n, double* locx, double* chunk_tot, double* cph, double* cpl,
-                  hipStream_t s) {
+int launch_prefix(const double* x, int64_t n, const PrefixBufs& p, hipStream_t s) {
     const long long nc = pav_num_chunks(n);
-    hipLaunchKernelGGL(k_chunk_scan<false>, dim3((unsigned)nc), dim3(256), 0, s, x, (long long)n, locx, chunk_tot,
+    hipLaunchKernelGGL(k_chunk_scan<false>, dim3((unsigned)nc), dim3(256), 0, s, x, (long long)n, p.locx, p.chunk,
                        (double*)nullptr);
-    hipLaunchKernelGGL(k_chunk_prefix_dd, dim3(1), dim3(1024), 0, s, chunk_tot, nc, cph, cpl);
+    hipLaunchKernelGGL(k_chunk_prefix_dd, dim3(1), dim3(1024), 0, s, p.chunk, nc, p.cph, p.cpl);
     RBL_HIP(hipGetLastError());
     return RBL_OK;
 }
 
 // sorted keys -> sorted m (ms) and its two-level prefix sums in one pass
-int launch_unflip_prefix(const u64* keys, int64_t n, double* ms, double* locx, double* chunk_tot, double* cph, double* cpl,
-                         hipStream_t s) {
+int launch_unflip_prefix(const u64* keys, int64_t n, double* ms, const PrefixBufs& p, hipStream_t s) {
     const long long nc = pav_num_chunks(n);
     hipLaunchKernelGGL(k_chunk_scan<true>, dim3((unsigned)nc), dim3(256), 0, s, reinterpret_cast<const double*>(keys),
-                       (long long)n, locx, chunk_tot, ms);
-    hipLaunchKernelGGL(k_chunk_prefix_dd, dim3(1), dim3(1024), 0, s, chunk_tot, nc, cph, cpl);
+                       (long long)n, p.locx, p.chunk, ms);
+    hipLaunchKernelGGL(k_chunk_prefix_dd, dim3(1), dim3(1024), 0, s, p.chunk, nc, p.cph, p.cpl);
     RBL_HIP(hipGetLastError());
     return RBL_OK;
 }

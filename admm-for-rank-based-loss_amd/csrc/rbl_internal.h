@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include <cstddef>
+#include <vector>
 #include "../../include/rbl.h"
 
 void rbl_set_error(const char* fmt, ...);
@@ -29,6 +30,55 @@ void rbl_note_host_sync();
         if (r_ != RBL_OK) return r_; \
     } while (0)
 
+// Owner of device (hipMalloc) and pinned host (hipHostMalloc) buffers: its destructor frees every buffer
+// allocated through it.  One per solver / baseline handle, or a local one for scoped temporaries.
+class DevArena {
+  public:
+    DevArena() = default;
+    DevArena(const DevArena&) = delete;
+    DevArena& operator=(const DevArena&) = delete;
+    ~DevArena() {
+        for (const Buf& b : bufs_) (void)(b.pinned ? hipHostFree(b.p) : hipFree(b.p));
+    }
+    // count == 0 allocates one element; on failure *p = NULL, the error text is set and RBL_ERR_NOMEM returned
+    template <typename T>
+    int alloc(T** p, size_t count) {
+        *p = nullptr;
+        if (count == 0) count = 1;
+        hipError_t e = hipMalloc((void**)p, count * sizeof(T));
+        if (e != hipSuccess) {
+            rbl_set_error("hipMalloc of %zu bytes failed: %s", count * sizeof(T), hipGetErrorString(e));
+            return RBL_ERR_NOMEM;
+        }
+        bufs_.push_back({*p, false});
+        return RBL_OK;
+    }
+    // pinned host memory the device accesses directly (flags as hipHostMalloc takes them)
+    template <typename T>
+    int pinned(T** p, size_t count, unsigned flags) {
+        *p = nullptr;
+        RBL_HIP(hipHostMalloc((void**)p, count * sizeof(T), flags));
+        bufs_.push_back({*p, true});
+        return RBL_OK;
+    }
+    // frees one buffer ahead of the others (a buffer that is regrown)
+    void release(void* p) {
+        for (size_t i = 0; i < bufs_.size(); ++i)
+            if (bufs_[i].p == p) {
+                (void)(bufs_[i].pinned ? hipHostFree(p) : hipFree(p));
+                bufs_.erase(bufs_.begin() + (long)i);
+                return;
+            }
+    }
+
+  private:
+    struct Buf {
+        void* p;
+        bool pinned;
+    };
+    std::vector<Buf> bufs_;
+};
+
 typedef unsigned long long u64;
 typedef unsigned int u32;
 
@@ -43,6 +93,14 @@ struct Prefix {
     const double* locx;  // n+1 entries, exclusive prefix inside the chunk
     const double* cph;   // chunk-level exclusive prefix, double-double high part
     const double* cpl;   //                               double-double low part
+};
+// the buffers behind one Prefix (api.hip: alloc_prefix)
+struct PrefixBufs {
+    double* locx = nullptr;    // n+1
+    double* chunk = nullptr;   // nchunks: chunk totals
+    double* cph = nullptr;     // nchunks
+    double* cpl = nullptr;     // nchunks
+    Prefix view() const { return Prefix{locx, cph, cpl}; }
 };
 
 struct SeamRec {
@@ -119,6 +177,8 @@ size_t sort_ghist_bytes();
 // key_bits: number of low key bits that can differ (digits above are skipped)
 int launch_radix_sort(SortWorkspace& ws, int64_t n, bool with_vals, hipStream_t s, int key_bits = 64);
 int launch_radix_sort32(SortWorkspace& ws, int64_t n, hipStream_t s);
+// api.hip: the workspace for n keys (and values) in mem; the done-counter is zeroed on s
+int alloc_sort(DevArena& mem, SortWorkspace& sw, int64_t n, bool with_vals, hipStream_t s);
 
 // ---- pav.hip ----------------------------------------------------------------------------
 // ex (round 3, optional): the upper levels in one persistent launch (bar / big / num_cu) and, for a single-handle EHRM
@@ -140,10 +200,7 @@ int64_t pav_fpart_doubles(int64_t n);
 struct PavWorkspace {
     double* ms;        // n   sorted m
     double* u;         // n   current block values by sorted position
-    double* locx_m;    // n+1
-    double* chunk_m;   // nchunks
-    double* cph_m;     // nchunks
-    double* cpl_m;     // nchunks
+    PrefixBufs pm;     // prefix sums of ms
     SeamRec* recs;     // seams of the upper levels
     u32* counters;     // [0] merges, [1] dirty upper levels, [2] long fills, [3] status of the persistent upper-level kernel
     double* partials;  // reduce scratch
@@ -152,11 +209,9 @@ struct PavWorkspace {
 };
 int64_t pav_num_chunks(int64_t n);
 int64_t pav_num_recs(int64_t n);
-int launch_prefix(const double* x, int64_t n, double* locx, double* chunk_tot, double* cph, double* cpl,
-                  hipStream_t s);
+int launch_prefix(const double* x, int64_t n, const PrefixBufs& p, hipStream_t s);
 int launch_unflip_keys(int64_t n, const u64* keys, double* ms, hipStream_t s);
-int launch_unflip_prefix(const u64* keys, int64_t n, double* ms, double* locx, double* chunk_tot, double* cph, double* cpl,
-                         hipStream_t s);
+int launch_unflip_prefix(const u64* keys, int64_t n, double* ms, const PrefixBufs& p, hipStream_t s);
 // EHRM: scalar branch test (PAV_cpt.py:205-226) -> *branch
 // u0a / u0b (optional): the element prox of both branches is kept for launch_pav_tree
 int launch_ehrm_branch(int64_t n, const double* sa, const double* sb, double B, double rho, const double* ms,
