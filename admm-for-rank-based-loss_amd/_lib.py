@@ -131,6 +131,7 @@ SIGNATURES = {
     "rbl_k_sort": (C.c_int, [C.c_int64, _P, _P, _P]),
     "rbl_k_pav": (C.c_int, [C.c_int, C.c_int64, _P, C.c_double, _P, _P, _I64]),
     "rbl_k_pav_ehrm": (C.c_int, [C.c_int64, _P, _P, C.c_double, C.c_double, _P, C.c_int, _P, C.POINTER(C.c_int)]),
+    "rbl_k_pav_seq": (C.c_int, [C.c_int, C.c_int64, _P, _P, C.c_double, C.c_double, C.c_int, _P, C.c_int, _P, _P, _P]),
     "rbl_k_gemv": (C.c_int, [C.c_int, C.c_int64, C.c_int64, _P, _P, _P]),
     "rbl_k_gemvt": (C.c_int, [C.c_int, C.c_int64, C.c_int64, _P, _P, _P]),
     "rbl_k_gram": (C.c_int, [C.c_int, C.c_int64, C.c_int64, _P, _P]),
@@ -251,6 +252,26 @@ def k_pav_ehrm(sigma_a, sigma_b, B, rho, m_sorted, branch=-1):
     check(load().rbl_k_pav_ehrm(m.size, ptr(sa), ptr(sb), float(B), float(rho), ptr(m), int(branch), ptr(out),
                                 C.byref(br)))
     return out, br.value
+
+
+PAV_UPPER = {"persist": 1, "two_launch": 2}
+
+
+def k_pav_seq(loss, sigma, rho, m_seq, upper, sigma_b=None, B=0.0):
+    """len(m_seq) PAV solves on one workspace (the upper seams' hints, the barrier parity and the EHRM branch carry
+    over).  upper: "persist" or "two_launch".  sigma_b: EHRM (BCE).  Returns (u, branch, counters): u (K, n) after the
+    EHRM clip, branch (K,) (-1 unless EHRM), counters (K, 4) uint32 = merges, dirty-level mask, long fills, status."""
+    sa = f64(sigma).reshape(-1)
+    ms = f64(m_seq)
+    ms = np.ascontiguousarray(ms.reshape(-1, sa.size))
+    K, n = ms.shape
+    sb = None if sigma_b is None else f64(sigma_b).reshape(-1)
+    out = np.empty((K, n))
+    br = np.full(K, -1, dtype=np.int32)
+    cnt = np.zeros((K, 4), dtype=np.uint32)
+    check(load().rbl_k_pav_seq(LOSS[loss], n, ptr(sa), ptr(sb), float(B), float(rho), K, ptr(ms), PAV_UPPER[upper],
+                               ptr(out), ptr(br), ptr(cnt)))
+    return out, br, cnt
 
 
 def k_gemv(D, w, storage="f32"):

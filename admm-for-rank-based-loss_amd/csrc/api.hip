@@ -216,14 +216,16 @@ int alloc_pav(DevArena& mem, PavWorkspace& pw, int64_t n, hipStream_t s) {
     RBL_TRY(alloc_prefix(mem, pw.pm, n));
     RBL_TRY(mem.alloc(&pw.recs, (size_t)pav_num_recs(n)));
     RBL_HIP(hipMemsetAsync(pw.recs, 0xff, sizeof(SeamRec) * (size_t)pav_num_recs(n), s));   // s = -1: no hint from a previous iteration
-    RBL_TRY(mem.alloc(&pw.counters, 4));
-    RBL_HIP(hipMemsetAsync(pw.counters, 0, 4 * sizeof(u32), s));   // (read by every iteration's statistics, also when the caller supplied z)
+    RBL_TRY(mem.alloc(&pw.counters, (size_t)PAV_COUNTERS));
+    RBL_HIP(hipMemsetAsync(pw.counters, 0, PAV_COUNTERS * sizeof(u32), s));   // (read by every iteration's statistics, also when the caller supplied z)
     RBL_TRY(mem.alloc(&pw.partials, (size_t)reduce_blocks() * 4));
     RBL_TRY(mem.alloc(&pw.branch, 1));
     pw.ex = PavExtras{};
     RBL_TRY(mem.alloc(&pw.ex.bar, pav_bar_uints()));
     RBL_HIP(hipMemsetAsync(pw.ex.bar, 0, sizeof(unsigned) * pav_bar_uints(), s));
-    RBL_TRY(mem.alloc(&pw.ex.big, (size_t)pav_big_recs()));
+    // n bounds every launch on this workspace: the solver's z-step (n_total positions) and the distributed z-step, whose
+    // chunk of the sorted order (zd_n) is at most n_total long (rbl_zd_prepare)
+    RBL_TRY(mem.alloc(&pw.ex.big, (size_t)pav_big_recs(n)));
     RBL_TRY(mem.alloc(&pw.ex.fpart, (size_t)pav_fpart_doubles(n)));
     pw.ex.spec = 1;   // EHRM: branch b on every ADMM trajectory seen; corrected by the first exact test
     return RBL_OK;
@@ -2223,19 +2225,20 @@ int rbl_k_sort(int64_t n, const double* keys, double* sorted_keys, uint32_t* per
     return RBL_OK;
 }
 
+// ncalls successive PAV solves on ONE workspace (m_sorted: ncalls x n): the hints of the upper seams, the barrier parity
+// and the EHRM speculated branch carry over from one call to the next as they do between the z-steps of a solve.
 static int k_pav_common(int loss, int64_t n, const double* sigma_a, const double* sigma_b, int ehrm, double B,
-                        double rho, const double* m_sorted, int branch_in, double* out, int64_t* n_merges,
-                        int* branch_out) {
+                        double rho, int ncalls, const double* m_sorted, int branch_in, int upper, double* out,
+                        int64_t* n_merges, int* branch_out, uint32_t* counters_out) {
     Scratch sc;
     RBL_TRY(scratch_begin(sc, nullptr));
-    if (n <= 0) return RBL_OK;
+    if (n <= 0 || ncalls <= 0) return RBL_OK;
     double *sa = nullptr, *sb = nullptr;
     RBL_TRY(sc.upload(&sa, sigma_a, (size_t)n));
     if (ehrm) RBL_TRY(sc.upload(&sb, sigma_b, (size_t)n));
     else sb = sa;
     PavWorkspace pw{};   // the sorted m goes to pw.ms, its prefix sums to pw.pm
     RBL_TRY(alloc_pav(sc.mem, pw, n, sc.s));
-    RBL_HIP(hipMemcpy(pw.ms, m_sorted, sizeof(double) * n, hipMemcpyHostToDevice));
     PrefixBufs pa, pb;
     RBL_TRY(alloc_prefix(sc.mem, pa, n));
     pb = pa;
@@ -2248,6 +2251,7 @@ static int k_pav_common(int loss, int64_t n, const double* sigma_a, const double
         ex.num_cu = cus;
     }
     ex.B = B;
+    ex.upper = upper;
     {
         const char* e = getenv("RBL_EHRM_SPEC");   // 0 / 1: the speculated branch; -1: round 2's separate pass
         if (e && (atoi(e) == 0 || atoi(e) == 1)) ex.spec = atoi(e);
@@ -2257,10 +2261,6 @@ static int k_pav_common(int loss, int64_t n, const double* sigma_a, const double
     }
     RBL_TRY(launch_prefix(sa, n, pa, sc.s));
     if (ehrm) RBL_TRY(launch_prefix(sb, n, pb, sc.s));
-    RBL_TRY(launch_prefix(pw.ms, n, pw.pm, sc.s));
-    if (ehrm && !ex.fpart) RBL_TRY(launch_ehrm_branch(n, sa, sb, B, rho, pw.ms, pw.partials, pw.branch, branch_in, sc.s));
-    RBL_TRY(launch_pav_tree(loss, n, rho, pw.ms, sa, sb, pw.u, pa.view(), pb.view(), pw.pm.view(), ehrm ? pw.branch : nullptr,
-                            pw.recs, pw.counters, sc.s, nullptr, nullptr, &ex));
     // identity permutation scatter applies the EHRM clip
     std::vector<u32> idh((size_t)n);
     for (int64_t i = 0; i < n; ++i) idh[(size_t)i] = (u32)i;
@@ -2268,31 +2268,62 @@ static int k_pav_common(int loss, int64_t n, const double* sigma_a, const double
     double* zz = nullptr;
     RBL_TRY(sc.upload(&idd, idh.data(), (size_t)n));
     RBL_TRY(sc.mem.alloc(&zz, (size_t)n));
-    RBL_TRY(launch_scatter_z(n, pw.u, idd, ehrm ? pw.branch : nullptr, B, ehrm, rho, nullptr, zz, nullptr, 0, n, sc.s));
-    RBL_HIP(hipMemcpyAsync(out, zz, sizeof(double) * n, hipMemcpyDeviceToHost, sc.s));
-    unsigned mc4[4] = {0, 0, 0, 0};
-    int br = -1;
-    RBL_HIP(hipMemcpyAsync(mc4, pw.counters, sizeof(mc4), hipMemcpyDeviceToHost, sc.s));
-    if (ehrm) RBL_HIP(hipMemcpyAsync(&br, pw.branch, sizeof(int), hipMemcpyDeviceToHost, sc.s));
-    RBL_HIP(hipStreamSynchronize(sc.s));
-    if (mc4[3] != 0) {
-        rbl_set_error("PAV: the upper-level kernel did not complete (a wait gave up or its fill list overflowed)");
-        return RBL_ERR_HIP;
+    for (int call = 0; call < ncalls; ++call) {
+        RBL_HIP(hipMemcpyAsync(pw.ms, m_sorted + (size_t)call * n, sizeof(double) * n, hipMemcpyHostToDevice, sc.s));
+        RBL_TRY(launch_prefix(pw.ms, n, pw.pm, sc.s));
+        if (ehrm && !ex.fpart) RBL_TRY(launch_ehrm_branch(n, sa, sb, B, rho, pw.ms, pw.partials, pw.branch, branch_in, sc.s));
+        RBL_TRY(launch_pav_tree(loss, n, rho, pw.ms, sa, sb, pw.u, pa.view(), pb.view(), pw.pm.view(), ehrm ? pw.branch : nullptr,
+                                pw.recs, pw.counters, sc.s, nullptr, nullptr, &ex));
+        RBL_TRY(launch_scatter_z(n, pw.u, idd, ehrm ? pw.branch : nullptr, B, ehrm, rho, nullptr, zz, nullptr, 0, n, sc.s));
+        RBL_HIP(hipMemcpyAsync(out + (size_t)call * n, zz, sizeof(double) * n, hipMemcpyDeviceToHost, sc.s));
+        unsigned mc4[4] = {0, 0, 0, 0};
+        int br = -1;
+        RBL_HIP(hipMemcpyAsync(mc4, pw.counters, sizeof(mc4), hipMemcpyDeviceToHost, sc.s));
+        if (ehrm) RBL_HIP(hipMemcpyAsync(&br, pw.branch, sizeof(int), hipMemcpyDeviceToHost, sc.s));
+        RBL_HIP(hipStreamSynchronize(sc.s));
+        if (counters_out)
+            for (int j = 0; j < 4; ++j) counters_out[4 * call + j] = mc4[j];
+        if (mc4[3] != 0) {
+            rbl_set_error("PAV: the upper-level kernel did not complete (a wait gave up or its fill list overflowed)");
+            return RBL_ERR_HIP;
+        }
+        if (n_merges) n_merges[call] = mc4[0];
+        if (branch_out) branch_out[call] = br;
+        if (ehrm && br >= 0) ex.spec = br;   // the next call speculates the branch this one took (rbl_phase_finish)
     }
-    const unsigned mc = mc4[0];
-    if (n_merges) *n_merges = mc;
-    if (branch_out) *branch_out = br;
     return RBL_OK;
 }
 
 int rbl_k_pav(int loss, int64_t n, const double* sigma, double rho, const double* m_sorted, double* out,
               int64_t* n_merges) {
-    return k_pav_common(loss, n, sigma, sigma, 0, 0.0, rho, m_sorted, -1, out, n_merges, nullptr);
+    return k_pav_common(loss, n, sigma, sigma, 0, 0.0, rho, 1, m_sorted, -1, PAV_UPPER_DEFAULT, out, n_merges, nullptr,
+                        nullptr);
 }
 
 int rbl_k_pav_ehrm(int64_t n, const double* sigma_a, const double* sigma_b, double B, double rho,
                    const double* m_sorted, int branch, double* out, int* branch_out) {
-    return k_pav_common(RBL_LOSS_BCE, n, sigma_a, sigma_b, 1, B, rho, m_sorted, branch, out, nullptr, branch_out);
+    return k_pav_common(RBL_LOSS_BCE, n, sigma_a, sigma_b, 1, B, rho, 1, m_sorted, branch, PAV_UPPER_DEFAULT, out, nullptr,
+                        branch_out, nullptr);
+}
+
+int rbl_k_pav_seq(int loss, int64_t n, const double* sigma_a, const double* sigma_b, double B, double rho, int ncalls,
+                  const double* m_sorted, int upper, double* out, int* branch_out, uint32_t* counters) {
+    if (loss != RBL_LOSS_BCE && loss != RBL_LOSS_HINGE) {
+        rbl_set_error("rbl_k_pav_seq: unknown loss %d", loss);
+        return RBL_ERR_INVALID;
+    }
+    if (upper != RBL_PAV_UPPER_PERSIST && upper != RBL_PAV_UPPER_TWO_LAUNCH) {
+        rbl_set_error("rbl_k_pav_seq: upper must be RBL_PAV_UPPER_PERSIST or RBL_PAV_UPPER_TWO_LAUNCH, got %d", upper);
+        return RBL_ERR_INVALID;
+    }
+    const int ehrm = sigma_b != nullptr;
+    if (ehrm && loss != RBL_LOSS_BCE) {
+        rbl_set_error("rbl_k_pav_seq: the EHRM z-step is defined for the BCE loss only");
+        return RBL_ERR_INVALID;
+    }
+    return k_pav_common(loss, n, sigma_a, ehrm ? sigma_b : sigma_a, ehrm, B, rho, ncalls, m_sorted, -1,
+                        upper == RBL_PAV_UPPER_PERSIST ? PAV_UPPER_PERSIST : PAV_UPPER_TWO_LAUNCH, out, nullptr, branch_out,
+                        counters);
 }
 
 int rbl_k_gemv(int storage, int64_t n, int64_t d, const double* D, const double* w, double* v) {

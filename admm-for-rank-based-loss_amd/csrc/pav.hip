@@ -825,15 +825,23 @@ __global__ __launch_bounds__(256) void k_pav_fill(double* __restrict__ u, long l
 //             cooperative fill.
 // A level's bit can only be set by phase 0 or by merges of lower levels, all of which lie before the barrier after
 // which the bit is read, so every block takes the same decisions and passes the same barriers.
+// The same holds for the cooperative fills: level l's long ranges are counted in a counter of that level alone
+// (counters[PAV_LEVEL_FILLS + l]), which only level l's merging waves increment, all before barrier l; read after
+// barrier l it is final, and every wave sees the same value.  Level l's entries are the slots
+// [big_done, big_done + count) - big_done, the sum of the counts of the levels below, is the same in every wave -
+// so whether a block fills, what it fills and whether it enters the second barrier depend on final values only.  (A
+// single counter for all levels is not final: a fast block can add level l + 1's entries before a slow one has read
+// it after barrier l.)
 constexpr long long PU_DIRECT_FILL = 8192;    // positions a merging wave writes itself
-constexpr int PU_BIG_CAP = 4096;              // capacity of the cooperative-fill list
 
 struct PavUpperArgs {
     SeamRec* hints;        // per level, concatenated
-    SeamRec* big;          // cooperative-fill list
-    u32* counters;         // [0] merges, [1] dirty levels, [2] entries of `big`, [3] status (1: a wait gave up / list overflow)
+    SeamRec* big;          // cooperative-fill list, big_cap entries
+    u32* counters;         // [0] merges, [1] dirty levels, [2] entries of `big`, [3] status (1: a wait gave up / list overflow),
+                           // [PAV_LEVEL_FILLS + l] long ranges of level l
     unsigned* bar;
     int parity, nlevels;
+    long long big_cap;
 };
 
 template <int LOSS>
@@ -846,7 +854,7 @@ __global__ __launch_bounds__(PV_THREADS) void k_pav_upper(double* __restrict__ u
     rbl::GridBarrier gb = rbl::gs_init(A.bar, A.parity);
     typedef unsigned gu32 __attribute__((address_space(1)));
     gu32* dirty = (gu32*)(A.counters + 1);
-    gu32* bigcnt = (gu32*)(A.counters + 2);
+    gu32* level_fills = (gu32*)(A.counters + PAV_LEVEL_FILLS);
     // ---- phase 0: which levels have a violating seam
     for (int l = 0; l < A.nlevels; ++l) {
         const long long half = (long long)PB_TILE << l, nseams = (n + 2 * half - 1) / (2 * half);
@@ -892,8 +900,9 @@ __global__ __launch_bounds__(PV_THREADS) void k_pav_upper(double* __restrict__ u
             if (e_star - s_star + 1 <= PU_DIRECT_FILL) {
                 for (long long i = s_star + lane; i <= e_star; i += 64) u[i] = x;
             } else if (lane == 0) {
-                const u32 slot = __hip_atomic_fetch_add(bigcnt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                if (slot < (u32)PU_BIG_CAP) {
+                const long long slot = (long long)big_done +
+                                       __hip_atomic_fetch_add(level_fills + l, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                if (slot < A.big_cap) {   // always (pav_big_recs): kept as a guard of the buffer
                     A.big[slot].s = s_star;
                     A.big[slot].e = e_star;
                     A.big[slot].x = x;
@@ -904,20 +913,22 @@ __global__ __launch_bounds__(PV_THREADS) void k_pav_upper(double* __restrict__ u
         }
         ok = rbl::gs_barrier(gb, &s_flag);
         if (!ok) break;
-        u32 nbig = __hip_atomic_load(bigcnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (nbig > (u32)PU_BIG_CAP) nbig = PU_BIG_CAP;
-        if (nbig > big_done) {
-            for (u32 r = big_done; r < nbig; ++r) {
+        const u32 nbig = __hip_atomic_load(level_fills + l, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // final (above)
+        if (nbig > 0) {
+            long long end = (long long)big_done + nbig;
+            if (end > A.big_cap) end = A.big_cap;
+            for (long long r = big_done; r < end; ++r) {
                 const SeamRec rec = A.big[r];
                 for (long long i = rec.s + tid_g; i <= rec.e; i += nthreads) u[i] = rec.x;
             }
-            big_done = nbig;
+            big_done += nbig;
             ok = rbl::gs_barrier(gb, &s_flag);
             if (!ok) break;
         }
         mask |= __hip_atomic_load(dirty, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
     if (lane == 0 && merges) atomicAdd(A.counters, merges);
+    if (blockIdx.x == 0 && threadIdx.x == 0) A.counters[2] = big_done;
     if (!ok && threadIdx.x == 0) __hip_atomic_store((gu32*)(A.counters + 3), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
@@ -1352,18 +1363,25 @@ int launch_add_u32(int64_t n, u32* x, u32 add, hipStream_t s) {
 }
 
 size_t pav_bar_uints() { return (size_t)rbl::GS_UINTS; }
-int64_t pav_big_recs() { return PU_BIG_CAP; }
+// Entries of the cooperative-fill list a launch over n positions can need.  A seam of level l pools inside its segment
+// of 2 half positions (half = PB_TILE << l), so a range longer than PU_DIRECT_FILL needs 2 half > PU_DIRECT_FILL, i.e.
+// half >= PU_DIRECT_FILL.  Each seam merges at most once per launch and adds at most one entry.  Level l has
+// ceil((n - half) / (2 half)) <= n / (2 half) + 1 seams; summed over half = PU_DIRECT_FILL, 2 PU_DIRECT_FILL, ... that is
+// at most n / PU_DIRECT_FILL + (number of levels), and there are fewer than 64 levels.
+int64_t pav_big_recs(int64_t n) { return (n > 0 ? n : 0) / PU_DIRECT_FILL + 64; }
 int64_t pav_fpart_doubles(int64_t n) { return 2 * ((n + PB_TILE - 1) / PB_TILE) + 2; }
 
 int launch_pav_tree(int loss, int64_t n, double rho, const double* ms, const double* sa, const double* sb, double* u,
                     Prefix pa, Prefix pb, Prefix pm, const int* branch, SeamRec* recs, u32* merge_counter,
                     hipStream_t s, const double* u0a, const double* u0b, PavExtras* ex) {
-    RBL_HIP(hipMemsetAsync(merge_counter, 0, 4 * sizeof(u32), s));   // merges | dirty levels | long fills | status
+    // merges | dirty levels | long fills | status | long fills per level
+    RBL_HIP(hipMemsetAsync(merge_counter, 0, PAV_COUNTERS * sizeof(u32), s));
     if (n <= 0) return RBL_OK;
-    static const bool no_upper = [] {
+    static const bool env_no_upper = [] {
         const char* e = getenv("RBL_PAV_UPPER_PERSIST");   // =0: two launches per upper level (round 2)
         return e && e[0] == '0';
     }();
+    const bool no_upper = (ex && ex->upper != PAV_UPPER_DEFAULT) ? ex->upper == PAV_UPPER_TWO_LAUNCH : env_no_upper;
     // levels 0 .. log2(PB_TILE): prox + in-LDS merges, one tile per workgroup
     const unsigned tiles = (unsigned)((n + PB_TILE - 1) / PB_TILE);
     if (ex && ex->fpart && loss == RBL_LOSS_BCE && branch) {
@@ -1395,6 +1413,7 @@ int launch_pav_tree(int loss, int64_t n, double rho, const double* ms, const dou
         A.bar = ex->bar;
         A.parity = ex->bar_parity;
         ex->bar_parity ^= 1;
+        A.big_cap = pav_big_recs(n);   // <= the allocation: the workspace was sized for at least n positions
         A.nlevels = 0;
         for (long long half = PB_TILE; half < n; half <<= 1) ++A.nlevels;
         long long want = ((n + 2LL * PB_TILE - 1) / (2LL * PB_TILE) + 3) / 4;    // one wave per seam of the lowest level

@@ -184,25 +184,31 @@ int alloc_sort(DevArena& mem, SortWorkspace& sw, int64_t n, bool with_vals, hipS
 // ex (round 3, optional): the upper levels in one persistent launch (bar / big / num_cu) and, for a single-handle EHRM
 // z-step, the branch speculated from the previous iteration with the singleton-stage sums formed inside the bottom
 // kernel (fpart / spec / B; `branch` is then WRITTEN by the exact test before the upper levels read it).
+enum { PAV_UPPER_DEFAULT = 0, PAV_UPPER_PERSIST = 1, PAV_UPPER_TWO_LAUNCH = 2 };
 struct PavExtras {
     unsigned* bar;      // pav_bar_uints() counters, zeroed at allocation
     int bar_parity;     // flips per launch
-    SeamRec* big;       // pav_big_recs() entries: long pooled ranges all blocks fill together
+    SeamRec* big;       // pav_big_recs(n) entries: long pooled ranges all blocks fill together
     int num_cu;
     double* fpart;      // pav_fpart_doubles(n): per-tile shares of the two sums (NULL: no speculation)
     int spec;           // speculated branch (0 = a, 1 = b)
     double B;
+    int upper;          // upper levels: PAV_UPPER_DEFAULT (RBL_PAV_UPPER_PERSIST decides, persistent unless it is 0),
+                        // PAV_UPPER_PERSIST (k_pav_upper) or PAV_UPPER_TWO_LAUNCH (k_pav_seam_wave + k_pav_fill per level)
 };
 size_t pav_bar_uints();
 int rbl_live_handles(int device);   // api.hip: solver handles of this process alive on a device
-int64_t pav_big_recs();
+int64_t pav_big_recs(int64_t n);   // n: the most positions the workspace's PAV sees
 int64_t pav_fpart_doubles(int64_t n);
+constexpr int PAV_LEVEL_FILLS = 4;
+constexpr int PAV_COUNTERS = PAV_LEVEL_FILLS + 64;
 struct PavWorkspace {
     double* ms;        // n   sorted m
     double* u;         // n   current block values by sorted position
     PrefixBufs pm;     // prefix sums of ms
     SeamRec* recs;     // seams of the upper levels
-    u32* counters;     // [0] merges, [1] dirty upper levels, [2] long fills, [3] status of the persistent upper-level kernel
+    u32* counters;     // PAV_COUNTERS: [0] merges, [1] dirty upper levels, [2] long fills, [3] status of the persistent
+                       // upper-level kernel, [PAV_LEVEL_FILLS + l] long fills of upper level l
     double* partials;  // reduce scratch
     int* branch;       // EHRM branch flag on the device (0 = a, 1 = b)
     PavExtras ex;      // round-3 paths of launch_pav_tree (buffers owned by this workspace)

@@ -321,6 +321,18 @@ int  rbl_k_pav(int loss, int64_t n, const double* sigma, double rho, const doubl
  * singleton-stage scalar test, 0 = a, 1 = b; *branch_out receives the choice */
 int  rbl_k_pav_ehrm(int64_t n, const double* sigma_a, const double* sigma_b, double B, double rho,
                     const double* m_sorted, int branch, double* out, int* branch_out);
+/* ncalls successive PAV solves on ONE workspace, which carries the upper seams' hints, the
+ * barrier parity and the EHRM speculated branch from one call to the next as a solver handle
+ * does between z-steps.  m_sorted and out: ncalls x n.  sigma_b != NULL: EHRM (BCE only; the
+ * branch is chosen per call, the EHRM clip is applied to out, branch_out[call] receives it).
+ * upper selects how the levels above the 2048-position tile run (RBL_PAV_UPPER_*, whatever
+ * RBL_PAV_UPPER_PERSIST says).  counters (ncalls x 4, optional): merges, bit mask of the upper
+ * levels the persistent kernel looked at, its long (cooperative) fills and its status; the last
+ * three are 0 on the two-launch path. */
+enum { RBL_PAV_UPPER_PERSIST = 1, RBL_PAV_UPPER_TWO_LAUNCH = 2 };
+int  rbl_k_pav_seq(int loss, int64_t n, const double* sigma_a, const double* sigma_b, double B, double rho,
+                   int ncalls, const double* m_sorted, int upper, double* out, int* branch_out,
+                   uint32_t* counters);
 /* v = D w and q = D^T c on a host matrix (storage: RBL_STORE_*) */
 int  rbl_k_gemv(int storage, int64_t n, int64_t d, const double* D, const double* w, double* v);
 int  rbl_k_gemvt(int storage, int64_t n, int64_t d, const double* D, const double* c, double* q);
