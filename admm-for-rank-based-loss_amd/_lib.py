@@ -69,6 +69,12 @@ SIGNATURES = {
     "rbl_device_count": (C.c_int, []),
     "rbl_create": (C.c_int, [C.POINTER(RblConfig), C.POINTER(_P)]),
     "rbl_destroy": (C.c_int, [_P]),
+    "rbl_create_shared": (C.c_int, [C.POINTER(RblConfig), _P, C.POINTER(_P)]),
+    "rbl_group_create": (C.c_int, [C.POINTER(_P), C.c_int, C.POINTER(_P)]),
+    "rbl_group_destroy": (C.c_int, [_P]),
+    "rbl_group_step": (C.c_int, [_P, C.c_int, C.POINTER(RblStats)]),
+    "rbl_group_solve": (C.c_int, [_P, C.c_int, C.c_int, C.POINTER(RblStats), _P, _P, _P, _P, _I64, C.c_int64]),
+    "rbl_group_counters": (C.c_int, [_P, C.POINTER(C.c_int), _I64, _I64, _I64]),
     "rbl_set_stream": (C.c_int, [_P, _P]),
     "rbl_set_data": (C.c_int, [_P, _P, _P, C.c_int64]),
     "rbl_generate_synthetic": (C.c_int, [_P, C.c_uint64, C.c_double, C.c_double]),
@@ -134,6 +140,8 @@ SIGNATURES = {
     "rbl_k_pav_seq": (C.c_int, [C.c_int, C.c_int64, _P, _P, C.c_double, C.c_double, C.c_int, _P, C.c_int, _P, _P, _P]),
     "rbl_k_gemv": (C.c_int, [C.c_int, C.c_int64, C.c_int64, _P, _P, _P]),
     "rbl_k_gemvt": (C.c_int, [C.c_int, C.c_int64, C.c_int64, _P, _P, _P]),
+    "rbl_k_gemv_multi": (C.c_int, [C.c_int, C.c_int64, C.c_int64, C.c_int, _P, _P, _P]),
+    "rbl_k_gemvt_multi": (C.c_int, [C.c_int, C.c_int64, C.c_int64, C.c_int, _P, _P, _P]),
     "rbl_k_gram": (C.c_int, [C.c_int, C.c_int64, C.c_int64, _P, _P]),
     "rbl_k_wstep": (C.c_int, [C.c_int, C.c_int64, _P, _P, C.c_double, C.c_double, C.c_double, _P, C.c_double, _P,
                               C.POINTER(C.c_int)]),
@@ -286,6 +294,24 @@ def k_gemvt(D, c, storage="f32"):
     q = np.empty(D.shape[1])
     check(load().rbl_k_gemvt(STORAGE[storage], D.shape[0], D.shape[1], ptr(D), ptr(c), ptr(q)))
     return q
+
+
+def k_gemv_multi(D, W, storage="f32"):
+    """V = D [w_1 .. w_k] through the multi-column pass; W: (k, d) -> V: (k, n)"""
+    D, W = f64(D), f64(W)
+    W = np.ascontiguousarray(W.reshape(-1, D.shape[1]))
+    V = np.empty((W.shape[0], D.shape[0]))
+    check(load().rbl_k_gemv_multi(STORAGE[storage], D.shape[0], D.shape[1], W.shape[0], ptr(D), ptr(W), ptr(V)))
+    return V
+
+
+def k_gemvt_multi(D, Cm, storage="f32"):
+    """Q = D^T [c_1 .. c_k] through the multi-column pass; Cm: (k, n) -> Q: (k, d)"""
+    D, Cm = f64(D), f64(Cm)
+    Cm = np.ascontiguousarray(Cm.reshape(-1, D.shape[0]))
+    Q = np.empty((Cm.shape[0], D.shape[1]))
+    check(load().rbl_k_gemvt_multi(STORAGE[storage], D.shape[0], D.shape[1], Cm.shape[0], ptr(D), ptr(Cm), ptr(Q)))
+    return Q
 
 
 def k_gram(D, storage="f32"):

@@ -55,12 +55,14 @@ def _as_matrix(X):
 
 
 class Solver:
-    """One librbl handle.  ``n`` local rows of an ``n_total``-row problem."""
+    """One librbl handle.  ``n`` local rows of an ``n_total``-row problem.  ``share``: another Solver whose device D and
+    Gram matrix this one borrows (include/rbl.h: rbl_create_shared) - no set_data / gram on this handle."""
 
     def __init__(self, n, d, weight_function="erm", loss="binary_cross_entropy", reg=0.0, wstep=_lib.WSTEP_L2,
                  B=None, args=None, smooth_t=1.0, rho0=0.0, tol=1e-4, w_tol=0.0, max_iter=200, storage="f32",
-                 device=0, objective_only=False, n_total=None, row_offset=0):
+                 device=0, objective_only=False, n_total=None, row_offset=0, share=None):
         self._h = None
+        self._share = share           # keeps the data's owner referenced (the library counts references itself)
         self.lib = _lib.load()
         if storage not in _lib.STORAGE:
             raise ValueError(f"storage must be one of {sorted(_lib.STORAGE)}")
@@ -89,7 +91,12 @@ class Solver:
         self.cfg = cfg
         self.n, self.d, self.n_total = cfg.n, cfg.d, cfg.n_total
         h = C.c_void_p()
-        _lib.check(self.lib.rbl_create(C.byref(cfg), C.byref(h)))
+        if share is not None:
+            if not isinstance(share, Solver) or not share._h:
+                raise ValueError("share must be a live Solver")
+            _lib.check(self.lib.rbl_create_shared(C.byref(cfg), share._h, C.byref(h)))
+        else:
+            _lib.check(self.lib.rbl_create(C.byref(cfg), C.byref(h)))
         self._h = h
 
     # ------------------------------------------------------------------ lifetime
@@ -388,6 +395,61 @@ class Solver:
         ms, cnt = C.c_double(0), C.c_int64(0)
         _lib.check(self.lib.rbl_kernel_time(self._h, int(which), C.byref(ms), C.byref(cnt)))
         return ms.value, cnt.value
+
+
+class Group:
+    """Several Solvers on one data matrix iterated together, the two passes over D shared (include/rbl.h:
+    rbl_group_*).  The solvers stay usable on their own after close()."""
+
+    def __init__(self, solvers):
+        self._g = None
+        self.solvers = list(solvers)
+        if not self.solvers:
+            raise ValueError("Group needs at least one solver")
+        if not all(isinstance(s, Solver) and s._h for s in self.solvers):
+            raise ValueError("Group members must be live Solver objects")
+        self.lib = _lib.load()
+        self.k = len(self.solvers)
+        arr = (C.c_void_p * self.k)(*[s._h.value for s in self.solvers])
+        g = C.c_void_p()
+        _lib.check(self.lib.rbl_group_create(arr, self.k, C.byref(g)))
+        self._g = g
+
+    def close(self):
+        if getattr(self, "_g", None):
+            self.lib.rbl_group_destroy(self._g)
+            self._g = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def step(self, want_objective=False):
+        """one ADMM iteration of every member that has not converged -> list of RblStats (member order)"""
+        st = (_lib.RblStats * self.k)()
+        _lib.check(self.lib.rbl_group_step(self._g, 1 if want_objective else 0, st))
+        return list(st)
+
+    def solve(self, max_iter=0, want_objective=False):
+        """-> (list of final RblStats, list of per-member history dicts)"""
+        cap = int(max_iter if max_iter > 0 else max(s.cfg.max_iter for s in self.solvers))
+        hist = {k: np.full((self.k, cap), np.nan) for k in ("objective", "primal", "dual", "rho")}
+        st = (_lib.RblStats * self.k)()
+        iters = np.zeros(self.k, dtype=np.int64)
+        _lib.check(self.lib.rbl_group_solve(self._g, cap, 1 if want_objective else 0, st, _lib.ptr(hist["objective"]),
+                                            _lib.ptr(hist["primal"]), _lib.ptr(hist["dual"]), _lib.ptr(hist["rho"]),
+                                            iters.ctypes.data_as(C.POINTER(C.c_int64)), cap))
+        return list(st), [{name: a[i, :int(iters[i])].copy() for name, a in hist.items()} for i in range(self.k)]
+
+    def counters(self):
+        kpp = C.c_int(0)
+        sv, sq = C.c_int64(0), C.c_int64(0)
+        single = np.zeros(self.k, dtype=np.int64)
+        _lib.check(self.lib.rbl_group_counters(self._g, C.byref(kpp), C.byref(sv), C.byref(sq),
+                                               single.ctypes.data_as(C.POINTER(C.c_int64))))
+        return dict(k_per_pass=kpp.value, shared_v=sv.value, shared_q=sq.value, single_passes=[int(x) for x in single])
 
 
 def reg_terms(w, l2_reg, l1_reg):

@@ -13,6 +13,7 @@
 #include <utility>
 #include <algorithm>
 #include <chrono>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -35,7 +36,14 @@ static std::atomic<int> g_live[64];
 int rbl_live_handles(int device) { return device >= 0 && device < 64 ? g_live[device].load(std::memory_order_relaxed) : 2; }
 
 struct rbl_solver {
-    DevArena mem;   // every device and pinned buffer of the handle
+    DevArena mem;   // every device and pinned buffer of the handle's own (per-problem) state
+    // what depends on (X, y) alone - D, G, the labels, the column statistics, the eigenbasis of G - lives in an arena of
+    // its own: the handle that uploaded the data and the handles that borrow it (rbl_create_shared) hold it together,
+    // the last one to go frees it
+    std::shared_ptr<DevArena> shared;
+    bool borrower = false;         // D and G are another handle's: no upload, no Gram launch on this one
+    int64_t nd_launches = 0;       // n x d launches this handle ran for itself (rbl_group_counters: single_passes)
+    bool in_group = false;         // member of an rbl_group: runs on the group's stream, erm without the single-sweep pass
     rbl_config cfg;
     bool counted = false;
     int64_t n = 0, d = 0, ld = 0, nt = 0, off = 0;
@@ -321,6 +329,7 @@ int build_sigma_prefix(rbl_solver* h) {
 
 int ensure_v(rbl_solver* h) {
     if (h->v_valid) return RBL_OK;
+    h->nd_launches += 1;
     RBL_TRY(launch_gemv(h->storage, h->D, h->n, h->ld, h->w, h->v, h->num_cu, h->stream));
     h->v_valid = true;
     return RBL_OK;
@@ -529,7 +538,8 @@ int rbl_destroy(rbl_solver* h) {
 }  // extern "C"
 
 // everything rbl_create sets up past the checks of its arguments; on failure the caller destroys h
-static int create_setup(rbl_solver* h) {
+// owner != NULL: a borrower of owner's D and G (rbl_create_shared)
+static int create_setup(rbl_solver* h, rbl_solver* owner = nullptr) {
     const rbl_config* cfg = &h->cfg;
     h->n = cfg->n;
     h->d = cfg->d;
@@ -553,11 +563,24 @@ static int create_setup(rbl_solver* h) {
     DevArena& mem = h->mem;
     RBL_TRY(mem.pinned(&h->hstat, 16, hipHostMallocCoherent));
     const int64_t n = h->n, ld = h->ld, nt = h->nt;
-    const size_t dbytes = (size_t)(n > 0 ? n : 1) * ld * h->esz;
-    if (mem.alloc((unsigned char**)&h->D, dbytes) != RBL_OK) {
-        rbl_set_error("hipMalloc of the %lld x %lld matrix (%zu bytes) failed: %s", (long long)n, (long long)ld, dbytes,
-                      hipGetErrorString(hipGetLastError()));
-        return RBL_ERR_NOMEM;
+    if (owner) {
+        h->shared = owner->shared;
+        h->borrower = true;
+        h->D = owner->D;
+        h->G = owner->G;
+        h->ysign = owner->ysign;
+        h->colstats = owner->colstats;
+    } else {
+        h->shared = std::make_shared<DevArena>();
+        const size_t dbytes = (size_t)(n > 0 ? n : 1) * ld * h->esz;
+        if (h->shared->alloc((unsigned char**)&h->D, dbytes) != RBL_OK) {
+            rbl_set_error("hipMalloc of the %lld x %lld matrix (%zu bytes) failed: %s", (long long)n, (long long)ld, dbytes,
+                          hipGetErrorString(hipGetLastError()));
+            return RBL_ERR_NOMEM;
+        }
+        RBL_TRY(h->shared->alloc(&h->ysign, (size_t)n));
+        RBL_TRY(h->shared->alloc(&h->colstats, (size_t)ld * 4));
+        if (!cfg->objective_only) RBL_TRY(h->shared->alloc(&h->G, (size_t)ld * ld));
     }
     RBL_TRY(mem.alloc(&h->w, (size_t)ld));
     RBL_TRY(mem.alloc(&h->w_tmp, (size_t)ld));
@@ -568,18 +591,15 @@ static int create_setup(rbl_solver* h) {
     RBL_TRY(mem.alloc(&h->partials, (size_t)reduce_blocks() * 4));
     if (cfg->objective_only) RBL_TRY(mem.alloc(&h->red, 8));
     RBL_TRY(mem.alloc(&h->red2, 8));
-    RBL_TRY(mem.alloc(&h->ysign, (size_t)n));
-    RBL_TRY(mem.alloc(&h->colstats, (size_t)ld * 4));
     h->slab_bytes = (size_t)gemvt_slab_rows(h->num_cu) * ld * sizeof(double) * 2;
     if (!cfg->objective_only) {
-        size_t gb = gram_slab_bytes(ld, h->num_cu, n > 0 ? n : 1);
+        size_t gb = owner ? 0 : gram_slab_bytes(ld, h->num_cu, n > 0 ? n : 1);   // (a borrower never forms G)
         if (gb > h->slab_bytes) h->slab_bytes = gb;
         RBL_TRY(mem.alloc(&h->w_prev, (size_t)ld));
         // one exchange buffer, summed over ranks in at most one collective per iteration:
         // [q (ld) | D^T lambda seed (ld) | ||z||^2 | primal^2 | sum loss]
         RBL_TRY(mem.alloc(&h->q, (size_t)ld * 2 + 3));
         h->red = h->q + 2 * ld + 1;
-        RBL_TRY(mem.alloc(&h->G, (size_t)ld * ld));
         RBL_TRY(mem.alloc(&h->z, (size_t)n));
         RBL_TRY(mem.alloc(&h->lam, (size_t)n));
         RBL_TRY(mem.alloc(&h->c, (size_t)n));
@@ -624,11 +644,67 @@ static int create_setup(rbl_solver* h) {
         h->rho = cfg->rho0 > 0.0 ? cfg->rho0 : default_rho(cfg->weight_function);
         h->smooth_t = cfg->smooth_t > 0.0 ? cfg->smooth_t : 1.0;
     }
+    if (owner) {
+        // everything rbl_gram_finish derives from G alone
+        h->L = owner->L;
+        h->ww.eig_Vt = owner->ww.eig_Vt;
+        h->ww.eig_V = owner->ww.eig_V;
+        h->ww.eig_lambda = owner->ww.eig_lambda;
+        h->ww.eig_ok = owner->ww.eig_ok;
+        h->eig_sweeps = owner->eig_sweeps;
+        h->data_ready = h->gram_local_done = h->gram_ready = true;
+    }
     RBL_HIP(hipStreamSynchronize(h->stream));
     return RBL_OK;
 }
 
 extern "C" {
+
+int rbl_create_shared(const rbl_config* cfg, rbl_solver* owner, rbl_solver** out) {
+    if (!out) {
+        rbl_set_error("out is NULL");
+        return RBL_ERR_INVALID;
+    }
+    *out = nullptr;
+    RBL_TRY(validate(cfg));
+    if (!owner) {
+        rbl_set_error("create_shared: owner is NULL");
+        return RBL_ERR_INVALID;
+    }
+    const rbl_config& oc = owner->cfg;
+    if (cfg->n != oc.n || cfg->d != oc.d || cfg->n_total != oc.n_total || cfg->row_offset != oc.row_offset ||
+        cfg->storage != oc.storage || cfg->device != oc.device) {
+        rbl_set_error("create_shared: config disagrees with the owner (n=%lld/%lld d=%lld/%lld n_total=%lld/%lld row_offset=%lld/%lld "
+                      "storage=%d/%d device=%d/%d)", (long long)cfg->n, (long long)oc.n, (long long)cfg->d, (long long)oc.d,
+                      (long long)cfg->n_total, (long long)oc.n_total, (long long)cfg->row_offset, (long long)oc.row_offset,
+                      cfg->storage, oc.storage, cfg->device, oc.device);
+        return RBL_ERR_INVALID;
+    }
+    if (!owner->data_ready) {
+        rbl_set_error("create_shared: the owner has no data yet (rbl_set_data / rbl_generate_synthetic first)");
+        return RBL_ERR_STATE;
+    }
+    if (!cfg->objective_only && (!owner->gram_ready || !owner->G)) {
+        rbl_set_error("create_shared: the owner's Gram matrix is not ready (rbl_gram_local + rbl_gram_finish first)");
+        return RBL_ERR_STATE;
+    }
+    RBL_TRY(check_device(nullptr));
+    RBL_HIP(hipSetDevice(oc.device));
+    RBL_HIP(hipStreamSynchronize(owner->stream));   // D and G are complete before another stream reads them
+    rbl_solver* h = new rbl_solver();
+    h->cfg = *cfg;
+    if (cfg->device < 64) {
+        g_live[cfg->device].fetch_add(1, std::memory_order_relaxed);
+        h->counted = true;
+    }
+    const int rc = create_setup(h, owner);
+    if (rc != RBL_OK) {
+        rbl_destroy(h);
+        return rc;
+    }
+    *out = h;
+    return RBL_OK;
+}
 
 int rbl_create(const rbl_config* cfg, rbl_solver** out) {
     if (!out) {
@@ -697,6 +773,7 @@ int zb_resolve(rbl_solver* h, bool* redone = nullptr) {
             if (q_done) {
                 RBL_TRY(launch_make_c(h->n, h->z, h->lam, h->step_rho, h->c, h->stream));
                 RBL_TRY(launch_gemvt(h->storage, h->D, h->n, h->ld, h->c, h->slab, h->q, h->num_cu, h->stream));
+                h->nd_launches += 1;
             }
             if (redone) *redone = true;
         }
@@ -724,6 +801,7 @@ int zb_resolve(rbl_solver* h, bool* redone = nullptr) {
     if (q_done) {
         RBL_TRY(launch_make_c(h->n, h->z, h->lam, h->step_rho, h->c, h->stream));
         RBL_TRY(launch_gemvt(h->storage, h->D, h->n, h->ld, h->c, h->slab, h->q, h->num_cu, h->stream));
+        h->nd_launches += 1;
     }
     if (redone) *redone = true;
     return RBL_OK;
@@ -748,6 +826,15 @@ int cancel_spec(rbl_solver* h) {
         RBL_TRY(cancel_spec(h));  \
     } while (0)
 
+// the data path (upload, generator, Gram matrix) belongs to the handle that owns D and G
+#define RBL_NOT_BORROWER(h, what)                                                                             \
+    do {                                                                                                      \
+        if ((h)->borrower) {                                                                                  \
+            rbl_set_error(what ": this handle borrows its data (rbl_create_shared) - call it on the owner");  \
+            return RBL_ERR_STATE;                                                                             \
+        }                                                                                                     \
+    } while (0)
+
 int rbl_set_stream(rbl_solver* h, void* hip_stream) {
     RBL_ENTER(h);
     RBL_HIP(hipStreamSynchronize(h->stream));
@@ -759,6 +846,7 @@ int rbl_set_stream(rbl_solver* h, void* hip_stream) {
 
 int rbl_set_data(rbl_solver* h, const double* X, const double* y, int64_t ldx) {
     RBL_ENTER(h);
+    RBL_NOT_BORROWER(h, "set_data");
     if (!X || !y || ldx < h->d) {
         rbl_set_error("set_data: bad arguments (ldx=%lld, d=%lld)", (long long)ldx, (long long)h->d);
         return RBL_ERR_INVALID;
@@ -850,6 +938,7 @@ int rbl_set_data(rbl_solver* h, const double* X, const double* y, int64_t ldx) {
 
 int rbl_synth_local(rbl_solver* h, uint64_t seed, double class_sep, double flip_y) {
     RBL_ENTER(h);
+    RBL_NOT_BORROWER(h, "synth_local");
     // positions of the 2 informative + 2 redundant columns, the 2x2 mixing matrix of the redundant ones, the four
     // clusters' covariance matrices A_k (entries uniform in (-1, 1)) and which hypercube vertex each cluster sits on
     // (a random permutation; cluster k belongs to class k % 2) - make_classification's geometry draws - from a small
@@ -892,6 +981,7 @@ int rbl_synth_local(rbl_solver* h, uint64_t seed, double class_sep, double flip_
 
 int rbl_synth_finish(rbl_solver* h) {
     RBL_ENTER(h);
+    RBL_NOT_BORROWER(h, "synth_finish");
     // preprocessing.scale (load_data.py:115): (x - mean) / std with the population std
     const int64_t ld = h->ld;
     std::vector<double> st((size_t)ld * 4, 0.0);
@@ -916,6 +1006,7 @@ int rbl_synth_finish(rbl_solver* h) {
 
 int rbl_generate_synthetic(rbl_solver* h, uint64_t seed, double class_sep, double flip_y) {
     RBL_ENTER(h);
+    RBL_NOT_BORROWER(h, "generate_synthetic");
     if (h->nt != h->n) {
         rbl_set_error("generate_synthetic: sharded problem - use rbl_synth_local, sum RBL_BUF_COLSTATS, rbl_synth_finish");
         return RBL_ERR_STATE;
@@ -934,6 +1025,7 @@ int rbl_get_labels(rbl_solver* h, double* y_out) {
 
 int rbl_gram_local(rbl_solver* h) {
     RBL_ENTER(h);
+    RBL_NOT_BORROWER(h, "gram_local");
     if (!h->data_ready || h->cfg.objective_only) {
         rbl_set_error("gram: no data (or objective-only handle)");
         return RBL_ERR_STATE;
@@ -947,6 +1039,7 @@ int rbl_gram_local(rbl_solver* h) {
 
 int rbl_gram_finish(rbl_solver* h) {
     RBL_ENTER(h);
+    RBL_NOT_BORROWER(h, "gram_finish");
     if (!h->gram_local_done) {
         rbl_set_error("gram_finish before gram_local");
         return RBL_ERR_STATE;
@@ -967,9 +1060,9 @@ int rbl_gram_finish(rbl_solver* h) {
         const size_t nn = (size_t)h->ld * (size_t)h->ld;
         if (!h->ww.eig_Vt) {
             double *Vt = nullptr, *V = nullptr, *lambda = nullptr;
-            RBL_TRY(h->mem.alloc(&Vt, nn));
-            RBL_TRY(h->mem.alloc(&V, nn));
-            RBL_TRY(h->mem.alloc(&lambda, (size_t)h->ld));
+            RBL_TRY(h->shared->alloc(&Vt, nn));   // derived from G alone: shared with the borrowers
+            RBL_TRY(h->shared->alloc(&V, nn));
+            RBL_TRY(h->shared->alloc(&lambda, (size_t)h->ld));
             h->ww.eig_V = V;
             h->ww.eig_lambda = lambda;
             h->ww.eig_Vt = Vt;   // set last: it says the basis buffers are there
@@ -1229,10 +1322,12 @@ int rbl_phase_q(rbl_solver* h) {
         h->s32.q_done = h->s32.used; // ... and of an unsettled 32-bit sort
         RBL_TRY(launch_gemvt(h->storage, h->D, h->n, h->ld, h->c, h->slab, h->q, h->num_cu, h->stream,
                              prof_now(h) ? h->kev[3] : nullptr));
+        h->nd_launches += 1;
         if (prof_now(h)) h->kev_pending[1] = h->n > 0;
         if (h->fused_ok && !h->p_valid) {
             // D^T lambda seeds the d-space recurrence used to predict the primal residual
             RBL_TRY(launch_gemvt(h->storage, h->D, h->n, h->ld, h->lam, h->slab, q_pinit(h), h->num_cu, h->stream));
+            h->nd_launches += 1;
             h->p_pending = true;
         }
     }
@@ -1325,6 +1420,7 @@ int rbl_phase_dual(rbl_solver* h, int want_objective) {
 
     h->fused_ran = false;
     h->fused_v_ran = false;
+    h->nd_launches += 1;
     if (h->fused_ok && h->pred_valid) {
         if (prof_now(h)) RBL_HIP(hipEventRecord(h->kev[4], h->stream));
         RBL_TRY(launch_sweep_erm(h->storage, h->cfg.loss, h->D, h->n, h->ld, h->w, h->z, h->lam, h->v, h->z_next,
@@ -1390,20 +1486,32 @@ static __global__ void k_pack_stats(const double* __restrict__ red, const double
     reinterpret_cast<volatile int*>(hstat + 15)[0] = seq;   // written last: the host polls this word
 }
 
+// part: FIN_ALL = the whole phase; a group step (rbl_group_step) enqueues every member's statistics kernel first
+// (FIN_ENQUEUE), waits once for the last one - they run in stream order - and then digests each (FIN_DIGEST: no wait).
+enum { FIN_ALL = 0, FIN_ENQUEUE = 1, FIN_DIGEST = 2 };
+static int phase_finish_part(rbl_solver* h, rbl_stats* out, int part);
+
 int rbl_phase_finish(rbl_solver* h, rbl_stats* out) {
     RBL_ENTER_ITER(h);
+    return phase_finish_part(h, out, FIN_ALL);
+}
+
+static int phase_finish_part(rbl_solver* h, rbl_stats* out, int part) {
     float spec_ms = 0.f;   // the w-step of THIS iteration ran before its ev[0]: add its time back
     if (h->spec_timed) (void)hipEventElapsedTime(&spec_ms, h->ev_spec[0], h->ev_spec[1]);
     h->spec_timed = false;
-    if (h->phase_timing) RBL_HIP(hipEventRecord(h->ev[5], h->stream));
+    if (h->phase_timing && part != FIN_DIGEST) RBL_HIP(hipEventRecord(h->ev[5], h->stream));
     volatile int* seq_word = reinterpret_cast<volatile int*>(h->hstat + 15);
     const int pack_seq = (int)((h->iter & 0x3fffffff) + 1);
-    *seq_word = 0;
-    hipLaunchKernelGGL(k_pack_stats, dim3(1), dim3(64), 0, h->stream, h->red, h->red2,
-                       h->fused_ran ? h->pred : (const double*)nullptr,
-                       (h->sorted_path && h->cfg.weight_function == RBL_W_EHRM) ? h->pw.branch : (const int*)nullptr,
-                       h->sorted_path ? h->pw.counters : (const unsigned*)nullptr, h->zd_err, h->hstat, pack_seq);
-    RBL_HIP(hipGetLastError());
+    if (part != FIN_DIGEST) {
+        *seq_word = 0;
+        hipLaunchKernelGGL(k_pack_stats, dim3(1), dim3(64), 0, h->stream, h->red, h->red2,
+                           h->fused_ran ? h->pred : (const double*)nullptr,
+                           (h->sorted_path && h->cfg.weight_function == RBL_W_EHRM) ? h->pw.branch : (const int*)nullptr,
+                           h->sorted_path ? h->pw.counters : (const unsigned*)nullptr, h->zd_err, h->hstat, pack_seq);
+        RBL_HIP(hipGetLastError());
+    }
+    if (part == FIN_ENQUEUE) return RBL_OK;   // (group members run the two-pass iteration: nothing to enqueue ahead)
     // Single-sweep lasso iterations: everything the next w-step needs is on the device already
     // (q from the pass, rho_{k+1} = pred[0]), so it is enqueued now and runs while the host waits
     // for and digests this iteration's statistics.  If they say "converged" or "rho was
@@ -1412,7 +1520,7 @@ int rbl_phase_finish(rbl_solver* h, rbl_stats* out) {
         const char* e = getenv("RBL_NO_SPECULATE");
         return e && e[0] == '1';
     }();
-    const bool try_spec = h->fused_ran && h->p_valid && h->cfg.wstep == RBL_WSTEP_L1 && !no_spec;
+    const bool try_spec = part == FIN_ALL && h->fused_ran && h->p_valid && h->cfg.wstep == RBL_WSTEP_L1 && !no_spec;
     if (try_spec) {
         if (h->phase_timing) RBL_HIP(hipEventRecord(h->ev_spec[0], h->stream));
         bool fs_pending = false;
@@ -1422,7 +1530,7 @@ int rbl_phase_finish(rbl_solver* h, rbl_stats* out) {
                                    217.0 * (double)h->d, h->pred, h->red2, h->stream, h->pred));
         if (h->phase_timing) RBL_HIP(hipEventRecord(h->ev_spec[1], h->stream));
     }
-    rbl_spin_wait(seq_word, 0, h->stream);
+    if (part == FIN_ALL) rbl_spin_wait(seq_word, 0, h->stream);
     if (*seq_word != pack_seq) {
         rbl_set_error("phase_finish: the statistics kernel did not complete");
         (void)hipGetLastError();
@@ -2145,6 +2253,301 @@ int rbl_info(rbl_solver* h, int64_t* ld, int* num_cu, double* lipschitz) {
 
 }  // extern "C"
 
+// ======================================================================== groups: K problems on one D
+// One ADMM iteration of every live member per rbl_group_step, the two n x d passes shared (sweep_multi.hip).
+struct rbl_group {
+    DevArena mem;
+    std::vector<rbl_solver*> m;
+    std::vector<char> live, saved_fused;
+    std::vector<hipStream_t> saved_stream;
+    std::vector<int64_t> base_launches;
+    std::vector<rbl_stats> last;
+    std::vector<int> syncs;          // host waits of each member's own calls in the step in flight
+    hipStream_t stream = nullptr;    // every member runs on it while the group exists: one order for all launches
+    int device = 0, kpp = 1;
+    bool shared_passes = false;      // the width is in the multi-column kernels' range
+    double* slab = nullptr;
+    int64_t shared_v = 0, shared_q = 0;
+};
+
+namespace {
+// runs a member's own calls and books the host waits they made on that member
+struct SyncBook {
+    int& slot;
+    int s0;
+    explicit SyncBook(int& sl) : slot(sl), s0(g_host_syncs) {}
+    ~SyncBook() { slot += g_host_syncs - s0; }
+};
+}  // namespace
+
+extern "C" {
+
+int rbl_group_create(rbl_solver* const* members, int k, rbl_group** out) {
+    if (!out) {
+        rbl_set_error("group_create: out is NULL");
+        return RBL_ERR_INVALID;
+    }
+    *out = nullptr;
+    if (!members || k < 1 || k > 64) {
+        rbl_set_error("group_create: 1..64 members (got %d)", k);
+        return RBL_ERR_INVALID;
+    }
+    for (int i = 0; i < k; ++i) {
+        rbl_solver* h = members[i];
+        if (!h) {
+            rbl_set_error("group_create: member %d is NULL", i);
+            return RBL_ERR_INVALID;
+        }
+        for (int j = 0; j < i; ++j)
+            if (members[j] == h) {
+                rbl_set_error("group_create: member %d is listed twice", i);
+                return RBL_ERR_INVALID;
+            }
+        if (h->in_group) {
+            rbl_set_error("group_create: member %d already belongs to a group", i);
+            return RBL_ERR_INVALID;
+        }
+        if (h->shared != members[0]->shared || h->D != members[0]->D) {
+            rbl_set_error("group_create: member %d does not share member 0's data (rbl_create_shared)", i);
+            return RBL_ERR_INVALID;
+        }
+        if (h->nt != h->n) {
+            rbl_set_error("group_create: member %d is a row shard (n=%lld of %lld): groups are single-process problems", i,
+                          (long long)h->n, (long long)h->nt);
+            return RBL_ERR_INVALID;
+        }
+        if (h->cfg.objective_only) {
+            rbl_set_error("group_create: member %d is an objective-only handle", i);
+            return RBL_ERR_INVALID;
+        }
+    }
+    rbl_solver* h0 = members[0];
+    RBL_HIP(hipSetDevice(h0->cfg.device));
+    for (int i = 0; i < k; ++i) {
+        RBL_TRY(require_ready(members[i]));
+        RBL_TRY(zb_resolve(members[i]));
+        RBL_TRY(cancel_spec(members[i]));
+        RBL_HIP(hipStreamSynchronize(members[i]->stream));
+    }
+    std::unique_ptr<rbl_group> g(new rbl_group());
+    g->device = h0->cfg.device;
+    RBL_HIP(hipStreamCreateWithFlags(&g->stream, hipStreamNonBlocking));
+    g->shared_passes = h0->n > 0 && sweep_multi_supported(h0->storage, h0->ld);
+    g->kpp = g->shared_passes ? sweep_multi_k(h0->storage, h0->ld) : 1;
+    if (g->shared_passes) {
+        const int rc = g->mem.alloc(&g->slab, sweep_multi_slab_doubles(h0->ld, h0->num_cu));
+        if (rc != RBL_OK) {
+            (void)hipStreamDestroy(g->stream);
+            return rc;
+        }
+    }
+    rbl_stats zero;
+    std::memset(&zero, 0, sizeof(zero));
+    for (int i = 0; i < k; ++i) {
+        rbl_solver* h = members[i];
+        g->m.push_back(h);
+        g->live.push_back(1);
+        g->saved_fused.push_back(h->fused_ok ? 1 : 0);
+        g->saved_stream.push_back(h->stream);
+        g->base_launches.push_back(h->nd_launches);
+        g->last.push_back(zero);
+        g->syncs.push_back(0);
+        h->in_group = true;
+        h->stream = g->stream;
+        // two-pass structure for every member: whatever a single-sweep erm pass prepared ahead is dropped
+        h->fused_ok = false;
+        h->z_ready = h->p_valid = h->p_pending = h->pred_valid = false;
+    }
+    *out = g.release();
+    return RBL_OK;
+}
+
+int rbl_group_destroy(rbl_group* g) {
+    if (!g) return RBL_OK;
+    (void)hipSetDevice(g->device);
+    if (g->stream) (void)hipStreamSynchronize(g->stream);
+    for (size_t i = 0; i < g->m.size(); ++i) {
+        rbl_solver* h = g->m[i];
+        (void)zb_resolve(h);   // a verdict still pending was written on the group's stream
+        if (h->stream == g->stream) h->stream = g->saved_stream[i];
+        h->fused_ok = g->saved_fused[i] != 0;
+        h->in_group = false;
+    }
+    if (g->stream) {
+        (void)hipStreamSynchronize(g->stream);
+        (void)hipStreamDestroy(g->stream);
+    }
+    delete g;   // g->mem frees the slab
+    return RBL_OK;
+}
+
+int rbl_group_step(rbl_group* g, int want_objective, rbl_stats* out) {
+    if (!g) {
+        rbl_set_error("group handle is NULL");
+        return RBL_ERR_INVALID;
+    }
+    RBL_HIP(hipSetDevice(g->device));
+    const int K = (int)g->m.size();
+    std::vector<int> idx;
+    for (int i = 0; i < K; ++i)
+        if (g->live[i]) idx.push_back(i);
+    hipStream_t s = g->stream;
+    for (int i : idx) g->syncs[i] = 0;
+    // A + B: every member's own z-step
+    for (int i : idx) {
+        SyncBook book(g->syncs[i]);
+        RBL_TRY(rbl_phase_m(g->m[i]));
+        RBL_TRY(rbl_phase_z(g->m[i], nullptr));
+    }
+    // C: q_k = D^T c_k, D read once per kpp members
+    if (g->shared_passes) {
+        for (int i : idx) {
+            rbl_solver* h = g->m[i];
+            if (h->sorted_path && !h->zb.c_ready) RBL_TRY(launch_make_c(h->n, h->z, h->lam, h->step_rho, h->c, s));
+            h->zb.c_ready = false;
+            h->zb.q_done = h->zb.used;     // an unsettled z-step's q is redone with it, by the member alone (zb_resolve)
+            h->s32.q_done = h->s32.used;
+        }
+        for (size_t b = 0; b < idx.size(); b += (size_t)g->kpp) {
+            const int kk = (int)std::min(idx.size() - b, (size_t)g->kpp);
+            const double* c[RBL_MULTI_KMAX];
+            double* q[RBL_MULTI_KMAX];
+            for (int j = 0; j < kk; ++j) {
+                c[j] = g->m[idx[b + j]]->c;
+                q[j] = g->m[idx[b + j]]->q;
+            }
+            rbl_solver* h0 = g->m[idx[b]];
+            RBL_TRY(launch_sweep_q_multi(h0->storage, h0->D, h0->n, h0->ld, kk, c, g->slab, q, h0->num_cu, s));
+            g->shared_q += 1;
+        }
+        for (int i : idx) {
+            rbl_solver* h = g->m[i];
+            h->pending_mask = 1;
+            h->z_ready = false;
+            if (h->phase_timing) RBL_HIP(hipEventRecord(h->ev[2], s));
+        }
+    } else {
+        for (int i : idx) {
+            SyncBook book(g->syncs[i]);
+            RBL_TRY(rbl_phase_q(g->m[i]));
+        }
+    }
+    // D: every member's own w-step (a z-step that was not certified is redone here, with its own q)
+    for (int i : idx) {
+        SyncBook book(g->syncs[i]);
+        RBL_TRY(rbl_phase_w(g->m[i]));
+    }
+    // E: v_k = D w_k, lambda_k += rho_k (z_k - v_k), the primal residuals - D read once per kpp members
+    if (g->shared_passes) {
+        for (size_t b = 0; b < idx.size(); b += (size_t)g->kpp) {
+            const int kk = (int)std::min(idx.size() - b, (size_t)g->kpp);
+            const double *w[RBL_MULTI_KMAX], *z[RBL_MULTI_KMAX];
+            double *lam[RBL_MULTI_KMAX], *v[RBL_MULTI_KMAX], *part[RBL_MULTI_KMAX], *red[RBL_MULTI_KMAX], rho[RBL_MULTI_KMAX];
+            for (int j = 0; j < kk; ++j) {
+                rbl_solver* h = g->m[idx[b + j]];
+                w[j] = h->w;
+                z[j] = h->z;
+                lam[j] = h->lam;
+                v[j] = h->v;
+                part[j] = h->partials;
+                red[j] = h->red;
+                rho[j] = h->step_rho;
+            }
+            rbl_solver* h0 = g->m[idx[b]];
+            RBL_TRY(launch_sweep_v_multi(h0->storage, h0->D, h0->n, h0->ld, kk, w, z, lam, v, rho, part, red, h0->num_cu, s));
+            g->shared_v += 1;
+        }
+        for (int i : idx) {
+            rbl_solver* h = g->m[i];
+            h->fused_ran = false;
+            h->fused_v_ran = true;
+            h->v_valid = true;
+            h->pending_mask = 2;
+            h->want_obj = want_objective;
+            h->obj_is_risk = false;
+            if (h->phase_timing) RBL_HIP(hipEventRecord(h->ev[4], s));
+            if (want_objective && h->sorted_path) {
+                RBL_TRY(risk_from_v(h, h->v, h->red + 1));
+                h->obj_is_risk = true;
+            } else if (want_objective) {
+                RBL_TRY(launch_loss_sum(h->cfg.loss, h->n, h->v, 1.0, h->partials, h->red + 1, s));   // objective.py:11-24
+            }
+        }
+    } else {
+        for (int i : idx) {
+            SyncBook book(g->syncs[i]);
+            RBL_TRY(rbl_phase_dual(g->m[i], want_objective));
+        }
+    }
+    // F: all statistics kernels first, ONE host wait (the last one's word: they complete in stream order), then the
+    // stop tests and schedules
+    for (int i : idx) RBL_TRY(phase_finish_part(g->m[i], nullptr, FIN_ENQUEUE));
+    if (!idx.empty()) {
+        rbl_solver* hl = g->m[idx.back()];
+        SyncBook book(g->syncs[idx[0]]);
+        rbl_spin_wait(reinterpret_cast<volatile int*>(hl->hstat + 15), 0, s);
+    }
+    for (int i : idx) {
+        g_host_syncs = g->syncs[i];
+        RBL_TRY(phase_finish_part(g->m[i], &g->last[i], FIN_DIGEST));
+        if (g->last[i].converged) g->live[i] = 0;   // frozen where its own rbl_solve would have stopped
+    }
+    g_host_syncs = 0;
+    if (out)
+        for (int i = 0; i < K; ++i) out[i] = g->last[i];
+    return RBL_OK;
+}
+
+int rbl_group_solve(rbl_group* g, int max_iter, int want_objective, rbl_stats* last, double* hist_objective,
+                    double* hist_primal, double* hist_dual, double* hist_rho, int64_t* iters, int64_t cap) {
+    if (!g) {
+        rbl_set_error("group handle is NULL");
+        return RBL_ERR_INVALID;
+    }
+    const int K = (int)g->m.size();
+    if (max_iter <= 0)
+        for (int i = 0; i < K; ++i) max_iter = std::max(max_iter, (int)g->m[i]->cfg.max_iter);
+    std::vector<int64_t> done((size_t)K, 0);
+    for (int it = 0; it < max_iter; ++it) {
+        bool any = false;
+        std::vector<char> was_live(g->live);
+        for (int i = 0; i < K; ++i) any = any || was_live[i];
+        if (!any) break;
+        RBL_TRY(rbl_group_step(g, want_objective, nullptr));
+        for (int i = 0; i < K; ++i) {
+            if (!was_live[i]) continue;
+            const rbl_stats& st = g->last[i];
+            const int64_t k = done[i]++;
+            if (k < cap) {
+                if (hist_objective) hist_objective[i * cap + k] = st.objective;
+                if (hist_primal) hist_primal[i * cap + k] = st.primal;
+                if (hist_dual) hist_dual[i * cap + k] = st.dual;
+                if (hist_rho) hist_rho[i * cap + k] = st.rho;
+            }
+        }
+    }
+    for (int i = 0; i < K; ++i) {
+        if (iters) iters[i] = done[i];
+        if (last) last[i] = g->last[i];
+    }
+    return RBL_OK;
+}
+
+int rbl_group_counters(rbl_group* g, int* k_per_pass, int64_t* shared_v, int64_t* shared_q, int64_t* single_passes) {
+    if (!g) {
+        rbl_set_error("group handle is NULL");
+        return RBL_ERR_INVALID;
+    }
+    if (k_per_pass) *k_per_pass = g->kpp;
+    if (shared_v) *shared_v = g->shared_v;
+    if (shared_q) *shared_q = g->shared_q;
+    if (single_passes)
+        for (size_t i = 0; i < g->m.size(); ++i) single_passes[i] = g->m[i]->nd_launches - g->base_launches[i];
+    return RBL_OK;
+}
+
+}  // extern "C"
+
 // =================================================== kernel-level entry points (host buffers)
 // They run on the same workspace allocators as the solver handle (alloc_sort, alloc_pav, alloc_prefix, alloc_wstep).
 namespace {
@@ -2358,6 +2761,82 @@ int rbl_k_gemvt(int storage, int64_t n, int64_t d, const double* D, const double
     RBL_TRY(sc.mem.alloc(&dq, (size_t)ld));
     RBL_TRY(launch_gemvt(storage, Dd, n, ld, dc, slab, dq, num_cu, sc.s));
     RBL_HIP(hipMemcpyAsync(q, dq, sizeof(double) * d, hipMemcpyDeviceToHost, sc.s));
+    RBL_HIP(hipStreamSynchronize(sc.s));
+    return RBL_OK;
+}
+
+int rbl_k_gemv_multi(int storage, int64_t n, int64_t d, int k, const double* D, const double* W, double* V) {
+    if (k < 1 || k > 64 || d <= 0) {
+        rbl_set_error("rbl_k_gemv_multi: 1..64 columns, d > 0");
+        return RBL_ERR_INVALID;
+    }
+    Scratch sc;
+    int num_cu = 256;
+    RBL_TRY(scratch_begin(sc, &num_cu));
+    if (n <= 0) return RBL_OK;
+    void* Dd = nullptr;
+    int64_t ld = 0;
+    RBL_TRY(upload_matrix(sc, storage, n, d, D, &Dd, &ld));
+    std::vector<double> wp((size_t)ld * k, 0.0);
+    for (int j = 0; j < k; ++j)
+        for (int64_t i = 0; i < d; ++i) wp[(size_t)j * ld + i] = W[(size_t)j * d + i];
+    double *dw = nullptr, *dv = nullptr;
+    RBL_TRY(sc.upload(&dw, wp.data(), wp.size()));
+    RBL_TRY(sc.mem.alloc(&dv, (size_t)n * k));
+    const bool multi = sweep_multi_supported(storage, ld);
+    const int kpp = multi ? sweep_multi_k(storage, ld) : 1;
+    for (int j0 = 0; j0 < k; j0 += kpp) {
+        const int kk = std::min(kpp, k - j0);
+        if (!multi) {   // outside the multi-column kernels' widths: the single-column pass per column
+            RBL_TRY(launch_gemv(storage, Dd, n, ld, dw + (size_t)j0 * ld, dv + (size_t)j0 * n, num_cu, sc.s));
+            continue;
+        }
+        const double* w[RBL_MULTI_KMAX];
+        double* v[RBL_MULTI_KMAX];
+        for (int j = 0; j < kk; ++j) {
+            w[j] = dw + (size_t)(j0 + j) * ld;
+            v[j] = dv + (size_t)(j0 + j) * n;
+        }
+        RBL_TRY(launch_sweep_v_multi(storage, Dd, n, ld, kk, w, nullptr, nullptr, v, nullptr, nullptr, nullptr, num_cu, sc.s));
+    }
+    RBL_HIP(hipMemcpyAsync(V, dv, sizeof(double) * n * k, hipMemcpyDeviceToHost, sc.s));
+    RBL_HIP(hipStreamSynchronize(sc.s));
+    return RBL_OK;
+}
+
+int rbl_k_gemvt_multi(int storage, int64_t n, int64_t d, int k, const double* D, const double* Cm, double* Q) {
+    if (k < 1 || k > 64 || d <= 0) {
+        rbl_set_error("rbl_k_gemvt_multi: 1..64 columns, d > 0");
+        return RBL_ERR_INVALID;
+    }
+    Scratch sc;
+    int num_cu = 256;
+    RBL_TRY(scratch_begin(sc, &num_cu));
+    void* Dd = nullptr;
+    int64_t ld = 0;
+    RBL_TRY(upload_matrix(sc, storage, n > 0 ? n : 0, d, D, &Dd, &ld));
+    double *dc = nullptr, *slab = nullptr, *dq = nullptr;
+    RBL_TRY(sc.upload(&dc, Cm, (size_t)(n > 0 ? n : 0) * k));
+    const bool multi = n > 0 && sweep_multi_supported(storage, ld);
+    const int kpp = multi ? sweep_multi_k(storage, ld) : 1;
+    RBL_TRY(sc.mem.alloc(&slab, multi ? sweep_multi_slab_doubles(ld, num_cu) : (size_t)gemvt_slab_rows(num_cu) * ld));
+    RBL_TRY(sc.mem.alloc(&dq, (size_t)ld * k));
+    for (int j0 = 0; j0 < k; j0 += kpp) {
+        const int kk = std::min(kpp, k - j0);
+        if (!multi) {
+            RBL_TRY(launch_gemvt(storage, Dd, n, ld, dc + (size_t)j0 * (n > 0 ? n : 0), slab, dq + (size_t)j0 * ld, num_cu, sc.s));
+            continue;
+        }
+        const double* c[RBL_MULTI_KMAX];
+        double* q[RBL_MULTI_KMAX];
+        for (int j = 0; j < kk; ++j) {
+            c[j] = dc + (size_t)(j0 + j) * n;
+            q[j] = dq + (size_t)(j0 + j) * ld;
+        }
+        RBL_TRY(launch_sweep_q_multi(storage, Dd, n, ld, kk, c, slab, q, num_cu, sc.s));
+    }
+    for (int j = 0; j < k; ++j)
+        RBL_HIP(hipMemcpyAsync(Q + (size_t)j * d, dq + (size_t)j * ld, sizeof(double) * d, hipMemcpyDeviceToHost, sc.s));
     RBL_HIP(hipStreamSynchronize(sc.s));
     return RBL_OK;
 }

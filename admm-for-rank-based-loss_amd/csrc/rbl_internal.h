@@ -334,6 +334,19 @@ int launch_sweep_q(int storage, const void* D, int64_t n, int64_t ld, const doub
                    hipStream_t s, hipEvent_t main_done);
 int launch_sweep_v(int storage, const void* D, int64_t n, int64_t ld, const double* w, const double* z, double* lam,
                    double* v, double rho, double* partials, double* red, int num_cu, hipStream_t s, hipEvent_t main_done);
+// ---- sweep_multi.hip: the two passes for up to RBL_MULTI_KMAX problems on one D per launch (widths of sweep_v_supported)
+#define RBL_MULTI_KMAX 4
+bool sweep_multi_supported(int storage, int64_t ld);
+int sweep_multi_k(int storage, int64_t ld);                      // columns one launch carries at this width
+size_t sweep_multi_slab_doubles(int64_t ld, int num_cu);         // slab of launch_sweep_q_multi
+// v_j = D w_j; z != NULL: also lambda_j += rho_j (z_j - v_j) and red_j[0] = sum (z_j - v_j)^2, red_j[1] = 0
+// (partials_j: 3 doubles per CU).  Arrays of k host-side pointers / values, 1 <= k <= RBL_MULTI_KMAX.
+int launch_sweep_v_multi(int storage, const void* D, int64_t n, int64_t ld, int k, const double* const* w, const double* const* z,
+                         double* const* lam, double* const* v, const double* rho, double* const* partials, double* const* red,
+                         int num_cu, hipStream_t s);
+// q_j = D^T c_j
+int launch_sweep_q_multi(int storage, const void* D, int64_t n, int64_t ld, int k, const double* const* c, double* slab,
+                         double* const* q, int num_cu, hipStream_t s);
 int launch_symv(const double* G, int64_t ld, const double* x, double* y, hipStream_t s);
 int launch_symv_ab(const double* G, int64_t ld, const double* x, double* y, double alpha, double beta, hipStream_t s);   // y = alpha G x + beta x
 

@@ -33,7 +33,7 @@ _ON_DEVICE = _OnDevice()
 class Optimizer:
     def __init__(self, X, y, weight_function="erm", loss="binary_cross_entropy", l2_reg=None, l1_reg=None,
                  B=None, n_class=None, args=None, w0=None, max_iter=200, tol=1e-4, storage="f32", device=0,
-                 _wstep=None, _smooth_t=1.0):
+                 _wstep=None, _smooth_t=1.0, share_data=None):
         # argument checks in the reference's order (objective first :22, then :55-68)
         _solver.check_problem(weight_function, loss, B, args)
         if l1_reg is None and l2_reg is None:
@@ -55,11 +55,22 @@ class Optimizer:
         self.weight_function = weight_function                                                # :73
         self.l1_reg, self.l2_reg = l1_reg, l2_reg
         wstep = _wstep if _wstep is not None else (_lib.WSTEP_L1 if self.w_flag == 1 else _lib.WSTEP_L2)
+        # share_data: another solver of this package built on the same (X, y) - its device D and DTD are borrowed
+        share = None
+        if share_data is not None:
+            share = getattr(share_data, "_s", share_data)
+            if not isinstance(share, _solver.Solver):
+                raise ValueError("share_data must be an ADMMmethod / smoothADMMmethod (or a Solver) on the same (X, y)")
+            if (share.n, share.d) != (self.num_row, self.num_feature) or share.n_total != share.n:
+                raise ValueError(f"share_data holds a {(share.n_total, share.d)} problem, X is {Xm.shape}")
+            if share.cfg.storage != _lib.STORAGE.get(storage, -1) or share.cfg.device != int(device):
+                raise ValueError("share_data was built with another storage type or device")
         self._s = _solver.Solver(self.num_row, self.num_feature, weight_function, loss, reg=self.reg, wstep=wstep,
                                  B=B, args=args, smooth_t=_smooth_t, tol=tol, max_iter=max_iter, storage=storage,
-                                 device=device)
-        self._s.set_data(Xm, y)                                                               # :23 D = -y*X
-        self._s.gram()                                                                        # :24 DTD
+                                 device=device, share=share)
+        if share is None:
+            self._s.set_data(Xm, y)                                                           # :23 D = -y*X
+            self._s.gram()                                                                    # :24 DTD
         if w0 is not None:                                                                    # :39-40
             self._s.set_state(w=np.asarray(w0, dtype=np.float64).reshape(-1))
         self.objective = rankbasedObjective(None, None, weight_function, loss, l2_reg, l1_reg, B, n_class, args,
@@ -120,9 +131,9 @@ class Optimizer:
 
     # ---- logging (:77-86) ------------------------------------------------------------------
     def start_store(self, X, y, weight_function="erm", loss="binary_cross_entropy", B=None, l2_reg=None,
-                    l1_reg=None, n_class=None, args=None):
+                    l1_reg=None, n_class=None, args=None, _share_data=None):
         self.test_objective = rankbasedObjective(X, y, weight_function, loss, l2_reg, l1_reg, B, n_class, args,
-                                                 storage=self._storage, device=self._device)
+                                                 storage=self._storage, device=self._device, _share_data=_share_data)
         w = self.w
         self._s.profile_kernels(2)     # z_time / w_time below come from HIP events around the phases
         self.w_time = [0]
@@ -190,9 +201,9 @@ class Optimizer:
 
 class ADMMmethod(Optimizer):
     def __init__(self, X, y, weight_function="erm", loss="binary_cross_entropy", l2_reg=None, l1_reg=None, B=None,
-                 n_class=None, args=None, w0=None, max_iter=200, tol=1e-4, storage="f32", device=0):
+                 n_class=None, args=None, w0=None, max_iter=200, tol=1e-4, storage="f32", device=0, share_data=None):
         super().__init__(X, y, weight_function, loss, l2_reg, l1_reg, B, n_class, args, w0, max_iter, tol,
-                         storage=storage, device=device)
+                         storage=storage, device=device, share_data=share_data)
 
     def start_store(self, X, y, weight_function="erm", loss="binary_cross_entropy", B=None, l2_reg=None,
                     l1_reg=None, n_class=None, args=None):
@@ -211,10 +222,10 @@ class ADMMmethod(Optimizer):
 
 class smoothADMMmethod(Optimizer):
     def __init__(self, X, y, weight_function="erm", loss="binary_cross_entropy", B=None, l2_reg=None, l1_reg=None,
-                 n_class=None, args=None, w0=None, t=1, max_iter=200, tol=1e-4, storage="f32", device=0):
+                 n_class=None, args=None, w0=None, t=1, max_iter=200, tol=1e-4, storage="f32", device=0, share_data=None):
         wstep = _lib.WSTEP_SMOOTH_L1 if l1_reg is not None else None
         super().__init__(X, y, weight_function, loss, l2_reg, l1_reg, B, n_class, args, w0, max_iter, tol,
-                         storage=storage, device=device, _wstep=wstep, _smooth_t=float(t))
+                         storage=storage, device=device, _wstep=wstep, _smooth_t=float(t), share_data=share_data)
 
     @property
     def t(self):
@@ -241,3 +252,115 @@ class smoothADMMmethod(Optimizer):
 
     def final_res(self):
         return super().final_res()
+
+
+class ADMMgroup:
+    """Several problems on ONE (X, y) - a regularisation path, superquantile levels, AoRR (k, m) pairs, ADMM beside
+    sADMM - iterated together: the data is uploaded once, D and DTD are formed once, and every iteration reads D once
+    for several problems in each of its two passes (include/rbl.h: rbl_group_*).
+
+    ``problems``: a list of dicts with the reference's constructor keywords (``weight_function, loss, l2_reg, l1_reg, B,
+    args, w0``; ``smooth=True`` and ``t=`` make the member a smoothADMMmethod).  ``solvers`` are ordinary ADMMmethod /
+    smoothADMMmethod objects; start_store / main_loop / final_res mirror the single-solver calls and return lists in
+    the order of ``problems``."""
+
+    _KEYS = ("weight_function", "loss", "l2_reg", "l1_reg", "B", "args", "w0", "smooth", "t")
+
+    def __init__(self, X, y, problems, storage="f32", device=0, max_iter=200, tol=1e-4):
+        if not isinstance(problems, (list, tuple)) or len(problems) == 0:
+            raise ValueError("ADMMgroup needs a non-empty list of problems")
+        if len(problems) > 64:
+            raise ValueError("ADMMgroup: at most 64 problems in one group")
+        self.problems = []
+        for k, pr in enumerate(problems):            # every argument error before any device call
+            if not isinstance(pr, dict):
+                raise ValueError(f"problem {k}: expected a dict of constructor keywords")
+            unknown = sorted(set(pr) - set(self._KEYS))
+            if unknown:
+                raise ValueError(f"problem {k}: unknown keyword(s) {unknown}; options: {list(self._KEYS)}")
+            pr = dict(pr)
+            pr.setdefault("weight_function", "erm")
+            pr.setdefault("loss", "binary_cross_entropy")
+            try:
+                _solver.check_problem(pr["weight_function"], pr["loss"], pr.get("B"), pr.get("args"))
+                if pr.get("l1_reg") is None and pr.get("l2_reg") is None:
+                    raise ValueError("More arguments: l1_reg or l2_reg not l1_reg and l2_reg!")
+                if pr.get("B") is not None and pr["weight_function"] != "ehrm":
+                    raise ValueError(f"Unrecognized weight_function '{pr['weight_function']}'! Options: ['ehrm']")
+                if pr["weight_function"] == "ehrm" and pr.get("B") is None:
+                    raise ValueError("ehrm needs the reference point B")
+                if "t" in pr and not pr.get("smooth"):
+                    raise ValueError("t is the smoothing parameter of smooth=True members")
+            except ValueError as e:
+                raise ValueError(f"problem {k}: {e}") from None
+            self.problems.append(pr)
+        if storage not in _lib.STORAGE:
+            raise ValueError(f"storage must be one of {sorted(_lib.STORAGE)}")
+        self.max_iter, self.tol = max_iter, tol
+        self.solvers = []
+        for pr in self.problems:
+            kw = {k: pr.get(k) for k in ("l2_reg", "l1_reg", "B", "args", "w0")}
+            share = self.solvers[0] if self.solvers else None
+            if pr.get("smooth"):
+                s = smoothADMMmethod(X, y, pr["weight_function"], pr["loss"], t=pr.get("t", 1), max_iter=max_iter, tol=tol,
+                                     storage=storage, device=device, share_data=share, **kw)
+            else:
+                s = ADMMmethod(X, y, pr["weight_function"], pr["loss"], max_iter=max_iter, tol=tol, storage=storage,
+                               device=device, share_data=share, **kw)
+            self.solvers.append(s)
+        self._group = _solver.Group([s._s for s in self.solvers])
+        self.store = False
+        self.last = [None] * len(self.solvers)
+        self.iterations = [0] * len(self.solvers)
+
+    def counters(self):
+        return self._group.counters()
+
+    def close(self):
+        self._group.close()
+
+    def start_store(self, X_test, y_test):
+        """test-set objectives of every member (Optimizer.start_store) on ONE uploaded test matrix"""
+        first = None
+        for s, pr in zip(self.solvers, self.problems):
+            Optimizer.start_store(s, X_test, y_test, pr["weight_function"], pr["loss"], pr.get("B"), pr.get("l2_reg"),
+                                  pr.get("l1_reg"), None, pr.get("args"), _share_data=first)
+            first = first or s.test_objective
+        self.store = True
+
+    def main_loop(self, verbose=True):
+        """up to max_iter group iterations; a member that converges is frozen where its own main_loop would have
+        stopped.  Returns the list of w."""
+        t_start = time.time()
+        live = [True] * len(self.solvers)
+        for i in range(self.max_iter):
+            if not any(live):
+                break
+            stats = self._group.step(want_objective=self.store or verbose)
+            for k, (s, st) in enumerate(zip(self.solvers, stats)):
+                if not live[k]:
+                    continue
+                self.last[k] = s._last = st
+                self.iterations[k] = i + 1
+                if s.store:
+                    s.z_time.append(st.ms_z / 1e3 + s.z_time[i])
+                    s.w_time.append((st.ms_q + st.ms_w) / 1e3 + s.w_time[i])
+                if st.converged:
+                    live[k] = False
+                    print(f'problem {k}: algorithm converges within tolerance')
+                    print('iter_num=', i, 'primal_feasibility: ', st.primal, 'dual_feasibility: ', st.dual)
+                    continue
+                if verbose and i % 10 == 0:
+                    print(f'problem {k}: iter_num=', i, 'primal_feasibility: ', st.primal, 'dual_feasibility: ', st.dual)
+                    print('loss=', st.objective)
+                if s.store:
+                    s.train_losses.append(st.objective)
+                    s.test_losses.append(s.test_objective.get_arrogate_loss(s.w))
+                    s.time_array.append(time.time() - t_start)
+        for s in self.solvers:
+            if isinstance(s, smoothADMMmethod) and s.w_flag == 1:
+                s._s.finalize_smooth()                                                     # :257-258
+        return [s.w for s in self.solvers]
+
+    def final_res(self):
+        return [s.final_res() for s in self.solvers]

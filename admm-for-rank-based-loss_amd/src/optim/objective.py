@@ -69,7 +69,7 @@ class rankbasedObjective:
     """objective.py:39-94.  Holds D = -y*X on the device (own handle, or the solver's)."""
 
     def __init__(self, X, y, weight_function="erm", loss="binary_cross_entropy", l2_reg=None, l1_reg=None,
-                 B=None, n_class=None, args=None, storage="f32", device=0, _shared_solver=None):
+                 B=None, n_class=None, args=None, storage="f32", device=0, _shared_solver=None, _share_data=None):
         _solver.check_problem(weight_function, loss, B, args, need_prox=False)
         if loss == "multinomial_cross_entropy":
             raise ValueError("multinomial_cross_entropy is outside the ADMM hot path (binary losses only)")
@@ -85,9 +85,14 @@ class rankbasedObjective:
         else:
             Xm = _solver._as_matrix(X)
             self.n, self.d = Xm.shape
+            # _share_data: another objective on the same (X, y) whose device matrix this one borrows (ADMMgroup)
+            share = None if _share_data is None else _share_data._s
+            if share is not None and (share.n, share.d) != (self.n, self.d):
+                raise ValueError(f"shared data is {(share.n, share.d)}, X is {(self.n, self.d)}")
             self._s = _solver.Solver(self.n, self.d, weight_function, loss, args=args, B=B, storage=storage,
-                                     device=device, objective_only=True)
-            self._s.set_data(Xm, y)
+                                     device=device, objective_only=True, share=share)
+            if share is None:
+                self._s.set_data(Xm, y)
         self._alphas = self._betas = None
 
     def _sig(self):

@@ -118,6 +118,16 @@ int  rbl_device_count(void);
 /* Optimizer.__init__ / rankbasedObjective.__init__ */
 int  rbl_create(const rbl_config* cfg, rbl_solver** out);
 int  rbl_destroy(rbl_solver* h);
+/* A second problem on the SAME (X, y): Optimizer.__init__ again with other weight_function / loss / regulariser / args
+ * (examples/run_srm.py:57,68 builds ADMMmethod and smoothADMMmethod on one X_train), without algorithms.py:23-24 being
+ * paid again.  The handle borrows the owner's device D = -y*X, G = D^T D and what derives from G alone (Lipschitz
+ * constant, eigenbasis) and owns only its per-problem state (w, z, lambda, rho, sigma, z-step and w-step workspaces):
+ * no upload, no Gram launch.  cfg must agree with the owner on n, d, n_total, row_offset, storage and device
+ * (RBL_ERR_INVALID); the owner must have its data and - unless cfg->objective_only - its Gram matrix ready
+ * (RBL_ERR_STATE).  The shared buffers are reference-counted: owner and borrowers may be destroyed in any order, the last
+ * one frees them.  rbl_set_data, rbl_generate_synthetic, rbl_synth_*, rbl_gram_* on a borrower are RBL_ERR_STATE.  A
+ * borrower used alone behaves exactly like a handle built from the same (X, y). */
+int  rbl_create_shared(const rbl_config* cfg, rbl_solver* owner, rbl_solver** out);
 /* run the library's kernels on this hipStream_t: NULL is the (legacy) default stream,
  * (void*)-1 goes back to the handle's own non-blocking stream (the initial setting) */
 int  rbl_set_stream(rbl_solver* h, void* hip_stream);
@@ -158,6 +168,43 @@ int  rbl_solve(rbl_solver* h, int max_iter, int want_objective, rbl_stats* last,
                double* hist_time_s, int64_t cap);
 /* smoothADMMmethod's final soft-threshold of w by t (algorithms.py:257-258) */
 int  rbl_finalize_smooth(rbl_solver* h);
+
+/* ---- groups: several problems on one data matrix, iterated together ------------------------------------------
+ * The reference's experiments are families of problems on one (X, y) - a regularisation path, superquantile levels,
+ * AoRR (k, m) pairs, ADMM beside sADMM (examples/run_srm.py:57,68) - each an Optimizer.main_loop of its own
+ * (algorithms.py:119-164).  A group runs one such iteration of EVERY member per step and reads D once for
+ * k_per_pass members in each of the two n x d passes (Q = D^T [c_1 .. c_K], V = D [w_1 .. w_K]) instead of once per
+ * member:  per member rbl_phase_m + rbl_phase_z  ->  shared Q pass  ->  per member rbl_phase_w  ->  shared V pass (with
+ * each member's lambda update and primal residual, rho per member)  ->  per member rbl_phase_finish.
+ *  - members: an owner and its borrowers (rbl_create_shared), single-process problems (n == n_total), 1 <= k <= 64;
+ *    anything else is RBL_ERR_INVALID.  While the group exists its members run on the group's stream; destroy the
+ *    group before its members.  After rbl_group_destroy the members are ordinary handles again.
+ *  - every member runs the two-pass structure: erm members do not use the single-sweep pass (rbl_stats.fused == 0).
+ *    K rank-weighted problems cost 2 ceil(K / k_per_pass) passes against 2 K standalone; K erm problems cost the same
+ *    2 ceil(K / k_per_pass) against K standalone single sweeps: with k_per_pass = 4 a group of erm problems is a loss
+ *    at K = 1 (2 passes against 1), a tie at K = 2 and pays from K = 3 on (2 against 3, 2 against 4, 4 against 5, ...).
+ *  - the shared passes exist for 32 < packets per row <= 512 (128 < ld <= 2048 with fp32 storage, 64 < ld <= 1024 with
+ *    fp64); outside that range a group runs each member's own passes (shared_v == shared_q == 0, counted in
+ *    single_passes).  Column k of a shared pass is bit-identical to the member's own single-column pass.
+ *  - a member whose z-step was not certified redoes it and its own q with the single-column pass (counted in
+ *    single_passes, as is the v = D w a member needs before its first z-step); the others are not disturbed.
+ *  - a member that converges (its own tol) is frozen exactly where rbl_solve would have stopped and drops out of the
+ *    later passes; rbl_group_solve ends when all have converged or after max_iter steps (<= 0: the members' largest
+ *    max_iter).
+ *  - host waits per group step: ONE spin on the pinned statistics for all members (booked on the first live member's
+ *    rbl_stats.host_syncs) beside what each member's own w-step / uncertified z-step waits for, as in rbl_step.
+ * out / last: k entries in member order (a frozen member keeps its last report); hist_*: k x cap, row i = member i,
+ * may be NULL; iters: iterations each member ran in this call. */
+typedef struct rbl_group rbl_group;
+int  rbl_group_create(rbl_solver* const* members, int k, rbl_group** out);
+int  rbl_group_destroy(rbl_group* g);
+int  rbl_group_step(rbl_group* g, int want_objective, rbl_stats* out);
+int  rbl_group_solve(rbl_group* g, int max_iter, int want_objective, rbl_stats* last,
+                     double* hist_objective, double* hist_primal, double* hist_dual, double* hist_rho,
+                     int64_t* iters, int64_t cap);
+/* k_per_pass: members one shared launch carries (1: no shared passes at this width); shared_v / shared_q: shared
+ * launches so far; single_passes[k]: n x d launches each member ran on its own since the group was created */
+int  rbl_group_counters(rbl_group* g, int* k_per_pass, int64_t* shared_v, int64_t* shared_q, int64_t* single_passes);
 /* rankbasedObjective.get_arrogate_loss(w) (objective.py:71-87); w: d host doubles */
 int  rbl_objective(rbl_solver* h, const double* w, int include_reg, double* out);
 
@@ -336,6 +383,11 @@ int  rbl_k_pav_seq(int loss, int64_t n, const double* sigma_a, const double* sig
 /* v = D w and q = D^T c on a host matrix (storage: RBL_STORE_*) */
 int  rbl_k_gemv(int storage, int64_t n, int64_t d, const double* D, const double* w, double* v);
 int  rbl_k_gemvt(int storage, int64_t n, int64_t d, const double* D, const double* c, double* q);
+/* V = D [w_1 .. w_k] and Q = D^T [c_1 .. c_k] with the multi-column passes of a group (W: k x d, V: k x n, C: k x n,
+ * Q: k x d, row j = column j; 1 <= k <= 64; widths outside the shared kernels' range run the single-column pass per
+ * column) - algorithms.py:89,132 / :192 for k problems at once */
+int  rbl_k_gemv_multi(int storage, int64_t n, int64_t d, int k, const double* D, const double* W, double* V);
+int  rbl_k_gemvt_multi(int storage, int64_t n, int64_t d, int k, const double* D, const double* C, double* Q);
 /* G = D^T D (MFMA f64) */
 int  rbl_k_gram(int storage, int64_t n, int64_t d, const double* D, double* G);
 /* w-steps in Gram space: lasso / ridge / smoothed-l1 */
