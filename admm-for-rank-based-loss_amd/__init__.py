@@ -11,9 +11,9 @@ Everything numerical runs in ``csrc/librbl.so`` (hand-written HIP for gfx950, C 
 """
 from . import _lib                                   # noqa: F401
 from ._solver import Solver, Group                          # noqa: F401
-from .src.optim.algorithms import Optimizer, ADMMmethod, smoothADMMmethod, ADMMgroup   # noqa: F401
+from .src.optim.algorithms import Optimizer, ADMMmethod, smoothADMMmethod, ADMMgroup, OneVsRest   # noqa: F401
 from .src.optim.objective import rankbasedObjective, get_weights            # noqa: F401
 from .SGD_solver import SGDmethod                    # noqa: F401  (competitor baselines)
 from .LSVRG_solver import LSVRGmethod                # noqa: F401
 
-__all__ = ["ADMMmethod", "smoothADMMmethod", "ADMMgroup", "Group", "Optimizer", "rankbasedObjective", "get_weights", "Solver", "SGDmethod", "LSVRGmethod"]
+__all__ = ["ADMMmethod", "smoothADMMmethod", "ADMMgroup", "OneVsRest", "Group", "Optimizer", "rankbasedObjective", "get_weights", "Solver", "SGDmethod", "LSVRGmethod"]

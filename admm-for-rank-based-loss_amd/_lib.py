@@ -70,6 +70,8 @@ SIGNATURES = {
     "rbl_create": (C.c_int, [C.POINTER(RblConfig), C.POINTER(_P)]),
     "rbl_destroy": (C.c_int, [_P]),
     "rbl_create_shared": (C.c_int, [C.POINTER(RblConfig), _P, C.POINTER(_P)]),
+    "rbl_set_labels": (C.c_int, [_P, _P]),
+    "rbl_decide_multi": (C.c_int, [_P, C.c_int, _P, _P]),
     "rbl_group_create": (C.c_int, [C.POINTER(_P), C.c_int, C.POINTER(_P)]),
     "rbl_group_destroy": (C.c_int, [_P]),
     "rbl_group_step": (C.c_int, [_P, C.c_int, C.POINTER(RblStats)]),

@@ -47,6 +47,18 @@ def _as_labels(y, n):
     return y
 
 
+def as_pm1_labels(y, n, what="y"):
+    """n labels in {+1, -1} ({0, 1} is accepted as in _as_labels); anything else is a ValueError naming `what`."""
+    try:
+        y = _as_labels(y, n)
+    except ValueError as e:
+        raise ValueError(f"{what}: {e}") from None
+    if not np.all((y == 1.0) | (y == -1.0)):
+        bad = int(np.flatnonzero(~((y == 1.0) | (y == -1.0)))[0])
+        raise ValueError(f"{what}: labels must be +1/-1 (entry {bad} is {y[bad]!r})")
+    return y
+
+
 def _as_matrix(X):
     X = X.detach().cpu().numpy() if hasattr(X, "detach") else np.asarray(X)
     if X.ndim != 2:
@@ -132,6 +144,22 @@ class Solver:
         y = np.empty(self.n)
         _lib.check(self.lib.rbl_get_labels(self._h, _lib.ptr(y)))
         return y
+
+    def set_labels(self, y):
+        """Labels of this handle's own on the data it borrows (include/rbl.h: rbl_set_labels): n values +-1, before the
+        first iteration.  The shape and the values are checked here, before any device call."""
+        y = as_pm1_labels(y, self.n)
+        _lib.check(self.lib.rbl_set_labels(self._h, _lib.ptr(y)))
+
+    def decide_multi(self, W):
+        """argmax_j x_i . w_j over the rows of this handle's data (ties: lowest j); W: (k, d) -> int32 (n,)
+        (include/rbl.h: rbl_decide_multi)"""
+        W = _lib.f64(W)
+        if W.ndim != 2 or W.shape[1] != self.d or not 1 <= W.shape[0] <= 64:
+            raise ValueError(f"W must be (k, {self.d}) with 1 <= k <= 64, got {W.shape}")
+        cls = np.empty(self.n, dtype=np.int32)
+        _lib.check(self.lib.rbl_decide_multi(self._h, W.shape[0], _lib.ptr(W), _lib.ptr(cls)))
+        return cls
 
     def gram(self):
         _lib.check(self.lib.rbl_gram_local(self._h))

@@ -63,6 +63,12 @@ struct rbl_solver {
     size_t slab_bytes = 0;
     double *partials = nullptr, *red = nullptr, *red2 = nullptr;
     signed char* ysign = nullptr;
+    // labels of this handle's own on a borrowed D (rbl_set_labels): rs[i] = y_i * y_owner_i, one byte per row in this
+    // handle's arena; NULL = the owner's labels.  v, z, lambda, c are then kept in the OWNER's sign convention (z~ = r z,
+    // lambda~ = r lambda, c~ = r c; v = D w as the passes over the owner's D leave it), m is the true m; the sign is taken
+    // out by the element-wise kernels around the z-step and the losses.  rs_host / ys_host: r and the own labels on the host
+    signed char* rs = nullptr;
+    std::vector<signed char> rs_host, ys_host;
     double* colstats = nullptr;  // [sum(ld) | sumsq(ld) | mean(ld) | inv_std(ld)]
 
     SortWorkspace sw{};
@@ -327,6 +333,24 @@ int build_sigma_prefix(rbl_solver* h) {
     return RBL_OK;
 }
 
+// own labels (rbl_set_labels): n host values between the handle's own sign convention and the owner's (an involution)
+void flip_rows(const rbl_solver* h, double* x) {
+    for (int64_t i = 0; i < h->n; ++i)
+        if (h->rs_host[(size_t)i] < 0) x[i] = -x[i];
+}
+
+// n host doubles in the handle's own sign convention -> a device vector in the convention it is stored in (blocking)
+int upload_rows(const rbl_solver* h, double* dst_dev, const double* src) {
+    if (!h->rs) {
+        RBL_HIP(hipMemcpy(dst_dev, src, sizeof(double) * h->n, hipMemcpyHostToDevice));
+        return RBL_OK;
+    }
+    std::vector<double> t(src, src + h->n);
+    flip_rows(h, t.data());
+    RBL_HIP(hipMemcpy(dst_dev, t.data(), sizeof(double) * h->n, hipMemcpyHostToDevice));
+    return RBL_OK;
+}
+
 int ensure_v(rbl_solver* h) {
     if (h->v_valid) return RBL_OK;
     h->nd_launches += 1;
@@ -401,7 +425,7 @@ int z_step_sorted(rbl_solver* h, const double* msrc, double rho, bool allow32 = 
                             h->pw.pm.view(), ehrm ? h->pw.branch : nullptr, h->pw.recs, h->pw.counters, s, u0a, u0b, &ex));
     h->pw.ex.bar_parity = ex.bar_parity;
     RBL_TRY(launch_scatter_z(nt, h->pw.u, perm, ehrm ? h->pw.branch : nullptr, h->cfg.B, ehrm ? 1 : 0, rho,
-                             h->lam, h->z, nullptr, h->off, h->n, s));
+                             h->lam, h->z, nullptr, h->off, h->n, s, h->rs));
     return RBL_OK;
 }
 
@@ -492,9 +516,9 @@ int zb_setup(rbl_solver* h) {
 int risk_from_v(rbl_solver* h, const double* v_all, double* out_dev) {
     hipStream_t s = h->stream;
     if (h->cfg.weight_function == RBL_W_ERM)
-        return launch_loss_sum(h->cfg.loss, h->nt, v_all, 1.0 / (double)h->nt, h->partials, out_dev, s);
+        return launch_loss_sum(h->cfg.loss, h->nt, v_all, 1.0 / (double)h->nt, h->partials, out_dev, s, h->rs);
     h->keys_ready = false;   // the sort workspace is reused: keys left by rbl_phase_m are gone
-    RBL_TRY(launch_loss_keys(h->nt, v_all, h->sw.keys[0], s));
+    RBL_TRY(launch_loss_keys(h->nt, v_all, h->sw.keys[0], s, h->rs));   // (own labels: the losses are taken at r * v)
     // piecewise-constant weights: the band sums of the losses need a select, not a sort (zband.hip; exact for any v)
     if (h->zb.enabled)
         return launch_zband_risk(h->cfg.loss, h->zb.cfg, h->nt, h->sw.keys[0], h->zb.st, h->zb.hist, h->zb.part, out_dev, s);
@@ -1015,8 +1039,139 @@ int rbl_generate_synthetic(rbl_solver* h, uint64_t seed, double class_sep, doubl
     return rbl_synth_finish(h);
 }
 
+int rbl_set_labels(rbl_solver* h, const double* y) {
+    RBL_ENTER(h);
+    if (!h->borrower) {
+        rbl_set_error("set_labels: only a handle that borrows its data (rbl_create_shared) can carry labels of its own");
+        return RBL_ERR_STATE;
+    }
+    if (h->iter > 0) {
+        rbl_set_error("set_labels: the handle has iterated already (iter = %lld)", (long long)h->iter);
+        return RBL_ERR_STATE;
+    }
+    if (h->in_group) {
+        rbl_set_error("set_labels: the handle is a member of a group - destroy the group first");
+        return RBL_ERR_STATE;
+    }
+    if (h->nt != h->n) {
+        rbl_set_error("set_labels: row-sharded handle (n=%lld of %lld) - the distributed z-steps carry no labels of their own",
+                      (long long)h->n, (long long)h->nt);
+        return RBL_ERR_INVALID;
+    }
+    if (!y) {
+        rbl_set_error("set_labels: y is NULL");
+        return RBL_ERR_INVALID;
+    }
+    const int64_t n = h->n;
+    for (int64_t i = 0; i < n; ++i)
+        if (!(y[i] == 1.0 || y[i] == -1.0)) {
+            rbl_set_error("set_labels: labels must be +1/-1 (y[%lld] = %g)", (long long)i, y[i]);
+            return RBL_ERR_INVALID;
+        }
+    RBL_HIP(hipStreamSynchronize(h->stream));
+    std::vector<signed char> yo((size_t)n), r((size_t)n), ys((size_t)n);
+    RBL_HIP(hipMemcpy(yo.data(), h->ysign, (size_t)n, hipMemcpyDeviceToHost));
+    bool differs = false;
+    for (int64_t i = 0; i < n; ++i) {
+        ys[(size_t)i] = y[i] > 0 ? 1 : -1;
+        r[(size_t)i] = (signed char)(ys[(size_t)i] * yo[(size_t)i]);
+        differs = differs || r[(size_t)i] < 0;
+    }
+    if (!differs && !h->rs) return RBL_OK;   // the owner's labels on an ordinary borrower: nothing changes
+    // z and lambda move from the sign convention they are stored in to the new one (both start as constants)
+    std::vector<double> zh, lh;
+    if (h->z) {
+        zh.resize((size_t)n);
+        lh.resize((size_t)n);
+        RBL_HIP(hipMemcpy(zh.data(), h->z, sizeof(double) * n, hipMemcpyDeviceToHost));
+        RBL_HIP(hipMemcpy(lh.data(), h->lam, sizeof(double) * n, hipMemcpyDeviceToHost));
+        if (h->rs) {
+            flip_rows(h, zh.data());
+            flip_rows(h, lh.data());
+        }
+    }
+    if (!differs) {   // the owner's labels: an ordinary borrower
+        if (h->rs) h->mem.release(h->rs);
+        h->rs = nullptr;
+        h->rs_host.clear();
+        h->ys_host.clear();
+    } else {
+        if (!h->rs) RBL_TRY(h->mem.alloc(&h->rs, (size_t)n));
+        RBL_HIP(hipMemcpy(h->rs, r.data(), (size_t)n, hipMemcpyHostToDevice));
+        h->rs_host.swap(r);
+        h->ys_host.swap(ys);
+    }
+    if (h->z) {
+        RBL_TRY(upload_rows(h, h->z, zh.data()));
+        RBL_TRY(upload_rows(h, h->lam, lh.data()));
+    }
+    if (!h->cfg.objective_only) {
+        // the sign is not part of the single-sweep erm pass' in-pass prox: such a handle runs the two-pass iteration
+        const char* nf = getenv("RBL_NO_FUSE");
+        h->fused_ok = !h->rs && !h->sorted_path && !(nf && nf[0] == '1') && sweep_erm_supported(h->storage, h->ld);
+    }
+    h->z_ready = h->p_valid = h->p_pending = h->pred_valid = false;
+    h->keys_ready = h->s32.m_ready = false;
+    return RBL_OK;
+}
+
+// One-vs-rest decision on the rows of `data`: cls[i] = argmax_j x_i . w_j (ties: the lowest j).  D = -y X, so the
+// scores are -y_i (D w_j)_i: the multi-column V product of the groups (sweep_multi.hip), ceil(k / k_per_pass) passes
+// over D, each followed by the row-wise comparison against the best score so far.
+int rbl_decide_multi(rbl_solver* h, int k, const double* W, int32_t* cls) {
+    RBL_ENTER(h);
+    if (!h->data_ready) {
+        rbl_set_error("decide_multi: no data");
+        return RBL_ERR_STATE;
+    }
+    if (k < 1 || k > 64 || !W || !cls) {
+        rbl_set_error("decide_multi: 1..64 columns (got %d), W and cls not NULL", k);
+        return RBL_ERR_INVALID;
+    }
+    const int64_t n = h->n, ld = h->ld, d = h->d;
+    if (n <= 0) return RBL_OK;
+    hipStream_t s = h->stream;
+    const bool multi = sweep_multi_supported(h->storage, ld);
+    const int kpp = multi ? sweep_multi_k(h->storage, ld) : 1;
+    DevArena mem;   // scratch of this call, freed on return (after the stream wait)
+    double *dw = nullptr, *dv = nullptr, *best = nullptr;
+    int* dcls = nullptr;
+    std::vector<double> wp((size_t)ld * k, 0.0);
+    for (int j = 0; j < k; ++j)
+        for (int64_t i = 0; i < d; ++i) wp[(size_t)j * ld + i] = W[(size_t)j * d + i];
+    RBL_TRY(mem.alloc(&dw, wp.size()));
+    RBL_TRY(mem.alloc(&dv, (size_t)n * kpp));
+    RBL_TRY(mem.alloc(&best, (size_t)n));
+    RBL_TRY(mem.alloc(&dcls, (size_t)n));
+    RBL_HIP(hipMemcpy(dw, wp.data(), sizeof(double) * wp.size(), hipMemcpyHostToDevice));
+    int rc = RBL_OK;
+    for (int j0 = 0; j0 < k && rc == RBL_OK; j0 += kpp) {
+        const int kk = std::min(kpp, k - j0);
+        if (!multi) {   // outside the multi-column kernels' widths: the single-column pass per column
+            rc = launch_gemv(h->storage, h->D, n, ld, dw + (size_t)j0 * ld, dv, h->num_cu, s);
+        } else {
+            const double* w[RBL_MULTI_KMAX];
+            double* v[RBL_MULTI_KMAX];
+            for (int j = 0; j < kk; ++j) {
+                w[j] = dw + (size_t)(j0 + j) * ld;
+                v[j] = dv + (size_t)j * n;
+            }
+            rc = launch_sweep_v_multi(h->storage, h->D, n, ld, kk, w, nullptr, nullptr, v, nullptr, nullptr, nullptr, h->num_cu, s);
+        }
+        if (rc == RBL_OK) rc = launch_decide_rows(n, kk, j0, dv, h->ysign, best, dcls, s);
+    }
+    if (rc == RBL_OK && (hipMemcpyAsync(cls, dcls, sizeof(int32_t) * n, hipMemcpyDeviceToHost, s) != hipSuccess)) rc = RBL_ERR_HIP;
+    if (hipStreamSynchronize(s) != hipSuccess && rc == RBL_OK) rc = RBL_ERR_HIP;   // before the scratch goes
+    if (rc == RBL_ERR_HIP) rbl_set_error("decide_multi: %s", hipGetErrorString(hipGetLastError()));
+    return rc;
+}
+
 int rbl_get_labels(rbl_solver* h, double* y_out) {
     RBL_ENTER(h);
+    if (h->rs) {   // labels of its own (rbl_set_labels)
+        for (int64_t i = 0; i < h->n; ++i) y_out[i] = (double)h->ys_host[(size_t)i];
+        return RBL_OK;
+    }
     std::vector<signed char> t((size_t)h->n);
     RBL_HIP(hipMemcpy(t.data(), h->ysign, (size_t)h->n, hipMemcpyDeviceToHost));
     for (int64_t i = 0; i < h->n; ++i) y_out[i] = (double)t[i];
@@ -1104,6 +1259,10 @@ int rbl_get_D(rbl_solver* h, double* out) {
             hipStreamSynchronize(h->stream) != hipSuccess)
             return RBL_ERR_HIP;
     }
+    if (h->rs)   // -y_k * X = r * (-y_owner * X)
+        for (int64_t i = 0; i < n; ++i)
+            if (h->rs_host[(size_t)i] < 0)
+                for (int64_t j = 0; j < d; ++j) out[i * d + j] = -out[i * d + j];
     return RBL_OK;
 }
 
@@ -1114,6 +1273,10 @@ int rbl_get_state(rbl_solver* h, double* w, double* z, double* lam, double* rho,
     if (w) RBL_HIP(hipMemcpy(w, h->spec_w ? h->w_prev : h->w, sizeof(double) * h->d, hipMemcpyDeviceToHost));
     if (z && h->z) RBL_HIP(hipMemcpy(z, h->z, sizeof(double) * h->n, hipMemcpyDeviceToHost));
     if (lam && h->lam) RBL_HIP(hipMemcpy(lam, h->lam, sizeof(double) * h->n, hipMemcpyDeviceToHost));
+    if (h->rs) {   // the caller sees the handle's own sign convention
+        if (z && h->z) flip_rows(h, z);
+        if (lam && h->lam) flip_rows(h, lam);
+    }
     if (rho) *rho = h->rho;
     if (iter) *iter = h->iter;
     if (smooth_t) *smooth_t = h->smooth_t;
@@ -1130,11 +1293,11 @@ int rbl_set_state(rbl_solver* h, const double* w, const double* z, const double*
         h->z_ready = false;
     }
     if (z && h->z) {
-        RBL_HIP(hipMemcpy(h->z, z, sizeof(double) * h->n, hipMemcpyHostToDevice));
+        RBL_TRY(upload_rows(h, h->z, z));
         h->z_ready = false;
     }
     if (lam && h->lam) {
-        RBL_HIP(hipMemcpy(h->lam, lam, sizeof(double) * h->n, hipMemcpyHostToDevice));
+        RBL_TRY(upload_rows(h, h->lam, lam));
         h->z_ready = false;
         h->p_valid = h->p_pending = false;
     }
@@ -1203,14 +1366,14 @@ int rbl_phase_m(rbl_solver* h) {
         h->s32.m_ready = false;
         if (s32) {
             // m = D w - lambda/rho (algorithms.py:89) and its range (the 32-bit keys are a fixed-point image on it)
-            RBL_TRY(launch_make_m_range(h->n, h->step_rho, h->v, h->lam, h->m, h->s32.mm, h->stream));
+            RBL_TRY(launch_make_m_range(h->n, h->step_rho, h->v, h->lam, h->m, h->s32.mm, h->stream, h->rs));
             h->s32.m_ready = true;
             h->keys_ready = false;
         } else {
             // m and, in the same pass, the 64-bit sort's input for the z-step: keys of m with the GLOBAL row id as
             // payload (single GPU: off = 0; sharded: what rbl_zd_sort_local sorts)
             RBL_TRY(launch_make_m_keys(h->n, h->step_rho, h->v, h->lam, h->m, h->sw.keys[0], h->sw.vals[0], (u32)h->off,
-                                       h->stream));
+                                       h->stream, h->rs));
             h->keys_ready = true;
         }
     }
@@ -1223,7 +1386,7 @@ int rbl_phase_z(rbl_solver* h, const void* m_all_dev) {
     if (h->fused_ok && h->z_ready) {
         std::swap(h->z, h->z_next);  // the z-step of this iteration was done by the previous pass
     } else if (!h->sorted_path) {
-        RBL_TRY(launch_erm_zc(h->cfg.loss, h->n, h->sigma0, rho, h->v, h->lam, h->m, h->z, h->c, h->stream));
+        RBL_TRY(launch_erm_zc(h->cfg.loss, h->n, h->sigma0, rho, h->v, h->lam, h->m, h->z, h->c, h->stream, h->rs));
         if (h->fused_ok) RBL_TRY(launch_sumsq(h->n, h->z, h->partials, q_zz(h), h->stream));
     } else {
         const double* msrc = (const double*)m_all_dev;
@@ -1241,7 +1404,7 @@ int rbl_phase_z(rbl_solver* h, const void* m_all_dev) {
             h->zb.seq = (h->zb.seq & 0x3fffffff) + 1;
             h->zb.pin[0] = 0;
             RBL_TRY(launch_zband(h->cfg.loss, h->zb.cfg, h->n, rho, h->sw.keys[0], h->m, h->z, h->lam, h->c, h->zb.st, h->zb.hist,
-                                 h->zb.part, h->zb.pin, h->zb.seq, h->pw.counters, h->stream));
+                                 h->zb.part, h->zb.pin, h->zb.seq, h->pw.counters, h->stream, h->rs));
             h->zb.used = true;
             h->zb.q_done = false;
             h->zb.c_ready = true;   // the element-wise pass wrote c = z + lambda/rho as well
@@ -1262,7 +1425,12 @@ int rbl_phase_z_external(rbl_solver* h, const double* z) {
         return RBL_ERR_INVALID;
     }
     RBL_TRY(rbl_phase_m(h));   // opens the iteration (step_rho); a no-op for what it has computed already
-    RBL_HIP(hipMemcpyAsync(h->z, z, sizeof(double) * h->n, hipMemcpyHostToDevice, h->stream));
+    if (h->rs) {
+        RBL_HIP(hipStreamSynchronize(h->stream));
+        RBL_TRY(upload_rows(h, h->z, z));   // the caller's z is in the handle's own sign convention
+    } else {
+        RBL_HIP(hipMemcpyAsync(h->z, z, sizeof(double) * h->n, hipMemcpyHostToDevice, h->stream));
+    }
     RBL_HIP(hipStreamSynchronize(h->stream));   // the caller's buffer may go away
     rbl_note_host_sync();
     // a z-step the previous single-sweep pass did ahead of time (z_next, q, ||z||^2) is void: the unfused kernels
@@ -1450,6 +1618,9 @@ int rbl_phase_dual(rbl_solver* h, int want_objective) {
         if (h->phase_timing) RBL_HIP(hipEventRecord(h->ev[4], h->stream));
         RBL_TRY(launch_dual(h->cfg.loss, h->n, h->step_rho, h->z, h->v, h->lam, h->partials, h->red, h->stream));
     }
+    // own labels: k_dual summed the losses at v as the pass left it - the handle's own are at r * v
+    if (h->rs && want_objective && !h->sorted_path)
+        RBL_TRY(launch_loss_sum(h->cfg.loss, h->n, h->v, 1.0, h->partials, h->red + 1, h->stream, h->rs));
     h->pending_mask = 2 | (h->fused_ran ? 1 : 0);
     h->want_obj = want_objective;
     h->obj_is_risk = false;
@@ -1736,7 +1907,7 @@ int rbl_accuracy(rbl_solver* h, const double* w, double threshold, double* out) 
     RBL_HIP(hipMemcpyAsync(h->w_tmp, w, sizeof(double) * h->d, hipMemcpyHostToDevice, h->stream));
     RBL_TRY(launch_gemv(h->storage, h->D, h->n, h->ld, h->w_tmp, h->m, h->num_cu, h->stream));
     RBL_TRY(launch_accuracy(h->cfg.loss, h->n, h->m, h->ysign, std::log(threshold / (1.0 - threshold)), h->partials,
-                            h->red2 + 4, h->stream));
+                            h->red2 + 4, h->stream, h->rs));
     double cnt = 0.0;
     RBL_HIP(hipMemcpyAsync(&cnt, h->red2 + 4, sizeof(double), hipMemcpyDeviceToHost, h->stream));
     RBL_HIP(hipStreamSynchronize(h->stream));
@@ -2205,7 +2376,7 @@ int rbl_fair_statistics(rbl_solver* h, const double* w, const double* group, dou
         }
         RBL_TRY(launch_gemv(h->storage, h->D, h->n, h->ld, h->w_tmp, h->m, h->num_cu, h->stream));
         double* out14 = h->slab;  // scratch (>= 14 doubles)
-        RBL_TRY(launch_fair_counts(h->n, h->m, h->ysign, gd, threshold, h->partials, out14, h->stream));
+        RBL_TRY(launch_fair_counts(h->n, h->m, h->ysign, gd, threshold, h->partials, out14, h->stream, h->rs));
         if (hipMemcpyAsync(c, out14, sizeof(double) * 14, hipMemcpyDeviceToHost, h->stream) != hipSuccess ||
             hipStreamSynchronize(h->stream) != hipSuccess) {
             rbl_set_error("fair_statistics: readback failed");
@@ -2470,7 +2641,7 @@ int rbl_group_step(rbl_group* g, int want_objective, rbl_stats* out) {
                 RBL_TRY(risk_from_v(h, h->v, h->red + 1));
                 h->obj_is_risk = true;
             } else if (want_objective) {
-                RBL_TRY(launch_loss_sum(h->cfg.loss, h->n, h->v, 1.0, h->partials, h->red + 1, s));   // objective.py:11-24
+                RBL_TRY(launch_loss_sum(h->cfg.loss, h->n, h->v, 1.0, h->partials, h->red + 1, s, h->rs));   // objective.py:11-24
             }
         }
     } else {

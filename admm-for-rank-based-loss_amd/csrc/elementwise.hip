@@ -20,17 +20,29 @@ inline unsigned ew_grid(long long n) {
 // erm: sigma is constant, the prox is monotone in m, so no sort and no PAV are needed:
 // z_i = prox(m_i) is the isotonic solution.  Fuses algorithms.py:89
 // (m), individual_solver.py:112-123 (prox) and the w-step's c = z + lambda/rho (:192).
-template <int LOSS>
+// Members with labels of their own on a borrowed D (rbl_set_labels): r_i = y_i * y_owner_i in {+1, -1}, one signed char
+// per row.  v, z, lambda and c of such a handle are kept in the OWNER's sign convention (v = D w as the shared pass
+// leaves it, z~ = r z, lambda~ = r lambda, c~ = r c), so the n x d passes need no sign; the kernels below take it out
+// where the z-step and the losses see a row: m = r (v - lambda~/rho), z~ = r z.  Negation is exact, so every value is
+// bit for bit what a handle built from (X, y) computes.  RS = false (rs unused) is the code of a handle without own labels.
+template <bool RS>
+__device__ __forceinline__ double rs_flip(double x, const signed char* __restrict__ rs, long long i) {
+    if (RS) return rs[i] < 0 ? -x : x;
+    return x;
+}
+
+template <int LOSS, bool RS>
 __global__ __launch_bounds__(EW_THREADS) void k_erm_zc(long long n, double sigma0, double rho,
                                                         const double* __restrict__ v,
                                                         const double* __restrict__ lam, double* __restrict__ m,
-                                                        double* __restrict__ z, double* __restrict__ c) {
+                                                        double* __restrict__ z, double* __restrict__ c,
+                                                        const signed char* __restrict__ rs) {
     const double inv_rho = 1.0 / rho;
     for (long long i = (long long)blockIdx.x * EW_THREADS + threadIdx.x; i < n;
          i += (long long)gridDim.x * EW_THREADS) {
         double lr = lam[i] / rho;
-        double mi = v[i] - lr;
-        double zi = rbl::prox<LOSS>(sigma0, rho, mi);
+        double mi = rs_flip<RS>(v[i] - lr, rs, i);
+        double zi = rs_flip<RS>(rbl::prox<LOSS>(sigma0, rho, mi), rs, i);
         m[i] = mi;
         z[i] = zi;
         c[i] = zi + lr;
@@ -38,11 +50,13 @@ __global__ __launch_bounds__(EW_THREADS) void k_erm_zc(long long n, double sigma
     (void)inv_rho;
 }
 
+template <bool RS>
 __global__ void k_make_m_keys(long long n, double rho, const double* __restrict__ v, const double* __restrict__ lam,
-                              double* __restrict__ m, u64* __restrict__ keys, u32* __restrict__ idx, u32 idx_off) {
+                              double* __restrict__ m, u64* __restrict__ keys, u32* __restrict__ idx, u32 idx_off,
+                              const signed char* __restrict__ rs) {
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n;
          i += (long long)gridDim.x * blockDim.x) {
-        const double x = v[i] - lam[i] / rho;  // algorithms.py:89
+        const double x = rs_flip<RS>(v[i] - lam[i] / rho, rs, i);  // algorithms.py:89
         m[i] = x;
         keys[i] = rbl::flip_key(x);
         idx[i] = (u32)i + idx_off;
@@ -54,13 +68,14 @@ __global__ void k_make_m_keys(long long n, double rho, const double* __restrict_
 // k_keys32 reduces those S32_RANGE_BLOCKS pairs again in every one of its blocks.  (Atomic max on two global words
 // from every wave was tried first: 16 384 contended atomics = 380 us at 6.25 M rows.)
 constexpr int S32_RANGE_BLOCKS = 1024;
+template <bool RS>
 __global__ __launch_bounds__(EW_THREADS) void k_make_m_range(long long n, double rho, const double* __restrict__ v,
                                                               const double* __restrict__ lam, double* __restrict__ m,
-                                                              u64* __restrict__ mm) {
+                                                              u64* __restrict__ mm, const signed char* __restrict__ rs) {
     __shared__ u64 s_lo[EW_THREADS / 64], s_hi[EW_THREADS / 64];
     u64 lo = ~0ull, hi = 0ull;
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
-        const double x = v[i] - lam[i] / rho;
+        const double x = rs_flip<RS>(v[i] - lam[i] / rho, rs, i);
         m[i] = x;
         const u64 k = rbl::flip_key(x);
         lo = k < lo ? k : lo;
@@ -218,10 +233,12 @@ __global__ __launch_bounds__(256) void k_sum_partials(const double* __restrict__
     }
 }
 
-__global__ void k_loss_keys(long long n, const double* __restrict__ v, u64* __restrict__ keys) {
+template <bool RS>
+__global__ void k_loss_keys(long long n, const double* __restrict__ v, u64* __restrict__ keys,
+                            const signed char* __restrict__ rs) {
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n;
          i += (long long)gridDim.x * blockDim.x)
-        keys[i] = rbl::flip_key(v[i]);
+        keys[i] = rbl::flip_key(rs_flip<RS>(v[i], rs, i));
 }
 
 // sum_i sigma_i * loss(v_(i)) over ascending v (objective.py:73-81: losses are monotone
@@ -239,14 +256,15 @@ __global__ __launch_bounds__(EW_THREADS) void k_sorted_loss_dot(long long n, con
     if (threadIdx.x == 0) partials[blockIdx.x] = acc[0];
 }
 
-template <int LOSS>
+template <int LOSS, bool RS>
 __global__ __launch_bounds__(EW_THREADS) void k_loss_sum(long long n, const double* __restrict__ v, double scale,
-                                                          double* __restrict__ partials) {
+                                                          double* __restrict__ partials,
+                                                          const signed char* __restrict__ rs) {
     __shared__ double smem[EW_THREADS / 64];
     double acc[1] = {0.0};
     for (long long i = (long long)blockIdx.x * EW_THREADS + threadIdx.x; i < n;
          i += (long long)gridDim.x * EW_THREADS)
-        acc[0] += rbl::sample_loss<LOSS>(v[i]);
+        acc[0] += rbl::sample_loss<LOSS>(rs_flip<RS>(v[i], rs, i));
     acc[0] *= scale;
     rbl::block_sum<1, EW_THREADS>(acc, smem);
     if (threadIdx.x == 0) partials[blockIdx.x] = acc[0];
@@ -257,18 +275,21 @@ __global__ __launch_bounds__(EW_THREADS) void k_loss_sum(long long n, const doub
 //   binary_cross_entropy: predict +1 iff sigmoid(x.w) >= threshold  <=>  x.w >= tau
 //   hinge: the reference maps BOTH outcomes of (x.w >= 0) to +1 (calculate_acc.py:13-15),
 //          i.e. its accuracy is the fraction of y == +1; mirrored as is.
-template <int LOSS>
+// rs (rbl_set_labels): v = D w carries the OWNER's label, the target is the handle's own y = r * y_owner
+template <int LOSS, bool RS>
 __global__ __launch_bounds__(EW_THREADS) void k_accuracy(long long n, const double* __restrict__ v,
                                                           const signed char* __restrict__ ysign, double tau,
-                                                          double* __restrict__ partials) {
+                                                          double* __restrict__ partials,
+                                                          const signed char* __restrict__ rs) {
     __shared__ double smem[EW_THREADS / 64];
     double acc[1] = {0.0};
     for (long long i = (long long)blockIdx.x * EW_THREADS + threadIdx.x; i < n;
          i += (long long)gridDim.x * EW_THREADS) {
-        const int y = ysign[i];
+        const int yo = ysign[i];
+        const int y = RS ? yo * rs[i] : yo;
         bool ok;
         if (LOSS == 0) {
-            const double xw = -(double)y * v[i];
+            const double xw = -(double)yo * v[i];
             const int pred = (xw >= tau) ? 1 : -1;
             ok = pred == y;
         } else {
@@ -284,18 +305,21 @@ __global__ __launch_bounds__(EW_THREADS) void k_accuracy(long long n, const doub
 // driver prints (reference: src/util/fair_metric.py:3-41, called from run_EHRM.py:41).
 // partials[b*14 + k]: k = 6*g + {rows, predicted +, TP, FN, TN, FP} for group g in {0,1};
 // k = 12: sum b, k = 13: sum b*log(b) with b = prob - y01 + 1  (fair_metric.py:36-39).
+template <bool RS>
 __global__ __launch_bounds__(EW_THREADS) void k_fair_counts(long long n, const double* __restrict__ v,
                                                              const signed char* __restrict__ ysign,
                                                              const double* __restrict__ group, double threshold,
-                                                             double* __restrict__ partials) {
+                                                             double* __restrict__ partials,
+                                                             const signed char* __restrict__ rs) {
     __shared__ double smem[14 * EW_THREADS / 64];
     double acc[14];
 #pragma unroll
     for (int k = 0; k < 14; ++k) acc[k] = 0.0;
     for (long long i = (long long)blockIdx.x * EW_THREADS + threadIdx.x; i < n;
          i += (long long)gridDim.x * EW_THREADS) {
-        const int y = ysign[i];
-        const double xw = -(double)y * v[i];
+        const int yo = ysign[i];
+        const int y = RS ? yo * rs[i] : yo;
+        const double xw = -(double)yo * v[i];
         const double prob = rbl::sigmoid1(xw);                 // fair_metric.py:5-7
         const int pred = prob >= threshold ? 1 : 0;            // :8
         const int y01 = y > 0 ? 1 : 0;                         // :9-10
@@ -316,6 +340,33 @@ __global__ __launch_bounds__(EW_THREADS) void k_fair_counts(long long n, const d
     rbl::block_sum<14, EW_THREADS>(acc, smem);
     if (threadIdx.x == 0)
         for (int k = 0; k < 14; ++k) partials[blockIdx.x * 14 + k] = acc[k];
+}
+
+// One-vs-rest decision (rbl_decide_multi): columns j0 .. j0 + kk - 1 of the scores x_i . w_j = -y_i (D w_j)_i against the
+// best score so far; ties keep the lowest j (columns arrive in ascending order, the comparison is strict).
+__global__ __launch_bounds__(EW_THREADS) void k_decide_rows(long long n, int kk, int j0, const double* __restrict__ V,
+                                                             const signed char* __restrict__ ysign,
+                                                             double* __restrict__ best, int* __restrict__ cls) {
+    for (long long i = (long long)blockIdx.x * EW_THREADS + threadIdx.x; i < n;
+         i += (long long)gridDim.x * EW_THREADS) {
+        const bool neg = ysign[i] > 0;   // D = -y X
+        double b = 0.0;
+        int arg = 0;
+        if (j0 > 0) {
+            b = best[i];
+            arg = cls[i];
+        }
+        for (int j = 0; j < kk; ++j) {
+            const double t = V[(long long)j * n + i];
+            const double sc = neg ? -t : t;
+            if ((j0 == 0 && j == 0) || sc > b) {
+                b = sc;
+                arg = j0 + j;
+            }
+        }
+        best[i] = b;
+        cls[i] = arg;
+    }
 }
 
 // ---- sigma generators: src/optim/objective.py:97-164 ---------------------------------
@@ -374,27 +425,45 @@ int reduce_blocks() { return RED_BLOCKS; }
             hipLaunchKernelGGL((KERN<1>), dim3(grid), dim3(block), 0, stream, __VA_ARGS__);      \
     } while (0)
 
+// the same for kernels that take the optional sign vector rs as their last argument (NULL: the instance without it)
+#define LAUNCH_LOSS_RS(KERN, loss, rs, grid, block, stream, ...)                                             \
+    do {                                                                                                     \
+        if ((loss) == RBL_LOSS_BCE) {                                                                        \
+            if (rs) hipLaunchKernelGGL((KERN<0, true>), dim3(grid), dim3(block), 0, stream, __VA_ARGS__, rs); \
+            else hipLaunchKernelGGL((KERN<0, false>), dim3(grid), dim3(block), 0, stream, __VA_ARGS__, rs);   \
+        } else {                                                                                             \
+            if (rs) hipLaunchKernelGGL((KERN<1, true>), dim3(grid), dim3(block), 0, stream, __VA_ARGS__, rs); \
+            else hipLaunchKernelGGL((KERN<1, false>), dim3(grid), dim3(block), 0, stream, __VA_ARGS__, rs);   \
+        }                                                                                                    \
+    } while (0)
+#define LAUNCH_RS(KERN, rs, grid, block, stream, ...)                                                    \
+    do {                                                                                                 \
+        if (rs) hipLaunchKernelGGL((KERN<true>), dim3(grid), dim3(block), 0, stream, __VA_ARGS__, rs);   \
+        else hipLaunchKernelGGL((KERN<false>), dim3(grid), dim3(block), 0, stream, __VA_ARGS__, rs);     \
+    } while (0)
+
 int launch_erm_zc(int loss, int64_t n, double sigma0, double rho, const double* v, const double* lam, double* m,
-                  double* z, double* c, hipStream_t s) {
+                  double* z, double* c, hipStream_t s, const signed char* rs) {
     if (n <= 0) return RBL_OK;
-    LAUNCH_LOSS(k_erm_zc, loss, ew_grid(n), EW_THREADS, s, (long long)n, sigma0, rho, v, lam, m, z, c);
+    LAUNCH_LOSS_RS(k_erm_zc, loss, rs, ew_grid(n), EW_THREADS, s, (long long)n, sigma0, rho, v, lam, m, z, c);
     RBL_HIP(hipGetLastError());
     return RBL_OK;
 }
 
 int launch_make_m_keys(int64_t n, double rho, const double* v, const double* lam, double* m, u64* keys, u32* idx,
-                       u32 idx_off, hipStream_t s) {
+                       u32 idx_off, hipStream_t s, const signed char* rs) {
     if (n <= 0) return RBL_OK;
-    hipLaunchKernelGGL(k_make_m_keys, dim3(ew_grid(n)), dim3(256), 0, s, (long long)n, rho, v, lam, m, keys, idx, idx_off);
+    LAUNCH_RS(k_make_m_keys, rs, ew_grid(n), 256, s, (long long)n, rho, v, lam, m, keys, idx, idx_off);
     RBL_HIP(hipGetLastError());
     return RBL_OK;
 }
 
 int s32_range_words() { return 2 * S32_RANGE_BLOCKS; }
 
-int launch_make_m_range(int64_t n, double rho, const double* v, const double* lam, double* m, u64* mm, hipStream_t s) {
+int launch_make_m_range(int64_t n, double rho, const double* v, const double* lam, double* m, u64* mm, hipStream_t s,
+                        const signed char* rs) {
     if (n <= 0) return RBL_OK;
-    hipLaunchKernelGGL(k_make_m_range, dim3(S32_RANGE_BLOCKS), dim3(EW_THREADS), 0, s, (long long)n, rho, v, lam, m, mm);
+    LAUNCH_RS(k_make_m_range, rs, S32_RANGE_BLOCKS, EW_THREADS, s, (long long)n, rho, v, lam, m, mm);
     RBL_HIP(hipGetLastError());
     return RBL_OK;
 }
@@ -446,9 +515,9 @@ int launch_dual(int loss, int64_t n, double rho, const double* z, const double* 
     return launch_sum_partials(partials, RED_BLOCKS, 2, red, s);
 }
 
-int launch_loss_keys(int64_t n, const double* v, u64* keys, hipStream_t s) {
+int launch_loss_keys(int64_t n, const double* v, u64* keys, hipStream_t s, const signed char* rs) {
     if (n <= 0) return RBL_OK;
-    hipLaunchKernelGGL(k_loss_keys, dim3(ew_grid(n)), dim3(256), 0, s, (long long)n, v, keys);
+    LAUNCH_RS(k_loss_keys, rs, ew_grid(n), 256, s, (long long)n, v, keys);
     RBL_HIP(hipGetLastError());
     return RBL_OK;
 }
@@ -461,15 +530,15 @@ int launch_sorted_loss_dot(int loss, int64_t n, const u64* sorted_keys, const do
 }
 
 int launch_loss_sum(int loss, int64_t n, const double* v, double scale, double* partials, double* out,
-                    hipStream_t s) {
-    LAUNCH_LOSS(k_loss_sum, loss, RED_BLOCKS, EW_THREADS, s, (long long)n, v, scale, partials);
+                    hipStream_t s, const signed char* rs) {
+    LAUNCH_LOSS_RS(k_loss_sum, loss, rs, RED_BLOCKS, EW_THREADS, s, (long long)n, v, scale, partials);
     RBL_HIP(hipGetLastError());
     return launch_sum_partials(partials, RED_BLOCKS, 1, out, s);
 }
 
 int launch_accuracy(int loss, int64_t n, const double* v, const signed char* ysign, double tau, double* partials,
-                    double* out, hipStream_t s) {
-    LAUNCH_LOSS(k_accuracy, loss, RED_BLOCKS, EW_THREADS, s, (long long)n, v, ysign, tau, partials);
+                    double* out, hipStream_t s, const signed char* rs) {
+    LAUNCH_LOSS_RS(k_accuracy, loss, rs, RED_BLOCKS, EW_THREADS, s, (long long)n, v, ysign, tau, partials);
     RBL_HIP(hipGetLastError());
     return launch_sum_partials(partials, RED_BLOCKS, 1, out, s);
 }
@@ -477,11 +546,18 @@ int launch_accuracy(int loss, int64_t n, const double* v, const signed char* ysi
 int fair_partial_blocks() { return 256; }
 
 int launch_fair_counts(int64_t n, const double* v, const signed char* ysign, const double* group, double threshold,
-                       double* partials, double* out14, hipStream_t s) {
-    hipLaunchKernelGGL(k_fair_counts, dim3(fair_partial_blocks()), dim3(EW_THREADS), 0, s, (long long)n, v, ysign,
-                       group, threshold, partials);
+                       double* partials, double* out14, hipStream_t s, const signed char* rs) {
+    LAUNCH_RS(k_fair_counts, rs, fair_partial_blocks(), EW_THREADS, s, (long long)n, v, ysign, group, threshold, partials);
     RBL_HIP(hipGetLastError());
     return launch_sum_partials(partials, fair_partial_blocks(), 14, out14, s);
+}
+
+int launch_decide_rows(int64_t n, int kk, int j0, const double* V, const signed char* ysign, double* best, int* cls,
+                       hipStream_t s) {
+    if (n <= 0 || kk <= 0) return RBL_OK;
+    hipLaunchKernelGGL(k_decide_rows, dim3(ew_grid(n)), dim3(EW_THREADS), 0, s, (long long)n, kk, j0, V, ysign, best, cls);
+    RBL_HIP(hipGetLastError());
+    return RBL_OK;
 }
 
 int launch_weights(int wf, int64_t n, const double* args, double* alphas, double* betas, hipStream_t s) {

@@ -984,10 +984,12 @@ __global__ void k_ehrm_pick(const double* __restrict__ partials, int nblocks, in
 }
 
 // z[perm[i]] = clip(u[i]); c = z + lambda/rho  (algorithms.py:103-104 and :192)
+// RS: a handle with labels of its own on a borrowed D (rbl_set_labels) stores z~ = r z, the owner's sign convention
+template <bool RS>
 __global__ void k_scatter_z(long long n, const double* __restrict__ u, const u32* __restrict__ perm,
                             const int* __restrict__ branch, double B, int has_B, double rho,
                             const double* __restrict__ lam, double* __restrict__ z, double* __restrict__ c,
-                            long long off, long long nloc) {
+                            long long off, long long nloc, const signed char* __restrict__ rs) {
     const int br = (has_B && branch) ? *branch : -1;
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n;
          i += (long long)gridDim.x * blockDim.x) {
@@ -997,6 +999,7 @@ __global__ void k_scatter_z(long long n, const double* __restrict__ u, const u32
         if (br == 0) x = fmin(x, B);       // branch a: all z <= B  (PAV_cpt.py:211)
         else if (br == 1) x = fmax(x, B);  // branch b: all z >= B  (PAV_cpt.py:218)
         const long long l = g - off;
+        if (RS) x = rs[l] < 0 ? -x : x;
         z[l] = x;
         if (c) c[l] = x + lam[l] / rho;
     }
@@ -1448,10 +1451,14 @@ int launch_pav_tree(int loss, int64_t n, double rho, const double* ms, const dou
 
 int launch_scatter_z(int64_t n, const double* u, const u32* perm, const int* branch, double B, int has_B,
                      double rho, const double* lam, double* z, double* c, int64_t off, int64_t nloc,
-                     hipStream_t s) {
+                     hipStream_t s, const signed char* rs) {
     if (n <= 0) return RBL_OK;
-    hipLaunchKernelGGL(k_scatter_z, dim3(pv_grid(n)), dim3(256), 0, s, (long long)n, u, perm, branch, B, has_B, rho,
-                       lam, z, c, (long long)off, (long long)nloc);
+    if (rs)
+        hipLaunchKernelGGL(k_scatter_z<true>, dim3(pv_grid(n)), dim3(256), 0, s, (long long)n, u, perm, branch, B, has_B, rho,
+                           lam, z, c, (long long)off, (long long)nloc, rs);
+    else
+        hipLaunchKernelGGL(k_scatter_z<false>, dim3(pv_grid(n)), dim3(256), 0, s, (long long)n, u, perm, branch, B, has_B, rho,
+                           lam, z, c, (long long)off, (long long)nloc, rs);
     RBL_HIP(hipGetLastError());
     return RBL_OK;
 }

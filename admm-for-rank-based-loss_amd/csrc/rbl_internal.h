@@ -129,16 +129,19 @@ int launch_standardize_negy(int storage, void* D, int64_t n, int64_t ld, int64_t
                             const double* inv_std, const signed char* ysign, hipStream_t s);
 
 // ---- elementwise.hip --------------------------------------------------------------------
+// rs (optional, in the launchers below): the sign vector of a handle with labels of its own on a borrowed D
+// (rbl_set_labels): r_i = y_i * y_owner_i.  v, z, lambda, c are then in the owner's sign convention, m is the true m.
 int launch_erm_zc(int loss, int64_t n, double sigma0, double rho, const double* v, const double* lam,
-                  double* m, double* z, double* c, hipStream_t s);
+                  double* m, double* z, double* c, hipStream_t s, const signed char* rs = nullptr);
 // m = v - lambda/rho together with the sort's input: keys[i] = order-preserving transform of m[i], idx[i] = i + idx_off
 int launch_make_m_keys(int64_t n, double rho, const double* v, const double* lam, double* m, u64* keys, u32* idx,
-                       u32 idx_off, hipStream_t s);
+                       u32 idx_off, hipStream_t s, const signed char* rs = nullptr);
 int launch_keys_from_m(int64_t n, const double* m, u64* keys, u32* idx, hipStream_t s);
 // z-step with 32-bit sort keys (round 3): m and its range; the fixed-point keys; after the sort, sorted m / row ids with
 // the runs of equal keys put in (m, row) order (*flag = 1: a run too long - sort 64-bit keys instead)
 int s32_range_words();   // u64 words of the range buffer mm
-int launch_make_m_range(int64_t n, double rho, const double* v, const double* lam, double* m, u64* mm, hipStream_t s);
+int launch_make_m_range(int64_t n, double rho, const double* v, const double* lam, double* m, u64* mm, hipStream_t s,
+                        const signed char* rs = nullptr);
 int launch_keys32(int64_t n, const double* m, const u64* mm, u32* keys, u32* idx, u32 idx_off, hipStream_t s);
 int launch_sort32_fix(int64_t n, const u32* keys, const u32* ids, const double* m, u32 off, double* ms, u32* ids_out, int* flag,
                       hipStream_t s);
@@ -148,19 +151,22 @@ int launch_prox(int loss, int64_t n, const double* sigma, double rho, const doub
 int launch_dual(int loss, int64_t n, double rho, const double* z, const double* v, double* lam,
                 double* partials, double* red, hipStream_t s);
 int launch_accuracy(int loss, int64_t n, const double* v, const signed char* ysign, double tau, double* partials,
-                    double* out, hipStream_t s);
+                    double* out, hipStream_t s, const signed char* rs = nullptr);
 int launch_fair_counts(int64_t n, const double* v, const signed char* ysign, const double* group, double threshold,
-                       double* partials, double* out14, hipStream_t s);
+                       double* partials, double* out14, hipStream_t s, const signed char* rs = nullptr);
+// row-wise arg-max of the scores -ysign_i * V[j][i] over columns j0 .. j0 + kk - 1 (V: kk x n) against best / cls so far
+int launch_decide_rows(int64_t n, int kk, int j0, const double* V, const signed char* ysign, double* best, int* cls,
+                       hipStream_t s);
 int launch_weights(int wf, int64_t n, const double* args, double* alphas, double* betas, hipStream_t s);
 // generic deterministic two-stage reduction helpers
 int reduce_blocks();
 int launch_sum_partials(const double* partials, int nblocks, int K, double* out, hipStream_t s);
 // losses of v (for the objective), optionally as sortable keys
-int launch_loss_keys(int64_t n, const double* v, u64* keys, hipStream_t s);
+int launch_loss_keys(int64_t n, const double* v, u64* keys, hipStream_t s, const signed char* rs = nullptr);
 int launch_sorted_loss_dot(int loss, int64_t n, const u64* sorted_keys, const double* sigma,
                            double* partials, double* out, hipStream_t s);
 int launch_loss_sum(int loss, int64_t n, const double* v, double scale, double* partials, double* out,
-                    hipStream_t s);
+                    hipStream_t s, const signed char* rs = nullptr);
 
 // ---- sort.hip -------------------------------------------------------------------------
 struct SortWorkspace {
@@ -261,7 +267,7 @@ int launch_zd_scatter(int64_t n, const u32* ids, const double* uu, const int* br
                       const double* lam, double* z, double* c, int64_t off, int64_t nloc, hipStream_t s);
 int launch_scatter_z(int64_t n, const double* u, const u32* perm, const int* branch, double B, int has_B,
                      double rho, const double* lam, double* z, double* c, int64_t off, int64_t nloc,
-                     hipStream_t s);
+                     hipStream_t s, const signed char* rs = nullptr);
 
 // ---- wstep.hip --------------------------------------------------------------------------
 struct WstepWorkspace {
@@ -414,8 +420,10 @@ size_t zb_hist_bytes();
 size_t zb_partials_bytes();
 int launch_zb_edges(const double* sigma, int64_t n, long long* pos, int* counter, int cap, hipStream_t s);
 // z = the z-step, c = z + lambda/rho in the same pass
+// rs (optional): z and c are written in the owner's sign convention (z~ = r z, c~ = z~ + lambda~/rho); keys and m are the true m's
 int launch_zband(int loss, const ZbConfig& cfg, int64_t n, double rho, const u64* keys, const double* m, double* z,
-                 const double* lam, double* c, ZbState* st, u32* hist, double* partials, int* pin, int seq, u32* counters, hipStream_t s);
+                 const double* lam, double* c, ZbState* st, u32* hist, double* partials, int* pin, int seq, u32* counters, hipStream_t s,
+                 const signed char* rs = nullptr);
 int launch_zband_risk(int loss, const ZbConfig& cfg, int64_t n, const u64* keys, ZbState* st, u32* hist, double* partials,
                       double* out_dev, hipStream_t s);
 // the steps of launch_zband one by one (multi-GPU driver: collectives in between)

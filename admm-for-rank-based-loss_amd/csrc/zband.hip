@@ -961,12 +961,14 @@ __global__ __launch_bounds__(256) void k_zb_risk_finish(const ZbState* __restric
 }
 
 // ------------------------------------------------------------------------------------------ apply
-template <int LOSS>
+// RS: a handle with labels of its own on a borrowed D (rbl_set_labels) - m is the true m, z and c are stored in the
+// owner's sign convention: z~ = r z, c~ = z~ + lambda~/rho
+template <int LOSS, bool RS>
 __global__ __launch_bounds__(ZB_THREADS) void k_zb_apply(const double* __restrict__ m, long long n,
                                                           const ZbState* __restrict__ st, ZbConfig cfg, double rho,
                                                           double* __restrict__ z, const double* __restrict__ lam,
                                                           double* __restrict__ c, int* __restrict__ pin, int seq,
-                                                          u32* __restrict__ counters) {
+                                                          u32* __restrict__ counters, const signed char* __restrict__ rs) {
     __shared__ u64 bhi[ZB_MAX_BANDS];
     __shared__ double lo[ZB_MAX_BANDS], hi[ZB_MAX_BANDS], mlo[ZB_MAX_BANDS], mhi[ZB_MAX_BANDS], sg[ZB_MAX_BANDS];
     __shared__ int status;
@@ -1030,13 +1032,19 @@ __global__ __launch_bounds__(ZB_THREADS) void k_zb_apply(const double* __restric
         double2 r, cc;
         r.x = one(v.x);
         r.y = one(v.y);
+        if (RS) {
+            const char2 sg2 = reinterpret_cast<const char2*>(rs)[i];
+            r.x = sg2.x < 0 ? -r.x : r.x;
+            r.y = sg2.y < 0 ? -r.y : r.y;
+        }
         cc.x = r.x + l.x / rho;
         cc.y = r.y + l.y / rho;
         z2[i] = r;
         c2[i] = cc;
     }
     if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {
-        z[n - 1] = one(m[n - 1]);
+        const double zl = one(m[n - 1]);
+        z[n - 1] = (RS && rs[n - 1] < 0) ? -zl : zl;
         c[n - 1] = z[n - 1] + lam[n - 1] / rho;
     }
 }
@@ -1077,7 +1085,8 @@ int launch_zb_edges(const double* sigma, int64_t n, long long* pos, int* counter
 
 // the whole banded z-step: keys (of m, any payload) -> z in row order; the status lands in pin[1] with pin[0] = seq
 int launch_zband(int loss, const ZbConfig& cfg, int64_t n, double rho, const u64* keys, const double* m, double* z,
-                 const double* lam, double* c, ZbState* st, u32* hist, double* partials, int* pin, int seq, u32* counters, hipStream_t s) {
+                 const double* lam, double* c, ZbState* st, u32* hist, double* partials, int* pin, int seq, u32* counters, hipStream_t s,
+                 const signed char* rs) {
     hipLaunchKernelGGL(k_zb_init, dim3(1), dim3(1024), 0, s, st, cfg, hist);
     const int hb = zb_eval_blocks(n), sb = zb_hist_blocks(n);
     double* glist = partials + 1024 * 4 * ZB_C;
@@ -1114,12 +1123,20 @@ int launch_zband(int loss, const ZbConfig& cfg, int64_t n, double rho, const u64
     }
     const int64_t ab = (n + ZB_THREADS * 8 - 1) / (ZB_THREADS * 8);
     const unsigned ag = (unsigned)(ab < 1 ? 1 : (ab > 2048 ? 2048 : ab));
-    if (loss == RBL_LOSS_BCE)
-        hipLaunchKernelGGL(k_zb_apply<0>, dim3(ag), dim3(ZB_THREADS), 0, s, m, (long long)n, (const ZbState*)st, cfg, rho, z, lam, c, pin,
-                           seq, counters);
+    const signed char* no_rs = nullptr;
+    if (rs) {
+        if (loss == RBL_LOSS_BCE)
+            hipLaunchKernelGGL((k_zb_apply<0, true>), dim3(ag), dim3(ZB_THREADS), 0, s, m, (long long)n, (const ZbState*)st, cfg, rho, z,
+                               lam, c, pin, seq, counters, rs);
+        else
+            hipLaunchKernelGGL((k_zb_apply<1, true>), dim3(ag), dim3(ZB_THREADS), 0, s, m, (long long)n, (const ZbState*)st, cfg, rho, z,
+                               lam, c, pin, seq, counters, rs);
+    } else if (loss == RBL_LOSS_BCE)
+        hipLaunchKernelGGL((k_zb_apply<0, false>), dim3(ag), dim3(ZB_THREADS), 0, s, m, (long long)n, (const ZbState*)st, cfg, rho, z,
+                           lam, c, pin, seq, counters, no_rs);
     else
-        hipLaunchKernelGGL(k_zb_apply<1>, dim3(ag), dim3(ZB_THREADS), 0, s, m, (long long)n, (const ZbState*)st, cfg, rho, z, lam, c, pin,
-                           seq, counters);
+        hipLaunchKernelGGL((k_zb_apply<1, false>), dim3(ag), dim3(ZB_THREADS), 0, s, m, (long long)n, (const ZbState*)st, cfg, rho, z,
+                           lam, c, pin, seq, counters, no_rs);
     RBL_HIP(hipGetLastError());
     return RBL_OK;
 }
@@ -1217,12 +1234,13 @@ int launch_zbd_apply(int loss, const ZbConfig& cfg, int64_t n, double rho, const
                      ZbState* st, int* pin, int seq, u32* counters, hipStream_t s) {
     const int64_t ab = (n + ZB_THREADS * 8 - 1) / (ZB_THREADS * 8);
     const unsigned ag = (unsigned)(ab < 1 ? 1 : (ab > 2048 ? 2048 : ab));
+    const signed char* no_rs = nullptr;   // (row-sharded handles carry no labels of their own)
     if (loss == RBL_LOSS_BCE)
-        hipLaunchKernelGGL(k_zb_apply<0>, dim3(ag), dim3(ZB_THREADS), 0, s, m, (long long)n, (const ZbState*)st, cfg, rho, z, lam, c, pin,
-                           seq, counters);
+        hipLaunchKernelGGL((k_zb_apply<0, false>), dim3(ag), dim3(ZB_THREADS), 0, s, m, (long long)n, (const ZbState*)st, cfg, rho, z,
+                           lam, c, pin, seq, counters, no_rs);
     else
-        hipLaunchKernelGGL(k_zb_apply<1>, dim3(ag), dim3(ZB_THREADS), 0, s, m, (long long)n, (const ZbState*)st, cfg, rho, z, lam, c, pin,
-                           seq, counters);
+        hipLaunchKernelGGL((k_zb_apply<1, false>), dim3(ag), dim3(ZB_THREADS), 0, s, m, (long long)n, (const ZbState*)st, cfg, rho, z,
+                           lam, c, pin, seq, counters, no_rs);
     RBL_HIP(hipGetLastError());
     return RBL_OK;
 }

@@ -55,8 +55,10 @@ class Optimizer:
         self.weight_function = weight_function                                                # :73
         self.l1_reg, self.l2_reg = l1_reg, l2_reg
         wstep = _wstep if _wstep is not None else (_lib.WSTEP_L1 if self.w_flag == 1 else _lib.WSTEP_L2)
-        # share_data: another solver of this package built on the same (X, y) - its device D and DTD are borrowed
+        # share_data: another solver of this package built on the same X - its device D and DTD are borrowed; a y that
+        # differs from that solver's becomes this solver's own labels (include/rbl.h: rbl_set_labels)
         share = None
+        y_own = None
         if share_data is not None:
             share = getattr(share_data, "_s", share_data)
             if not isinstance(share, _solver.Solver):
@@ -65,12 +67,16 @@ class Optimizer:
                 raise ValueError(f"share_data holds a {(share.n_total, share.d)} problem, X is {Xm.shape}")
             if share.cfg.storage != _lib.STORAGE.get(storage, -1) or share.cfg.device != int(device):
                 raise ValueError("share_data was built with another storage type or device")
+            if y is not None:
+                y_own = _solver.as_pm1_labels(y, self.num_row)      # shape / +-1 before any device call
         self._s = _solver.Solver(self.num_row, self.num_feature, weight_function, loss, reg=self.reg, wstep=wstep,
                                  B=B, args=args, smooth_t=_smooth_t, tol=tol, max_iter=max_iter, storage=storage,
                                  device=device, share=share)
         if share is None:
             self._s.set_data(Xm, y)                                                           # :23 D = -y*X
             self._s.gram()                                                                    # :24 DTD
+        elif y_own is not None:
+            self._s.set_labels(y_own)
         if w0 is not None:                                                                    # :39-40
             self._s.set_state(w=np.asarray(w0, dtype=np.float64).reshape(-1))
         self.objective = rankbasedObjective(None, None, weight_function, loss, l2_reg, l1_reg, B, n_class, args,
@@ -260,11 +266,12 @@ class ADMMgroup:
     for several problems in each of its two passes (include/rbl.h: rbl_group_*).
 
     ``problems``: a list of dicts with the reference's constructor keywords (``weight_function, loss, l2_reg, l1_reg, B,
-    args, w0``; ``smooth=True`` and ``t=`` make the member a smoothADMMmethod).  ``solvers`` are ordinary ADMMmethod /
+    args, w0``; ``smooth=True`` and ``t=`` make the member a smoothADMMmethod; ``y=`` gives the member labels of its own
+    on the shared X - one-vs-rest, multi-label - default: the group's ``y``).  ``solvers`` are ordinary ADMMmethod /
     smoothADMMmethod objects; start_store / main_loop / final_res mirror the single-solver calls and return lists in
     the order of ``problems``."""
 
-    _KEYS = ("weight_function", "loss", "l2_reg", "l1_reg", "B", "args", "w0", "smooth", "t")
+    _KEYS = ("weight_function", "loss", "l2_reg", "l1_reg", "B", "args", "w0", "smooth", "t", "y")
 
     def __init__(self, X, y, problems, storage="f32", device=0, max_iter=200, tol=1e-4):
         if not isinstance(problems, (list, tuple)) or len(problems) == 0:
@@ -291,6 +298,8 @@ class ADMMgroup:
                     raise ValueError("ehrm needs the reference point B")
                 if "t" in pr and not pr.get("smooth"):
                     raise ValueError("t is the smoothing parameter of smooth=True members")
+                if pr.get("y") is not None:
+                    pr["y"] = _solver.as_pm1_labels(pr["y"], np.shape(X)[0])
             except ValueError as e:
                 raise ValueError(f"problem {k}: {e}") from None
             self.problems.append(pr)
@@ -301,11 +310,12 @@ class ADMMgroup:
         for pr in self.problems:
             kw = {k: pr.get(k) for k in ("l2_reg", "l1_reg", "B", "args", "w0")}
             share = self.solvers[0] if self.solvers else None
+            yk = pr["y"] if pr.get("y") is not None else y
             if pr.get("smooth"):
-                s = smoothADMMmethod(X, y, pr["weight_function"], pr["loss"], t=pr.get("t", 1), max_iter=max_iter, tol=tol,
+                s = smoothADMMmethod(X, yk, pr["weight_function"], pr["loss"], t=pr.get("t", 1), max_iter=max_iter, tol=tol,
                                      storage=storage, device=device, share_data=share, **kw)
             else:
-                s = ADMMmethod(X, y, pr["weight_function"], pr["loss"], max_iter=max_iter, tol=tol, storage=storage,
+                s = ADMMmethod(X, yk, pr["weight_function"], pr["loss"], max_iter=max_iter, tol=tol, storage=storage,
                                device=device, share_data=share, **kw)
             self.solvers.append(s)
         self._group = _solver.Group([s._s for s in self.solvers])
@@ -320,10 +330,24 @@ class ADMMgroup:
         self._group.close()
 
     def start_store(self, X_test, y_test):
-        """test-set objectives of every member (Optimizer.start_store) on ONE uploaded test matrix"""
+        """test-set objectives of every member (Optimizer.start_store) on ONE uploaded test matrix.  y_test: one label
+        array for all members, or a list of K label arrays when the members carry labels of their own."""
+        K = len(self.solvers)
+        if isinstance(y_test, (list, tuple)) and len(y_test) > 0 and np.ndim(y_test[0]) >= 1:
+            if len(y_test) != K:
+                raise ValueError(f"problem {min(len(y_test), K)}: y_test lists {len(y_test)} label arrays for {K} problems")
+            n_test = _solver._as_matrix(X_test).shape[0]
+            ys = []
+            for k, yt in enumerate(y_test):
+                try:
+                    ys.append(_solver.as_pm1_labels(yt, n_test, what="y_test"))
+                except ValueError as e:
+                    raise ValueError(f"problem {k}: {e}") from None
+        else:
+            ys = [y_test] * K
         first = None
-        for s, pr in zip(self.solvers, self.problems):
-            Optimizer.start_store(s, X_test, y_test, pr["weight_function"], pr["loss"], pr.get("B"), pr.get("l2_reg"),
+        for s, pr, yk in zip(self.solvers, self.problems, ys):
+            Optimizer.start_store(s, X_test, yk, pr["weight_function"], pr["loss"], pr.get("B"), pr.get("l2_reg"),
                                   pr.get("l1_reg"), None, pr.get("args"), _share_data=first)
             first = first or s.test_objective
         self.store = True
@@ -364,3 +388,70 @@ class ADMMgroup:
 
     def final_res(self):
         return [s.final_res() for s in self.solvers]
+
+
+class OneVsRest:
+    """K-class classification as K one-vs-rest rank-based problems on ONE feature matrix: member k has the labels
+    y_k = +1 where ``labels == classes_[k]`` and -1 elsewhere; X is uploaded once, D and DTD are formed once and every
+    iteration reads D once for several classes in each of its two passes (ADMMgroup with per-member labels,
+    include/rbl.h: rbl_set_labels).  The reference's ``n_class`` / multinomial loss has no z-step (its prox is missing),
+    so this is the multi-class route of the ADMM.  ``predict`` takes the arg-max of x . w_k over the classes on the
+    GPU (rbl_decide_multi)."""
+
+    def __init__(self, X, labels, weight_function="erm", loss="binary_cross_entropy", l2_reg=None, l1_reg=None, B=None,
+                 args=None, storage="f32", device=0, max_iter=200, tol=1e-4):
+        Xm = _solver._as_matrix(X)
+        lab = np.asarray(labels.detach().cpu().numpy() if hasattr(labels, "detach") else labels).reshape(-1)
+        if lab.shape[0] != Xm.shape[0]:
+            raise ValueError(f"labels has {lab.shape[0]} entries for {Xm.shape[0]} rows")
+        self.classes_ = np.unique(lab)
+        if self.classes_.size < 2:
+            raise ValueError(f"OneVsRest needs at least 2 classes, labels holds {self.classes_.size}")
+        if self.classes_.size > 64:
+            raise ValueError(f"OneVsRest: at most 64 classes in one group, labels holds {self.classes_.size}")
+        ys = [np.where(lab == c, 1.0, -1.0) for c in self.classes_]
+        problems = [dict(weight_function=weight_function, loss=loss, l2_reg=l2_reg, l1_reg=l1_reg, B=B, args=args, y=yk)
+                    for yk in ys]
+        self._storage, self._device = storage, device
+        self.group = ADMMgroup(Xm, ys[0], problems, storage=storage, device=device, max_iter=max_iter, tol=tol)
+        self.W = None
+        self._test = None      # (objective-only solver holding the last test matrix, that matrix)
+
+    def main_loop(self, verbose=True):
+        """solves the K problems together -> W of shape (d, K), column k = class classes_[k]"""
+        ws = self.group.main_loop(verbose)
+        self.W = np.concatenate([np.asarray(w, dtype=np.float64).reshape(-1, 1) for w in ws], axis=1)
+        return self.W
+
+    def _current_W(self):
+        if self.W is None:
+            self.W = np.concatenate([s.w.reshape(-1, 1) for s in self.group.solvers], axis=1)
+        return self.W
+
+    def predict(self, X_test):
+        """class label of every row of X_test: classes_[argmax_k x . w_k] (ties: the first class)"""
+        Xt = _solver._as_matrix(X_test)
+        W = self._current_W()
+        if Xt.shape[1] != W.shape[0]:
+            raise ValueError(f"X_test has {Xt.shape[1]} features, the model {W.shape[0]}")
+        if self._test is None or self._test[1] is not X_test:
+            if self._test is not None:
+                self._test[0].close()
+            t = _solver.Solver(Xt.shape[0], Xt.shape[1], "erm", "binary_cross_entropy", storage=self._storage,
+                               device=self._device, objective_only=True)
+            t.set_data(Xt, np.ones(Xt.shape[0]))
+            self._test = (t, X_test)
+        return self.classes_[self._test[0].decide_multi(np.ascontiguousarray(W.T))]
+
+    def accuracy(self, X_test, labels_test):
+        lab = np.asarray(labels_test.detach().cpu().numpy() if hasattr(labels_test, "detach") else labels_test).reshape(-1)
+        pred = self.predict(X_test)
+        if lab.shape[0] != pred.shape[0]:
+            raise ValueError(f"labels_test has {lab.shape[0]} entries for {pred.shape[0]} rows")
+        return float(np.mean(pred == lab))
+
+    def close(self):
+        if self._test is not None:
+            self._test[0].close()
+            self._test = None
+        self.group.close()

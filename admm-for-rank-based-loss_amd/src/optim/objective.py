@@ -89,10 +89,13 @@ class rankbasedObjective:
             share = None if _share_data is None else _share_data._s
             if share is not None and (share.n, share.d) != (self.n, self.d):
                 raise ValueError(f"shared data is {(share.n, share.d)}, X is {(self.n, self.d)}")
+            y_own = _solver.as_pm1_labels(y, self.n) if share is not None and y is not None else None
             self._s = _solver.Solver(self.n, self.d, weight_function, loss, args=args, B=B, storage=storage,
                                      device=device, objective_only=True, share=share)
             if share is None:
                 self._s.set_data(Xm, y)
+            elif y_own is not None:
+                self._s.set_labels(y_own)      # labels of its own on the borrowed matrix (rbl_set_labels)
         self._alphas = self._betas = None
 
     def _sig(self):

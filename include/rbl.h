@@ -128,6 +128,21 @@ int  rbl_destroy(rbl_solver* h);
  * one frees them.  rbl_set_data, rbl_generate_synthetic, rbl_synth_*, rbl_gram_* on a borrower are RBL_ERR_STATE.  A
  * borrower used alone behaves exactly like a handle built from the same (X, y). */
 int  rbl_create_shared(const rbl_config* cfg, rbl_solver* owner, rbl_solver** out);
+/* Labels of its own for a borrower: K label vectors on ONE feature matrix (one-vs-rest, multi-label) are K borrowers of
+ * one upload.  y: n host doubles, +-1.  Labels are +-1, so with r = y * y_owner the member's D_k = -y_k*X is r*D and its
+ * Gram matrix is the owner's; the handle keeps r as one signed char per row (its only extra device memory) and runs the
+ * owner's passes in the owner's sign convention (z~ = r z, lambda~ = r lambda, c~ = r c: v = D w, the lambda update, the
+ * primal residual and q = D^T c~ are then literally the owner's launches), the sign being taken out where the z-step
+ * and the losses look at a row.  Negation is exact: the handle computes bit for bit what a handle built from (X, y)
+ * computes on the two-pass paths.  An erm handle with labels of its own runs the two-pass iteration
+ * (rbl_stats.fused == 0).  Every host-side entry point speaks the handle's OWN convention (rbl_get_state,
+ * rbl_set_state, rbl_phase_z_external, rbl_get_D = -y*X, rbl_get_labels, rbl_objective, rbl_accuracy,
+ * rbl_fair_statistics); of the device buffers, RBL_BUF_M holds the true m while RBL_BUF_Z / RBL_BUF_LAM / RBL_BUF_V are
+ * in the owner's sign convention.  y equal to the owner's labels leaves an ordinary borrower.  Call it before the
+ * first iteration and before the handle joins a group: not a borrower, iter > 0 or member of a live group is
+ * RBL_ERR_STATE; a value other than +-1 or a row-sharded handle (n != n_total) is RBL_ERR_INVALID.  Works on
+ * objective_only borrowers (a test matrix with per-member test labels). */
+int  rbl_set_labels(rbl_solver* h, const double* y);
 /* run the library's kernels on this hipStream_t: NULL is the (legacy) default stream,
  * (void*)-1 goes back to the handle's own non-blocking stream (the initial setting) */
 int  rbl_set_stream(rbl_solver* h, void* hip_stream);
@@ -205,6 +220,11 @@ int  rbl_group_solve(rbl_group* g, int max_iter, int want_objective, rbl_stats* 
 /* k_per_pass: members one shared launch carries (1: no shared passes at this width); shared_v / shared_q: shared
  * launches so far; single_passes[k]: n x d launches each member ran on its own since the group was created */
 int  rbl_group_counters(rbl_group* g, int* k_per_pass, int64_t* shared_v, int64_t* shared_q, int64_t* single_passes);
+/* The decision of k one-vs-rest classifiers on the rows of `data` (typically an objective_only handle holding a test
+ * matrix): cls[i] = argmax_j x_i . w_j, ties to the lowest j.  W: k x d host doubles (row j = w_j), cls: n host int32,
+ * 1 <= k <= 64.  The scores come from the groups' multi-column V product (ceil(k / k_per_pass) passes over data's D,
+ * the label sign in D = -y*X taken out), each pass followed by a row-wise comparison against the best score so far. */
+int  rbl_decide_multi(rbl_solver* data, int k, const double* W, int32_t* cls);
 /* rankbasedObjective.get_arrogate_loss(w) (objective.py:71-87); w: d host doubles */
 int  rbl_objective(rbl_solver* h, const double* w, int include_reg, double* out);
 

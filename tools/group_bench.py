@@ -3,12 +3,16 @@
 k_per_pass members) against the same K members stepped one after another through rbl_step, interleaved in one process.
 
     python tools/group_bench.py [--n 6000000] [--d 1000] [--storage f32] [--ks 1 2 4 8] [--warmup 5] [--steps 20]
-                                [--rounds 3] [--out profiles/group_bench_C2sq.json]
+                                [--rounds 3] [--labels] [--out profiles/group_bench_C2sq.json]
 
 Per K and per round: `warmup` + `steps` group steps, then `warmup` + `steps` sequential sweeps over the members (both
 end in a host wait, so wall time is device time + launch gaps).  Reported: median over rounds and the spread
 (min..max) of the per-iteration time of both, problems x iterations / s, and the bytes/s of D the group's shared
-passes sustain if the whole step were passes (a lower bound: the step also holds K z-steps and w-steps)."""
+passes sustain if the whole step were passes (a lower bound: the step also holds K z-steps and w-steps).
+
+--labels adds a third set of members to every round: the same K problems, members 2..K with random +-1 label vectors
+of their own (drawn on the host, rbl_set_labels) - the shape of a one-vs-rest job.  Its group step runs between the
+equal-label group and the sequential sweep of every round (relabelled_ms beside group_ms)."""
 import argparse
 import json
 import os
@@ -29,6 +33,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--labels", action="store_true", help="also time a group whose members 2..K carry random labels of their own")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     import admm_for_rank_based_loss_amd as rbl
@@ -41,13 +46,22 @@ def main():
     esz = 4 if a.storage == "f32" else 8
     ld = owner.info()["ld"]
     dbytes = a.n * ld * esz
-    record = dict(n=a.n, d=a.d, storage=a.storage, warmup=a.warmup, steps=a.steps, rounds=a.rounds, D_bytes=dbytes, results=[])
+    y0 = owner.labels() if a.labels else None
+    record = dict(labels=bool(a.labels), n=a.n, d=a.d, storage=a.storage, warmup=a.warmup, steps=a.steps, rounds=a.rounds, D_bytes=dbytes, results=[])
     for K in a.ks:
         # two sets of members on the same D: one iterated as a group, one member by member
         grp_members = [S(a.n, a.d, "superquantile", args=[levels[k]], share=owner, **kw) for k in range(K)]
         seq_members = [S(a.n, a.d, "superquantile", args=[levels[k]], share=owner, **kw) for k in range(K)]
         g = G(grp_members)
-        tg, ts = [], []
+        rel_members, gr = [], None
+        if a.labels:
+            import numpy as np
+            rng = np.random.default_rng(1000 + K)
+            rel_members = [S(a.n, a.d, "superquantile", args=[levels[k]], share=owner, **kw) for k in range(K)]
+            for s in rel_members[1:]:
+                s.set_labels(np.where(rng.random(a.n) < 0.5, -1.0, 1.0))
+            gr = G(rel_members)
+        tg, ts, tr = [], [], []
         for _ in range(a.rounds):
             for _ in range(a.warmup):
                 g.step()
@@ -55,6 +69,13 @@ def main():
             for _ in range(a.steps):
                 g.step()
             tg.append((time.perf_counter() - t0) / a.steps)
+            if gr is not None:
+                for _ in range(a.warmup):
+                    gr.step()
+                t0 = time.perf_counter()
+                for _ in range(a.steps):
+                    gr.step()
+                tr.append((time.perf_counter() - t0) / a.steps)
             for _ in range(a.warmup):
                 for s in seq_members:
                     s.step()
@@ -72,10 +93,18 @@ def main():
                    group_problem_iters_per_s=K / mg, sequential_problem_iters_per_s=K / ms,
                    shared_passes_per_step=passes, D_bytes_per_s_lower_bound=passes * dbytes / mg,
                    shared_v=cnt["shared_v"], shared_q=cnt["shared_q"], single_passes=cnt["single_passes"])
+        if gr is not None:
+            cr = gr.counters()
+            mr = statistics.median(tr)
+            res.update(relabelled_ms=mr * 1e3, relabelled_ms_range=[min(tr) * 1e3, max(tr) * 1e3], relabelled_over_equal=mr / mg,
+                       relabelled_shared_v=cr["shared_v"], relabelled_shared_q=cr["shared_q"],
+                       relabelled_single_passes=cr["single_passes"])
         record["results"].append(res)
         print(json.dumps(res), flush=True)
         g.close()
-        for s in grp_members + seq_members:
+        if gr is not None:
+            gr.close()
+        for s in grp_members + seq_members + rel_members:
             s.close()
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
