@@ -15,7 +15,34 @@ RBL_OK, RBL_ERR_INVALID, RBL_ERR_NO_DEVICE, RBL_ERR_HIP, RBL_ERR_STATE, RBL_ERR_
 LOSS = {"binary_cross_entropy": 0, "hinge": 1}
 WEIGHT = {"erm": 0, "extremile": 1, "superquantile": 2, "esrm": 3, "aorr": 4, "aorr_dc": 5, "ehrm": 6}
 WSTEP_L1, WSTEP_L2, WSTEP_SMOOTH_L1 = 1, 2, 3
-STORAGE = {"f32": 0, "float32": 0, "f64": 1, "float64": 1}
+STORAGE = {"f32": 0, "float32": 0, "f64": 1, "float64": 1, "fp16": 2, "float16": 2}
+_STORAGE_DTYPE = {0: np.float32, 1: np.float64, 2: np.float16}
+
+
+def storage_ld(d, storage):
+    """Row stride (elements) of the stored matrix: rows are whole 16-byte packets, zero padded - a multiple of 8 elements
+    with fp16 storage, of 4 with f32 / f64."""
+    e = 8 if STORAGE[storage] == 2 else 4
+    return (int(d) + e - 1) // e * e
+
+
+def storage_round(X, storage):
+    """The matrix the device stores for X, as float64: every entry rounded once (to nearest even) to the storage type.
+    The device solves, in fp64 arithmetic, the problem whose data matrix is this one.  A finite entry that does not fit the
+    storage type (fp16: |x| >= 65520) is a ValueError, as it is in rbl_set_data - never clipped."""
+    X = np.asarray(X, dtype=np.float64)
+    dt = _STORAGE_DTYPE[STORAGE[storage]]
+    with np.errstate(over="ignore"):
+        R = X.astype(dt).astype(np.float64)
+    bad = np.isinf(R) & np.isfinite(X)
+    if bad.any():
+        first = np.argwhere(bad)[0]
+        where = ", ".join(str(int(i)) for i in first)
+        name = {np.float16: "fp16", np.float32: "f32"}[dt]
+        limit = {np.float16: "float16 (|x| >= 65520)", np.float32: "float32"}[dt]
+        raise ValueError(f"{name} storage: {int(bad.sum())} finite entries do not fit {limit}, first at index ({where}) "
+                         f"(value {float(X[tuple(first)]):g}) - standardise the columns or use storage {'f32' if dt is np.float16 else 'f64'}")
+    return R
 BUF_M, BUF_Q, BUF_RED, BUF_G, BUF_V, BUF_Z, BUF_LAM, BUF_W, BUF_COLSTATS = range(9)
 (BUF_ZD_SKEYS, BUF_ZD_SIDS, BUF_ZD_RKEYS, BUF_ZD_RIDS, BUF_ZD_SMALL, BUF_ZD_BIDS, BUF_ZD_BU, BUF_ZD_ZIDS,
  BUF_ZD_ZU, BUF_ZD_COUNTS) = range(16, 26)

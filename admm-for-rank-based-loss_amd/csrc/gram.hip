@@ -1,7 +1,8 @@
 // gram.hip - G = D^T D (src/optim/algorithms.py:24), the one dense contraction of the
 // path and the only MFMA-shaped work: 2*n*d^2 flops, done once per problem.
 // fp64 matrix cores (v_mfma_f64_16x16x4_f64): D is widened to fp64 in registers so G is
-// exact to fp64 accumulation regardless of the storage type.
+// exact to fp64 accumulation regardless of the storage type (fp16 storage: halves are loaded as 16-bit values and
+// widened half -> float -> double, the arithmetic stays the fp64 MFMA).
 // Tiling: 128 x 128 output tile per 4-wave workgroup (each wave a 64 x 64 quadrant =
 // 4 x 4 MFMA tiles, 128 accumulator VGPRs), only tile pairs ti <= tj (symmetry), the row
 // (K) dimension split over blockIdx.y; partial tiles go to a slab and are summed in a
@@ -12,6 +13,16 @@ namespace {
 
 typedef double v4d __attribute__((ext_vector_type(4)));
 constexpr int GT = 128;  // block tile
+
+// an operand as it waits in registers between its load and its MFMA step
+template <typename T> struct GramRaw {
+    typedef T type;
+    __device__ static inline double widen(T x) { return (double)x; }
+};
+template <> struct GramRaw<rbl_half> {
+    typedef unsigned type;   // the half in the low 16 bits
+    __device__ static inline double widen(unsigned x) { return (double)(float)__builtin_bit_cast(_Float16, (unsigned short)x); }
+};
 
 template <typename T>
 __global__ __launch_bounds__(256) void k_gram(const T* __restrict__ D, long long n, long long ld, int ntiles,
@@ -65,8 +76,9 @@ __global__ __launch_bounds__(256) void k_gram(const T* __restrict__ D, long long
     }
     const long long row_bytes = ld * (long long)sizeof(T);
 
-    T ra[DEPTH][4], rb[DEPTH][4];
-    auto load_step = [&](long long r, T (&a)[4], T (&b)[4]) {
+    typedef typename GramRaw<T>::type raw_t;
+    raw_t ra[DEPTH][4], rb[DEPTH][4];
+    auto load_step = [&](long long r, raw_t (&a)[4], raw_t (&b)[4]) {
         long long left = (r_end - r) * row_bytes;   // bytes of this split from row r on (<= 0: nothing)
         if (left < 0) left = 0;
         if (left > 4 * row_bytes) left = 4 * row_bytes;
@@ -75,7 +87,10 @@ __global__ __launch_bounds__(256) void k_gram(const T* __restrict__ D, long long
             __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(D + rr * ld), 0, (int)left, 0x00020000);
 #pragma unroll
         for (int s = 0; s < 4; ++s) {
-            if constexpr (sizeof(T) == 4) {
+            if constexpr (sizeof(T) == 2) {
+                a[s] = (unsigned)__builtin_amdgcn_raw_buffer_load_b16(rs, (int)offa[s], 0, 0);
+                b[s] = (unsigned)__builtin_amdgcn_raw_buffer_load_b16(rs, (int)offb[s], 0, 0);
+            } else if constexpr (sizeof(T) == 4) {
                 a[s] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs, (int)offa[s], 0, 0));
                 b[s] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs, (int)offb[s], 0, 0));
             } else {
@@ -87,15 +102,15 @@ __global__ __launch_bounds__(256) void k_gram(const T* __restrict__ D, long long
             }
         }
     };
-    auto mfma_step = [&](T (&a)[4], T (&b)[4]) {
+    auto mfma_step = [&](raw_t (&a)[4], raw_t (&b)[4]) {
         double da[4], db[4];
 #pragma unroll
         for (int s = 0; s < 4; ++s) {
             // opaque use of the raw registers HERE: otherwise the compiler widens all DEPTH steps at the
             // top of the loop body and its s_waitcnt vmcnt(0) there drains the whole prefetch
             asm volatile("" : "+v"(a[s]), "+v"(b[s]));
-            da[s] = (double)a[s];
-            db[s] = (double)b[s];
+            da[s] = GramRaw<T>::widen(a[s]);
+            db[s] = GramRaw<T>::widen(b[s]);
         }
 #pragma unroll
         for (int si = 0; si < 4; ++si)
@@ -193,6 +208,9 @@ int launch_gram(int storage, const void* D, int64_t n, int64_t ld, int64_t d, do
     dim3 grid(g.npairs, g.ksplit);
     if (storage == RBL_STORE_F32)
         hipLaunchKernelGGL(k_gram<float>, grid, dim3(256), 0, s, (const float*)D, (long long)n, (long long)ld,
+                           g.ntiles, g.rows_per_split, slab);
+    else if (storage == RBL_STORE_F16)
+        hipLaunchKernelGGL(k_gram<rbl_half>, grid, dim3(256), 0, s, (const rbl_half*)D, (long long)n, (long long)ld,
                            g.ntiles, g.rows_per_split, slab);
     else
         hipLaunchKernelGGL(k_gram<double>, grid, dim3(256), 0, s, (const double*)D, (long long)n, (long long)ld,

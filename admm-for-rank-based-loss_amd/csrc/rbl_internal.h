@@ -83,6 +83,38 @@ typedef unsigned long long u64;
 typedef unsigned int u32;
 
 constexpr int RBL_WAVE = 64;
+
+// ---- RBL_STORE_F16: IEEE binary16 elements ----------------------------------------------------------------------
+// The kernels read halves as bit patterns out of 16-byte packets and widen them half -> float -> double (both exact);
+// rbl_half only types the pointers.  Every write of a half goes through f64_to_f16_bits: ONE round-to-nearest-even from
+// the fp64 value (integer arithmetic, the same on host and device - NumPy's float64 -> float16 conversion bit for bit),
+// subnormals kept, overflow to +-inf (the callers count those: rbl_set_data rejects them).
+typedef _Float16 rbl_half;
+__host__ __device__ inline unsigned short f64_to_f16_bits(double x) {
+    const u64 b = __builtin_bit_cast(u64, x);
+    const unsigned sign = (unsigned)(b >> 48) & 0x8000u;
+    const int e = (int)((b >> 52) & 0x7ff);
+    const u64 m = b & ((1ull << 52) - 1);
+    if (e == 0x7ff) return (unsigned short)(sign | 0x7c00u | (m ? 0x200u : 0u));   // inf / nan
+    const int he = e - 1023 + 15;                                                 // biased binary16 exponent
+    if (he >= 31) return (unsigned short)(sign | 0x7c00u);
+    if (e == 0 || he < -11) return (unsigned short)sign;                          // below half the smallest subnormal
+    const int shift = he > 0 ? 42 : 43 - he;                                      // bits dropped (subnormals: more)
+    const u64 mant = m | (1ull << 52);
+    u64 r = mant >> shift;
+    const u64 rem = mant & ((1ull << shift) - 1), half = 1ull << (shift - 1);
+    if (rem > half || (rem == half && (r & 1))) ++r;
+    // normal: r carries the implicit bit (1024 .. 2048), a carry moves into the exponent (and to inf from he = 30)
+    return (unsigned short)(sign | (unsigned)(he > 0 ? ((u64)(he - 1) << 10) + r : r));
+}
+__host__ __device__ inline bool f16_bits_inf(unsigned short h) { return (h & 0x7fffu) == 0x7c00u; }
+// the row stride: whole 16-byte packets, zero padded
+inline int64_t rbl_storage_ld(int storage, int64_t d) {
+    const int64_t e = storage == RBL_STORE_F16 ? 8 : 4;
+    return (d + e - 1) / e * e;
+}
+inline size_t rbl_storage_esz(int storage) { return storage == RBL_STORE_F16 ? 2 : storage == RBL_STORE_F32 ? 4 : 8; }
+inline int rbl_storage_packet(int storage) { return storage == RBL_STORE_F16 ? 8 : storage == RBL_STORE_F32 ? 4 : 2; }   // elements per 16 bytes
 constexpr int PAV_CHUNK_LOG = 10;              // prefix-sum chunk = 1024 sorted positions
 constexpr int PAV_CHUNK = 1 << PAV_CHUNK_LOG;
 
@@ -110,7 +142,7 @@ struct SeamRec {
 };
 
 // ---- sweep.hip ------------------------------------------------------------------------
-// v = D w : D is n x ld row-major (ld % 4 == 0, columns >= d are zero)
+// v = D w : D is n x ld row-major (ld % 4 == 0, fp16 storage: ld % 8 == 0; columns >= d are zero)
 int launch_gemv(int storage, const void* D, int64_t n, int64_t ld, const double* w, double* v,
                 int num_cu, hipStream_t s);
 // q = D^T c : partial column sums go to slab (gemvt_slab_rows() x ld doubles), then q
@@ -118,8 +150,9 @@ int gemvt_slab_rows(int num_cu);
 int launch_gemvt(int storage, const void* D, int64_t n, int64_t ld, const double* c, double* slab,
                  double* q, int num_cu, hipStream_t s, hipEvent_t main_done = nullptr);
 // D[r0+i][j] = -y[i] * X[i][j] for a chunk of rows already on the device (fp64 staging)
+// ovf (RBL_STORE_F16, else NULL): [0] += finite entries that rounded to +-inf, [1] = min of their row * d + column
 int launch_form_D(int storage, void* D, int64_t ld, int64_t row0, const double* Xdev, int64_t ldx,
-                  const double* ydev, int64_t rows, int64_t d, hipStream_t s);
+                  const double* ydev, int64_t rows, int64_t d, hipStream_t s, u64* ovf = nullptr);
 int launch_D_to_f64(int storage, const void* D, int64_t ld, int64_t n, int64_t d, double* out,
                     hipStream_t s);
 // column sums / sums of squares (slab-reduced, deterministic) and in-place standardisation
@@ -371,6 +404,15 @@ int launch_gram(int storage, const void* D, int64_t n, int64_t ld, int64_t d, do
 int launch_synth(int storage, void* D, int64_t n, int64_t ld, int64_t d, int64_t row_offset, u64 seed,
                  double class_sep, double flip_y, const int* special, const double* mix, const double* A16,
                  const int* vertex, signed char* ysign, hipStream_t s);
+// RBL_STORE_F16 (the matrix is written once, from regenerated draws): the labels and the column sums / sums of squares
+// of the unrounded fp32 draws (slab: 2 x synth_stats_rows(num_cu) x ld doubles), then D = half(-y (x - mean) inv_std)
+int synth_stats_rows(int num_cu);
+int launch_synth_stats(int64_t n, int64_t ld, int64_t d, int64_t row_offset, u64 seed, double class_sep, double flip_y,
+                       const int* special, const double* mix, const double* A16, const int* vertex, signed char* ysign,
+                       double* slab, double* sum, double* sumsq, int num_cu, hipStream_t s);
+int launch_synth_f16(void* D, int64_t n, int64_t ld, int64_t d, int64_t row_offset, u64 seed, double class_sep, double flip_y,
+                     const int* special, const double* mix, const double* A16, const int* vertex, const double* mean,
+                     const double* inv_std, hipStream_t s);
 
 // ---- zband.hip: z-step for piecewise-constant rank weights without a sort -------------------
 constexpr int ZB_BITS = 11;          // radix-select digit (last pass: the remaining 9 bits)

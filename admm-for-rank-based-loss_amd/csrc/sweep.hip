@@ -3,7 +3,7 @@
 //   v = D w      replaces the three GEMVs of src/optim/algorithms.py:89,132,135
 //   q = D^T c    replaces the n-space sweeps of src/util/fast_lasso.py:41,43,55 and
 //                src/util/w_LBFGS.py:34,43 (the w-step then runs in d-space on G = D^T D)
-// D is row-major, ld % 4 == 0, stored fp32 (default) or fp64; accumulation is fp64.
+// D is row-major, ld % 4 == 0, stored fp32 (default), fp64 or fp16 (ld % 8 == 0); accumulation is fp64.
 // Both kernels read D exactly once with 16-byte per-lane loads (1 KiB per wave
 // instruction); they are memory bound: algorithmic bytes = n*ld*sizeof(T) per launch.
 #include "rbl_internal.h"
@@ -41,6 +41,26 @@ template <> struct Pkt<double> {
     }
 };
 
+// fp16 storage: 8 halves per packet, element k = the low (k even) or high half of dword k / 2, widened
+// half -> float -> double (both exact)
+typedef unsigned int u32x4_t __attribute__((ext_vector_type(4)));
+template <> struct Pkt<rbl_half> {
+    static constexpr int E = 8;
+    typedef u32x4_t type;
+    __device__ static inline double at(const u32x4_t& p, int k) {
+        const unsigned short h = (unsigned short)((k & 1) ? p[k >> 1] >> 16 : p[k >> 1]);
+        return (double)(float)__builtin_bit_cast(_Float16, h);
+    }
+    __device__ static inline void fma(const u32x4_t& p, const double* w, double& acc) {
+#pragma unroll
+        for (int k = 0; k < 8; ++k) acc = __builtin_fma(at(p, k), w[k], acc);
+    }
+    __device__ static inline void axpy(const u32x4_t& p, double c, double* acc) {
+#pragma unroll
+        for (int k = 0; k < 8; ++k) acc[k] = __builtin_fma(at(p, k), c, acc[k]);
+    }
+};
+
 // D is streamed once per pass and is far larger than L2 + MALL: the loads carry the non-temporal hint (measured on
 // MI355X: +8 % on the single-sweep kernel; RBL_D_STREAM=0 at compile time restores plain loads)
 #ifndef RBL_D_STREAM
@@ -60,6 +80,14 @@ __device__ inline double2 ld_stream(const double2* p) {
 #if RBL_D_STREAM
     const f64x2_t v = __builtin_nontemporal_load(reinterpret_cast<const f64x2_t*>(p));
     return make_double2(v.x, v.y);
+#else
+    return *p;
+#endif
+}
+
+__device__ inline u32x4_t ld_stream(const u32x4_t* p) {
+#if RBL_D_STREAM
+    return __builtin_nontemporal_load(p);
 #else
     return *p;
 #endif
@@ -295,7 +323,7 @@ __global__ __launch_bounds__(256) void k_gemvt(const T* __restrict__ D, long lon
 
     // fold the RPB row groups of the block (only when a row is narrower than the block)
     if (RPB > 1) {
-        __shared__ double red[256 * 4];
+        __shared__ double red[256 * (E > 4 ? E : 4)];
         for (int pass = 0; pass < (SQ ? 2 : 1); ++pass) {
 #pragma unroll
             for (int j = 0; j < PJ; ++j) {
@@ -415,6 +443,26 @@ __global__ void k_form_D(T* __restrict__ D, long long ld, long long row0, const 
     double val = (j < d) ? -y[r] * X[r * ldx + j] : 0.0;  // algorithms.py:23  D = -y * X
     D[(row0 + r) * ld + j] = (T)val;
 }
+// fp16 storage: one thread per pair of columns (a 4-byte store), one rounding from the fp64 product; finite entries that
+// round to +-inf are counted and the first one (smallest row * d + column) is kept for the error message
+__global__ void k_form_D_f16(unsigned* __restrict__ D, long long ld, long long row0, const double* __restrict__ X,
+                             long long ldx, const double* __restrict__ y, long long rows, long long d, u64* ovf) {
+    const long long hl = ld / 2;
+    long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= rows * hl) return;
+    const long long r = i / hl, j = (i - r * hl) * 2;
+    unsigned short h[2];
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+        const double val = (j + k < d) ? -y[r] * X[r * ldx + j + k] : 0.0;
+        h[k] = f64_to_f16_bits(val);
+        if (f16_bits_inf(h[k]) && val - val == 0.0) {   // finite in, infinite out
+            atomicAdd(&ovf[0], 1ull);
+            atomicMin(&ovf[1], (u64)((row0 + r) * d + j + k));
+        }
+    }
+    D[(row0 + r) * hl + j / 2] = (unsigned)h[0] | ((unsigned)h[1] << 16);
+}
 
 template <typename T>
 __global__ void k_D_to_f64(const T* __restrict__ D, long long ld, long long n, long long d,
@@ -422,9 +470,8 @@ __global__ void k_D_to_f64(const T* __restrict__ D, long long ld, long long n, l
     long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n * d) return;
     long long r = i / d, j = i - r * d;
-    out[i] = (double)D[r * ld + j];
+    out[i] = (double)D[r * ld + j];   // (fp16: half -> float -> double, exact)
 }
-
 template <typename T>
 __global__ void k_standardize_negy(T* __restrict__ D, long long n, long long ld, long long d,
                                    const double* __restrict__ mean, const double* __restrict__ inv_std,
@@ -450,6 +497,7 @@ int launch_gemv(int storage, const void* D, int64_t n, int64_t ld, const double*
                 hipStream_t s) {
     if (n <= 0) return RBL_OK;
     if (storage == RBL_STORE_F32) return gemv_T<float>((const float*)D, n, ld, w, v, num_cu, s);
+    if (storage == RBL_STORE_F16) return gemv_T<rbl_half>((const rbl_half*)D, n, ld, w, v, num_cu, s);
     return gemv_T<double>((const double*)D, n, ld, w, v, num_cu, s);
 }
 
@@ -463,6 +511,8 @@ int launch_gemvt(int storage, const void* D, int64_t n, int64_t ld, const double
     int nb = gemvt_blocks(num_cu, n);
     if (storage == RBL_STORE_F32)
         RBL_TRY((gemvt_T<float, false>((const float*)D, n, ld, c, slab, nullptr, nb, s)));
+    else if (storage == RBL_STORE_F16)
+        RBL_TRY((gemvt_T<rbl_half, false>((const rbl_half*)D, n, ld, c, slab, nullptr, nb, s)));
     else
         RBL_TRY((gemvt_T<double, false>((const double*)D, n, ld, c, slab, nullptr, nb, s)));
     if (main_done) RBL_HIP(hipEventRecord(main_done, s));  // the sweep kernel alone (roofline timing)
@@ -473,6 +523,10 @@ int launch_gemvt(int storage, const void* D, int64_t n, int64_t ld, const double
 
 int launch_colstats(int storage, const void* D, int64_t n, int64_t ld, double* slab, double* sum,
                     double* sumsq, int num_cu, hipStream_t s) {
+    if (storage == RBL_STORE_F16) {   // the generator takes them from the unrounded draws (synth.hip: launch_synth_stats)
+        rbl_set_error("colstats: not available for RBL_STORE_F16");
+        return RBL_ERR_INVALID;
+    }
     int nb = gemvt_blocks(num_cu, n);
     double* slab2 = slab + (size_t)gemvt_slab_rows(num_cu) * ld;
     if (storage == RBL_STORE_F32)
@@ -486,11 +540,14 @@ int launch_colstats(int storage, const void* D, int64_t n, int64_t ld, double* s
 }
 
 int launch_form_D(int storage, void* D, int64_t ld, int64_t row0, const double* Xdev, int64_t ldx,
-                  const double* ydev, int64_t rows, int64_t d, hipStream_t s) {
+                  const double* ydev, int64_t rows, int64_t d, hipStream_t s, u64* ovf) {
     long long total = rows * ld;
     if (total <= 0) return RBL_OK;
     unsigned grid = (unsigned)((total + 255) / 256);
-    if (storage == RBL_STORE_F32)
+    if (storage == RBL_STORE_F16)
+        hipLaunchKernelGGL(k_form_D_f16, dim3((unsigned)((total / 2 + 255) / 256)), dim3(256), 0, s, (unsigned*)D, (long long)ld,
+                           (long long)row0, Xdev, (long long)ldx, ydev, (long long)rows, (long long)d, ovf);
+    else if (storage == RBL_STORE_F32)
         hipLaunchKernelGGL(k_form_D<float>, dim3(grid), dim3(256), 0, s, (float*)D, (long long)ld, (long long)row0,
                            Xdev, (long long)ldx, ydev, (long long)rows, (long long)d);
     else
@@ -507,6 +564,9 @@ int launch_D_to_f64(int storage, const void* D, int64_t ld, int64_t n, int64_t d
     if (storage == RBL_STORE_F32)
         hipLaunchKernelGGL(k_D_to_f64<float>, dim3(grid), dim3(256), 0, s, (const float*)D, (long long)ld,
                            (long long)n, (long long)d, out);
+    else if (storage == RBL_STORE_F16)
+        hipLaunchKernelGGL(k_D_to_f64<rbl_half>, dim3(grid), dim3(256), 0, s, (const rbl_half*)D, (long long)ld,
+                           (long long)n, (long long)d, out);
     else
         hipLaunchKernelGGL(k_D_to_f64<double>, dim3(grid), dim3(256), 0, s, (const double*)D, (long long)ld,
                            (long long)n, (long long)d, out);
@@ -520,6 +580,10 @@ int launch_standardize_negy(int storage, void* D, int64_t n, int64_t ld, int64_t
     if (total <= 0) return RBL_OK;
     long long nblk = (total + 255) / 256;
     if (nblk > (1 << 20)) nblk = 1 << 20;   // grid-stride kernel: at most 2^28 threads per launch
+    if (storage == RBL_STORE_F16) {   // would round twice: the generator writes fp16 matrices in one rounding (synth.hip)
+        rbl_set_error("standardize_negy: not available for RBL_STORE_F16");
+        return RBL_ERR_INVALID;
+    }
     if (storage == RBL_STORE_F32)
         hipLaunchKernelGGL(k_standardize_negy<float>, dim3((unsigned)nblk), dim3(256), 0, s, (float*)D, (long long)n,
                            (long long)ld, (long long)d, mean, inv_std, ysign);

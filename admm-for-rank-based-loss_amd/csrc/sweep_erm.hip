@@ -39,6 +39,14 @@ template <> struct Pk<double> {
     static constexpr int E = 2;
     __device__ static inline double at(const u32x4& p, int k) { return __hiloint2double((int)p[2 * k + 1], (int)p[2 * k]); }
 };
+// fp16 storage: element k is the low (k even) or high half of dword k / 2, widened half -> float -> double (both exact)
+template <> struct Pk<rbl_half> {
+    static constexpr int E = 8;
+    __device__ static inline double at(const u32x4& p, int k) {
+        const unsigned short h = (unsigned short)((k & 1) ? p[k >> 1] >> 16 : p[k >> 1]);
+        return (double)(float)__builtin_bit_cast(_Float16, h);
+    }
+};
 
 constexpr int SE_THREADS = 256;
 
@@ -53,11 +61,11 @@ __device__ inline void row_store(double* __restrict__ base, long long row, doubl
                        __HIP_MEMORY_SCOPE_AGENT);
 }
 
-// fp32 storage: hide the packets from the optimiser between the dot phase and the accumulation
+// fp32 / fp16 storage: hide the packets from the optimiser between the dot phase and the accumulation
 // phase (otherwise the widened fp64 copies of the dot phase are kept alive: 2 VGPRs per element)
 template <typename T, int R, int P>
 __device__ inline void opaque(u32x4 (&buf)[R][P]) {
-    if (sizeof(T) == 4) {
+    if (sizeof(T) <= 4) {
 #pragma unroll
         for (int r = 0; r < R; ++r)
 #pragma unroll
@@ -623,7 +631,12 @@ int launch_T(const T* D, long long n, long long ld, const double* w, const doubl
     // packets per sub-batch (64 KB in flight per wave) 143.7 it/s against round 2's one row per sub-batch with two
     // blocks per CU 136.4-138.6, two rows 140.5-143.5.  fp32 storage took the workgroup-per-row kernel from d = 1025 on
     // until round 3 (4M x 2000: 171.8 it/s, 5.5 TB/s).
-    if (passes <= 8) RBL_ONE(8, 4, 4, true);
+    // fp16 storage leaves the wave-per-row kernel at 4 packets per lane (ld <= 2048, as fp32 storage does): at 8 the
+    // block's fold of 64 x 8 x 8 column sums per wave (128 KB) and w (32 KB) do not fit the CU's LDS together; rows of
+    // 257-512 packets take the workgroup-per-row kernel's first instance
+    if constexpr (sizeof(T) > 2) {
+        if (passes <= 8) RBL_ONE(8, 4, 4, true);
+    }
 #undef RBL_ONE
     // wider rows: one workgroup of 512 threads per row batch (grid = one workgroup per CU)
     const long long pt = (PK + SEW_THREADS - 1) / SEW_THREADS;
@@ -650,13 +663,21 @@ int launch_T(const T* D, long long n, long long ld, const double* w, const doubl
     // 4 rows 203.2, 5 rows 208.0, 6 rows 210.6;  d = 8000: 2 rows 178.7, 3 rows 200.4, 4 rows 209.8;  d = 10 000: 1 row
     // 80.0, 2 rows 124.6, 3 rows 132.3 (4 rows spill: 68);  d = 12 000: 1 row 130.7, 2 rows 200.6;  d = 16 000: 1 row
     // 147.1 (two spill).
-    if (pt <= 1) RBL_WIDE(1, 16, 1);   // (fp32 storage reaches this kernel from 9 packets per lane on: pt >= 2)
+    if (pt <= 1) RBL_WIDE(1, 16, 1);   // (fp32 storage reaches this kernel from 9 packets per lane on: pt >= 2; fp16 from 5 on)
     if (pt <= 2) RBL_WIDE(2, 8, 2);
-    if (pt <= 3) RBL_WIDE(3, 6, 4);
-    if (pt <= 4) RBL_WIDE(4, 4, 4);
-    if (pt <= 5) RBL_WIDE(5, 3, 8);
-    if (pt <= 6) RBL_WIDE(6, 2, 8);
-    if (pt <= 8) RBL_WIDE(8, 1, 16);   // (two rows spill with fp32 storage)
+    // fp16 storage: w in LDS is PT x 32 KB and a thread's column sums are PT x 8 doubles (twice fp32's registers at equal
+    // PT), so its rows end at 4 packets per thread (sweep_erm_supported) and the two widest instances hold fewer rows
+    // per sub-batch than fp32's (3, 6, 4) / (4, 4, 4), which spill 48-212 bytes per lane with 8 halves per packet
+    if constexpr (sizeof(T) == 2) {
+        if (pt <= 3) RBL_WIDE(3, 4, 4);
+        if (pt <= 4) RBL_WIDE(4, 2, 8);
+    } else {
+        if (pt <= 3) RBL_WIDE(3, 6, 4);
+        if (pt <= 4) RBL_WIDE(4, 4, 4);
+        if (pt <= 5) RBL_WIDE(5, 3, 8);
+        if (pt <= 6) RBL_WIDE(6, 2, 8);
+        if (pt <= 8) RBL_WIDE(8, 1, 16);   // (two rows spill with fp32 storage)
+    }
 #undef RBL_WIDE
     rbl_set_error("single-sweep kernel: d=%lld too wide", (long long)ld);
     return RBL_ERR_INVALID;
@@ -665,10 +686,11 @@ int launch_T(const T* D, long long n, long long ld, const double* w, const doubl
 }  // namespace
 
 bool sweep_erm_supported(int storage, int64_t ld) {
-    const int64_t PK = ld / (storage == RBL_STORE_F32 ? 4 : 2);
+    const int64_t PK = ld / rbl_storage_packet(storage);
     // wave-per-row kernel up to 4 (fp32) / 8 (fp64) passes of 64 packets, workgroup-per-row
-    // kernel up to 8 packets per thread: d <= 16384 (fp32) / 8192 (fp64)
-    return PK > 32 && PK <= 8 * SEW_THREADS;
+    // kernel up to 8 packets per thread: d <= 16384 (fp32) / 8192 (fp64).  fp16: 4 packets per thread (w in LDS is
+    // 8 doubles per packet: 128 KB at 4), which is the same d <= 16384; rows of <= 32 packets are ld <= 256
+    return PK > 32 && PK <= (storage == RBL_STORE_F16 ? 4 : 8) * SEW_THREADS;
 }
 // upper bound of the blocks a single-sweep launch uses (slab rows, partial triples): 2 per CU; the shapes that run one
 // block per CU (launch_T) use the first half
@@ -683,7 +705,11 @@ int launch_sweep_erm(int storage, int loss, const void* D, int64_t n, int64_t ld
     double* const v_for_loss = v;
     if (!want_obj) v = nullptr;   // 8 of the 24 B/row of row-wise stores: only the loss sum reads v after the pass
     int rc;
-    if (storage == RBL_STORE_F32) {
+    if (storage == RBL_STORE_F16) {
+        rc = (loss == RBL_LOSS_BCE)
+                 ? launch_T<rbl_half, 0>((const rbl_half*)D, n, ld, w, z_old, lam, v, z_new, sigma0, rho, pred_dev, slab, partials, grid, num_cu, &nrows, s)
+                 : launch_T<rbl_half, 1>((const rbl_half*)D, n, ld, w, z_old, lam, v, z_new, sigma0, rho, pred_dev, slab, partials, grid, num_cu, &nrows, s);
+    } else if (storage == RBL_STORE_F32) {
         rc = (loss == RBL_LOSS_BCE)
                  ? launch_T<float, 0>((const float*)D, n, ld, w, z_old, lam, v, z_new, sigma0, rho, pred_dev, slab, partials, grid, num_cu, &nrows, s)
                  : launch_T<float, 1>((const float*)D, n, ld, w, z_old, lam, v, z_new, sigma0, rho, pred_dev, slab, partials, grid, num_cu, &nrows, s);
@@ -745,7 +771,7 @@ int launch_v_T(const T* D, long long n, long long ld, const double* w, const dou
 // rank-weighted problems: v = D w, lambda += rho (z - v), red[0] = sum (z - v)^2 in one pass
 // (replaces k_gemv + k_dual when the row width fits the wave-per-row kernel)
 bool sweep_v_supported(int storage, int64_t ld) {
-    const int64_t PK = ld / (storage == RBL_STORE_F32 ? 4 : 2);
+    const int64_t PK = ld / rbl_storage_packet(storage);   // (fp16: 256 < ld <= 4096)
     return PK > 32 && PK <= 512;
 }
 
@@ -757,6 +783,8 @@ int launch_sweep_v(int storage, const void* D, int64_t n, int64_t ld, const doub
     const int grid = num_cu;
     if (storage == RBL_STORE_F32)
         RBL_TRY(launch_v_T<float>((const float*)D, n, ld, w, z, lam, v, rho, partials, grid, s));
+    else if (storage == RBL_STORE_F16)
+        RBL_TRY(launch_v_T<rbl_half>((const rbl_half*)D, n, ld, w, z, lam, v, rho, partials, grid, s));
     else
         RBL_TRY(launch_v_T<double>((const double*)D, n, ld, w, z, lam, v, rho, partials, grid, s));
     if (main_done) RBL_HIP(hipEventRecord(main_done, s));
@@ -802,6 +830,8 @@ int launch_sweep_q(int storage, const void* D, int64_t n, int64_t ld, const doub
     const int grid = num_cu;   // one block per CU (see launch_sweep_v)
     if (storage == RBL_STORE_F32)
         RBL_TRY(launch_q_T<float>((const float*)D, n, ld, c, slab, grid, s));
+    else if (storage == RBL_STORE_F16)
+        RBL_TRY(launch_q_T<rbl_half>((const rbl_half*)D, n, ld, c, slab, grid, s));
     else
         RBL_TRY(launch_q_T<double>((const double*)D, n, ld, c, slab, grid, s));
     if (main_done) RBL_HIP(hipEventRecord(main_done, s));

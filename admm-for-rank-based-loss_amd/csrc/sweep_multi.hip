@@ -33,6 +33,14 @@ template <> struct Pk<double> {
     static constexpr int E = 2;
     __device__ static inline double at(const u32x4& p, int k) { return __hiloint2double((int)p[2 * k + 1], (int)p[2 * k]); }
 };
+// fp16 storage: element k is the low (k even) or high half of dword k / 2, widened half -> float -> double (both exact)
+template <> struct Pk<rbl_half> {
+    static constexpr int E = 8;
+    __device__ static inline double at(const u32x4& p, int k) {
+        const unsigned short h = (unsigned short)((k & 1) ? p[k >> 1] >> 16 : p[k >> 1]);
+        return (double)(float)__builtin_bit_cast(_Float16, h);
+    }
+};
 
 constexpr int SM_THREADS = 256;
 constexpr int SM_SLICES = 8;   // slices of the column reduction (CR_SLICES of sweep_erm.hip: same order of the sums)
@@ -411,7 +419,9 @@ int launch_vm_T(const T* D, long long n, long long ld, const MultiV& a, int grid
     if (passes == 1) RBL_VM(1, 8, 2);
     if (passes == 2) RBL_VM(2, 4, 4);
     if (passes <= 4) RBL_VM(4, 2, 8);
-    if (passes <= 8) RBL_VM(8, 2, 8);
+    if constexpr (sizeof(T) > 2) {   // fp16 storage: up to 4 packets per lane (sweep_multi_supported)
+        if (passes <= 8) RBL_VM(8, 2, 8);
+    }
 #undef RBL_VM
     rbl_set_error("multi-column V pass: ld=%lld outside the wave-per-row range", ld);
     return RBL_ERR_INVALID;
@@ -429,7 +439,9 @@ int launch_qm_T(const T* D, long long n, long long ld, const MultiQ& a, double* 
     if (passes == 1) RBL_QM(1, 8, 2);
     if (passes == 2) RBL_QM(2, 4, 4);
     if (passes <= 4) RBL_QM(4, 2, 8);
-    if (passes <= 8) RBL_QM(8, 2, 8);
+    if constexpr (sizeof(T) > 2) {
+        if (passes <= 8) RBL_QM(8, 2, 8);
+    }
 #undef RBL_QM
     rbl_set_error("multi-column Q pass: ld=%lld outside the wave-per-row range", ld);
     return RBL_ERR_INVALID;
@@ -437,9 +449,15 @@ int launch_qm_T(const T* D, long long n, long long ld, const MultiQ& a, double* 
 
 }  // namespace
 
-bool sweep_multi_supported(int storage, int64_t ld) { return sweep_v_supported(storage, ld); }
+// fp16 storage: the Q pass keeps K x P x 8 fp64 column sums per lane - 4 packets per lane (ld <= 2048) are the 256
+// registers that 8 packets are with fp32 storage, so the shared range ends at the same width in ELEMENTS and begins, as
+// everywhere, above 32 packets per row (ld > 256); wider fp16 rows run each member's own passes
+bool sweep_multi_supported(int storage, int64_t ld) {
+    if (storage == RBL_STORE_F16) return sweep_v_supported(storage, ld) && ld <= 2048;
+    return sweep_v_supported(storage, ld);
+}
 
-// columns one launch carries: 4 for every supported width and both storage types (the Q pass' column sums at 8 packets
+// columns one launch carries: 4 for every supported width and every storage type (the Q pass' column sums at 8 packets
 // per lane and fp32 storage are 256 of the 512 registers a lane of the one block per CU may use; 8 columns do not fit)
 int sweep_multi_k(int storage, int64_t ld) {
     (void)storage;
@@ -477,6 +495,8 @@ int launch_sweep_v_multi(int storage, const void* D, int64_t n, int64_t ld, int 
     int rc;
     if (storage == RBL_STORE_F32)
         rc = k <= 2 ? launch_vm_T<float, 2>((const float*)D, n, ld, a, grid, s) : launch_vm_T<float, 4>((const float*)D, n, ld, a, grid, s);
+    else if (storage == RBL_STORE_F16)
+        rc = k <= 2 ? launch_vm_T<rbl_half, 2>((const rbl_half*)D, n, ld, a, grid, s) : launch_vm_T<rbl_half, 4>((const rbl_half*)D, n, ld, a, grid, s);
     else
         rc = k <= 2 ? launch_vm_T<double, 2>((const double*)D, n, ld, a, grid, s) : launch_vm_T<double, 4>((const double*)D, n, ld, a, grid, s);
     RBL_TRY(rc);
@@ -509,6 +529,9 @@ int launch_sweep_q_multi(int storage, const void* D, int64_t n, int64_t ld, int 
     if (storage == RBL_STORE_F32)
         rc = k <= 2 ? launch_qm_T<float, 2>((const float*)D, n, ld, a, slab, plane, grid, s)
                     : launch_qm_T<float, 4>((const float*)D, n, ld, a, slab, plane, grid, s);
+    else if (storage == RBL_STORE_F16)
+        rc = k <= 2 ? launch_qm_T<rbl_half, 2>((const rbl_half*)D, n, ld, a, slab, plane, grid, s)
+                    : launch_qm_T<rbl_half, 4>((const rbl_half*)D, n, ld, a, slab, plane, grid, s);
     else
         rc = k <= 2 ? launch_qm_T<double, 2>((const double*)D, n, ld, a, slab, plane, grid, s)
                     : launch_qm_T<double, 4>((const double*)D, n, ld, a, slab, plane, grid, s);

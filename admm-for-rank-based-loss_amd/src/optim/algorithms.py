@@ -7,7 +7,7 @@ the reference (citations: reference ``src/optim/algorithms.py``), so ``run_SRM.p
 directory on ``PYTHONPATH``.  State (w, z, lambda) lives on the GPU; the ``w`` / ``z`` /
 ``lagrangian`` attributes download it on access.  All arithmetic is done by librbl.so
 (include/rbl.h); this file is host glue.  Extra keyword arguments (after the reference's
-own): ``storage`` ("f32" default | "f64" strict), ``device``.
+own): ``storage`` ("f32" default | "f64" strict | "fp16" half the bytes of D, data rounded once to float16), ``device``.
 """
 import time
 

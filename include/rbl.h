@@ -50,8 +50,10 @@ enum {
  * (smoothADMMmethod) */
 enum { RBL_WSTEP_L1 = 1, RBL_WSTEP_L2 = 2, RBL_WSTEP_SMOOTH_L1 = 3 };
 
-/* element type D = -y*X is stored in (accumulation is always float64) */
-enum { RBL_STORE_F32 = 0, RBL_STORE_F64 = 1 };
+/* element type D = -y*X is stored in (accumulation is always float64).  RBL_STORE_F16 is IEEE binary16: rows are padded
+ * to a multiple of 8 elements (f32 / f64: of 4), the upload rounds to nearest even once, and a finite entry that does not
+ * fit the format (|x| >= 65520) is rejected by rbl_set_data (RBL_ERR_INVALID), never clipped. */
+enum { RBL_STORE_F32 = 0, RBL_STORE_F64 = 1, RBL_STORE_F16 = 2 };
 
 /* Constructor arguments of Optimizer.__init__ (src/optim/algorithms.py:20-75). */
 typedef struct rbl_config {
@@ -148,13 +150,17 @@ int  rbl_set_labels(rbl_solver* h, const double* y);
 int  rbl_set_stream(rbl_solver* h, void* hip_stream);
 
 /* ---- data: D = -y * X (algorithms.py:23), G = D^T D (algorithms.py:24) ---------- */
-/* X: n x d host rows with leading dimension ldx, y: n labels (+-1). */
+/* X: n x d host rows with leading dimension ldx, y: n labels (+-1).  RBL_STORE_F16: a finite entry that rounds to
+ * +-inf fails the call with RBL_ERR_INVALID (the message counts them and names the first one); the handle is then
+ * without data. */
 int  rbl_set_data(rbl_solver* h, const double* X, const double* y, int64_t ldx);
 /* Synthetic two-class data generated on the device (statistics of
  * src/util/load_data.py:101-116), never materialised on the host. */
 int  rbl_generate_synthetic(rbl_solver* h, uint64_t seed, double class_sep, double flip_y);
 /* sharded form: raw local rows + local column sums (RBL_BUF_COLSTATS, to be summed over
- * ranks), then standardise and scale by -y.  Same matrix for any sharding of the rows. */
+ * ranks), then standardise and scale by -y.  Same matrix for any sharding of the rows.
+ * RBL_STORE_F16: the column sums are those of the unrounded draws and the standardised values are regenerated and
+ * rounded once - the matrix is the element-wise binary16 rounding of the RBL_STORE_F64 generator's. */
 int  rbl_synth_local(rbl_solver* h, uint64_t seed, double class_sep, double flip_y);
 int  rbl_synth_finish(rbl_solver* h);
 /* labels of the generated rows (+-1), n doubles */
@@ -199,7 +205,7 @@ int  rbl_finalize_smooth(rbl_solver* h);
  *    2 ceil(K / k_per_pass) against K standalone single sweeps: with k_per_pass = 4 a group of erm problems is a loss
  *    at K = 1 (2 passes against 1), a tie at K = 2 and pays from K = 3 on (2 against 3, 2 against 4, 4 against 5, ...).
  *  - the shared passes exist for 32 < packets per row <= 512 (128 < ld <= 2048 with fp32 storage, 64 < ld <= 1024 with
- *    fp64); outside that range a group runs each member's own passes (shared_v == shared_q == 0, counted in
+ *    fp64, 256 < ld <= 2048 with fp16: the Q pass' column sums bound the width in elements); outside that range a group runs each member's own passes (shared_v == shared_q == 0, counted in
  *    single_passes).  Column k of a shared pass is bit-identical to the member's own single-column pass.
  *  - a member whose z-step was not certified redoes it and its own q with the single-column pass (counted in
  *    single_passes, as is the v = D w a member needs before its first z-step); the others are not disturbed.

@@ -43,7 +43,7 @@ def main():
     owner = S(a.n, a.d, "superquantile", args=[levels[0]], **kw)
     owner.generate_synthetic(seed=17)
     owner.gram()
-    esz = 4 if a.storage == "f32" else 8
+    esz = {0: 4, 1: 8, 2: 2}[rbl._lib.STORAGE[a.storage]]
     ld = owner.info()["ld"]
     dbytes = a.n * ld * esz
     y0 = owner.labels() if a.labels else None
