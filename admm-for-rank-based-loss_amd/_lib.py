@@ -12,7 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "librbl.so")
 
 RBL_OK, RBL_ERR_INVALID, RBL_ERR_NO_DEVICE, RBL_ERR_HIP, RBL_ERR_STATE, RBL_ERR_NOMEM = 0, -1, -2, -3, -4, -5
-LOSS = {"binary_cross_entropy": 0, "hinge": 1}
+LOSS = {"binary_cross_entropy": 0, "hinge": 1, "squared_hinge": 2}
 WEIGHT = {"erm": 0, "extremile": 1, "superquantile": 2, "esrm": 3, "aorr": 4, "aorr_dc": 5, "ehrm": 6}
 WSTEP_L1, WSTEP_L2, WSTEP_SMOOTH_L1 = 1, 2, 3
 STORAGE = {"f32": 0, "float32": 0, "f64": 1, "float64": 1, "fp16": 2, "float16": 2}

@@ -12,7 +12,7 @@ except ImportError:  # package directory itself on sys.path (drop-in `src.optim`
     import _lib
 
 _FAMILIES = "['erm','extremile','superquantile','esrm','aorr','aorr_dc','ehrm']"
-_LOSSES = "['binary_cross_entropy', 'multinomial_cross_entropy', 'hinge']"
+_LOSSES = "['binary_cross_entropy', 'multinomial_cross_entropy', 'hinge', 'squared_hinge']"
 
 
 def check_problem(weight_function, loss, B, args, need_prox=True):
@@ -27,14 +27,14 @@ def check_problem(weight_function, loss, B, args, need_prox=True):
         raise ValueError("args for framework is None!")
     if weight_function == "aorr_dc" and args[0] <= args[1]:
         raise ValueError("need args[0] > args[1]!")                              # objective.py:140-141
-    if loss not in ("binary_cross_entropy", "multinomial_cross_entropy", "hinge"):
+    if loss not in ("binary_cross_entropy", "multinomial_cross_entropy", "hinge", "squared_hinge"):
         raise ValueError(f"Unrecognized loss '{loss}'! Options: {_LOSSES}")      # objective.py:35-37
     if B is not None and loss != "binary_cross_entropy":
         raise ValueError("erhm only can be with the binary_cross_entropy.")      # objective.py:57-58
     if loss == "multinomial_cross_entropy" and need_prox:
         # the reference accepts it in the objective but its z-step has no prox for it
         # (src/util/individual_solver.py:124-125 is `pass`): unsupported there too
-        raise ValueError(f"Unrecognized loss '{loss}'! Options: ['binary_cross_entropy', 'hinge'] for the ADMM z-step")
+        raise ValueError(f"Unrecognized loss '{loss}'! Options: ['binary_cross_entropy', 'hinge', 'squared_hinge'] for the ADMM z-step")
 
 
 def _as_labels(y, n):

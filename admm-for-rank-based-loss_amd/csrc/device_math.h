@@ -165,20 +165,33 @@ __device__ inline double prox_hinge(double sigma, double rho, double m) {
     return (a >= -1.0) ? a : ((m <= -1.0) ? m : -1.0);
 }
 
+// Squared hinge l(v) = max(0, 1 + v)^2, l'(v) = 2 max(0, 1 + v): the root of sigma l'(z) + rho (z - m) in closed form.
+// m <= -1 lies on the flat side (z = m); above it the root of 2 sigma (1 + z) + rho (z - m) is > -1 as well, so the
+// two pieces never disagree.  Every operation is non-decreasing in m under rounding, so the computed prox is monotone
+// too.  sigma = 0 returns m itself (rho m / rho may be an ulp off).  A pooled block (mean sigma, mean m) is the same
+// formula: (rho M - 2 S) / (rho N + 2 S).
+__device__ inline double prox_sqhinge(double sigma, double rho, double m) {
+    return (m <= -1.0 || sigma == 0.0) ? m : (rho * m - 2.0 * sigma) / (rho + 2.0 * sigma);
+}
+
 template <int LOSS>
 __device__ inline double prox(double sigma, double rho, double m) {
-    return LOSS == 0 ? prox_bce(sigma, rho, m) : prox_hinge(sigma, rho, m);
+    return LOSS == 0 ? prox_bce(sigma, rho, m) : (LOSS == 1 ? prox_hinge(sigma, rho, m) : prox_sqhinge(sigma, rho, m));
 }
 
 // element prox with the first-order estimate as the starting point (level 0 of the PAV tree, the EHRM branch test)
 template <int LOSS>
 __device__ inline double prox_est(double sigma, double rho, double m) {
-    return LOSS == 0 ? prox_bce_est(sigma, rho, m, sigmoid1(m)) : prox_hinge(sigma, rho, m);
+    return LOSS == 0 ? prox_bce_est(sigma, rho, m, sigmoid1(m)) : (LOSS == 1 ? prox_hinge(sigma, rho, m) : prox_sqhinge(sigma, rho, m));
 }
 
 template <int LOSS>
 __device__ inline double sample_loss(double v) {
-    // objective.py:11-24 with D = -y*X: BCE-with-logits == softplus(v), hinge == max(1+v,0)
+    // objective.py:11-24 with D = -y*X: BCE-with-logits == softplus(v), hinge == max(1+v,0); squared hinge: its square
+    if (LOSS == 2) {
+        const double t = fmax(1.0 + v, 0.0);
+        return t * t;
+    }
     return LOSS == 0 ? softplus(v) : fmax(1.0 + v, 0.0);
 }
 

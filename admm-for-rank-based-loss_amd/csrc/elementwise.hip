@@ -275,6 +275,7 @@ __global__ __launch_bounds__(EW_THREADS) void k_loss_sum(long long n, const doub
 //   binary_cross_entropy: predict +1 iff sigmoid(x.w) >= threshold  <=>  x.w >= tau
 //   hinge: the reference maps BOTH outcomes of (x.w >= 0) to +1 (calculate_acc.py:13-15),
 //          i.e. its accuracy is the fraction of y == +1; mirrored as is.
+//   squared hinge (not a loss of the reference): predict +1 iff x.w >= 0; tau is not used.
 // rs (rbl_set_labels): v = D w carries the OWNER's label, the target is the handle's own y = r * y_owner
 template <int LOSS, bool RS>
 __global__ __launch_bounds__(EW_THREADS) void k_accuracy(long long n, const double* __restrict__ v,
@@ -291,6 +292,10 @@ __global__ __launch_bounds__(EW_THREADS) void k_accuracy(long long n, const doub
         if (LOSS == 0) {
             const double xw = -(double)yo * v[i];
             const int pred = (xw >= tau) ? 1 : -1;
+            ok = pred == y;
+        } else if (LOSS == 2) {
+            const double xw = -(double)yo * v[i];
+            const int pred = (xw >= 0.0) ? 1 : -1;
             ok = pred == y;
         } else {
             ok = y == 1;
@@ -417,25 +422,15 @@ __global__ void k_weights(WeightParams P, double* __restrict__ alphas, double* _
 
 int reduce_blocks() { return RED_BLOCKS; }
 
-#define LAUNCH_LOSS(KERN, loss, grid, block, stream, ...)                                        \
-    do {                                                                                         \
-        if ((loss) == RBL_LOSS_BCE)                                                              \
-            hipLaunchKernelGGL((KERN<0>), dim3(grid), dim3(block), 0, stream, __VA_ARGS__);      \
-        else                                                                                     \
-            hipLaunchKernelGGL((KERN<1>), dim3(grid), dim3(block), 0, stream, __VA_ARGS__);      \
-    } while (0)
+// (an unknown loss id returns RBL_ERR_INVALID from the calling launcher: RBL_LOSS_SWITCH)
+#define LAUNCH_LOSS(KERN, loss, grid, block, stream, ...) \
+    RBL_LOSS_SWITCH(loss, L_, hipLaunchKernelGGL((KERN<L_>), dim3(grid), dim3(block), 0, stream, __VA_ARGS__))
 
 // the same for kernels that take the optional sign vector rs as their last argument (NULL: the instance without it)
-#define LAUNCH_LOSS_RS(KERN, loss, rs, grid, block, stream, ...)                                             \
-    do {                                                                                                     \
-        if ((loss) == RBL_LOSS_BCE) {                                                                        \
-            if (rs) hipLaunchKernelGGL((KERN<0, true>), dim3(grid), dim3(block), 0, stream, __VA_ARGS__, rs); \
-            else hipLaunchKernelGGL((KERN<0, false>), dim3(grid), dim3(block), 0, stream, __VA_ARGS__, rs);   \
-        } else {                                                                                             \
-            if (rs) hipLaunchKernelGGL((KERN<1, true>), dim3(grid), dim3(block), 0, stream, __VA_ARGS__, rs); \
-            else hipLaunchKernelGGL((KERN<1, false>), dim3(grid), dim3(block), 0, stream, __VA_ARGS__, rs);   \
-        }                                                                                                    \
-    } while (0)
+#define LAUNCH_LOSS_RS(KERN, loss, rs, grid, block, stream, ...)                                                     \
+    RBL_LOSS_SWITCH(loss, L_,                                                                                        \
+                    if (rs) hipLaunchKernelGGL((KERN<L_, true>), dim3(grid), dim3(block), 0, stream, __VA_ARGS__, rs); \
+                    else hipLaunchKernelGGL((KERN<L_, false>), dim3(grid), dim3(block), 0, stream, __VA_ARGS__, rs))
 #define LAUNCH_RS(KERN, rs, grid, block, stream, ...)                                                    \
     do {                                                                                                 \
         if (rs) hipLaunchKernelGGL((KERN<true>), dim3(grid), dim3(block), 0, stream, __VA_ARGS__, rs);   \

@@ -146,6 +146,7 @@ __device__ inline double block_value(double ssig, double sm, double cnt, double 
     // expansion around the mean of m (device_math.h: prox_bce_est - 2-3 exponentials per block) instead of cold from
     // x = m (6-8, with IEEE divisions, until the iterate repeats): same root to rounding.  With rank weights that pool
     // everywhere (EHRM's CPT weights) these solves, not level 0, are what k_pav_bottom / k_pav_upper spend their time on.
+    // Squared hinge: the same call is the closed form (rho M - 2 S) / (rho N + 2 S) (M / N where M / N <= -1).
     return rbl::prox_est<LOSS>(ssig / cnt, rho, sm / cnt);
 }
 
@@ -167,7 +168,7 @@ __device__ inline double psi_sign(const Acc& ac, double rho, long long s, long l
     if (e < s) return 0.0;
     const double A = ac.sum_a(s, e + 1), M = ac.sum_m(s, e + 1), cnt = (double)(e + 1 - s);
     if (LOSS == 0) return A * rbl::sigmoid1(t) + rho * (cnt * t - M);
-    return t - block_value<1>(A, M, cnt, rho);
+    return t - block_value<LOSS>(A, M, cnt, rho);   // closed-form block values (hinge, squared hinge): Psi is increasing
 }
 
 template <typename Acc>
@@ -1107,7 +1108,7 @@ template <int LOSS>
 __device__ inline double zd_psi(double cnt, double A, double M, double rho, double t) {
     if (!(cnt > 0.0)) return 0.0;
     if (LOSS == 0) return A * rbl::sigmoid1(t) + rho * (cnt * t - M);
-    return t - block_value<1>(A, M, cnt, rho);
+    return t - block_value<LOSS>(A, M, cnt, rho);
 }
 
 // narrow [lo, hi) with the summed (count, sum sigma, sum m) of the previous round's candidates
@@ -1398,12 +1399,10 @@ int launch_pav_tree(int loss, int64_t n, double rho, const double* ms, const dou
         hipLaunchKernelGGL((k_pav_bottom<0, false>), dim3(tiles), dim3(PV_THREADS), 0, s, ms, sa, sb, branch, rho, (long long)n, u,
                            merge_counter, (const double*)nullptr, (const double*)nullptr, ex->spec, 0.0, 0,
                            (double*)nullptr);
-    } else if (loss == RBL_LOSS_BCE) {
-        hipLaunchKernelGGL((k_pav_bottom<0, false>), dim3(tiles), dim3(PV_THREADS), 0, s, ms, sa, sb, branch, rho, (long long)n, u,
-                           merge_counter, u0a, u0b, -1, 0.0, 0, (double*)nullptr);
     } else {
-        hipLaunchKernelGGL((k_pav_bottom<1, false>), dim3(tiles), dim3(PV_THREADS), 0, s, ms, sa, sb, branch, rho, (long long)n, u,
-                           merge_counter, u0a, u0b, -1, 0.0, 0, (double*)nullptr);
+        RBL_LOSS_SWITCH(loss, L_,
+                        hipLaunchKernelGGL((k_pav_bottom<L_, false>), dim3(tiles), dim3(PV_THREADS), 0, s, ms, sa, sb, branch, rho,
+                                           (long long)n, u, merge_counter, u0a, u0b, -1, 0.0, 0, (double*)nullptr));
     }
     // upper levels: one WAVE per seam (64-ary inner searches)
     SeamRec* hint_base = recs + pav_level_recs(n);
@@ -1422,10 +1421,8 @@ int launch_pav_tree(int loss, int64_t n, double rho, const double* ms, const dou
         long long want = ((n + 2LL * PB_TILE - 1) / (2LL * PB_TILE) + 3) / 4;    // one wave per seam of the lowest level
         int grid = ex->num_cu > 0 ? ex->num_cu : 64;
         if (want < grid) grid = (int)(want < 1 ? 1 : want);
-        if (loss == RBL_LOSS_BCE)
-            hipLaunchKernelGGL(k_pav_upper<0>, dim3(grid), dim3(PV_THREADS), 0, s, u, (long long)n, pa, pb, pm, branch, rho, A);
-        else
-            hipLaunchKernelGGL(k_pav_upper<1>, dim3(grid), dim3(PV_THREADS), 0, s, u, (long long)n, pa, pb, pm, branch, rho, A);
+        RBL_LOSS_SWITCH(loss, L_,
+                        hipLaunchKernelGGL(k_pav_upper<L_>, dim3(grid), dim3(PV_THREADS), 0, s, u, (long long)n, pa, pb, pm, branch, rho, A));
         RBL_HIP(hipGetLastError());
         return RBL_OK;
     }
@@ -1436,12 +1433,9 @@ int launch_pav_tree(int loss, int64_t n, double rho, const double* ms, const dou
         SeamRec* hints = hint_base;
         hint_base += nseams;
         const unsigned grid = pv_grid(nseams * 64, PV_THREADS, 1LL << 30);
-        if (loss == RBL_LOSS_BCE)
-            hipLaunchKernelGGL(k_pav_seam_wave<0>, dim3(grid), dim3(PV_THREADS), 0, s, u, (long long)n, half, pa, pb,
-                               pm, branch, rho, recs, nseams, merge_counter, hints);
-        else
-            hipLaunchKernelGGL(k_pav_seam_wave<1>, dim3(grid), dim3(PV_THREADS), 0, s, u, (long long)n, half, pa, pb,
-                               pm, branch, rho, recs, nseams, merge_counter, hints);
+        RBL_LOSS_SWITCH(loss, L_,
+                        hipLaunchKernelGGL(k_pav_seam_wave<L_>, dim3(grid), dim3(PV_THREADS), 0, s, u, (long long)n, half, pa, pb,
+                                           pm, branch, rho, recs, nseams, merge_counter, hints));
         hipLaunchKernelGGL(k_pav_fill, dim3((unsigned)((n + PF_CHUNK - 1) / PF_CHUNK)), dim3(256), 0, s, u, (long long)n, level,
                            recs);
     }
@@ -1492,10 +1486,8 @@ int launch_zd_seam_setup(int rank, int world, int level, const double* bounds_al
 }
 int launch_zd_update_propose(int loss, ZdSeam* st, const double* u, int K, int world, const double* cand_prev,
                              const double* part_prev, double rho, double* cand_out, hipStream_t s) {
-    if (loss == RBL_LOSS_BCE)
-        hipLaunchKernelGGL(k_zd_update_propose<0>, dim3(1), dim3(256), 0, s, st, u, K, world, cand_prev, part_prev, rho, cand_out);
-    else
-        hipLaunchKernelGGL(k_zd_update_propose<1>, dim3(1), dim3(256), 0, s, st, u, K, world, cand_prev, part_prev, rho, cand_out);
+    RBL_LOSS_SWITCH(loss, L_,
+                    hipLaunchKernelGGL(k_zd_update_propose<L_>, dim3(1), dim3(256), 0, s, st, u, K, world, cand_prev, part_prev, rho, cand_out));
     RBL_HIP(hipGetLastError());
     return RBL_OK;
 }
@@ -1513,8 +1505,7 @@ int launch_zd_pooled(const ZdSeam* st, Prefix pa, Prefix pb, Prefix pm, const in
     return RBL_OK;
 }
 int launch_zd_fill(int loss, ZdSeam* st, const double* sums_total, double rho, double* u, int64_t n, hipStream_t s) {
-    if (loss == RBL_LOSS_BCE) hipLaunchKernelGGL(k_zd_fill_value<0>, dim3(1), dim3(64), 0, s, st, sums_total, rho);
-    else hipLaunchKernelGGL(k_zd_fill_value<1>, dim3(1), dim3(64), 0, s, st, sums_total, rho);
+    RBL_LOSS_SWITCH(loss, L_, hipLaunchKernelGGL(k_zd_fill_value<L_>, dim3(1), dim3(64), 0, s, st, sums_total, rho));
     hipLaunchKernelGGL(k_zd_fill_range, dim3(pv_grid(n > 0 ? n : 1, 256, 4096)), dim3(256), 0, s, st, u);
     RBL_HIP(hipGetLastError());
     return RBL_OK;

@@ -30,6 +30,36 @@ void rbl_note_host_sync();
         if (r_ != RBL_OK) return r_; \
     } while (0)
 
+// Launchers that pick a kernel instance by the loss id: STMT is compiled once per loss with the constant L_ = the id;
+// any other id is an error of the caller (rbl_create checks the configuration, the rbl_k_* entry points their argument).
+#define RBL_LOSS_SWITCH(loss, L_, ...)                                \
+    do {                                                              \
+        switch (loss) {                                               \
+            case RBL_LOSS_BCE: {                                      \
+                constexpr int L_ = RBL_LOSS_BCE;                      \
+                __VA_ARGS__;                                          \
+            } break;                                                  \
+            case RBL_LOSS_HINGE: {                                    \
+                constexpr int L_ = RBL_LOSS_HINGE;                    \
+                __VA_ARGS__;                                          \
+            } break;                                                  \
+            case RBL_LOSS_SQHINGE: {                                  \
+                constexpr int L_ = RBL_LOSS_SQHINGE;                  \
+                __VA_ARGS__;                                          \
+            } break;                                                  \
+            default:                                                  \
+                rbl_set_error("unknown loss id %d", (int)(loss));     \
+                return RBL_ERR_INVALID;                               \
+        }                                                             \
+    } while (0)
+
+// RBL_OK for an id RBL_LOSS_SWITCH dispatches on, else RBL_ERR_INVALID with the message set: the one list of losses that
+// rbl_create's check of the configuration and the rbl_k_* entry points share with the launchers
+inline int rbl_check_loss(int loss) {
+    RBL_LOSS_SWITCH(loss, L_, return (void)L_, RBL_OK);
+    return RBL_OK;
+}
+
 // Owner of device (hipMalloc) and pinned host (hipHostMalloc) buffers: its destructor frees every buffer
 // allocated through it.  One per solver / baseline handle, or a local one for scoped temporaries.
 class DevArena {

@@ -198,7 +198,8 @@ __global__ __launch_bounds__(SE_THREADS, OCC) void k_sweep_erm(
             s_prim += res * res;                                   // algorithms.py:135
             const double lr = l / rho_next;
             const double m = myv - lr;                             // algorithms.py:89 (next iteration)
-            const double zn = VONLY ? m : ((LOSS == 0) ? rbl::prox_bce_warm(sigma0, rho_next, m, zo) : rbl::prox_hinge(sigma0, rho_next, m));
+            // (squared hinge: the closed form, no warm start)
+            const double zn = VONLY ? m : ((LOSS == 0) ? rbl::prox_bce_warm(sigma0, rho_next, m, zo) : rbl::prox<LOSS>(sigma0, rho_next, m));
             s_zz += zn * zn;
             l_out = l;
             v_out = myv;
@@ -410,7 +411,7 @@ __global__ __launch_bounds__(SEW_THREADS, 1) void k_sweep_erm_wide(
             rw_prim[tid] += res * res;                             // algorithms.py:135
             const double lr = l / rho_next;
             const double m = myv - lr;                             // algorithms.py:89 (next iteration)
-            const double zn = (LOSS == 0) ? rbl::prox_bce_warm(sigma0, rho_next, m, zo) : rbl::prox_hinge(sigma0, rho_next, m);
+            const double zn = (LOSS == 0) ? rbl::prox_bce_warm(sigma0, rho_next, m, zo) : rbl::prox<LOSS>(sigma0, rho_next, m);
             rw_zz[tid] += zn * zn;
             rw_l[tid] = l;
             rw_v[tid] = myv;
@@ -704,20 +705,15 @@ int launch_sweep_erm(int storage, int loss, const void* D, int64_t n, int64_t ld
     int nrows = grid;   // slab rows / partial triples produced = blocks launched
     double* const v_for_loss = v;
     if (!want_obj) v = nullptr;   // 8 of the 24 B/row of row-wise stores: only the loss sum reads v after the pass
-    int rc;
-    if (storage == RBL_STORE_F16) {
-        rc = (loss == RBL_LOSS_BCE)
-                 ? launch_T<rbl_half, 0>((const rbl_half*)D, n, ld, w, z_old, lam, v, z_new, sigma0, rho, pred_dev, slab, partials, grid, num_cu, &nrows, s)
-                 : launch_T<rbl_half, 1>((const rbl_half*)D, n, ld, w, z_old, lam, v, z_new, sigma0, rho, pred_dev, slab, partials, grid, num_cu, &nrows, s);
-    } else if (storage == RBL_STORE_F32) {
-        rc = (loss == RBL_LOSS_BCE)
-                 ? launch_T<float, 0>((const float*)D, n, ld, w, z_old, lam, v, z_new, sigma0, rho, pred_dev, slab, partials, grid, num_cu, &nrows, s)
-                 : launch_T<float, 1>((const float*)D, n, ld, w, z_old, lam, v, z_new, sigma0, rho, pred_dev, slab, partials, grid, num_cu, &nrows, s);
-    } else {
-        rc = (loss == RBL_LOSS_BCE)
-                 ? launch_T<double, 0>((const double*)D, n, ld, w, z_old, lam, v, z_new, sigma0, rho, pred_dev, slab, partials, grid, num_cu, &nrows, s)
-                 : launch_T<double, 1>((const double*)D, n, ld, w, z_old, lam, v, z_new, sigma0, rho, pred_dev, slab, partials, grid, num_cu, &nrows, s);
-    }
+    int rc = RBL_OK;
+    // the fused instances exist per loss and storage type, with the same (P, R, S, WL, OCC) / (PT, R, S) tables (launch_T)
+    RBL_LOSS_SWITCH(loss, L_,
+                    if (storage == RBL_STORE_F16)
+                        rc = launch_T<rbl_half, L_>((const rbl_half*)D, n, ld, w, z_old, lam, v, z_new, sigma0, rho, pred_dev, slab, partials, grid, num_cu, &nrows, s);
+                    else if (storage == RBL_STORE_F32)
+                        rc = launch_T<float, L_>((const float*)D, n, ld, w, z_old, lam, v, z_new, sigma0, rho, pred_dev, slab, partials, grid, num_cu, &nrows, s);
+                    else
+                        rc = launch_T<double, L_>((const double*)D, n, ld, w, z_old, lam, v, z_new, sigma0, rho, pred_dev, slab, partials, grid, num_cu, &nrows, s));
     RBL_TRY(rc);
     if (main_done) RBL_HIP(hipEventRecord(main_done, s));
     double* part = slab + (size_t)grid * ld;   // CR_SLICES rows behind the grid rows of the slab

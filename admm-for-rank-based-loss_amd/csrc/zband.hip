@@ -130,14 +130,19 @@ __global__ __launch_bounds__(ZB_HTHREADS) void k_zb_hist(const u64* __restrict__
 }
 
 // u_i > x  <=>  m_i > zb_theta_gt(x);   u_i < x  <=>  m_i < zb_theta_lt(x)     (u_i = prox_{s l / rho}(m_i))
+// Squared hinge: l'(x) = 2 max(0, 1 + x) is continuous, so the two one-sided thresholds coincide (as for BCE) and none
+// of the hinge's special cases below (LOSS == 1: the kink as a forced candidate, psi jumping across 0 between adjacent
+// doubles) applies: the prox has no plateau, tied block values do not occur.
 template <int LOSS>
 __device__ inline double zb_theta_gt(double s_over_rho, double x) {
     if (LOSS == 0) return x + s_over_rho * rbl::sigmoid1(x);
+    if (LOSS == 2) return x + s_over_rho * (2.0 * fmax(1.0 + x, 0.0));
     return x >= -1.0 ? x + s_over_rho : x;
 }
 template <int LOSS>
 __device__ inline double zb_theta_lt(double s_over_rho, double x) {
     if (LOSS == 0) return x + s_over_rho * rbl::sigmoid1(x);
+    if (LOSS == 2) return x + s_over_rho * (2.0 * fmax(1.0 + x, 0.0));
     return x > -1.0 ? x + s_over_rho : x;
 }
 template <int LOSS>
@@ -148,7 +153,7 @@ template <int LOSS>
 __device__ inline double zb_psi(double A, double M, double cnt, double rho, double x) {
     if (!(cnt > 0.0)) return 0.0;
     if (LOSS == 0) return A * rbl::sigmoid1(x) + rho * (cnt * x - M);
-    return x - zb_block_value<1>(A, M, cnt, rho);
+    return x - zb_block_value<LOSS>(A, M, cnt, rho);   // closed-form block values (hinge, squared hinge)
 }
 
 // candidates a = x_0 < ... < x_{C-1} = b.  Hinge: the prox has a plateau at the kink (u = -1 for a whole range of m), so a
@@ -1092,51 +1097,30 @@ int launch_zband(int loss, const ZbConfig& cfg, int64_t n, double rho, const u64
     double* glist = partials + 1024 * 4 * ZB_C;
     for (int pass = 0; pass < 6; ++pass) {
         hipLaunchKernelGGL(k_zb_hist, dim3(sb), dim3(ZB_HTHREADS), 0, s, keys, (long long)n, (const ZbState*)st, hist, pass);
-        if (loss == RBL_LOSS_BCE)
-            hipLaunchKernelGGL(k_zb_scan<0>, dim3(1), dim3(1024), 0, s, st, cfg, hist, pass, rho, 1);
-        else
-            hipLaunchKernelGGL(k_zb_scan<1>, dim3(1), dim3(1024), 0, s, st, cfg, hist, pass, rho, 1);
+        RBL_LOSS_SWITCH(loss, L_, hipLaunchKernelGGL(k_zb_scan<L_>, dim3(1), dim3(1024), 0, s, st, cfg, hist, pass, rho, 1));
     }
     for (int k = 0; k < cfg.nclusters; ++k) {
         if (!cfg.cl_root[k]) continue;
         for (int r = 0; r < ZB_ROOT_PASSES; ++r) {
             const int last = r == ZB_ROOT_PASSES - 1;
-            if (loss == RBL_LOSS_BCE) {
-                hipLaunchKernelGGL(k_zb_eval<0>, dim3(hb), dim3(ZB_THREADS), 0, s, keys, (long long)n, (const ZbState*)st, cfg, k,
-                                   rho, partials);
-                hipLaunchKernelGGL(k_zb_refine<0>, dim3(1), dim3(1024), 0, s, st, cfg, k, rho, (const double*)partials, hb, last,
-                                   (double*)nullptr, (const double*)nullptr);
-            } else {
-                hipLaunchKernelGGL(k_zb_eval<1>, dim3(hb), dim3(ZB_THREADS), 0, s, keys, (long long)n, (const ZbState*)st, cfg, k,
-                                   rho, partials);
-                hipLaunchKernelGGL(k_zb_refine<1>, dim3(1), dim3(1024), 0, s, st, cfg, k, rho, (const double*)partials, hb, last,
-                                   (double*)nullptr, (const double*)nullptr);
-            }
+            RBL_LOSS_SWITCH(loss, L_,
+                            hipLaunchKernelGGL(k_zb_eval<L_>, dim3(hb), dim3(ZB_THREADS), 0, s, keys, (long long)n, (const ZbState*)st,
+                                               cfg, k, rho, partials);
+                            hipLaunchKernelGGL(k_zb_refine<L_>, dim3(1), dim3(1024), 0, s, st, cfg, k, rho, (const double*)partials, hb,
+                                               last, (double*)nullptr, (const double*)nullptr));
         }
-        if (loss == RBL_LOSS_BCE) {
-            hipLaunchKernelGGL(k_zb_gather<0>, dim3(hb), dim3(ZB_THREADS), 0, s, keys, (long long)n, st, cfg, k, rho, glist);
-            hipLaunchKernelGGL(k_zb_finish<0>, dim3(1), dim3(1024), 0, s, st, cfg, k, rho, (const double*)glist);
-        } else {
-            hipLaunchKernelGGL(k_zb_gather<1>, dim3(hb), dim3(ZB_THREADS), 0, s, keys, (long long)n, st, cfg, k, rho, glist);
-            hipLaunchKernelGGL(k_zb_finish<1>, dim3(1), dim3(1024), 0, s, st, cfg, k, rho, (const double*)glist);
-        }
+        RBL_LOSS_SWITCH(loss, L_,
+                        hipLaunchKernelGGL(k_zb_gather<L_>, dim3(hb), dim3(ZB_THREADS), 0, s, keys, (long long)n, st, cfg, k, rho, glist);
+                        hipLaunchKernelGGL(k_zb_finish<L_>, dim3(1), dim3(1024), 0, s, st, cfg, k, rho, (const double*)glist));
     }
     const int64_t ab = (n + ZB_THREADS * 8 - 1) / (ZB_THREADS * 8);
     const unsigned ag = (unsigned)(ab < 1 ? 1 : (ab > 2048 ? 2048 : ab));
     const signed char* no_rs = nullptr;
-    if (rs) {
-        if (loss == RBL_LOSS_BCE)
-            hipLaunchKernelGGL((k_zb_apply<0, true>), dim3(ag), dim3(ZB_THREADS), 0, s, m, (long long)n, (const ZbState*)st, cfg, rho, z,
-                               lam, c, pin, seq, counters, rs);
-        else
-            hipLaunchKernelGGL((k_zb_apply<1, true>), dim3(ag), dim3(ZB_THREADS), 0, s, m, (long long)n, (const ZbState*)st, cfg, rho, z,
-                               lam, c, pin, seq, counters, rs);
-    } else if (loss == RBL_LOSS_BCE)
-        hipLaunchKernelGGL((k_zb_apply<0, false>), dim3(ag), dim3(ZB_THREADS), 0, s, m, (long long)n, (const ZbState*)st, cfg, rho, z,
-                           lam, c, pin, seq, counters, no_rs);
-    else
-        hipLaunchKernelGGL((k_zb_apply<1, false>), dim3(ag), dim3(ZB_THREADS), 0, s, m, (long long)n, (const ZbState*)st, cfg, rho, z,
-                           lam, c, pin, seq, counters, no_rs);
+    RBL_LOSS_SWITCH(loss, L_,
+                    if (rs) hipLaunchKernelGGL((k_zb_apply<L_, true>), dim3(ag), dim3(ZB_THREADS), 0, s, m, (long long)n,
+                                               (const ZbState*)st, cfg, rho, z, lam, c, pin, seq, counters, rs);
+                    else hipLaunchKernelGGL((k_zb_apply<L_, false>), dim3(ag), dim3(ZB_THREADS), 0, s, m, (long long)n,
+                                            (const ZbState*)st, cfg, rho, z, lam, c, pin, seq, counters, no_rs));
     RBL_HIP(hipGetLastError());
     return RBL_OK;
 }
@@ -1150,13 +1134,10 @@ int launch_zband_risk(int loss, const ZbConfig& cfg, int64_t n, const u64* keys,
         hipLaunchKernelGGL(k_zb_hist, dim3(sb), dim3(ZB_HTHREADS), 0, s, keys, (long long)n, (const ZbState*)st, hist, pass);
         hipLaunchKernelGGL(k_zb_scan<0>, dim3(1), dim3(1024), 0, s, st, cfg, hist, pass, 1.0, 0);
     }
-    if (loss == RBL_LOSS_BCE) {
-        hipLaunchKernelGGL(k_zb_risk<0>, dim3(hb), dim3(ZB_THREADS), 0, s, keys, (long long)n, (const ZbState*)st, cfg, partials);
-        hipLaunchKernelGGL(k_zb_risk_finish<0>, dim3(1), dim3(256), 0, s, (const ZbState*)st, cfg, (const double*)partials, hb, out_dev);
-    } else {
-        hipLaunchKernelGGL(k_zb_risk<1>, dim3(hb), dim3(ZB_THREADS), 0, s, keys, (long long)n, (const ZbState*)st, cfg, partials);
-        hipLaunchKernelGGL(k_zb_risk_finish<1>, dim3(1), dim3(256), 0, s, (const ZbState*)st, cfg, (const double*)partials, hb, out_dev);
-    }
+    RBL_LOSS_SWITCH(loss, L_,
+                    hipLaunchKernelGGL(k_zb_risk<L_>, dim3(hb), dim3(ZB_THREADS), 0, s, keys, (long long)n, (const ZbState*)st, cfg, partials);
+                    hipLaunchKernelGGL(k_zb_risk_finish<L_>, dim3(1), dim3(256), 0, s, (const ZbState*)st, cfg, (const double*)partials, hb,
+                                       out_dev));
     RBL_HIP(hipGetLastError());
     return RBL_OK;
 }
@@ -1173,10 +1154,7 @@ int launch_zbd_hist(int64_t n, const u64* keys, ZbState* st, u32* hist, int pass
     return RBL_OK;
 }
 int launch_zbd_scan(int loss, const ZbConfig& cfg, ZbState* st, u32* hist, int pass, double rho, hipStream_t s) {
-    if (loss == RBL_LOSS_BCE)
-        hipLaunchKernelGGL(k_zb_scan<0>, dim3(1), dim3(1024), 0, s, st, cfg, hist, pass, rho, 1);
-    else
-        hipLaunchKernelGGL(k_zb_scan<1>, dim3(1), dim3(1024), 0, s, st, cfg, hist, pass, rho, 1);
+    RBL_LOSS_SWITCH(loss, L_, hipLaunchKernelGGL(k_zb_scan<L_>, dim3(1), dim3(1024), 0, s, st, cfg, hist, pass, rho, 1));
     RBL_HIP(hipGetLastError());
     return RBL_OK;
 }
@@ -1184,26 +1162,19 @@ int launch_zbd_scan(int loss, const ZbConfig& cfg, ZbState* st, u32* hist, int p
 int launch_zbd_eval(int loss, const ZbConfig& cfg, int64_t n, const u64* keys, ZbState* st, int k, double rho, double* partials,
                     double* tot, hipStream_t s) {
     const int hb = zb_eval_blocks(n);
-    if (loss == RBL_LOSS_BCE) {
-        hipLaunchKernelGGL(k_zb_eval<0>, dim3(hb), dim3(ZB_THREADS), 0, s, keys, (long long)n, (const ZbState*)st, cfg, k, rho, partials);
-        hipLaunchKernelGGL(k_zb_refine<0>, dim3(1), dim3(1024), 0, s, st, cfg, k, rho, (const double*)partials, hb, 0, tot,
-                           (const double*)nullptr);
-    } else {
-        hipLaunchKernelGGL(k_zb_eval<1>, dim3(hb), dim3(ZB_THREADS), 0, s, keys, (long long)n, (const ZbState*)st, cfg, k, rho, partials);
-        hipLaunchKernelGGL(k_zb_refine<1>, dim3(1), dim3(1024), 0, s, st, cfg, k, rho, (const double*)partials, hb, 0, tot,
-                           (const double*)nullptr);
-    }
+    RBL_LOSS_SWITCH(loss, L_,
+                    hipLaunchKernelGGL(k_zb_eval<L_>, dim3(hb), dim3(ZB_THREADS), 0, s, keys, (long long)n, (const ZbState*)st, cfg, k, rho,
+                                       partials);
+                    hipLaunchKernelGGL(k_zb_refine<L_>, dim3(1), dim3(1024), 0, s, st, cfg, k, rho, (const double*)partials, hb, 0, tot,
+                                       (const double*)nullptr));
     RBL_HIP(hipGetLastError());
     return RBL_OK;
 }
 int launch_zbd_decide(int loss, const ZbConfig& cfg, ZbState* st, int k, double rho, const double* tot, int last, hipStream_t s,
                       int* pin_settled, int dseq) {
-    if (loss == RBL_LOSS_BCE)
-        hipLaunchKernelGGL(k_zb_refine<0>, dim3(1), dim3(1024), 0, s, st, cfg, k, rho, (const double*)nullptr, 0, last,
-                           (double*)nullptr, tot, pin_settled, dseq);
-    else
-        hipLaunchKernelGGL(k_zb_refine<1>, dim3(1), dim3(1024), 0, s, st, cfg, k, rho, (const double*)nullptr, 0, last,
-                           (double*)nullptr, tot, pin_settled, dseq);
+    RBL_LOSS_SWITCH(loss, L_,
+                    hipLaunchKernelGGL(k_zb_refine<L_>, dim3(1), dim3(1024), 0, s, st, cfg, k, rho, (const double*)nullptr, 0, last,
+                                       (double*)nullptr, tot, pin_settled, dseq));
     RBL_HIP(hipGetLastError());
     return RBL_OK;
 }
@@ -1211,10 +1182,8 @@ int launch_zbd_gather(int loss, const ZbConfig& cfg, int64_t n, const u64* keys,
                       double* pack, hipStream_t s) {
     double* glist = partials + 1024 * 4 * ZB_C;
     const int hb = zb_eval_blocks(n);
-    if (loss == RBL_LOSS_BCE)
-        hipLaunchKernelGGL(k_zb_gather<0>, dim3(hb), dim3(ZB_THREADS), 0, s, keys, (long long)n, st, cfg, k, rho, glist);
-    else
-        hipLaunchKernelGGL(k_zb_gather<1>, dim3(hb), dim3(ZB_THREADS), 0, s, keys, (long long)n, st, cfg, k, rho, glist);
+    RBL_LOSS_SWITCH(loss, L_,
+                    hipLaunchKernelGGL(k_zb_gather<L_>, dim3(hb), dim3(ZB_THREADS), 0, s, keys, (long long)n, st, cfg, k, rho, glist));
     hipLaunchKernelGGL(k_zb_pack, dim3(8), dim3(256), 0, s, (const ZbState*)st, k, (const double*)glist, pack);
     RBL_HIP(hipGetLastError());
     return RBL_OK;
@@ -1223,10 +1192,7 @@ int launch_zbd_finish(int loss, const ZbConfig& cfg, ZbState* st, int k, double 
                       int world, hipStream_t s) {
     double* glist = partials + 1024 * 4 * ZB_C;
     hipLaunchKernelGGL(k_zb_union, dim3(1), dim3(1024), 0, s, st, k, packs_all, world, glist);
-    if (loss == RBL_LOSS_BCE)
-        hipLaunchKernelGGL(k_zb_finish<0>, dim3(1), dim3(1024), 0, s, st, cfg, k, rho, (const double*)glist);
-    else
-        hipLaunchKernelGGL(k_zb_finish<1>, dim3(1), dim3(1024), 0, s, st, cfg, k, rho, (const double*)glist);
+    RBL_LOSS_SWITCH(loss, L_, hipLaunchKernelGGL(k_zb_finish<L_>, dim3(1), dim3(1024), 0, s, st, cfg, k, rho, (const double*)glist));
     RBL_HIP(hipGetLastError());
     return RBL_OK;
 }
@@ -1235,12 +1201,9 @@ int launch_zbd_apply(int loss, const ZbConfig& cfg, int64_t n, double rho, const
     const int64_t ab = (n + ZB_THREADS * 8 - 1) / (ZB_THREADS * 8);
     const unsigned ag = (unsigned)(ab < 1 ? 1 : (ab > 2048 ? 2048 : ab));
     const signed char* no_rs = nullptr;   // (row-sharded handles carry no labels of their own)
-    if (loss == RBL_LOSS_BCE)
-        hipLaunchKernelGGL((k_zb_apply<0, false>), dim3(ag), dim3(ZB_THREADS), 0, s, m, (long long)n, (const ZbState*)st, cfg, rho, z,
-                           lam, c, pin, seq, counters, no_rs);
-    else
-        hipLaunchKernelGGL((k_zb_apply<1, false>), dim3(ag), dim3(ZB_THREADS), 0, s, m, (long long)n, (const ZbState*)st, cfg, rho, z,
-                           lam, c, pin, seq, counters, no_rs);
+    RBL_LOSS_SWITCH(loss, L_,
+                    hipLaunchKernelGGL((k_zb_apply<L_, false>), dim3(ag), dim3(ZB_THREADS), 0, s, m, (long long)n, (const ZbState*)st, cfg,
+                                       rho, z, lam, c, pin, seq, counters, no_rs));
     RBL_HIP(hipGetLastError());
     return RBL_OK;
 }

@@ -12,9 +12,10 @@ except ImportError:      # package directory on sys.path: imported as ``src.util
 def calculate_accuracy(w, X_test, y_test, threshold=0.5, loss='binary_cross_entropy'):
     """Fraction of rows with prediction == label (reference calculate_acc.py:3-19).
     binary_cross_entropy: predict +1 iff sigmoid(x.w) >= threshold.  hinge: the reference sets
-    every prediction to +1 (calculate_acc.py:13-15); mirrored as is."""
-    if loss not in ('binary_cross_entropy', 'hinge'):
-        raise ValueError(f"loss '{loss}' is not supported! Options: ['binary_cross_entropy','hinge']")
+    every prediction to +1 (calculate_acc.py:13-15); mirrored as is.  squared_hinge (not a loss of the reference):
+    predict +1 iff x.w >= 0, ``threshold`` is ignored."""
+    if loss not in ('binary_cross_entropy', 'hinge', 'squared_hinge'):
+        raise ValueError(f"loss '{loss}' is not supported! Options: ['binary_cross_entropy','hinge','squared_hinge']")
     X = _solver._as_matrix(X_test)
     s = _solver.Solver(X.shape[0], X.shape[1], "erm", loss, objective_only=True)
     try:

@@ -36,9 +36,11 @@ enum {
     RBL_ERR_NOMEM = -5
 };
 
-/* loss: src/optim/objective.py:27-37 (get_loss); the ADMM z-step supports these two
- * (src/util/individual_solver.py:112-123) */
-enum { RBL_LOSS_BCE = 0, RBL_LOSS_HINGE = 1 };
+/* loss: src/optim/objective.py:27-37 (get_loss); the reference's z-step has a prox for the first two
+ * (src/util/individual_solver.py:112-123).  RBL_LOSS_SQHINGE, max(0, 1 - y x.w)^2, is this library's own: every prox and
+ * every pooled block is closed form.  The ADMM solver, the objective and the rbl_k_* entry points take all
+ * three; EHRM (has_B) is BCE only, and the baselines (rbl_bl_create) mirror the reference's competitors: first two only. */
+enum { RBL_LOSS_BCE = 0, RBL_LOSS_HINGE = 1, RBL_LOSS_SQHINGE = 2 };
 
 /* weight_function: src/optim/objective.py:166-187 (get_weights) */
 enum {
@@ -235,7 +237,8 @@ int  rbl_decide_multi(rbl_solver* data, int k, const double* W, int32_t* cls);
 int  rbl_objective(rbl_solver* h, const double* w, int include_reg, double* out);
 
 /* calculate_accuracy(w, X, y, threshold, loss) of src/util/calculate_acc.py:3-19 on this handle's
- * rows (hinge mirrors the reference's quirk: every prediction is +1) */
+ * rows.  BCE: predict +1 iff sigmoid(x.w) >= threshold.  Hinge mirrors the reference's quirk: every prediction is +1.
+ * Squared hinge (not in the reference, nothing to mirror): predict +1 iff x.w >= 0; threshold is ignored. */
 int  rbl_accuracy(rbl_solver* h, const double* w, double threshold, double* out);
 /* calculate_statistics(w, X, label, group, threshold) of src/util/fair_metric.py:3-41 on this
  * handle's rows: out6 = {SPD, DI, EOD, AOD, TI, FNRD}; group: n doubles (0 / 1) */
@@ -383,11 +386,11 @@ int  rbl_profile_kernels(rbl_solver* h, int enable);
 int  rbl_profile_sampling(rbl_solver* h, int every);
 
 /* ---- kernel-level entry points over host buffers (parity tests call these) -------- */
-/* element prox (src/util/individual_solver.py:112-123) */
+/* element prox (src/util/individual_solver.py:112-123; RBL_LOSS_SQHINGE: the closed form); loss: any RBL_LOSS_* */
 int  rbl_k_prox(int loss, int64_t n, const double* sigma, double rho, const double* m, double* out);
 /* stable ascending sort of float64 keys with index payload (algorithms.py:92-93) */
 int  rbl_k_sort(int64_t n, const double* keys, double* sorted_keys, uint32_t* perm);
-/* generalised PAV on sorted m (src/util/pav.py:93-178) */
+/* generalised PAV on sorted m (src/util/pav.py:93-178); loss: any RBL_LOSS_* */
 int  rbl_k_pav(int loss, int64_t n, const double* sigma, double rho, const double* m_sorted,
                double* out, int64_t* n_merges);
 /* EHRM z-step on sorted m (src/util/PAV_cpt.py:169-293): branch -1 = choose by the
