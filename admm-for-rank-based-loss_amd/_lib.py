@@ -98,6 +98,8 @@ SIGNATURES = {
     "rbl_destroy": (C.c_int, [_P]),
     "rbl_create_shared": (C.c_int, [C.POINTER(RblConfig), _P, C.POINTER(_P)]),
     "rbl_set_labels": (C.c_int, [_P, _P]),
+    "rbl_set_penalty": (C.c_int, [_P, _P, _P]),
+    "rbl_get_penalty": (C.c_int, [_P, _P, _P, C.POINTER(C.c_int)]),
     "rbl_decide_multi": (C.c_int, [_P, C.c_int, _P, _P]),
     "rbl_group_create": (C.c_int, [C.POINTER(_P), C.c_int, C.POINTER(_P)]),
     "rbl_group_destroy": (C.c_int, [_P]),
@@ -174,6 +176,8 @@ SIGNATURES = {
     "rbl_k_gram": (C.c_int, [C.c_int, C.c_int64, C.c_int64, _P, _P]),
     "rbl_k_wstep": (C.c_int, [C.c_int, C.c_int64, _P, _P, C.c_double, C.c_double, C.c_double, _P, C.c_double, _P,
                               C.POINTER(C.c_int)]),
+    "rbl_k_wstep_pen": (C.c_int, [C.c_int64, _P, _P, C.c_double, _P, _P, _P, C.c_double, _P, C.POINTER(C.c_int),
+                                  C.POINTER(C.c_int)]),
     "rbl_k_weights": (C.c_int, [C.c_int, C.c_int64, _P, C.c_int, _P, _P]),
     "rbl_bl_create": (C.c_int, [C.c_int64, C.c_int64, _P, _P, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_int,
                                 C.POINTER(_P)]),
@@ -359,6 +363,20 @@ def k_wstep(wstep, G, q, rho, reg, w0=None, smooth_t=1.0, tol=1e-13):
     check(load().rbl_k_wstep(int(wstep), d, ptr(G), ptr(q), float(rho), float(reg), float(smooth_t), ptr(w0),
                              float(tol), ptr(out), C.byref(it)))
     return out, it.value
+
+
+def k_wstep_pen(G, q, rho, l1=None, l2=None, w0=None, tol=1e-13):
+    """The w-step with per-coordinate penalties; returns (w, iterations, form)."""
+    G, q = f64(G), f64(q).reshape(-1)
+    d = q.size
+    l1 = None if l1 is None else f64(np.broadcast_to(np.asarray(l1, dtype=np.float64), (d,)))
+    l2 = None if l2 is None else f64(np.broadcast_to(np.asarray(l2, dtype=np.float64), (d,)))
+    w0 = f64(w0).reshape(-1) if w0 is not None else np.zeros(d)
+    out = np.empty(d)
+    it, form = C.c_int(0), C.c_int(0)
+    check(load().rbl_k_wstep_pen(d, ptr(G), ptr(q), float(rho), ptr(l1), ptr(l2), ptr(w0), float(tol), ptr(out),
+                                 C.byref(it), C.byref(form)))
+    return out, it.value, form.value
 
 
 def k_weights(weight_function, n, args=None):

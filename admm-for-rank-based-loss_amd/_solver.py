@@ -59,6 +59,60 @@ def as_pm1_labels(y, n, what="y"):
     return y
 
 
+def as_penalty(v, d, what):
+    """A penalty vector: a scalar or d values, finite and >= 0 -> float64 (d,); anything else is a ValueError naming
+    `what`.  Checked on the host, before any device call."""
+    a = np.asarray(v.detach().cpu().numpy() if hasattr(v, "detach") else v)
+    try:
+        a = np.asarray(a, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError(f"{what}: expected a number or {d} numbers") from None
+    if a.ndim == 0 or a.size == 1 and d != 1:
+        a = np.full(d, float(a.reshape(-1)[0]) if a.size else np.nan)
+    a = np.ascontiguousarray(a.reshape(-1))
+    if a.shape[0] != d:
+        raise ValueError(f"{what}: has {a.shape[0]} entries for {d} coordinates")
+    if not np.all(np.isfinite(a)):
+        bad = int(np.flatnonzero(~np.isfinite(a))[0])
+        raise ValueError(f"{what}: entries must be finite (entry {bad} is {a[bad]!r})")
+    if np.any(a < 0):
+        bad = int(np.flatnonzero(a < 0)[0])
+        raise ValueError(f"{what}: entries must be >= 0 (entry {bad} is {a[bad]!r})")
+    return a
+
+
+def resolve_penalty(d, l1_reg=None, l2_reg=None, l1_weights=None, l2_weights=None, fit_intercept=False):
+    """Per-coordinate penalties of a problem with d features (include/rbl.h: rbl_set_penalty).
+
+    None when none of l1_weights / l2_weights / fit_intercept is given: the scalar path, exactly as before.  Otherwise a
+    dict: ``l1`` / ``l2`` (d values each, d + 1 with the intercept's zeros appended), ``wstep`` (the lasso form if any
+    l1 > 0, else the ridge form) and ``reg`` (mean of the feature's l1 weights if any is positive, else of the l2
+    weights) - it only sets the reference's starting values, so l1_weights=a starts where l1_reg=a does.  Each norm takes
+    its weights if given, else its scalar; with no weights at all and both scalars given the reference's rule stays:
+    l1_reg is used."""
+    if l1_weights is None and l2_weights is None and not fit_intercept:
+        return None
+    if l1_weights is None and l2_weights is None and l1_reg is not None:
+        l2_reg = None                                  # algorithms.py:30, :57-60: l1_reg wins
+    l1 = as_penalty(l1_weights if l1_weights is not None else (0.0 if l1_reg is None else l1_reg), d,
+                    "l1_weights" if l1_weights is not None else "l1_reg")
+    l2 = as_penalty(l2_weights if l2_weights is not None else (0.0 if l2_reg is None else l2_reg), d,
+                    "l2_weights" if l2_weights is not None else "l2_reg")
+    if not (np.any(l1 > 0) or np.any(l2 > 0)):
+        raise ValueError("More arguments: l1_reg, l2_reg, l1_weights or l2_weights must hold a positive penalty")
+    any_l1 = bool(np.any(l1 > 0))
+    v = l1 if any_l1 else l2
+    reg = float(v[0]) if np.all(v == v[0]) else float(np.mean(v))     # (a constant vector: its value, not a rounded mean)
+    if fit_intercept:
+        l1, l2 = np.append(l1, 0.0), np.append(l2, 0.0)
+    return dict(l1=l1, l2=l2, wstep=_lib.WSTEP_L1 if any_l1 else _lib.WSTEP_L2, reg=reg)
+
+
+def add_intercept_column(X):
+    """[X | 1]: a host copy of X with a column of ones appended (fit_intercept=True)"""
+    return np.ascontiguousarray(np.hstack([X, np.ones((X.shape[0], 1))]))
+
+
 def _as_matrix(X):
     X = X.detach().cpu().numpy() if hasattr(X, "detach") else np.asarray(X)
     if X.ndim != 2:
@@ -151,6 +205,19 @@ class Solver:
         y = as_pm1_labels(y, self.n)
         _lib.check(self.lib.rbl_set_labels(self._h, _lib.ptr(y)))
 
+    def set_penalty(self, l1=None, l2=None):
+        """Per-coordinate penalties R(w) = 1/2 sum_j (l1_j |w_j| + l2_j w_j^2) (include/rbl.h: rbl_set_penalty): a
+        scalar or d values each, before the first iteration.  Shape, finiteness and sign are checked here first."""
+        l1 = None if l1 is None else as_penalty(l1, self.d, "l1_weights")
+        l2 = None if l2 is None else as_penalty(l2, self.d, "l2_weights")
+        _lib.check(self.lib.rbl_set_penalty(self._h, _lib.ptr(l1), _lib.ptr(l2)))
+
+    def get_penalty(self):
+        """(l1, l2) of set_penalty, or None when the handle runs on its scalar reg"""
+        l1, l2, flag = np.empty(self.d), np.empty(self.d), C.c_int(0)
+        _lib.check(self.lib.rbl_get_penalty(self._h, _lib.ptr(l1), _lib.ptr(l2), C.byref(flag)))
+        return (l1, l2) if flag.value else None
+
     def decide_multi(self, W):
         """argmax_j x_i . w_j over the rows of this handle's data (ties: lowest j); W: (k, d) -> int32 (n,)
         (include/rbl.h: rbl_decide_multi)"""
@@ -239,6 +306,15 @@ class Solver:
             raise ValueError(f"w has {w.size} entries, expected {self.d}")
         out = C.c_double(0)
         _lib.check(self.lib.rbl_objective(self._h, _lib.ptr(w), 0, C.byref(out)))
+        return out.value
+
+    def objective(self, w):
+        """risk(w) + the handle's regulariser (cfg.reg, or the vectors of set_penalty)"""
+        w = _lib.f64(w).reshape(-1)
+        if w.size != self.d:
+            raise ValueError(f"w has {w.size} entries, expected {self.d}")
+        out = C.c_double(0)
+        _lib.check(self.lib.rbl_objective(self._h, _lib.ptr(w), 1, C.byref(out)))
         return out.value
 
     def accuracy(self, w, threshold=0.5):

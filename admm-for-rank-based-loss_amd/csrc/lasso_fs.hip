@@ -39,6 +39,24 @@ struct FsShared {
     unsigned char active[FS_MAXD];
 };
 
+// the per-coordinate instance keeps each active coordinate's threshold and diagonal shift next to it
+struct FsSharedPen : FsShared {
+    double kp[FS_MAX], sh[FS_MAX];
+};
+template <bool PEN>
+struct FsSel {
+    typedef FsShared type;
+};
+template <>
+struct FsSel<true> {
+    typedef FsSharedPen type;
+};
+
+__device__ inline double* fs_kp(FsShared&) { return nullptr; }
+__device__ inline double* fs_sh(FsShared&) { return nullptr; }
+__device__ inline double* fs_kp(FsSharedPen& S) { return S.kp; }
+__device__ inline double* fs_sh(FsSharedPen& S) { return S.sh; }
+
 __device__ inline double sgn(double v) { return v > 0.0 ? 1.0 : (v < 0.0 ? -1.0 : 0.0); }
 
 // block-wide (max value, smallest index) reduction; result valid in every thread
@@ -97,19 +115,33 @@ __device__ inline void chol_solve(FsShared& S, int na, double* b, double* xo) {
 
 // out[0] = status (0 converged, 1 active set overflow, 2 iteration cap), out[1] = outer
 // iterations, out[2] = inner (feature-sign) steps, out[3] = final support size
+//
+// PEN = true: per-coordinate penalties, 1/2 w'(G + diag(l2)/rho) w - q'w + sum_j kappa_j |w_j| with
+// kappa_j = l1[j] / (2 rho) (kappa_val then carries rho, and reg is not used).  l2[j]/rho joins the diagonal of the
+// active block (Cholesky factor, refinement matrix, gradient on active coordinates).  A coordinate with kappa_j = 0
+// is FREE: activated when |g_j| exceeds the rounding allowance of the activation test alone, theta_j = 0, no break
+// point of the line search, never dropped.  Gw_out stays the product with the unshifted G.
+template <bool PEN>
 __global__ __launch_bounds__(FS_THREADS) void k_lasso_fs(const double* __restrict__ G, long long ld, long long d,
                                                           const double* __restrict__ q, double* __restrict__ w,
                                                           double kappa_val, const double* __restrict__ rho_dev,
                                                           double reg, double* __restrict__ w_prev_out,
                                                           double* __restrict__ Gw_out, int max_steps,
-                                                          int* __restrict__ out) {
+                                                          int* __restrict__ out, const double* __restrict__ l1,
+                                                          const double* __restrict__ l2) {
     extern __shared__ __align__(16) unsigned char fs_raw[];
-    FsShared& S = *reinterpret_cast<FsShared*>(fs_raw);
+    typename FsSel<PEN>::type& S = *reinterpret_cast<typename FsSel<PEN>::type*>(fs_raw);
+    double* const kp = fs_kp(S);   // threshold / diagonal shift of each active coordinate (PEN only)
+    double* const sh = fs_sh(S);
     const int tid = threadIdx.x;
     const int nd = (int)d;
     // kappa = reg / (2 rho) with rho read on the device when the launch was enqueued before the
     // host knew it (the w-step of the next iteration, api.hip: rbl_phase_finish)
-    const double kappa = rho_dev ? reg / (2.0 * rho_dev[0]) : kappa_val;
+    const double kappa = PEN ? 0.0 : (rho_dev ? reg / (2.0 * rho_dev[0]) : kappa_val);
+    const double rho_inv = PEN ? 1.0 / (rho_dev ? rho_dev[0] : kappa_val) : 0.0;
+    // per-coordinate threshold and diagonal shift (the scalar instance folds both to its constants)
+    auto kap = [&](int j) -> double { return PEN ? 0.5 * l1[j] * rho_inv : kappa; };
+    auto shf = [&](int j) -> double { return PEN ? l2[j] * rho_inv : 0.0; };
     if (w_prev_out)   // the warm start is the previous iterate: keep it for the dual residual
         for (long long j = tid; j < ld; j += FS_THREADS) w_prev_out[j] = w[j];
 
@@ -123,6 +155,8 @@ __global__ __launch_bounds__(FS_THREADS) void k_lasso_fs(const double* __restric
         cnt += nz;
     }
     for (int j = tid; j < nd; j += FS_THREADS) qmax = fmax(qmax, fabs(q[j]));
+    if (PEN)   // scale = max(||q||_inf, max_j kappa_j), as the scalar instance's max(||q||_inf, kappa)
+        for (int j = tid; j < nd; j += FS_THREADS) qmax = fmax(qmax, kap(j));
     S.scan[tid] = cnt;
     __syncthreads();
     for (int off = 1; off < FS_THREADS; off <<= 1) {
@@ -150,7 +184,11 @@ __global__ __launch_bounds__(FS_THREADS) void k_lasso_fs(const double* __restric
             if (S.active[j]) {
                 S.A[pos] = j;
                 S.wA[pos] = w[j];
-                S.theta[pos] = sgn(w[j]);
+                S.theta[pos] = (PEN && !(kap(j) > 0.0)) ? 0.0 : sgn(w[j]);
+                if (PEN) {
+                    kp[pos] = kap(j);
+                    sh[pos] = shf(j);
+                }
                 ++pos;
             }
     }
@@ -170,7 +208,8 @@ __global__ __launch_bounds__(FS_THREADS) void k_lasso_fs(const double* __restric
                 double g = -q[i];
                 for (int a = 0; a < na; ++a) g = __builtin_fma(G[(long long)S.A[a] * ld + i], S.wA[a], g);
                 if (Gw_out) Gw_out[i] = g + q[i];   // (G w)_i: final once this test lets the loop end
-                const double ag = fabs(g);
+                // PEN: the excess over the coordinate's own threshold decides (a free coordinate: |g| itself)
+                const double ag = PEN ? fabs(g) - kap(i) * (1.0 + 1e-12) : fabs(g);
                 if (ag > best) {  // ascending i: keeps the smallest index among equals
                     best = ag;
                     besti = i;
@@ -182,7 +221,7 @@ __global__ __launch_bounds__(FS_THREADS) void k_lasso_fs(const double* __restric
             block_argmax(v, idx, S);
             if (idx == besti && best == v && tid == (besti % FS_THREADS)) S.bcast[0] = bestg;
             __syncthreads();
-            if (!(v > kappa * (1.0 + 1e-12) + 1e-14 * scale)) break;  // KKT holds everywhere: done
+            if (PEN ? !(v > 1e-14 * scale) : !(v > kappa * (1.0 + 1e-12) + 1e-14 * scale)) break;  // KKT holds everywhere: done
             if (na >= FS_MAX) {
                 status = 1;
                 break;
@@ -190,7 +229,11 @@ __global__ __launch_bounds__(FS_THREADS) void k_lasso_fs(const double* __restric
             if (tid == 0) {
                 S.A[na] = idx;
                 S.wA[na] = 0.0;
-                S.theta[na] = -sgn(S.bcast[0]);
+                S.theta[na] = (PEN && !(kap(idx) > 0.0)) ? 0.0 : -sgn(S.bcast[0]);
+                if (PEN) {
+                    kp[na] = kap(idx);
+                    sh[na] = shf(idx);
+                }
                 S.active[idx] = 1;
             }
             ++na;
@@ -213,11 +256,12 @@ __global__ __launch_bounds__(FS_THREADS) void k_lasso_fs(const double* __restric
             __syncthreads();
             double dmax = 0.0;
             for (int a = tid; a < na; a += FS_THREADS) {
+                if (PEN) S.M[a * FS_S + a] += sh[a];   // before any product below: they all see the shifted block
                 S.diag[a] = S.M[a * FS_S + a];
                 double acc = -q[S.A[a]];
                 for (int b = 0; b < na; ++b) acc = __builtin_fma(S.M[a * FS_S + b], S.wA[b], acc);
                 S.gq[a] = acc;
-                S.rhs[a] = q[S.A[a]] - kappa * S.theta[a];
+                S.rhs[a] = q[S.A[a]] - (PEN ? kp[a] : kappa) * S.theta[a];
                 S.rr[a] = S.rhs[a];
             }
             for (int a = tid; a < na; a += FS_THREADS) dmax = fmax(dmax, S.M[a * FS_S + a]);
@@ -265,7 +309,7 @@ __global__ __launch_bounds__(FS_THREADS) void k_lasso_fs(const double* __restric
             if (tid == 0) {
                 for (int a = 0; a < na; ++a) {
                     const double del = S.x[a] - S.wA[a];
-                    aa += del * (-(kappa * S.theta[a] + S.gq[a]));
+                    aa += del * (-((PEN ? kp[a] : kappa) * S.theta[a] + S.gq[a]));
                     bb += S.gq[a] * del;
                 }
                 S.bcast[1] = aa;
@@ -279,14 +323,15 @@ __global__ __launch_bounds__(FS_THREADS) void k_lasso_fs(const double* __restric
                 bool valid = true;
                 if (c < na) {
                     const double wa = S.wA[c], xa = S.x[c];
-                    valid = (wa != 0.0) && (xa * wa < 0.0);
+                    valid = (wa != 0.0) && (xa * wa < 0.0) && !(PEN && !(kp[c] > 0.0));   // free: no break point
                     t = valid ? wa / (wa - xa) : 2.0;
                 }
                 double f = 1e300;
                 if (valid) {
-                    double l1 = 0.0;
-                    for (int a = 0; a < na; ++a) l1 += fabs(S.wA[a] + t * (S.x[a] - S.wA[a]));
-                    f = 0.5 * aa * t * t + bb * t + kappa * l1;
+                    double l1n = 0.0;
+                    for (int a = 0; a < na; ++a)
+                        l1n += (PEN ? kp[a] : 1.0) * fabs(S.wA[a] + t * (S.x[a] - S.wA[a]));
+                    f = 0.5 * aa * t * t + bb * t + (PEN ? 1.0 : kappa) * l1n;
                 }
                 S.tc[c] = t;
                 S.fc[c] = f;
@@ -303,10 +348,15 @@ __global__ __launch_bounds__(FS_THREADS) void k_lasso_fs(const double* __restric
                     if (a < na && S.tc[a] == t && bc != na) nv = 0.0;  // the coefficient(s) that cross at t
                     if (a == bc) nv = 0.0;
                     const int j = S.A[a];
-                    if (nv != 0.0) {
+                    const bool freec = PEN && !(kp[a] > 0.0);
+                    if (nv != 0.0 || freec) {
                         S.A[keep] = j;
                         S.wA[keep] = nv;
-                        S.theta[keep] = sgn(nv);
+                        S.theta[keep] = freec ? 0.0 : sgn(nv);
+                        if (PEN) {
+                            kp[keep] = kp[a];
+                            sh[keep] = sh[a];
+                        }
                         ++keep;
                     } else {
                         S.active[j] = 0;
@@ -323,7 +373,8 @@ __global__ __launch_bounds__(FS_THREADS) void k_lasso_fs(const double* __restric
             for (int a = tid; a < na; a += FS_THREADS) {
                 double g = -q[S.A[a]];
                 for (int b = 0; b < na; ++b) g = __builtin_fma(G[(long long)S.A[a] * ld + S.A[b]], S.wA[b], g);
-                res = fmax(res, fabs(g + kappa * S.theta[a]));
+                if (PEN) g = __builtin_fma(sh[a], S.wA[a], g);
+                res = fmax(res, fabs(g + (PEN ? kp[a] : kappa) * S.theta[a]));
             }
             res = block_max(res, S);
             inner_done = res <= kkt_tol;
@@ -358,20 +409,38 @@ __global__ __launch_bounds__(FS_THREADS) void k_lasso_fs(const double* __restric
 }  // namespace
 
 
+template <bool PEN>
+static int fs_launch(const double* G, int64_t ld, int64_t d, const double* q, double* w, double kappa, int* out_dev,
+                     hipStream_t s, const double* rho_dev, double reg, double* w_prev_out, double* Gw_out, const double* l1,
+                     const double* l2) {
+    const size_t lds = sizeof(typename FsSel<PEN>::type);
+    static bool attr_set = false;
+    if (!attr_set) {
+        RBL_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_lasso_fs<PEN>),
+                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        attr_set = true;
+    }
+    hipLaunchKernelGGL(k_lasso_fs<PEN>, dim3(1), dim3(FS_THREADS), lds, s, G, (long long)ld, (long long)d, q, w, kappa,
+                       rho_dev, reg, w_prev_out, Gw_out, 6 * FS_MAX + 64, out_dev, l1, l2);
+    RBL_HIP(hipGetLastError());
+    return RBL_OK;
+}
+
 int launch_lasso_fs(const double* G, int64_t ld, int64_t d, const double* q, double* w, double kappa, int* out_dev,
                     hipStream_t s, const double* rho_dev, double reg, double* w_prev_out, double* Gw_out) {
     if (d > FS_MAXD) {
         rbl_set_error("lasso_fs: d too large");
         return RBL_ERR_INVALID;
     }
-    static bool attr_set = false;
-    if (!attr_set) {
-        RBL_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_lasso_fs),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(FsShared)));
-        attr_set = true;
+    return fs_launch<false>(G, ld, d, q, w, kappa, out_dev, s, rho_dev, reg, w_prev_out, Gw_out, nullptr, nullptr);
+}
+
+int launch_lasso_fs_pen(const double* G, int64_t ld, int64_t d, const double* q, double* w, double rho, const double* l1,
+                        const double* l2, int* out_dev, hipStream_t s, const double* rho_dev, double* w_prev_out,
+                        double* Gw_out) {
+    if (d > FS_MAXD) {
+        rbl_set_error("lasso_fs: d too large");
+        return RBL_ERR_INVALID;
     }
-    hipLaunchKernelGGL(k_lasso_fs, dim3(1), dim3(FS_THREADS), sizeof(FsShared), s, G, (long long)ld, (long long)d, q, w,
-                       kappa, rho_dev, reg, w_prev_out, Gw_out, 6 * FS_MAX + 64, out_dev);
-    RBL_HIP(hipGetLastError());
-    return RBL_OK;
+    return fs_launch<true>(G, ld, d, q, w, rho, out_dev, s, rho_dev, 0.0, w_prev_out, Gw_out, l1, l2);
 }

@@ -355,6 +355,10 @@ struct WstepWorkspace {
     bool gw_valid;  // ws.Gy holds G w of the w the last run_wstep returned
     int form;       // how the last run_wstep ran (rbl_stats.wstep_form)
     int ncg_skip, ncg_backoff;   // persistent nonlinear CG: w-steps left without / length of the pause of its linear first phase
+    // per-coordinate penalties (rbl_set_penalty): device vectors of ld doubles each (padding 0), NULL = the scalar reg;
+    // pen_l2max = max_j l2_j (FISTA's step constant)
+    const double *pen_l1, *pen_l2;
+    double pen_l2max;
 };
 constexpr int WSTEP_BAR_UINTS = 2 * 10 * 32;
 constexpr int WSTEP_PERSIST_MAX_LD = 2048;                                  // 8 vector elements per thread of a 256-thread block
@@ -373,13 +377,22 @@ int run_wstep(int wstep, const double* G, int64_t d, const double* q, double rho
               double* w_prev_out = nullptr, bool want_Gw = false);   // want_Gw: the lasso kernel leaves G w in ws.Gy
 int finish_wstep_l1(const double* G, int64_t d, const double* q, double rho, double reg, double L, double tol,
                     int max_inner, double* w, WstepWorkspace& ws, int* iters_host, hipStream_t s, bool* fell_back);
-int launch_w_stats(int64_t d, const double* w, const double* w_prev, double* out3, hipStream_t s);
+// l1 != NULL: pen_out4 = [sum w^2, ||w||_1, sum_j l1_j |w_j|, sum_j l2_j w_j^2] as well
+int launch_w_stats(int64_t d, const double* w, const double* w_prev, double* out3, hipStream_t s, const double* l1 = nullptr,
+                   const double* l2 = nullptr, double* pen_out4 = nullptr);
 // lasso_fs.hip: exact active-set (feature-sign) lasso in one workgroup; out_dev = 4 ints
 // rho_dev != NULL: kappa = reg / (2 rho_dev[0]) is formed on the device; w_prev_out != NULL: the warm start is saved there
 int launch_lasso_fs(const double* G, int64_t ld, int64_t d, const double* q, double* w, double kappa, int* out_dev,
                     hipStream_t s, const double* rho_dev = nullptr, double reg = 0.0, double* w_prev_out = nullptr,
                     double* Gw_out = nullptr);   // Gw_out: G w of the solution (valid when the status is 0)
 int launch_reg_terms(int64_t d, const double* w, double* out2 /* [sum w^2, sum |w|] */, hipStream_t s);
+// [sum w^2, sum |w|, sum_j l1_j |w_j|, sum_j l2_j w_j^2]
+int launch_pen_terms(int64_t d, const double* w, const double* l1, const double* l2, double* out4, hipStream_t s);
+// the active-set kernel's per-coordinate instance: kappa_j = l1[j] / (2 rho), l2[j] / rho on the diagonal; rho from
+// rho_dev[0] when given
+int launch_lasso_fs_pen(const double* G, int64_t ld, int64_t d, const double* q, double* w, double rho, const double* l1,
+                        const double* l2, int* out_dev, hipStream_t s, const double* rho_dev = nullptr,
+                        double* w_prev_out = nullptr, double* Gw_out = nullptr);
 int launch_soft_threshold(int64_t d, double* w, double t, hipStream_t s);
 
 // ---- sweep_erm.hip: one pass over D per iteration for erm (fused dual update + next z-step + D^T c)

@@ -25,9 +25,12 @@
 namespace {
 
 // y = alpha * G x + beta * x ; G is ld x ld row-major, one row per wave
+// DIAG: y = alpha * G x + beta * x + dg .* x (the per-coordinate l2 penalties of the CG system)
+template <bool DIAG>
 __global__ __launch_bounds__(256) void k_symv(const double* __restrict__ G, long long ld,
                                                const double* __restrict__ x, double* __restrict__ y, double alpha,
-                                               double beta, const int* __restrict__ done) {
+                                               double beta, const int* __restrict__ done,
+                                               const double* __restrict__ dg) {
     if (done && *done) return;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     for (long long row = (long long)blockIdx.x * 4 + wave; row < ld; row += (long long)gridDim.x * 4) {
@@ -41,7 +44,7 @@ __global__ __launch_bounds__(256) void k_symv(const double* __restrict__ G, long
         }
 #pragma unroll
         for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off, 64);
-        if (lane == 0) y[row] = alpha * acc + beta * x[row];
+        if (lane == 0) y[row] = DIAG ? alpha * acc + beta * x[row] + dg[row] * x[row] : alpha * acc + beta * x[row];
     }
 }
 
@@ -68,11 +71,15 @@ __device__ inline double huber_prox(double b, double Ls, double reg, double t) {
 }
 
 // scal[0] = FISTA t_k ; flags[0] = done, flags[1] = iterations performed
+// PEN (lasso mode): the smooth part is 1/2 w'(G + diag(l2)/rho) w - q'w, P.L includes max_j l2_j / rho, and the prox is
+// the soft threshold with kappa_j = l1[j] / (2 rho) per coordinate
+template <bool PEN>
 __global__ __launch_bounds__(UPD_THREADS) void k_fista_update(long long ld, const double* __restrict__ Gy,
                                                                const double* __restrict__ q, double* __restrict__ w,
                                                                double* __restrict__ yk, FistaParams P,
                                                                double* __restrict__ scal, int* __restrict__ flags,
-                                                               int* __restrict__ publish) {
+                                                               int* __restrict__ publish, const double* __restrict__ l1,
+                                                               const double* __restrict__ l2) {
     // publish != NULL on the last update of a batch: (done, iterations) to pinned host memory, word 0 last
     if (flags[0]) {
         if (publish && threadIdx.x == 0) {
@@ -93,11 +100,14 @@ __global__ __launch_bounds__(UPD_THREADS) void k_fista_update(long long ld, cons
         dw[k] = 0.0;
         if (j < ld) {
             const double y = yk[j];
-            const double b = y - (Gy[j] - q[j]) / P.L;
-            const double x = (P.mode == 0) ? soft_thr(b, P.kappa / P.L) : huber_prox(b, P.rho * P.L, P.reg, P.t);
+            const double b = PEN ? y - (Gy[j] + (l2[j] / P.rho) * y - q[j]) / P.L : y - (Gy[j] - q[j]) / P.L;
+            const double x = PEN ? soft_thr(b, l1[j] / (2.0 * P.rho) / P.L)
+                                 : ((P.mode == 0) ? soft_thr(b, P.kappa / P.L) : huber_prox(b, P.rho * P.L, P.reg, P.t));
             const double dd = x - w[j];
-            wn[k] = x;
-            dw[k] = dd;
+            if (!PEN) {   // (PEN forms both again below from the same inputs: no 32 live doubles, no scratch)
+                wn[k] = x;
+                dw[k] = dd;
+            }
             acc[0] += (y - x) * dd;
             mx_dw = fmax(mx_dw, fabs(dd));
             mx_w = fmax(mx_w, fabs(x));
@@ -128,8 +138,15 @@ __global__ __launch_bounds__(UPD_THREADS) void k_fista_update(long long ld, cons
     for (int k = 0; k < UPD_PER; ++k) {
         const long long j = (long long)k * UPD_THREADS + threadIdx.x;
         if (j < ld) {
-            w[j] = wn[k];
-            yk[j] = wn[k] + coef * dw[k];
+            double x = wn[k], dd = dw[k];
+            if (PEN) {
+                const double y = yk[j];
+                const double b = y - (Gy[j] + (l2[j] / P.rho) * y - q[j]) / P.L;
+                x = soft_thr(b, l1[j] / (2.0 * P.rho) / P.L);
+                dd = x - w[j];
+            }
+            w[j] = x;
+            yk[j] = x + coef * dd;
         }
     }
     __syncthreads();
@@ -406,37 +423,64 @@ __global__ void k_power_init(long long ld, long long d, double* __restrict__ x) 
     }
 }
 
+// PEN: also out[2] = sum_j l1_j |w_j|, out[3] = sum_j l2_j w_j^2 (same strided order, same tree)
+template <bool PEN>
 __global__ __launch_bounds__(UPD_THREADS) void k_reg_terms(long long d, const double* __restrict__ w,
-                                                            double* __restrict__ out) {
-    __shared__ double smem[2 * UPD_THREADS / 64];
-    double acc[2] = {0.0, 0.0};
+                                                            double* __restrict__ out, const double* __restrict__ l1,
+                                                            const double* __restrict__ l2) {
+    constexpr int NA = PEN ? 4 : 2;
+    __shared__ double smem[NA * UPD_THREADS / 64];
+    double acc[NA] = {};
     for (long long j = threadIdx.x; j < d; j += UPD_THREADS) {
         acc[0] += w[j] * w[j];
         acc[1] += fabs(w[j]);
+        if (PEN) {
+            acc[NA - 2] += l1[j] * fabs(w[j]);
+            acc[NA - 1] += l2[j] * (w[j] * w[j]);
+        }
     }
-    rbl::block_sum<2, UPD_THREADS>(acc, smem);
+    rbl::block_sum<NA, UPD_THREADS>(acc, smem);
     if (threadIdx.x == 0) {
         out[0] = acc[0];  // objective.py:83-84  sum w^2
         out[1] = acc[1];  // objective.py:85-86  ||w||_1
+        if (PEN) {
+            out[2] = acc[NA - 2];
+            out[3] = acc[NA - 1];
+        }
     }
 }
 
 // out[0] = ||w - w_prev||^2 (algorithms.py:136), out[1] = sum w^2, out[2] = ||w||_1 (objective.py:83-86)
+// PEN: also pen_out[0..3] = sum w^2, ||w||_1, sum_j l1_j |w_j|, sum_j l2_j w_j^2 (the layout of k_reg_terms<true>)
+template <bool PEN>
 __global__ __launch_bounds__(UPD_THREADS) void k_w_stats(long long d, const double* __restrict__ w,
-                                                          const double* __restrict__ w_prev, double* __restrict__ out) {
-    __shared__ double smem[3 * UPD_THREADS / 64];
-    double acc[3] = {0.0, 0.0, 0.0};
+                                                          const double* __restrict__ w_prev, double* __restrict__ out,
+                                                          const double* __restrict__ l1, const double* __restrict__ l2,
+                                                          double* __restrict__ pen_out) {
+    constexpr int NA = PEN ? 5 : 3;
+    __shared__ double smem[NA * UPD_THREADS / 64];
+    double acc[NA] = {};
     for (long long j = threadIdx.x; j < d; j += UPD_THREADS) {
         const double t = w[j] - w_prev[j];
         acc[0] += t * t;
         acc[1] += w[j] * w[j];
         acc[2] += fabs(w[j]);
+        if (PEN) {
+            acc[NA - 2] += l1[j] * fabs(w[j]);
+            acc[NA - 1] += l2[j] * (w[j] * w[j]);
+        }
     }
-    rbl::block_sum<3, UPD_THREADS>(acc, smem);
+    rbl::block_sum<NA, UPD_THREADS>(acc, smem);
     if (threadIdx.x == 0) {
         out[0] = acc[0];
         out[1] = acc[1];
         out[2] = acc[2];
+        if (PEN) {
+            pen_out[0] = acc[1];
+            pen_out[1] = acc[2];
+            pen_out[2] = acc[NA - 2];
+            pen_out[3] = acc[NA - 1];
+        }
     }
 }
 
@@ -461,8 +505,8 @@ int launch_power_iteration(const double* G, int64_t ld, double* x, double* y, do
     hipLaunchKernelGGL(k_power_init, dim3(64), dim3(256), 0, s, (long long)ld, (long long)ld, x);
     hipLaunchKernelGGL(k_normalize, dim3(1), dim3(UPD_THREADS), 0, s, (long long)ld, x, x, scal);
     for (int it = 0; it < iters; ++it) {
-        hipLaunchKernelGGL(k_symv, dim3(symv_grid(ld)), dim3(256), 0, s, G, (long long)ld, x, y, 1.0, 0.0,
-                           (const int*)nullptr);
+        hipLaunchKernelGGL(k_symv<false>, dim3(symv_grid(ld)), dim3(256), 0, s, G, (long long)ld, x, y, 1.0, 0.0,
+                           (const int*)nullptr, (const double*)nullptr);
         hipLaunchKernelGGL(k_normalize, dim3(1), dim3(UPD_THREADS), 0, s, (long long)ld, y, x, scal);
     }
     RBL_HIP(hipGetLastError());
@@ -479,8 +523,10 @@ int run_fista(int mode, const double* G, int64_t ld, const double* q, double rho
     constexpr int BATCH = 8;
     const unsigned sg = symv_grid(ld);
     FistaParams P;
+    // per-coordinate penalties (lasso mode only): the shifted quadratic's constant, thresholds formed in the kernel
+    const bool pen = mode == 0 && ws.pen_l1 != nullptr;
     P.mode = mode;
-    P.L = L;
+    P.L = pen ? L + ws.pen_l2max / rho : L;
     P.kappa = reg / (2.0 * rho);
     P.rho = rho;
     P.reg = reg;
@@ -499,9 +545,14 @@ int run_fista(int mode, const double* G, int64_t ld, const double* q, double rho
     while (done_iters < max_inner) {
         ws.pin[6] = -1;
         for (int b = 0; b < batch; ++b) {
-            hipLaunchKernelGGL(k_symv, dim3(sg), dim3(256), 0, s, G, (long long)ld, ws.yk, ws.Gy, 1.0, 0.0, ws.flags);
-            hipLaunchKernelGGL(k_fista_update, dim3(1), dim3(UPD_THREADS), 0, s, (long long)ld, ws.Gy, q, w, ws.yk, P,
-                               ws.scal, ws.flags, b == batch - 1 ? ws.pin + 6 : (int*)nullptr);
+            hipLaunchKernelGGL(k_symv<false>, dim3(sg), dim3(256), 0, s, G, (long long)ld, ws.yk, ws.Gy, 1.0, 0.0, ws.flags, (const double*)nullptr);
+            if (pen)
+                hipLaunchKernelGGL(k_fista_update<true>, dim3(1), dim3(UPD_THREADS), 0, s, (long long)ld, ws.Gy, q, w, ws.yk, P,
+                                   ws.scal, ws.flags, b == batch - 1 ? ws.pin + 6 : (int*)nullptr, ws.pen_l1, ws.pen_l2);
+            else
+                hipLaunchKernelGGL(k_fista_update<false>, dim3(1), dim3(UPD_THREADS), 0, s, (long long)ld, ws.Gy, q, w, ws.yk, P,
+                                   ws.scal, ws.flags, b == batch - 1 ? ws.pin + 6 : (int*)nullptr, (const double*)nullptr,
+                                   (const double*)nullptr);
         }
         RBL_HIP(hipGetLastError());
         done_iters += batch;
@@ -552,7 +603,7 @@ int run_ncg(const double* G, int64_t ld, const double* q, double rho, double reg
         }
     }
     double *p = ws.p, *sv = ws.r, *Gp = ws.Gy, *Gw = ws.wn, *gdiag = ws.yk;
-    hipLaunchKernelGGL(k_symv, dim3(sg), dim3(256), 0, s, G, (long long)ld, w, Gw, 1.0, 0.0, (const int*)nullptr);
+    hipLaunchKernelGGL(k_symv<false>, dim3(sg), dim3(256), 0, s, G, (long long)ld, w, Gw, 1.0, 0.0, (const int*)nullptr, (const double*)nullptr);
     hipLaunchKernelGGL(k_ncg_init, dim3(1), dim3(UPD_THREADS), 0, s, (long long)ld, G, Gw, q, w, P, p, sv, gdiag, ws.scal,
                        ws.flags);
     // one batch of about as many iterations as last time (+1): updates after convergence are no-op launches
@@ -566,7 +617,7 @@ int run_ncg(const double* G, int64_t ld, const double* q, double rho, double reg
     while (done_iters < cap) {
         ws.pin[8] = -1;
         for (int b = 0; b < batch; ++b) {
-            hipLaunchKernelGGL(k_symv, dim3(sg), dim3(256), 0, s, G, (long long)ld, p, Gp, 1.0, 0.0, ws.flags);
+            hipLaunchKernelGGL(k_symv<false>, dim3(sg), dim3(256), 0, s, G, (long long)ld, p, Gp, 1.0, 0.0, ws.flags, (const double*)nullptr);
             hipLaunchKernelGGL(k_ncg_update, dim3(1), dim3(UPD_THREADS), 0, s, (long long)ld, Gp, q, w, Gw, p, sv, gdiag, P,
                                ws.scal, ws.flags, b == batch - 1 ? ws.pin + 8 : (int*)nullptr);
         }
@@ -691,9 +742,10 @@ __device__ inline bool wp_exchange(unsigned tag, const double* ybuf, unsigned lo
 
 // rows [r0, r1) of y = alpha G x + beta x -> ybuf[row - r0] (LDS; rows beyond r1 up to r0 + WP_RPB: 0); x in LDS,
 // the block's rows of G in LDS (GLDS) or in global memory
-template <bool GLDS>
+// DIAG: + dg .* x (per-coordinate l2 penalties)
+template <bool GLDS, bool DIAG = false>
 __device__ inline void wp_matvec(const double* __restrict__ G, const double* gs, int ld, int r0, int r1,
-                                 const double* xs, double alpha, double beta, double* ybuf) {
+                                 const double* xs, double alpha, double beta, double* ybuf, const double* dg = nullptr) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     for (int row = r0 + wave; row < r0 + WP_RPB; row += WP_THREADS / 64) {
         double acc = 0.0;
@@ -703,7 +755,8 @@ __device__ inline void wp_matvec(const double* __restrict__ G, const double* gs,
 #pragma unroll
             for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off, 64);
         }
-        if (lane == 0) ybuf[row - r0] = row < r1 ? alpha * acc + beta * xs[row] : 0.0;
+        if (lane == 0)
+            ybuf[row - r0] = row < r1 ? (DIAG ? alpha * acc + beta * xs[row] + dg[row] * xs[row] : alpha * acc + beta * xs[row]) : 0.0;
     }
 }
 
@@ -737,12 +790,13 @@ __device__ inline void wp_publish(int* pin, int done, int iters) {
 }
 
 // (rho G + reg I) w = rho q by CG, warm-started from w (w_LBFGS.py:31-53 solves the same system by L-BFGS-B)
-template <bool GLDS, int PER>
+// DIAG: (rho G + reg I + diag(dg)) w = rho q - the per-coordinate l2 penalties (reg = 0 then)
+template <bool GLDS, int PER, bool DIAG>
 __global__ __launch_bounds__(WP_THREADS) void k_cg_persist(const double* __restrict__ G, int ld, const double* __restrict__ q,
                                                             double rho, double reg, double tol, int max_iter,
                                                             double* __restrict__ w, unsigned long long* x0, unsigned long long* x1,
                                                             unsigned tag_base, double* __restrict__ Gw_out, unsigned* abort_word,
-                                                            int* pin) {
+                                                            int* pin, const double* __restrict__ dg) {
     extern __shared__ __attribute__((aligned(16))) double wp_lds[];
     double* xs = wp_lds;                       // ld
     double* red = wp_lds + ld;                 // 16 (block sums)
@@ -759,7 +813,7 @@ __global__ __launch_bounds__(WP_THREADS) void k_cg_persist(const double* __restr
         if (j < ld) xs[j] = wj[k];
     }
     __syncthreads();
-    wp_matvec<GLDS>(G, gs, ld, r0, r1, xs, rho, reg, ybuf);          // A w
+    wp_matvec<GLDS, DIAG>(G, gs, ld, r0, r1, xs, rho, reg, ybuf, dg);          // A w
     int iters = 0, done = 0, ok = 1;
     double rr = 0.0, thr = 0.0;
     ++xn;
@@ -790,7 +844,7 @@ __global__ __launch_bounds__(WP_THREADS) void k_cg_persist(const double* __restr
             if (j < ld) xs[j] = pj[k];
         }
         __syncthreads();
-        wp_matvec<GLDS>(G, gs, ld, r0, r1, xs, rho, reg, ybuf);      // A p
+        wp_matvec<GLDS, DIAG>(G, gs, ld, r0, r1, xs, rho, reg, ybuf, dg);      // A p
         ++xn;
         if (!wp_exchange<PER>(tag_base + xn, ybuf, (iters & 1) ? x0 : x1, ld, aj, abort_word)) {
             ok = 0;
@@ -1201,14 +1255,18 @@ int wp_run(const WpPlan& pl, int64_t ld, K const (&kern)[2][2], int* pin, int ma
 }
 
 int run_cg_persist(const WpPlan& pl, const double* G, int64_t ld, const double* q, double rho, double reg, double tol,
-                   int max_iter, double* w, WstepWorkspace& ws, bool want_Gw, int* status, int* iters, hipStream_t s) {
-    static decltype(&k_cg_persist<true, 4>) const kern[2][2] = {{k_cg_persist<false, 4>, k_cg_persist<false, 8>},
-                                                                 {k_cg_persist<true, 4>, k_cg_persist<true, 8>}};
+                   int max_iter, double* w, WstepWorkspace& ws, bool want_Gw, int* status, int* iters, hipStream_t s,
+                   const double* dg = nullptr) {
+    typedef decltype(&k_cg_persist<true, 4, false>) Kern;
+    static Kern const kern[2][2] = {{k_cg_persist<false, 4, false>, k_cg_persist<false, 8, false>},
+                                    {k_cg_persist<true, 4, false>, k_cg_persist<true, 8, false>}};
+    static Kern const kern_dg[2][2] = {{k_cg_persist<false, 4, true>, k_cg_persist<false, 8, true>},
+                                       {k_cg_persist<true, 4, true>, k_cg_persist<true, 8, true>}};
     int* pin = ws.pin + 4;
-    return wp_run(pl, ld, kern, pin, max_iter, ws, want_Gw, status, iters, s,
+    return wp_run(pl, ld, dg ? kern_dg : kern, pin, max_iter, ws, want_Gw, status, iters, s,
                   [&](auto k, unsigned tag_base, int cap, double* gw, unsigned long long* x0, unsigned long long* x1) {
                       hipLaunchKernelGGL(k, dim3(pl.nblocks), dim3(WP_THREADS), pl.lds_bytes, s, G, (int)ld, q, rho, reg, tol,
-                                         cap, w, x0, x1, tag_base, gw, ws.bar, pin);
+                                         cap, w, x0, x1, tag_base, gw, ws.bar, pin, dg);
                       RBL_HIP(hipGetLastError());
                       return RBL_OK;
                   });
@@ -1263,7 +1321,11 @@ int run_wstep(int wstep, const double* G, int64_t ld, const double* q, double rh
         rbl_set_error("w-step: d=%lld exceeds the single-block update limit %d", (long long)ld, UPD_THREADS * UPD_PER);
         return RBL_ERR_INVALID;
     }
-    if (wstep == RBL_WSTEP_L2 && ws.eig_ok) {
+    // per-coordinate penalties (rbl_set_penalty): ws.pen_l1 / ws.pen_l2 replace reg; the eigen-decomposition ridge
+    // needs a multiple of the identity and is not used with them
+    const bool pen = ws.pen_l1 != nullptr;
+    if (pen) reg = 0.0;
+    if (wstep == RBL_WSTEP_L2 && ws.eig_ok && !pen) {
         // (rho G + reg I) w = rho q through the one-time eigendecomposition of G (eig.hip): two mat-vecs for any rho,
         // plus one step of iterative refinement against G itself
         if (iters_host) *iters_host = 1;
@@ -1276,7 +1338,7 @@ int run_wstep(int wstep, const double* G, int64_t ld, const double* q, double rh
             // the whole CG in one persistent launch (k_cg_persist)
             int status = 0, it = 0;
             RBL_TRY(run_cg_persist(pl, G, ld, q, rho, reg, tol, max_inner < 20000 ? max_inner : 20000, w, ws, want_Gw, &status,
-                                   &it, s));
+                                   &it, s, pen ? ws.pen_l2 : nullptr));
             if (status < 0) {
                 rbl_set_error("w-step: the persistent CG kernel did not complete (status %d)", status);
                 return RBL_ERR_HIP;
@@ -1292,7 +1354,12 @@ int run_wstep(int wstep, const double* G, int64_t ld, const double* q, double rh
         // iterations) to pinned memory and the host spins on that word - one host round trip per
         // w-step and no device-to-host copy; updates after convergence are no-ops (device flag).
         const unsigned sg = symv_grid(ld);
-        hipLaunchKernelGGL(k_symv, dim3(sg), dim3(256), 0, s, G, (long long)ld, w, ws.Gy, rho, reg, (const int*)nullptr);
+        if (pen)   // A = rho G + diag(l2)
+            hipLaunchKernelGGL(k_symv<true>, dim3(sg), dim3(256), 0, s, G, (long long)ld, w, ws.Gy, rho, 0.0, (const int*)nullptr,
+                               ws.pen_l2);
+        else
+            hipLaunchKernelGGL(k_symv<false>, dim3(sg), dim3(256), 0, s, G, (long long)ld, w, ws.Gy, rho, reg, (const int*)nullptr,
+                               (const double*)nullptr);
         hipLaunchKernelGGL(k_cg_init, dim3(1), dim3(UPD_THREADS), 0, s, (long long)ld, ws.Gy, q, rho, ws.r, ws.p, tol,
                            ws.scal, ws.flags);
         int batch = ws.last_iters > 0 ? ws.last_iters + 2 : 16;
@@ -1302,7 +1369,12 @@ int run_wstep(int wstep, const double* G, int64_t ld, const double* q, double rh
         while (done_iters < max_inner) {
             ws.pin[4] = -1;
             for (int b = 0; b < batch; ++b) {
-                hipLaunchKernelGGL(k_symv, dim3(sg), dim3(256), 0, s, G, (long long)ld, ws.p, ws.Gy, rho, reg, ws.flags);
+                if (pen)
+                    hipLaunchKernelGGL(k_symv<true>, dim3(sg), dim3(256), 0, s, G, (long long)ld, ws.p, ws.Gy, rho, 0.0, ws.flags,
+                                       ws.pen_l2);
+                else
+                    hipLaunchKernelGGL(k_symv<false>, dim3(sg), dim3(256), 0, s, G, (long long)ld, ws.p, ws.Gy, rho, reg, ws.flags,
+                                       (const double*)nullptr);
                 hipLaunchKernelGGL(k_cg_update, dim3(1), dim3(UPD_THREADS), 0, s, (long long)ld, ws.Gy, w, ws.r, ws.p,
                                    ws.scal, ws.flags, b == batch - 1 ? ws.pin + 4 : (int*)nullptr);
             }
@@ -1325,8 +1397,12 @@ int run_wstep(int wstep, const double* G, int64_t ld, const double* q, double rh
         // kernel writes its status block straight into pinned host memory.
         ws.pin[0] = -1;   // sentinel: the kernel stores its status (>= 0) here last
         ws.form = 2;
-        RBL_TRY(launch_lasso_fs(G, ld, ld, q, w, reg / (2.0 * rho), ws.pin, s, rho_dev, reg, w_prev_out,
-                                want_Gw ? ws.Gy : nullptr));
+        if (pen)
+            RBL_TRY(launch_lasso_fs_pen(G, ld, ld, q, w, rho, ws.pen_l1, ws.pen_l2, ws.pin, s, rho_dev, w_prev_out,
+                                        want_Gw ? ws.Gy : nullptr));
+        else
+            RBL_TRY(launch_lasso_fs(G, ld, ld, q, w, reg / (2.0 * rho), ws.pin, s, rho_dev, reg, w_prev_out,
+                                    want_Gw ? ws.Gy : nullptr));
         if (fs_pending) {
             *fs_pending = true;
             return RBL_OK;
@@ -1352,25 +1428,37 @@ int finish_wstep_l1(const double* G, int64_t ld, const double* q, double rho, do
 }
 
 int launch_symv(const double* G, int64_t ld, const double* x, double* y, hipStream_t s) {
-    hipLaunchKernelGGL(k_symv, dim3(symv_grid(ld)), dim3(256), 0, s, G, (long long)ld, x, y, 1.0, 0.0, (const int*)nullptr);
+    hipLaunchKernelGGL(k_symv<false>, dim3(symv_grid(ld)), dim3(256), 0, s, G, (long long)ld, x, y, 1.0, 0.0, (const int*)nullptr, (const double*)nullptr);
     RBL_HIP(hipGetLastError());
     return RBL_OK;
 }
 
 int launch_symv_ab(const double* G, int64_t ld, const double* x, double* y, double alpha, double beta, hipStream_t s) {
-    hipLaunchKernelGGL(k_symv, dim3(symv_grid(ld)), dim3(256), 0, s, G, (long long)ld, x, y, alpha, beta, (const int*)nullptr);
+    hipLaunchKernelGGL(k_symv<false>, dim3(symv_grid(ld)), dim3(256), 0, s, G, (long long)ld, x, y, alpha, beta, (const int*)nullptr, (const double*)nullptr);
     RBL_HIP(hipGetLastError());
     return RBL_OK;
 }
 
 int launch_reg_terms(int64_t d, const double* w, double* out2, hipStream_t s) {
-    hipLaunchKernelGGL(k_reg_terms, dim3(1), dim3(UPD_THREADS), 0, s, (long long)d, w, out2);
+    hipLaunchKernelGGL(k_reg_terms<false>, dim3(1), dim3(UPD_THREADS), 0, s, (long long)d, w, out2, (const double*)nullptr,
+                       (const double*)nullptr);
     RBL_HIP(hipGetLastError());
     return RBL_OK;
 }
 
-int launch_w_stats(int64_t d, const double* w, const double* w_prev, double* out3, hipStream_t s) {
-    hipLaunchKernelGGL(k_w_stats, dim3(1), dim3(UPD_THREADS), 0, s, (long long)d, w, w_prev, out3);
+int launch_pen_terms(int64_t d, const double* w, const double* l1, const double* l2, double* out4, hipStream_t s) {
+    hipLaunchKernelGGL(k_reg_terms<true>, dim3(1), dim3(UPD_THREADS), 0, s, (long long)d, w, out4, l1, l2);
+    RBL_HIP(hipGetLastError());
+    return RBL_OK;
+}
+
+int launch_w_stats(int64_t d, const double* w, const double* w_prev, double* out3, hipStream_t s, const double* l1,
+                   const double* l2, double* pen_out4) {
+    if (l1)
+        hipLaunchKernelGGL(k_w_stats<true>, dim3(1), dim3(UPD_THREADS), 0, s, (long long)d, w, w_prev, out3, l1, l2, pen_out4);
+    else
+        hipLaunchKernelGGL(k_w_stats<false>, dim3(1), dim3(UPD_THREADS), 0, s, (long long)d, w, w_prev, out3,
+                           (const double*)nullptr, (const double*)nullptr, (double*)nullptr);
     RBL_HIP(hipGetLastError());
     return RBL_OK;
 }

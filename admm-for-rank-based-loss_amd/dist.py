@@ -79,6 +79,9 @@ class GpuEngine:
     def pending_reduce(self):
         return self.s.pending_reduce()
 
+    def set_penalty(self, l1, l2):
+        self.s.set_penalty(l1, l2)
+
     def synth_local(self, seed, class_sep, flip_y):
         self.s.synth_local(seed, class_sep, flip_y)
 
@@ -243,12 +246,16 @@ class ShardedADMM:
     NS = 64      # regular samples per rank for the splitters
     K = 63       # seam-search candidates per rank and round (64-ary search: 5 rounds decide 16M positions)
 
-    def __init__(self, engine, group=None, dist_z=True, world=None, rank=None):
-        """world / rank: only for drivers that bring their own collectives by overriding _allreduce,
+    def __init__(self, engine, group=None, dist_z=True, world=None, rank=None, l1_weights=None, l2_weights=None):
+        """l1_weights / l2_weights: per-coordinate penalties (include/rbl.h: rbl_set_penalty) handed to this rank's
+        handle - the w-step is replicated, so every rank must pass the same vectors.
+        world / rank: only for drivers that bring their own collectives by overriding _allreduce,
         _allgather_rows, _gather_small, _gather_counts and _alltoall (tests/test_gpu_dist.py runs 8
         ranks as threads of one process that way); otherwise they come from torch.distributed."""
         self.e = engine
         self.group = group
+        if l1_weights is not None or l2_weights is not None:
+            engine.set_penalty(l1_weights, l2_weights)
         if world is not None:
             self.world, self.rank = int(world), int(rank)
         else:

@@ -7,7 +7,11 @@ the reference (citations: reference ``src/optim/algorithms.py``), so ``run_SRM.p
 directory on ``PYTHONPATH``.  State (w, z, lambda) lives on the GPU; the ``w`` / ``z`` /
 ``lagrangian`` attributes download it on access.  All arithmetic is done by librbl.so
 (include/rbl.h); this file is host glue.  Extra keyword arguments (after the reference's
-own): ``storage`` ("f32" default | "f64" strict | "fp16" half the bytes of D, data rounded once to float16), ``device``.
+own): ``storage`` ("f32" default | "f64" strict | "fp16" half the bytes of D, data rounded once to float16), ``device``;
+``l1_weights`` / ``l2_weights`` (a scalar or one value per feature: the regulariser becomes
+1/2 sum_j (l1_j |w_j| + l2_j w_j^2) - elastic net, penalty factors, unpenalised coordinates) and ``fit_intercept``
+(an unpenalised bias: a column of ones is appended to a host copy of X, the solver has d + 1 coordinates, ``coef_`` /
+``intercept_`` split the result while ``w`` and ``final_res()`` keep the full vector).
 """
 import time
 
@@ -33,21 +37,27 @@ _ON_DEVICE = _OnDevice()
 class Optimizer:
     def __init__(self, X, y, weight_function="erm", loss="binary_cross_entropy", l2_reg=None, l1_reg=None,
                  B=None, n_class=None, args=None, w0=None, max_iter=200, tol=1e-4, storage="f32", device=0,
-                 _wstep=None, _smooth_t=1.0, share_data=None):
+                 _wstep=None, _smooth_t=1.0, share_data=None, l1_weights=None, l2_weights=None, fit_intercept=False):
         # argument checks in the reference's order (objective first :22, then :55-68)
         _solver.check_problem(weight_function, loss, B, args)
-        if l1_reg is None and l2_reg is None:
+        if l1_reg is None and l2_reg is None and l1_weights is None and l2_weights is None:
             raise ValueError("More arguments: l1_reg or l2_reg not l1_reg and l2_reg!")       # :62
         if B is not None and weight_function != "ehrm":
             raise ValueError(f"Unrecognized weight_function '{weight_function}'! Options: ['ehrm']")  # :65-68
         if weight_function == "ehrm" and B is None:
             raise ValueError("ehrm needs the reference point B")
         Xm = _solver._as_matrix(X)
+        # per-coordinate penalties / intercept: validated on the host before any device call; None = the scalar path
+        pen = _solver.resolve_penalty(Xm.shape[1], l1_reg, l2_reg, l1_weights, l2_weights, fit_intercept)
+        self.fit_intercept = bool(fit_intercept)
+        if self.fit_intercept:
+            Xm = _solver.add_intercept_column(Xm)       # a host copy of X with the column of ones
+        self._pen = pen
         self.num_row, self.num_feature = Xm.shape                                             # :26-27
-        self.reg = l1_reg or l2_reg                                                           # :30
+        self.reg = pen["reg"] if pen else (l1_reg or l2_reg)                                  # :30
         self.loss = loss                                                                      # :36
         self.tol, self.max_iter = tol, max_iter                                               # :44-45
-        self.w_flag = 1 if l1_reg is not None else 2                                          # :57-60
+        self.w_flag = (1 if pen["wstep"] == _lib.WSTEP_L1 else 2) if pen else (1 if l1_reg is not None else 2)  # :57-60
         self.B = B
         self.w_tol = 7e-5                       # :69 (kept for callers; the GPU w-step is exact)
         self.z_maxiter = self.num_row           # :70 (the GPU PAV needs no sweep cap)
@@ -77,10 +87,16 @@ class Optimizer:
             self._s.gram()                                                                    # :24 DTD
         elif y_own is not None:
             self._s.set_labels(y_own)
+        if pen:
+            self._s.set_penalty(pen["l1"], pen["l2"])
         if w0 is not None:                                                                    # :39-40
-            self._s.set_state(w=np.asarray(w0, dtype=np.float64).reshape(-1))
+            w0 = np.asarray(w0, dtype=np.float64).reshape(-1)
+            if self.fit_intercept and w0.size == self.num_feature - 1:
+                w0 = np.append(w0, 0.0)                 # coefficients only: the intercept starts at 0
+            self._s.set_state(w=w0)
         self.objective = rankbasedObjective(None, None, weight_function, loss, l2_reg, l1_reg, B, n_class, args,
-                                            _shared_solver=self._s)                           # :22
+                                            _shared_solver=self._s,
+                                            _penalty=(pen["l1"], pen["l2"]) if pen else None)  # :22
         self._storage, self._device = storage, device
         self._last = None
 
@@ -92,6 +108,17 @@ class Optimizer:
     @w.setter
     def w(self, value):
         self._s.set_state(w=np.asarray(value, dtype=np.float64).reshape(-1))
+
+    @property
+    def coef_(self):
+        """the feature coefficients (d,): w without the intercept's coordinate"""
+        w = self.w.reshape(-1)
+        return w[:-1] if self.fit_intercept else w
+
+    @property
+    def intercept_(self):
+        """the unpenalised bias (0.0 without fit_intercept)"""
+        return float(self.w.reshape(-1)[-1]) if self.fit_intercept else 0.0
 
     @property
     def z(self):
@@ -138,8 +165,11 @@ class Optimizer:
     # ---- logging (:77-86) ------------------------------------------------------------------
     def start_store(self, X, y, weight_function="erm", loss="binary_cross_entropy", B=None, l2_reg=None,
                     l1_reg=None, n_class=None, args=None, _share_data=None):
+        if self.fit_intercept:
+            X = _solver.add_intercept_column(_solver._as_matrix(X))
         self.test_objective = rankbasedObjective(X, y, weight_function, loss, l2_reg, l1_reg, B, n_class, args,
-                                                 storage=self._storage, device=self._device, _share_data=_share_data)
+                                                 storage=self._storage, device=self._device, _share_data=_share_data,
+                                                 _penalty=(self._pen["l1"], self._pen["l2"]) if self._pen else None)
         w = self.w
         self._s.profile_kernels(2)     # z_time / w_time below come from HIP events around the phases
         self.w_time = [0]
@@ -207,9 +237,12 @@ class Optimizer:
 
 class ADMMmethod(Optimizer):
     def __init__(self, X, y, weight_function="erm", loss="binary_cross_entropy", l2_reg=None, l1_reg=None, B=None,
-                 n_class=None, args=None, w0=None, max_iter=200, tol=1e-4, storage="f32", device=0, share_data=None):
+                 n_class=None, args=None, w0=None, max_iter=200, tol=1e-4, storage="f32", device=0,
+                 l1_weights=None, l2_weights=None, fit_intercept=False, share_data=None):
+        # (share_data stays the trailing keyword; the three before it are meant to be given by name)
         super().__init__(X, y, weight_function, loss, l2_reg, l1_reg, B, n_class, args, w0, max_iter, tol,
-                         storage=storage, device=device, share_data=share_data)
+                         storage=storage, device=device, share_data=share_data, l1_weights=l1_weights,
+                         l2_weights=l2_weights, fit_intercept=fit_intercept)
 
     def start_store(self, X, y, weight_function="erm", loss="binary_cross_entropy", B=None, l2_reg=None,
                     l1_reg=None, n_class=None, args=None):
@@ -228,7 +261,11 @@ class ADMMmethod(Optimizer):
 
 class smoothADMMmethod(Optimizer):
     def __init__(self, X, y, weight_function="erm", loss="binary_cross_entropy", B=None, l2_reg=None, l1_reg=None,
-                 n_class=None, args=None, w0=None, t=1, max_iter=200, tol=1e-4, storage="f32", device=0, share_data=None):
+                 n_class=None, args=None, w0=None, t=1, max_iter=200, tol=1e-4, storage="f32", device=0,
+                 l1_weights=None, l2_weights=None, fit_intercept=False, share_data=None):
+        if l1_weights is not None or l2_weights is not None or fit_intercept:
+            raise ValueError("smoothADMMmethod has no per-coordinate penalties: l1_weights, l2_weights and fit_intercept "
+                             "belong to ADMMmethod (the smoothed-l1 w-step smooths one scalar l1 norm)")
         wstep = _lib.WSTEP_SMOOTH_L1 if l1_reg is not None else None
         super().__init__(X, y, weight_function, loss, l2_reg, l1_reg, B, n_class, args, w0, max_iter, tol,
                          storage=storage, device=device, _wstep=wstep, _smooth_t=float(t), share_data=share_data)
@@ -271,7 +308,8 @@ class ADMMgroup:
     smoothADMMmethod objects; start_store / main_loop / final_res mirror the single-solver calls and return lists in
     the order of ``problems``."""
 
-    _KEYS = ("weight_function", "loss", "l2_reg", "l1_reg", "B", "args", "w0", "smooth", "t", "y")
+    _KEYS = ("weight_function", "loss", "l2_reg", "l1_reg", "B", "args", "w0", "smooth", "t", "y", "l1_weights",
+             "l2_weights", "fit_intercept")
 
     def __init__(self, X, y, problems, storage="f32", device=0, max_iter=200, tol=1e-4):
         if not isinstance(problems, (list, tuple)) or len(problems) == 0:
@@ -290,8 +328,15 @@ class ADMMgroup:
             pr.setdefault("loss", "binary_cross_entropy")
             try:
                 _solver.check_problem(pr["weight_function"], pr["loss"], pr.get("B"), pr.get("args"))
-                if pr.get("l1_reg") is None and pr.get("l2_reg") is None:
+                if all(pr.get(k) is None for k in ("l1_reg", "l2_reg", "l1_weights", "l2_weights")):
                     raise ValueError("More arguments: l1_reg or l2_reg not l1_reg and l2_reg!")
+                if pr.get("smooth") and (pr.get("l1_weights") is not None or pr.get("l2_weights") is not None
+                                         or pr.get("fit_intercept")):
+                    raise ValueError("smooth=True members have no l1_weights, l2_weights or fit_intercept")
+                if bool(pr.get("fit_intercept")) != bool(problems[0].get("fit_intercept")):
+                    raise ValueError("fit_intercept must be the same for every problem of a group (one data matrix)")
+                _solver.resolve_penalty(np.shape(X)[1], pr.get("l1_reg"), pr.get("l2_reg"), pr.get("l1_weights"),
+                                        pr.get("l2_weights"), bool(pr.get("fit_intercept")))
                 if pr.get("B") is not None and pr["weight_function"] != "ehrm":
                     raise ValueError(f"Unrecognized weight_function '{pr['weight_function']}'! Options: ['ehrm']")
                 if pr["weight_function"] == "ehrm" and pr.get("B") is None:
@@ -316,7 +361,8 @@ class ADMMgroup:
                                      storage=storage, device=device, share_data=share, **kw)
             else:
                 s = ADMMmethod(X, yk, pr["weight_function"], pr["loss"], max_iter=max_iter, tol=tol, storage=storage,
-                               device=device, share_data=share, **kw)
+                               device=device, share_data=share, l1_weights=pr.get("l1_weights"),
+                               l2_weights=pr.get("l2_weights"), fit_intercept=bool(pr.get("fit_intercept")), **kw)
             self.solvers.append(s)
         self._group = _solver.Group([s._s for s in self.solvers])
         self.store = False
@@ -399,8 +445,10 @@ class OneVsRest:
     GPU (rbl_decide_multi)."""
 
     def __init__(self, X, labels, weight_function="erm", loss="binary_cross_entropy", l2_reg=None, l1_reg=None, B=None,
-                 args=None, storage="f32", device=0, max_iter=200, tol=1e-4):
+                 args=None, storage="f32", device=0, max_iter=200, tol=1e-4, l1_weights=None, l2_weights=None,
+                 fit_intercept=False):
         Xm = _solver._as_matrix(X)
+        self.fit_intercept = bool(fit_intercept)
         lab = np.asarray(labels.detach().cpu().numpy() if hasattr(labels, "detach") else labels).reshape(-1)
         if lab.shape[0] != Xm.shape[0]:
             raise ValueError(f"labels has {lab.shape[0]} entries for {Xm.shape[0]} rows")
@@ -410,8 +458,8 @@ class OneVsRest:
         if self.classes_.size > 64:
             raise ValueError(f"OneVsRest: at most 64 classes in one group, labels holds {self.classes_.size}")
         ys = [np.where(lab == c, 1.0, -1.0) for c in self.classes_]
-        problems = [dict(weight_function=weight_function, loss=loss, l2_reg=l2_reg, l1_reg=l1_reg, B=B, args=args, y=yk)
-                    for yk in ys]
+        problems = [dict(weight_function=weight_function, loss=loss, l2_reg=l2_reg, l1_reg=l1_reg, B=B, args=args, y=yk,
+                         l1_weights=l1_weights, l2_weights=l2_weights, fit_intercept=self.fit_intercept) for yk in ys]
         self._storage, self._device = storage, device
         self.group = ADMMgroup(Xm, ys[0], problems, storage=storage, device=device, max_iter=max_iter, tol=tol)
         self.W = None
@@ -431,6 +479,8 @@ class OneVsRest:
     def predict(self, X_test):
         """class label of every row of X_test: classes_[argmax_k x . w_k] (ties: the first class)"""
         Xt = _solver._as_matrix(X_test)
+        if self.fit_intercept:
+            Xt = _solver.add_intercept_column(Xt)      # W holds the intercepts in its last row
         W = self._current_W()
         if Xt.shape[1] != W.shape[0]:
             raise ValueError(f"X_test has {Xt.shape[1]} features, the model {W.shape[0]}")

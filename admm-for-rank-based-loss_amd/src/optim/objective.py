@@ -69,7 +69,8 @@ class rankbasedObjective:
     """objective.py:39-94.  Holds D = -y*X on the device (own handle, or the solver's)."""
 
     def __init__(self, X, y, weight_function="erm", loss="binary_cross_entropy", l2_reg=None, l1_reg=None,
-                 B=None, n_class=None, args=None, storage="f32", device=0, _shared_solver=None, _share_data=None):
+                 B=None, n_class=None, args=None, storage="f32", device=0, _shared_solver=None, _share_data=None,
+                 _penalty=None):
         _solver.check_problem(weight_function, loss, B, args, need_prox=False)
         if loss == "multinomial_cross_entropy":
             raise ValueError("multinomial_cross_entropy is outside the ADMM hot path (binary losses only)")
@@ -96,6 +97,11 @@ class rankbasedObjective:
                 self._s.set_data(Xm, y)
             elif y_own is not None:
                 self._s.set_labels(y_own)      # labels of its own on the borrowed matrix (rbl_set_labels)
+        # per-coordinate penalties (l1, l2) of the solver (ADMMmethod's l1_weights / l2_weights / fit_intercept): the
+        # regulariser is then evaluated by the library on this handle (rbl_objective), an own handle is given the vectors
+        self._penalty = _penalty
+        if _penalty is not None and _shared_solver is None:
+            self._s.set_penalty(_penalty[0], _penalty[1])
         self._alphas = self._betas = None
 
     def _sig(self):
@@ -118,6 +124,8 @@ class rankbasedObjective:
         """objective.py:71-87 (betas = alphas there, :76, so the EHRM split sums to the same dot)."""
         wv = w.detach().cpu().numpy() if hasattr(w, "detach") else np.asarray(w)
         wv = np.asarray(wv, dtype=np.float64).reshape(-1)
+        if include_reg and self._penalty is not None:
+            return self._s.objective(wv)
         risk = self._s.risk(wv)
         if include_reg:
             risk += _solver.reg_terms(wv, self.l2_reg, self.l1_reg)

@@ -147,6 +147,25 @@ int  rbl_create_shared(const rbl_config* cfg, rbl_solver* owner, rbl_solver** ou
  * RBL_ERR_STATE; a value other than +-1 or a row-sharded handle (n != n_total) is RBL_ERR_INVALID.  Works on
  * objective_only borrowers (a test matrix with per-member test labels). */
 int  rbl_set_labels(rbl_solver* h, const double* y);
+/* Per-coordinate penalties: the regulariser becomes R(w) = 1/2 sum_j (l1[j] |w_j| + l2[j] w_j^2) in place of
+ * reg/2 ||w||_1 or reg/2 ||w||^2 - the elastic net, penalty factors, and coordinates left unpenalised (an intercept:
+ * a column of ones with l1 = l2 = 0).  l1 and l2 hold d host doubles each, NULL = all zeros.  The w-step is then
+ *     min_w 1/2 w'(G + diag(l2)/rho) w - q'w + sum_j kappa_j |w_j|,   kappa_j = l1[j] / (2 rho):
+ * cfg.wstep == RBL_WSTEP_L1 runs the active-set kernel's per-coordinate instance (wstep_form 2; FISTA when the support
+ * outgrows it), where a coordinate with l1[j] = 0 is free - it enters when its gradient is non-zero to rounding, is no
+ * break point of the line search and is never dropped; cfg.wstep == RBL_WSTEP_L2 (use it when every l1[j] = 0) runs CG
+ * on (rho G + diag(l2)) w = rho q (wstep_form 0 or 1; the eigen-decomposition ridge, form 3, needs a multiple of the
+ * identity and is not used).  With some l2[j] = 0 that system is only as definite as G: CG keeps its iteration cap.
+ * rbl_step, rbl_solve, rbl_phase_w, the w-step rbl_phase_finish enqueues ahead, rbl_group_step, rbl_objective(include_reg)
+ * and the logged objective all use the vectors; the z-step, both passes, the residuals and the rho schedule do not see
+ * them.  The initial state is untouched: cfg.reg still sets the starting values.  Both NULL, a negative or non-finite
+ * entry, or a smoothed-l1 handle (RBL_WSTEP_SMOOTH_L1) is RBL_ERR_INVALID; iter > 0 is RBL_ERR_STATE.  Allowed on owners,
+ * borrowers (relabelled ones too), members before they join a group, objective_only handles (so that a logged test
+ * objective carries the same R) and row-sharded handles - every rank must pass the same vectors, the w-step is
+ * replicated.  The vectors live in the handle's own arena (2 ld doubles). */
+int  rbl_set_penalty(rbl_solver* h, const double* l1, const double* l2);
+/* the vectors of rbl_set_penalty (d doubles each, either may be NULL); *is_set = 0 and zeros when none were set */
+int  rbl_get_penalty(rbl_solver* h, double* l1, double* l2, int* is_set);
 /* run the library's kernels on this hipStream_t: NULL is the (legacy) default stream,
  * (void*)-1 goes back to the handle's own non-blocking stream (the initial setting) */
 int  rbl_set_stream(rbl_solver* h, void* hip_stream);
@@ -422,6 +441,10 @@ int  rbl_k_gram(int storage, int64_t n, int64_t d, const double* D, double* G);
 /* w-steps in Gram space: lasso / ridge / smoothed-l1 */
 int  rbl_k_wstep(int wstep, int64_t d, const double* G, const double* q, double rho, double reg,
                  double smooth_t, const double* w0, double tol, double* w_out, int* iters);
+/* the w-step with per-coordinate penalties (rbl_set_penalty) over host buffers: the lasso form when any l1[j] > 0,
+ * else CG; *form as rbl_stats.wstep_form reports it (2 active-set kernel, 0 / 1 CG or FISTA) */
+int  rbl_k_wstep_pen(int64_t d, const double* G, const double* q, double rho, const double* l1, const double* l2,
+                     const double* w0, double tol, double* w_out, int* iters, int* form);
 /* sigma generators (src/optim/objective.py:97-164) */
 int  rbl_k_weights(int weight_function, int64_t n, const double* args, int n_args,
                    double* alphas, double* betas);
