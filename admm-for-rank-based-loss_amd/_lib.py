@@ -166,6 +166,7 @@ SIGNATURES = {
     "rbl_profile_sampling": (C.c_int, [_P, C.c_int]),
     "rbl_k_prox": (C.c_int, [C.c_int, C.c_int64, _P, C.c_double, _P, _P]),
     "rbl_k_sort": (C.c_int, [C.c_int64, _P, _P, _P]),
+    "rbl_k_sort32": (C.c_int, [C.c_int64, _P, C.c_uint32, _P, _P, C.POINTER(C.c_int)]),
     "rbl_k_pav": (C.c_int, [C.c_int, C.c_int64, _P, C.c_double, _P, _P, _I64]),
     "rbl_k_pav_ehrm": (C.c_int, [C.c_int64, _P, _P, C.c_double, C.c_double, _P, C.c_int, _P, C.POINTER(C.c_int)]),
     "rbl_k_pav_seq": (C.c_int, [C.c_int, C.c_int64, _P, _P, C.c_double, C.c_double, C.c_int, _P, C.c_int, _P, _P, _P]),
@@ -276,6 +277,19 @@ def k_sort(keys):
     perm = np.empty(keys.size, dtype=np.uint32)
     check(load().rbl_k_sort(keys.size, ptr(keys), ptr(out), ptr(perm)))
     return out, perm
+
+
+def k_sort32(m, idx_off=0):
+    """The z-step's sort with 32-bit keys (include/rbl.h: rbl_k_sort32).  Returns (m_sorted, ids, flag): ids =
+    idx_off + row, in (m, row) order; flag = 1: a run of more than 32 equal keys - m_sorted and ids are meaningless."""
+    m = f64(m).reshape(-1)
+    if not 0 <= int(idx_off) <= (1 << 32) - m.size:
+        raise ValueError(f"idx_off must be in [0, 2^32 - n], got {idx_off}")
+    out = np.empty_like(m)
+    ids = np.empty(m.size, dtype=np.uint32)
+    flag = C.c_int(0)
+    check(load().rbl_k_sort32(m.size, ptr(m), int(idx_off), ptr(out), ptr(ids), C.byref(flag)))
+    return out, ids, flag.value
 
 
 def k_pav(loss, sigma, rho, m_sorted):

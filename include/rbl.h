@@ -409,6 +409,14 @@ int  rbl_profile_sampling(rbl_solver* h, int every);
 int  rbl_k_prox(int loss, int64_t n, const double* sigma, double rho, const double* m, double* out);
 /* stable ascending sort of float64 keys with index payload (algorithms.py:92-93) */
 int  rbl_k_sort(int64_t n, const double* keys, double* sorted_keys, uint32_t* perm);
+/* the z-step's sort with 32-bit keys, exactly its launches: range of m -> fixed-point keys on [min m, max m] -> four
+ * radix passes -> fix-up of the runs of equal keys into (m, row id) order.  ids[p] = idx_off + row at sorted position
+ * p, m_sorted[p] = its m (the input's bits); *flag = 1: a run of more than 32 equal keys - m_sorted and ids are then
+ * meaningless (a solve redoes that z-step with rbl_k_sort's 64-bit keys).  n + idx_off <= 2^32.
+ * Signed zeros: the fix-up compares m numerically, so -0.0 and +0.0 tie and keep their row order (as NumPy's stable
+ * argsort does); rbl_k_sort orders the bit patterns and puts every -0.0 before every +0.0.  The z-step's result does
+ * not depend on it: both zeros are the same m.  NaN in m is not supported (a solve has diverged by then). */
+int  rbl_k_sort32(int64_t n, const double* m, uint32_t idx_off, double* m_sorted, uint32_t* ids, int* flag);
 /* generalised PAV on sorted m (src/util/pav.py:93-178); loss: any RBL_LOSS_* */
 int  rbl_k_pav(int loss, int64_t n, const double* sigma, double rho, const double* m_sorted,
                double* out, int64_t* n_merges);
