@@ -464,6 +464,16 @@ class Solver:
         _lib.check(self.lib.rbl_zbd_apply(self._h, C.byref(st)))
         return st.value
 
+    def zband_status(self):
+        """status word of the last sort-free z-step (include/rbl.h: rbl_zband_status); 0 = certified, -1 = none yet"""
+        return self.zband_status_split()[0]
+
+    def zband_status_split(self):
+        """-> (status word, pooled blocks of that z-step whose value comes from bracket-split sums; -1 = none yet)"""
+        st, split = C.c_int(0), C.c_int(0)
+        _lib.check(self.lib.rbl_zband_status(self._h, C.byref(st), C.byref(split)))
+        return st.value, split.value
+
     def pending_reduce(self):
         m = C.c_int(0)
         _lib.check(self.lib.rbl_pending_reduce(self._h, C.byref(m)))

@@ -500,6 +500,8 @@ struct ZbState {                         // device scratch of one z-step
     double frozen[ZB_MAX_CLUSTERS][4];    // outside the bracket for certain: top count / sum m, bottom count / sum m
     double und[ZB_MAX_CLUSTERS];          // elements whose membership changes inside the bracket
     int gcount[ZB_MAX_CLUSTERS];          // gathered so far
+    double blk[ZB_MAX_CLUSTERS][2];       // the certified block: elements of band L / of band R in it
+    int canon[ZB_MAX_CLUSTERS];           // x[k] comes from sums over the certified block alone (k_zb_canon), or is an exact -1
 };
 size_t zb_hist_bytes();
 size_t zb_partials_bytes();

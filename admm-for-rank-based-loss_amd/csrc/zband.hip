@@ -16,13 +16,14 @@
 //   2. the root of psi: passes that evaluate the block sums for 16 candidate values at once (thresholds in m-space,
 //      u_i > x  <=>  m_i > x + (s/rho) l'(x)); the first pass packs its candidates around a prediction from the last
 //      three block values, the others shrink the bracket 15x each; once at most 2048 elements are undecided they are
-//      gathered and one workgroup settles the block exactly (its value is pav.py's own formula);
+//      gathered and one workgroup settles the block exactly (its value is pav.py's own formula); one more pass sums
+//      the certified block alone, so that its value does not depend on the brackets that led to it (k_zb_canon);
 //   3. one element-wise pass.
 // All sums are accumulated per thread in a fixed element order and reduced in a fixed order: bit-reproducible.
 // Whatever the fast path cannot certify (keys tied across a band edge, a block that swallows a whole band or stays
 // on one side of a single-rank band, an unresolved bracket) is REPORTED through a pinned status word; the caller
-// (api.hip: zb_resolve) then runs the sort + merge-tree PAV for that iteration.  6M rows, superquantile: ~0.35 ms
-// instead of ~1.1 ms for sort + PAV + unsort.  The same select gives the logged objective sum_k sigma_k loss(v_(k))
+// (api.hip: zb_resolve) then runs the sort + merge-tree PAV for that iteration.  6M rows, superquantile: ~0.33 ms
+// of kernel time (0.05 of it the pass behind k_zb_canon) instead of ~1.1 ms for sort + PAV + unsort.  The same select gives the logged objective sum_k sigma_k loss(v_(k))
 // without sorting v (k_zb_risk).  CPU restatement of the structure and of the certification rules: oracle/zband.py.
 #include "rbl_internal.h"
 #include "device_math.h"
@@ -52,6 +53,7 @@ __global__ void k_zb_init(ZbState* __restrict__ st, ZbConfig cfg, u32* __restric
         st->x[t] = 0.0;
         st->und[t] = 1e300;
         st->gcount[t] = 0;
+        st->canon[t] = 0;
     }
     if (t == 0) {
         st->ngroups = 1;
@@ -376,6 +378,8 @@ __device__ void zb_accept(ZbState* st, const ZbConfig& cfg, int k, double rho, d
         return;
     }
     st->x[k] = x;
+    st->blk[k][0] = cT;
+    st->blk[k][1] = cB;
     st->xh[k][2] = st->xh[k][1];
     st->xh[k][1] = st->xh[k][0];
     st->xh[k][0] = x;
@@ -393,11 +397,14 @@ __device__ inline void zb_band_keys(const ZbState* st, const ZbConfig& cfg, int 
 }
 
 // partials[block][4][ZB_C]: sum m / count of the top part of band L (u > x_c), of the bottom part of band R (u < x_c)
+// canon: every candidate is the certified block value st->x[k] - each element of the block falls into the "all
+// candidates" class, so the sums are those of the block in an order that no bracket had a part in (k_zb_canon)
 template <int LOSS>
 __global__ __launch_bounds__(ZB_THREADS) void k_zb_eval(const u64* __restrict__ keys, long long n,
                                                          const ZbState* __restrict__ st, ZbConfig cfg, int k, double rho,
-                                                         double* __restrict__ partials) {
-    if (st->status != ZB_OK || st->done[k] || st->und[k] <= (double)ZB_GCAP) return;
+                                                         double* __restrict__ partials, int canon) {
+    if (st->status != ZB_OK) return;
+    if (canon ? !st->has_block[k] : (st->done[k] || st->und[k] <= (double)ZB_GCAP)) return;
     __shared__ double red[(ZB_THREADS / 64) * 4 * ZB_C];
     const int L = cfg.cl_L[k], R = cfg.cl_R[k];
     u64 Llo, Lhi, Rlo, Rhi;
@@ -408,7 +415,7 @@ __global__ __launch_bounds__(ZB_THREADS) void k_zb_eval(const u64* __restrict__ 
     __shared__ double thT[ZB_C], thB[ZB_C];
     const double sl = cfg.sigma[L] / rho, sr = cfg.sigma[R] / rho;
     if (threadIdx.x < ZB_C) {
-        const double x = st->cand[k][threadIdx.x];
+        const double x = canon ? st->x[k] : st->cand[k][threadIdx.x];
         thT[threadIdx.x] = zb_theta_gt<LOSS>(sl, x);
         thB[threadIdx.x] = zb_theta_lt<LOSS>(sr, x);
     }
@@ -651,6 +658,55 @@ __global__ __launch_bounds__(1024) void k_zb_refine(ZbState* __restrict__ st, Zb
         __threadfence_system();
         *reinterpret_cast<volatile int*>(pin_settled) = dseq;
     }
+}
+
+// The block value as k_zb_refine / k_zb_finish certify it is pav.py's formula on sums that were split between a root
+// pass's frozen part and the gathered elements: the split follows the bracket, the bracket follows the hint, and the
+// last bit of x followed both (the same m gave two values of x, one ulp apart, on one handle).  One more pass sums the
+// certified block alone (k_zb_eval with canon = 1) and this kernel takes x from those sums when they cover the block
+// that was certified (same counts = same elements: both are the upper part of band L and the lower part of band R).
+// A hinge block on the plateau keeps its exact -1.
+template <int LOSS>
+__global__ __launch_bounds__(1024) void k_zb_canon(ZbState* __restrict__ st, ZbConfig cfg, int k, double rho,
+                                                    const double* __restrict__ partials, int nblocks) {
+    if (st->status != ZB_OK || !st->has_block[k]) return;
+    __shared__ double tot[4 * ZB_C];
+    __shared__ double tmp[4 * ZB_C * 16];
+    const int v = threadIdx.x & 63, part = threadIdx.x >> 6;
+    double s = 0.0;
+#pragma unroll 4
+    for (int b = part; b < nblocks; b += 16) s += partials[(size_t)b * 4 * ZB_C + v];
+    tmp[part * 64 + v] = s;
+    __syncthreads();
+    if (part == 0) {
+        double a = 0.0;
+        for (int p = 0; p < 16; ++p) a += tmp[p * 64 + v];
+        tot[v] = a;
+    }
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    const double mT = tot[0], cT = tot[ZB_C], mB = tot[2 * ZB_C], cB = tot[3 * ZB_C];
+    if (LOSS == 1 && st->x[k] == -1.0) {   // the plateau's value is exact whatever the sums are
+        st->canon[k] = 1;
+        return;
+    }
+    // (k_zb_finish compares prox values, this pass compares m with a threshold: an element within rounding of the edge
+    // of the block may be counted differently - the certified value stays, and k_zb_apply reports the block as split)
+    if (cT != st->blk[k][0] || cB != st->blk[k][1]) return;
+    const int L = cfg.cl_L[k], R = cfg.cl_R[k];
+    double At = 0.0, Mt = 0.0, nt = 0.0;
+    for (int j = L + 1; j < R; ++j) {
+        At += cfg.sigma[j];
+        Mt += rbl::unflip_key(st->key[cfg.first_t[j]]);
+        nt += 1.0;
+    }
+    const double cnt = cT + nt + cB;
+    if (!(cnt > 0.0)) return;
+    const double x = zb_block_value<LOSS>(cfg.sigma[L] * cT + At + cfg.sigma[R] * cB, mT + Mt + mB, cnt, rho);
+    if (!(x == x)) return;
+    st->x[k] = x;   // the same formula on the same elements as the certified value: no tolerance between the two
+    st->xh[k][0] = x;
+    st->canon[k] = 1;
 }
 
 // ------------------------------------------------------------------------------------------ gather + finish
@@ -989,9 +1045,10 @@ __global__ __launch_bounds__(ZB_THREADS) void k_zb_apply(const double* __restric
             lo[j] = -inf;
             hi[j] = inf;
         }
-        int blocks = 0;
+        int blocks = 0, split = 0;
         for (int k = 0; k < cfg.nclusters; ++k)
             if (st->has_block[k]) {
+                split += st->canon[k] ? 0 : 1;
                 const double x = st->x[k];
                 hi[cfg.cl_L[k]] = x;
                 lo[cfg.cl_R[k]] = x;
@@ -1009,6 +1066,7 @@ __global__ __launch_bounds__(ZB_THREADS) void k_zb_apply(const double* __restric
         if (blockIdx.x == 0) {
             if (counters) counters[0] = (u32)blocks;
             __threadfence_system();
+            reinterpret_cast<volatile int*>(pin)[2] = split;   // blocks whose value comes from bracket-split sums
             reinterpret_cast<volatile int*>(pin)[1] = s;
             __threadfence_system();
             reinterpret_cast<volatile int*>(pin)[0] = seq;   // written last: the host polls this word
@@ -1105,13 +1163,16 @@ int launch_zband(int loss, const ZbConfig& cfg, int64_t n, double rho, const u64
             const int last = r == ZB_ROOT_PASSES - 1;
             RBL_LOSS_SWITCH(loss, L_,
                             hipLaunchKernelGGL(k_zb_eval<L_>, dim3(hb), dim3(ZB_THREADS), 0, s, keys, (long long)n, (const ZbState*)st,
-                                               cfg, k, rho, partials);
+                                               cfg, k, rho, partials, 0);
                             hipLaunchKernelGGL(k_zb_refine<L_>, dim3(1), dim3(1024), 0, s, st, cfg, k, rho, (const double*)partials, hb,
                                                last, (double*)nullptr, (const double*)nullptr));
         }
         RBL_LOSS_SWITCH(loss, L_,
                         hipLaunchKernelGGL(k_zb_gather<L_>, dim3(hb), dim3(ZB_THREADS), 0, s, keys, (long long)n, st, cfg, k, rho, glist);
-                        hipLaunchKernelGGL(k_zb_finish<L_>, dim3(1), dim3(1024), 0, s, st, cfg, k, rho, (const double*)glist));
+                        hipLaunchKernelGGL(k_zb_finish<L_>, dim3(1), dim3(1024), 0, s, st, cfg, k, rho, (const double*)glist);
+                        hipLaunchKernelGGL(k_zb_eval<L_>, dim3(hb), dim3(ZB_THREADS), 0, s, keys, (long long)n, (const ZbState*)st, cfg,
+                                           k, rho, partials, 1);
+                        hipLaunchKernelGGL(k_zb_canon<L_>, dim3(1), dim3(1024), 0, s, st, cfg, k, rho, (const double*)partials, hb));
     }
     const int64_t ab = (n + ZB_THREADS * 8 - 1) / (ZB_THREADS * 8);
     const unsigned ag = (unsigned)(ab < 1 ? 1 : (ab > 2048 ? 2048 : ab));
@@ -1164,7 +1225,7 @@ int launch_zbd_eval(int loss, const ZbConfig& cfg, int64_t n, const u64* keys, Z
     const int hb = zb_eval_blocks(n);
     RBL_LOSS_SWITCH(loss, L_,
                     hipLaunchKernelGGL(k_zb_eval<L_>, dim3(hb), dim3(ZB_THREADS), 0, s, keys, (long long)n, (const ZbState*)st, cfg, k, rho,
-                                       partials);
+                                       partials, 0);
                     hipLaunchKernelGGL(k_zb_refine<L_>, dim3(1), dim3(1024), 0, s, st, cfg, k, rho, (const double*)partials, hb, 0, tot,
                                        (const double*)nullptr));
     RBL_HIP(hipGetLastError());

@@ -374,6 +374,17 @@ int  rbl_zbd_root_passes(void);
 int  rbl_zbd_gather(rbl_solver* h, int k);
 int  rbl_zbd_finish(rbl_solver* h, int k, const void* packs_all_dev, int world);
 int  rbl_zbd_apply(rbl_solver* h, int* status);
+/* read-only (tests, diagnostics): the status word of this handle's last sort-free z-step, single handle or sharded -
+ * 0 certified, 1 keys tied across a band edge, 2 select failed, 3 too many key prefixes, 4 bracket lost, 5 unresolved
+ * after the root passes, 6 / 7 a block swallows the inner band below / above, 8 a block on one side of a single-rank
+ * band, 9 two blocks meet; -1: the handle has not run one.  A verdict still pending is settled first, as by any other
+ * entry that looks at the state (rbl_stats.zband tells the path, this tells why a step was redone).  split (may be
+ * NULL): how many pooled blocks of that step took their value from sums that were split by the root bracket (the last
+ * bit of such a value depends on the hint of the steps before) and not from the pass over the certified block alone;
+ * 0 on a certified single-handle step unless an element sits within rounding of the block's edge, every block on the
+ * sharded path, which has no such pass.  It changes nothing in the iterate, but like every entry it is a call between
+ * phases: a w-step computed ahead of time is discarded (w_prev is copied back, the stream is synchronised). */
+int  rbl_zband_status(rbl_solver* h, int* status, int* split);
 
 /* RBL_BUF_Q is the whole exchange buffer [q (ld) | D^T lambda seed (ld) | ||z||^2 | primal^2 |
  * sum loss]; RBL_BUF_RED is its 2-double tail.  After rbl_phase_q and after rbl_phase_dual this
