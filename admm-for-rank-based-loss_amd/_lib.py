@@ -17,6 +17,12 @@ WEIGHT = {"erm": 0, "extremile": 1, "superquantile": 2, "esrm": 3, "aorr": 4, "a
 WSTEP_L1, WSTEP_L2, WSTEP_SMOOTH_L1 = 1, 2, 3
 STORAGE = {"f32": 0, "float32": 0, "f64": 1, "float64": 1, "fp16": 2, "float16": 2}
 _STORAGE_DTYPE = {0: np.float32, 1: np.float64, 2: np.float16}
+# rbl_set_data_from: element type of the caller's X, where it lives, column scaling, flags
+DTYPE_F64, DTYPE_F32, DTYPE_F16 = 0, 1, 2
+SOURCE_DTYPE = {np.dtype(np.float64): DTYPE_F64, np.dtype(np.float32): DTYPE_F32, np.dtype(np.float16): DTYPE_F16}
+MEM_HOST, MEM_DEVICE = 0, 1
+SCALING = {"none": 0, "fit": 1, "apply": 2}
+DATA_ONES_COLUMN = 1
 
 
 def storage_ld(d, storage):
@@ -48,6 +54,7 @@ BUF_M, BUF_Q, BUF_RED, BUF_G, BUF_V, BUF_Z, BUF_LAM, BUF_W, BUF_COLSTATS = range
  BUF_ZD_ZU, BUF_ZD_COUNTS) = range(16, 26)
 BUF_ZB_HIST, BUF_ZB_TOT, BUF_ZB_PACK = 26, 27, 28
 KERNEL_GEMV, KERNEL_GEMVT, KERNEL_SWEEP_ERM = 0, 1, 2
+KERNEL_SRC_STATS, KERNEL_SRC_FORM = 3, 4      # the two passes of the last rbl_set_data_from
 
 
 class RblConfig(C.Structure):
@@ -108,6 +115,9 @@ SIGNATURES = {
     "rbl_group_counters": (C.c_int, [_P, C.POINTER(C.c_int), _I64, _I64, _I64]),
     "rbl_set_stream": (C.c_int, [_P, _P]),
     "rbl_set_data": (C.c_int, [_P, _P, _P, C.c_int64]),
+    "rbl_set_data_from": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int64, _P, C.c_int, C.c_int]),
+    "rbl_set_scaling": (C.c_int, [_P, _P, _P]),
+    "rbl_get_scaling": (C.c_int, [_P, _P, _P, C.POINTER(C.c_int)]),
     "rbl_generate_synthetic": (C.c_int, [_P, C.c_uint64, C.c_double, C.c_double]),
     "rbl_synth_local": (C.c_int, [_P, C.c_uint64, C.c_double, C.c_double]),
     "rbl_synth_finish": (C.c_int, [_P]),

@@ -114,10 +114,95 @@ def add_intercept_column(X):
 
 
 def _as_matrix(X):
+    """X as a C-contiguous float64 host array (the baselines' path, and what as_source falls back to)"""
     X = X.detach().cpu().numpy() if hasattr(X, "detach") else np.asarray(X)
     if X.ndim != 2:
         raise ValueError("X must be a 2-D array")
     return np.ascontiguousarray(X, dtype=np.float64)
+
+
+_SOURCE_TYPES = "float64, float32 and float16"
+
+
+class Source:
+    """A data matrix as rbl_set_data_from takes it: ``ptr`` (integer address), ``dtype`` (_lib.DTYPE_*), ``mem``
+    (_lib.MEM_HOST / MEM_DEVICE), ``ldx`` (row stride in elements), ``shape`` and ``keep`` - the object that owns the
+    memory (the caller's array or tensor itself when it is used in place)."""
+    __slots__ = ("ptr", "dtype", "mem", "ldx", "shape", "keep")
+
+    def __init__(self, ptr, dtype, mem, ldx, shape, keep):
+        self.ptr, self.dtype, self.mem, self.ldx, self.shape, self.keep = int(ptr), dtype, mem, int(ldx), tuple(shape), keep
+
+
+def _row_stride(shape, strides, itemsize):
+    """row stride in elements if the rows are contiguous and the stride a positive multiple of the item size, else None"""
+    n, d = shape
+    if n == 0 or d == 0:
+        return None
+    if d > 1 and strides[1] != itemsize:
+        return None
+    if n == 1:
+        return d
+    if strides[0] <= 0 or strides[0] % itemsize or strides[0] < d * itemsize:
+        return None
+    return strides[0] // itemsize
+
+
+def as_source(X, device=None):
+    """X in the type it has and from where it lives (include/rbl.h: rbl_set_data_from) -> Source.
+
+    No copy for NumPy float64 / float32 / float16 arrays with contiguous rows (a column slice of a wider array is used
+    in place with its row stride), for torch CPU tensors of those types (a view) and for torch tensors on the handle's
+    GPU (``device``: its index; the tensor's current stream is synchronised first).  A tensor on the GPU whose rows are
+    not contiguous (transposed, strided columns) stays there: ``contiguous()`` makes a second copy of it ON THE DEVICE,
+    in its own type, for the duration of the call - for a tensor of tens of GB pass contiguous rows.  Integer / bool data, Fortran
+    order, negative strides and lists are converted to a C-contiguous float64 host array.  A tensor on another device,
+    or of a type the library has no instance for (bfloat16, complex), is a ValueError."""
+    if isinstance(X, Source):
+        return X
+    if hasattr(X, "detach") and hasattr(X, "data_ptr"):
+        import torch
+        t = X.detach()
+        if t.dim() != 2:
+            raise ValueError("X must be a 2-D array")
+        kinds = {torch.float64: _lib.DTYPE_F64, torch.float32: _lib.DTYPE_F32, torch.float16: _lib.DTYPE_F16}
+        if t.dtype not in kinds and (t.dtype.is_floating_point or t.dtype.is_complex):
+            raise ValueError(f"X has dtype {t.dtype}: the supported element types are {_SOURCE_TYPES}")
+        if t.device.type == "cuda" and t.dtype in kinds:
+            if device is not None and t.device.index != int(device):
+                raise ValueError(f"X lives on {t.device}, the solver on device {int(device)}: move it there (supported "
+                                 f"element types: {_SOURCE_TYPES})")
+            ldx = _row_stride(tuple(t.shape), tuple(st * t.element_size() for st in t.stride()), t.element_size())
+            if ldx is None:
+                t = t.contiguous()          # (a copy on the device: transposed or strided columns)
+                ldx = t.shape[1]
+            torch.cuda.current_stream(t.device).synchronize()      # X's writes are complete before the library reads it
+            return Source(t.data_ptr(), kinds[t.dtype], _lib.MEM_DEVICE, ldx, t.shape, t)
+        if t.device.type not in ("cpu", "cuda"):
+            raise ValueError(f"X lives on {t.device}: host memory or the solver's GPU (element types {_SOURCE_TYPES})")
+        X = t.cpu().numpy()                 # a view of a CPU tensor; integer / bool tensors are converted below
+    A = X if isinstance(X, np.ndarray) else np.asarray(X)
+    if A.ndim != 2:
+        raise ValueError("X must be a 2-D array")
+    if A.dtype.kind == "c":
+        raise ValueError(f"X has dtype {A.dtype}: the supported element types are {_SOURCE_TYPES}")
+    dt = _lib.SOURCE_DTYPE.get(A.dtype) if A.dtype.isnative else None
+    ldx = _row_stride(A.shape, A.strides, A.itemsize) if dt is not None and A.flags["ALIGNED"] else None
+    if ldx is None:
+        A = np.ascontiguousarray(A, dtype=np.float64)
+        dt, ldx = _lib.DTYPE_F64, max(A.shape[1], 1)
+    return Source(A.ctypes.data, dt, _lib.MEM_HOST, ldx, A.shape, A)
+
+
+def as_scaling(mean, scale, d, ones_column=False):
+    """(mean, scale) for d coordinates as float64; with ones_column the vectors of the d - 1 features are accepted and
+    the unscaled column's (0, 1) appended"""
+    mean, scale = (np.ascontiguousarray(np.asarray(v, dtype=np.float64).reshape(-1)) for v in (mean, scale))
+    if ones_column and mean.size == d - 1 and scale.size == d - 1:
+        mean, scale = np.append(mean, 0.0), np.append(scale, 1.0)
+    if mean.size != d or scale.size != d:
+        raise ValueError(f"scaling: mean / scale have {mean.size} / {scale.size} entries for {d} columns")
+    return mean, scale
 
 
 class Solver:
@@ -178,12 +263,42 @@ class Solver:
             pass
 
     # ---------------------------------------------------------------------- data
-    def set_data(self, X, y):
+    def set_data(self, X, y, scaling="none", ones_column=False):
+        """D = -y * X from X as it is (as_source: float64 / float32 / float16, host or this handle's GPU; include/rbl.h:
+        rbl_set_data_from).  scaling: "none", "fit" (standardise the columns on the device, keep the vectors:
+        get_scaling) or "apply" (the vectors of set_scaling).  ones_column: X has d - 1 columns, column d - 1 of D is
+        -y * 1 (the intercept's), never scaled.  Labels are a host float64 vector (a device y is copied, 8 bytes a row)."""
+        if scaling not in _lib.SCALING:
+            raise ValueError(f"scaling must be one of {sorted(_lib.SCALING)}")
+        src = as_source(X, self.cfg.device)
+        y = _as_labels(y, src.shape[0])
+        shape = (src.shape[0], src.shape[1] + (1 if ones_column else 0))
+        if shape != (self.n, self.d):
+            raise ValueError(f"X is {shape}, expected {(self.n, self.d)}")
+        _lib.check(self.lib.rbl_set_data_from(self._h, C.c_void_p(src.ptr), src.dtype, src.mem, src.ldx, _lib.ptr(y),
+                                              _lib.SCALING[scaling], _lib.DATA_ONES_COLUMN if ones_column else 0))
+
+    def set_data_f64(self, X, y):
+        """the float64 host route (include/rbl.h: rbl_set_data): X is converted to a C-contiguous float64 host array"""
         X = _as_matrix(X)
         y = _as_labels(y, X.shape[0])
         if X.shape != (self.n, self.d):
             raise ValueError(f"X is {X.shape}, expected {(self.n, self.d)}")
         _lib.check(self.lib.rbl_set_data(self._h, _lib.ptr(X), _lib.ptr(y), X.shape[1]))
+
+    def set_scaling(self, mean, scale):
+        """the column means / scales scaling="apply" uses (d values each; None, None clears them)"""
+        if mean is None and scale is None:
+            _lib.check(self.lib.rbl_set_scaling(self._h, None, None))
+            return
+        mean, scale = as_scaling(mean, scale, self.d)
+        _lib.check(self.lib.rbl_set_scaling(self._h, _lib.ptr(mean), _lib.ptr(scale)))
+
+    def get_scaling(self):
+        """(mean, scale) of scaling="fit" / set_scaling, or None when the handle has none"""
+        mean, scale, flag = np.empty(self.d), np.empty(self.d), C.c_int(0)
+        _lib.check(self.lib.rbl_get_scaling(self._h, _lib.ptr(mean), _lib.ptr(scale), C.byref(flag)))
+        return (mean, scale) if flag.value else None
 
     def generate_synthetic(self, seed=17, class_sep=1.0, flip_y=0.01):
         _lib.check(self.lib.rbl_generate_synthetic(self._h, int(seed), float(class_sep), float(flip_y)))

@@ -190,6 +190,19 @@ int launch_colstats(int storage, const void* D, int64_t n, int64_t ld, double* s
                     double* sumsq, int num_cu, hipStream_t s);
 int launch_standardize_negy(int storage, void* D, int64_t n, int64_t ld, int64_t d, const double* mean,
                             const double* inv_std, const signed char* ysign, hipStream_t s);
+// typed sources (rbl_set_data_from): X of element type dtype (RBL_DTYPE_*) already on the device, ds source columns.
+// D[row0 + r][j] = round(-y_r x), x = widen(X[r][j]) or, with mean / inv given (device, ld doubles), (widen - mean[j]) *
+// inv[j]; columns ds .. d - 1 are -y_r (the column of ones), the pad zeros.  ysign: the signs of rows row0 .. row0 + rows.
+int launch_form_src(int dtype, int storage, void* D, int64_t ld, int64_t row0, const void* X, int64_t ldx,
+                    const signed char* ysign, int64_t rows, int64_t ds, int64_t d, const double* mean, const double* inv,
+                    int num_cu, hipStream_t s, u64* ovf);
+// shifted column sums sum (x - shift_j), sum (x - shift_j)^2 of row blocks of src_stat_rows() rows -> slab rows blk0 + b
+// (ld doubles each); launch_src_colreduce folds nb slab rows in a fixed order; launch_src_row widens one row
+int64_t src_stat_rows();
+int launch_src_colstats(int dtype, const void* X, int64_t ldx, int64_t rows, int64_t ds, const double* shift, double* slab1,
+                        double* slab2, int64_t ld, int64_t blk0, hipStream_t s);
+int launch_src_colreduce(const double* slab, int64_t nb, int64_t ld, double* out, hipStream_t s);
+int launch_src_row(int dtype, const void* X, int64_t ds, double* out, hipStream_t s);
 
 // ---- elementwise.hip --------------------------------------------------------------------
 // rs (optional, in the launchers below): the sign vector of a handle with labels of its own on a borrowed D

@@ -489,7 +489,266 @@ __global__ void k_standardize_negy(T* __restrict__ D, long long n, long long ld,
     }
 }
 
+// ------------------------------------------------- typed sources (rbl_set_data_from): X as the caller holds it
+// S = double / float / unsigned short (IEEE binary16 bits); widening to double is exact.
+__device__ inline double src_widen(double x) { return x; }
+__device__ inline double src_widen(float x) { return (double)x; }
+__device__ inline double src_widen(unsigned short x) { return (double)(float)__builtin_bit_cast(_Float16, x); }
+
+template <int W> struct SrcDw;   // W dwords loaded at once
+template <> struct SrcDw<1> { typedef unsigned int type; };
+template <> struct SrcDw<2> { typedef unsigned int type __attribute__((ext_vector_type(2))); };
+template <> struct SrcDw<4> { typedef u32x4_t type; };
+// bytes one load instruction of the packet-wise path moves for this pair of types: 16, or the E source elements of one
+// output packet when those are fewer (half -> f32: 8, half -> f64: 4).  Base and row stride must be multiples of it.
+template <typename S, int E> struct SrcLoad {
+    static constexpr int BYTES = E * (int)sizeof(S), UNIT = BYTES < 16 ? BYTES : 16, NL = BYTES / UNIT;
+};
+// the E source elements behind one output packet (read once, non-temporal: X is streamed and far larger than L2 + MALL)
+template <typename S, int E>
+__device__ inline void src_load_vec(const S* __restrict__ p, double* xs) {
+    typedef SrcLoad<S, E> L;
+    typedef typename SrcDw<L::UNIT / 4>::type vec_t;
+    union {
+        vec_t v[L::NL];
+        S e[E];
+    } u;
+#pragma unroll
+    for (int l = 0; l < L::NL; ++l) u.v[l] = __builtin_nontemporal_load(reinterpret_cast<const vec_t*>(p) + l);
+#pragma unroll
+    for (int k = 0; k < E; ++k) xs[k] = src_widen(u.e[k]);
+}
+
+template <typename T> struct StorePkt;   // one 16-byte packet of the padded row, from E fp64 values
+template <> struct StorePkt<double> {
+    static constexpr int E = 2;
+    __device__ static inline void put(double* p, const double* v, u64*, long long) { *reinterpret_cast<double2*>(p) = make_double2(v[0], v[1]); }
+};
+template <> struct StorePkt<float> {
+    static constexpr int E = 4;
+    __device__ static inline void put(float* p, const double* v, u64*, long long) {
+        *reinterpret_cast<float4*>(p) = make_float4((float)v[0], (float)v[1], (float)v[2], (float)v[3]);
+    }
+};
+template <> struct StorePkt<rbl_half> {
+    static constexpr int E = 8;
+    // one rounding from the fp64 value; finite in, infinite out: counted, the first one (smallest row * d + column) kept
+    __device__ static inline void put(rbl_half* p, const double* v, u64* ovf, long long pos0) {
+        u32x4_t w;
+#pragma unroll
+        for (int k = 0; k < 8; k += 2) {
+            const unsigned short lo = f64_to_f16_bits(v[k]), hi = f64_to_f16_bits(v[k + 1]);
+            if (f16_bits_inf(lo) && v[k] - v[k] == 0.0) {
+                atomicAdd(&ovf[0], 1ull);
+                atomicMin(&ovf[1], (u64)(pos0 + k));
+            }
+            if (f16_bits_inf(hi) && v[k + 1] - v[k + 1] == 0.0) {
+                atomicAdd(&ovf[0], 1ull);
+                atomicMin(&ovf[1], (u64)(pos0 + k + 1));
+            }
+            w[k >> 1] = (unsigned)lo | ((unsigned)hi << 16);
+        }
+        *reinterpret_cast<u32x4_t*>(p) = w;
+    }
+};
+
+// D[row0 + r][j] = round_to_storage(-y_r * x)  with x = widen(X[r][j]) (SC = false) or (widen(X[r][j]) - mean[j]) * inv[j]
+// (SC = true, the arithmetic of k_standardize_negy formed straight from the source: one rounding).  Columns ds <= j < d
+// (the column of ones, ds = d - 1) are -y_r * 1, columns >= d the zero pad.  1 << tpr_log threads share a row, a thread
+// owns whole 16-byte packets of the padded row and reads the row's sign once; rows are taken in a grid-stride loop and
+// every index is 64-bit (n * ld exceeds 2^32 at the project's sizes).  VEC: the source packets are read with
+// SrcLoad::UNIT-byte loads (base and row stride allow it); a packet that reaches beyond column ds, and every packet
+// when VEC is false (d = 1001 in fp32, a sliced tensor), is read element by element.
+template <typename S, typename T, bool SC, bool VEC>
+__global__ __launch_bounds__(256) void k_form_src(T* __restrict__ D, long long ld, long long row0, const S* __restrict__ X,
+                                                   long long ldx, const signed char* __restrict__ ysign, long long rows,
+                                                   long long ds, long long d, const double* __restrict__ mean,
+                                                   const double* __restrict__ inv, int tpr_log, u64* ovf) {
+    constexpr int E = StorePkt<T>::E;
+    const int tpr = 1 << tpr_log, sub = (int)threadIdx.x & (tpr - 1), rsub = (int)threadIdx.x >> tpr_log;
+    const long long rpb = 256 >> tpr_log, PK = ld / E;
+    // U rows per thread and step: their loads are issued together, the packet's means / inverse scales are read once for
+    // the U rows, then the rows are converted and stored (profiles/upload_sources.json: against one row per step, "*_one_row"
+    // there, 14.5 -> 11.4 ms with scaling and 11.0 -> 10.8 ms without at 6 000 000 x 1000 fp32)
+    constexpr int U = E == 8 ? 2 : 4;
+    const long long rstep = (long long)gridDim.x * rpb;
+    for (long long rb = (long long)blockIdx.x * rpb + rsub; rb < rows; rb += rstep * U) {
+        double ny[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const long long r = rb + u * rstep;
+            ny[u] = r < rows ? -(double)ysign[r] : 0.0;
+        }
+        for (long long k = sub; k < PK; k += tpr) {
+            const long long j0 = k * E;
+            double v[U][E];
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const long long r = rb + u * rstep;
+                if (r >= rows) continue;
+                const S* __restrict__ xr = X + r * ldx;
+                if (VEC && j0 + E <= ds) {
+                    src_load_vec<S, E>(xr + j0, v[u]);
+                } else {
+#pragma unroll
+                    for (int e = 0; e < E; ++e) v[u][e] = (j0 + e < ds) ? src_widen(xr[j0 + e]) : 0.0;
+                }
+            }
+            double mj[SC ? E : 1], ij[SC ? E : 1];   // the packet's means and inverse scales, once for the U rows
+            if (SC) {
+#pragma unroll
+                for (int e = 0; e < E; ++e) {
+                    mj[e] = (j0 + e < ds) ? mean[j0 + e] : 0.0;
+                    ij[e] = (j0 + e < ds) ? inv[j0 + e] : 1.0;
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const long long r = rb + u * rstep;
+                if (r >= rows) continue;
+#pragma unroll
+                for (int e = 0; e < E; ++e) {
+                    const long long j = j0 + e;
+                    if (j < ds) {
+                        double x = v[u][e];
+                        if (SC) x = (x - mj[e]) * ij[e];
+                        v[u][e] = ny[u] * x;
+                    } else {
+                        v[u][e] = (j < d) ? ny[u] * 1.0 : 0.0;
+                    }
+                }
+                // (fp16 storage: the pad and the ones never overflow, so pos0 + e only ever names a column < d)
+                StorePkt<T>::put(D + (row0 + r) * ld + j0, v[u], ovf, (row0 + r) * d + j0);
+            }
+        }
+    }
+}
+
+// Shifted column sums of a typed source, in an order fixed by the row count alone: rows are cut into blocks of
+// SRC_STAT_ROWS; one thread per (block, column) adds s1 += x - shift, s2 += (x - shift)^2 in row order; the blocks' sums
+// go to slab rows blk0 + b and are folded by k_colreduce (a fixed tree over the block index).  Neither the grid nor the
+// chunks a host source arrives in (whole row blocks) change a bit of the result.
+constexpr int SRC_STAT_ROWS = 1024;
+template <typename S>
+__global__ __launch_bounds__(256) void k_src_colstats(const S* __restrict__ X, long long ldx, long long rows, long long ds,
+                                                       const double* __restrict__ shift, double* __restrict__ slab1,
+                                                       double* __restrict__ slab2, long long ld, long long blk0) {
+    const long long j = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (j >= ds) return;
+    const double c = shift[j];
+    const long long nb = (rows + SRC_STAT_ROWS - 1) / SRC_STAT_ROWS;
+    for (long long b = blockIdx.y; b < nb; b += gridDim.y) {
+        const long long r0 = b * SRC_STAT_ROWS;
+        const long long r1 = r0 + SRC_STAT_ROWS < rows ? r0 + SRC_STAT_ROWS : rows;
+        double s1 = 0.0, s2 = 0.0;
+        long long r = r0;
+        for (; r + 8 <= r1; r += 8) {   // eight loads in flight, added in row order
+            S x[8];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) x[u] = __builtin_nontemporal_load(X + (r + u) * ldx + j);
+#pragma unroll
+            for (int u = 0; u < 8; ++u) {
+                const double dl = src_widen(x[u]) - c;
+                s1 += dl;
+                s2 += dl * dl;
+            }
+        }
+        for (; r < r1; ++r) {
+            const double dl = src_widen(X[r * ldx + j]) - c;
+            s1 += dl;
+            s2 += dl * dl;
+        }
+        slab1[(blk0 + b) * ld + j] = s1;
+        slab2[(blk0 + b) * ld + j] = s2;
+    }
+}
+template <typename S>
+__global__ void k_src_row(const S* __restrict__ X, long long ds, double* __restrict__ out) {
+    const long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j < ds) out[j] = src_widen(X[j]);
+}
+
+template <typename S, typename T>
+int form_src_T(void* D, long long ld, long long row0, const void* X, long long ldx, const signed char* ysign, long long rows,
+               long long ds, long long d, const double* mean, const double* inv, int num_cu, hipStream_t s, u64* ovf) {
+    constexpr int E = StorePkt<T>::E;
+    const long long PK = ld / E;
+    int tpr_log = 0;
+    while ((1LL << tpr_log) < PK && tpr_log < 8) ++tpr_log;
+    const long long rpb = 256 >> tpr_log;
+    long long grid = (rows + rpb - 1) / rpb;
+    if (grid > (long long)num_cu * 32) grid = (long long)num_cu * 32;
+    const size_t unit = SrcLoad<S, E>::UNIT;
+    const bool vec = ((size_t)(uintptr_t)X % unit == 0) && (((size_t)ldx * sizeof(S)) % unit == 0);
+    const bool sc = mean != nullptr;
+#define RBL_FORM_SRC(SC_, VEC_)                                                                                          \
+    hipLaunchKernelGGL((k_form_src<S, T, SC_, VEC_>), dim3((unsigned)grid), dim3(256), 0, s, (T*)D, ld, row0, (const S*)X, \
+                       ldx, ysign, rows, ds, d, mean, inv, tpr_log, ovf)
+    if (sc && vec) RBL_FORM_SRC(true, true);
+    else if (sc) RBL_FORM_SRC(true, false);
+    else if (vec) RBL_FORM_SRC(false, true);
+    else RBL_FORM_SRC(false, false);
+#undef RBL_FORM_SRC
+    RBL_HIP(hipGetLastError());
+    return RBL_OK;
+}
+template <typename S>
+int form_src_S(int storage, void* D, long long ld, long long row0, const void* X, long long ldx, const signed char* ysign,
+               long long rows, long long ds, long long d, const double* mean, const double* inv, int num_cu, hipStream_t s,
+               u64* ovf) {
+    if (storage == RBL_STORE_F16)
+        return form_src_T<S, rbl_half>(D, ld, row0, X, ldx, ysign, rows, ds, d, mean, inv, num_cu, s, ovf);
+    if (storage == RBL_STORE_F32)
+        return form_src_T<S, float>(D, ld, row0, X, ldx, ysign, rows, ds, d, mean, inv, num_cu, s, ovf);
+    return form_src_T<S, double>(D, ld, row0, X, ldx, ysign, rows, ds, d, mean, inv, num_cu, s, ovf);
+}
+template <typename S>
+int src_colstats_S(const void* X, long long ldx, long long rows, long long ds, const double* shift, double* slab1,
+                   double* slab2, long long ld, long long blk0, hipStream_t s) {
+    const long long nb = (rows + SRC_STAT_ROWS - 1) / SRC_STAT_ROWS;
+    if (nb <= 0 || ds <= 0) return RBL_OK;
+    dim3 grid((unsigned)((ds + 255) / 256), (unsigned)(nb < 65535 ? nb : 65535));
+    hipLaunchKernelGGL(k_src_colstats<S>, grid, dim3(256), 0, s, (const S*)X, ldx, rows, ds, shift, slab1, slab2, ld, blk0);
+    RBL_HIP(hipGetLastError());
+    return RBL_OK;
+}
+
 }  // namespace
+
+int64_t src_stat_rows() { return SRC_STAT_ROWS; }
+
+int launch_form_src(int dtype, int storage, void* D, int64_t ld, int64_t row0, const void* X, int64_t ldx,
+                    const signed char* ysign, int64_t rows, int64_t ds, int64_t d, const double* mean, const double* inv,
+                    int num_cu, hipStream_t s, u64* ovf) {
+    if (rows <= 0) return RBL_OK;
+    if (dtype == RBL_DTYPE_F16)
+        return form_src_S<unsigned short>(storage, D, ld, row0, X, ldx, ysign, rows, ds, d, mean, inv, num_cu, s, ovf);
+    if (dtype == RBL_DTYPE_F32) return form_src_S<float>(storage, D, ld, row0, X, ldx, ysign, rows, ds, d, mean, inv, num_cu, s, ovf);
+    return form_src_S<double>(storage, D, ld, row0, X, ldx, ysign, rows, ds, d, mean, inv, num_cu, s, ovf);
+}
+
+int launch_src_colstats(int dtype, const void* X, int64_t ldx, int64_t rows, int64_t ds, const double* shift, double* slab1,
+                        double* slab2, int64_t ld, int64_t blk0, hipStream_t s) {
+    if (dtype == RBL_DTYPE_F16) return src_colstats_S<unsigned short>(X, ldx, rows, ds, shift, slab1, slab2, ld, blk0, s);
+    if (dtype == RBL_DTYPE_F32) return src_colstats_S<float>(X, ldx, rows, ds, shift, slab1, slab2, ld, blk0, s);
+    return src_colstats_S<double>(X, ldx, rows, ds, shift, slab1, slab2, ld, blk0, s);
+}
+
+int launch_src_colreduce(const double* slab, int64_t nb, int64_t ld, double* out, hipStream_t s) {
+    hipLaunchKernelGGL(k_colreduce, dim3((unsigned)((ld + 63) / 64)), dim3(1024), 0, s, slab, (int)nb, (long long)ld, out);
+    RBL_HIP(hipGetLastError());
+    return RBL_OK;
+}
+
+int launch_src_row(int dtype, const void* X, int64_t ds, double* out, hipStream_t s) {
+    if (ds <= 0) return RBL_OK;
+    const unsigned grid = (unsigned)((ds + 255) / 256);
+    if (dtype == RBL_DTYPE_F16) hipLaunchKernelGGL(k_src_row<unsigned short>, dim3(grid), dim3(256), 0, s, (const unsigned short*)X, (long long)ds, out);
+    else if (dtype == RBL_DTYPE_F32) hipLaunchKernelGGL(k_src_row<float>, dim3(grid), dim3(256), 0, s, (const float*)X, (long long)ds, out);
+    else hipLaunchKernelGGL(k_src_row<double>, dim3(grid), dim3(256), 0, s, (const double*)X, (long long)ds, out);
+    RBL_HIP(hipGetLastError());
+    return RBL_OK;
+}
 
 int gemvt_slab_rows(int num_cu) { return num_cu * GEMVT_BLOCKS_PER_CU; }
 

@@ -10,8 +10,13 @@ directory on ``PYTHONPATH``.  State (w, z, lambda) lives on the GPU; the ``w`` /
 own): ``storage`` ("f32" default | "f64" strict | "fp16" half the bytes of D, data rounded once to float16), ``device``;
 ``l1_weights`` / ``l2_weights`` (a scalar or one value per feature: the regulariser becomes
 1/2 sum_j (l1_j |w_j| + l2_j w_j^2) - elastic net, penalty factors, unpenalised coordinates) and ``fit_intercept``
-(an unpenalised bias: a column of ones is appended to a host copy of X, the solver has d + 1 coordinates, ``coef_`` /
-``intercept_`` split the result while ``w`` and ``final_res()`` keep the full vector).
+(an unpenalised bias: the library forms the column -y * 1 itself, no host copy of X; the solver has d + 1 coordinates,
+``coef_`` / ``intercept_`` split the result while ``w`` and ``final_res()`` keep the full vector); ``standardize`` (the
+columns of X are centred and scaled to unit population variance on the device, one rounding into the storage type;
+``scale_mean_`` / ``scale_scale_`` hold the vectors, every later matrix of the object - the test set of ``start_store`` -
+gets the same scaling, ``unscaled()`` gives the coefficients for raw features).  X is taken as it is: a NumPy array or
+torch CPU tensor of float64 / float32 / float16 is uploaded in its own type without a host copy, a torch tensor on the
+solver's GPU is read where it lives (_solver.as_source).
 """
 import time
 
@@ -37,7 +42,8 @@ _ON_DEVICE = _OnDevice()
 class Optimizer:
     def __init__(self, X, y, weight_function="erm", loss="binary_cross_entropy", l2_reg=None, l1_reg=None,
                  B=None, n_class=None, args=None, w0=None, max_iter=200, tol=1e-4, storage="f32", device=0,
-                 _wstep=None, _smooth_t=1.0, share_data=None, l1_weights=None, l2_weights=None, fit_intercept=False):
+                 _wstep=None, _smooth_t=1.0, share_data=None, l1_weights=None, l2_weights=None, fit_intercept=False,
+                 standardize=False):
         # argument checks in the reference's order (objective first :22, then :55-68)
         _solver.check_problem(weight_function, loss, B, args)
         if l1_reg is None and l2_reg is None and l1_weights is None and l2_weights is None:
@@ -46,14 +52,14 @@ class Optimizer:
             raise ValueError(f"Unrecognized weight_function '{weight_function}'! Options: ['ehrm']")  # :65-68
         if weight_function == "ehrm" and B is None:
             raise ValueError("ehrm needs the reference point B")
-        Xm = _solver._as_matrix(X)
+        src = _solver.as_source(X, device)              # X in its own type, where it lives: no host copy
         # per-coordinate penalties / intercept: validated on the host before any device call; None = the scalar path
-        pen = _solver.resolve_penalty(Xm.shape[1], l1_reg, l2_reg, l1_weights, l2_weights, fit_intercept)
+        pen = _solver.resolve_penalty(src.shape[1], l1_reg, l2_reg, l1_weights, l2_weights, fit_intercept)
         self.fit_intercept = bool(fit_intercept)
-        if self.fit_intercept:
-            Xm = _solver.add_intercept_column(Xm)       # a host copy of X with the column of ones
+        self.standardize = bool(standardize)
         self._pen = pen
-        self.num_row, self.num_feature = Xm.shape                                             # :26-27
+        # (fit_intercept: the library forms the column of ones, RBL_DATA_ONES_COLUMN)
+        self.num_row, self.num_feature = src.shape[0], src.shape[1] + (1 if self.fit_intercept else 0)   # :26-27
         self.reg = pen["reg"] if pen else (l1_reg or l2_reg)                                  # :30
         self.loss = loss                                                                      # :36
         self.tol, self.max_iter = tol, max_iter                                               # :44-45
@@ -74,7 +80,7 @@ class Optimizer:
             if not isinstance(share, _solver.Solver):
                 raise ValueError("share_data must be an ADMMmethod / smoothADMMmethod (or a Solver) on the same (X, y)")
             if (share.n, share.d) != (self.num_row, self.num_feature) or share.n_total != share.n:
-                raise ValueError(f"share_data holds a {(share.n_total, share.d)} problem, X is {Xm.shape}")
+                raise ValueError(f"share_data holds a {(share.n_total, share.d)} problem, X is {(self.num_row, self.num_feature)}")
             if share.cfg.storage != _lib.STORAGE.get(storage, -1) or share.cfg.device != int(device):
                 raise ValueError("share_data was built with another storage type or device")
             if y is not None:
@@ -83,10 +89,21 @@ class Optimizer:
                                  B=B, args=args, smooth_t=_smooth_t, tol=tol, max_iter=max_iter, storage=storage,
                                  device=device, share=share)
         if share is None:
-            self._s.set_data(Xm, y)                                                           # :23 D = -y*X
+            self._s.set_data(src, y, scaling="fit" if self.standardize else "none",
+                             ones_column=self.fit_intercept)                                  # :23 D = -y*X
             self._s.gram()                                                                    # :24 DTD
         elif y_own is not None:
             self._s.set_labels(y_own)
+        # the scaling of the data this solver runs on (its own, or the one of the solver it borrows from)
+        sc = (share if share is not None else self._s).get_scaling() if self.standardize else None
+        if self.standardize and sc is None:
+            raise ValueError("standardize=True, but share_data was built without it")
+        if share is not None and not self.standardize and share.get_scaling() is not None:
+            raise ValueError("standardize=False, but share_data holds standardised data: pass standardize=True")
+        self._scaling = sc
+        nf = src.shape[1]
+        self.scale_mean_ = None if sc is None else sc[0][:nf].copy()
+        self.scale_scale_ = None if sc is None else sc[1][:nf].copy()
         if pen:
             self._s.set_penalty(pen["l1"], pen["l2"])
         if w0 is not None:                                                                    # :39-40
@@ -119,6 +136,16 @@ class Optimizer:
     def intercept_(self):
         """the unpenalised bias (0.0 without fit_intercept)"""
         return float(self.w.reshape(-1)[-1]) if self.fit_intercept else 0.0
+
+    def unscaled(self):
+        """(coef, intercept) for raw features: with standardize the model is x_std . w + b, x_std = (x - mean) / scale,
+        so coef_j = w_j / scale_j and intercept = b - sum_j w_j mean_j / scale_j (b = 0 without fit_intercept).  Without
+        standardize: (coef_, intercept_)."""
+        coef, b = self.coef_, self.intercept_
+        if self._scaling is None:
+            return coef.copy(), b
+        coef = coef / self.scale_scale_
+        return coef, b - float(np.dot(coef, self.scale_mean_))
 
     @property
     def z(self):
@@ -165,10 +192,10 @@ class Optimizer:
     # ---- logging (:77-86) ------------------------------------------------------------------
     def start_store(self, X, y, weight_function="erm", loss="binary_cross_entropy", B=None, l2_reg=None,
                     l1_reg=None, n_class=None, args=None, _share_data=None):
-        if self.fit_intercept:
-            X = _solver.add_intercept_column(_solver._as_matrix(X))
+        # the test matrix as it is, with the training scaling and the library's own column of ones
         self.test_objective = rankbasedObjective(X, y, weight_function, loss, l2_reg, l1_reg, B, n_class, args,
                                                  storage=self._storage, device=self._device, _share_data=_share_data,
+                                                 scaling=self._scaling, _ones_column=self.fit_intercept,
                                                  _penalty=(self._pen["l1"], self._pen["l2"]) if self._pen else None)
         w = self.w
         self._s.profile_kernels(2)     # z_time / w_time below come from HIP events around the phases
@@ -238,11 +265,11 @@ class Optimizer:
 class ADMMmethod(Optimizer):
     def __init__(self, X, y, weight_function="erm", loss="binary_cross_entropy", l2_reg=None, l1_reg=None, B=None,
                  n_class=None, args=None, w0=None, max_iter=200, tol=1e-4, storage="f32", device=0,
-                 l1_weights=None, l2_weights=None, fit_intercept=False, share_data=None):
-        # (share_data stays the trailing keyword; the three before it are meant to be given by name)
+                 l1_weights=None, l2_weights=None, fit_intercept=False, standardize=False, share_data=None):
+        # (share_data stays the trailing keyword; the four before it are meant to be given by name)
         super().__init__(X, y, weight_function, loss, l2_reg, l1_reg, B, n_class, args, w0, max_iter, tol,
                          storage=storage, device=device, share_data=share_data, l1_weights=l1_weights,
-                         l2_weights=l2_weights, fit_intercept=fit_intercept)
+                         l2_weights=l2_weights, fit_intercept=fit_intercept, standardize=standardize)
 
     def start_store(self, X, y, weight_function="erm", loss="binary_cross_entropy", B=None, l2_reg=None,
                     l1_reg=None, n_class=None, args=None):
@@ -262,13 +289,14 @@ class ADMMmethod(Optimizer):
 class smoothADMMmethod(Optimizer):
     def __init__(self, X, y, weight_function="erm", loss="binary_cross_entropy", B=None, l2_reg=None, l1_reg=None,
                  n_class=None, args=None, w0=None, t=1, max_iter=200, tol=1e-4, storage="f32", device=0,
-                 l1_weights=None, l2_weights=None, fit_intercept=False, share_data=None):
+                 l1_weights=None, l2_weights=None, fit_intercept=False, standardize=False, share_data=None):
         if l1_weights is not None or l2_weights is not None or fit_intercept:
             raise ValueError("smoothADMMmethod has no per-coordinate penalties: l1_weights, l2_weights and fit_intercept "
                              "belong to ADMMmethod (the smoothed-l1 w-step smooths one scalar l1 norm)")
         wstep = _lib.WSTEP_SMOOTH_L1 if l1_reg is not None else None
         super().__init__(X, y, weight_function, loss, l2_reg, l1_reg, B, n_class, args, w0, max_iter, tol,
-                         storage=storage, device=device, _wstep=wstep, _smooth_t=float(t), share_data=share_data)
+                         storage=storage, device=device, _wstep=wstep, _smooth_t=float(t), share_data=share_data,
+                         standardize=standardize)
 
     @property
     def t(self):
@@ -306,10 +334,11 @@ class ADMMgroup:
     args, w0``; ``smooth=True`` and ``t=`` make the member a smoothADMMmethod; ``y=`` gives the member labels of its own
     on the shared X - one-vs-rest, multi-label - default: the group's ``y``).  ``solvers`` are ordinary ADMMmethod /
     smoothADMMmethod objects; start_store / main_loop / final_res mirror the single-solver calls and return lists in
-    the order of ``problems``."""
+    the order of ``problems``.  ``standardize=True`` (in every problem, like ``fit_intercept``: one data matrix) standardises
+    the columns of X on the device.  X is taken as it is (_solver.as_source)."""
 
     _KEYS = ("weight_function", "loss", "l2_reg", "l1_reg", "B", "args", "w0", "smooth", "t", "y", "l1_weights",
-             "l2_weights", "fit_intercept")
+             "l2_weights", "fit_intercept", "standardize")
 
     def __init__(self, X, y, problems, storage="f32", device=0, max_iter=200, tol=1e-4):
         if not isinstance(problems, (list, tuple)) or len(problems) == 0:
@@ -317,6 +346,7 @@ class ADMMgroup:
         if len(problems) > 64:
             raise ValueError("ADMMgroup: at most 64 problems in one group")
         self.problems = []
+        X = _solver.as_source(X, device)             # once for all members: no copy, or one conversion
         for k, pr in enumerate(problems):            # every argument error before any device call
             if not isinstance(pr, dict):
                 raise ValueError(f"problem {k}: expected a dict of constructor keywords")
@@ -335,7 +365,9 @@ class ADMMgroup:
                     raise ValueError("smooth=True members have no l1_weights, l2_weights or fit_intercept")
                 if bool(pr.get("fit_intercept")) != bool(problems[0].get("fit_intercept")):
                     raise ValueError("fit_intercept must be the same for every problem of a group (one data matrix)")
-                _solver.resolve_penalty(np.shape(X)[1], pr.get("l1_reg"), pr.get("l2_reg"), pr.get("l1_weights"),
+                if bool(pr.get("standardize")) != bool(problems[0].get("standardize")):
+                    raise ValueError("standardize must be the same for every problem of a group (one data matrix)")
+                _solver.resolve_penalty(X.shape[1], pr.get("l1_reg"), pr.get("l2_reg"), pr.get("l1_weights"),
                                         pr.get("l2_weights"), bool(pr.get("fit_intercept")))
                 if pr.get("B") is not None and pr["weight_function"] != "ehrm":
                     raise ValueError(f"Unrecognized weight_function '{pr['weight_function']}'! Options: ['ehrm']")
@@ -344,7 +376,7 @@ class ADMMgroup:
                 if "t" in pr and not pr.get("smooth"):
                     raise ValueError("t is the smoothing parameter of smooth=True members")
                 if pr.get("y") is not None:
-                    pr["y"] = _solver.as_pm1_labels(pr["y"], np.shape(X)[0])
+                    pr["y"] = _solver.as_pm1_labels(pr["y"], X.shape[0])
             except ValueError as e:
                 raise ValueError(f"problem {k}: {e}") from None
             self.problems.append(pr)
@@ -358,11 +390,12 @@ class ADMMgroup:
             yk = pr["y"] if pr.get("y") is not None else y
             if pr.get("smooth"):
                 s = smoothADMMmethod(X, yk, pr["weight_function"], pr["loss"], t=pr.get("t", 1), max_iter=max_iter, tol=tol,
-                                     storage=storage, device=device, share_data=share, **kw)
+                                     storage=storage, device=device, share_data=share, standardize=bool(pr.get("standardize")), **kw)
             else:
                 s = ADMMmethod(X, yk, pr["weight_function"], pr["loss"], max_iter=max_iter, tol=tol, storage=storage,
                                device=device, share_data=share, l1_weights=pr.get("l1_weights"),
-                               l2_weights=pr.get("l2_weights"), fit_intercept=bool(pr.get("fit_intercept")), **kw)
+                               l2_weights=pr.get("l2_weights"), fit_intercept=bool(pr.get("fit_intercept")),
+                               standardize=bool(pr.get("standardize")), **kw)
             self.solvers.append(s)
         self._group = _solver.Group([s._s for s in self.solvers])
         self.store = False
@@ -379,10 +412,11 @@ class ADMMgroup:
         """test-set objectives of every member (Optimizer.start_store) on ONE uploaded test matrix.  y_test: one label
         array for all members, or a list of K label arrays when the members carry labels of their own."""
         K = len(self.solvers)
+        X_test = _solver.as_source(X_test)           # once for all members (the library checks a tensor's device)
         if isinstance(y_test, (list, tuple)) and len(y_test) > 0 and np.ndim(y_test[0]) >= 1:
             if len(y_test) != K:
                 raise ValueError(f"problem {min(len(y_test), K)}: y_test lists {len(y_test)} label arrays for {K} problems")
-            n_test = _solver._as_matrix(X_test).shape[0]
+            n_test = X_test.shape[0]
             ys = []
             for k, yt in enumerate(y_test):
                 try:
@@ -446,8 +480,8 @@ class OneVsRest:
 
     def __init__(self, X, labels, weight_function="erm", loss="binary_cross_entropy", l2_reg=None, l1_reg=None, B=None,
                  args=None, storage="f32", device=0, max_iter=200, tol=1e-4, l1_weights=None, l2_weights=None,
-                 fit_intercept=False):
-        Xm = _solver._as_matrix(X)
+                 fit_intercept=False, standardize=False):
+        Xm = _solver.as_source(X, device)
         self.fit_intercept = bool(fit_intercept)
         lab = np.asarray(labels.detach().cpu().numpy() if hasattr(labels, "detach") else labels).reshape(-1)
         if lab.shape[0] != Xm.shape[0]:
@@ -459,9 +493,13 @@ class OneVsRest:
             raise ValueError(f"OneVsRest: at most 64 classes in one group, labels holds {self.classes_.size}")
         ys = [np.where(lab == c, 1.0, -1.0) for c in self.classes_]
         problems = [dict(weight_function=weight_function, loss=loss, l2_reg=l2_reg, l1_reg=l1_reg, B=B, args=args, y=yk,
-                         l1_weights=l1_weights, l2_weights=l2_weights, fit_intercept=self.fit_intercept) for yk in ys]
+                         l1_weights=l1_weights, l2_weights=l2_weights, fit_intercept=self.fit_intercept,
+                         standardize=bool(standardize)) for yk in ys]
         self._storage, self._device = storage, device
         self.group = ADMMgroup(Xm, ys[0], problems, storage=storage, device=device, max_iter=max_iter, tol=tol)
+        first = self.group.solvers[0]
+        self._scaling = first._scaling          # the training scaling: predict applies it to its matrix
+        self.scale_mean_, self.scale_scale_ = first.scale_mean_, first.scale_scale_
         self.W = None
         self._test = None      # (objective-only solver holding the last test matrix, that matrix)
 
@@ -478,18 +516,20 @@ class OneVsRest:
 
     def predict(self, X_test):
         """class label of every row of X_test: classes_[argmax_k x . w_k] (ties: the first class)"""
-        Xt = _solver._as_matrix(X_test)
-        if self.fit_intercept:
-            Xt = _solver.add_intercept_column(Xt)      # W holds the intercepts in its last row
+        Xt = _solver.as_source(X_test, self._device)
+        d = Xt.shape[1] + (1 if self.fit_intercept else 0)     # W holds the intercepts in its last row
         W = self._current_W()
-        if Xt.shape[1] != W.shape[0]:
-            raise ValueError(f"X_test has {Xt.shape[1]} features, the model {W.shape[0]}")
+        if d != W.shape[0]:
+            raise ValueError(f"X_test has {d} features, the model {W.shape[0]}")
         if self._test is None or self._test[1] is not X_test:
             if self._test is not None:
                 self._test[0].close()
-            t = _solver.Solver(Xt.shape[0], Xt.shape[1], "erm", "binary_cross_entropy", storage=self._storage,
+            t = _solver.Solver(Xt.shape[0], d, "erm", "binary_cross_entropy", storage=self._storage,
                                device=self._device, objective_only=True)
-            t.set_data(Xt, np.ones(Xt.shape[0]))
+            if self._scaling is not None:
+                t.set_scaling(*self._scaling)
+            t.set_data(Xt, np.ones(Xt.shape[0]), scaling="none" if self._scaling is None else "apply",
+                       ones_column=self.fit_intercept)
             self._test = (t, X_test)
         return self.classes_[self._test[0].decide_multi(np.ascontiguousarray(W.T))]
 

@@ -70,7 +70,7 @@ class rankbasedObjective:
 
     def __init__(self, X, y, weight_function="erm", loss="binary_cross_entropy", l2_reg=None, l1_reg=None,
                  B=None, n_class=None, args=None, storage="f32", device=0, _shared_solver=None, _share_data=None,
-                 _penalty=None):
+                 _penalty=None, scaling=None, _ones_column=False):
         _solver.check_problem(weight_function, loss, B, args, need_prox=False)
         if loss == "multinomial_cross_entropy":
             raise ValueError("multinomial_cross_entropy is outside the ADMM hot path (binary losses only)")
@@ -84,8 +84,10 @@ class rankbasedObjective:
             self._s = _shared_solver
             self.n, self.d = self._s.n_total, self._s.d
         else:
-            Xm = _solver._as_matrix(X)
-            self.n, self.d = Xm.shape
+            # X as it is (_solver.as_source).  scaling: (mean, scale) of a solver (its scale_mean_ / scale_scale_, or
+            # Solver.get_scaling()) - this matrix is standardised with them on the device; _ones_column: the intercept's
+            Xm = _solver.as_source(X, device)
+            self.n, self.d = Xm.shape[0], Xm.shape[1] + (1 if _ones_column else 0)
             # _share_data: another objective on the same (X, y) whose device matrix this one borrows (ADMMgroup)
             share = None if _share_data is None else _share_data._s
             if share is not None and (share.n, share.d) != (self.n, self.d):
@@ -94,7 +96,9 @@ class rankbasedObjective:
             self._s = _solver.Solver(self.n, self.d, weight_function, loss, args=args, B=B, storage=storage,
                                      device=device, objective_only=True, share=share)
             if share is None:
-                self._s.set_data(Xm, y)
+                if scaling is not None:
+                    self._s.set_scaling(*_solver.as_scaling(scaling[0], scaling[1], self.d, _ones_column))
+                self._s.set_data(Xm, y, scaling="none" if scaling is None else "apply", ones_column=_ones_column)
             elif y_own is not None:
                 self._s.set_labels(y_own)      # labels of its own on the borrowed matrix (rbl_set_labels)
         # per-coordinate penalties (l1, l2) of the solver (ADMMmethod's l1_weights / l2_weights / fit_intercept): the

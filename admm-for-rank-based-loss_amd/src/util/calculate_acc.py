@@ -9,17 +9,24 @@ except ImportError:      # package directory on sys.path: imported as ``src.util
     import _solver
 
 
-def calculate_accuracy(w, X_test, y_test, threshold=0.5, loss='binary_cross_entropy'):
+def calculate_accuracy(w, X_test, y_test, threshold=0.5, loss='binary_cross_entropy', scaling=None):
     """Fraction of rows with prediction == label (reference calculate_acc.py:3-19).
     binary_cross_entropy: predict +1 iff sigmoid(x.w) >= threshold.  hinge: the reference sets
     every prediction to +1 (calculate_acc.py:13-15); mirrored as is.  squared_hinge (not a loss of the reference):
-    predict +1 iff x.w >= 0, ``threshold`` is ignored."""
+    predict +1 iff x.w >= 0, ``threshold`` is ignored.  X_test is taken as it is (float64 / float32 / float16, host or
+    GPU 0).  ``scaling``: (mean, scale) of a solver trained with standardize=True (``scale_mean_``, ``scale_scale_``) -
+    X_test is standardised with them on the device; a w with one entry more than X_test has columns carries the
+    intercept last."""
     if loss not in ('binary_cross_entropy', 'hinge', 'squared_hinge'):
         raise ValueError(f"loss '{loss}' is not supported! Options: ['binary_cross_entropy','hinge','squared_hinge']")
-    X = _solver._as_matrix(X_test)
-    s = _solver.Solver(X.shape[0], X.shape[1], "erm", loss, objective_only=True)
+    X = _solver.as_source(X_test, 0)
+    w = np.asarray(w, dtype=np.float64).reshape(-1)
+    ones = scaling is not None and w.size == X.shape[1] + 1
+    s = _solver.Solver(X.shape[0], X.shape[1] + (1 if ones else 0), "erm", loss, objective_only=True)
     try:
-        s.set_data(X, y_test)
-        return s.accuracy(np.asarray(w, dtype=np.float64).reshape(-1), threshold)
+        if scaling is not None:
+            s.set_scaling(*_solver.as_scaling(scaling[0], scaling[1], s.d, ones))
+        s.set_data(X, y_test, scaling="none" if scaling is None else "apply", ones_column=ones)
+        return s.accuracy(w, threshold)
     finally:
         s.close()

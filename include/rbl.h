@@ -175,6 +175,37 @@ int  rbl_set_stream(rbl_solver* h, void* hip_stream);
  * +-inf fails the call with RBL_ERR_INVALID (the message counts them and names the first one); the handle is then
  * without data. */
 int  rbl_set_data(rbl_solver* h, const double* X, const double* y, int64_t ldx);
+/* X in the type it has and from where it lives.  X: n rows of d columns (d - 1 with RBL_DATA_ONES_COLUMN: column d - 1 of
+ * D is then -y * 1, never scaled, reported as mean 0 / scale 1), row stride ldx ELEMENTS, naturally aligned, element type
+ * dtype, in host memory or in memory of the handle's device (checked: anything else is RBL_ERR_INVALID, with a message).
+ * y: n host doubles, +-1.  X is read, never modified and never adopted: the caller may free it when the call returns.
+ *   RBL_SCALE_NONE   D = round_to_storage(-y * widen(X)): bit for bit the D of rbl_set_data on the float64 widening
+ *                    (widening is exact), including the rejection of entries that do not fit RBL_STORE_F16.
+ *   RBL_SCALE_FIT    per column the mean and the population standard deviation (ddof 0; zero variance: 1) of the widened
+ *                    source are formed on the device in fp64, then D = round_to_storage(-y * ((widen(x) - mean) * (1.0 /
+ *                    scale))): one rounding into the storage type.  The vectors stay in the handle (rbl_get_scaling) once
+ *                    the call has succeeded; a call that fails leaves the handle's earlier vectors, if any, as they were.  The
+ *                    sums are shifted by the column's first row and run over fixed blocks of 1024 rows folded in a fixed
+ *                    order: the vectors are bit-identical for a host and a device source and for any chunk size.  A
+ *                    non-finite statistic is RBL_ERR_INVALID (the column is named).  Row-sharded handles (n != n_total):
+ *                    RBL_ERR_INVALID - reduce the column sums in the driver and use RBL_SCALE_APPLY on every rank.
+ *   RBL_SCALE_APPLY  the same formula with the vectors of rbl_set_scaling (none set: RBL_ERR_STATE): test matrices,
+ *                    shards.
+ * A device source is read on the handle's stream (the caller's writes to X must be complete or ordered on the stream given
+ * to rbl_set_stream) and the call synchronises before it returns; with RBL_SCALE_FIT it is read twice (statistics, then
+ * D).  A host source is pinned in place and streamed over PCIe in chunks of 64 MB (RBL_UPLOAD_CHUNK_BYTES in the
+ * environment overrides the size; whole blocks of 1024 rows) in the caller's type - 2, 4 or 8 bytes per entry - and
+ * converted on the device; with RBL_SCALE_FIT it crosses PCIe twice.  Borrowers: RBL_ERR_STATE. */
+enum { RBL_DTYPE_F64 = 0, RBL_DTYPE_F32 = 1, RBL_DTYPE_F16 = 2 };   /* element type of the caller's X (IEEE binary64/32/16) */
+enum { RBL_MEM_HOST = 0, RBL_MEM_DEVICE = 1 };                       /* where X lives; DEVICE = memory of the handle's device */
+enum { RBL_SCALE_NONE = 0, RBL_SCALE_FIT = 1, RBL_SCALE_APPLY = 2 };
+enum { RBL_DATA_ONES_COLUMN = 1 };                                   /* flags */
+int  rbl_set_data_from(rbl_solver* h, const void* X, int dtype, int mem, int64_t ldx /* in elements */,
+                       const double* y /* n host doubles, +-1 */, int scaling, int flags);
+/* the column means and scales RBL_SCALE_APPLY uses: d host doubles each (finite, scale > 0); both NULL clears them */
+int  rbl_set_scaling(rbl_solver* h, const double* mean, const double* scale);
+/* the vectors of RBL_SCALE_FIT / rbl_set_scaling (either may be NULL); *is_set = 0, means 0 and scales 1 when there are none */
+int  rbl_get_scaling(rbl_solver* h, double* mean, double* scale, int* is_set);
 /* Synthetic two-class data generated on the device (statistics of
  * src/util/load_data.py:101-116), never materialised on the host. */
 int  rbl_generate_synthetic(rbl_solver* h, uint64_t seed, double class_sep, double flip_y);
@@ -400,6 +431,10 @@ int  rbl_info(rbl_solver* h, int64_t* ld, int* num_cu, double* lipschitz);
 /* ---- measurement ------------------------------------------------------------------ */
 /* accumulated HIP-event time of the two n x d sweep kernels since the last reset */
 enum { RBL_KERNEL_GEMV = 0, RBL_KERNEL_GEMVT = 1, RBL_KERNEL_SWEEP_ERM = 2 };
+/* the two passes of the last rbl_set_data_from on the handle's stream (not accumulated; launches = 1 if the pass ran):
+ * the column statistics of RBL_SCALE_FIT and the forming of D.  Device source: the kernels alone; host source: the
+ * pipelined pass, the copies it waits for included. */
+enum { RBL_KERNEL_SRC_STATS = 3, RBL_KERNEL_SRC_FORM = 4 };
 int  rbl_kernel_time(rbl_solver* h, int which, double* total_ms, int64_t* launches);
 int  rbl_reset_kernel_times(rbl_solver* h);
 /* The timed launches of one kernel since the last reset, one by one in launch order (milliseconds): the first
