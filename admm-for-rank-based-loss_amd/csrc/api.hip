@@ -1,22 +1,9 @@
-// api.hip - the C ABI of librbl.so (include/rbl.h): solver handle, data path, the ADMM
-// iteration of src/optim/algorithms.py:119-164 as a sequence of device phases, and the
-// kernel-level entry points used by the parity tests.  Host code only orchestrates:
-// every arithmetic step runs in a HIP kernel; there is no CPU fallback.
-#include "rbl_internal.h"
-
-#include <atomic>
-#include <cmath>
-#include <cstdarg>
-#include <cstdio>
-#include <cstring>
-#include <cstdlib>
-#include <functional>
-#include <utility>
-#include <algorithm>
-#include <chrono>
-#include <memory>
-#include <string>
-#include <vector>
+// api.hip - the C ABI of librbl.so (include/rbl.h), first unit: error state, the solver handle's life (create, shared
+// create, destroy), its workspaces, state and buffers in and out, the profiling getters.  Host code only orchestrates:
+// every arithmetic step runs in a HIP kernel; there is no CPU fallback.  The other units: api_data.hip (data path),
+// api_iter.hip (the ADMM iteration), api_dist.hip (distributed z-step), api_group.hip (groups), api_kernels.hip
+// (kernel-level entry points of the parity tests).
+#include "api_internal.h"
 
 // ------------------------------------------------------------------------- error state
 static thread_local std::string g_err;
@@ -36,140 +23,7 @@ void rbl_set_error(const char* fmt, ...) {
 static std::atomic<int> g_live[64];
 int rbl_live_handles(int device) { return device >= 0 && device < 64 ? g_live[device].load(std::memory_order_relaxed) : 2; }
 
-struct rbl_solver {
-    DevArena mem;   // every device and pinned buffer of the handle's own (per-problem) state
-    // what depends on (X, y) alone - D, G, the labels, the column statistics, the eigenbasis of G - lives in an arena of
-    // its own: the handle that uploaded the data and the handles that borrow it (rbl_create_shared) hold it together,
-    // the last one to go frees it
-    std::shared_ptr<DevArena> shared;
-    bool borrower = false;         // D and G are another handle's: no upload, no Gram launch on this one
-    int64_t nd_launches = 0;       // n x d launches this handle ran for itself (rbl_group_counters: single_passes)
-    bool in_group = false;         // member of an rbl_group: runs on the group's stream, erm without the single-sweep pass
-    rbl_config cfg;
-    bool counted = false;
-    int64_t n = 0, d = 0, ld = 0, nt = 0, off = 0;
-    int storage = 0;
-    size_t esz = 4;
-    // RBL_STORE_F16: the generator's draws of rbl_synth_local, regenerated by rbl_synth_finish (the matrix is written once)
-    struct {
-        bool pending = false;
-        uint64_t seed = 0;
-        double class_sep = 0.0, flip_y = 0.0, mix[4] = {}, A16[16] = {};
-        int special[4] = {}, vertex[4] = {};
-    } synth;
-    hipStream_t stream = nullptr;
-    hipStream_t own_stream = nullptr;
-    int num_cu = 256;
-    bool data_ready = false, gram_ready = false, gram_local_done = false, v_valid = false;
-    bool sorted_path = false;  // weight function needs sort + PAV
-
-    void* D = nullptr;
-    double *w = nullptr, *w_prev = nullptr, *q = nullptr, *G = nullptr, *w_tmp = nullptr;
-    double *z = nullptr, *lam = nullptr, *v = nullptr, *m = nullptr, *c = nullptr;
-    double *sigma_a = nullptr, *sigma_b = nullptr;
-    double *slab = nullptr;
-    size_t slab_bytes = 0;
-    double *partials = nullptr, *red = nullptr, *red2 = nullptr;
-    signed char* ysign = nullptr;
-    // labels of this handle's own on a borrowed D (rbl_set_labels): rs[i] = y_i * y_owner_i, one byte per row in this
-    // handle's arena; NULL = the owner's labels.  v, z, lambda, c are then kept in the OWNER's sign convention (z~ = r z,
-    // lambda~ = r lambda, c~ = r c; v = D w as the passes over the owner's D leave it), m is the true m; the sign is taken
-    // out by the element-wise kernels around the z-step and the losses.  rs_host / ys_host: r and the own labels on the host
-    signed char* rs = nullptr;
-    std::vector<signed char> rs_host, ys_host;
-    double* colstats = nullptr;  // [sum(ld) | sumsq(ld) | mean(ld) | inv_std(ld)]
-
-    SortWorkspace sw{};
-    PavWorkspace pw{};
-    PrefixBufs pfx_a, pfx_b;   // prefix sums of sigma_a / sigma_b (pfx_b = pfx_a unless EHRM)
-    WstepWorkspace ww{};
-    double L = 0.0;
-    // per-coordinate penalties (rbl_set_penalty), NULL = the scalar cfg.reg:
-    // [l1 (ld) | l2 (ld) | sum w^2, ||w||_1, sum l1|w|, sum l2 w^2 of the iteration | the same four of rbl_objective]
-    double* pen = nullptr;
-    std::vector<double> pen_host;   // l1 (d) | l2 (d)
-    // column scaling of rbl_set_data_from (RBL_SCALE_FIT writes it, rbl_set_scaling sets it, RBL_SCALE_APPLY reads it)
-    std::vector<double> sc_mean, sc_scale;   // d each
-    bool sc_set = false;
-    double src_ms[2] = {0.0, 0.0};   // the last rbl_set_data_from: statistics pass, forming pass (rbl_kernel_time 3 / 4)
-    int src_timed[2] = {0, 0};
-
-    // host-side state of the iteration (algorithms.py:32-52)
-    double rho = 0.0, smooth_t = 1.0, sigma0 = 0.0;
-    int64_t iter = 0;
-    // scratch of the step in flight
-    double step_rho = 0.0;
-    int inner_iters = 0;
-    int want_obj = 0;
-    bool obj_is_risk = false;
-
-    hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    hipEvent_t kev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // gemv, gemvt, sweep_erm: begin/end
-    bool profile = false, kev_pending[3] = {false, false, false};
-    int profile_every = 1;   // kernel events on every profile_every-th iteration (rbl_profile_sampling)
-    double kt_ms[3] = {0.0, 0.0, 0.0};
-    int64_t kt_n[3] = {0, 0, 0};
-    std::vector<float> kt_samples[3];   // the timed launches one by one, in order (rbl_kernel_samples)
-
-    // single-sweep erm iteration (sweep_erm.hip)
-    bool fused_ok = false, z_ready = false, p_valid = false, p_pending = false, pred_valid = false, fused_ran = false;
-    // distributed z-step (rbl_zd_*): this rank's chunk of the globally sorted order
-    double* zd_small = nullptr;      // samples | bounds | fvals | candidates | partial sums | seam sums
-    ZdSeam* zd_seam = nullptr;
-    int* zd_err = nullptr;
-    long long* zd_bounds_dev = nullptr;
-    long long* zd_counts_dev = nullptr;   // RBL_BUF_ZD_COUNTS: per-destination counts of the sample sort (64 x int64)
-    u32* zd_zids = nullptr;          // row ids received back (n)
-    PrefixBufs zd_a, zd_b;           // prefix sums of the chunk's slice of sigma_a / sigma_b (zd_b = zd_a unless EHRM)
-    int64_t zd_n = 0, zd_off = 0;    // chunk length and its offset in the sorted order
-    int zd_world = 0;
-    bool fuse_v = false;   // rank-weighted problems: v = D w fused with the lambda update (sweep_erm.hip, SE_VONLY)
-    int pending_mask = 0;  // bit 0: the q part, bit 1: the residual part of the exchange buffer awaits a sum over ranks
-    double *z_next = nullptr, *p = nullptr, *p_alt = nullptr, *pred = nullptr;
-    double* hstat = nullptr;   // pinned host block the end-of-iteration statistics are packed into by the device
-    // The lasso w-step of iteration k+1 is enqueued by rbl_phase_finish(k) before the host has
-    // read iteration k's statistics (its inputs q and rho_{k+1} = pred[0] are already on the
-    // device); spec_w says that w currently holds that speculative w_{k+1} (w_prev = w_k).
-    bool spec_w = false, spec_timed = false;
-    hipEvent_t ev_spec[2] = {nullptr, nullptr};
-    bool phase_timing = false;   // rbl_profile_kernels level 2: HIP events around the phases (ms_* of rbl_stats)
-    int64_t n_fused = 0, n_mispred = 0;
-    bool fused_v_ran = false;
-    int eig_sweeps = 0;    // Jacobi sweeps of the one-time eigendecomposition of G (l2 w-step), 0 = CG is used
-    bool keys_ready = false;   // rbl_phase_m left the sort's input (keys of m, global row ids) in sw.keys[0] / vals[0]
-    // z-step with 32-bit sort keys (round 3; elementwise.hip: k_keys32 / k_sort32_fix): rbl_phase_m left m and its range
-    // (m32_ready); the sort's verdict - no run of equal keys too long to repair - arrives in pinned memory like the
-    // sort-free z-step's and is settled by the same entries (zb_resolve): not certified = redone with 64-bit keys
-    struct {
-        bool m_ready = false, used = false, q_done = false;
-        bool off = false;        // RBL_NO_SORT32=1 (tests): 64-bit keys in every iteration
-        u64* mm = nullptr;       // range of m (device)
-        int* flag = nullptr;     // device: 1 = a run too long
-        int* pin = nullptr;      // pinned: [0] sequence number (written last), [1] flag
-        int seq = 0;
-        int64_t skip_until = 0;
-    } s32;
-    int sort_passes = 0;   // radix passes executed by the z-step in flight
-    // z-step without a sort for piecewise-constant rank weights (zband.hip); `used`: this iteration's z came from it
-    // and its status word has not been looked at yet
-    struct {
-        bool checked = false, enabled = false, used = false, c_ready = false, q_done = false;
-        ZbConfig cfg;
-        ZbState* st = nullptr;
-        u32* hist = nullptr;
-        double* part = nullptr;
-        double* tot = nullptr;     // multi-GPU: the sums of one root pass (all-reduced by the driver)
-        double* pack = nullptr;    // multi-GPU: [count | undecided elements] of this rank (all-gathered by the driver)
-        int* pin = nullptr;    // pinned: [0] sequence number (written last), [1] status
-        int seq = 0, mode = 0, dseq = 0;
-        int64_t backoff = 0, skip_until = 0;   // after an uncertified z-step the fast path pauses for 2, 4, ... 64 iterations   // mode of the iteration in flight: 0 sort, 1 banded, 2 banded then redone with the sort
-    } zb;
-};
-
-// where the iteration's regulariser terms of a handle with per-coordinate penalties go (NULL without them)
-static inline double* pen_terms(rbl_solver* h) { return h->pen ? h->pen + 2 * h->ld : nullptr; }
-
-static thread_local int g_host_syncs = 0;   // one solver handle per host thread (include/rbl.h)
+thread_local int g_host_syncs = 0;   // one solver handle per host thread (include/rbl.h); declared in api_internal.h
 void rbl_note_host_sync() { ++g_host_syncs; }
 
 void rbl_spin_wait(const volatile int* word, int sentinel, hipStream_t stream) {
@@ -203,8 +57,6 @@ int alloc_sort(DevArena& mem, SortWorkspace& sw, int64_t n, bool with_vals, hipS
     return RBL_OK;
 }
 
-namespace {
-
 int check_device(int* count_out) {
     int cnt = 0;
     hipError_t e = hipGetDeviceCount(&cnt);
@@ -217,24 +69,7 @@ int check_device(int* count_out) {
     return RBL_OK;
 }
 
-double default_rho(int wf) {
-    // src/optim/algorithms.py:47-52
-    if (wf == RBL_W_EHRM) return 1e-4;
-    if (wf == RBL_W_AORR || wf == RBL_W_AORR_DC) return 2e-7;
-    return 1e-5;
-}
-
 int64_t round_up(int64_t x, int64_t m) { return (x + m - 1) / m * m; }
-
-int fill_const(double* p, int64_t count, double val, hipStream_t s) {
-    std::vector<double> h((size_t)(count < (1 << 20) ? count : (1 << 20)), val);
-    for (int64_t o = 0; o < count; o += (int64_t)h.size()) {
-        int64_t c = count - o < (int64_t)h.size() ? count - o : (int64_t)h.size();
-        RBL_HIP(hipMemcpyAsync(p + o, h.data(), sizeof(double) * c, hipMemcpyHostToDevice, s));
-        RBL_HIP(hipStreamSynchronize(s));
-    }
-    return RBL_OK;
-}
 
 int alloc_prefix(DevArena& mem, PrefixBufs& p, int64_t n) {
     const int64_t nc = pav_num_chunks(n);
@@ -282,6 +117,43 @@ int alloc_wstep(DevArena& mem, WstepWorkspace& ww, int64_t ld, hipStream_t s) {
     // writes directly (status word last): the host spins on the word - no copy, no stream-wide wait
     RBL_TRY(mem.pinned(&ww.pin, 16, hipHostMallocCoherent));
     for (int i = 0; i < 16; ++i) ww.pin[i] = 0;
+    return RBL_OK;
+}
+
+// own labels (rbl_set_labels): n host values between the handle's own sign convention and the owner's (an involution)
+void flip_rows(const rbl_solver* h, double* x) {
+    for (int64_t i = 0; i < h->n; ++i)
+        if (h->rs_host[(size_t)i] < 0) x[i] = -x[i];
+}
+
+// n host doubles in the handle's own sign convention -> a device vector in the convention it is stored in (blocking)
+int upload_rows(const rbl_solver* h, double* dst_dev, const double* src) {
+    if (!h->rs) {
+        RBL_HIP(hipMemcpy(dst_dev, src, sizeof(double) * h->n, hipMemcpyHostToDevice));
+        return RBL_OK;
+    }
+    std::vector<double> t(src, src + h->n);
+    flip_rows(h, t.data());
+    RBL_HIP(hipMemcpy(dst_dev, t.data(), sizeof(double) * h->n, hipMemcpyHostToDevice));
+    return RBL_OK;
+}
+
+namespace {
+
+double default_rho(int wf) {
+    // src/optim/algorithms.py:47-52
+    if (wf == RBL_W_EHRM) return 1e-4;
+    if (wf == RBL_W_AORR || wf == RBL_W_AORR_DC) return 2e-7;
+    return 1e-5;
+}
+
+int fill_const(double* p, int64_t count, double val, hipStream_t s) {
+    std::vector<double> h((size_t)(count < (1 << 20) ? count : (1 << 20)), val);
+    for (int64_t o = 0; o < count; o += (int64_t)h.size()) {
+        int64_t c = count - o < (int64_t)h.size() ? count - o : (int64_t)h.size();
+        RBL_HIP(hipMemcpyAsync(p + o, h.data(), sizeof(double) * c, hipMemcpyHostToDevice, s));
+        RBL_HIP(hipStreamSynchronize(s));
+    }
     return RBL_OK;
 }
 
@@ -352,203 +224,6 @@ int build_sigma_prefix(rbl_solver* h) {
     RBL_TRY(launch_prefix(h->sigma_a, h->nt, h->pfx_a, h->stream));
     if (h->cfg.weight_function == RBL_W_EHRM) RBL_TRY(launch_prefix(h->sigma_b, h->nt, h->pfx_b, h->stream));
     return RBL_OK;
-}
-
-// own labels (rbl_set_labels): n host values between the handle's own sign convention and the owner's (an involution)
-void flip_rows(const rbl_solver* h, double* x) {
-    for (int64_t i = 0; i < h->n; ++i)
-        if (h->rs_host[(size_t)i] < 0) x[i] = -x[i];
-}
-
-// n host doubles in the handle's own sign convention -> a device vector in the convention it is stored in (blocking)
-int upload_rows(const rbl_solver* h, double* dst_dev, const double* src) {
-    if (!h->rs) {
-        RBL_HIP(hipMemcpy(dst_dev, src, sizeof(double) * h->n, hipMemcpyHostToDevice));
-        return RBL_OK;
-    }
-    std::vector<double> t(src, src + h->n);
-    flip_rows(h, t.data());
-    RBL_HIP(hipMemcpy(dst_dev, t.data(), sizeof(double) * h->n, hipMemcpyHostToDevice));
-    return RBL_OK;
-}
-
-int ensure_v(rbl_solver* h) {
-    if (h->v_valid) return RBL_OK;
-    h->nd_launches += 1;
-    RBL_TRY(launch_gemv(h->storage, h->D, h->n, h->ld, h->w, h->v, h->num_cu, h->stream));
-    h->v_valid = true;
-    return RBL_OK;
-}
-
-// written by one thread behind the 32-bit sort's fix-up: its verdict for the host (sequence number last)
-static __global__ void k_publish_flag(const int* __restrict__ flag, int* __restrict__ pin, int seq) {
-    if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    pin[1] = flag[0];
-    __threadfence_system();
-    reinterpret_cast<volatile int*>(pin)[0] = seq;
-}
-
-// Sorted-path z-step over the n_total values in msrc (device), writing the local slice.
-// allow32: the 32-bit-key sort may be used when rbl_phase_m prepared it (h->s32.m_ready) - its verdict is settled later
-// (zb_resolve); false: 64-bit keys (the redo of an uncertified step, gathered m of the replicated distributed form).
-int z_step_sorted(rbl_solver* h, const double* msrc, double rho, bool allow32 = true) {
-    hipStream_t s = h->stream;
-    const int64_t nt = h->nt;
-    const u32* perm = h->sw.vals[0];
-    const bool use32 = allow32 && h->s32.m_ready && msrc == h->m && nt == h->n;
-    h->s32.m_ready = false;
-    if (use32) {
-        // fixed-point 32-bit keys of m: 4 radix passes over 8 bytes per row instead of 8 over 12, then one pass that gathers
-        // the sorted m through the row ids and repairs the short runs the 32 bits cannot tell apart
-        u32* k32 = reinterpret_cast<u32*>(h->sw.keys[0]);
-        RBL_TRY(launch_keys32(nt, h->m, h->s32.mm, k32, h->sw.vals[0], (u32)h->off, s));
-        RBL_TRY(launch_radix_sort32(h->sw, nt, s));
-        RBL_TRY(launch_sort32_fix(nt, k32, h->sw.vals[0], h->m, (u32)h->off, h->pw.ms, h->sw.vals[1], h->s32.flag, s));
-        h->s32.seq = (h->s32.seq & 0x3fffffff) + 1;
-        h->s32.pin[0] = 0;
-        hipLaunchKernelGGL(k_publish_flag, dim3(1), dim3(64), 0, s, (const int*)h->s32.flag, h->s32.pin, h->s32.seq);
-        RBL_HIP(hipGetLastError());
-        h->s32.used = true;
-        h->s32.q_done = false;
-        RBL_TRY(launch_prefix(h->pw.ms, nt, h->pw.pm, s));
-        perm = h->sw.vals[1];
-        h->sort_passes += 4;
-    } else {
-        // rbl_phase_m already formed the keys with m when it covers the whole problem (one pass instead of two)
-        if (!(h->keys_ready && msrc == h->m && nt == h->n)) RBL_TRY(launch_keys_from_m(nt, msrc, h->sw.keys[0], h->sw.vals[0], s));
-        RBL_TRY(launch_radix_sort(h->sw, nt, true, s));
-        RBL_TRY(launch_unflip_prefix(h->sw.keys[0], nt, h->pw.ms, h->pw.pm, s));
-        h->sort_passes += 8;
-    }
-    h->keys_ready = false;   // the sort consumes its input
-    const bool ehrm = h->cfg.weight_function == RBL_W_EHRM;
-    // EHRM: the branch of the previous iteration is speculated and the exact test rides on the bottom kernel
-    // (pav.hip: k_pav_bottom<0, true>).  RBL_EHRM_SPEC=0 / 1: the first speculation (tests force a wrong one);
-    // RBL_EHRM_SPEC=-1: round 2's form - a pass of its own solves both element prox problems (k_ehrm_fvals), the tree
-    // reads the chosen one as its level 0
-    int spec_env = 2;
-    if (ehrm) {
-        const char* e = getenv("RBL_EHRM_SPEC");   // (read per z-step: the tests switch it between handles)
-        if (e) spec_env = atoi(e);
-    }
-    PavExtras ex = h->pw.ex;
-    ex.num_cu = h->num_cu;
-    ex.B = h->cfg.B;
-    const bool spec = ehrm && spec_env != -1;
-    if (!spec) ex.fpart = nullptr;
-    if (spec && h->iter == 0 && (spec_env == 0 || spec_env == 1)) ex.spec = spec_env;
-    double* u0a = (ehrm && !spec) ? h->pw.u : nullptr;
-    double* u0b = (ehrm && !spec) ? (double*)h->sw.keys[1] : nullptr;   // free once the sort is done
-    if (ehrm && !spec)
-        RBL_TRY(launch_ehrm_branch(nt, h->sigma_a, h->sigma_b, h->cfg.B, rho, h->pw.ms, h->pw.partials, h->pw.branch,
-                                   -1, s, u0a, u0b));
-    RBL_TRY(launch_pav_tree(h->cfg.loss, nt, rho, h->pw.ms, h->sigma_a, h->sigma_b, h->pw.u, h->pfx_a.view(), h->pfx_b.view(),
-                            h->pw.pm.view(), ehrm ? h->pw.branch : nullptr, h->pw.recs, h->pw.counters, s, u0a, u0b, &ex));
-    h->pw.ex.bar_parity = ex.bar_parity;
-    RBL_TRY(launch_scatter_z(nt, h->pw.u, perm, ehrm ? h->pw.branch : nullptr, h->cfg.B, ehrm ? 1 : 0, rho,
-                             h->lam, h->z, nullptr, h->off, h->n, s, h->rs));
-    return RBL_OK;
-}
-
-// Are the rank weights constant on a few bands (superquantile, aorr, aorr_dc)?  Then the z-step needs no sort
-// (zband.hip).  Looked at once per handle, at the first rank-weighted z-step.
-int zb_setup(rbl_solver* h) {
-    h->zb.checked = true;
-    h->zb.enabled = false;
-    // RBL_NO_SORT32=1 (tests): rbl_phase_m never prepares the 32-bit keys, so every sorted z-step sorts 64-bit keys - the
-    // run the default one is compared with bit for bit.  Looked at here, once per handle, like RBL_NO_ZBAND
-    const char* no32 = getenv("RBL_NO_SORT32");
-    h->s32.off = no32 && no32[0] == '1';
-    const char* off = getenv("RBL_NO_ZBAND");
-    if (off && off[0] == '1') return RBL_OK;
-    const char* mn = getenv("RBL_ZBAND_MIN_N");
-    const long long min_n = mn ? atoll(mn) : 4096;   // (6000 x 1000: 0.47 against 0.63 ms per iteration; below a few thousand rows nothing is gained)
-    // (the configuration speaks of GLOBAL ranks: a row-sharded handle builds the same one; its driver runs the steps with
-    // collectives in between - rbl_zbd_*)
-    if (!h->sorted_path || h->cfg.weight_function == RBL_W_EHRM || h->nt < min_n || h->nt < 16) return RBL_OK;
-    constexpr int CAP = 16;
-    long long pos[CAP];
-    int cnt = 0;
-    {
-        DevArena tmp;   // the edge buffers, freed once read back
-        long long* pos_dev = nullptr;
-        int* cnt_dev = nullptr;
-        RBL_TRY(tmp.alloc(&pos_dev, (size_t)CAP));
-        RBL_TRY(tmp.alloc(&cnt_dev, (size_t)1));
-        int rc = launch_zb_edges(h->sigma_a, h->nt, pos_dev, cnt_dev, CAP, h->stream);
-        if (rc == RBL_OK && (hipMemcpyAsync(&cnt, cnt_dev, sizeof(int), hipMemcpyDeviceToHost, h->stream) != hipSuccess ||
-                             hipMemcpyAsync(pos, pos_dev, sizeof(pos), hipMemcpyDeviceToHost, h->stream) != hipSuccess ||
-                             hipStreamSynchronize(h->stream) != hipSuccess))
-            rc = RBL_ERR_HIP;
-        if (rc != RBL_OK) {
-            rbl_set_error("zband setup: reading the edges of sigma failed");
-            return rc;
-        }
-    }
-    if (cnt < 1 || cnt > ZB_MAX_BANDS - 1) return RBL_OK;   // constant weights never come here (erm); smooth families: sort
-    std::sort(pos, pos + cnt);
-    ZbConfig& c = h->zb.cfg;
-    std::memset(&c, 0, sizeof(c));
-    c.nbands = cnt + 1;
-    c.start[0] = 0;
-    for (int j = 0; j < cnt; ++j) c.start[j + 1] = pos[j];
-    c.start[c.nbands] = h->nt;
-    for (int j = 0; j < c.nbands; ++j)
-        RBL_HIP(hipMemcpy(&c.sigma[j], h->sigma_a + c.start[j], sizeof(double), hipMemcpyDeviceToHost));
-    auto size = [&](int j) { return c.start[j + 1] - c.start[j]; };
-    if (size(0) < 2 || size(c.nbands - 1) < 2) return RBL_OK;
-    // targets: last rank of every band but the last, first rank of every band but the first (ascending, unique)
-    auto add_target = [&](long long r) {
-        for (int t = 0; t < c.ntargets; ++t)
-            if (c.target_rank[t] == r) return t;
-        if (c.ntargets == ZB_MAX_TARGETS) return -1;
-        c.target_rank[c.ntargets] = r;
-        return c.ntargets++;
-    };
-    for (int j = 0; j < c.nbands; ++j) {
-        if (j > 0 && (c.first_t[j] = add_target(c.start[j])) < 0) return RBL_OK;
-        if (j < c.nbands - 1 && (c.last_t[j] = add_target(c.start[j + 1] - 1)) < 0) return RBL_OK;
-    }
-    for (int t = 1; t < c.ntargets; ++t)
-        if (c.target_rank[t] <= c.target_rank[t - 1]) return RBL_OK;   // (cannot happen: bands are disjoint and ordered)
-    // clusters: a band of two or more ranks, single-rank bands, the next band of two or more ranks
-    int L = 0;
-    for (int j = 1; j < c.nbands; ++j) {
-        if (size(j) == 1) continue;
-        if (c.nclusters == ZB_MAX_CLUSTERS) return RBL_OK;
-        bool up = false;
-        for (int q = L; q < j; ++q) up = up || c.sigma[q + 1] > c.sigma[q];
-        if (j - L > 3) return RBL_OK;   // more than two single-rank bands in a row: left to the sort
-        c.cl_L[c.nclusters] = L;
-        c.cl_R[c.nclusters] = j;
-        c.cl_root[c.nclusters] = up ? 1 : 0;
-        ++c.nclusters;
-        L = j;
-    }
-    RBL_TRY(h->mem.alloc(&h->zb.st, (size_t)1));
-    RBL_HIP(hipMemsetAsync(h->zb.st, 0, sizeof(ZbState), h->stream));
-    RBL_TRY(h->mem.alloc((unsigned char**)&h->zb.hist, zb_hist_bytes()));
-    RBL_TRY(h->mem.alloc((unsigned char**)&h->zb.part, zb_partials_bytes()));
-    RBL_TRY(h->mem.alloc(&h->zb.tot, (size_t)(4 * ZB_C)));
-    RBL_TRY(h->mem.alloc(&h->zb.pack, (size_t)(ZB_GCAP + 1)));
-    RBL_TRY(h->mem.pinned(&h->zb.pin, 16, hipHostMallocDefault));
-    for (int i = 0; i < 16; ++i) h->zb.pin[i] = 0;
-    h->zb.enabled = true;   // set last: the buffers above are all there
-    return RBL_OK;
-}
-
-// sum_i sigma_i * loss_(i) from n_total values of v (device) -> *out_dev
-int risk_from_v(rbl_solver* h, const double* v_all, double* out_dev) {
-    hipStream_t s = h->stream;
-    if (h->cfg.weight_function == RBL_W_ERM)
-        return launch_loss_sum(h->cfg.loss, h->nt, v_all, 1.0 / (double)h->nt, h->partials, out_dev, s, h->rs);
-    h->keys_ready = false;   // the sort workspace is reused: keys left by rbl_phase_m are gone
-    RBL_TRY(launch_loss_keys(h->nt, v_all, h->sw.keys[0], s, h->rs));   // (own labels: the losses are taken at r * v)
-    // piecewise-constant weights: the band sums of the losses need a select, not a sort (zband.hip; exact for any v)
-    if (h->zb.enabled)
-        return launch_zband_risk(h->cfg.loss, h->zb.cfg, h->nt, h->sw.keys[0], h->zb.st, h->zb.hist, h->zb.part, out_dev, s);
-    RBL_TRY(launch_radix_sort(h->sw, h->nt, false, s));
-    return launch_sorted_loss_dot(h->cfg.loss, h->nt, h->sw.keys[0], h->sigma_a, h->partials, out_dev, s);
 }
 
 }  // namespace
@@ -784,947 +459,12 @@ int rbl_create(const rbl_config* cfg, rbl_solver** out) {
     return RBL_OK;
 }
 
-// Entry of the functions that advance the iteration (phases, step, solve) or only read handle
-// bookkeeping: a speculative w-step in flight stays.
-#define RBL_ENTER_ITER(h)                              \
-    do {                                               \
-        if (!(h)) {                                    \
-            rbl_set_error("solver handle is NULL");    \
-            return RBL_ERR_INVALID;                    \
-        }                                              \
-        RBL_HIP(hipSetDevice((h)->cfg.device));        \
-    } while (0)
-
-// The sort-free z-step (zband.hip) reports through a pinned word whether it could certify its result.  Whoever is about
-// to look at z (or at the q formed from it) before rbl_phase_w has done so settles it here: wait for the word; not
-// certified -> the z-step (and q, if rbl_phase_q has run) is redone with the sort + merge-tree PAV, and the fast path
-// pauses for 2, 4, ... 64 iterations (the first iterations pool most of the rows in one block; that passes).
-// *redone (optional): tells rbl_phase_w that its w-step has to be repeated.
-int zb_resolve(rbl_solver* h, bool* redone = nullptr) {
-    if (redone) *redone = false;
-    if (h->s32.used) {
-        // z-step with 32-bit sort keys: a run of equal keys too long for the fix-up (many m within range / 2^32 of each
-        // other: ties on a grid, a degenerate range) - redo this iteration's z-step (and q) with 64-bit keys, and stay on
-        // them for the next 64 iterations
-        h->s32.used = false;
-        volatile int* pin = h->s32.pin;
-        if (pin[0] != h->s32.seq) rbl_spin_wait(pin, 0, h->stream);
-        if (pin[0] != h->s32.seq) {
-            rbl_set_error("z-step: the verdict of the 32-bit sort was never written");
-            (void)hipGetLastError();
-            return RBL_ERR_HIP;
-        }
-        if (pin[1] != 0) {
-            h->s32.skip_until = h->iter + 1 + 64;
-            const bool q_done = h->s32.q_done;
-            h->s32.q_done = false;
-            RBL_TRY(z_step_sorted(h, h->m, h->step_rho, false));
-            if (q_done) {
-                RBL_TRY(launch_make_c(h->n, h->z, h->lam, h->step_rho, h->c, h->stream));
-                RBL_TRY(launch_gemvt(h->storage, h->D, h->n, h->ld, h->c, h->slab, h->q, h->num_cu, h->stream));
-                h->nd_launches += 1;
-            }
-            if (redone) *redone = true;
-        }
-        return RBL_OK;
-    }
-    if (!h->zb.used) return RBL_OK;
-    h->zb.used = false;
-    volatile int* pin = h->zb.pin;
-    if (pin[0] != h->zb.seq) rbl_spin_wait(pin, 0, h->stream);
-    if (pin[0] != h->zb.seq) {
-        rbl_set_error("banded z-step: its status word was never written");
-        (void)hipGetLastError();
-        return RBL_ERR_HIP;
-    }
-    if (pin[1] == ZB_OK) {
-        h->zb.backoff = 0;
-        return RBL_OK;
-    }
-    h->zb.backoff = h->zb.backoff < 2 ? 2 : (h->zb.backoff >= 32 ? 64 : 2 * h->zb.backoff);
-    h->zb.skip_until = h->iter + 1 + h->zb.backoff;
-    h->zb.mode = 2;
-    const bool q_done = h->zb.q_done;
-    h->zb.c_ready = h->zb.q_done = false;
-    RBL_TRY(z_step_sorted(h, h->m, h->step_rho, false));
-    if (q_done) {
-        RBL_TRY(launch_make_c(h->n, h->z, h->lam, h->step_rho, h->c, h->stream));
-        RBL_TRY(launch_gemvt(h->storage, h->D, h->n, h->ld, h->c, h->slab, h->q, h->num_cu, h->stream));
-        h->nd_launches += 1;
-    }
-    if (redone) *redone = true;
-    return RBL_OK;
-}
-
-// w_{k+1} was computed ahead of time (rbl_phase_finish); anything that looks at or replaces the
-// state between two iterations must see w_k: put it back (the w-step is simply redone later).
-int cancel_spec(rbl_solver* h) {
-    if (!h->spec_w) return RBL_OK;
-    h->spec_w = false;
-    h->spec_timed = false;
-    RBL_HIP(hipMemcpyAsync(h->w, h->w_prev, sizeof(double) * h->ld, hipMemcpyDeviceToDevice, h->stream));
-    RBL_HIP(hipStreamSynchronize(h->stream));
-    return RBL_OK;
-}
-
-// Entry of every other function of the API
-#define RBL_ENTER(h)              \
-    do {                          \
-        RBL_ENTER_ITER(h);        \
-        RBL_TRY(zb_resolve(h));   \
-        RBL_TRY(cancel_spec(h));  \
-    } while (0)
-
-// the data path (upload, generator, Gram matrix) belongs to the handle that owns D and G
-#define RBL_NOT_BORROWER(h, what)                                                                             \
-    do {                                                                                                      \
-        if ((h)->borrower) {                                                                                  \
-            rbl_set_error(what ": this handle borrows its data (rbl_create_shared) - call it on the owner");  \
-            return RBL_ERR_STATE;                                                                             \
-        }                                                                                                     \
-    } while (0)
-
 int rbl_set_stream(rbl_solver* h, void* hip_stream) {
     RBL_ENTER(h);
     RBL_HIP(hipStreamSynchronize(h->stream));
     // NULL is a real stream (the legacy default stream torch uses unless told otherwise);
     // (void*)-1 restores the handle's own non-blocking stream
     h->stream = (hip_stream == (void*)-1) ? h->own_stream : (hipStream_t)hip_stream;
-    return RBL_OK;
-}
-
-int rbl_set_data(rbl_solver* h, const double* X, const double* y, int64_t ldx) {
-    RBL_ENTER(h);
-    RBL_NOT_BORROWER(h, "set_data");
-    if (!X || !y || ldx < h->d) {
-        rbl_set_error("set_data: bad arguments (ldx=%lld, d=%lld)", (long long)ldx, (long long)h->d);
-        return RBL_ERR_INVALID;
-    }
-    for (int64_t i = 0; i < h->n; ++i) {
-        if (!(y[i] == 1.0 || y[i] == -1.0)) {
-            rbl_set_error("set_data: labels must be +1/-1 (y[%lld] = %g)", (long long)i, y[i]);
-            return RBL_ERR_INVALID;
-        }
-    }
-    const int64_t n = h->n, d = h->d;
-    if (n > 0) {
-        // The caller's rows are pinned in place for the duration of the call (hipHostRegister), so the
-        // 64 MB chunks go over PCIe by DMA at link speed, and two staging buffers let the copy of chunk
-        // k+1 run (second stream) while chunk k is converted to the storage type into D.  If the
-        // pages cannot be pinned the chunks are copied from pageable memory instead (slower, same result).
-        int64_t chunk = (int64_t)((64LL << 20) / (sizeof(double) * (size_t)ldx));
-        if (chunk < 1) chunk = 1;
-        if (chunk > n) chunk = n;
-        const size_t xbytes = sizeof(double) * (size_t)n * (size_t)ldx;
-        const bool pinned = hipHostRegister(const_cast<double*>(X), xbytes, hipHostRegisterDefault) == hipSuccess;
-        if (!pinned) (void)hipGetLastError();
-        int rc = RBL_OK;
-        {
-            DevArena tmp;   // the staging buffers, freed at the end of this block (after the last stream wait)
-            double *Xd[2] = {nullptr, nullptr}, *yd = nullptr;
-            u64* ovf = nullptr;   // RBL_STORE_F16: {entries that do not fit, first of them} written by the conversion kernel
-            hipStream_t copy_stream = nullptr;
-            hipEvent_t copied[2] = {nullptr, nullptr}, formed[2] = {nullptr, nullptr};
-            auto cleanup = [&]() {
-                for (int k = 0; k < 2; ++k) {
-                    if (copied[k]) (void)hipEventDestroy(copied[k]);
-                    if (formed[k]) (void)hipEventDestroy(formed[k]);
-                }
-                if (copy_stream) (void)hipStreamDestroy(copy_stream);
-                if (pinned) (void)hipHostUnregister(const_cast<double*>(X));
-            };
-            if (tmp.alloc(&Xd[0], (size_t)chunk * ldx) != RBL_OK || tmp.alloc(&Xd[1], (size_t)chunk * ldx) != RBL_OK ||
-                tmp.alloc(&yd, (size_t)n) != RBL_OK || (h->storage == RBL_STORE_F16 && tmp.alloc(&ovf, 2) != RBL_OK)) {
-                cleanup();
-                return RBL_ERR_NOMEM;
-            }
-            const u64 ovf0[2] = {0ull, ~0ull};
-            bool ok = hipStreamCreateWithFlags(&copy_stream, hipStreamNonBlocking) == hipSuccess;
-            for (int k = 0; k < 2 && ok; ++k)
-                ok = hipEventCreateWithFlags(&copied[k], hipEventDisableTiming) == hipSuccess &&
-                     hipEventCreateWithFlags(&formed[k], hipEventDisableTiming) == hipSuccess;
-            ok = ok && hipMemcpyAsync(yd, y, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, h->stream) == hipSuccess;
-            if (ovf) ok = ok && hipMemcpyAsync(ovf, ovf0, sizeof(ovf0), hipMemcpyHostToDevice, h->stream) == hipSuccess;
-            ok = ok && hipStreamSynchronize(h->stream) == hipSuccess;
-            if (!ok) {
-                rbl_set_error("set_data: stream / event / label upload failed: %s", hipGetErrorString(hipGetLastError()));
-                cleanup();
-                return RBL_ERR_HIP;
-            }
-            int64_t k = 0;
-            for (int64_t r0 = 0; r0 < n && rc == RBL_OK; r0 += chunk, ++k) {
-                const int64_t rows = n - r0 < chunk ? n - r0 : chunk;
-                const int b = (int)(k & 1);
-                hipError_t e = hipSuccess;
-                if (k >= 2) e = hipStreamWaitEvent(copy_stream, formed[b], 0);   // staging buffer b has been consumed
-                if (e == hipSuccess)
-                    e = hipMemcpyAsync(Xd[b], X + r0 * ldx, sizeof(double) * rows * ldx, hipMemcpyHostToDevice, copy_stream);
-                if (e == hipSuccess) e = hipEventRecord(copied[b], copy_stream);
-                if (e == hipSuccess) e = hipStreamWaitEvent(h->stream, copied[b], 0);
-                if (e != hipSuccess) {
-                    rbl_set_error("set_data: upload failed: %s", hipGetErrorString(e));
-                    rc = RBL_ERR_HIP;
-                    break;
-                }
-                rc = launch_form_D(h->storage, h->D, h->ld, r0, Xd[b], ldx, yd + r0, rows, d, h->stream, ovf);
-                if (rc == RBL_OK && hipEventRecord(formed[b], h->stream) != hipSuccess) rc = RBL_ERR_HIP;
-            }
-            if (hipStreamSynchronize(copy_stream) != hipSuccess || hipStreamSynchronize(h->stream) != hipSuccess) {
-                if (rc == RBL_OK) {
-                    rbl_set_error("set_data: %s", hipGetErrorString(hipGetLastError()));
-                    rc = RBL_ERR_HIP;
-                }
-            }
-            if (rc == RBL_OK && ovf) {   // read once, after the last chunk
-                u64 got[2] = {0ull, 0ull};
-                if (hipMemcpy(got, ovf, sizeof(got), hipMemcpyDeviceToHost) != hipSuccess) {
-                    rbl_set_error("set_data: %s", hipGetErrorString(hipGetLastError()));
-                    rc = RBL_ERR_HIP;
-                } else if (got[0] > 0) {
-                    const long long r = (long long)(got[1] / (u64)d), c = (long long)(got[1] % (u64)d);
-                    rbl_set_error("fp16 storage: %llu finite entries do not fit float16 (|x| >= 65520), first at row %lld, column %lld "
-                                  "(value %g) - standardise the columns or use storage f32",
-                                  got[0], r, c, X[r * ldx + c]);
-                    rc = RBL_ERR_INVALID;
-                }
-            }
-            cleanup();
-        }
-        if (rc != RBL_OK) h->data_ready = false;   // a failed upload leaves the handle without data
-        RBL_TRY(rc);
-        std::vector<signed char> ys((size_t)n);
-        for (int64_t i = 0; i < n; ++i) ys[(size_t)i] = y[i] > 0 ? 1 : -1;
-        RBL_HIP(hipMemcpy(h->ysign, ys.data(), (size_t)n, hipMemcpyHostToDevice));
-    }
-    h->data_ready = true;
-    h->gram_ready = h->gram_local_done = false;
-    h->v_valid = false;
-    return RBL_OK;
-}
-
-// ---- rbl_set_data_from: X in the caller's type, from host or device memory ------------------------------------------
-static inline size_t src_esz(int dtype) { return dtype == RBL_DTYPE_F16 ? 2 : dtype == RBL_DTYPE_F32 ? 4 : 8; }
-static inline double src_host_widen(const void* p, int dtype) {
-    if (dtype == RBL_DTYPE_F16) return (double)(float)__builtin_bit_cast(_Float16, *(const unsigned short*)p);
-    if (dtype == RBL_DTYPE_F32) return (double)*(const float*)p;
-    return *(const double*)p;
-}
-// first and last byte of the claimed range must be device memory of the handle's device (a host pointer must fail here,
-// with a message, not fault in a kernel)
-static int src_check_device_range(const void* X, size_t bytes, int device) {
-    const char* ends[2] = {(const char*)X, (const char*)X + (bytes ? bytes - 1 : 0)};
-    for (const char* p : ends) {
-        hipPointerAttribute_t a;
-        const hipError_t e = hipPointerGetAttributes(&a, p);
-        if (e != hipSuccess) (void)hipGetLastError();
-        if (e != hipSuccess || a.type != hipMemoryTypeDevice) {
-            rbl_set_error("set_data_from: X was passed as RBL_MEM_DEVICE but %p is not device memory (a host array goes "
-                          "with RBL_MEM_HOST)", (const void*)p);
-            return RBL_ERR_INVALID;
-        }
-        if (a.device != device) {
-            rbl_set_error("set_data_from: X lives on device %d, the handle on device %d", a.device, device);
-            return RBL_ERR_INVALID;
-        }
-    }
-    return RBL_OK;
-}
-// The upload pipeline of rbl_set_data for a source of any element type: the caller's rows are pinned in place and go over
-// PCIe untouched, chunk by chunk, into two staging buffers (the copy of chunk k + 1 runs on a second stream while the
-// kernels of chunk k read staging buffer k & 1).  A device source is one "chunk": the caller's own memory.
-struct SrcPipe {
-    DevArena tmp;
-    unsigned char* Xd[2] = {nullptr, nullptr};
-    hipStream_t stream = nullptr, copy_stream = nullptr;
-    hipEvent_t copied[2] = {nullptr, nullptr}, formed[2] = {nullptr, nullptr};
-    void* registered = nullptr;
-    ~SrcPipe() {   // (the arena's buffers are freed after this body: nothing may still be running on them)
-        if (copy_stream) (void)hipStreamSynchronize(copy_stream);
-        (void)hipStreamSynchronize(stream);
-        for (int k = 0; k < 2; ++k) {
-            if (copied[k]) (void)hipEventDestroy(copied[k]);
-            if (formed[k]) (void)hipEventDestroy(formed[k]);
-        }
-        if (copy_stream) (void)hipStreamDestroy(copy_stream);
-        if (registered) (void)hipHostUnregister(registered);
-        (void)hipGetLastError();
-    }
-    int open_host(const void* X, size_t xbytes, size_t chunk_bytes) {
-        if (hipHostRegister(const_cast<void*>(X), xbytes, hipHostRegisterDefault) == hipSuccess) registered = const_cast<void*>(X);
-        else (void)hipGetLastError();   // pageable copies instead: slower, same result
-        RBL_TRY(tmp.alloc(&Xd[0], chunk_bytes));
-        RBL_TRY(tmp.alloc(&Xd[1], chunk_bytes));
-        RBL_HIP(hipStreamCreateWithFlags(&copy_stream, hipStreamNonBlocking));
-        for (int k = 0; k < 2; ++k) {
-            RBL_HIP(hipEventCreateWithFlags(&copied[k], hipEventDisableTiming));
-            RBL_HIP(hipEventCreateWithFlags(&formed[k], hipEventDisableTiming));
-        }
-        return RBL_OK;
-    }
-    // one pass over the source: fn(rows on the device, first row, row count) enqueues its kernels on `stream`; returns
-    // with both streams idle
-    int pass(const void* X, int mem, size_t esz, int64_t ldx, int64_t ds, int64_t n, int64_t chunk,
-             const std::function<int(const void*, int64_t, int64_t)>& fn, double* ms = nullptr) {
-        int rc = RBL_OK;
-        hipEvent_t t0 = nullptr, t1 = nullptr;   // the pass on the handle's stream, first kernel to last (host source: the
-                                                 // copies it waits for in between included)
-        if (ms && (hipEventCreate(&t0) != hipSuccess || hipEventCreate(&t1) != hipSuccess || hipEventRecord(t0, stream) != hipSuccess))
-            ms = nullptr;
-        if (mem == RBL_MEM_DEVICE) {
-            rc = fn(X, (int64_t)0, n);
-        } else {
-            int64_t k = 0;
-            for (int64_t r0 = 0; r0 < n && rc == RBL_OK; r0 += chunk, ++k) {
-                const int64_t rows = n - r0 < chunk ? n - r0 : chunk;
-                const int b = (int)(k & 1);
-                const size_t bytes = ((size_t)(rows - 1) * (size_t)ldx + (size_t)ds) * esz;   // (the last row ends at column ds)
-                hipError_t e = hipSuccess;
-                if (k >= 2) e = hipStreamWaitEvent(copy_stream, formed[b], 0);   // staging buffer b has been consumed
-                if (e == hipSuccess)
-                    e = hipMemcpyAsync(Xd[b], (const unsigned char*)X + (size_t)r0 * (size_t)ldx * esz, bytes, hipMemcpyHostToDevice,
-                                       copy_stream);
-                if (e == hipSuccess) e = hipEventRecord(copied[b], copy_stream);
-                if (e == hipSuccess) e = hipStreamWaitEvent(stream, copied[b], 0);
-                if (e != hipSuccess) {
-                    rbl_set_error("set_data_from: upload failed: %s", hipGetErrorString(e));
-                    rc = RBL_ERR_HIP;
-                    break;
-                }
-                rc = fn((const void*)Xd[b], r0, rows);
-                if (rc == RBL_OK && hipEventRecord(formed[b], stream) != hipSuccess) rc = RBL_ERR_HIP;
-            }
-            if (hipStreamSynchronize(copy_stream) != hipSuccess && rc == RBL_OK) rc = RBL_ERR_HIP;
-        }
-        if (ms && hipEventRecord(t1, stream) != hipSuccess) ms = nullptr;
-        if (hipStreamSynchronize(stream) != hipSuccess && rc == RBL_OK) rc = RBL_ERR_HIP;
-        float el = 0.f;
-        if (ms && rc == RBL_OK && hipEventElapsedTime(&el, t0, t1) == hipSuccess) *ms = (double)el;
-        if (t0) (void)hipEventDestroy(t0);
-        if (t1) (void)hipEventDestroy(t1);
-        if (rc == RBL_ERR_HIP) {
-            const hipError_t e = hipGetLastError();
-            if (e != hipSuccess) rbl_set_error("set_data_from: %s", hipGetErrorString(e));
-        }
-        return rc;
-    }
-};
-
-static int set_data_from_impl(rbl_solver* h, const void* X, int dtype, int mem, int64_t ldx, const double* y, int scaling,
-                              int64_t ds) {
-    const int64_t n = h->n, d = h->d, ld = h->ld;
-    const size_t esz = src_esz(dtype);
-    {
-        std::vector<signed char> ys((size_t)n);
-        for (int64_t i = 0; i < n; ++i) ys[(size_t)i] = y[i] > 0 ? 1 : -1;
-        RBL_HIP(hipMemcpy(h->ysign, ys.data(), (size_t)n, hipMemcpyHostToDevice));
-    }
-    SrcPipe p;
-    p.stream = h->stream;
-    h->src_ms[0] = h->src_ms[1] = 0.0;
-    h->src_timed[0] = h->src_timed[1] = 0;
-    const int64_t SB = src_stat_rows();
-    int64_t chunk = n;
-    if (mem == RBL_MEM_HOST) {
-        long long cb = 64LL << 20;
-        if (const char* e = getenv("RBL_UPLOAD_CHUNK_BYTES")) {   // test hook: several chunks at small sizes
-            const long long v = atoll(e);
-            if (v > 0) cb = v;
-        }
-        chunk = (int64_t)(cb / (long long)(esz * (size_t)ldx));
-        if (scaling == RBL_SCALE_FIT) {   // whole row blocks of the statistics (the other modes keep rbl_set_data's chunk)
-            chunk = chunk / SB * SB;
-            if (chunk < SB) chunk = SB;
-        }
-        if (chunk < 1) chunk = 1;
-        if (chunk > n) chunk = n;
-        const size_t xbytes = ((size_t)(n - 1) * (size_t)ldx + (size_t)ds) * esz;
-        RBL_TRY(p.open_host(X, xbytes, (size_t)chunk * (size_t)ldx * esz));
-    }
-    u64* ovf = nullptr;   // RBL_STORE_F16: {entries that do not fit, first of them} written by the forming kernel
-    if (h->storage == RBL_STORE_F16) {
-        const u64 ovf0[2] = {0ull, ~0ull};
-        RBL_TRY(p.tmp.alloc(&ovf, 2));
-        RBL_HIP(hipMemcpy(ovf, ovf0, sizeof(ovf0), hipMemcpyHostToDevice));
-    }
-    double *dmean = nullptr, *dinv = nullptr;
-    std::vector<double> fit_mean, fit_scale;   // RBL_SCALE_FIT: kept in the handle after the forming pass has succeeded
-    if (scaling == RBL_SCALE_FIT) {
-        const int64_t nb = (n + SB - 1) / SB;
-        double *slab = nullptr, *shift = nullptr, *sums = nullptr;
-        RBL_TRY(p.tmp.alloc(&slab, (size_t)nb * ld * 2));
-        RBL_TRY(p.tmp.alloc(&shift, (size_t)ld));
-        RBL_TRY(p.tmp.alloc(&sums, (size_t)ld * 2));
-        RBL_HIP(hipMemsetAsync(slab, 0, sizeof(double) * (size_t)nb * ld * 2, h->stream));
-        std::vector<double> sh((size_t)ld, 0.0), st((size_t)ld * 2, 0.0);
-        if (mem == RBL_MEM_HOST) {   // the shift: the column's first row, widened
-            for (int64_t j = 0; j < ds; ++j) sh[(size_t)j] = src_host_widen((const unsigned char*)X + (size_t)j * esz, dtype);
-            RBL_HIP(hipMemcpyAsync(shift, sh.data(), sizeof(double) * ld, hipMemcpyHostToDevice, h->stream));
-            RBL_HIP(hipStreamSynchronize(h->stream));
-        } else {
-            RBL_HIP(hipMemsetAsync(shift, 0, sizeof(double) * ld, h->stream));
-            RBL_TRY(launch_src_row(dtype, X, ds, shift, h->stream));
-        }
-        double* slab2 = slab + (size_t)nb * ld;
-        RBL_TRY(p.pass(X, mem, esz, ldx, ds, n, chunk, [&](const void* Xc, int64_t r0, int64_t rows) {
-            return launch_src_colstats(dtype, Xc, ldx, rows, ds, shift, slab, slab2, ld, r0 / SB, h->stream);
-        }, &h->src_ms[0]));
-        h->src_timed[0] = 1;
-        RBL_TRY(launch_src_colreduce(slab, nb, ld, sums, h->stream));
-        RBL_TRY(launch_src_colreduce(slab2, nb, ld, sums + ld, h->stream));
-        RBL_HIP(hipMemcpyAsync(st.data(), sums, sizeof(double) * ld * 2, hipMemcpyDeviceToHost, h->stream));
-        RBL_HIP(hipMemcpyAsync(sh.data(), shift, sizeof(double) * ld, hipMemcpyDeviceToHost, h->stream));
-        RBL_HIP(hipStreamSynchronize(h->stream));
-        std::vector<double> mean((size_t)d, 0.0), scale((size_t)d, 1.0);
-        const double nn = (double)n;
-        for (int64_t j = 0; j < ds; ++j) {
-            // x = shift + dl:  mean = shift + sum dl / n,  var = sum dl^2 / n - (sum dl / n)^2  (dl is of the size of the
-            // column's spread, so nothing cancels against the column's mean)
-            const double m1 = st[(size_t)j] / nn;
-            const double mu = sh[(size_t)j] + m1;
-            double var = st[(size_t)(ld + j)] / nn - m1 * m1;
-            if (!std::isfinite(mu) || !std::isfinite(var)) {
-                rbl_set_error("set_data_from: column %lld has a non-finite mean or variance (mean %g, variance %g) - the "
-                              "source holds inf / nan or overflows fp64 sums", (long long)j, mu, var);
-                return RBL_ERR_INVALID;
-            }
-            if (!(var > 0.0)) var = 1.0;   // a constant column is left at x - mean = 0
-            mean[(size_t)j] = mu;
-            scale[(size_t)j] = std::sqrt(var);
-        }
-        fit_mean.swap(mean);
-        fit_scale.swap(scale);
-    }
-    if (scaling != RBL_SCALE_NONE) {
-        const std::vector<double>& use_mean = scaling == RBL_SCALE_FIT ? fit_mean : h->sc_mean;
-        const std::vector<double>& use_scale = scaling == RBL_SCALE_FIT ? fit_scale : h->sc_scale;
-        std::vector<double> mi((size_t)ld * 2, 0.0);
-        for (int64_t j = 0; j < ld; ++j) mi[(size_t)(ld + j)] = 1.0;
-        for (int64_t j = 0; j < ds; ++j) {
-            mi[(size_t)j] = use_mean[(size_t)j];
-            mi[(size_t)(ld + j)] = 1.0 / use_scale[(size_t)j];
-        }
-        dmean = h->colstats + 2 * ld;
-        dinv = h->colstats + 3 * ld;
-        RBL_HIP(hipMemcpy(dmean, mi.data(), sizeof(double) * ld * 2, hipMemcpyHostToDevice));
-    }
-    RBL_TRY(p.pass(X, mem, esz, ldx, ds, n, chunk, [&](const void* Xc, int64_t r0, int64_t rows) {
-        return launch_form_src(dtype, h->storage, h->D, ld, r0, Xc, ldx, h->ysign + r0, rows, ds, d, dmean, dinv, h->num_cu,
-                               h->stream, ovf);
-    }, &h->src_ms[1]));
-    h->src_timed[1] = 1;
-    if (ovf) {   // read once, after the last chunk
-        u64 got[2] = {0ull, 0ull};
-        RBL_HIP(hipMemcpy(got, ovf, sizeof(got), hipMemcpyDeviceToHost));
-        if (got[0] > 0) {
-            const long long r = (long long)(got[1] / (u64)d), c = (long long)(got[1] % (u64)d);
-            double raw = 0.0;
-            const unsigned char* at = (const unsigned char*)X + ((size_t)r * (size_t)ldx + (size_t)c) * esz;
-            if (mem == RBL_MEM_HOST) {
-                raw = src_host_widen(at, dtype);
-            } else {
-                unsigned char tmp8[8] = {0};
-                RBL_HIP(hipMemcpy(tmp8, at, esz, hipMemcpyDeviceToHost));
-                raw = src_host_widen(tmp8, dtype);
-            }
-            rbl_set_error("fp16 storage: %llu finite entries do not fit float16 (|x| >= 65520), first at row %lld, column %lld "
-                          "(value %g) - standardise the columns or use storage f32",
-                          got[0], r, c, raw);
-            return RBL_ERR_INVALID;
-        }
-    }
-    if (scaling == RBL_SCALE_FIT) {   // the vectors are the handle's only once D stands: a failed call leaves the old ones
-        h->sc_mean.swap(fit_mean);
-        h->sc_scale.swap(fit_scale);
-        h->sc_set = true;
-    }
-    return RBL_OK;
-}
-
-int rbl_set_data_from(rbl_solver* h, const void* X, int dtype, int mem, int64_t ldx, const double* y, int scaling, int flags) {
-    RBL_ENTER(h);
-    RBL_NOT_BORROWER(h, "set_data_from");
-    if (dtype != RBL_DTYPE_F64 && dtype != RBL_DTYPE_F32 && dtype != RBL_DTYPE_F16) {
-        rbl_set_error("set_data_from: unknown dtype %d (RBL_DTYPE_F64 / F32 / F16)", dtype);
-        return RBL_ERR_INVALID;
-    }
-    if (mem != RBL_MEM_HOST && mem != RBL_MEM_DEVICE) {
-        rbl_set_error("set_data_from: unknown memory kind %d (RBL_MEM_HOST / RBL_MEM_DEVICE)", mem);
-        return RBL_ERR_INVALID;
-    }
-    if (scaling != RBL_SCALE_NONE && scaling != RBL_SCALE_FIT && scaling != RBL_SCALE_APPLY) {
-        rbl_set_error("set_data_from: unknown scaling %d (RBL_SCALE_NONE / FIT / APPLY)", scaling);
-        return RBL_ERR_INVALID;
-    }
-    if (flags & ~RBL_DATA_ONES_COLUMN) {
-        rbl_set_error("set_data_from: unknown flags 0x%x", (unsigned)flags);
-        return RBL_ERR_INVALID;
-    }
-    const int64_t n = h->n, d = h->d;
-    const int64_t ds = d - ((flags & RBL_DATA_ONES_COLUMN) ? 1 : 0);
-    if (!X || !y || ds < 1 || ldx < ds) {
-        rbl_set_error("set_data_from: bad arguments (X %s, y %s, ldx=%lld, source columns=%lld)", X ? "given" : "NULL",
-                      y ? "given" : "NULL", (long long)ldx, (long long)ds);
-        return RBL_ERR_INVALID;
-    }
-    if ((size_t)(uintptr_t)X % src_esz(dtype) != 0) {
-        rbl_set_error("set_data_from: X is not aligned to its element size (%zu bytes)", src_esz(dtype));
-        return RBL_ERR_INVALID;
-    }
-    for (int64_t i = 0; i < n; ++i) {
-        if (!(y[i] == 1.0 || y[i] == -1.0)) {
-            rbl_set_error("set_data_from: labels must be +1/-1 (y[%lld] = %g)", (long long)i, y[i]);
-            return RBL_ERR_INVALID;
-        }
-    }
-    if (scaling == RBL_SCALE_FIT && h->nt != h->n) {
-        rbl_set_error("set_data_from: RBL_SCALE_FIT on a row-sharded handle (n = %lld of n_total = %lld) - reduce the column "
-                      "sums over the ranks in the driver, hand every rank the same vectors (rbl_set_scaling) and use "
-                      "RBL_SCALE_APPLY", (long long)h->n, (long long)h->nt);
-        return RBL_ERR_INVALID;
-    }
-    if (scaling == RBL_SCALE_FIT && n < 1) {
-        rbl_set_error("set_data_from: RBL_SCALE_FIT needs at least one row");
-        return RBL_ERR_INVALID;
-    }
-    if (scaling == RBL_SCALE_APPLY && !h->sc_set) {
-        rbl_set_error("set_data_from: RBL_SCALE_APPLY without a scaling - call rbl_set_scaling first");
-        return RBL_ERR_STATE;
-    }
-    if (n > 0) {
-        if (mem == RBL_MEM_DEVICE)
-            RBL_TRY(src_check_device_range(X, ((size_t)(n - 1) * (size_t)ldx + (size_t)ds) * src_esz(dtype), h->cfg.device));
-        h->data_ready = false;   // a failed upload leaves the handle without data
-        RBL_TRY(set_data_from_impl(h, X, dtype, mem, ldx, y, scaling, ds));
-    }
-    h->data_ready = true;
-    h->gram_ready = h->gram_local_done = false;
-    h->v_valid = false;
-    return RBL_OK;
-}
-
-int rbl_set_scaling(rbl_solver* h, const double* mean, const double* scale) {
-    RBL_ENTER(h);
-    if (!mean && !scale) {
-        h->sc_mean.clear();
-        h->sc_scale.clear();
-        h->sc_set = false;
-        return RBL_OK;
-    }
-    if (!mean || !scale) {
-        rbl_set_error("set_scaling: mean and scale go together (both NULL clears them)");
-        return RBL_ERR_INVALID;
-    }
-    for (int64_t j = 0; j < h->d; ++j) {
-        if (!std::isfinite(mean[j]) || !std::isfinite(scale[j]) || !(scale[j] > 0.0)) {
-            rbl_set_error("set_scaling: column %lld: mean %g / scale %g (finite values, scale > 0)", (long long)j, mean[j], scale[j]);
-            return RBL_ERR_INVALID;
-        }
-    }
-    h->sc_mean.assign(mean, mean + h->d);
-    h->sc_scale.assign(scale, scale + h->d);
-    h->sc_set = true;
-    return RBL_OK;
-}
-
-int rbl_get_scaling(rbl_solver* h, double* mean, double* scale, int* is_set) {
-    RBL_ENTER_ITER(h);
-    for (int64_t j = 0; j < h->d; ++j) {
-        if (mean) mean[j] = h->sc_set ? h->sc_mean[(size_t)j] : 0.0;
-        if (scale) scale[j] = h->sc_set ? h->sc_scale[(size_t)j] : 1.0;
-    }
-    if (is_set) *is_set = h->sc_set ? 1 : 0;
-    return RBL_OK;
-}
-
-int rbl_synth_local(rbl_solver* h, uint64_t seed, double class_sep, double flip_y) {
-    RBL_ENTER(h);
-    RBL_NOT_BORROWER(h, "synth_local");
-    // positions of the 2 informative + 2 redundant columns, the 2x2 mixing matrix of the redundant ones, the four
-    // clusters' covariance matrices A_k (entries uniform in (-1, 1)) and which hypercube vertex each cluster sits on
-    // (a random permutation; cluster k belongs to class k % 2) - make_classification's geometry draws - from a small
-    // host-side LCG keyed by the seed (identical on every rank)
-    uint64_t st = seed * 6364136223846793005ull + 1442695040888963407ull;
-    auto next = [&]() {
-        st = st * 6364136223846793005ull + 1442695040888963407ull;
-        return (uint32_t)(st >> 33);
-    };
-    int special[4] = {-1, -1, -1, -1};
-    const int nspec = h->d >= 4 ? 4 : (int)h->d;
-    for (int k = 0; k < nspec; ++k) {
-        for (;;) {
-            int c = (int)(next() % (uint32_t)h->d);
-            bool dup = false;
-            for (int j = 0; j < k; ++j) dup |= special[j] == c;
-            if (!dup) {
-                special[k] = c;
-                break;
-            }
-        }
-    }
-    double mix[4];
-    for (int k = 0; k < 4; ++k) mix[k] = 2.0 * ((double)next() / 2147483648.0) - 1.0;
-    double A16[16];
-    for (int k = 0; k < 16; ++k) A16[k] = 2.0 * ((double)next() / 2147483648.0) - 1.0;
-    int vertex[4] = {0, 1, 2, 3};
-    for (int i = 3; i > 0; --i) {
-        const int j = (int)(next() % (uint32_t)(i + 1));
-        std::swap(vertex[i], vertex[j]);
-    }
-    if (h->storage == RBL_STORE_F16) {
-        // the statistics of the unrounded draws; the matrix itself is written by rbl_synth_finish, in one rounding
-        h->synth.pending = true;
-        h->synth.seed = seed;
-        h->synth.class_sep = class_sep;
-        h->synth.flip_y = flip_y;
-        for (int k = 0; k < 4; ++k) {
-            h->synth.special[k] = special[k];
-            h->synth.vertex[k] = vertex[k];
-            h->synth.mix[k] = mix[k];
-        }
-        for (int k = 0; k < 16; ++k) h->synth.A16[k] = A16[k];
-        h->data_ready = false;
-        RBL_TRY(launch_synth_stats(h->n, h->ld, h->d, h->off, seed, class_sep, flip_y, special, mix, A16, vertex, h->ysign, h->slab,
-                                   h->colstats, h->colstats + h->ld, h->num_cu, h->stream));
-        RBL_HIP(hipStreamSynchronize(h->stream));
-        return RBL_OK;
-    }
-    RBL_TRY(launch_synth(h->storage, h->D, h->n, h->ld, h->d, h->off, seed, class_sep, flip_y, special, mix, A16, vertex,
-                         h->ysign, h->stream));
-    // column sums / sums of squares of the local rows -> colstats[0 .. 2 ld)
-    RBL_TRY(launch_colstats(h->storage, h->D, h->n, h->ld, h->slab, h->colstats, h->colstats + h->ld, h->num_cu,
-                            h->stream));
-    RBL_HIP(hipStreamSynchronize(h->stream));
-    return RBL_OK;
-}
-
-int rbl_synth_finish(rbl_solver* h) {
-    RBL_ENTER(h);
-    RBL_NOT_BORROWER(h, "synth_finish");
-    // preprocessing.scale (load_data.py:115): (x - mean) / std with the population std
-    const int64_t ld = h->ld;
-    std::vector<double> st((size_t)ld * 4, 0.0);
-    RBL_HIP(hipMemcpy(st.data(), h->colstats, sizeof(double) * ld * 2, hipMemcpyDeviceToHost));
-    const double nt = (double)h->nt;
-    for (int64_t j = 0; j < ld; ++j) {
-        const double mean = st[j] / nt;
-        double var = st[ld + j] / nt - mean * mean;
-        if (!(var > 0.0)) var = 1.0;
-        st[2 * ld + j] = mean;
-        st[3 * ld + j] = 1.0 / std::sqrt(var);
-    }
-    RBL_HIP(hipMemcpy(h->colstats + 2 * ld, st.data() + 2 * ld, sizeof(double) * ld * 2, hipMemcpyHostToDevice));
-    if (h->storage == RBL_STORE_F16) {
-        if (!h->synth.pending) {
-            rbl_set_error("synth_finish: call rbl_synth_local first");
-            return RBL_ERR_STATE;
-        }
-        RBL_TRY(launch_synth_f16(h->D, h->n, ld, h->d, h->off, h->synth.seed, h->synth.class_sep, h->synth.flip_y, h->synth.special,
-                                 h->synth.mix, h->synth.A16, h->synth.vertex, h->colstats + 2 * ld, h->colstats + 3 * ld, h->stream));
-        h->synth.pending = false;
-    } else {
-        RBL_TRY(launch_standardize_negy(h->storage, h->D, h->n, ld, h->d, h->colstats + 2 * ld, h->colstats + 3 * ld,
-                                        h->ysign, h->stream));
-    }
-    RBL_HIP(hipStreamSynchronize(h->stream));
-    h->data_ready = true;
-    h->gram_ready = h->gram_local_done = false;
-    h->v_valid = false;
-    return RBL_OK;
-}
-
-int rbl_generate_synthetic(rbl_solver* h, uint64_t seed, double class_sep, double flip_y) {
-    RBL_ENTER(h);
-    RBL_NOT_BORROWER(h, "generate_synthetic");
-    if (h->nt != h->n) {
-        rbl_set_error("generate_synthetic: sharded problem - use rbl_synth_local, sum RBL_BUF_COLSTATS, rbl_synth_finish");
-        return RBL_ERR_STATE;
-    }
-    RBL_TRY(rbl_synth_local(h, seed, class_sep, flip_y));
-    return rbl_synth_finish(h);
-}
-
-int rbl_set_penalty(rbl_solver* h, const double* l1, const double* l2) {
-    RBL_ENTER(h);
-    if (h->iter > 0) {
-        rbl_set_error("set_penalty: the handle has iterated already (iter = %lld)", (long long)h->iter);
-        return RBL_ERR_STATE;
-    }
-    if (!l1 && !l2) {
-        rbl_set_error("set_penalty: l1 and l2 are both NULL");
-        return RBL_ERR_INVALID;
-    }
-    if (!h->cfg.objective_only && h->cfg.wstep == RBL_WSTEP_SMOOTH_L1) {
-        rbl_set_error("set_penalty: the smoothed-l1 w-step (sADMM) has no per-coordinate penalties");
-        return RBL_ERR_INVALID;
-    }
-    const int64_t d = h->d, ld = h->ld;
-    for (int k = 0; k < 2; ++k) {
-        const double* v = k ? l2 : l1;
-        for (int64_t j = 0; v && j < d; ++j)
-            if (!(v[j] >= 0.0) || !std::isfinite(v[j])) {
-                rbl_set_error("set_penalty: %s[%lld] = %g - penalties must be finite and >= 0", k ? "l2" : "l1", (long long)j,
-                              v[j]);
-                return RBL_ERR_INVALID;
-            }
-    }
-    std::vector<double> host((size_t)(2 * ld + 8), 0.0);
-    double l2max = 0.0;
-    for (int64_t j = 0; j < d; ++j) {
-        if (l1) host[(size_t)j] = l1[j];
-        if (l2) {
-            host[(size_t)(ld + j)] = l2[j];
-            if (l2[j] > l2max) l2max = l2[j];
-        }
-    }
-    if (!h->pen) RBL_TRY(h->mem.alloc(&h->pen, (size_t)(2 * ld + 8)));
-    RBL_HIP(hipMemcpyAsync(h->pen, host.data(), sizeof(double) * host.size(), hipMemcpyHostToDevice, h->stream));
-    RBL_HIP(hipStreamSynchronize(h->stream));
-    h->pen_host.assign((size_t)(2 * d), 0.0);
-    for (int64_t j = 0; j < d; ++j) {
-        h->pen_host[(size_t)j] = host[(size_t)j];
-        h->pen_host[(size_t)(d + j)] = host[(size_t)(ld + j)];
-    }
-    h->ww.pen_l1 = h->pen;
-    h->ww.pen_l2 = h->pen + ld;
-    h->ww.pen_l2max = l2max;
-    return RBL_OK;
-}
-
-int rbl_get_penalty(rbl_solver* h, double* l1, double* l2, int* is_set) {
-    RBL_ENTER_ITER(h);
-    const int64_t d = h->d;
-    if (is_set) *is_set = h->pen ? 1 : 0;
-    for (int64_t j = 0; j < d; ++j) {
-        if (l1) l1[j] = h->pen ? h->pen_host[(size_t)j] : 0.0;
-        if (l2) l2[j] = h->pen ? h->pen_host[(size_t)(d + j)] : 0.0;
-    }
-    return RBL_OK;
-}
-
-int rbl_set_labels(rbl_solver* h, const double* y) {
-    RBL_ENTER(h);
-    if (!h->borrower) {
-        rbl_set_error("set_labels: only a handle that borrows its data (rbl_create_shared) can carry labels of its own");
-        return RBL_ERR_STATE;
-    }
-    if (h->iter > 0) {
-        rbl_set_error("set_labels: the handle has iterated already (iter = %lld)", (long long)h->iter);
-        return RBL_ERR_STATE;
-    }
-    if (h->in_group) {
-        rbl_set_error("set_labels: the handle is a member of a group - destroy the group first");
-        return RBL_ERR_STATE;
-    }
-    if (h->nt != h->n) {
-        rbl_set_error("set_labels: row-sharded handle (n=%lld of %lld) - the distributed z-steps carry no labels of their own",
-                      (long long)h->n, (long long)h->nt);
-        return RBL_ERR_INVALID;
-    }
-    if (!y) {
-        rbl_set_error("set_labels: y is NULL");
-        return RBL_ERR_INVALID;
-    }
-    const int64_t n = h->n;
-    for (int64_t i = 0; i < n; ++i)
-        if (!(y[i] == 1.0 || y[i] == -1.0)) {
-            rbl_set_error("set_labels: labels must be +1/-1 (y[%lld] = %g)", (long long)i, y[i]);
-            return RBL_ERR_INVALID;
-        }
-    RBL_HIP(hipStreamSynchronize(h->stream));
-    std::vector<signed char> yo((size_t)n), r((size_t)n), ys((size_t)n);
-    RBL_HIP(hipMemcpy(yo.data(), h->ysign, (size_t)n, hipMemcpyDeviceToHost));
-    bool differs = false;
-    for (int64_t i = 0; i < n; ++i) {
-        ys[(size_t)i] = y[i] > 0 ? 1 : -1;
-        r[(size_t)i] = (signed char)(ys[(size_t)i] * yo[(size_t)i]);
-        differs = differs || r[(size_t)i] < 0;
-    }
-    if (!differs && !h->rs) return RBL_OK;   // the owner's labels on an ordinary borrower: nothing changes
-    // z and lambda move from the sign convention they are stored in to the new one (both start as constants)
-    std::vector<double> zh, lh;
-    if (h->z) {
-        zh.resize((size_t)n);
-        lh.resize((size_t)n);
-        RBL_HIP(hipMemcpy(zh.data(), h->z, sizeof(double) * n, hipMemcpyDeviceToHost));
-        RBL_HIP(hipMemcpy(lh.data(), h->lam, sizeof(double) * n, hipMemcpyDeviceToHost));
-        if (h->rs) {
-            flip_rows(h, zh.data());
-            flip_rows(h, lh.data());
-        }
-    }
-    if (!differs) {   // the owner's labels: an ordinary borrower
-        if (h->rs) h->mem.release(h->rs);
-        h->rs = nullptr;
-        h->rs_host.clear();
-        h->ys_host.clear();
-    } else {
-        if (!h->rs) RBL_TRY(h->mem.alloc(&h->rs, (size_t)n));
-        RBL_HIP(hipMemcpy(h->rs, r.data(), (size_t)n, hipMemcpyHostToDevice));
-        h->rs_host.swap(r);
-        h->ys_host.swap(ys);
-    }
-    if (h->z) {
-        RBL_TRY(upload_rows(h, h->z, zh.data()));
-        RBL_TRY(upload_rows(h, h->lam, lh.data()));
-    }
-    if (!h->cfg.objective_only) {
-        // the sign is not part of the single-sweep erm pass' in-pass prox: such a handle runs the two-pass iteration
-        const char* nf = getenv("RBL_NO_FUSE");
-        h->fused_ok = !h->rs && !h->sorted_path && !(nf && nf[0] == '1') && sweep_erm_supported(h->storage, h->ld);
-    }
-    h->z_ready = h->p_valid = h->p_pending = h->pred_valid = false;
-    h->keys_ready = h->s32.m_ready = false;
-    return RBL_OK;
-}
-
-// One-vs-rest decision on the rows of `data`: cls[i] = argmax_j x_i . w_j (ties: the lowest j).  D = -y X, so the
-// scores are -y_i (D w_j)_i: the multi-column V product of the groups (sweep_multi.hip), ceil(k / k_per_pass) passes
-// over D, each followed by the row-wise comparison against the best score so far.
-int rbl_decide_multi(rbl_solver* h, int k, const double* W, int32_t* cls) {
-    RBL_ENTER(h);
-    if (!h->data_ready) {
-        rbl_set_error("decide_multi: no data");
-        return RBL_ERR_STATE;
-    }
-    if (k < 1 || k > 64 || !W || !cls) {
-        rbl_set_error("decide_multi: 1..64 columns (got %d), W and cls not NULL", k);
-        return RBL_ERR_INVALID;
-    }
-    const int64_t n = h->n, ld = h->ld, d = h->d;
-    if (n <= 0) return RBL_OK;
-    hipStream_t s = h->stream;
-    const bool multi = sweep_multi_supported(h->storage, ld);
-    const int kpp = multi ? sweep_multi_k(h->storage, ld) : 1;
-    DevArena mem;   // scratch of this call, freed on return (after the stream wait)
-    double *dw = nullptr, *dv = nullptr, *best = nullptr;
-    int* dcls = nullptr;
-    std::vector<double> wp((size_t)ld * k, 0.0);
-    for (int j = 0; j < k; ++j)
-        for (int64_t i = 0; i < d; ++i) wp[(size_t)j * ld + i] = W[(size_t)j * d + i];
-    RBL_TRY(mem.alloc(&dw, wp.size()));
-    RBL_TRY(mem.alloc(&dv, (size_t)n * kpp));
-    RBL_TRY(mem.alloc(&best, (size_t)n));
-    RBL_TRY(mem.alloc(&dcls, (size_t)n));
-    RBL_HIP(hipMemcpy(dw, wp.data(), sizeof(double) * wp.size(), hipMemcpyHostToDevice));
-    int rc = RBL_OK;
-    for (int j0 = 0; j0 < k && rc == RBL_OK; j0 += kpp) {
-        const int kk = std::min(kpp, k - j0);
-        if (!multi) {   // outside the multi-column kernels' widths: the single-column pass per column
-            rc = launch_gemv(h->storage, h->D, n, ld, dw + (size_t)j0 * ld, dv, h->num_cu, s);
-        } else {
-            const double* w[RBL_MULTI_KMAX];
-            double* v[RBL_MULTI_KMAX];
-            for (int j = 0; j < kk; ++j) {
-                w[j] = dw + (size_t)(j0 + j) * ld;
-                v[j] = dv + (size_t)j * n;
-            }
-            rc = launch_sweep_v_multi(h->storage, h->D, n, ld, kk, w, nullptr, nullptr, v, nullptr, nullptr, nullptr, h->num_cu, s);
-        }
-        if (rc == RBL_OK) rc = launch_decide_rows(n, kk, j0, dv, h->ysign, best, dcls, s);
-    }
-    if (rc == RBL_OK && (hipMemcpyAsync(cls, dcls, sizeof(int32_t) * n, hipMemcpyDeviceToHost, s) != hipSuccess)) rc = RBL_ERR_HIP;
-    if (hipStreamSynchronize(s) != hipSuccess && rc == RBL_OK) rc = RBL_ERR_HIP;   // before the scratch goes
-    if (rc == RBL_ERR_HIP) rbl_set_error("decide_multi: %s", hipGetErrorString(hipGetLastError()));
-    return rc;
-}
-
-int rbl_get_labels(rbl_solver* h, double* y_out) {
-    RBL_ENTER(h);
-    if (h->rs) {   // labels of its own (rbl_set_labels)
-        for (int64_t i = 0; i < h->n; ++i) y_out[i] = (double)h->ys_host[(size_t)i];
-        return RBL_OK;
-    }
-    std::vector<signed char> t((size_t)h->n);
-    RBL_HIP(hipMemcpy(t.data(), h->ysign, (size_t)h->n, hipMemcpyDeviceToHost));
-    for (int64_t i = 0; i < h->n; ++i) y_out[i] = (double)t[i];
-    return RBL_OK;
-}
-
-int rbl_gram_local(rbl_solver* h) {
-    RBL_ENTER(h);
-    RBL_NOT_BORROWER(h, "gram_local");
-    if (!h->data_ready || h->cfg.objective_only) {
-        rbl_set_error("gram: no data (or objective-only handle)");
-        return RBL_ERR_STATE;
-    }
-    RBL_TRY(launch_gram(h->storage, h->D, h->n, h->ld, h->d, h->slab, h->G, h->num_cu, h->stream));
-    RBL_HIP(hipStreamSynchronize(h->stream));
-    h->gram_local_done = true;
-    h->ww.eig_ok = false;
-    return RBL_OK;
-}
-
-int rbl_gram_finish(rbl_solver* h) {
-    RBL_ENTER(h);
-    RBL_NOT_BORROWER(h, "gram_finish");
-    if (!h->gram_local_done) {
-        rbl_set_error("gram_finish before gram_local");
-        return RBL_ERR_STATE;
-    }
-    double lam = 0.0;
-    RBL_TRY(launch_power_iteration(h->G, h->ld, h->ww.yk, h->ww.Gy, h->ww.scal, 100, &lam, h->stream));
-    h->L = 1.02 * lam;
-    if (!(h->L > 0.0)) h->L = 1.0;
-    // l2 w-step: RBL_RIDGE_EIG=1 replaces the warm-started CG by a one-time eigendecomposition of G (eig.hip).
-    // Opt-in: it makes an iteration 0.13 ms shorter at d = 1000 (14 CG iterations -> 5 small launches) but the
-    // Jacobi sweeps cost 0.8 s of setup there - 6000 iterations to break even, and a solve runs a few hundred
-    h->ww.eig_ok = false;
-    static const bool ridge_eig = [] {
-        const char* e = getenv("RBL_RIDGE_EIG");
-        return e && e[0] == '1';
-    }();
-    if (h->cfg.wstep == RBL_WSTEP_L2 && h->ld <= 2048 && ridge_eig) {
-        const size_t nn = (size_t)h->ld * (size_t)h->ld;
-        if (!h->ww.eig_Vt) {
-            double *Vt = nullptr, *V = nullptr, *lambda = nullptr;
-            RBL_TRY(h->shared->alloc(&Vt, nn));   // derived from G alone: shared with the borrowers
-            RBL_TRY(h->shared->alloc(&V, nn));
-            RBL_TRY(h->shared->alloc(&lambda, (size_t)h->ld));
-            h->ww.eig_V = V;
-            h->ww.eig_lambda = lambda;
-            h->ww.eig_Vt = Vt;   // set last: it says the basis buffers are there
-        }
-        int rc = RBL_OK, sweeps = 0;
-        {
-            DevArena tmp;   // Jacobi scratch, freed after the stream wait
-            double* Bt = nullptr;
-            unsigned long long* off = nullptr;
-            RBL_TRY(tmp.alloc(&Bt, nn));
-            RBL_TRY(tmp.alloc(&off, 1));
-            rc = launch_eig_jacobi(h->G, h->ld, h->d, Bt, h->ww.eig_Vt, h->ww.eig_V, h->ww.eig_lambda, off, h->stream, &sweeps);
-            (void)hipStreamSynchronize(h->stream);
-        }
-        RBL_TRY(rc);
-        h->ww.eig_ok = sweeps > 0;
-        h->eig_sweeps = sweeps;
-    }
-    h->gram_ready = true;
-    return RBL_OK;
-}
-
-int rbl_get_D(rbl_solver* h, double* out) {
-    RBL_ENTER(h);
-    if (!h->data_ready) {
-        rbl_set_error("get_D: no data");
-        return RBL_ERR_STATE;
-    }
-    const int64_t n = h->n, d = h->d;
-    int64_t chunk = (64LL << 20) / (8 * d);
-    if (chunk < 1) chunk = 1;
-    DevArena mem;   // the conversion buffer, freed on return
-    double* tmp = nullptr;
-    RBL_TRY(mem.alloc(&tmp, (size_t)chunk * d));
-    for (int64_t r0 = 0; r0 < n; r0 += chunk) {
-        const int64_t rows = n - r0 < chunk ? n - r0 : chunk;
-        RBL_TRY(launch_D_to_f64(h->storage, (const char*)h->D + (size_t)r0 * h->ld * h->esz, h->ld, rows, d, tmp, h->stream));
-        if (hipMemcpyAsync(out + r0 * d, tmp, sizeof(double) * rows * d, hipMemcpyDeviceToHost, h->stream) != hipSuccess ||
-            hipStreamSynchronize(h->stream) != hipSuccess)
-            return RBL_ERR_HIP;
-    }
-    if (h->rs)   // -y_k * X = r * (-y_owner * X)
-        for (int64_t i = 0; i < n; ++i)
-            if (h->rs_host[(size_t)i] < 0)
-                for (int64_t j = 0; j < d; ++j) out[i * d + j] = -out[i * d + j];
     return RBL_OK;
 }
 
@@ -1783,986 +523,6 @@ int rbl_get_sigma(rbl_solver* h, double* alphas, double* betas) {
     return RBL_OK;
 }
 
-// ------------------------------------------------------------------------------- phases
-static int require_ready(rbl_solver* h) {
-    if (h->cfg.objective_only) {
-        rbl_set_error("objective-only handle cannot step");
-        return RBL_ERR_STATE;
-    }
-    if (!h->data_ready) {
-        rbl_set_error("step before set_data / generate_synthetic");
-        return RBL_ERR_STATE;
-    }
-    if (!h->gram_ready) {
-        if (h->nt != h->n) {
-            rbl_set_error("sharded problem: call rbl_gram_local, sum RBL_BUF_G over ranks, rbl_gram_finish first");
-            return RBL_ERR_STATE;
-        }
-        RBL_TRY(rbl_gram_local(h));
-        RBL_TRY(rbl_gram_finish(h));
-    }
-    return RBL_OK;
-}
-
-// erm problems run ONE sweep of D per iteration (sweep_erm.hip): the pass of iteration k also
-// performs the z-step and the q = D^T c accumulation of iteration k+1.  `z_ready` says that
-// z_next / q / zz already hold that work for rho == the predicted rho_{k+1}; the phases below
-// then skip it.  A wrong prediction only clears the flag (the unfused kernels redo it).
-static inline double* q_pinit(rbl_solver* h) { return h->q + h->ld; }      // D^T lambda (first pass only)
-static inline double* q_zz(rbl_solver* h) { return h->q + 2 * h->ld; }     // ||z||^2 of the current z
-
-// kernel events in this iteration?  (every profile_every-th one: an event record costs ~5 us of stream time)
-static inline bool prof_now(const rbl_solver* h) { return h->profile && (h->iter % h->profile_every) == 0; }
-
-int rbl_phase_m(rbl_solver* h) {
-    RBL_ENTER_ITER(h);
-    RBL_TRY(require_ready(h));
-    h->step_rho = h->rho;
-    if (h->phase_timing) RBL_HIP(hipEventRecord(h->ev[0], h->stream));
-    if (h->fused_ok && h->z_ready) return RBL_OK;
-    RBL_TRY(ensure_v(h));
-    if (h->sorted_path) {
-        if (!h->zb.checked) RBL_TRY(zb_setup(h));
-        // which z-step will follow on a single handle: the sort-free one (banded weights), else the sort - with 32-bit
-        // keys from the second iteration on (iteration 0 starts from equal m: one run) unless a step was not certified
-        const bool banded_next = h->zb.enabled && h->nt == h->n && h->iter > 0 && h->iter >= h->zb.skip_until;
-        const bool s32 = h->s32.pin && !h->s32.off && h->nt == h->n && h->n >= 2 && h->iter > 0 &&
-                         h->iter >= h->s32.skip_until && !banded_next;
-        h->s32.m_ready = false;
-        if (s32) {
-            // m = D w - lambda/rho (algorithms.py:89) and its range (the 32-bit keys are a fixed-point image on it)
-            RBL_TRY(launch_make_m_range(h->n, h->step_rho, h->v, h->lam, h->m, h->s32.mm, h->stream, h->rs));
-            h->s32.m_ready = true;
-            h->keys_ready = false;
-        } else {
-            // m and, in the same pass, the 64-bit sort's input for the z-step: keys of m with the GLOBAL row id as
-            // payload (single GPU: off = 0; sharded: what rbl_zd_sort_local sorts)
-            RBL_TRY(launch_make_m_keys(h->n, h->step_rho, h->v, h->lam, h->m, h->sw.keys[0], h->sw.vals[0], (u32)h->off,
-                                       h->stream, h->rs));
-            h->keys_ready = true;
-        }
-    }
-    return RBL_OK;
-}
-
-int rbl_phase_z(rbl_solver* h, const void* m_all_dev) {
-    RBL_ENTER_ITER(h);
-    const double rho = h->step_rho;
-    if (h->fused_ok && h->z_ready) {
-        std::swap(h->z, h->z_next);  // the z-step of this iteration was done by the previous pass
-    } else if (!h->sorted_path) {
-        RBL_TRY(launch_erm_zc(h->cfg.loss, h->n, h->sigma0, rho, h->v, h->lam, h->m, h->z, h->c, h->stream, h->rs));
-        if (h->fused_ok) RBL_TRY(launch_sumsq(h->n, h->z, h->partials, q_zz(h), h->stream));
-    } else {
-        const double* msrc = (const double*)m_all_dev;
-        if (!msrc) {
-            if (h->nt != h->n) {
-                rbl_set_error("phase_z: sharded rank-weighted problem needs the gathered m vector");
-                return RBL_ERR_STATE;
-            }
-            msrc = h->m;
-        }
-        if (!h->zb.checked) RBL_TRY(zb_setup(h));
-        h->zb.mode = 0;
-        // iteration 0 starts from w = 0, lambda = 0: every m is equal, the keys tie across every band edge
-        if (h->zb.enabled && h->nt == h->n && h->keys_ready && msrc == h->m && h->iter > 0 && h->iter >= h->zb.skip_until) {
-            h->zb.seq = (h->zb.seq & 0x3fffffff) + 1;
-            h->zb.pin[0] = 0;
-            RBL_TRY(launch_zband(h->cfg.loss, h->zb.cfg, h->n, rho, h->sw.keys[0], h->m, h->z, h->lam, h->c, h->zb.st, h->zb.hist,
-                                 h->zb.part, h->zb.pin, h->zb.seq, h->pw.counters, h->stream, h->rs));
-            h->zb.used = true;
-            h->zb.q_done = false;
-            h->zb.c_ready = true;   // the element-wise pass wrote c = z + lambda/rho as well
-            h->zb.mode = 1;
-        } else {
-            h->zb.c_ready = false;
-            RBL_TRY(z_step_sorted(h, msrc, rho));
-        }
-    }
-    if (h->phase_timing) RBL_HIP(hipEventRecord(h->ev[1], h->stream));
-    return RBL_OK;
-}
-
-int rbl_phase_z_external(rbl_solver* h, const double* z) {
-    RBL_ENTER(h);   // a w-step enqueued ahead of time was computed for the library's own z: put w_k back
-    if (!z) {
-        rbl_set_error("phase_z_external: z is NULL");
-        return RBL_ERR_INVALID;
-    }
-    RBL_TRY(rbl_phase_m(h));   // opens the iteration (step_rho); a no-op for what it has computed already
-    if (h->rs) {
-        RBL_HIP(hipStreamSynchronize(h->stream));
-        RBL_TRY(upload_rows(h, h->z, z));   // the caller's z is in the handle's own sign convention
-    } else {
-        RBL_HIP(hipMemcpyAsync(h->z, z, sizeof(double) * h->n, hipMemcpyHostToDevice, h->stream));
-    }
-    RBL_HIP(hipStreamSynchronize(h->stream));   // the caller's buffer may go away
-    rbl_note_host_sync();
-    // a z-step the previous single-sweep pass did ahead of time (z_next, q, ||z||^2) is void: the unfused kernels
-    // rebuild q in rbl_phase_q; erm keeps c = z + lambda/rho and ||z||^2 next to z (launch_erm_zc), rebuild both
-    h->z_ready = false;
-    h->keys_ready = false;
-    h->zb.used = h->zb.c_ready = false;   // whatever the library's own z-step left behind is void
-    h->s32.used = h->s32.m_ready = false;
-    h->zb.mode = 0;
-    if (!h->sorted_path) {
-        RBL_TRY(launch_make_c(h->n, h->z, h->lam, h->step_rho, h->c, h->stream));
-        if (h->fused_ok) RBL_TRY(launch_sumsq(h->n, h->z, h->partials, q_zz(h), h->stream));
-    }
-    if (h->phase_timing) RBL_HIP(hipEventRecord(h->ev[1], h->stream));
-    return RBL_OK;
-}
-
-int rbl_phase_w_external(rbl_solver* h, const double* w) {
-    RBL_ENTER_ITER(h);
-    RBL_TRY(zb_resolve(h));   // the caller's w was formed from a z (and q) it could only read through the resolving entries
-    if (!w) {
-        rbl_set_error("phase_w_external: w is NULL");
-        return RBL_ERR_INVALID;
-    }
-    // w_prev = w_k: while a w-step enqueued ahead of time is in flight w_k already sits in w_prev
-    if (!h->spec_w)
-        RBL_HIP(hipMemcpyAsync(h->w_prev, h->w, sizeof(double) * h->ld, hipMemcpyDeviceToDevice, h->stream));
-    h->spec_w = false;
-    h->spec_timed = false;
-    RBL_HIP(hipMemsetAsync(h->w, 0, sizeof(double) * h->ld, h->stream));
-    RBL_HIP(hipMemcpyAsync(h->w, w, sizeof(double) * h->d, hipMemcpyHostToDevice, h->stream));
-    RBL_HIP(hipStreamSynchronize(h->stream));
-    rbl_note_host_sync();
-    RBL_TRY(launch_w_stats(h->ld, h->w, h->w_prev, h->red2, h->stream, h->ww.pen_l1, h->ww.pen_l2,
-                           pen_terms(h)));   // dual residual, regulariser terms
-    // no rho prediction was made for this w: the dual update runs unfused, and the d-space recurrence for
-    // D^T lambda is re-seeded by the next rbl_phase_q
-    h->pred_valid = false;
-    h->p_valid = h->p_pending = false;
-    h->z_ready = false;        // (a caller that skipped rbl_phase_q: nothing of a previous pass is pending any more)
-    h->v_valid = false;
-    h->inner_iters = 0;
-    h->ww.form = -1;
-    if (h->phase_timing) RBL_HIP(hipEventRecord(h->ev[3], h->stream));
-    return RBL_OK;
-}
-
-int rbl_phase_q(rbl_solver* h) {
-    RBL_ENTER_ITER(h);
-    if (!(h->fused_ok && h->z_ready)) {
-        if (prof_now(h)) RBL_HIP(hipEventRecord(h->kev[2], h->stream));
-        // rank-weighted problems: the z-step's scatter writes z alone (one random access per row); c = z +
-        // lambda/rho (algorithms.py:192) is a streaming pass here.  (Forming it inside the sweep was tried:
-        // the per-row division on the sweep's critical path costs 0.9 ms, the streaming pass 30 us.)
-        if (h->sorted_path && !h->zb.c_ready) RBL_TRY(launch_make_c(h->n, h->z, h->lam, h->step_rho, h->c, h->stream));
-        h->zb.c_ready = false;
-        h->zb.q_done = h->zb.used;   // q of an unsettled sort-free z-step (zb_resolve redoes it with the z-step)
-        h->s32.q_done = h->s32.used; // ... and of an unsettled 32-bit sort
-        RBL_TRY(launch_gemvt(h->storage, h->D, h->n, h->ld, h->c, h->slab, h->q, h->num_cu, h->stream,
-                             prof_now(h) ? h->kev[3] : nullptr));
-        h->nd_launches += 1;
-        if (prof_now(h)) h->kev_pending[1] = h->n > 0;
-        if (h->fused_ok && !h->p_valid) {
-            // D^T lambda seeds the d-space recurrence used to predict the primal residual
-            RBL_TRY(launch_gemvt(h->storage, h->D, h->n, h->ld, h->lam, h->slab, q_pinit(h), h->num_cu, h->stream));
-            h->nd_launches += 1;
-            h->p_pending = true;
-        }
-    }
-    h->pending_mask = (h->fused_ok && h->z_ready) ? 0 : 1;  // a fused pass' q was already summed with its residuals
-    h->z_ready = false;  // consumed: q (and zz) now belong to the iteration in flight
-    if (h->phase_timing) RBL_HIP(hipEventRecord(h->ev[2], h->stream));
-    return RBL_OK;
-}
-
-// the single-sweep iteration's statistics kernel (launch_predict_rho) knows the two norms only: the weighted sums
-// come from a launch of their own behind it
-static int pen_terms_after_predict(rbl_solver* h) {
-    if (!h->pen) return RBL_OK;
-    return launch_pen_terms(h->ld, h->w, h->ww.pen_l1, h->ww.pen_l2, pen_terms(h), h->stream);
-}
-
-static int phase_w_body(rbl_solver* h) {
-    const bool spec = h->spec_w;   // this w-step (and what follows it) was enqueued by the previous rbl_phase_finish
-    h->spec_w = false;
-    int wstep = h->cfg.wstep;
-    if (!spec && wstep != RBL_WSTEP_L1)   // the lasso kernel saves its warm start itself
-        RBL_HIP(hipMemcpyAsync(h->w_prev, h->w, sizeof(double) * h->ld, hipMemcpyDeviceToDevice, h->stream));
-    if (h->p_pending) {
-        RBL_HIP(hipMemcpyAsync(h->p, q_pinit(h), sizeof(double) * h->ld, hipMemcpyDeviceToDevice, h->stream));
-        h->p_pending = false;
-        h->p_valid = true;
-    }
-    // The lasso's active-set kernel reports its status through pinned memory; the statistics of
-    // the new w and the rho prediction are enqueued behind it before the host looks at the
-    // status, so the device works through them while the host waits.  Only when the kernel did
-    // not converge (FISTA then changes w again) are they enqueued a second time.
-    bool fs_pending = spec;
-    const bool predict = h->fused_ok && h->p_valid;
-    // the active-set lasso kernel leaves G w of its solution in ww.Gy (it needs the gradient for its
-    // own optimality test): no d x d product for the rho prediction unless FISTA had to take over
-    bool gw_ready = predict && wstep == RBL_WSTEP_L1;
-    if (!spec) {
-        RBL_TRY(run_wstep(wstep, h->G, h->ld, h->q, h->step_rho, h->cfg.reg, h->smooth_t, h->L, h->cfg.w_tol, 100000,
-                          h->w, h->ww, &h->inner_iters, h->stream, &fs_pending, nullptr, h->w_prev, predict));
-        // the persistent CG / nonlinear-CG kernels leave G w of their solution in ww.Gy as well
-        if (wstep != RBL_WSTEP_L1) gw_ready = predict && h->ww.gw_valid;
-    }
-    auto after_w = [&]() -> int {
-        if (predict) {
-            if (!gw_ready) RBL_TRY(launch_symv(h->G, h->ld, h->w, h->ww.Gy, h->stream));
-            RBL_TRY(launch_predict_rho(h->ld, h->q, h->p, h->p_alt, h->w, h->w_prev, h->ww.Gy, q_zz(h), h->step_rho,
-                                       217.0 * (double)h->d, h->pred, h->red2, h->stream));
-            RBL_TRY(pen_terms_after_predict(h));
-        } else {
-            RBL_TRY(launch_w_stats(h->ld, h->w, h->w_prev, h->red2, h->stream, h->ww.pen_l1, h->ww.pen_l2, pen_terms(h)));
-        }
-        return RBL_OK;
-    };
-    if (!spec) RBL_TRY(after_w());
-    if (fs_pending) {
-        bool fell_back = false;
-        RBL_TRY(finish_wstep_l1(h->G, h->ld, h->q, h->step_rho, h->cfg.reg, h->L, h->cfg.w_tol, 100000, h->w, h->ww,
-                                &h->inner_iters, h->stream, &fell_back));
-        if (fell_back) {
-            gw_ready = false;
-            RBL_TRY(after_w());
-        }
-    }
-    h->pred_valid = false;
-    if (predict) {
-        std::swap(h->p, h->p_alt);   // the recurrence's output becomes D^T lambda of the next iteration
-        // test hook: RBL_DEBUG_MISPREDICT_EVERY=N corrupts every N-th prediction so that the
-        // verification + unfused recomputation path is exercised (tests/test_gpu_solver.py)
-        static const int mis_every = [] {
-            const char* e = getenv("RBL_DEBUG_MISPREDICT_EVERY");
-            return e ? atoi(e) : 0;
-        }();
-        if (mis_every > 0 && (h->iter % mis_every) == mis_every - 1) {
-            const double wrong = h->step_rho * 1.5;
-            RBL_HIP(hipMemcpyAsync(h->pred, &wrong, sizeof(double), hipMemcpyHostToDevice, h->stream));
-            RBL_HIP(hipStreamSynchronize(h->stream));
-        }
-        h->pred_valid = true;
-    }
-    if (h->phase_timing) RBL_HIP(hipEventRecord(h->ev[3], h->stream));
-    return RBL_OK;
-}
-
-int rbl_phase_w(rbl_solver* h) {
-    RBL_ENTER_ITER(h);
-    RBL_TRY(phase_w_body(h));
-    // the w-step's own host wait is behind us, so the z-step's status word (written milliseconds earlier in stream
-    // order) is there already: no extra synchronisation.  Not certified: z and q were redone, the w-step follows
-    bool redone = false;
-    RBL_TRY(zb_resolve(h, &redone));
-    if (!redone) return RBL_OK;
-    RBL_HIP(hipMemcpyAsync(h->w, h->w_prev, sizeof(double) * h->ld, hipMemcpyDeviceToDevice, h->stream));
-    return phase_w_body(h);
-}
-
-int rbl_phase_dual(rbl_solver* h, int want_objective) {
-    RBL_ENTER_ITER(h);
-
-    h->fused_ran = false;
-    h->fused_v_ran = false;
-    h->nd_launches += 1;
-    if (h->fused_ok && h->pred_valid) {
-        if (prof_now(h)) RBL_HIP(hipEventRecord(h->kev[4], h->stream));
-        RBL_TRY(launch_sweep_erm(h->storage, h->cfg.loss, h->D, h->n, h->ld, h->w, h->z, h->lam, h->v, h->z_next,
-                                 h->sigma0, h->step_rho, h->pred, h->slab, h->partials, h->q, h->red, q_zz(h),
-                                 h->num_cu, h->stream, prof_now(h) ? h->kev[5] : nullptr, want_objective));
-        if (prof_now(h)) h->kev_pending[2] = h->n > 0;
-        h->fused_ran = true;
-        h->v_valid = want_objective != 0;   // without objective logging the pass does not store v (ensure_v recomputes it if a misprediction asks)
-        if (h->phase_timing) RBL_HIP(hipEventRecord(h->ev[4], h->stream));
-    } else if (h->fuse_v) {
-        // v = D w and the lambda update in one pass (timed as the gemv of the iteration)
-        if (prof_now(h)) RBL_HIP(hipEventRecord(h->kev[0], h->stream));
-        RBL_TRY(launch_sweep_v(h->storage, h->D, h->n, h->ld, h->w, h->z, h->lam, h->v, h->step_rho, h->partials, h->red,
-                               h->num_cu, h->stream, prof_now(h) ? h->kev[1] : nullptr));
-        if (prof_now(h)) h->kev_pending[0] = h->n > 0;
-        h->v_valid = true;
-        h->fused_v_ran = true;
-        if (h->phase_timing) RBL_HIP(hipEventRecord(h->ev[4], h->stream));
-    } else {
-        if (prof_now(h)) RBL_HIP(hipEventRecord(h->kev[0], h->stream));
-        RBL_TRY(launch_gemv(h->storage, h->D, h->n, h->ld, h->w, h->v, h->num_cu, h->stream));
-        if (prof_now(h)) {
-            RBL_HIP(hipEventRecord(h->kev[1], h->stream));
-            h->kev_pending[0] = true;
-        }
-        h->v_valid = true;
-        if (h->phase_timing) RBL_HIP(hipEventRecord(h->ev[4], h->stream));
-        RBL_TRY(launch_dual(h->cfg.loss, h->n, h->step_rho, h->z, h->v, h->lam, h->partials, h->red, h->stream));
-    }
-    // own labels: k_dual summed the losses at v as the pass left it - the handle's own are at r * v
-    if (h->rs && want_objective && !h->sorted_path)
-        RBL_TRY(launch_loss_sum(h->cfg.loss, h->n, h->v, 1.0, h->partials, h->red + 1, h->stream, h->rs));
-    h->pending_mask = 2 | (h->fused_ran ? 1 : 0);
-    h->want_obj = want_objective;
-    h->obj_is_risk = false;
-    if (want_objective && h->sorted_path && h->nt == h->n) {
-        RBL_TRY(risk_from_v(h, h->v, h->red + 1));
-        h->obj_is_risk = true;
-    }
-    return RBL_OK;
-}
-
-// One thread gathers the iteration's scalars into the pinned host block: the host then needs a
-// single stream wait and no copies (each small device-to-host copy costs ~15 us of stream time).
-static __global__ void k_pack_stats(const double* __restrict__ red, const double* __restrict__ red2,
-                             const double* __restrict__ pred, const int* __restrict__ branch,
-                             const unsigned* __restrict__ counters, int* __restrict__ zd_err,
-                             double* __restrict__ hstat, int seq, const double* __restrict__ pen4) {
-    if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    hstat[9] = 0.0;
-    if (zd_err) {          // distributed z-step: a seam search that ran out of rounds (reported, then cleared)
-        hstat[9] = (double)zd_err[0];
-        zd_err[0] = 0;
-    }
-    hstat[0] = red[0];
-    hstat[1] = red[1];
-    hstat[2] = red2[0];
-    hstat[3] = red2[1];
-    hstat[4] = red2[2];
-    hstat[5] = pred ? pred[0] : 0.0;
-    hstat[6] = pred ? pred[1] : 0.0;
-    hstat[7] = branch ? (double)branch[0] : -1.0;
-    hstat[8] = counters ? (double)counters[0] : 0.0;
-    hstat[10] = counters ? (double)counters[3] : 0.0;   // persistent upper-level PAV kernel: 1 = it did not complete
-    hstat[11] = pen4 ? pen4[2] : 0.0;   // per-coordinate penalties: sum l1_j |w_j|, sum l2_j w_j^2
-    hstat[12] = pen4 ? pen4[3] : 0.0;
-    __threadfence_system();
-    reinterpret_cast<volatile int*>(hstat + 15)[0] = seq;   // written last: the host polls this word
-}
-
-// part: FIN_ALL = the whole phase; a group step (rbl_group_step) enqueues every member's statistics kernel first
-// (FIN_ENQUEUE), waits once for the last one - they run in stream order - and then digests each (FIN_DIGEST: no wait).
-enum { FIN_ALL = 0, FIN_ENQUEUE = 1, FIN_DIGEST = 2 };
-static int phase_finish_part(rbl_solver* h, rbl_stats* out, int part);
-
-int rbl_phase_finish(rbl_solver* h, rbl_stats* out) {
-    RBL_ENTER_ITER(h);
-    return phase_finish_part(h, out, FIN_ALL);
-}
-
-static int phase_finish_part(rbl_solver* h, rbl_stats* out, int part) {
-    float spec_ms = 0.f;   // the w-step of THIS iteration ran before its ev[0]: add its time back
-    if (h->spec_timed) (void)hipEventElapsedTime(&spec_ms, h->ev_spec[0], h->ev_spec[1]);
-    h->spec_timed = false;
-    if (h->phase_timing && part != FIN_DIGEST) RBL_HIP(hipEventRecord(h->ev[5], h->stream));
-    volatile int* seq_word = reinterpret_cast<volatile int*>(h->hstat + 15);
-    const int pack_seq = (int)((h->iter & 0x3fffffff) + 1);
-    if (part != FIN_DIGEST) {
-        *seq_word = 0;
-        hipLaunchKernelGGL(k_pack_stats, dim3(1), dim3(64), 0, h->stream, h->red, h->red2,
-                           h->fused_ran ? h->pred : (const double*)nullptr,
-                           (h->sorted_path && h->cfg.weight_function == RBL_W_EHRM) ? h->pw.branch : (const int*)nullptr,
-                           h->sorted_path ? h->pw.counters : (const unsigned*)nullptr, h->zd_err, h->hstat, pack_seq,
-                           (const double*)pen_terms(h));
-        RBL_HIP(hipGetLastError());
-    }
-    if (part == FIN_ENQUEUE) return RBL_OK;   // (group members run the two-pass iteration: nothing to enqueue ahead)
-    // Single-sweep lasso iterations: everything the next w-step needs is on the device already
-    // (q from the pass, rho_{k+1} = pred[0]), so it is enqueued now and runs while the host waits
-    // for and digests this iteration's statistics.  If they say "converged" or "rho was
-    // mispredicted", w is put back from w_prev below.
-    static const bool no_spec = [] {
-        const char* e = getenv("RBL_NO_SPECULATE");
-        return e && e[0] == '1';
-    }();
-    const bool try_spec = part == FIN_ALL && h->fused_ran && h->p_valid && h->cfg.wstep == RBL_WSTEP_L1 && !no_spec;
-    if (try_spec) {
-        if (h->phase_timing) RBL_HIP(hipEventRecord(h->ev_spec[0], h->stream));
-        bool fs_pending = false;
-        RBL_TRY(run_wstep(RBL_WSTEP_L1, h->G, h->ld, h->q, 1.0, h->cfg.reg, h->smooth_t, h->L, h->cfg.w_tol, 100000, h->w,
-                          h->ww, nullptr, h->stream, &fs_pending, h->pred, h->w_prev, true));   // leaves G w in ww.Gy
-        RBL_TRY(launch_predict_rho(h->ld, h->q, h->p, h->p_alt, h->w, h->w_prev, h->ww.Gy, q_zz(h), 0.0,
-                                   217.0 * (double)h->d, h->pred, h->red2, h->stream, h->pred));
-        RBL_TRY(pen_terms_after_predict(h));
-        if (h->phase_timing) RBL_HIP(hipEventRecord(h->ev_spec[1], h->stream));
-    }
-    if (part == FIN_ALL) rbl_spin_wait(seq_word, 0, h->stream);
-    if (*seq_word != pack_seq) {
-        rbl_set_error("phase_finish: the statistics kernel did not complete");
-        (void)hipGetLastError();
-        return RBL_ERR_HIP;
-    }
-    const volatile double* hs = h->hstat;
-    const double r[2] = {hs[0], hs[1]}, r2[3] = {hs[2], hs[3], hs[4]}, pr[2] = {hs[5], hs[6]};
-    const int br = (int)hs[7];
-    const unsigned merges = (unsigned)hs[8];
-    if (hs[9] != 0.0) {
-        rbl_set_error("distributed z-step: a seam search did not finish within its rounds");
-        return RBL_ERR_STATE;
-    }
-    if (hs[10] != 0.0) {
-        rbl_set_error("z-step: the upper-level PAV kernel did not complete (a wait gave up or its fill list overflowed)");
-        return RBL_ERR_HIP;
-    }
-    if (br >= 0) h->pw.ex.spec = br;   // EHRM: the next iteration speculates the branch this one took
-    const double primal = std::sqrt(r[0] > 0.0 ? r[0] : 0.0);   // algorithms.py:135
-    const double dual = std::sqrt(r2[0] > 0.0 ? r2[0] : 0.0);   // algorithms.py:136
-    double objective = NAN;
-    if (h->want_obj) {
-        // sharded rank-weighted runs: the caller adds rbl_risk_from_v() of the gathered v
-        double risk = 0.0;
-        if (h->obj_is_risk) risk = r[1];
-        else if (!h->sorted_path) risk = r[1] / (double)h->nt;  // erm: sum over ALL ranks of loss / n
-        objective = risk;
-        if (h->pen) objective += 0.5 * (hs[11] + hs[12]);                           // R(w) = 1/2 sum (l1_j |w_j| + l2_j w_j^2)
-        else if (h->cfg.wstep == RBL_WSTEP_L2) objective += 0.5 * h->cfg.reg * r2[1];   // objective.py:83-84
-        else objective += 0.5 * h->cfg.reg * r2[2];                                 // objective.py:85-86
-    }
-    const bool conv = primal < h->cfg.tol && dual < h->cfg.tol;  // algorithms.py:137
-    const int64_t i = h->iter;
-    double rho_next = h->rho;
-    if (!conv) {
-        // algorithms.py:154-157: the only live branch of the schedule
-        const double cap = 217.0 * (double)h->d;
-        rho_next = h->rho * (primal > 1e-2 ? 1.02 : 1.07);
-        if (rho_next > cap) rho_next = cap;
-        if (h->cfg.wstep == RBL_WSTEP_SMOOTH_L1 && i >= 17) {
-            // algorithms.py:254-255 (python float %, both operands positive)
-            double t = h->smooth_t * 0.9;
-            if (t < 1e-9) t = 1e-9;
-            h->smooth_t = std::fmod(t, std::pow(rho_next, -0.1)) * std::pow((double)i, -0.1);
-        }
-    }
-    int fused = 0, mispred = 0;
-    if (h->fused_ran) {
-        fused = 1;
-        // the pass already did iteration i+1's z-step with the predicted rho: keep it only if the
-        // exact residual leads to exactly that rho (same double arithmetic on both sides)
-        h->z_ready = !conv && pr[0] == rho_next;
-        if (!conv && !h->z_ready) mispred = 1;
-        h->n_fused += 1;
-        h->n_mispred += mispred;
-    }
-    h->pred_valid = false;
-    if (try_spec) {
-        if (!conv && h->z_ready) {
-            h->spec_w = true;
-            h->spec_timed = h->phase_timing;
-        } else {
-            RBL_HIP(hipMemcpyAsync(h->w, h->w_prev, sizeof(double) * h->ld, hipMemcpyDeviceToDevice, h->stream));
-        }
-    }
-    float ms[5] = {0, 0, 0, 0, 0};
-    if (h->phase_timing) {
-        (void)hipEventElapsedTime(&ms[0], h->ev[0], h->ev[1]);
-        (void)hipEventElapsedTime(&ms[1], h->ev[1], h->ev[2]);
-        (void)hipEventElapsedTime(&ms[2], h->ev[2], h->ev[3]);
-        (void)hipEventElapsedTime(&ms[3], h->ev[3], h->ev[4]);
-        (void)hipEventElapsedTime(&ms[4], h->ev[0], h->ev[5]);
-        ms[2] += spec_ms;
-        ms[4] += spec_ms;
-    }
-    for (int k = 0; k < 3; ++k) {
-        if (h->kev_pending[k]) {
-            float t = 0.f;
-            if (hipEventElapsedTime(&t, h->kev[2 * k], h->kev[2 * k + 1]) == hipSuccess) {
-                h->kt_ms[k] += t;
-                h->kt_n[k] += 1;
-                if (h->kt_samples[k].size() < (size_t)1 << 16) h->kt_samples[k].push_back(t);
-            }
-            h->kev_pending[k] = false;
-        }
-    }
-    (void)hipGetLastError();
-    if (out) {
-        out->iter = i + 1;
-        out->primal = primal;
-        out->dual = dual;
-        out->rho = h->rho;
-        out->rho_next = rho_next;
-        out->objective = objective;
-        out->converged = conv ? 1 : 0;
-        out->inner_iters = h->inner_iters;
-        out->ehrm_branch = br;
-        out->pav_merges = h->sorted_path ? (int)merges : -1;
-        out->ms_z = ms[0];
-        out->ms_q = ms[1];
-        out->ms_w = ms[2];
-        out->ms_v = ms[3];
-        out->ms_total = ms[4];
-        out->fused = fused;
-        out->mispredicted = mispred;
-        out->fused_v = h->fused_v_ran ? 1 : 0;
-        out->host_syncs = g_host_syncs;    // stream waits, blocking copies and spins since the last rbl_phase_finish
-        out->sort_passes = h->sorted_path ? h->sort_passes : -1;
-        out->zband = h->sorted_path ? h->zb.mode : -1;
-        out->wstep_form = h->ww.form;
-    }
-    h->rho = rho_next;
-    h->iter = i + 1;
-    g_host_syncs = 0;
-    h->sort_passes = 0;
-    return RBL_OK;
-}
-
-int rbl_step(rbl_solver* h, int want_objective, rbl_stats* out) {
-    RBL_ENTER_ITER(h);
-    if (h->nt != h->n) {
-        rbl_set_error("rbl_step: sharded problem - drive the phase API with collectives in between");
-        return RBL_ERR_STATE;
-    }
-    RBL_TRY(rbl_phase_m(h));
-    RBL_TRY(rbl_phase_z(h, nullptr));
-    RBL_TRY(rbl_phase_q(h));
-    RBL_TRY(rbl_phase_w(h));
-    RBL_TRY(rbl_phase_dual(h, want_objective));
-    return rbl_phase_finish(h, out);
-}
-
-int rbl_solve(rbl_solver* h, int max_iter, int want_objective, rbl_stats* last, double* hist_objective,
-              double* hist_primal, double* hist_dual, double* hist_rho, double* hist_time_s, int64_t cap) {
-    RBL_ENTER(h);
-    if (max_iter <= 0) max_iter = h->cfg.max_iter;
-    rbl_stats st;
-    std::memset(&st, 0, sizeof(st));
-    const auto t0 = std::chrono::steady_clock::now();
-    for (int it = 0; it < max_iter; ++it) {
-        RBL_TRY(rbl_step(h, want_objective, &st));
-        const int64_t k = st.iter - 1;
-        if (k >= 0 && k < cap) {
-            if (hist_objective) hist_objective[k] = st.objective;
-            if (hist_primal) hist_primal[k] = st.primal;
-            if (hist_dual) hist_dual[k] = st.dual;
-            if (hist_rho) hist_rho[k] = st.rho;
-            if (hist_time_s)
-                hist_time_s[k] = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-        }
-        if (st.converged) break;
-    }
-    RBL_TRY(cancel_spec(h));   // a solve ends on w_k, not on the w-step enqueued ahead of iteration k+1
-    if (last) *last = st;
-    return RBL_OK;
-}
-
-int rbl_finalize_smooth(rbl_solver* h) {
-    RBL_ENTER(h);
-    if (h->cfg.wstep != RBL_WSTEP_SMOOTH_L1) return RBL_OK;
-    RBL_TRY(launch_soft_threshold(h->ld, h->w, h->smooth_t, h->stream));
-    h->v_valid = false;
-    RBL_HIP(hipStreamSynchronize(h->stream));
-    return RBL_OK;
-}
-
-int rbl_objective(rbl_solver* h, const double* w, int include_reg, double* out) {
-    RBL_ENTER(h);
-    if (!h->data_ready || !w || !out) {
-        rbl_set_error("objective: no data or NULL argument");
-        return RBL_ERR_STATE;
-    }
-    if (h->nt != h->n) {
-        rbl_set_error("objective: sharded handle - use the phase API");
-        return RBL_ERR_STATE;
-    }
-    RBL_HIP(hipMemcpyAsync(h->w_tmp, w, sizeof(double) * h->d, hipMemcpyHostToDevice, h->stream));
-    RBL_TRY(launch_gemv(h->storage, h->D, h->n, h->ld, h->w_tmp, h->m, h->num_cu, h->stream));
-    RBL_TRY(risk_from_v(h, h->m, h->red2 + 4));
-    double pr4[4] = {0.0, 0.0, 0.0, 0.0};
-    if (h->pen) {
-        RBL_TRY(launch_pen_terms(h->ld, h->w_tmp, h->ww.pen_l1, h->ww.pen_l2, h->pen + 2 * h->ld + 4, h->stream));
-        RBL_HIP(hipMemcpyAsync(pr4, h->pen + 2 * h->ld + 4, sizeof(double) * 4, hipMemcpyDeviceToHost, h->stream));
-    } else {
-        RBL_TRY(launch_reg_terms(h->ld, h->w_tmp, h->red2 + 5, h->stream));
-    }
-    double r[3];
-    RBL_HIP(hipMemcpyAsync(r, h->red2 + 4, sizeof(double) * 3, hipMemcpyDeviceToHost, h->stream));
-    RBL_HIP(hipStreamSynchronize(h->stream));
-    double val = r[0];
-    if (include_reg && h->pen) {
-        val += 0.5 * (pr4[2] + pr4[3]);
-    } else if (include_reg && h->cfg.reg > 0.0) {
-        if (h->cfg.wstep == RBL_WSTEP_L2) val += 0.5 * h->cfg.reg * r[1];
-        else val += 0.5 * h->cfg.reg * r[2];
-    }
-    *out = val;
-    return RBL_OK;
-}
-
-// fraction of correctly classified rows of this handle's data (src/util/calculate_acc.py:3-19)
-int rbl_accuracy(rbl_solver* h, const double* w, double threshold, double* out) {
-    RBL_ENTER(h);
-    if (!h->data_ready || !w || !out) {
-        rbl_set_error("accuracy: no data or NULL argument");
-        return RBL_ERR_STATE;
-    }
-    if (!(threshold > 0.0 && threshold < 1.0)) {
-        rbl_set_error("accuracy: threshold must be in (0, 1)");
-        return RBL_ERR_INVALID;
-    }
-    RBL_HIP(hipMemcpyAsync(h->w_tmp, w, sizeof(double) * h->d, hipMemcpyHostToDevice, h->stream));
-    RBL_TRY(launch_gemv(h->storage, h->D, h->n, h->ld, h->w_tmp, h->m, h->num_cu, h->stream));
-    RBL_TRY(launch_accuracy(h->cfg.loss, h->n, h->m, h->ysign, std::log(threshold / (1.0 - threshold)), h->partials,
-                            h->red2 + 4, h->stream, h->rs));
-    double cnt = 0.0;
-    RBL_HIP(hipMemcpyAsync(&cnt, h->red2 + 4, sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    RBL_HIP(hipStreamSynchronize(h->stream));
-    *out = h->n > 0 ? cnt / (double)h->n : 0.0;   // local rows; sharded callers average by n
-    return RBL_OK;
-}
-
-
-// ================================================================== distributed z-step
-// Rank-weighted problems on several GPUs: the driver (dist.py: _z_distributed)
-// calls these between its collectives; oracle/zdist.py restates every step on the CPU.
-// Layout of RBL_BUF_ZD_SMALL (doubles): [0,256) samples | [256,259) bounds | [260,262) EHRM
-// fvals | [320,384) candidates | [512, 512+3*4096) partial sums | [12800+..) seam sums.
-namespace {
-constexpr int ZD_SMALL_DOUBLES = 16384;
-constexpr int ZD_OFF_SAMPLES = 0, ZD_OFF_BOUNDS = 256, ZD_OFF_FV = 260, ZD_OFF_CAND = 320, ZD_OFF_PART = 512,
-              ZD_OFF_SUMS = 512 + 3 * 4096;
-constexpr int ZD_MAX_CAND = 4096;   // world * K
-
-int zd_ensure(rbl_solver* h) {
-    if (h->zd_small) return RBL_OK;
-    if (!h->sorted_path || h->cfg.objective_only) {
-        rbl_set_error("distributed z-step: only for rank-weighted solver handles");
-        return RBL_ERR_STATE;
-    }
-    DevArena& mem = h->mem;
-    double* small = nullptr;
-    RBL_TRY(mem.alloc(&small, ZD_SMALL_DOUBLES));
-    RBL_TRY(mem.alloc(&h->zd_seam, 1));
-    RBL_TRY(mem.alloc(&h->zd_err, 1));
-    RBL_TRY(mem.alloc(&h->zd_bounds_dev, 80));
-    RBL_TRY(mem.alloc(&h->zd_counts_dev, 64));
-    RBL_TRY(mem.alloc(&h->zd_zids, (size_t)h->n));
-    RBL_TRY(alloc_prefix(mem, h->zd_a, h->nt));
-    h->zd_b = h->zd_a;
-    if (h->cfg.weight_function == RBL_W_EHRM) RBL_TRY(alloc_prefix(mem, h->zd_b, h->nt));
-    RBL_HIP(hipMemsetAsync(h->zd_err, 0, sizeof(int), h->stream));
-    h->zd_small = small;   // set last: it says the group is there
-    return RBL_OK;
-}
-}  // namespace
-
-int rbl_zd_sort_local(rbl_solver* h, int nsamples) {
-    RBL_ENTER_ITER(h);
-    RBL_TRY(zd_ensure(h));
-    if (nsamples < 1 || nsamples > 256) {
-        rbl_set_error("zd_sort_local: 1..256 samples");
-        return RBL_ERR_INVALID;
-    }
-    hipStream_t s = h->stream;
-    // keys of the local m, payload = GLOBAL row id
-    if (!h->keys_ready) {
-        RBL_TRY(launch_keys_from_m(h->n, h->m, h->sw.keys[0], h->sw.vals[0], s));
-        if (h->off != 0) RBL_TRY(launch_add_u32(h->n, h->sw.vals[0], (u32)h->off, s));
-    }
-    h->keys_ready = false;
-    RBL_TRY(launch_radix_sort(h->sw, h->n, true, s));
-    RBL_TRY(launch_zd_sample(h->sw.keys[0], h->n, nsamples, h->zd_small + ZD_OFF_SAMPLES, s));
-    return RBL_OK;
-}
-
-// the logged objective of rank weights, sum_i sigma_i loss_(i) (objective.py:73-82), needs the global
-// order of the per-sample losses: same sample sort, keys only
-int rbl_zd_sort_losses(rbl_solver* h, int nsamples) {
-    RBL_ENTER_ITER(h);
-    RBL_TRY(zd_ensure(h));
-    if (nsamples < 1 || nsamples > 256) {
-        rbl_set_error("zd_sort_losses: 1..256 samples");
-        return RBL_ERR_INVALID;
-    }
-    hipStream_t s = h->stream;
-    RBL_TRY(ensure_v(h));
-    h->keys_ready = false;
-    RBL_TRY(launch_loss_keys(h->n, h->v, h->sw.keys[0], s));
-    RBL_TRY(launch_radix_sort(h->sw, h->n, false, s));
-    RBL_TRY(launch_zd_sample(h->sw.keys[0], h->n, nsamples, h->zd_small + ZD_OFF_SAMPLES, s));
-    return RBL_OK;
-}
-
-// received loss keys in RBL_BUF_ZD_RKEYS: this chunk's share of the risk -> ZD_SMALL[264]
-int rbl_zd_risk(rbl_solver* h, int64_t nrecv, int64_t sigma_off) {
-    RBL_ENTER_ITER(h);
-    RBL_TRY(zd_ensure(h));
-    if (nrecv < 0 || sigma_off < 0 || sigma_off + nrecv > h->nt) {
-        rbl_set_error("zd_risk: chunk [%lld, %lld) outside the %lld sorted positions", (long long)sigma_off,
-                      (long long)(sigma_off + nrecv), (long long)h->nt);
-        return RBL_ERR_INVALID;
-    }
-    hipStream_t s = h->stream;
-    double* out = h->zd_small + ZD_OFF_FV + 4;
-    if (nrecv == 0) {
-        RBL_HIP(hipMemsetAsync(out, 0, sizeof(double), s));
-        return RBL_OK;
-    }
-    RBL_HIP(hipMemcpyAsync(h->sw.keys[0], h->sw.keys[1], sizeof(u64) * (size_t)nrecv, hipMemcpyDeviceToDevice, s));
-    RBL_TRY(launch_radix_sort(h->sw, nrecv, false, s));
-    return launch_sorted_loss_dot(h->cfg.loss, nrecv, h->sw.keys[0], h->sigma_a + sigma_off, h->partials, out, s);
-}
-
-int rbl_zd_partition(rbl_solver* h, const void* splitters_dev, int nparts, int64_t* send_counts) {
-    RBL_ENTER_ITER(h);
-    RBL_TRY(zd_ensure(h));
-    if (nparts < 1 || nparts > 64) return RBL_ERR_INVALID;
-    if (nparts > 1)
-        RBL_TRY(launch_zd_split_bounds(h->sw.keys[0], h->n, (const double*)splitters_dev, nparts - 1, h->zd_bounds_dev,
-                                       h->stream));
-    // the counts stay on the device (RBL_BUF_ZD_COUNTS): the driver all-gathers them there and reads the whole
-    // count matrix with ONE host wait; send_counts != NULL additionally downloads this rank's row
-    RBL_TRY(launch_zd_counts_from_bounds(h->zd_bounds_dev, nparts, h->n, h->zd_counts_dev, h->stream));
-    h->zd_world = nparts;
-    if (send_counts) {
-        long long hc[64];
-        RBL_HIP(hipMemcpyAsync(hc, h->zd_counts_dev, sizeof(long long) * nparts, hipMemcpyDeviceToHost, h->stream));
-        RBL_HIP(hipStreamSynchronize(h->stream));
-        rbl_note_host_sync();
-        for (int j = 0; j < nparts; ++j) send_counts[j] = hc[j];
-    }
-    return RBL_OK;
-}
-
-// the received (key, id) pairs are in RBL_BUF_ZD_RKEYS / RIDS: sort the chunk, sorted m, prefix
-// sums of m and of the chunk's slice of sigma; EHRM: this chunk's two singleton-stage sums
-int rbl_zd_prepare(rbl_solver* h, int64_t nrecv, int64_t sigma_off) {
-    RBL_ENTER_ITER(h);
-    RBL_TRY(zd_ensure(h));
-    if (nrecv < 0 || sigma_off < 0 || sigma_off + nrecv > h->nt) {
-        rbl_set_error("zd_prepare: chunk [%lld, %lld) outside the %lld sorted positions", (long long)sigma_off,
-                      (long long)(sigma_off + nrecv), (long long)h->nt);
-        return RBL_ERR_INVALID;
-    }
-    hipStream_t s = h->stream;
-    // the received pairs move to the sort's input buffers (the pointers behind the typed views stay put)
-    RBL_HIP(hipMemcpyAsync(h->sw.keys[0], h->sw.keys[1], sizeof(u64) * (size_t)nrecv, hipMemcpyDeviceToDevice, s));
-    RBL_HIP(hipMemcpyAsync(h->sw.vals[0], h->sw.vals[1], sizeof(u32) * (size_t)nrecv, hipMemcpyDeviceToDevice, s));
-    h->zd_n = nrecv;
-    h->zd_off = sigma_off;
-    RBL_TRY(launch_radix_sort(h->sw, nrecv, true, s));   // runs arrive in rank order: stable => ties in row order
-    RBL_TRY(launch_unflip_prefix(h->sw.keys[0], nrecv, h->pw.ms, h->pw.pm, s));
-    RBL_TRY(launch_prefix(h->sigma_a + sigma_off, nrecv, h->zd_a, s));
-    const bool ehrm = h->cfg.weight_function == RBL_W_EHRM;
-    double* fv = h->zd_small + ZD_OFF_FV;
-    if (ehrm) {
-        RBL_TRY(launch_prefix(h->sigma_b + sigma_off, nrecv, h->zd_b, s));
-        RBL_TRY(launch_ehrm_fvals(nrecv, h->sigma_a + sigma_off, h->sigma_b + sigma_off, h->cfg.B, h->step_rho, h->pw.ms,
-                                  h->pw.partials, fv, s, h->pw.u, (double*)h->sw.keys[1]));
-    } else {
-        RBL_HIP(hipMemsetAsync(fv, 0, 2 * sizeof(double), s));
-    }
-    return RBL_OK;
-}
-
-int rbl_zd_pav(rbl_solver* h, const void* fvals_total_dev) {
-    RBL_ENTER_ITER(h);
-    hipStream_t s = h->stream;
-    const bool ehrm = h->cfg.weight_function == RBL_W_EHRM;
-    if (ehrm) RBL_TRY(launch_ehrm_pick((const double*)fvals_total_dev, h->pw.branch, s));
-    PavExtras ex = h->pw.ex;      // the chunk's upper levels in one launch; the branch comes from the sums over ALL ranks
-    ex.num_cu = h->num_cu;
-    ex.fpart = nullptr;
-    RBL_TRY(launch_pav_tree(h->cfg.loss, h->zd_n, h->step_rho, h->pw.ms, h->sigma_a + h->zd_off, h->sigma_b + h->zd_off,
-                            h->pw.u, h->zd_a.view(), h->zd_b.view(), h->pw.pm.view(), ehrm ? h->pw.branch : nullptr, h->pw.recs,
-                            h->pw.counters, s,
-                            ehrm ? h->pw.u : nullptr, ehrm ? (const double*)h->sw.keys[1] : nullptr, &ex));
-    h->pw.ex.bar_parity = ex.bar_parity;
-    return RBL_OK;
-}
-
-int rbl_zd_bounds(rbl_solver* h) {
-    RBL_ENTER_ITER(h);
-    return launch_zd_bounds(h->pw.u, h->zd_n, h->zd_small + ZD_OFF_BOUNDS, h->stream);
-}
-
-int rbl_zd_seam_setup(rbl_solver* h, int rank, int world, int level, const void* bounds_all_dev) {
-    RBL_ENTER_ITER(h);
-    if (world < 1 || world > 64 || rank < 0 || rank >= world || level < 1) return RBL_ERR_INVALID;
-    h->zd_world = world;
-    return launch_zd_seam_setup(rank, world, level, (const double*)bounds_all_dev, h->zd_n, h->zd_seam, h->stream);
-}
-
-int rbl_zd_seam_propose(rbl_solver* h, int K, const void* cand_all_prev, const void* part_sum_prev) {
-    RBL_ENTER_ITER(h);
-    if (K < 1 || K > 64 || K * h->zd_world > ZD_MAX_CAND) return RBL_ERR_INVALID;
-    return launch_zd_update_propose(h->cfg.loss, h->zd_seam, h->pw.u, K, h->zd_world, (const double*)cand_all_prev,
-                                    (const double*)part_sum_prev, h->step_rho, h->zd_small + ZD_OFF_CAND, h->stream);
-}
-
-int rbl_zd_seam_eval(rbl_solver* h, int K, const void* cand_all_dev) {
-    RBL_ENTER_ITER(h);
-    if (K < 1 || K > 64 || K * h->zd_world > ZD_MAX_CAND) return RBL_ERR_INVALID;
-    const bool ehrm = h->cfg.weight_function == RBL_W_EHRM;
-    return launch_zd_eval(h->zd_seam, h->pw.u, h->zd_a.view(), h->zd_b.view(), h->pw.pm.view(), ehrm ? h->pw.branch : nullptr, K,
-                          h->zd_world,
-                          (const double*)cand_all_dev, h->zd_small + ZD_OFF_PART, h->stream);
-}
-
-int rbl_zd_seam_sums(rbl_solver* h, int K, const void* cand_all_prev, const void* part_sum_prev, int nseams) {
-    RBL_ENTER_ITER(h);
-    if (nseams < 1 || nseams > 32) return RBL_ERR_INVALID;
-    RBL_TRY(launch_zd_update_propose(h->cfg.loss, h->zd_seam, h->pw.u, K, h->zd_world, (const double*)cand_all_prev,
-                                     (const double*)part_sum_prev, h->step_rho, nullptr, h->stream));
-    const bool ehrm = h->cfg.weight_function == RBL_W_EHRM;
-    return launch_zd_pooled(h->zd_seam, h->zd_a.view(), h->zd_b.view(), h->pw.pm.view(), ehrm ? h->pw.branch : nullptr, nseams,
-                            h->zd_small + ZD_OFF_SUMS, h->zd_err, h->stream);
-}
-
-int rbl_zd_seam_fill(rbl_solver* h, const void* sums_total_dev) {
-    RBL_ENTER_ITER(h);
-    return launch_zd_fill(h->cfg.loss, h->zd_seam, (const double*)sums_total_dev, h->step_rho, h->pw.u, h->zd_n, h->stream);
-}
-
-// sort the chunk's (row id, u) by row id: contiguous per owner rank (rows are sharded in
-// blocks of nmax); counts[r] = how many go back to rank r.  RBL_BUF_ZD_BIDS / BU hold them.
-int rbl_zd_return_partition(rbl_solver* h, int64_t nmax, int world, int64_t* counts) {
-    RBL_ENTER_ITER(h);
-    if (world < 1 || world > 64 || nmax < 1) return RBL_ERR_INVALID;
-    hipStream_t s = h->stream;
-    RBL_TRY(launch_zd_ids_to_keys(h->zd_n, h->sw.vals[0], h->sw.keys[0], h->sw.vals[0], s));
-    int id_bits = 1;
-    while (id_bits < 32 && (1LL << id_bits) < h->nt) ++id_bits;
-    RBL_TRY(launch_radix_sort(h->sw, h->zd_n, true, s, id_bits));   // row ids < n_total: 4 passes up to 2^32 rows
-    RBL_TRY(launch_zd_gather_back(h->zd_n, h->sw.keys[0], h->sw.vals[0], h->pw.u, h->sw.vals[1], (double*)h->sw.keys[1], s));
-    // counts == NULL: no host wait.  How many rows go back to owner r is known to the driver already: it is what
-    // r sent to this chunk in the forward exchange (the count matrix of the return trip is the transpose);
-    // a seam search that did not finish is reported by rbl_phase_finish (the flag travels in the statistics block)
-    if (!counts) return RBL_OK;
-    int herr = 0;
-    RBL_TRY(launch_zd_owner_bounds(h->sw.keys[0], h->zd_n, nmax, world, h->zd_bounds_dev, s));
-    long long hb[65];
-    RBL_HIP(hipMemcpyAsync(hb, h->zd_bounds_dev, sizeof(long long) * (world + 1), hipMemcpyDeviceToHost, s));
-    RBL_HIP(hipMemcpyAsync(&herr, h->zd_err, sizeof(int), hipMemcpyDeviceToHost, s));
-    RBL_HIP(hipStreamSynchronize(s));
-    rbl_note_host_sync();
-    if (herr) {
-        RBL_HIP(hipMemsetAsync(h->zd_err, 0, sizeof(int), s));
-        rbl_set_error("distributed z-step: a seam search did not finish within its rounds");
-        return RBL_ERR_STATE;
-    }
-    for (int r = 0; r < world; ++r) counts[r] = hb[r + 1] - hb[r];
-    return RBL_OK;
-}
-
-// rows received back in RBL_BUF_ZD_ZIDS / ZU: z, c = z + lambda/rho (algorithms.py:103-104, :192)
-int rbl_zd_scatter(rbl_solver* h, int64_t n_back) {
-    RBL_ENTER_ITER(h);
-    if (n_back != h->n) {
-        rbl_set_error("zd_scatter: %lld rows came back, %lld are local", (long long)n_back, (long long)h->n);
-        return RBL_ERR_STATE;
-    }
-    const bool ehrm = h->cfg.weight_function == RBL_W_EHRM;
-    RBL_TRY(launch_zd_scatter(n_back, h->zd_zids, h->m, ehrm ? h->pw.branch : nullptr, h->cfg.B, ehrm ? 1 : 0, h->step_rho,
-                              h->lam, h->z, nullptr, h->off, h->n, h->stream));
-    if (h->phase_timing) RBL_HIP(hipEventRecord(h->ev[1], h->stream));
-    return RBL_OK;
-}
-
-// ---- sort-free z-step for banded rank weights, sharded rows (zband.hip step by step; the driver sums / gathers in between)
-static int zbd_ready(rbl_solver* h) {
-    if (!h->zb.enabled || !h->keys_ready) {
-        rbl_set_error("rbl_zbd_*: call rbl_phase_m and rbl_zbd_begin (applicable) first");
-        return RBL_ERR_STATE;
-    }
-    return RBL_OK;
-}
-int rbl_zbd_begin(rbl_solver* h, int* applicable, int* root_clusters) {
-    RBL_ENTER_ITER(h);
-    if (applicable) *applicable = 0;
-    if (root_clusters) *root_clusters = 0;
-    if (!h->sorted_path) return RBL_OK;
-    if (!h->zb.checked) RBL_TRY(zb_setup(h));
-    h->zb.mode = 0;
-    // iteration 0 (every m equal) and the pause after an uncertified z-step: the caller takes the sort path
-    if (!(h->zb.enabled && h->keys_ready && h->iter > 0 && h->iter >= h->zb.skip_until)) return RBL_OK;
-    RBL_TRY(launch_zbd_init(h->zb.cfg, h->zb.st, h->zb.hist, h->stream));
-    if (applicable) *applicable = 1;
-    if (root_clusters) {
-        int mask = 0;
-        for (int k = 0; k < h->zb.cfg.nclusters; ++k) mask |= h->zb.cfg.cl_root[k] ? (1 << k) : 0;
-        *root_clusters = mask;   // bit k: cluster k can pool (rbl_zbd_eval / decide / gather / finish run for it)
-    }
-    return RBL_OK;
-}
-int rbl_zbd_hist(rbl_solver* h, int pass) {
-    RBL_ENTER_ITER(h);
-    RBL_TRY(zbd_ready(h));
-    return launch_zbd_hist(h->n, h->sw.keys[0], h->zb.st, h->zb.hist, pass, h->stream);
-}
-int rbl_zbd_scan(rbl_solver* h, int pass) {
-    RBL_ENTER_ITER(h);
-    RBL_TRY(zbd_ready(h));
-    return launch_zbd_scan(h->cfg.loss, h->zb.cfg, h->zb.st, h->zb.hist, pass, h->step_rho, h->stream);
-}
-int rbl_zbd_eval(rbl_solver* h, int k) {
-    RBL_ENTER_ITER(h);
-    RBL_TRY(zbd_ready(h));
-    return launch_zbd_eval(h->cfg.loss, h->zb.cfg, h->n, h->sw.keys[0], h->zb.st, k, h->step_rho, h->zb.part, h->zb.tot, h->stream);
-}
-int rbl_zbd_decide(rbl_solver* h, int k, int last, int* settled) {
-    RBL_ENTER_ITER(h);
-    RBL_TRY(zbd_ready(h));
-    if (!settled) return launch_zbd_decide(h->cfg.loss, h->zb.cfg, h->zb.st, k, h->step_rho, h->zb.tot, last, h->stream);
-    // the verdict of this pass through pinned memory (one host wait): every rank reads the same answer, the driver stops
-    // issuing root passes (and their all-reduces) for this cluster after the pass that settles it
-    volatile int* pin = h->zb.pin + 4;
-    h->zb.dseq = (h->zb.dseq & 0x3fffffff) + 1;
-    pin[0] = 0;
-    RBL_TRY(launch_zbd_decide(h->cfg.loss, h->zb.cfg, h->zb.st, k, h->step_rho, h->zb.tot, last, h->stream, h->zb.pin + 4,
-                              h->zb.dseq));
-    rbl_spin_wait(pin, 0, h->stream);
-    if (pin[0] != h->zb.dseq) {
-        rbl_set_error("zbd_decide: the verdict of the root pass was never written");
-        (void)hipGetLastError();
-        return RBL_ERR_HIP;
-    }
-    *settled = pin[1];
-    return RBL_OK;
-}
-int rbl_zbd_root_passes(void) { return ZB_ROOT_PASSES; }
-int rbl_zbd_gather(rbl_solver* h, int k) {
-    RBL_ENTER_ITER(h);
-    RBL_TRY(zbd_ready(h));
-    return launch_zbd_gather(h->cfg.loss, h->zb.cfg, h->n, h->sw.keys[0], h->zb.st, k, h->step_rho, h->zb.part, h->zb.pack, h->stream);
-}
-int rbl_zbd_finish(rbl_solver* h, int k, const void* packs_all_dev, int world) {
-    RBL_ENTER_ITER(h);
-    RBL_TRY(zbd_ready(h));
-    if (!packs_all_dev || world < 1 || world > 64) return RBL_ERR_INVALID;
-    return launch_zbd_finish(h->cfg.loss, h->zb.cfg, h->zb.st, k, h->step_rho, h->zb.part, (const double*)packs_all_dev, world,
-                             h->stream);
-}
-int rbl_zbd_apply(rbl_solver* h, int* status) {
-    RBL_ENTER_ITER(h);
-    RBL_TRY(zbd_ready(h));
-    h->zb.seq = (h->zb.seq & 0x3fffffff) + 1;
-    h->zb.pin[0] = 0;
-    RBL_TRY(launch_zbd_apply(h->cfg.loss, h->zb.cfg, h->n, h->step_rho, h->m, h->z, h->lam, h->c, h->zb.st, h->zb.pin, h->zb.seq,
-                             h->pw.counters, h->stream));
-    // every rank holds the same state, so every rank reads the same verdict and takes the same branch afterwards
-    volatile int* pin = h->zb.pin;
-    rbl_spin_wait(pin, 0, h->stream);
-    if (pin[0] != h->zb.seq) {
-        rbl_set_error("banded z-step: its status word was never written");
-        (void)hipGetLastError();
-        return RBL_ERR_HIP;
-    }
-    if (status) *status = pin[1];
-    if (pin[1] == ZB_OK) {
-        h->zb.backoff = 0;
-        h->zb.c_ready = true;
-        h->zb.mode = 1;
-        h->keys_ready = false;
-        if (h->phase_timing) RBL_HIP(hipEventRecord(h->ev[1], h->stream));
-    } else {
-        h->zb.backoff = h->zb.backoff < 2 ? 2 : (h->zb.backoff >= 32 ? 64 : 2 * h->zb.backoff);
-        h->zb.skip_until = h->iter + 1 + h->zb.backoff;
-        h->zb.mode = 2;   // the caller runs the sort-based distributed z-step (rbl_zd_*) for this iteration
-    }
-    return RBL_OK;
-}
-
-// why the last sort-free z-step was (not) certified: the pinned status word stays as written until the next one is launched
-int rbl_zband_status(rbl_solver* h, int* status, int* split) {
-    RBL_ENTER(h);
-    const bool have = h->zb.pin && h->zb.seq > 0 && h->zb.pin[0] == h->zb.seq;
-    if (status) *status = have ? h->zb.pin[1] : -1;
-    if (split) *split = have ? h->zb.pin[2] : -1;
-    return RBL_OK;
-}
-
 int rbl_buffer(rbl_solver* h, int which, void** dev_ptr, int64_t* n_doubles) {
     RBL_ENTER(h);
     void* p = nullptr;
@@ -2795,16 +555,6 @@ int rbl_buffer(rbl_solver* h, int which, void** dev_ptr, int64_t* n_doubles) {
     }
     if (dev_ptr) *dev_ptr = p;
     if (n_doubles) *n_doubles = cnt;
-    return RBL_OK;
-}
-
-// risk (sum sigma_i loss_(i)) of n_total values of v on the device -> host double
-int rbl_risk_from_v(rbl_solver* h, const void* v_all_dev, double* out) {
-    RBL_ENTER(h);
-    RBL_TRY(risk_from_v(h, (const double*)v_all_dev, h->red2 + 4));
-    RBL_HIP(hipMemcpyAsync(out, h->red2 + 4, sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    RBL_HIP(hipStreamSynchronize(h->stream));
-    rbl_note_host_sync();
     return RBL_OK;
 }
 
@@ -2847,8 +597,6 @@ int rbl_profile_kernels(rbl_solver* h, int enable) {
     return RBL_OK;
 }
 
-// SPD, DI, EOD, AOD, TI, FNRD of the linear classifier on this handle's rows
-// (src/util/fair_metric.py:3-41); group: n doubles with values 0 / 1
 int rbl_profile_sampling(rbl_solver* h, int every) {
     RBL_ENTER_ITER(h);   // bookkeeping only: a w-step in flight stays
     if (every < 1) {
@@ -2856,54 +604,6 @@ int rbl_profile_sampling(rbl_solver* h, int every) {
         return RBL_ERR_INVALID;
     }
     h->profile_every = every;
-    return RBL_OK;
-}
-
-int rbl_fair_statistics(rbl_solver* h, const double* w, const double* group, double threshold, double* out6) {
-    RBL_ENTER(h);
-    if (!h->data_ready || !w || !group || !out6) {
-        rbl_set_error("fair_statistics: no data or NULL argument");
-        return RBL_ERR_STATE;
-    }
-    double c[14];
-    {
-        DevArena mem;   // the group vector, freed after the readback
-        double* gd = nullptr;
-        RBL_TRY(mem.alloc(&gd, (size_t)h->n));
-        if (hipMemcpyAsync(gd, group, sizeof(double) * h->n, hipMemcpyHostToDevice, h->stream) != hipSuccess ||
-            hipMemcpyAsync(h->w_tmp, w, sizeof(double) * h->d, hipMemcpyHostToDevice, h->stream) != hipSuccess) {
-            rbl_set_error("fair_statistics: upload failed");
-            return RBL_ERR_HIP;
-        }
-        RBL_TRY(launch_gemv(h->storage, h->D, h->n, h->ld, h->w_tmp, h->m, h->num_cu, h->stream));
-        double* out14 = h->slab;  // scratch (>= 14 doubles)
-        RBL_TRY(launch_fair_counts(h->n, h->m, h->ysign, gd, threshold, h->partials, out14, h->stream, h->rs));
-        if (hipMemcpyAsync(c, out14, sizeof(double) * 14, hipMemcpyDeviceToHost, h->stream) != hipSuccess ||
-            hipStreamSynchronize(h->stream) != hipSuccess) {
-            rbl_set_error("fair_statistics: readback failed");
-            return RBL_ERR_HIP;
-        }
-    }
-    // fair_metric.py:11-41, group 0 = G1, group 1 = G2
-    const double G1P = c[1] / c[0], G2P = c[7] / c[6];
-    const double G1TP = c[2], G1FN = c[3], G1TN = c[4], G1FP = c[5];
-    const double G2TP = c[8], G2FN = c[9], G2TN = c[10], G2FP = c[11];
-    const double SPD = G2P - G1P;
-    const double DI = (G1P == 0.0) ? INFINITY : G2P / G1P;
-    const double TPRG1 = G1TP / (G1TP + G1FN), TPRG2 = G2TP / (G2TP + G2FN);
-    const double FPRG1 = G1FP / (G1FP + G1TN), FPRG2 = G2FP / (G2FP + G2TN);
-    const double FNRG1 = G1FN / (G1TP + G1FN), FNRG2 = G2FN / (G2TP + G2FN);
-    const double EOD = TPRG2 - TPRG1;
-    const double AOD = 0.5 * (FPRG2 - FPRG1 + EOD);
-    const double nn = (double)h->n;
-    const double mu = c[12] / nn;
-    const double TI = (c[13] - std::log(mu) * c[12]) / mu / nn;  // sum (b/mu) log(b/mu) / n
-    out6[0] = SPD;
-    out6[1] = DI;
-    out6[2] = EOD;
-    out6[3] = AOD;
-    out6[4] = TI;
-    out6[5] = FNRG2 - FNRG1;
     return RBL_OK;
 }
 
@@ -2920,771 +620,6 @@ int rbl_info(rbl_solver* h, int64_t* ld, int* num_cu, double* lipschitz) {
     if (ld) *ld = h->ld;
     if (num_cu) *num_cu = h->num_cu;
     if (lipschitz) *lipschitz = h->L;
-    return RBL_OK;
-}
-
-}  // extern "C"
-
-// ======================================================================== groups: K problems on one D
-// One ADMM iteration of every live member per rbl_group_step, the two n x d passes shared (sweep_multi.hip).
-struct rbl_group {
-    DevArena mem;
-    std::vector<rbl_solver*> m;
-    std::vector<char> live, saved_fused;
-    std::vector<hipStream_t> saved_stream;
-    std::vector<int64_t> base_launches;
-    std::vector<rbl_stats> last;
-    std::vector<int> syncs;          // host waits of each member's own calls in the step in flight
-    hipStream_t stream = nullptr;    // every member runs on it while the group exists: one order for all launches
-    int device = 0, kpp = 1;
-    bool shared_passes = false;      // the width is in the multi-column kernels' range
-    double* slab = nullptr;
-    int64_t shared_v = 0, shared_q = 0;
-};
-
-namespace {
-// runs a member's own calls and books the host waits they made on that member
-struct SyncBook {
-    int& slot;
-    int s0;
-    explicit SyncBook(int& sl) : slot(sl), s0(g_host_syncs) {}
-    ~SyncBook() { slot += g_host_syncs - s0; }
-};
-}  // namespace
-
-extern "C" {
-
-int rbl_group_create(rbl_solver* const* members, int k, rbl_group** out) {
-    if (!out) {
-        rbl_set_error("group_create: out is NULL");
-        return RBL_ERR_INVALID;
-    }
-    *out = nullptr;
-    if (!members || k < 1 || k > 64) {
-        rbl_set_error("group_create: 1..64 members (got %d)", k);
-        return RBL_ERR_INVALID;
-    }
-    for (int i = 0; i < k; ++i) {
-        rbl_solver* h = members[i];
-        if (!h) {
-            rbl_set_error("group_create: member %d is NULL", i);
-            return RBL_ERR_INVALID;
-        }
-        for (int j = 0; j < i; ++j)
-            if (members[j] == h) {
-                rbl_set_error("group_create: member %d is listed twice", i);
-                return RBL_ERR_INVALID;
-            }
-        if (h->in_group) {
-            rbl_set_error("group_create: member %d already belongs to a group", i);
-            return RBL_ERR_INVALID;
-        }
-        if (h->shared != members[0]->shared || h->D != members[0]->D) {
-            rbl_set_error("group_create: member %d does not share member 0's data (rbl_create_shared)", i);
-            return RBL_ERR_INVALID;
-        }
-        if (h->nt != h->n) {
-            rbl_set_error("group_create: member %d is a row shard (n=%lld of %lld): groups are single-process problems", i,
-                          (long long)h->n, (long long)h->nt);
-            return RBL_ERR_INVALID;
-        }
-        if (h->cfg.objective_only) {
-            rbl_set_error("group_create: member %d is an objective-only handle", i);
-            return RBL_ERR_INVALID;
-        }
-    }
-    rbl_solver* h0 = members[0];
-    RBL_HIP(hipSetDevice(h0->cfg.device));
-    for (int i = 0; i < k; ++i) {
-        RBL_TRY(require_ready(members[i]));
-        RBL_TRY(zb_resolve(members[i]));
-        RBL_TRY(cancel_spec(members[i]));
-        RBL_HIP(hipStreamSynchronize(members[i]->stream));
-    }
-    std::unique_ptr<rbl_group> g(new rbl_group());
-    g->device = h0->cfg.device;
-    RBL_HIP(hipStreamCreateWithFlags(&g->stream, hipStreamNonBlocking));
-    g->shared_passes = h0->n > 0 && sweep_multi_supported(h0->storage, h0->ld);
-    g->kpp = g->shared_passes ? sweep_multi_k(h0->storage, h0->ld) : 1;
-    if (g->shared_passes) {
-        const int rc = g->mem.alloc(&g->slab, sweep_multi_slab_doubles(h0->ld, h0->num_cu));
-        if (rc != RBL_OK) {
-            (void)hipStreamDestroy(g->stream);
-            return rc;
-        }
-    }
-    rbl_stats zero;
-    std::memset(&zero, 0, sizeof(zero));
-    for (int i = 0; i < k; ++i) {
-        rbl_solver* h = members[i];
-        g->m.push_back(h);
-        g->live.push_back(1);
-        g->saved_fused.push_back(h->fused_ok ? 1 : 0);
-        g->saved_stream.push_back(h->stream);
-        g->base_launches.push_back(h->nd_launches);
-        g->last.push_back(zero);
-        g->syncs.push_back(0);
-        h->in_group = true;
-        h->stream = g->stream;
-        // two-pass structure for every member: whatever a single-sweep erm pass prepared ahead is dropped
-        h->fused_ok = false;
-        h->z_ready = h->p_valid = h->p_pending = h->pred_valid = false;
-    }
-    *out = g.release();
-    return RBL_OK;
-}
-
-int rbl_group_destroy(rbl_group* g) {
-    if (!g) return RBL_OK;
-    (void)hipSetDevice(g->device);
-    if (g->stream) (void)hipStreamSynchronize(g->stream);
-    for (size_t i = 0; i < g->m.size(); ++i) {
-        rbl_solver* h = g->m[i];
-        (void)zb_resolve(h);   // a verdict still pending was written on the group's stream
-        if (h->stream == g->stream) h->stream = g->saved_stream[i];
-        h->fused_ok = g->saved_fused[i] != 0;
-        h->in_group = false;
-    }
-    if (g->stream) {
-        (void)hipStreamSynchronize(g->stream);
-        (void)hipStreamDestroy(g->stream);
-    }
-    delete g;   // g->mem frees the slab
-    return RBL_OK;
-}
-
-int rbl_group_step(rbl_group* g, int want_objective, rbl_stats* out) {
-    if (!g) {
-        rbl_set_error("group handle is NULL");
-        return RBL_ERR_INVALID;
-    }
-    RBL_HIP(hipSetDevice(g->device));
-    const int K = (int)g->m.size();
-    std::vector<int> idx;
-    for (int i = 0; i < K; ++i)
-        if (g->live[i]) idx.push_back(i);
-    hipStream_t s = g->stream;
-    for (int i : idx) g->syncs[i] = 0;
-    // A + B: every member's own z-step
-    for (int i : idx) {
-        SyncBook book(g->syncs[i]);
-        RBL_TRY(rbl_phase_m(g->m[i]));
-        RBL_TRY(rbl_phase_z(g->m[i], nullptr));
-    }
-    // C: q_k = D^T c_k, D read once per kpp members
-    if (g->shared_passes) {
-        for (int i : idx) {
-            rbl_solver* h = g->m[i];
-            if (h->sorted_path && !h->zb.c_ready) RBL_TRY(launch_make_c(h->n, h->z, h->lam, h->step_rho, h->c, s));
-            h->zb.c_ready = false;
-            h->zb.q_done = h->zb.used;     // an unsettled z-step's q is redone with it, by the member alone (zb_resolve)
-            h->s32.q_done = h->s32.used;
-        }
-        for (size_t b = 0; b < idx.size(); b += (size_t)g->kpp) {
-            const int kk = (int)std::min(idx.size() - b, (size_t)g->kpp);
-            const double* c[RBL_MULTI_KMAX];
-            double* q[RBL_MULTI_KMAX];
-            for (int j = 0; j < kk; ++j) {
-                c[j] = g->m[idx[b + j]]->c;
-                q[j] = g->m[idx[b + j]]->q;
-            }
-            rbl_solver* h0 = g->m[idx[b]];
-            RBL_TRY(launch_sweep_q_multi(h0->storage, h0->D, h0->n, h0->ld, kk, c, g->slab, q, h0->num_cu, s));
-            g->shared_q += 1;
-        }
-        for (int i : idx) {
-            rbl_solver* h = g->m[i];
-            h->pending_mask = 1;
-            h->z_ready = false;
-            if (h->phase_timing) RBL_HIP(hipEventRecord(h->ev[2], s));
-        }
-    } else {
-        for (int i : idx) {
-            SyncBook book(g->syncs[i]);
-            RBL_TRY(rbl_phase_q(g->m[i]));
-        }
-    }
-    // D: every member's own w-step (a z-step that was not certified is redone here, with its own q)
-    for (int i : idx) {
-        SyncBook book(g->syncs[i]);
-        RBL_TRY(rbl_phase_w(g->m[i]));
-    }
-    // E: v_k = D w_k, lambda_k += rho_k (z_k - v_k), the primal residuals - D read once per kpp members
-    if (g->shared_passes) {
-        for (size_t b = 0; b < idx.size(); b += (size_t)g->kpp) {
-            const int kk = (int)std::min(idx.size() - b, (size_t)g->kpp);
-            const double *w[RBL_MULTI_KMAX], *z[RBL_MULTI_KMAX];
-            double *lam[RBL_MULTI_KMAX], *v[RBL_MULTI_KMAX], *part[RBL_MULTI_KMAX], *red[RBL_MULTI_KMAX], rho[RBL_MULTI_KMAX];
-            for (int j = 0; j < kk; ++j) {
-                rbl_solver* h = g->m[idx[b + j]];
-                w[j] = h->w;
-                z[j] = h->z;
-                lam[j] = h->lam;
-                v[j] = h->v;
-                part[j] = h->partials;
-                red[j] = h->red;
-                rho[j] = h->step_rho;
-            }
-            rbl_solver* h0 = g->m[idx[b]];
-            RBL_TRY(launch_sweep_v_multi(h0->storage, h0->D, h0->n, h0->ld, kk, w, z, lam, v, rho, part, red, h0->num_cu, s));
-            g->shared_v += 1;
-        }
-        for (int i : idx) {
-            rbl_solver* h = g->m[i];
-            h->fused_ran = false;
-            h->fused_v_ran = true;
-            h->v_valid = true;
-            h->pending_mask = 2;
-            h->want_obj = want_objective;
-            h->obj_is_risk = false;
-            if (h->phase_timing) RBL_HIP(hipEventRecord(h->ev[4], s));
-            if (want_objective && h->sorted_path) {
-                RBL_TRY(risk_from_v(h, h->v, h->red + 1));
-                h->obj_is_risk = true;
-            } else if (want_objective) {
-                RBL_TRY(launch_loss_sum(h->cfg.loss, h->n, h->v, 1.0, h->partials, h->red + 1, s, h->rs));   // objective.py:11-24
-            }
-        }
-    } else {
-        for (int i : idx) {
-            SyncBook book(g->syncs[i]);
-            RBL_TRY(rbl_phase_dual(g->m[i], want_objective));
-        }
-    }
-    // F: all statistics kernels first, ONE host wait (the last one's word: they complete in stream order), then the
-    // stop tests and schedules
-    for (int i : idx) RBL_TRY(phase_finish_part(g->m[i], nullptr, FIN_ENQUEUE));
-    if (!idx.empty()) {
-        rbl_solver* hl = g->m[idx.back()];
-        SyncBook book(g->syncs[idx[0]]);
-        rbl_spin_wait(reinterpret_cast<volatile int*>(hl->hstat + 15), 0, s);
-    }
-    for (int i : idx) {
-        g_host_syncs = g->syncs[i];
-        RBL_TRY(phase_finish_part(g->m[i], &g->last[i], FIN_DIGEST));
-        if (g->last[i].converged) g->live[i] = 0;   // frozen where its own rbl_solve would have stopped
-    }
-    g_host_syncs = 0;
-    if (out)
-        for (int i = 0; i < K; ++i) out[i] = g->last[i];
-    return RBL_OK;
-}
-
-int rbl_group_solve(rbl_group* g, int max_iter, int want_objective, rbl_stats* last, double* hist_objective,
-                    double* hist_primal, double* hist_dual, double* hist_rho, int64_t* iters, int64_t cap) {
-    if (!g) {
-        rbl_set_error("group handle is NULL");
-        return RBL_ERR_INVALID;
-    }
-    const int K = (int)g->m.size();
-    if (max_iter <= 0)
-        for (int i = 0; i < K; ++i) max_iter = std::max(max_iter, (int)g->m[i]->cfg.max_iter);
-    std::vector<int64_t> done((size_t)K, 0);
-    for (int it = 0; it < max_iter; ++it) {
-        bool any = false;
-        std::vector<char> was_live(g->live);
-        for (int i = 0; i < K; ++i) any = any || was_live[i];
-        if (!any) break;
-        RBL_TRY(rbl_group_step(g, want_objective, nullptr));
-        for (int i = 0; i < K; ++i) {
-            if (!was_live[i]) continue;
-            const rbl_stats& st = g->last[i];
-            const int64_t k = done[i]++;
-            if (k < cap) {
-                if (hist_objective) hist_objective[i * cap + k] = st.objective;
-                if (hist_primal) hist_primal[i * cap + k] = st.primal;
-                if (hist_dual) hist_dual[i * cap + k] = st.dual;
-                if (hist_rho) hist_rho[i * cap + k] = st.rho;
-            }
-        }
-    }
-    for (int i = 0; i < K; ++i) {
-        if (iters) iters[i] = done[i];
-        if (last) last[i] = g->last[i];
-    }
-    return RBL_OK;
-}
-
-int rbl_group_counters(rbl_group* g, int* k_per_pass, int64_t* shared_v, int64_t* shared_q, int64_t* single_passes) {
-    if (!g) {
-        rbl_set_error("group handle is NULL");
-        return RBL_ERR_INVALID;
-    }
-    if (k_per_pass) *k_per_pass = g->kpp;
-    if (shared_v) *shared_v = g->shared_v;
-    if (shared_q) *shared_q = g->shared_q;
-    if (single_passes)
-        for (size_t i = 0; i < g->m.size(); ++i) single_passes[i] = g->m[i]->nd_launches - g->base_launches[i];
-    return RBL_OK;
-}
-
-}  // extern "C"
-
-// =================================================== kernel-level entry points (host buffers)
-// They run on the same workspace allocators as the solver handle (alloc_sort, alloc_pav, alloc_prefix, alloc_wstep).
-namespace {
-struct Scratch {   // the buffers and the stream of one call
-    DevArena mem;
-    hipStream_t s = nullptr;
-    ~Scratch() {
-        if (s) (void)hipStreamDestroy(s);
-    }
-    template <typename T>
-    int upload(T** p, const T* host, size_t count) {
-        RBL_TRY(mem.alloc(p, count));
-        if (count) RBL_HIP(hipMemcpy(*p, host, count * sizeof(T), hipMemcpyHostToDevice));
-        return RBL_OK;
-    }
-};
-
-int scratch_begin(Scratch& sc, int* num_cu) {
-    RBL_TRY(check_device(nullptr));
-    RBL_HIP(hipStreamCreateWithFlags(&sc.s, hipStreamNonBlocking));
-    if (num_cu) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        RBL_HIP(hipGetDevice(&dev));
-        RBL_HIP(hipGetDeviceProperties(&prop, dev));
-        *num_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-    }
-    return RBL_OK;
-}
-
-// D (host fp64 n x d) -> device storage with ld padding
-int upload_matrix(Scratch& sc, int storage, int64_t n, int64_t d, const double* D, void** Dd, int64_t* ld_out) {
-    const int64_t ld = rbl_storage_ld(storage, d);
-    const size_t esz = rbl_storage_esz(storage);
-    std::vector<unsigned char> host((size_t)n * ld * esz, 0);
-    for (int64_t r = 0; r < n; ++r)
-        for (int64_t j = 0; j < d; ++j) {
-            if (storage == RBL_STORE_F16) ((unsigned short*)host.data())[r * ld + j] = f64_to_f16_bits(D[r * d + j]);
-            else if (storage == RBL_STORE_F32) ((float*)host.data())[r * ld + j] = (float)D[r * d + j];
-            else ((double*)host.data())[r * ld + j] = D[r * d + j];
-        }
-    RBL_TRY(sc.upload((unsigned char**)Dd, host.data(), host.size()));
-    *ld_out = ld;
-    return RBL_OK;
-}
-}  // namespace
-
-extern "C" {
-
-// the kernel-level entry points check the loss id before any device work
-static int k_check_loss(const char* who, int loss) {
-    if (rbl_check_loss(loss) == RBL_OK) return RBL_OK;
-    rbl_set_error("%s: unknown loss id %d", who, loss);
-    return RBL_ERR_INVALID;
-}
-
-int rbl_k_prox(int loss, int64_t n, const double* sigma, double rho, const double* m, double* out) {
-    RBL_TRY(k_check_loss("rbl_k_prox", loss));
-    Scratch sc;
-    RBL_TRY(scratch_begin(sc, nullptr));
-    if (n <= 0) return RBL_OK;
-    double *ds = nullptr, *dm = nullptr, *dout = nullptr;
-    RBL_TRY(sc.upload(&ds, sigma, (size_t)n));
-    RBL_TRY(sc.upload(&dm, m, (size_t)n));
-    RBL_TRY(sc.mem.alloc(&dout, (size_t)n));
-    RBL_TRY(launch_prox(loss, n, ds, rho, dm, dout, sc.s));
-    RBL_HIP(hipMemcpyAsync(out, dout, sizeof(double) * n, hipMemcpyDeviceToHost, sc.s));
-    RBL_HIP(hipStreamSynchronize(sc.s));
-    return RBL_OK;
-}
-
-int rbl_k_sort(int64_t n, const double* keys, double* sorted_keys, uint32_t* perm) {
-    Scratch sc;
-    RBL_TRY(scratch_begin(sc, nullptr));
-    if (n <= 0) return RBL_OK;
-    double *dk = nullptr, *ms = nullptr;
-    RBL_TRY(sc.upload(&dk, keys, (size_t)n));
-    SortWorkspace sw{};
-    RBL_TRY(alloc_sort(sc.mem, sw, n, true, sc.s));
-    RBL_TRY(sc.mem.alloc(&ms, (size_t)n));
-    RBL_TRY(launch_keys_from_m(n, dk, sw.keys[0], sw.vals[0], sc.s));
-    RBL_TRY(launch_radix_sort(sw, n, true, sc.s));
-    RBL_TRY(launch_unflip_keys(n, sw.keys[0], ms, sc.s));
-    if (sorted_keys) RBL_HIP(hipMemcpyAsync(sorted_keys, ms, sizeof(double) * n, hipMemcpyDeviceToHost, sc.s));
-    if (perm) RBL_HIP(hipMemcpyAsync(perm, sw.vals[0], sizeof(u32) * n, hipMemcpyDeviceToHost, sc.s));
-    RBL_HIP(hipStreamSynchronize(sc.s));
-    return RBL_OK;
-}
-
-// The sort of the z-step with 32-bit keys: the launches of z_step_sorted's use32 branch, in its order, on buffers laid
-// out as a handle's (rbl_phase_m: launch_make_m_range with v = m, lambda = 0, rho = 1 - m - 0/1 has the input's bits).
-// The fix-up compares m numerically: -0.0 and +0.0 tie and keep their row order, where rbl_k_sort orders the bit
-// patterns (every -0.0 before every +0.0).  *flag = 1: a run of more than S32_MAX_RUN equal keys; m_sorted / ids are
-// then meaningless (zb_resolve redoes such a z-step with 64-bit keys).
-int rbl_k_sort32(int64_t n, const double* m, uint32_t idx_off, double* m_sorted, uint32_t* ids, int* flag) {
-    Scratch sc;
-    RBL_TRY(scratch_begin(sc, nullptr));
-    if (flag) *flag = 0;
-    if (n <= 0) return RBL_OK;
-    if (!m || n + (int64_t)idx_off > (1LL << 32)) {
-        rbl_set_error("rbl_k_sort32: m is NULL or n + idx_off exceeds 2^32 (row ids are 32 bits)");
-        return RBL_ERR_INVALID;
-    }
-    double *dv = nullptr, *dlam = nullptr, *dm = nullptr, *ms = nullptr;
-    u64* mm = nullptr;
-    int* dflag = nullptr;
-    RBL_TRY(sc.upload(&dv, m, (size_t)n));
-    RBL_TRY(sc.mem.alloc(&dlam, (size_t)n));
-    RBL_TRY(sc.mem.alloc(&dm, (size_t)n));
-    RBL_TRY(sc.mem.alloc(&ms, (size_t)n));
-    RBL_TRY(sc.mem.alloc(&mm, (size_t)s32_range_words()));
-    RBL_TRY(sc.mem.alloc(&dflag, 1));
-    RBL_HIP(hipMemsetAsync(dlam, 0, sizeof(double) * n, sc.s));
-    SortWorkspace sw{};
-    RBL_TRY(alloc_sort(sc.mem, sw, n, true, sc.s));
-    u32* k32 = reinterpret_cast<u32*>(sw.keys[0]);
-    RBL_TRY(launch_make_m_range(n, 1.0, dv, dlam, dm, mm, sc.s, nullptr));
-    RBL_TRY(launch_keys32(n, dm, mm, k32, sw.vals[0], idx_off, sc.s));
-    RBL_TRY(launch_radix_sort32(sw, n, sc.s));
-    RBL_TRY(launch_sort32_fix(n, k32, sw.vals[0], dm, idx_off, ms, sw.vals[1], dflag, sc.s));
-    if (m_sorted) RBL_HIP(hipMemcpyAsync(m_sorted, ms, sizeof(double) * n, hipMemcpyDeviceToHost, sc.s));
-    if (ids) RBL_HIP(hipMemcpyAsync(ids, sw.vals[1], sizeof(u32) * n, hipMemcpyDeviceToHost, sc.s));
-    int f = 0;
-    RBL_HIP(hipMemcpyAsync(&f, dflag, sizeof(int), hipMemcpyDeviceToHost, sc.s));
-    RBL_HIP(hipStreamSynchronize(sc.s));
-    if (flag) *flag = f;
-    return RBL_OK;
-}
-
-// ncalls successive PAV solves on ONE workspace (m_sorted: ncalls x n): the hints of the upper seams, the barrier parity
-// and the EHRM speculated branch carry over from one call to the next as they do between the z-steps of a solve.
-static int k_pav_common(int loss, int64_t n, const double* sigma_a, const double* sigma_b, int ehrm, double B,
-                        double rho, int ncalls, const double* m_sorted, int branch_in, int upper, double* out,
-                        int64_t* n_merges, int* branch_out, uint32_t* counters_out) {
-    Scratch sc;
-    RBL_TRY(scratch_begin(sc, nullptr));
-    if (n <= 0 || ncalls <= 0) return RBL_OK;
-    double *sa = nullptr, *sb = nullptr;
-    RBL_TRY(sc.upload(&sa, sigma_a, (size_t)n));
-    if (ehrm) RBL_TRY(sc.upload(&sb, sigma_b, (size_t)n));
-    else sb = sa;
-    PavWorkspace pw{};   // the sorted m goes to pw.ms, its prefix sums to pw.pm
-    RBL_TRY(alloc_pav(sc.mem, pw, n, sc.s));
-    PrefixBufs pa, pb;
-    RBL_TRY(alloc_prefix(sc.mem, pa, n));
-    pb = pa;
-    if (ehrm) RBL_TRY(alloc_prefix(sc.mem, pb, n));
-    PavExtras ex = pw.ex;
-    {
-        int dev = 0, cus = 0;
-        RBL_HIP(hipGetDevice(&dev));
-        RBL_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-        ex.num_cu = cus;
-    }
-    ex.B = B;
-    ex.upper = upper;
-    {
-        const char* e = getenv("RBL_EHRM_SPEC");   // 0 / 1: the speculated branch; -1: round 2's separate pass
-        if (e && (atoi(e) == 0 || atoi(e) == 1)) ex.spec = atoi(e);
-        // a forced branch (the tests pin both) and RBL_EHRM_SPEC=-1 go through the separate test; the automatic choice
-        // through the speculation inside the bottom kernel
-        if (!ehrm || branch_in >= 0 || (e && atoi(e) == -1)) ex.fpart = nullptr;
-    }
-    RBL_TRY(launch_prefix(sa, n, pa, sc.s));
-    if (ehrm) RBL_TRY(launch_prefix(sb, n, pb, sc.s));
-    // identity permutation scatter applies the EHRM clip
-    std::vector<u32> idh((size_t)n);
-    for (int64_t i = 0; i < n; ++i) idh[(size_t)i] = (u32)i;
-    u32* idd = nullptr;
-    double* zz = nullptr;
-    RBL_TRY(sc.upload(&idd, idh.data(), (size_t)n));
-    RBL_TRY(sc.mem.alloc(&zz, (size_t)n));
-    for (int call = 0; call < ncalls; ++call) {
-        RBL_HIP(hipMemcpyAsync(pw.ms, m_sorted + (size_t)call * n, sizeof(double) * n, hipMemcpyHostToDevice, sc.s));
-        RBL_TRY(launch_prefix(pw.ms, n, pw.pm, sc.s));
-        if (ehrm && !ex.fpart) RBL_TRY(launch_ehrm_branch(n, sa, sb, B, rho, pw.ms, pw.partials, pw.branch, branch_in, sc.s));
-        RBL_TRY(launch_pav_tree(loss, n, rho, pw.ms, sa, sb, pw.u, pa.view(), pb.view(), pw.pm.view(), ehrm ? pw.branch : nullptr,
-                                pw.recs, pw.counters, sc.s, nullptr, nullptr, &ex));
-        RBL_TRY(launch_scatter_z(n, pw.u, idd, ehrm ? pw.branch : nullptr, B, ehrm, rho, nullptr, zz, nullptr, 0, n, sc.s));
-        RBL_HIP(hipMemcpyAsync(out + (size_t)call * n, zz, sizeof(double) * n, hipMemcpyDeviceToHost, sc.s));
-        unsigned mc4[4] = {0, 0, 0, 0};
-        int br = -1;
-        RBL_HIP(hipMemcpyAsync(mc4, pw.counters, sizeof(mc4), hipMemcpyDeviceToHost, sc.s));
-        if (ehrm) RBL_HIP(hipMemcpyAsync(&br, pw.branch, sizeof(int), hipMemcpyDeviceToHost, sc.s));
-        RBL_HIP(hipStreamSynchronize(sc.s));
-        if (counters_out)
-            for (int j = 0; j < 4; ++j) counters_out[4 * call + j] = mc4[j];
-        if (mc4[3] != 0) {
-            rbl_set_error("PAV: the upper-level kernel did not complete (a wait gave up or its fill list overflowed)");
-            return RBL_ERR_HIP;
-        }
-        if (n_merges) n_merges[call] = mc4[0];
-        if (branch_out) branch_out[call] = br;
-        if (ehrm && br >= 0) ex.spec = br;   // the next call speculates the branch this one took (rbl_phase_finish)
-    }
-    return RBL_OK;
-}
-
-int rbl_k_pav(int loss, int64_t n, const double* sigma, double rho, const double* m_sorted, double* out,
-              int64_t* n_merges) {
-    RBL_TRY(k_check_loss("rbl_k_pav", loss));
-    return k_pav_common(loss, n, sigma, sigma, 0, 0.0, rho, 1, m_sorted, -1, PAV_UPPER_DEFAULT, out, n_merges, nullptr,
-                        nullptr);
-}
-
-int rbl_k_pav_ehrm(int64_t n, const double* sigma_a, const double* sigma_b, double B, double rho,
-                   const double* m_sorted, int branch, double* out, int* branch_out) {
-    return k_pav_common(RBL_LOSS_BCE, n, sigma_a, sigma_b, 1, B, rho, 1, m_sorted, branch, PAV_UPPER_DEFAULT, out, nullptr,
-                        branch_out, nullptr);
-}
-
-int rbl_k_pav_seq(int loss, int64_t n, const double* sigma_a, const double* sigma_b, double B, double rho, int ncalls,
-                  const double* m_sorted, int upper, double* out, int* branch_out, uint32_t* counters) {
-    RBL_TRY(k_check_loss("rbl_k_pav_seq", loss));
-    if (upper != RBL_PAV_UPPER_PERSIST && upper != RBL_PAV_UPPER_TWO_LAUNCH) {
-        rbl_set_error("rbl_k_pav_seq: upper must be RBL_PAV_UPPER_PERSIST or RBL_PAV_UPPER_TWO_LAUNCH, got %d", upper);
-        return RBL_ERR_INVALID;
-    }
-    const int ehrm = sigma_b != nullptr;
-    if (ehrm && loss != RBL_LOSS_BCE) {
-        rbl_set_error("rbl_k_pav_seq: the EHRM z-step is defined for the BCE loss only");
-        return RBL_ERR_INVALID;
-    }
-    return k_pav_common(loss, n, sigma_a, ehrm ? sigma_b : sigma_a, ehrm, B, rho, ncalls, m_sorted, -1,
-                        upper == RBL_PAV_UPPER_PERSIST ? PAV_UPPER_PERSIST : PAV_UPPER_TWO_LAUNCH, out, nullptr, branch_out,
-                        counters);
-}
-
-int rbl_k_gemv(int storage, int64_t n, int64_t d, const double* D, const double* w, double* v) {
-    Scratch sc;
-    int num_cu = 256;
-    RBL_TRY(scratch_begin(sc, &num_cu));
-    if (n <= 0) return RBL_OK;
-    void* Dd = nullptr;
-    int64_t ld = 0;
-    RBL_TRY(upload_matrix(sc, storage, n, d, D, &Dd, &ld));
-    std::vector<double> wp((size_t)ld, 0.0);
-    for (int64_t j = 0; j < d; ++j) wp[(size_t)j] = w[j];
-    double *dw = nullptr, *dv = nullptr;
-    RBL_TRY(sc.upload(&dw, wp.data(), (size_t)ld));
-    RBL_TRY(sc.mem.alloc(&dv, (size_t)n));
-    RBL_TRY(launch_gemv(storage, Dd, n, ld, dw, dv, num_cu, sc.s));
-    RBL_HIP(hipMemcpyAsync(v, dv, sizeof(double) * n, hipMemcpyDeviceToHost, sc.s));
-    RBL_HIP(hipStreamSynchronize(sc.s));
-    return RBL_OK;
-}
-
-int rbl_k_gemvt(int storage, int64_t n, int64_t d, const double* D, const double* c, double* q) {
-    Scratch sc;
-    int num_cu = 256;
-    RBL_TRY(scratch_begin(sc, &num_cu));
-    void* Dd = nullptr;
-    int64_t ld = 0;
-    RBL_TRY(upload_matrix(sc, storage, n > 0 ? n : 0, d, D, &Dd, &ld));
-    double *dc = nullptr, *slab = nullptr, *dq = nullptr;
-    RBL_TRY(sc.upload(&dc, c, (size_t)n));
-    RBL_TRY(sc.mem.alloc(&slab, (size_t)gemvt_slab_rows(num_cu) * ld));
-    RBL_TRY(sc.mem.alloc(&dq, (size_t)ld));
-    RBL_TRY(launch_gemvt(storage, Dd, n, ld, dc, slab, dq, num_cu, sc.s));
-    RBL_HIP(hipMemcpyAsync(q, dq, sizeof(double) * d, hipMemcpyDeviceToHost, sc.s));
-    RBL_HIP(hipStreamSynchronize(sc.s));
-    return RBL_OK;
-}
-
-int rbl_k_gemv_multi(int storage, int64_t n, int64_t d, int k, const double* D, const double* W, double* V) {
-    if (k < 1 || k > 64 || d <= 0) {
-        rbl_set_error("rbl_k_gemv_multi: 1..64 columns, d > 0");
-        return RBL_ERR_INVALID;
-    }
-    Scratch sc;
-    int num_cu = 256;
-    RBL_TRY(scratch_begin(sc, &num_cu));
-    if (n <= 0) return RBL_OK;
-    void* Dd = nullptr;
-    int64_t ld = 0;
-    RBL_TRY(upload_matrix(sc, storage, n, d, D, &Dd, &ld));
-    std::vector<double> wp((size_t)ld * k, 0.0);
-    for (int j = 0; j < k; ++j)
-        for (int64_t i = 0; i < d; ++i) wp[(size_t)j * ld + i] = W[(size_t)j * d + i];
-    double *dw = nullptr, *dv = nullptr;
-    RBL_TRY(sc.upload(&dw, wp.data(), wp.size()));
-    RBL_TRY(sc.mem.alloc(&dv, (size_t)n * k));
-    const bool multi = sweep_multi_supported(storage, ld);
-    const int kpp = multi ? sweep_multi_k(storage, ld) : 1;
-    for (int j0 = 0; j0 < k; j0 += kpp) {
-        const int kk = std::min(kpp, k - j0);
-        if (!multi) {   // outside the multi-column kernels' widths: the single-column pass per column
-            RBL_TRY(launch_gemv(storage, Dd, n, ld, dw + (size_t)j0 * ld, dv + (size_t)j0 * n, num_cu, sc.s));
-            continue;
-        }
-        const double* w[RBL_MULTI_KMAX];
-        double* v[RBL_MULTI_KMAX];
-        for (int j = 0; j < kk; ++j) {
-            w[j] = dw + (size_t)(j0 + j) * ld;
-            v[j] = dv + (size_t)(j0 + j) * n;
-        }
-        RBL_TRY(launch_sweep_v_multi(storage, Dd, n, ld, kk, w, nullptr, nullptr, v, nullptr, nullptr, nullptr, num_cu, sc.s));
-    }
-    RBL_HIP(hipMemcpyAsync(V, dv, sizeof(double) * n * k, hipMemcpyDeviceToHost, sc.s));
-    RBL_HIP(hipStreamSynchronize(sc.s));
-    return RBL_OK;
-}
-
-int rbl_k_gemvt_multi(int storage, int64_t n, int64_t d, int k, const double* D, const double* Cm, double* Q) {
-    if (k < 1 || k > 64 || d <= 0) {
-        rbl_set_error("rbl_k_gemvt_multi: 1..64 columns, d > 0");
-        return RBL_ERR_INVALID;
-    }
-    Scratch sc;
-    int num_cu = 256;
-    RBL_TRY(scratch_begin(sc, &num_cu));
-    void* Dd = nullptr;
-    int64_t ld = 0;
-    RBL_TRY(upload_matrix(sc, storage, n > 0 ? n : 0, d, D, &Dd, &ld));
-    double *dc = nullptr, *slab = nullptr, *dq = nullptr;
-    RBL_TRY(sc.upload(&dc, Cm, (size_t)(n > 0 ? n : 0) * k));
-    const bool multi = n > 0 && sweep_multi_supported(storage, ld);
-    const int kpp = multi ? sweep_multi_k(storage, ld) : 1;
-    RBL_TRY(sc.mem.alloc(&slab, multi ? sweep_multi_slab_doubles(ld, num_cu) : (size_t)gemvt_slab_rows(num_cu) * ld));
-    RBL_TRY(sc.mem.alloc(&dq, (size_t)ld * k));
-    for (int j0 = 0; j0 < k; j0 += kpp) {
-        const int kk = std::min(kpp, k - j0);
-        if (!multi) {
-            RBL_TRY(launch_gemvt(storage, Dd, n, ld, dc + (size_t)j0 * (n > 0 ? n : 0), slab, dq + (size_t)j0 * ld, num_cu, sc.s));
-            continue;
-        }
-        const double* c[RBL_MULTI_KMAX];
-        double* q[RBL_MULTI_KMAX];
-        for (int j = 0; j < kk; ++j) {
-            c[j] = dc + (size_t)(j0 + j) * n;
-            q[j] = dq + (size_t)(j0 + j) * ld;
-        }
-        RBL_TRY(launch_sweep_q_multi(storage, Dd, n, ld, kk, c, slab, q, num_cu, sc.s));
-    }
-    for (int j = 0; j < k; ++j)
-        RBL_HIP(hipMemcpyAsync(Q + (size_t)j * d, dq + (size_t)j * ld, sizeof(double) * d, hipMemcpyDeviceToHost, sc.s));
-    RBL_HIP(hipStreamSynchronize(sc.s));
-    return RBL_OK;
-}
-
-int rbl_k_gram(int storage, int64_t n, int64_t d, const double* D, double* G) {
-    Scratch sc;
-    int num_cu = 256;
-    RBL_TRY(scratch_begin(sc, &num_cu));
-    void* Dd = nullptr;
-    int64_t ld = 0;
-    RBL_TRY(upload_matrix(sc, storage, n, d, D, &Dd, &ld));
-    double *slab = nullptr, *dG = nullptr;
-    RBL_TRY(sc.mem.alloc((unsigned char**)&slab, gram_slab_bytes(ld, num_cu, n > 0 ? n : 1)));
-    RBL_TRY(sc.mem.alloc(&dG, (size_t)ld * ld));
-    RBL_TRY(launch_gram(storage, Dd, n, ld, d, slab, dG, num_cu, sc.s));
-    std::vector<double> hG((size_t)ld * ld);
-    RBL_HIP(hipMemcpyAsync(hG.data(), dG, sizeof(double) * ld * ld, hipMemcpyDeviceToHost, sc.s));
-    RBL_HIP(hipStreamSynchronize(sc.s));
-    for (int64_t i = 0; i < d; ++i)
-        for (int64_t j = 0; j < d; ++j) G[i * d + j] = hG[(size_t)(i * ld + j)];
-    return RBL_OK;
-}
-
-int rbl_k_wstep(int wstep, int64_t d, const double* G, const double* q, double rho, double reg, double smooth_t,
-                const double* w0, double tol, double* w_out, int* iters) {
-    Scratch sc;
-    RBL_TRY(scratch_begin(sc, nullptr));
-    const int64_t ld = round_up(d, 4);
-    std::vector<double> hG((size_t)ld * ld, 0.0), hq((size_t)ld, 0.0), hw((size_t)ld, 0.0);
-    for (int64_t i = 0; i < d; ++i) {
-        for (int64_t j = 0; j < d; ++j) hG[(size_t)(i * ld + j)] = G[i * d + j];
-        hq[(size_t)i] = q[i];
-        hw[(size_t)i] = w0 ? w0[i] : 0.0;
-    }
-    double *dG = nullptr, *dq = nullptr, *dw = nullptr;
-    RBL_TRY(sc.upload(&dG, hG.data(), hG.size()));
-    RBL_TRY(sc.upload(&dq, hq.data(), hq.size()));
-    RBL_TRY(sc.upload(&dw, hw.data(), hw.size()));
-    WstepWorkspace ww{};
-    RBL_TRY(alloc_wstep(sc.mem, ww, ld, sc.s));
-    double lam = 0.0;
-    RBL_TRY(launch_power_iteration(dG, ld, ww.yk, ww.Gy, ww.scal, 100, &lam, sc.s));
-    double L = 1.02 * lam;
-    if (!(L > 0.0)) L = 1.0;
-    int it = 0;
-    RBL_TRY(run_wstep(wstep, dG, ld, dq, rho, reg, smooth_t, L, tol > 0.0 ? tol : 1e-13, 100000, dw, ww, &it, sc.s));
-    RBL_HIP(hipMemcpyAsync(w_out, dw, sizeof(double) * d, hipMemcpyDeviceToHost, sc.s));
-    RBL_HIP(hipStreamSynchronize(sc.s));
-    if (iters) *iters = it;
-    return RBL_OK;
-}
-
-int rbl_k_wstep_pen(int64_t d, const double* G, const double* q, double rho, const double* l1, const double* l2,
-                    const double* w0, double tol, double* w_out, int* iters, int* form) {
-    if (d <= 0 || !G || !q || !w_out || (!l1 && !l2) || !(rho > 0.0)) {
-        rbl_set_error("k_wstep_pen: bad argument (d > 0, G, q, w_out, rho > 0 and l1 or l2 are needed)");
-        return RBL_ERR_INVALID;
-    }
-    bool any_l1 = false;
-    double l2max = 0.0;
-    for (int k = 0; k < 2; ++k) {
-        const double* v = k ? l2 : l1;
-        for (int64_t j = 0; v && j < d; ++j) {
-            if (!(v[j] >= 0.0) || !std::isfinite(v[j])) {
-                rbl_set_error("k_wstep_pen: %s[%lld] = %g - penalties must be finite and >= 0", k ? "l2" : "l1", (long long)j,
-                              v[j]);
-                return RBL_ERR_INVALID;
-            }
-            if (!k && v[j] > 0.0) any_l1 = true;
-            if (k && v[j] > l2max) l2max = v[j];
-        }
-    }
-    Scratch sc;
-    RBL_TRY(scratch_begin(sc, nullptr));
-    const int64_t ld = round_up(d, 4);
-    std::vector<double> hG((size_t)ld * ld, 0.0), hq((size_t)ld, 0.0), hw((size_t)ld, 0.0), hp((size_t)(2 * ld), 0.0);
-    for (int64_t i = 0; i < d; ++i) {
-        for (int64_t j = 0; j < d; ++j) hG[(size_t)(i * ld + j)] = G[i * d + j];
-        hq[(size_t)i] = q[i];
-        hw[(size_t)i] = w0 ? w0[i] : 0.0;
-        hp[(size_t)i] = l1 ? l1[i] : 0.0;
-        hp[(size_t)(ld + i)] = l2 ? l2[i] : 0.0;
-    }
-    double *dG = nullptr, *dq = nullptr, *dw = nullptr, *dp = nullptr;
-    RBL_TRY(sc.upload(&dG, hG.data(), hG.size()));
-    RBL_TRY(sc.upload(&dq, hq.data(), hq.size()));
-    RBL_TRY(sc.upload(&dw, hw.data(), hw.size()));
-    RBL_TRY(sc.upload(&dp, hp.data(), hp.size()));
-    WstepWorkspace ww{};
-    RBL_TRY(alloc_wstep(sc.mem, ww, ld, sc.s));
-    ww.pen_l1 = dp;
-    ww.pen_l2 = dp + ld;
-    ww.pen_l2max = l2max;
-    double lam = 0.0;
-    RBL_TRY(launch_power_iteration(dG, ld, ww.yk, ww.Gy, ww.scal, 100, &lam, sc.s));
-    double L = 1.02 * lam;
-    if (!(L > 0.0)) L = 1.0;
-    int it = 0;
-    RBL_TRY(run_wstep(any_l1 ? RBL_WSTEP_L1 : RBL_WSTEP_L2, dG, ld, dq, rho, 0.0, 1.0, L, tol > 0.0 ? tol : 1e-13, 100000, dw,
-                      ww, &it, sc.s));
-    RBL_HIP(hipMemcpyAsync(w_out, dw, sizeof(double) * d, hipMemcpyDeviceToHost, sc.s));
-    RBL_HIP(hipStreamSynchronize(sc.s));
-    if (iters) *iters = it;
-    if (form) *form = ww.form;
-    return RBL_OK;
-}
-
-int rbl_k_weights(int weight_function, int64_t n, const double* args, int n_args, double* alphas, double* betas) {
-    Scratch sc;
-    RBL_TRY(scratch_begin(sc, nullptr));
-    if (weight_function < RBL_W_ERM || weight_function > RBL_W_EHRM) {
-        rbl_set_error("Unrecognized framework! Options: ['erm','extremile','superquantile','esrm','aorr','aorr_dc','ehrm']");
-        return RBL_ERR_INVALID;
-    }
-    if (weight_function != RBL_W_ERM && weight_function != RBL_W_EHRM) {
-        const int need = (weight_function == RBL_W_AORR || weight_function == RBL_W_AORR_DC) ? 2 : 1;
-        if (!args || n_args < need) {
-            rbl_set_error("args for framework is None!");
-            return RBL_ERR_INVALID;
-        }
-    }
-    double a2[2] = {args && n_args > 0 ? args[0] : 0.0, args && n_args > 1 ? args[1] : 0.0};
-    double *da = nullptr, *db = nullptr;
-    RBL_TRY(sc.mem.alloc(&da, (size_t)n));
-    RBL_TRY(sc.mem.alloc(&db, (size_t)n));
-    RBL_TRY(launch_weights(weight_function, n, a2, da, db, sc.s));
-    if (alphas) RBL_HIP(hipMemcpyAsync(alphas, da, sizeof(double) * n, hipMemcpyDeviceToHost, sc.s));
-    if (betas) RBL_HIP(hipMemcpyAsync(betas, db, sizeof(double) * n, hipMemcpyDeviceToHost, sc.s));
-    RBL_HIP(hipStreamSynchronize(sc.s));
     return RBL_OK;
 }
 

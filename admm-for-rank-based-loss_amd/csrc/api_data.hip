@@ -1,0 +1,740 @@
+// api_data.hip - the data path of a solver handle: rbl_set_data / rbl_set_data_from (X in the caller's type, from host
+// or device memory, optional column scaling), the synthetic generator's host side, penalties, labels, the one-vs-rest
+// decision, the Gram matrix and rbl_get_D.
+#include "api_internal.h"
+
+// ---- rbl_set_data_from: X in the caller's type, from host or device memory ------------------------------------------
+static inline size_t src_esz(int dtype) { return dtype == RBL_DTYPE_F16 ? 2 : dtype == RBL_DTYPE_F32 ? 4 : 8; }
+static inline double src_host_widen(const void* p, int dtype) {
+    if (dtype == RBL_DTYPE_F16) return (double)(float)__builtin_bit_cast(_Float16, *(const unsigned short*)p);
+    if (dtype == RBL_DTYPE_F32) return (double)*(const float*)p;
+    return *(const double*)p;
+}
+// first and last byte of the claimed range must be device memory of the handle's device (a host pointer must fail here,
+// with a message, not fault in a kernel)
+static int src_check_device_range(const void* X, size_t bytes, int device) {
+    const char* ends[2] = {(const char*)X, (const char*)X + (bytes ? bytes - 1 : 0)};
+    for (const char* p : ends) {
+        hipPointerAttribute_t a;
+        const hipError_t e = hipPointerGetAttributes(&a, p);
+        if (e != hipSuccess) (void)hipGetLastError();
+        if (e != hipSuccess || a.type != hipMemoryTypeDevice) {
+            rbl_set_error("set_data_from: X was passed as RBL_MEM_DEVICE but %p is not device memory (a host array goes "
+                          "with RBL_MEM_HOST)", (const void*)p);
+            return RBL_ERR_INVALID;
+        }
+        if (a.device != device) {
+            rbl_set_error("set_data_from: X lives on device %d, the handle on device %d", a.device, device);
+            return RBL_ERR_INVALID;
+        }
+    }
+    return RBL_OK;
+}
+// The upload pipeline of a host source of any element type: the caller's rows are pinned in place and go over
+// PCIe untouched, chunk by chunk, into two staging buffers (the copy of chunk k + 1 runs on a second stream while the
+// kernels of chunk k read staging buffer k & 1).  A device source is one "chunk": the caller's own memory.
+struct SrcPipe {
+    DevArena tmp;
+    unsigned char* Xd[2] = {nullptr, nullptr};
+    hipStream_t stream = nullptr, copy_stream = nullptr;
+    hipEvent_t copied[2] = {nullptr, nullptr}, formed[2] = {nullptr, nullptr};
+    void* registered = nullptr;
+    ~SrcPipe() {   // (the arena's buffers are freed after this body: nothing may still be running on them)
+        if (copy_stream) (void)hipStreamSynchronize(copy_stream);
+        (void)hipStreamSynchronize(stream);
+        for (int k = 0; k < 2; ++k) {
+            if (copied[k]) (void)hipEventDestroy(copied[k]);
+            if (formed[k]) (void)hipEventDestroy(formed[k]);
+        }
+        if (copy_stream) (void)hipStreamDestroy(copy_stream);
+        if (registered) (void)hipHostUnregister(registered);
+        (void)hipGetLastError();
+    }
+    int open_host(const void* X, size_t xbytes, size_t chunk_bytes) {
+        if (hipHostRegister(const_cast<void*>(X), xbytes, hipHostRegisterDefault) == hipSuccess) registered = const_cast<void*>(X);
+        else (void)hipGetLastError();   // pageable copies instead: slower, same result
+        RBL_TRY(tmp.alloc(&Xd[0], chunk_bytes));
+        RBL_TRY(tmp.alloc(&Xd[1], chunk_bytes));
+        RBL_HIP(hipStreamCreateWithFlags(&copy_stream, hipStreamNonBlocking));
+        for (int k = 0; k < 2; ++k) {
+            RBL_HIP(hipEventCreateWithFlags(&copied[k], hipEventDisableTiming));
+            RBL_HIP(hipEventCreateWithFlags(&formed[k], hipEventDisableTiming));
+        }
+        return RBL_OK;
+    }
+    // one pass over the source: fn(rows on the device, first row, row count) enqueues its kernels on `stream`; returns
+    // with both streams idle
+    int pass(const void* X, int mem, size_t esz, int64_t ldx, int64_t ds, int64_t n, int64_t chunk,
+             const std::function<int(const void*, int64_t, int64_t)>& fn, double* ms = nullptr) {
+        int rc = RBL_OK;
+        hipEvent_t t0 = nullptr, t1 = nullptr;   // the pass on the handle's stream, first kernel to last (host source: the
+                                                 // copies it waits for in between included)
+        if (ms && (hipEventCreate(&t0) != hipSuccess || hipEventCreate(&t1) != hipSuccess || hipEventRecord(t0, stream) != hipSuccess))
+            ms = nullptr;
+        if (mem == RBL_MEM_DEVICE) {
+            rc = fn(X, (int64_t)0, n);
+        } else {
+            int64_t k = 0;
+            for (int64_t r0 = 0; r0 < n && rc == RBL_OK; r0 += chunk, ++k) {
+                const int64_t rows = n - r0 < chunk ? n - r0 : chunk;
+                const int b = (int)(k & 1);
+                const size_t bytes = ((size_t)(rows - 1) * (size_t)ldx + (size_t)ds) * esz;   // (the last row ends at column ds)
+                hipError_t e = hipSuccess;
+                if (k >= 2) e = hipStreamWaitEvent(copy_stream, formed[b], 0);   // staging buffer b has been consumed
+                if (e == hipSuccess)
+                    e = hipMemcpyAsync(Xd[b], (const unsigned char*)X + (size_t)r0 * (size_t)ldx * esz, bytes, hipMemcpyHostToDevice,
+                                       copy_stream);
+                if (e == hipSuccess) e = hipEventRecord(copied[b], copy_stream);
+                if (e == hipSuccess) e = hipStreamWaitEvent(stream, copied[b], 0);
+                if (e != hipSuccess) {
+                    rbl_set_error("set_data_from: upload failed: %s", hipGetErrorString(e));
+                    rc = RBL_ERR_HIP;
+                    break;
+                }
+                rc = fn((const void*)Xd[b], r0, rows);
+                if (rc == RBL_OK && hipEventRecord(formed[b], stream) != hipSuccess) rc = RBL_ERR_HIP;
+            }
+            if (hipStreamSynchronize(copy_stream) != hipSuccess && rc == RBL_OK) rc = RBL_ERR_HIP;
+        }
+        if (ms && hipEventRecord(t1, stream) != hipSuccess) ms = nullptr;
+        if (hipStreamSynchronize(stream) != hipSuccess && rc == RBL_OK) rc = RBL_ERR_HIP;
+        float el = 0.f;
+        if (ms && rc == RBL_OK && hipEventElapsedTime(&el, t0, t1) == hipSuccess) *ms = (double)el;
+        if (t0) (void)hipEventDestroy(t0);
+        if (t1) (void)hipEventDestroy(t1);
+        if (rc == RBL_ERR_HIP) {
+            const hipError_t e = hipGetLastError();
+            if (e != hipSuccess) rbl_set_error("set_data_from: %s", hipGetErrorString(e));
+        }
+        return rc;
+    }
+};
+
+static int set_data_from_impl(rbl_solver* h, const void* X, int dtype, int mem, int64_t ldx, const double* y, int scaling,
+                              int64_t ds) {
+    const int64_t n = h->n, d = h->d, ld = h->ld;
+    const size_t esz = src_esz(dtype);
+    {
+        std::vector<signed char> ys((size_t)n);
+        for (int64_t i = 0; i < n; ++i) ys[(size_t)i] = y[i] > 0 ? 1 : -1;
+        RBL_HIP(hipMemcpy(h->ysign, ys.data(), (size_t)n, hipMemcpyHostToDevice));
+    }
+    SrcPipe p;
+    p.stream = h->stream;
+    h->src_ms[0] = h->src_ms[1] = 0.0;
+    h->src_timed[0] = h->src_timed[1] = 0;
+    const int64_t SB = src_stat_rows();
+    int64_t chunk = n;
+    if (mem == RBL_MEM_HOST) {
+        long long cb = 64LL << 20;
+        if (const char* e = getenv("RBL_UPLOAD_CHUNK_BYTES")) {   // test hook: several chunks at small sizes
+            const long long v = atoll(e);
+            if (v > 0) cb = v;
+        }
+        chunk = (int64_t)(cb / (long long)(esz * (size_t)ldx));
+        if (scaling == RBL_SCALE_FIT) {   // whole row blocks of the statistics (the other modes: 64 MB)
+            chunk = chunk / SB * SB;
+            if (chunk < SB) chunk = SB;
+        }
+        if (chunk < 1) chunk = 1;
+        if (chunk > n) chunk = n;
+        const size_t xbytes = ((size_t)(n - 1) * (size_t)ldx + (size_t)ds) * esz;
+        RBL_TRY(p.open_host(X, xbytes, (size_t)chunk * (size_t)ldx * esz));
+    }
+    u64* ovf = nullptr;   // RBL_STORE_F16: {entries that do not fit, first of them} written by the forming kernel
+    if (h->storage == RBL_STORE_F16) {
+        const u64 ovf0[2] = {0ull, ~0ull};
+        RBL_TRY(p.tmp.alloc(&ovf, 2));
+        RBL_HIP(hipMemcpy(ovf, ovf0, sizeof(ovf0), hipMemcpyHostToDevice));
+    }
+    double *dmean = nullptr, *dinv = nullptr;
+    std::vector<double> fit_mean, fit_scale;   // RBL_SCALE_FIT: kept in the handle after the forming pass has succeeded
+    if (scaling == RBL_SCALE_FIT) {
+        const int64_t nb = (n + SB - 1) / SB;
+        double *slab = nullptr, *shift = nullptr, *sums = nullptr;
+        RBL_TRY(p.tmp.alloc(&slab, (size_t)nb * ld * 2));
+        RBL_TRY(p.tmp.alloc(&shift, (size_t)ld));
+        RBL_TRY(p.tmp.alloc(&sums, (size_t)ld * 2));
+        RBL_HIP(hipMemsetAsync(slab, 0, sizeof(double) * (size_t)nb * ld * 2, h->stream));
+        std::vector<double> sh((size_t)ld, 0.0), st((size_t)ld * 2, 0.0);
+        if (mem == RBL_MEM_HOST) {   // the shift: the column's first row, widened
+            for (int64_t j = 0; j < ds; ++j) sh[(size_t)j] = src_host_widen((const unsigned char*)X + (size_t)j * esz, dtype);
+            RBL_HIP(hipMemcpyAsync(shift, sh.data(), sizeof(double) * ld, hipMemcpyHostToDevice, h->stream));
+            RBL_HIP(hipStreamSynchronize(h->stream));
+        } else {
+            RBL_HIP(hipMemsetAsync(shift, 0, sizeof(double) * ld, h->stream));
+            RBL_TRY(launch_src_row(dtype, X, ds, shift, h->stream));
+        }
+        double* slab2 = slab + (size_t)nb * ld;
+        RBL_TRY(p.pass(X, mem, esz, ldx, ds, n, chunk, [&](const void* Xc, int64_t r0, int64_t rows) {
+            return launch_src_colstats(dtype, Xc, ldx, rows, ds, shift, slab, slab2, ld, r0 / SB, h->stream);
+        }, &h->src_ms[0]));
+        h->src_timed[0] = 1;
+        RBL_TRY(launch_src_colreduce(slab, nb, ld, sums, h->stream));
+        RBL_TRY(launch_src_colreduce(slab2, nb, ld, sums + ld, h->stream));
+        RBL_HIP(hipMemcpyAsync(st.data(), sums, sizeof(double) * ld * 2, hipMemcpyDeviceToHost, h->stream));
+        RBL_HIP(hipMemcpyAsync(sh.data(), shift, sizeof(double) * ld, hipMemcpyDeviceToHost, h->stream));
+        RBL_HIP(hipStreamSynchronize(h->stream));
+        std::vector<double> mean((size_t)d, 0.0), scale((size_t)d, 1.0);
+        const double nn = (double)n;
+        for (int64_t j = 0; j < ds; ++j) {
+            // x = shift + dl:  mean = shift + sum dl / n,  var = sum dl^2 / n - (sum dl / n)^2  (dl is of the size of the
+            // column's spread, so nothing cancels against the column's mean)
+            const double m1 = st[(size_t)j] / nn;
+            const double mu = sh[(size_t)j] + m1;
+            double var = st[(size_t)(ld + j)] / nn - m1 * m1;
+            if (!std::isfinite(mu) || !std::isfinite(var)) {
+                rbl_set_error("set_data_from: column %lld has a non-finite mean or variance (mean %g, variance %g) - the "
+                              "source holds inf / nan or overflows fp64 sums", (long long)j, mu, var);
+                return RBL_ERR_INVALID;
+            }
+            if (!(var > 0.0)) var = 1.0;   // a constant column is left at x - mean = 0
+            mean[(size_t)j] = mu;
+            scale[(size_t)j] = std::sqrt(var);
+        }
+        fit_mean.swap(mean);
+        fit_scale.swap(scale);
+    }
+    if (scaling != RBL_SCALE_NONE) {
+        const std::vector<double>& use_mean = scaling == RBL_SCALE_FIT ? fit_mean : h->sc_mean;
+        const std::vector<double>& use_scale = scaling == RBL_SCALE_FIT ? fit_scale : h->sc_scale;
+        std::vector<double> mi((size_t)ld * 2, 0.0);
+        for (int64_t j = 0; j < ld; ++j) mi[(size_t)(ld + j)] = 1.0;
+        for (int64_t j = 0; j < ds; ++j) {
+            mi[(size_t)j] = use_mean[(size_t)j];
+            mi[(size_t)(ld + j)] = 1.0 / use_scale[(size_t)j];
+        }
+        dmean = h->colstats + 2 * ld;
+        dinv = h->colstats + 3 * ld;
+        RBL_HIP(hipMemcpy(dmean, mi.data(), sizeof(double) * ld * 2, hipMemcpyHostToDevice));
+    }
+    RBL_TRY(p.pass(X, mem, esz, ldx, ds, n, chunk, [&](const void* Xc, int64_t r0, int64_t rows) {
+        return launch_form_src(dtype, h->storage, h->D, ld, r0, Xc, ldx, h->ysign + r0, rows, ds, d, dmean, dinv, h->num_cu,
+                               h->stream, ovf);
+    }, &h->src_ms[1]));
+    h->src_timed[1] = 1;
+    if (ovf) {   // read once, after the last chunk
+        u64 got[2] = {0ull, 0ull};
+        RBL_HIP(hipMemcpy(got, ovf, sizeof(got), hipMemcpyDeviceToHost));
+        if (got[0] > 0) {
+            const long long r = (long long)(got[1] / (u64)d), c = (long long)(got[1] % (u64)d);
+            double raw = 0.0;
+            const unsigned char* at = (const unsigned char*)X + ((size_t)r * (size_t)ldx + (size_t)c) * esz;
+            if (mem == RBL_MEM_HOST) {
+                raw = src_host_widen(at, dtype);
+            } else {
+                unsigned char tmp8[8] = {0};
+                RBL_HIP(hipMemcpy(tmp8, at, esz, hipMemcpyDeviceToHost));
+                raw = src_host_widen(tmp8, dtype);
+            }
+            rbl_set_error("fp16 storage: %llu finite entries do not fit float16 (|x| >= 65520), first at row %lld, column %lld "
+                          "(value %g) - standardise the columns or use storage f32",
+                          got[0], r, c, raw);
+            return RBL_ERR_INVALID;
+        }
+    }
+    if (scaling == RBL_SCALE_FIT) {   // the vectors are the handle's only once D stands: a failed call leaves the old ones
+        h->sc_mean.swap(fit_mean);
+        h->sc_scale.swap(fit_scale);
+        h->sc_set = true;
+    }
+    return RBL_OK;
+}
+
+// labels are +1 / -1, nothing else (`who`: the entry point's name in the message)
+static int check_labels(const char* who, const double* y, int64_t n) {
+    for (int64_t i = 0; i < n; ++i)
+        if (!(y[i] == 1.0 || y[i] == -1.0)) {
+            rbl_set_error("%s: labels must be +1/-1 (y[%lld] = %g)", who, (long long)i, y[i]);
+            return RBL_ERR_INVALID;
+        }
+    return RBL_OK;
+}
+
+extern "C" {
+
+int rbl_set_data_from(rbl_solver* h, const void* X, int dtype, int mem, int64_t ldx, const double* y, int scaling, int flags) {
+    RBL_ENTER(h);
+    RBL_NOT_BORROWER(h, "set_data_from");
+    if (dtype != RBL_DTYPE_F64 && dtype != RBL_DTYPE_F32 && dtype != RBL_DTYPE_F16) {
+        rbl_set_error("set_data_from: unknown dtype %d (RBL_DTYPE_F64 / F32 / F16)", dtype);
+        return RBL_ERR_INVALID;
+    }
+    if (mem != RBL_MEM_HOST && mem != RBL_MEM_DEVICE) {
+        rbl_set_error("set_data_from: unknown memory kind %d (RBL_MEM_HOST / RBL_MEM_DEVICE)", mem);
+        return RBL_ERR_INVALID;
+    }
+    if (scaling != RBL_SCALE_NONE && scaling != RBL_SCALE_FIT && scaling != RBL_SCALE_APPLY) {
+        rbl_set_error("set_data_from: unknown scaling %d (RBL_SCALE_NONE / FIT / APPLY)", scaling);
+        return RBL_ERR_INVALID;
+    }
+    if (flags & ~RBL_DATA_ONES_COLUMN) {
+        rbl_set_error("set_data_from: unknown flags 0x%x", (unsigned)flags);
+        return RBL_ERR_INVALID;
+    }
+    const int64_t n = h->n, d = h->d;
+    const int64_t ds = d - ((flags & RBL_DATA_ONES_COLUMN) ? 1 : 0);
+    if (!X || !y || ds < 1 || ldx < ds) {
+        rbl_set_error("set_data_from: bad arguments (X %s, y %s, ldx=%lld, source columns=%lld)", X ? "given" : "NULL",
+                      y ? "given" : "NULL", (long long)ldx, (long long)ds);
+        return RBL_ERR_INVALID;
+    }
+    if ((size_t)(uintptr_t)X % src_esz(dtype) != 0) {
+        rbl_set_error("set_data_from: X is not aligned to its element size (%zu bytes)", src_esz(dtype));
+        return RBL_ERR_INVALID;
+    }
+    RBL_TRY(check_labels("set_data_from", y, n));
+    if (scaling == RBL_SCALE_FIT && h->nt != h->n) {
+        rbl_set_error("set_data_from: RBL_SCALE_FIT on a row-sharded handle (n = %lld of n_total = %lld) - reduce the column "
+                      "sums over the ranks in the driver, hand every rank the same vectors (rbl_set_scaling) and use "
+                      "RBL_SCALE_APPLY", (long long)h->n, (long long)h->nt);
+        return RBL_ERR_INVALID;
+    }
+    if (scaling == RBL_SCALE_FIT && n < 1) {
+        rbl_set_error("set_data_from: RBL_SCALE_FIT needs at least one row");
+        return RBL_ERR_INVALID;
+    }
+    if (scaling == RBL_SCALE_APPLY && !h->sc_set) {
+        rbl_set_error("set_data_from: RBL_SCALE_APPLY without a scaling - call rbl_set_scaling first");
+        return RBL_ERR_STATE;
+    }
+    if (n > 0) {
+        if (mem == RBL_MEM_DEVICE)
+            RBL_TRY(src_check_device_range(X, ((size_t)(n - 1) * (size_t)ldx + (size_t)ds) * src_esz(dtype), h->cfg.device));
+        h->data_ready = false;   // a failed upload leaves the handle without data
+        RBL_TRY(set_data_from_impl(h, X, dtype, mem, ldx, y, scaling, ds));
+    }
+    h->data_ready = true;
+    h->gram_ready = h->gram_local_done = false;
+    h->v_valid = false;
+    return RBL_OK;
+}
+
+// the float64 host route is the typed one (include/rbl.h)
+int rbl_set_data(rbl_solver* h, const double* X, const double* y, int64_t ldx) {
+    return rbl_set_data_from(h, X, RBL_DTYPE_F64, RBL_MEM_HOST, ldx, y, RBL_SCALE_NONE, 0);
+}
+
+int rbl_set_scaling(rbl_solver* h, const double* mean, const double* scale) {
+    RBL_ENTER(h);
+    if (!mean && !scale) {
+        h->sc_mean.clear();
+        h->sc_scale.clear();
+        h->sc_set = false;
+        return RBL_OK;
+    }
+    if (!mean || !scale) {
+        rbl_set_error("set_scaling: mean and scale go together (both NULL clears them)");
+        return RBL_ERR_INVALID;
+    }
+    for (int64_t j = 0; j < h->d; ++j) {
+        if (!std::isfinite(mean[j]) || !std::isfinite(scale[j]) || !(scale[j] > 0.0)) {
+            rbl_set_error("set_scaling: column %lld: mean %g / scale %g (finite values, scale > 0)", (long long)j, mean[j], scale[j]);
+            return RBL_ERR_INVALID;
+        }
+    }
+    h->sc_mean.assign(mean, mean + h->d);
+    h->sc_scale.assign(scale, scale + h->d);
+    h->sc_set = true;
+    return RBL_OK;
+}
+
+int rbl_get_scaling(rbl_solver* h, double* mean, double* scale, int* is_set) {
+    RBL_ENTER_ITER(h);
+    for (int64_t j = 0; j < h->d; ++j) {
+        if (mean) mean[j] = h->sc_set ? h->sc_mean[(size_t)j] : 0.0;
+        if (scale) scale[j] = h->sc_set ? h->sc_scale[(size_t)j] : 1.0;
+    }
+    if (is_set) *is_set = h->sc_set ? 1 : 0;
+    return RBL_OK;
+}
+
+int rbl_synth_local(rbl_solver* h, uint64_t seed, double class_sep, double flip_y) {
+    RBL_ENTER(h);
+    RBL_NOT_BORROWER(h, "synth_local");
+    // positions of the 2 informative + 2 redundant columns, the 2x2 mixing matrix of the redundant ones, the four
+    // clusters' covariance matrices A_k (entries uniform in (-1, 1)) and which hypercube vertex each cluster sits on
+    // (a random permutation; cluster k belongs to class k % 2) - make_classification's geometry draws - from a small
+    // host-side LCG keyed by the seed (identical on every rank)
+    uint64_t st = seed * 6364136223846793005ull + 1442695040888963407ull;
+    auto next = [&]() {
+        st = st * 6364136223846793005ull + 1442695040888963407ull;
+        return (uint32_t)(st >> 33);
+    };
+    int special[4] = {-1, -1, -1, -1};
+    const int nspec = h->d >= 4 ? 4 : (int)h->d;
+    for (int k = 0; k < nspec; ++k) {
+        for (;;) {
+            int c = (int)(next() % (uint32_t)h->d);
+            bool dup = false;
+            for (int j = 0; j < k; ++j) dup |= special[j] == c;
+            if (!dup) {
+                special[k] = c;
+                break;
+            }
+        }
+    }
+    double mix[4];
+    for (int k = 0; k < 4; ++k) mix[k] = 2.0 * ((double)next() / 2147483648.0) - 1.0;
+    double A16[16];
+    for (int k = 0; k < 16; ++k) A16[k] = 2.0 * ((double)next() / 2147483648.0) - 1.0;
+    int vertex[4] = {0, 1, 2, 3};
+    for (int i = 3; i > 0; --i) {
+        const int j = (int)(next() % (uint32_t)(i + 1));
+        std::swap(vertex[i], vertex[j]);
+    }
+    if (h->storage == RBL_STORE_F16) {
+        // the statistics of the unrounded draws; the matrix itself is written by rbl_synth_finish, in one rounding
+        h->synth.pending = true;
+        h->synth.seed = seed;
+        h->synth.class_sep = class_sep;
+        h->synth.flip_y = flip_y;
+        for (int k = 0; k < 4; ++k) {
+            h->synth.special[k] = special[k];
+            h->synth.vertex[k] = vertex[k];
+            h->synth.mix[k] = mix[k];
+        }
+        for (int k = 0; k < 16; ++k) h->synth.A16[k] = A16[k];
+        h->data_ready = false;
+        RBL_TRY(launch_synth_stats(h->n, h->ld, h->d, h->off, seed, class_sep, flip_y, special, mix, A16, vertex, h->ysign, h->slab,
+                                   h->colstats, h->colstats + h->ld, h->num_cu, h->stream));
+        RBL_HIP(hipStreamSynchronize(h->stream));
+        return RBL_OK;
+    }
+    RBL_TRY(launch_synth(h->storage, h->D, h->n, h->ld, h->d, h->off, seed, class_sep, flip_y, special, mix, A16, vertex,
+                         h->ysign, h->stream));
+    // column sums / sums of squares of the local rows -> colstats[0 .. 2 ld)
+    RBL_TRY(launch_colstats(h->storage, h->D, h->n, h->ld, h->slab, h->colstats, h->colstats + h->ld, h->num_cu,
+                            h->stream));
+    RBL_HIP(hipStreamSynchronize(h->stream));
+    return RBL_OK;
+}
+
+int rbl_synth_finish(rbl_solver* h) {
+    RBL_ENTER(h);
+    RBL_NOT_BORROWER(h, "synth_finish");
+    // preprocessing.scale (load_data.py:115): (x - mean) / std with the population std
+    const int64_t ld = h->ld;
+    std::vector<double> st((size_t)ld * 4, 0.0);
+    RBL_HIP(hipMemcpy(st.data(), h->colstats, sizeof(double) * ld * 2, hipMemcpyDeviceToHost));
+    const double nt = (double)h->nt;
+    for (int64_t j = 0; j < ld; ++j) {
+        const double mean = st[j] / nt;
+        double var = st[ld + j] / nt - mean * mean;
+        if (!(var > 0.0)) var = 1.0;
+        st[2 * ld + j] = mean;
+        st[3 * ld + j] = 1.0 / std::sqrt(var);
+    }
+    RBL_HIP(hipMemcpy(h->colstats + 2 * ld, st.data() + 2 * ld, sizeof(double) * ld * 2, hipMemcpyHostToDevice));
+    if (h->storage == RBL_STORE_F16) {
+        if (!h->synth.pending) {
+            rbl_set_error("synth_finish: call rbl_synth_local first");
+            return RBL_ERR_STATE;
+        }
+        RBL_TRY(launch_synth_f16(h->D, h->n, ld, h->d, h->off, h->synth.seed, h->synth.class_sep, h->synth.flip_y, h->synth.special,
+                                 h->synth.mix, h->synth.A16, h->synth.vertex, h->colstats + 2 * ld, h->colstats + 3 * ld, h->stream));
+        h->synth.pending = false;
+    } else {
+        RBL_TRY(launch_standardize_negy(h->storage, h->D, h->n, ld, h->d, h->colstats + 2 * ld, h->colstats + 3 * ld,
+                                        h->ysign, h->stream));
+    }
+    RBL_HIP(hipStreamSynchronize(h->stream));
+    h->data_ready = true;
+    h->gram_ready = h->gram_local_done = false;
+    h->v_valid = false;
+    return RBL_OK;
+}
+
+int rbl_generate_synthetic(rbl_solver* h, uint64_t seed, double class_sep, double flip_y) {
+    RBL_ENTER(h);
+    RBL_NOT_BORROWER(h, "generate_synthetic");
+    if (h->nt != h->n) {
+        rbl_set_error("generate_synthetic: sharded problem - use rbl_synth_local, sum RBL_BUF_COLSTATS, rbl_synth_finish");
+        return RBL_ERR_STATE;
+    }
+    RBL_TRY(rbl_synth_local(h, seed, class_sep, flip_y));
+    return rbl_synth_finish(h);
+}
+
+int rbl_set_penalty(rbl_solver* h, const double* l1, const double* l2) {
+    RBL_ENTER(h);
+    if (h->iter > 0) {
+        rbl_set_error("set_penalty: the handle has iterated already (iter = %lld)", (long long)h->iter);
+        return RBL_ERR_STATE;
+    }
+    if (!l1 && !l2) {
+        rbl_set_error("set_penalty: l1 and l2 are both NULL");
+        return RBL_ERR_INVALID;
+    }
+    if (!h->cfg.objective_only && h->cfg.wstep == RBL_WSTEP_SMOOTH_L1) {
+        rbl_set_error("set_penalty: the smoothed-l1 w-step (sADMM) has no per-coordinate penalties");
+        return RBL_ERR_INVALID;
+    }
+    const int64_t d = h->d, ld = h->ld;
+    for (int k = 0; k < 2; ++k) {
+        const double* v = k ? l2 : l1;
+        for (int64_t j = 0; v && j < d; ++j)
+            if (!(v[j] >= 0.0) || !std::isfinite(v[j])) {
+                rbl_set_error("set_penalty: %s[%lld] = %g - penalties must be finite and >= 0", k ? "l2" : "l1", (long long)j,
+                              v[j]);
+                return RBL_ERR_INVALID;
+            }
+    }
+    std::vector<double> host((size_t)(2 * ld + 8), 0.0);
+    double l2max = 0.0;
+    for (int64_t j = 0; j < d; ++j) {
+        if (l1) host[(size_t)j] = l1[j];
+        if (l2) {
+            host[(size_t)(ld + j)] = l2[j];
+            if (l2[j] > l2max) l2max = l2[j];
+        }
+    }
+    if (!h->pen) RBL_TRY(h->mem.alloc(&h->pen, (size_t)(2 * ld + 8)));
+    RBL_HIP(hipMemcpyAsync(h->pen, host.data(), sizeof(double) * host.size(), hipMemcpyHostToDevice, h->stream));
+    RBL_HIP(hipStreamSynchronize(h->stream));
+    h->pen_host.assign((size_t)(2 * d), 0.0);
+    for (int64_t j = 0; j < d; ++j) {
+        h->pen_host[(size_t)j] = host[(size_t)j];
+        h->pen_host[(size_t)(d + j)] = host[(size_t)(ld + j)];
+    }
+    h->ww.pen_l1 = h->pen;
+    h->ww.pen_l2 = h->pen + ld;
+    h->ww.pen_l2max = l2max;
+    return RBL_OK;
+}
+
+int rbl_get_penalty(rbl_solver* h, double* l1, double* l2, int* is_set) {
+    RBL_ENTER_ITER(h);
+    const int64_t d = h->d;
+    if (is_set) *is_set = h->pen ? 1 : 0;
+    for (int64_t j = 0; j < d; ++j) {
+        if (l1) l1[j] = h->pen ? h->pen_host[(size_t)j] : 0.0;
+        if (l2) l2[j] = h->pen ? h->pen_host[(size_t)(d + j)] : 0.0;
+    }
+    return RBL_OK;
+}
+
+int rbl_set_labels(rbl_solver* h, const double* y) {
+    RBL_ENTER(h);
+    if (!h->borrower) {
+        rbl_set_error("set_labels: only a handle that borrows its data (rbl_create_shared) can carry labels of its own");
+        return RBL_ERR_STATE;
+    }
+    if (h->iter > 0) {
+        rbl_set_error("set_labels: the handle has iterated already (iter = %lld)", (long long)h->iter);
+        return RBL_ERR_STATE;
+    }
+    if (h->in_group) {
+        rbl_set_error("set_labels: the handle is a member of a group - destroy the group first");
+        return RBL_ERR_STATE;
+    }
+    if (h->nt != h->n) {
+        rbl_set_error("set_labels: row-sharded handle (n=%lld of %lld) - the distributed z-steps carry no labels of their own",
+                      (long long)h->n, (long long)h->nt);
+        return RBL_ERR_INVALID;
+    }
+    if (!y) {
+        rbl_set_error("set_labels: y is NULL");
+        return RBL_ERR_INVALID;
+    }
+    const int64_t n = h->n;
+    RBL_TRY(check_labels("set_labels", y, n));
+    RBL_HIP(hipStreamSynchronize(h->stream));
+    std::vector<signed char> yo((size_t)n), r((size_t)n), ys((size_t)n);
+    RBL_HIP(hipMemcpy(yo.data(), h->ysign, (size_t)n, hipMemcpyDeviceToHost));
+    bool differs = false;
+    for (int64_t i = 0; i < n; ++i) {
+        ys[(size_t)i] = y[i] > 0 ? 1 : -1;
+        r[(size_t)i] = (signed char)(ys[(size_t)i] * yo[(size_t)i]);
+        differs = differs || r[(size_t)i] < 0;
+    }
+    if (!differs && !h->rs) return RBL_OK;   // the owner's labels on an ordinary borrower: nothing changes
+    // z and lambda move from the sign convention they are stored in to the new one (both start as constants)
+    std::vector<double> zh, lh;
+    if (h->z) {
+        zh.resize((size_t)n);
+        lh.resize((size_t)n);
+        RBL_HIP(hipMemcpy(zh.data(), h->z, sizeof(double) * n, hipMemcpyDeviceToHost));
+        RBL_HIP(hipMemcpy(lh.data(), h->lam, sizeof(double) * n, hipMemcpyDeviceToHost));
+        if (h->rs) {
+            flip_rows(h, zh.data());
+            flip_rows(h, lh.data());
+        }
+    }
+    if (!differs) {   // the owner's labels: an ordinary borrower
+        if (h->rs) h->mem.release(h->rs);
+        h->rs = nullptr;
+        h->rs_host.clear();
+        h->ys_host.clear();
+    } else {
+        if (!h->rs) RBL_TRY(h->mem.alloc(&h->rs, (size_t)n));
+        RBL_HIP(hipMemcpy(h->rs, r.data(), (size_t)n, hipMemcpyHostToDevice));
+        h->rs_host.swap(r);
+        h->ys_host.swap(ys);
+    }
+    if (h->z) {
+        RBL_TRY(upload_rows(h, h->z, zh.data()));
+        RBL_TRY(upload_rows(h, h->lam, lh.data()));
+    }
+    if (!h->cfg.objective_only) {
+        // the sign is not part of the single-sweep erm pass' in-pass prox: such a handle runs the two-pass iteration
+        const char* nf = getenv("RBL_NO_FUSE");
+        h->fused_ok = !h->rs && !h->sorted_path && !(nf && nf[0] == '1') && sweep_erm_supported(h->storage, h->ld);
+    }
+    h->z_ready = h->p_valid = h->p_pending = h->pred_valid = false;
+    h->keys_ready = h->s32.m_ready = false;
+    return RBL_OK;
+}
+
+// One-vs-rest decision on the rows of `data`: cls[i] = argmax_j x_i . w_j (ties: the lowest j).  D = -y X, so the
+// scores are -y_i (D w_j)_i: the multi-column V product of the groups (sweep_multi.hip), ceil(k / k_per_pass) passes
+// over D, each followed by the row-wise comparison against the best score so far.
+int rbl_decide_multi(rbl_solver* h, int k, const double* W, int32_t* cls) {
+    RBL_ENTER(h);
+    if (!h->data_ready) {
+        rbl_set_error("decide_multi: no data");
+        return RBL_ERR_STATE;
+    }
+    if (k < 1 || k > 64 || !W || !cls) {
+        rbl_set_error("decide_multi: 1..64 columns (got %d), W and cls not NULL", k);
+        return RBL_ERR_INVALID;
+    }
+    const int64_t n = h->n, ld = h->ld, d = h->d;
+    if (n <= 0) return RBL_OK;
+    hipStream_t s = h->stream;
+    const bool multi = sweep_multi_supported(h->storage, ld);
+    const int kpp = multi ? sweep_multi_k(h->storage, ld) : 1;
+    DevArena mem;   // scratch of this call, freed on return (after the stream wait)
+    double *dw = nullptr, *dv = nullptr, *best = nullptr;
+    int* dcls = nullptr;
+    std::vector<double> wp((size_t)ld * k, 0.0);
+    for (int j = 0; j < k; ++j)
+        for (int64_t i = 0; i < d; ++i) wp[(size_t)j * ld + i] = W[(size_t)j * d + i];
+    RBL_TRY(mem.alloc(&dw, wp.size()));
+    RBL_TRY(mem.alloc(&dv, (size_t)n * kpp));
+    RBL_TRY(mem.alloc(&best, (size_t)n));
+    RBL_TRY(mem.alloc(&dcls, (size_t)n));
+    RBL_HIP(hipMemcpy(dw, wp.data(), sizeof(double) * wp.size(), hipMemcpyHostToDevice));
+    int rc = RBL_OK;
+    for (int j0 = 0; j0 < k && rc == RBL_OK; j0 += kpp) {
+        const int kk = std::min(kpp, k - j0);
+        if (!multi) {   // outside the multi-column kernels' widths: the single-column pass per column
+            rc = launch_gemv(h->storage, h->D, n, ld, dw + (size_t)j0 * ld, dv, h->num_cu, s);
+        } else {
+            const double* w[RBL_MULTI_KMAX];
+            double* v[RBL_MULTI_KMAX];
+            for (int j = 0; j < kk; ++j) {
+                w[j] = dw + (size_t)(j0 + j) * ld;
+                v[j] = dv + (size_t)j * n;
+            }
+            rc = launch_sweep_v_multi(h->storage, h->D, n, ld, kk, w, nullptr, nullptr, v, nullptr, nullptr, nullptr, h->num_cu, s);
+        }
+        if (rc == RBL_OK) rc = launch_decide_rows(n, kk, j0, dv, h->ysign, best, dcls, s);
+    }
+    if (rc == RBL_OK && (hipMemcpyAsync(cls, dcls, sizeof(int32_t) * n, hipMemcpyDeviceToHost, s) != hipSuccess)) rc = RBL_ERR_HIP;
+    if (hipStreamSynchronize(s) != hipSuccess && rc == RBL_OK) rc = RBL_ERR_HIP;   // before the scratch goes
+    if (rc == RBL_ERR_HIP) rbl_set_error("decide_multi: %s", hipGetErrorString(hipGetLastError()));
+    return rc;
+}
+
+int rbl_get_labels(rbl_solver* h, double* y_out) {
+    RBL_ENTER(h);
+    if (h->rs) {   // labels of its own (rbl_set_labels)
+        for (int64_t i = 0; i < h->n; ++i) y_out[i] = (double)h->ys_host[(size_t)i];
+        return RBL_OK;
+    }
+    std::vector<signed char> t((size_t)h->n);
+    RBL_HIP(hipMemcpy(t.data(), h->ysign, (size_t)h->n, hipMemcpyDeviceToHost));
+    for (int64_t i = 0; i < h->n; ++i) y_out[i] = (double)t[i];
+    return RBL_OK;
+}
+
+int rbl_gram_local(rbl_solver* h) {
+    RBL_ENTER(h);
+    RBL_NOT_BORROWER(h, "gram_local");
+    if (!h->data_ready || h->cfg.objective_only) {
+        rbl_set_error("gram: no data (or objective-only handle)");
+        return RBL_ERR_STATE;
+    }
+    RBL_TRY(launch_gram(h->storage, h->D, h->n, h->ld, h->d, h->slab, h->G, h->num_cu, h->stream));
+    RBL_HIP(hipStreamSynchronize(h->stream));
+    h->gram_local_done = true;
+    h->ww.eig_ok = false;
+    return RBL_OK;
+}
+
+int rbl_gram_finish(rbl_solver* h) {
+    RBL_ENTER(h);
+    RBL_NOT_BORROWER(h, "gram_finish");
+    if (!h->gram_local_done) {
+        rbl_set_error("gram_finish before gram_local");
+        return RBL_ERR_STATE;
+    }
+    double lam = 0.0;
+    RBL_TRY(launch_power_iteration(h->G, h->ld, h->ww.yk, h->ww.Gy, h->ww.scal, 100, &lam, h->stream));
+    h->L = 1.02 * lam;
+    if (!(h->L > 0.0)) h->L = 1.0;
+    // l2 w-step: RBL_RIDGE_EIG=1 replaces the warm-started CG by a one-time eigendecomposition of G (eig.hip).
+    // Opt-in: it makes an iteration 0.13 ms shorter at d = 1000 (14 CG iterations -> 5 small launches) but the
+    // Jacobi sweeps cost 0.8 s of setup there - 6000 iterations to break even, and a solve runs a few hundred
+    h->ww.eig_ok = false;
+    static const bool ridge_eig = [] {
+        const char* e = getenv("RBL_RIDGE_EIG");
+        return e && e[0] == '1';
+    }();
+    if (h->cfg.wstep == RBL_WSTEP_L2 && h->ld <= 2048 && ridge_eig) {
+        const size_t nn = (size_t)h->ld * (size_t)h->ld;
+        if (!h->ww.eig_Vt) {
+            double *Vt = nullptr, *V = nullptr, *lambda = nullptr;
+            RBL_TRY(h->shared->alloc(&Vt, nn));   // derived from G alone: shared with the borrowers
+            RBL_TRY(h->shared->alloc(&V, nn));
+            RBL_TRY(h->shared->alloc(&lambda, (size_t)h->ld));
+            h->ww.eig_V = V;
+            h->ww.eig_lambda = lambda;
+            h->ww.eig_Vt = Vt;   // set last: it says the basis buffers are there
+        }
+        int rc = RBL_OK, sweeps = 0;
+        {
+            DevArena tmp;   // Jacobi scratch, freed after the stream wait
+            double* Bt = nullptr;
+            unsigned long long* off = nullptr;
+            RBL_TRY(tmp.alloc(&Bt, nn));
+            RBL_TRY(tmp.alloc(&off, 1));
+            rc = launch_eig_jacobi(h->G, h->ld, h->d, Bt, h->ww.eig_Vt, h->ww.eig_V, h->ww.eig_lambda, off, h->stream, &sweeps);
+            (void)hipStreamSynchronize(h->stream);
+        }
+        RBL_TRY(rc);
+        h->ww.eig_ok = sweeps > 0;
+        h->eig_sweeps = sweeps;
+    }
+    h->gram_ready = true;
+    return RBL_OK;
+}
+
+int rbl_get_D(rbl_solver* h, double* out) {
+    RBL_ENTER(h);
+    if (!h->data_ready) {
+        rbl_set_error("get_D: no data");
+        return RBL_ERR_STATE;
+    }
+    const int64_t n = h->n, d = h->d;
+    int64_t chunk = (64LL << 20) / (8 * d);
+    if (chunk < 1) chunk = 1;
+    DevArena mem;   // the conversion buffer, freed on return
+    double* tmp = nullptr;
+    RBL_TRY(mem.alloc(&tmp, (size_t)chunk * d));
+    for (int64_t r0 = 0; r0 < n; r0 += chunk) {
+        const int64_t rows = n - r0 < chunk ? n - r0 : chunk;
+        RBL_TRY(launch_D_to_f64(h->storage, (const char*)h->D + (size_t)r0 * h->ld * h->esz, h->ld, rows, d, tmp, h->stream));
+        if (hipMemcpyAsync(out + r0 * d, tmp, sizeof(double) * rows * d, hipMemcpyDeviceToHost, h->stream) != hipSuccess ||
+            hipStreamSynchronize(h->stream) != hipSuccess)
+            return RBL_ERR_HIP;
+    }
+    if (h->rs)   // -y_k * X = r * (-y_owner * X)
+        for (int64_t i = 0; i < n; ++i)
+            if (h->rs_host[(size_t)i] < 0)
+                for (int64_t j = 0; j < d; ++j) out[i * d + j] = -out[i * d + j];
+    return RBL_OK;
+}
+
+}  // extern "C"

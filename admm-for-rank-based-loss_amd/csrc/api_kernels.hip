@@ -1,0 +1,472 @@
+// api_kernels.hip - the kernel-level entry points (rbl_k_*) of the parity tests: host buffers in, host buffers out.
+#include "api_internal.h"
+
+// =================================================== kernel-level entry points (host buffers)
+// They run on the same workspace allocators as the solver handle (alloc_sort, alloc_pav, alloc_prefix, alloc_wstep).
+namespace {
+struct Scratch {   // the buffers and the stream of one call
+    DevArena mem;
+    hipStream_t s = nullptr;
+    ~Scratch() {
+        if (s) (void)hipStreamDestroy(s);
+    }
+    template <typename T>
+    int upload(T** p, const T* host, size_t count) {
+        RBL_TRY(mem.alloc(p, count));
+        if (count) RBL_HIP(hipMemcpy(*p, host, count * sizeof(T), hipMemcpyHostToDevice));
+        return RBL_OK;
+    }
+};
+
+int scratch_begin(Scratch& sc, int* num_cu) {
+    RBL_TRY(check_device(nullptr));
+    RBL_HIP(hipStreamCreateWithFlags(&sc.s, hipStreamNonBlocking));
+    if (num_cu) {
+        int dev = 0;
+        hipDeviceProp_t prop;
+        RBL_HIP(hipGetDevice(&dev));
+        RBL_HIP(hipGetDeviceProperties(&prop, dev));
+        *num_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
+    }
+    return RBL_OK;
+}
+
+// D (host fp64 n x d) -> device storage with ld padding
+int upload_matrix(Scratch& sc, int storage, int64_t n, int64_t d, const double* D, void** Dd, int64_t* ld_out) {
+    const int64_t ld = rbl_storage_ld(storage, d);
+    const size_t esz = rbl_storage_esz(storage);
+    std::vector<unsigned char> host((size_t)n * ld * esz, 0);
+    for (int64_t r = 0; r < n; ++r)
+        for (int64_t j = 0; j < d; ++j) {
+            if (storage == RBL_STORE_F16) ((unsigned short*)host.data())[r * ld + j] = f64_to_f16_bits(D[r * d + j]);
+            else if (storage == RBL_STORE_F32) ((float*)host.data())[r * ld + j] = (float)D[r * d + j];
+            else ((double*)host.data())[r * ld + j] = D[r * d + j];
+        }
+    RBL_TRY(sc.upload((unsigned char**)Dd, host.data(), host.size()));
+    *ld_out = ld;
+    return RBL_OK;
+}
+}  // namespace
+
+extern "C" {
+
+// the kernel-level entry points check the loss id before any device work
+static int k_check_loss(const char* who, int loss) {
+    if (rbl_check_loss(loss) == RBL_OK) return RBL_OK;
+    rbl_set_error("%s: unknown loss id %d", who, loss);
+    return RBL_ERR_INVALID;
+}
+
+int rbl_k_prox(int loss, int64_t n, const double* sigma, double rho, const double* m, double* out) {
+    RBL_TRY(k_check_loss("rbl_k_prox", loss));
+    Scratch sc;
+    RBL_TRY(scratch_begin(sc, nullptr));
+    if (n <= 0) return RBL_OK;
+    double *ds = nullptr, *dm = nullptr, *dout = nullptr;
+    RBL_TRY(sc.upload(&ds, sigma, (size_t)n));
+    RBL_TRY(sc.upload(&dm, m, (size_t)n));
+    RBL_TRY(sc.mem.alloc(&dout, (size_t)n));
+    RBL_TRY(launch_prox(loss, n, ds, rho, dm, dout, sc.s));
+    RBL_HIP(hipMemcpyAsync(out, dout, sizeof(double) * n, hipMemcpyDeviceToHost, sc.s));
+    RBL_HIP(hipStreamSynchronize(sc.s));
+    return RBL_OK;
+}
+
+int rbl_k_sort(int64_t n, const double* keys, double* sorted_keys, uint32_t* perm) {
+    Scratch sc;
+    RBL_TRY(scratch_begin(sc, nullptr));
+    if (n <= 0) return RBL_OK;
+    double *dk = nullptr, *ms = nullptr;
+    RBL_TRY(sc.upload(&dk, keys, (size_t)n));
+    SortWorkspace sw{};
+    RBL_TRY(alloc_sort(sc.mem, sw, n, true, sc.s));
+    RBL_TRY(sc.mem.alloc(&ms, (size_t)n));
+    RBL_TRY(launch_keys_from_m(n, dk, sw.keys[0], sw.vals[0], sc.s));
+    RBL_TRY(launch_radix_sort(sw, n, true, sc.s));
+    RBL_TRY(launch_unflip_keys(n, sw.keys[0], ms, sc.s));
+    if (sorted_keys) RBL_HIP(hipMemcpyAsync(sorted_keys, ms, sizeof(double) * n, hipMemcpyDeviceToHost, sc.s));
+    if (perm) RBL_HIP(hipMemcpyAsync(perm, sw.vals[0], sizeof(u32) * n, hipMemcpyDeviceToHost, sc.s));
+    RBL_HIP(hipStreamSynchronize(sc.s));
+    return RBL_OK;
+}
+
+// The sort of the z-step with 32-bit keys: the launches of z_step_sorted's use32 branch, in its order, on buffers laid
+// out as a handle's (rbl_phase_m: launch_make_m_range with v = m, lambda = 0, rho = 1 - m - 0/1 has the input's bits).
+// The fix-up compares m numerically: -0.0 and +0.0 tie and keep their row order, where rbl_k_sort orders the bit
+// patterns (every -0.0 before every +0.0).  *flag = 1: a run of more than S32_MAX_RUN equal keys; m_sorted / ids are
+// then meaningless (zb_resolve redoes such a z-step with 64-bit keys).
+int rbl_k_sort32(int64_t n, const double* m, uint32_t idx_off, double* m_sorted, uint32_t* ids, int* flag) {
+    Scratch sc;
+    RBL_TRY(scratch_begin(sc, nullptr));
+    if (flag) *flag = 0;
+    if (n <= 0) return RBL_OK;
+    if (!m || n + (int64_t)idx_off > (1LL << 32)) {
+        rbl_set_error("rbl_k_sort32: m is NULL or n + idx_off exceeds 2^32 (row ids are 32 bits)");
+        return RBL_ERR_INVALID;
+    }
+    double *dv = nullptr, *dlam = nullptr, *dm = nullptr, *ms = nullptr;
+    u64* mm = nullptr;
+    int* dflag = nullptr;
+    RBL_TRY(sc.upload(&dv, m, (size_t)n));
+    RBL_TRY(sc.mem.alloc(&dlam, (size_t)n));
+    RBL_TRY(sc.mem.alloc(&dm, (size_t)n));
+    RBL_TRY(sc.mem.alloc(&ms, (size_t)n));
+    RBL_TRY(sc.mem.alloc(&mm, (size_t)s32_range_words()));
+    RBL_TRY(sc.mem.alloc(&dflag, 1));
+    RBL_HIP(hipMemsetAsync(dlam, 0, sizeof(double) * n, sc.s));
+    SortWorkspace sw{};
+    RBL_TRY(alloc_sort(sc.mem, sw, n, true, sc.s));
+    u32* k32 = reinterpret_cast<u32*>(sw.keys[0]);
+    RBL_TRY(launch_make_m_range(n, 1.0, dv, dlam, dm, mm, sc.s, nullptr));
+    RBL_TRY(launch_keys32(n, dm, mm, k32, sw.vals[0], idx_off, sc.s));
+    RBL_TRY(launch_radix_sort32(sw, n, sc.s));
+    RBL_TRY(launch_sort32_fix(n, k32, sw.vals[0], dm, idx_off, ms, sw.vals[1], dflag, sc.s));
+    if (m_sorted) RBL_HIP(hipMemcpyAsync(m_sorted, ms, sizeof(double) * n, hipMemcpyDeviceToHost, sc.s));
+    if (ids) RBL_HIP(hipMemcpyAsync(ids, sw.vals[1], sizeof(u32) * n, hipMemcpyDeviceToHost, sc.s));
+    int f = 0;
+    RBL_HIP(hipMemcpyAsync(&f, dflag, sizeof(int), hipMemcpyDeviceToHost, sc.s));
+    RBL_HIP(hipStreamSynchronize(sc.s));
+    if (flag) *flag = f;
+    return RBL_OK;
+}
+
+// ncalls successive PAV solves on ONE workspace (m_sorted: ncalls x n): the hints of the upper seams, the barrier parity
+// and the EHRM speculated branch carry over from one call to the next as they do between the z-steps of a solve.
+static int k_pav_common(int loss, int64_t n, const double* sigma_a, const double* sigma_b, int ehrm, double B,
+                        double rho, int ncalls, const double* m_sorted, int branch_in, int upper, double* out,
+                        int64_t* n_merges, int* branch_out, uint32_t* counters_out) {
+    Scratch sc;
+    RBL_TRY(scratch_begin(sc, nullptr));
+    if (n <= 0 || ncalls <= 0) return RBL_OK;
+    double *sa = nullptr, *sb = nullptr;
+    RBL_TRY(sc.upload(&sa, sigma_a, (size_t)n));
+    if (ehrm) RBL_TRY(sc.upload(&sb, sigma_b, (size_t)n));
+    else sb = sa;
+    PavWorkspace pw{};   // the sorted m goes to pw.ms, its prefix sums to pw.pm
+    RBL_TRY(alloc_pav(sc.mem, pw, n, sc.s));
+    PrefixBufs pa, pb;
+    RBL_TRY(alloc_prefix(sc.mem, pa, n));
+    pb = pa;
+    if (ehrm) RBL_TRY(alloc_prefix(sc.mem, pb, n));
+    PavExtras ex = pw.ex;
+    {
+        int dev = 0, cus = 0;
+        RBL_HIP(hipGetDevice(&dev));
+        RBL_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+        ex.num_cu = cus;
+    }
+    ex.B = B;
+    ex.upper = upper;
+    {
+        const char* e = getenv("RBL_EHRM_SPEC");   // 0 / 1: the speculated branch; -1: round 2's separate pass
+        if (e && (atoi(e) == 0 || atoi(e) == 1)) ex.spec = atoi(e);
+        // a forced branch (the tests pin both) and RBL_EHRM_SPEC=-1 go through the separate test; the automatic choice
+        // through the speculation inside the bottom kernel
+        if (!ehrm || branch_in >= 0 || (e && atoi(e) == -1)) ex.fpart = nullptr;
+    }
+    RBL_TRY(launch_prefix(sa, n, pa, sc.s));
+    if (ehrm) RBL_TRY(launch_prefix(sb, n, pb, sc.s));
+    // identity permutation scatter applies the EHRM clip
+    std::vector<u32> idh((size_t)n);
+    for (int64_t i = 0; i < n; ++i) idh[(size_t)i] = (u32)i;
+    u32* idd = nullptr;
+    double* zz = nullptr;
+    RBL_TRY(sc.upload(&idd, idh.data(), (size_t)n));
+    RBL_TRY(sc.mem.alloc(&zz, (size_t)n));
+    for (int call = 0; call < ncalls; ++call) {
+        RBL_HIP(hipMemcpyAsync(pw.ms, m_sorted + (size_t)call * n, sizeof(double) * n, hipMemcpyHostToDevice, sc.s));
+        RBL_TRY(launch_prefix(pw.ms, n, pw.pm, sc.s));
+        if (ehrm && !ex.fpart) RBL_TRY(launch_ehrm_branch(n, sa, sb, B, rho, pw.ms, pw.partials, pw.branch, branch_in, sc.s));
+        RBL_TRY(launch_pav_tree(loss, n, rho, pw.ms, sa, sb, pw.u, pa.view(), pb.view(), pw.pm.view(), ehrm ? pw.branch : nullptr,
+                                pw.recs, pw.counters, sc.s, nullptr, nullptr, &ex));
+        RBL_TRY(launch_scatter_z(n, pw.u, idd, ehrm ? pw.branch : nullptr, B, ehrm, rho, nullptr, zz, nullptr, 0, n, sc.s));
+        RBL_HIP(hipMemcpyAsync(out + (size_t)call * n, zz, sizeof(double) * n, hipMemcpyDeviceToHost, sc.s));
+        unsigned mc4[4] = {0, 0, 0, 0};
+        int br = -1;
+        RBL_HIP(hipMemcpyAsync(mc4, pw.counters, sizeof(mc4), hipMemcpyDeviceToHost, sc.s));
+        if (ehrm) RBL_HIP(hipMemcpyAsync(&br, pw.branch, sizeof(int), hipMemcpyDeviceToHost, sc.s));
+        RBL_HIP(hipStreamSynchronize(sc.s));
+        if (counters_out)
+            for (int j = 0; j < 4; ++j) counters_out[4 * call + j] = mc4[j];
+        if (mc4[3] != 0) {
+            rbl_set_error("PAV: the upper-level kernel did not complete (a wait gave up or its fill list overflowed)");
+            return RBL_ERR_HIP;
+        }
+        if (n_merges) n_merges[call] = mc4[0];
+        if (branch_out) branch_out[call] = br;
+        if (ehrm && br >= 0) ex.spec = br;   // the next call speculates the branch this one took (rbl_phase_finish)
+    }
+    return RBL_OK;
+}
+
+int rbl_k_pav(int loss, int64_t n, const double* sigma, double rho, const double* m_sorted, double* out,
+              int64_t* n_merges) {
+    RBL_TRY(k_check_loss("rbl_k_pav", loss));
+    return k_pav_common(loss, n, sigma, sigma, 0, 0.0, rho, 1, m_sorted, -1, PAV_UPPER_DEFAULT, out, n_merges, nullptr,
+                        nullptr);
+}
+
+int rbl_k_pav_ehrm(int64_t n, const double* sigma_a, const double* sigma_b, double B, double rho,
+                   const double* m_sorted, int branch, double* out, int* branch_out) {
+    return k_pav_common(RBL_LOSS_BCE, n, sigma_a, sigma_b, 1, B, rho, 1, m_sorted, branch, PAV_UPPER_DEFAULT, out, nullptr,
+                        branch_out, nullptr);
+}
+
+int rbl_k_pav_seq(int loss, int64_t n, const double* sigma_a, const double* sigma_b, double B, double rho, int ncalls,
+                  const double* m_sorted, int upper, double* out, int* branch_out, uint32_t* counters) {
+    RBL_TRY(k_check_loss("rbl_k_pav_seq", loss));
+    if (upper != RBL_PAV_UPPER_PERSIST && upper != RBL_PAV_UPPER_TWO_LAUNCH) {
+        rbl_set_error("rbl_k_pav_seq: upper must be RBL_PAV_UPPER_PERSIST or RBL_PAV_UPPER_TWO_LAUNCH, got %d", upper);
+        return RBL_ERR_INVALID;
+    }
+    const int ehrm = sigma_b != nullptr;
+    if (ehrm && loss != RBL_LOSS_BCE) {
+        rbl_set_error("rbl_k_pav_seq: the EHRM z-step is defined for the BCE loss only");
+        return RBL_ERR_INVALID;
+    }
+    return k_pav_common(loss, n, sigma_a, ehrm ? sigma_b : sigma_a, ehrm, B, rho, ncalls, m_sorted, -1,
+                        upper == RBL_PAV_UPPER_PERSIST ? PAV_UPPER_PERSIST : PAV_UPPER_TWO_LAUNCH, out, nullptr, branch_out,
+                        counters);
+}
+
+int rbl_k_gemv(int storage, int64_t n, int64_t d, const double* D, const double* w, double* v) {
+    Scratch sc;
+    int num_cu = 256;
+    RBL_TRY(scratch_begin(sc, &num_cu));
+    if (n <= 0) return RBL_OK;
+    void* Dd = nullptr;
+    int64_t ld = 0;
+    RBL_TRY(upload_matrix(sc, storage, n, d, D, &Dd, &ld));
+    std::vector<double> wp((size_t)ld, 0.0);
+    for (int64_t j = 0; j < d; ++j) wp[(size_t)j] = w[j];
+    double *dw = nullptr, *dv = nullptr;
+    RBL_TRY(sc.upload(&dw, wp.data(), (size_t)ld));
+    RBL_TRY(sc.mem.alloc(&dv, (size_t)n));
+    RBL_TRY(launch_gemv(storage, Dd, n, ld, dw, dv, num_cu, sc.s));
+    RBL_HIP(hipMemcpyAsync(v, dv, sizeof(double) * n, hipMemcpyDeviceToHost, sc.s));
+    RBL_HIP(hipStreamSynchronize(sc.s));
+    return RBL_OK;
+}
+
+int rbl_k_gemvt(int storage, int64_t n, int64_t d, const double* D, const double* c, double* q) {
+    Scratch sc;
+    int num_cu = 256;
+    RBL_TRY(scratch_begin(sc, &num_cu));
+    void* Dd = nullptr;
+    int64_t ld = 0;
+    RBL_TRY(upload_matrix(sc, storage, n > 0 ? n : 0, d, D, &Dd, &ld));
+    double *dc = nullptr, *slab = nullptr, *dq = nullptr;
+    RBL_TRY(sc.upload(&dc, c, (size_t)n));
+    RBL_TRY(sc.mem.alloc(&slab, (size_t)gemvt_slab_rows(num_cu) * ld));
+    RBL_TRY(sc.mem.alloc(&dq, (size_t)ld));
+    RBL_TRY(launch_gemvt(storage, Dd, n, ld, dc, slab, dq, num_cu, sc.s));
+    RBL_HIP(hipMemcpyAsync(q, dq, sizeof(double) * d, hipMemcpyDeviceToHost, sc.s));
+    RBL_HIP(hipStreamSynchronize(sc.s));
+    return RBL_OK;
+}
+
+int rbl_k_gemv_multi(int storage, int64_t n, int64_t d, int k, const double* D, const double* W, double* V) {
+    if (k < 1 || k > 64 || d <= 0) {
+        rbl_set_error("rbl_k_gemv_multi: 1..64 columns, d > 0");
+        return RBL_ERR_INVALID;
+    }
+    Scratch sc;
+    int num_cu = 256;
+    RBL_TRY(scratch_begin(sc, &num_cu));
+    if (n <= 0) return RBL_OK;
+    void* Dd = nullptr;
+    int64_t ld = 0;
+    RBL_TRY(upload_matrix(sc, storage, n, d, D, &Dd, &ld));
+    std::vector<double> wp((size_t)ld * k, 0.0);
+    for (int j = 0; j < k; ++j)
+        for (int64_t i = 0; i < d; ++i) wp[(size_t)j * ld + i] = W[(size_t)j * d + i];
+    double *dw = nullptr, *dv = nullptr;
+    RBL_TRY(sc.upload(&dw, wp.data(), wp.size()));
+    RBL_TRY(sc.mem.alloc(&dv, (size_t)n * k));
+    const bool multi = sweep_multi_supported(storage, ld);
+    const int kpp = multi ? sweep_multi_k(storage, ld) : 1;
+    for (int j0 = 0; j0 < k; j0 += kpp) {
+        const int kk = std::min(kpp, k - j0);
+        if (!multi) {   // outside the multi-column kernels' widths: the single-column pass per column
+            RBL_TRY(launch_gemv(storage, Dd, n, ld, dw + (size_t)j0 * ld, dv + (size_t)j0 * n, num_cu, sc.s));
+            continue;
+        }
+        const double* w[RBL_MULTI_KMAX];
+        double* v[RBL_MULTI_KMAX];
+        for (int j = 0; j < kk; ++j) {
+            w[j] = dw + (size_t)(j0 + j) * ld;
+            v[j] = dv + (size_t)(j0 + j) * n;
+        }
+        RBL_TRY(launch_sweep_v_multi(storage, Dd, n, ld, kk, w, nullptr, nullptr, v, nullptr, nullptr, nullptr, num_cu, sc.s));
+    }
+    RBL_HIP(hipMemcpyAsync(V, dv, sizeof(double) * n * k, hipMemcpyDeviceToHost, sc.s));
+    RBL_HIP(hipStreamSynchronize(sc.s));
+    return RBL_OK;
+}
+
+int rbl_k_gemvt_multi(int storage, int64_t n, int64_t d, int k, const double* D, const double* Cm, double* Q) {
+    if (k < 1 || k > 64 || d <= 0) {
+        rbl_set_error("rbl_k_gemvt_multi: 1..64 columns, d > 0");
+        return RBL_ERR_INVALID;
+    }
+    Scratch sc;
+    int num_cu = 256;
+    RBL_TRY(scratch_begin(sc, &num_cu));
+    void* Dd = nullptr;
+    int64_t ld = 0;
+    RBL_TRY(upload_matrix(sc, storage, n > 0 ? n : 0, d, D, &Dd, &ld));
+    double *dc = nullptr, *slab = nullptr, *dq = nullptr;
+    RBL_TRY(sc.upload(&dc, Cm, (size_t)(n > 0 ? n : 0) * k));
+    const bool multi = n > 0 && sweep_multi_supported(storage, ld);
+    const int kpp = multi ? sweep_multi_k(storage, ld) : 1;
+    RBL_TRY(sc.mem.alloc(&slab, multi ? sweep_multi_slab_doubles(ld, num_cu) : (size_t)gemvt_slab_rows(num_cu) * ld));
+    RBL_TRY(sc.mem.alloc(&dq, (size_t)ld * k));
+    for (int j0 = 0; j0 < k; j0 += kpp) {
+        const int kk = std::min(kpp, k - j0);
+        if (!multi) {
+            RBL_TRY(launch_gemvt(storage, Dd, n, ld, dc + (size_t)j0 * (n > 0 ? n : 0), slab, dq + (size_t)j0 * ld, num_cu, sc.s));
+            continue;
+        }
+        const double* c[RBL_MULTI_KMAX];
+        double* q[RBL_MULTI_KMAX];
+        for (int j = 0; j < kk; ++j) {
+            c[j] = dc + (size_t)(j0 + j) * n;
+            q[j] = dq + (size_t)(j0 + j) * ld;
+        }
+        RBL_TRY(launch_sweep_q_multi(storage, Dd, n, ld, kk, c, slab, q, num_cu, sc.s));
+    }
+    for (int j = 0; j < k; ++j)
+        RBL_HIP(hipMemcpyAsync(Q + (size_t)j * d, dq + (size_t)j * ld, sizeof(double) * d, hipMemcpyDeviceToHost, sc.s));
+    RBL_HIP(hipStreamSynchronize(sc.s));
+    return RBL_OK;
+}
+
+int rbl_k_gram(int storage, int64_t n, int64_t d, const double* D, double* G) {
+    Scratch sc;
+    int num_cu = 256;
+    RBL_TRY(scratch_begin(sc, &num_cu));
+    void* Dd = nullptr;
+    int64_t ld = 0;
+    RBL_TRY(upload_matrix(sc, storage, n, d, D, &Dd, &ld));
+    double *slab = nullptr, *dG = nullptr;
+    RBL_TRY(sc.mem.alloc((unsigned char**)&slab, gram_slab_bytes(ld, num_cu, n > 0 ? n : 1)));
+    RBL_TRY(sc.mem.alloc(&dG, (size_t)ld * ld));
+    RBL_TRY(launch_gram(storage, Dd, n, ld, d, slab, dG, num_cu, sc.s));
+    std::vector<double> hG((size_t)ld * ld);
+    RBL_HIP(hipMemcpyAsync(hG.data(), dG, sizeof(double) * ld * ld, hipMemcpyDeviceToHost, sc.s));
+    RBL_HIP(hipStreamSynchronize(sc.s));
+    for (int64_t i = 0; i < d; ++i)
+        for (int64_t j = 0; j < d; ++j) G[i * d + j] = hG[(size_t)(i * ld + j)];
+    return RBL_OK;
+}
+
+int rbl_k_wstep(int wstep, int64_t d, const double* G, const double* q, double rho, double reg, double smooth_t,
+                const double* w0, double tol, double* w_out, int* iters) {
+    Scratch sc;
+    RBL_TRY(scratch_begin(sc, nullptr));
+    const int64_t ld = round_up(d, 4);
+    std::vector<double> hG((size_t)ld * ld, 0.0), hq((size_t)ld, 0.0), hw((size_t)ld, 0.0);
+    for (int64_t i = 0; i < d; ++i) {
+        for (int64_t j = 0; j < d; ++j) hG[(size_t)(i * ld + j)] = G[i * d + j];
+        hq[(size_t)i] = q[i];
+        hw[(size_t)i] = w0 ? w0[i] : 0.0;
+    }
+    double *dG = nullptr, *dq = nullptr, *dw = nullptr;
+    RBL_TRY(sc.upload(&dG, hG.data(), hG.size()));
+    RBL_TRY(sc.upload(&dq, hq.data(), hq.size()));
+    RBL_TRY(sc.upload(&dw, hw.data(), hw.size()));
+    WstepWorkspace ww{};
+    RBL_TRY(alloc_wstep(sc.mem, ww, ld, sc.s));
+    double lam = 0.0;
+    RBL_TRY(launch_power_iteration(dG, ld, ww.yk, ww.Gy, ww.scal, 100, &lam, sc.s));
+    double L = 1.02 * lam;
+    if (!(L > 0.0)) L = 1.0;
+    int it = 0;
+    RBL_TRY(run_wstep(wstep, dG, ld, dq, rho, reg, smooth_t, L, tol > 0.0 ? tol : 1e-13, 100000, dw, ww, &it, sc.s));
+    RBL_HIP(hipMemcpyAsync(w_out, dw, sizeof(double) * d, hipMemcpyDeviceToHost, sc.s));
+    RBL_HIP(hipStreamSynchronize(sc.s));
+    if (iters) *iters = it;
+    return RBL_OK;
+}
+
+int rbl_k_wstep_pen(int64_t d, const double* G, const double* q, double rho, const double* l1, const double* l2,
+                    const double* w0, double tol, double* w_out, int* iters, int* form) {
+    if (d <= 0 || !G || !q || !w_out || (!l1 && !l2) || !(rho > 0.0)) {
+        rbl_set_error("k_wstep_pen: bad argument (d > 0, G, q, w_out, rho > 0 and l1 or l2 are needed)");
+        return RBL_ERR_INVALID;
+    }
+    bool any_l1 = false;
+    double l2max = 0.0;
+    for (int k = 0; k < 2; ++k) {
+        const double* v = k ? l2 : l1;
+        for (int64_t j = 0; v && j < d; ++j) {
+            if (!(v[j] >= 0.0) || !std::isfinite(v[j])) {
+                rbl_set_error("k_wstep_pen: %s[%lld] = %g - penalties must be finite and >= 0", k ? "l2" : "l1", (long long)j,
+                              v[j]);
+                return RBL_ERR_INVALID;
+            }
+            if (!k && v[j] > 0.0) any_l1 = true;
+            if (k && v[j] > l2max) l2max = v[j];
+        }
+    }
+    Scratch sc;
+    RBL_TRY(scratch_begin(sc, nullptr));
+    const int64_t ld = round_up(d, 4);
+    std::vector<double> hG((size_t)ld * ld, 0.0), hq((size_t)ld, 0.0), hw((size_t)ld, 0.0), hp((size_t)(2 * ld), 0.0);
+    for (int64_t i = 0; i < d; ++i) {
+        for (int64_t j = 0; j < d; ++j) hG[(size_t)(i * ld + j)] = G[i * d + j];
+        hq[(size_t)i] = q[i];
+        hw[(size_t)i] = w0 ? w0[i] : 0.0;
+        hp[(size_t)i] = l1 ? l1[i] : 0.0;
+        hp[(size_t)(ld + i)] = l2 ? l2[i] : 0.0;
+    }
+    double *dG = nullptr, *dq = nullptr, *dw = nullptr, *dp = nullptr;
+    RBL_TRY(sc.upload(&dG, hG.data(), hG.size()));
+    RBL_TRY(sc.upload(&dq, hq.data(), hq.size()));
+    RBL_TRY(sc.upload(&dw, hw.data(), hw.size()));
+    RBL_TRY(sc.upload(&dp, hp.data(), hp.size()));
+    WstepWorkspace ww{};
+    RBL_TRY(alloc_wstep(sc.mem, ww, ld, sc.s));
+    ww.pen_l1 = dp;
+    ww.pen_l2 = dp + ld;
+    ww.pen_l2max = l2max;
+    double lam = 0.0;
+    RBL_TRY(launch_power_iteration(dG, ld, ww.yk, ww.Gy, ww.scal, 100, &lam, sc.s));
+    double L = 1.02 * lam;
+    if (!(L > 0.0)) L = 1.0;
+    int it = 0;
+    RBL_TRY(run_wstep(any_l1 ? RBL_WSTEP_L1 : RBL_WSTEP_L2, dG, ld, dq, rho, 0.0, 1.0, L, tol > 0.0 ? tol : 1e-13, 100000, dw,
+                      ww, &it, sc.s));
+    RBL_HIP(hipMemcpyAsync(w_out, dw, sizeof(double) * d, hipMemcpyDeviceToHost, sc.s));
+    RBL_HIP(hipStreamSynchronize(sc.s));
+    if (iters) *iters = it;
+    if (form) *form = ww.form;
+    return RBL_OK;
+}
+
+int rbl_k_weights(int weight_function, int64_t n, const double* args, int n_args, double* alphas, double* betas) {
+    Scratch sc;
+    RBL_TRY(scratch_begin(sc, nullptr));
+    if (weight_function < RBL_W_ERM || weight_function > RBL_W_EHRM) {
+        rbl_set_error("Unrecognized framework! Options: ['erm','extremile','superquantile','esrm','aorr','aorr_dc','ehrm']");
+        return RBL_ERR_INVALID;
+    }
+    if (weight_function != RBL_W_ERM && weight_function != RBL_W_EHRM) {
+        const int need = (weight_function == RBL_W_AORR || weight_function == RBL_W_AORR_DC) ? 2 : 1;
+        if (!args || n_args < need) {
+            rbl_set_error("args for framework is None!");
+            return RBL_ERR_INVALID;
+        }
+    }
+    double a2[2] = {args && n_args > 0 ? args[0] : 0.0, args && n_args > 1 ? args[1] : 0.0};
+    double *da = nullptr, *db = nullptr;
+    RBL_TRY(sc.mem.alloc(&da, (size_t)n));
+    RBL_TRY(sc.mem.alloc(&db, (size_t)n));
+    RBL_TRY(launch_weights(weight_function, n, a2, da, db, sc.s));
+    if (alphas) RBL_HIP(hipMemcpyAsync(alphas, da, sizeof(double) * n, hipMemcpyDeviceToHost, sc.s));
+    if (betas) RBL_HIP(hipMemcpyAsync(betas, db, sizeof(double) * n, hipMemcpyDeviceToHost, sc.s));
+    RBL_HIP(hipStreamSynchronize(sc.s));
+    return RBL_OK;
+}
+
+}  // extern "C"

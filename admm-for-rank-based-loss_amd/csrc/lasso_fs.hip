@@ -136,7 +136,7 @@ __global__ __launch_bounds__(FS_THREADS) void k_lasso_fs(const double* __restric
     const int tid = threadIdx.x;
     const int nd = (int)d;
     // kappa = reg / (2 rho) with rho read on the device when the launch was enqueued before the
-    // host knew it (the w-step of the next iteration, api.hip: rbl_phase_finish)
+    // host knew it (the w-step of the next iteration, api_iter.hip: rbl_phase_finish)
     const double kappa = PEN ? 0.0 : (rho_dev ? reg / (2.0 * rho_dev[0]) : kappa_val);
     const double rho_inv = PEN ? 1.0 / (rho_dev ? rho_dev[0] : kappa_val) : 0.0;
     // per-coordinate threshold and diagonal shift (the scalar instance folds both to its constants)

@@ -118,7 +118,7 @@ constexpr int RBL_WAVE = 64;
 // The kernels read halves as bit patterns out of 16-byte packets and widen them half -> float -> double (both exact);
 // rbl_half only types the pointers.  Every write of a half goes through f64_to_f16_bits: ONE round-to-nearest-even from
 // the fp64 value (integer arithmetic, the same on host and device - NumPy's float64 -> float16 conversion bit for bit),
-// subnormals kept, overflow to +-inf (the callers count those: rbl_set_data rejects them).
+// subnormals kept, overflow to +-inf (the callers count those: rbl_set_data_from rejects them).
 typedef _Float16 rbl_half;
 __host__ __device__ inline unsigned short f64_to_f16_bits(double x) {
     const u64 b = __builtin_bit_cast(u64, x);
@@ -179,10 +179,6 @@ int launch_gemv(int storage, const void* D, int64_t n, int64_t ld, const double*
 int gemvt_slab_rows(int num_cu);
 int launch_gemvt(int storage, const void* D, int64_t n, int64_t ld, const double* c, double* slab,
                  double* q, int num_cu, hipStream_t s, hipEvent_t main_done = nullptr);
-// D[r0+i][j] = -y[i] * X[i][j] for a chunk of rows already on the device (fp64 staging)
-// ovf (RBL_STORE_F16, else NULL): [0] += finite entries that rounded to +-inf, [1] = min of their row * d + column
-int launch_form_D(int storage, void* D, int64_t ld, int64_t row0, const double* Xdev, int64_t ldx,
-                  const double* ydev, int64_t rows, int64_t d, hipStream_t s, u64* ovf = nullptr);
 int launch_D_to_f64(int storage, const void* D, int64_t ld, int64_t n, int64_t d, double* out,
                     hipStream_t s);
 // column sums / sums of squares (slab-reduced, deterministic) and in-place standardisation
@@ -193,6 +189,7 @@ int launch_standardize_negy(int storage, void* D, int64_t n, int64_t ld, int64_t
 // typed sources (rbl_set_data_from): X of element type dtype (RBL_DTYPE_*) already on the device, ds source columns.
 // D[row0 + r][j] = round(-y_r x), x = widen(X[r][j]) or, with mean / inv given (device, ld doubles), (widen - mean[j]) *
 // inv[j]; columns ds .. d - 1 are -y_r (the column of ones), the pad zeros.  ysign: the signs of rows row0 .. row0 + rows.
+// ovf (RBL_STORE_F16, else NULL): [0] += finite entries that rounded to +-inf, [1] = min of their row * d + column
 int launch_form_src(int dtype, int storage, void* D, int64_t ld, int64_t row0, const void* X, int64_t ldx,
                     const signed char* ysign, int64_t rows, int64_t ds, int64_t d, const double* mean, const double* inv,
                     int num_cu, hipStream_t s, u64* ovf);

@@ -435,36 +435,6 @@ int gemvt_blocks(int num_cu, long long n) {
 
 // ------------------------------------------------------------------- forming / reading D
 template <typename T>
-__global__ void k_form_D(T* __restrict__ D, long long ld, long long row0, const double* __restrict__ X,
-                         long long ldx, const double* __restrict__ y, long long rows, long long d) {
-    long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= rows * ld) return;
-    long long r = i / ld, j = i - r * ld;
-    double val = (j < d) ? -y[r] * X[r * ldx + j] : 0.0;  // algorithms.py:23  D = -y * X
-    D[(row0 + r) * ld + j] = (T)val;
-}
-// fp16 storage: one thread per pair of columns (a 4-byte store), one rounding from the fp64 product; finite entries that
-// round to +-inf are counted and the first one (smallest row * d + column) is kept for the error message
-__global__ void k_form_D_f16(unsigned* __restrict__ D, long long ld, long long row0, const double* __restrict__ X,
-                             long long ldx, const double* __restrict__ y, long long rows, long long d, u64* ovf) {
-    const long long hl = ld / 2;
-    long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= rows * hl) return;
-    const long long r = i / hl, j = (i - r * hl) * 2;
-    unsigned short h[2];
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-        const double val = (j + k < d) ? -y[r] * X[r * ldx + j + k] : 0.0;
-        h[k] = f64_to_f16_bits(val);
-        if (f16_bits_inf(h[k]) && val - val == 0.0) {   // finite in, infinite out
-            atomicAdd(&ovf[0], 1ull);
-            atomicMin(&ovf[1], (u64)((row0 + r) * d + j + k));
-        }
-    }
-    D[(row0 + r) * hl + j / 2] = (unsigned)h[0] | ((unsigned)h[1] << 16);
-}
-
-template <typename T>
 __global__ void k_D_to_f64(const T* __restrict__ D, long long ld, long long n, long long d,
                            double* __restrict__ out) {
     long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -794,24 +764,6 @@ int launch_colstats(int storage, const void* D, int64_t n, int64_t ld, double* s
         RBL_TRY((gemvt_T<double, true>((const double*)D, n, ld, nullptr, slab, slab2, nb, s)));
     hipLaunchKernelGGL(k_colreduce, dim3((unsigned)((ld + 63) / 64)), dim3(1024), 0, s, slab, nb, (long long)ld, sum);
     hipLaunchKernelGGL(k_colreduce, dim3((unsigned)((ld + 63) / 64)), dim3(1024), 0, s, slab2, nb, (long long)ld, sumsq);
-    RBL_HIP(hipGetLastError());
-    return RBL_OK;
-}
-
-int launch_form_D(int storage, void* D, int64_t ld, int64_t row0, const double* Xdev, int64_t ldx,
-                  const double* ydev, int64_t rows, int64_t d, hipStream_t s, u64* ovf) {
-    long long total = rows * ld;
-    if (total <= 0) return RBL_OK;
-    unsigned grid = (unsigned)((total + 255) / 256);
-    if (storage == RBL_STORE_F16)
-        hipLaunchKernelGGL(k_form_D_f16, dim3((unsigned)((total / 2 + 255) / 256)), dim3(256), 0, s, (unsigned*)D, (long long)ld,
-                           (long long)row0, Xdev, (long long)ldx, ydev, (long long)rows, (long long)d, ovf);
-    else if (storage == RBL_STORE_F32)
-        hipLaunchKernelGGL(k_form_D<float>, dim3(grid), dim3(256), 0, s, (float*)D, (long long)ld, (long long)row0,
-                           Xdev, (long long)ldx, ydev, (long long)rows, (long long)d);
-    else
-        hipLaunchKernelGGL(k_form_D<double>, dim3(grid), dim3(256), 0, s, (double*)D, (long long)ld,
-                           (long long)row0, Xdev, (long long)ldx, ydev, (long long)rows, (long long)d);
     RBL_HIP(hipGetLastError());
     return RBL_OK;
 }

@@ -17,7 +17,7 @@
 // rho_{k+1} depends on the GLOBAL primal residual of iteration k; it is predicted in d-space
 // before the pass (k_predict_rho: ||z - D w||^2 = ||z||^2 - 2 (D^T z)'w + w'Gw) and verified
 // after it with the exact residual this kernel accumulates; on a misprediction the host
-// simply recomputes the z-step / q with the unfused kernels (api.hip).
+// simply recomputes the z-step / q with the unfused kernels (api_iter.hip).
 // Algorithmic bytes = n*ld*sizeof(T): half of the unfused iteration's.
 #include "rbl_internal.h"
 #ifndef RBL_D_AUX

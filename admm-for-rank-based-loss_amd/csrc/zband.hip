@@ -22,7 +22,7 @@
 // All sums are accumulated per thread in a fixed element order and reduced in a fixed order: bit-reproducible.
 // Whatever the fast path cannot certify (keys tied across a band edge, a block that swallows a whole band or stays
 // on one side of a single-rank band, an unresolved bracket) is REPORTED through a pinned status word; the caller
-// (api.hip: zb_resolve) then runs the sort + merge-tree PAV for that iteration.  6M rows, superquantile: ~0.33 ms
+// (api_iter.hip: zb_resolve) then runs the sort + merge-tree PAV for that iteration.  6M rows, superquantile: ~0.33 ms
 // of kernel time (0.05 of it the pass behind k_zb_canon) instead of ~1.1 ms for sort + PAV + unsort.  The same select gives the logged objective sum_k sigma_k loss(v_(k))
 // without sorting v (k_zb_risk).  CPU restatement of the structure and of the certification rules: oracle/zband.py.
 #include "rbl_internal.h"

@@ -54,7 +54,7 @@ enum { RBL_WSTEP_L1 = 1, RBL_WSTEP_L2 = 2, RBL_WSTEP_SMOOTH_L1 = 3 };
 
 /* element type D = -y*X is stored in (accumulation is always float64).  RBL_STORE_F16 is IEEE binary16: rows are padded
  * to a multiple of 8 elements (f32 / f64: of 4), the upload rounds to nearest even once, and a finite entry that does not
- * fit the format (|x| >= 65520) is rejected by rbl_set_data (RBL_ERR_INVALID), never clipped. */
+ * fit the format (|x| >= 65520) is rejected by rbl_set_data / rbl_set_data_from (RBL_ERR_INVALID), never clipped. */
 enum { RBL_STORE_F32 = 0, RBL_STORE_F64 = 1, RBL_STORE_F16 = 2 };
 
 /* Constructor arguments of Optimizer.__init__ (src/optim/algorithms.py:20-75). */
@@ -171,16 +171,19 @@ int  rbl_get_penalty(rbl_solver* h, double* l1, double* l2, int* is_set);
 int  rbl_set_stream(rbl_solver* h, void* hip_stream);
 
 /* ---- data: D = -y * X (algorithms.py:23), G = D^T D (algorithms.py:24) ---------- */
-/* X: n x d host rows with leading dimension ldx, y: n labels (+-1).  RBL_STORE_F16: a finite entry that rounds to
- * +-inf fails the call with RBL_ERR_INVALID (the message counts them and names the first one); the handle is then
- * without data. */
+/* X: n x d host rows of doubles with leading dimension ldx, y: n labels (+-1).  By definition
+ *     rbl_set_data(h, X, y, ldx) = rbl_set_data_from(h, X, RBL_DTYPE_F64, RBL_MEM_HOST, ldx, y, RBL_SCALE_NONE, 0)
+ * (below): the same checks, messages ("set_data_from: ..."), 64 MB chunks (RBL_UPLOAD_CHUNK_BYTES applies), and
+ * rbl_kernel_time(RBL_KERNEL_SRC_FORM) reports its forming pass.  Of a strided source (ldx > d) nothing is read beyond
+ * column d of the last row.  RBL_STORE_F16: a finite entry that rounds to +-inf fails the call with RBL_ERR_INVALID (the
+ * message counts them and names the first one); the handle is then without data. */
 int  rbl_set_data(rbl_solver* h, const double* X, const double* y, int64_t ldx);
 /* X in the type it has and from where it lives.  X: n rows of d columns (d - 1 with RBL_DATA_ONES_COLUMN: column d - 1 of
  * D is then -y * 1, never scaled, reported as mean 0 / scale 1), row stride ldx ELEMENTS, naturally aligned, element type
  * dtype, in host memory or in memory of the handle's device (checked: anything else is RBL_ERR_INVALID, with a message).
  * y: n host doubles, +-1.  X is read, never modified and never adopted: the caller may free it when the call returns.
- *   RBL_SCALE_NONE   D = round_to_storage(-y * widen(X)): bit for bit the D of rbl_set_data on the float64 widening
- *                    (widening is exact), including the rejection of entries that do not fit RBL_STORE_F16.
+ *   RBL_SCALE_NONE   D = round_to_storage(-y * widen(X)): the product is formed in fp64 (widening is exact, y = +-1) and
+ *                    rounded once, to nearest even; entries that do not fit RBL_STORE_F16 are rejected (see above).
  *   RBL_SCALE_FIT    per column the mean and the population standard deviation (ddof 0; zero variance: 1) of the widened
  *                    source are formed on the device in fp64, then D = round_to_storage(-y * ((widen(x) - mean) * (1.0 /
  *                    scale))): one rounding into the storage type.  The vectors stay in the handle (rbl_get_scaling) once
@@ -431,7 +434,8 @@ int  rbl_info(rbl_solver* h, int64_t* ld, int* num_cu, double* lipschitz);
 /* ---- measurement ------------------------------------------------------------------ */
 /* accumulated HIP-event time of the two n x d sweep kernels since the last reset */
 enum { RBL_KERNEL_GEMV = 0, RBL_KERNEL_GEMVT = 1, RBL_KERNEL_SWEEP_ERM = 2 };
-/* the two passes of the last rbl_set_data_from on the handle's stream (not accumulated; launches = 1 if the pass ran):
+/* the two passes of the last rbl_set_data_from (or rbl_set_data: the forming pass) on the handle's stream (not
+ * accumulated; launches = 1 if the pass ran):
  * the column statistics of RBL_SCALE_FIT and the forming of D.  Device source: the kernels alone; host source: the
  * pipelined pass, the copies it waits for included. */
 enum { RBL_KERNEL_SRC_STATS = 3, RBL_KERNEL_SRC_FORM = 4 };

@@ -1,5 +1,5 @@
 """NumPy restatement of the on-device synthetic data generator (csrc/synth.hip + the column
-statistics / standardisation of csrc/sweep.hip and api.hip: rbl_synth_local / rbl_synth_finish).
+statistics / standardisation of csrc/sweep.hip and api_data.hip: rbl_synth_local / rbl_synth_finish).
 
 The generator reproduces the STATISTICS of the reference's synthetic branch
 (src/util/load_data.py:101-116: sklearn make_classification defaults - 2 informative + 2 redundant
@@ -48,7 +48,7 @@ def special_columns(seed, d):
     """positions of the 2 informative + 2 redundant columns, the 2x2 mixing matrix, the four clusters' 2x2
     covariance matrices A_k (row-major) and the hypercube vertex of each cluster (bit 0 / bit 1 = sign of the first /
     second informative coordinate; cluster k belongs to class k % 2, as in make_classification): the host-side LCG
-    of api.hip: rbl_synth_local (identical on every rank)"""
+    of api_data.hip: rbl_synth_local (identical on every rank)"""
     m64 = (1 << 64) - 1
     st = (seed * 6364136223846793005 + 1442695040888963407) & m64
 

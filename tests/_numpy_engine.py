@@ -263,7 +263,7 @@ class NumpyEngine:
 
 
 class FusedNumpyEngine(NumpyEngine):
-    """erm only: the exchange protocol of librbl's single-sweep iteration (csrc/api.hip: rbl_phase_* with
+    """erm only: the exchange protocol of librbl's single-sweep iteration (csrc/api_iter.hip: rbl_phase_* with
     fused_ok) restated in NumPy, so that the CPU gloo tests reach dist.py's ``pending_reduce`` branches:
 
     * ONE exchange buffer ``[q (d) | D^T lambda seed (d) | ||z||^2 | primal^2 | sum loss]``; ``buf("q")`` is the

@@ -1,8 +1,9 @@
 """GPU checks of the typed data path (include/rbl.h: rbl_set_data_from, rbl_set_scaling, rbl_get_scaling).
 
 * RBL_SCALE_NONE: for every source type {f64, f32, f16} x storage {f64, f32, fp16} x memory {host, device} x row stride
-  {d, d + 3}, rbl_get_D is bit for bit what rbl_set_data gives for the float64 widening of the same values; the fp16
-  overflow refusal reads as on the float64 host route.
+  {d, d + 3}, rbl_get_D is bit for bit the NumPy formula (tests/scaling_ref.py: form_D without a scaling) on the float64
+  widening of the same values; so is rbl_set_data (one chunk, five chunks, a row stride beyond d); the fp16 overflow
+  refusal reads as on the float64 host route.
 * RBL_SCALE_FIT: mean / scale against the two-pass NumPy restatement (tests/scaling_ref.py); D bit-identical to the NumPy
   formula given the returned vectors; everything bit-identical between a host source, a device source and a host
   source uploaded in five chunks.  RBL_SCALE_APPLY, RBL_DATA_ONES_COLUMN, the refusals.
@@ -64,7 +65,8 @@ def _wide(X, pad, dev, torch):
 @pytest.mark.parametrize("shape", [(1, 1), (3, 5), (257, 130), (1000, 1001), (4099, 264)])
 def test_none_is_bit_identical_to_set_data(R, torch, shape, storage):
     """one packet, a padded tail, rows that are 16-byte aligned (264, all types) and rows that are not (1001 in fp32 /
-    fp16; 130 in fp16), more rows than one block"""
+    fp16; 130 in fp16), more rows than one block.  The reference is the NumPy formula: rbl_set_data is this very path
+    with a float64 host source (its own tests are below)"""
     n, d = shape
     rng = np.random.default_rng(n * 1000 + d)
     X64 = rng.standard_normal((n, d))
@@ -72,8 +74,7 @@ def test_none_is_bit_identical_to_set_data(R, torch, shape, storage):
     s = R.Solver(n, d, "erm", reg=0.1, storage=storage, objective_only=True)
     for name, dt in SRC.items():
         X = X64.astype(dt)
-        s.set_data_f64(X.astype(np.float64), y)          # the reference: rbl_set_data of the widened values
-        ref = s.get_D()
+        ref = scaling_ref.form_D(X.astype(np.float64), y, None, None, storage)    # the widened values, rounded once
         for dev in (False, True):
             for pad in (0, 3):
                 src = _wide(X, pad, dev, torch) if pad else (torch.from_numpy(X).cuda() if dev else X)
@@ -98,11 +99,72 @@ def test_none_on_a_slice_with_a_misaligned_base(R, torch, name):
     y = _labels(rng, n)
     for storage in ("f64", "f32", "fp16"):
         s = R.Solver(n, d, "erm", reg=0.1, storage=storage, objective_only=True)
-        s.set_data_f64(V.cpu().numpy().astype(np.float64), y)
-        ref = s.get_D()
+        ref = scaling_ref.form_D(V.cpu().numpy().astype(np.float64), y, None, None, storage)
         s.set_data(V, y)
         assert _same(s.get_D(), ref), storage
         s.close()
+
+
+# ------------------------------------------------------------------------- rbl_set_data, the float64 host route
+F64_SHAPES = [(1, 1), (3, 5), (257, 130), (1000, 1001)]
+
+
+@pytest.mark.parametrize("storage", ["f64", "f32", "fp16"])
+@pytest.mark.parametrize("shape", F64_SHAPES)
+def test_set_data_f64_is_the_numpy_formula(R, shape, storage):
+    """one packet, a padded tail, rows that are no multiple of 16 bytes (1001 doubles: the element-wise loads), more
+    rows than one block"""
+    n, d = shape
+    rng = np.random.default_rng(n * 1000 + d + 1)
+    X = rng.standard_normal((n, d))
+    y = _labels(rng, n)
+    s = R.Solver(n, d, "erm", reg=0.1, storage=storage, objective_only=True)
+    s.set_data(np.zeros((n, d)), y)
+    s.set_data_f64(X, y)
+    assert _same(s.get_D(), scaling_ref.form_D(X, y, None, None, storage))
+    s.close()
+
+
+@pytest.mark.parametrize("storage", ["f64", "f32", "fp16"])
+def test_set_data_f64_in_five_chunks(R, storage, monkeypatch):
+    """1024 rows a chunk at 4099 x 264: both staging buffers are used twice, the copy of chunk 2 waits for chunk 0's
+    kernel"""
+    n, d = 4099, 264
+    rng = np.random.default_rng(13)
+    X = rng.standard_normal((n, d))
+    y = _labels(rng, n)
+    out = []
+    for chunk_bytes in (None, 1024 * 264 * 8):
+        monkeypatch.delenv("RBL_UPLOAD_CHUNK_BYTES", raising=False)
+        if chunk_bytes:
+            monkeypatch.setenv("RBL_UPLOAD_CHUNK_BYTES", str(chunk_bytes))
+        s = R.Solver(n, d, "erm", reg=0.1, storage=storage, objective_only=True)
+        s.set_data(np.zeros((n, d)), y)
+        s.set_data_f64(X, y)
+        out.append(s.get_D())
+        s.close()
+    monkeypatch.delenv("RBL_UPLOAD_CHUNK_BYTES", raising=False)
+    assert _same(out[1], out[0])
+    assert _same(out[1], scaling_ref.form_D(X, y, None, None, storage))
+
+
+@pytest.mark.parametrize("storage", ["f64", "f32", "fp16"])
+def test_rbl_set_data_with_a_row_stride_beyond_d(R, storage):
+    """ldx = d + 3: the rows of the [:, :d] view of a C-contiguous 257 x 133 array (7.0 beyond column 130); the view's
+    last row ends three elements before the array does, and nothing beyond column d is read into D"""
+    L = R._lib
+    n, d, pad = 257, 130, 3
+    rng = np.random.default_rng(17)
+    W = np.full((n, d + pad), 7.0)
+    W[:, :d] = rng.standard_normal((n, d))
+    V = W[:, :d]
+    assert W.flags["C_CONTIGUOUS"] and V.strides == ((d + pad) * 8, 8)
+    y = _labels(rng, n)
+    s = R.Solver(n, d, "erm", reg=0.1, storage=storage, objective_only=True)
+    s.set_data(np.zeros((n, d)), y)
+    L.check(s.lib.rbl_set_data(s._h, C.c_void_p(V.ctypes.data), L.ptr(y), d + pad))
+    assert _same(s.get_D(), scaling_ref.form_D(V, y, None, None, storage))
+    s.close()
 
 
 def test_fp16_overflow_reads_as_on_the_float64_host_route(R, torch):
@@ -213,11 +275,9 @@ def test_ones_column(R, torch):
     n, d = 257, 130
     X = rng.standard_normal((n, d)).astype(np.float32)
     y = _labels(rng, n)
-    H = np.hstack([X.astype(np.float64), np.ones((n, 1))])
     for storage in ("f64", "f32", "fp16"):
         s = R.Solver(n, d + 1, "erm", reg=0.1, storage=storage, objective_only=True)
-        s.set_data_f64(H, y)
-        ref = s.get_D()
+        ref = scaling_ref.form_D(X.astype(np.float64), y, None, None, storage, ones_column=True)
         for src in (X, torch.from_numpy(X).cuda()):
             s.set_data(np.zeros((n, d + 1)), y)
             s.set_data(src, y, ones_column=True)

@@ -369,7 +369,7 @@ def test_weights_golden_g8(L):
 # ------------------------------------------------------------------- synthetic generator
 @pytest.mark.parametrize("n,d,storage", [(1000, 37, "f64"), (1000, 1000, "f32"), (3001, 6, "f64"), (257, 3, "f32")])
 def test_synthetic_generator_vs_numpy_restatement(n, d, storage):
-    """k_synth + column statistics + standardisation (synth.hip, sweep.hip, api.hip: rbl_synth_*) against
+    """k_synth + column statistics + standardisation (synth.hip, sweep.hip, api_data.hip: rbl_synth_*) against
     oracle/synth.py: labels, flips, cluster draws and special-column positions bit for bit (integer Philox
     work); matrix values to 2e-5 (the device's __logf / __sincosf fast intrinsics against NumPy's float32
     log / sin / cos), through the whole pipeline D = -y * (x - mean) / std."""

@@ -384,7 +384,7 @@ def test_overridden_subproblem_hooks(R, kw, d):
 
 def test_w_step_ahead_of_the_host_is_invisible(R):
     """Single-sweep lasso iterations enqueue the NEXT w-step before the host has read the
-    current statistics (api.hip: rbl_phase_finish).  Whatever is called between two iterations
+    current statistics (api_iter.hip: rbl_phase_finish).  Whatever is called between two iterations
     must see w_k and must not change the trajectory: the same solve (a) uninterrupted, (b) with
     state reads / objective / accuracy calls between the iterations, (c) with
     the look-ahead disabled, gives bit-identical iterates."""

@@ -1,4 +1,4 @@
-"""The z-step's sort with 32-bit keys (csrc/elementwise.hip: k_make_m_range, k_keys32, k_sort32_fix; csrc/api.hip:
+"""The z-step's sort with 32-bit keys (csrc/elementwise.hip: k_make_m_range, k_keys32, k_sort32_fix; csrc/api_iter.hip:
 z_step_sorted, zb_resolve) driven on purpose.
 
 Kernel level (rbl_k_sort32 runs exactly the launches of the z-step's 32-bit branch): the permutation and the sorted m,
