@@ -19,7 +19,7 @@ except ImportError:      # package directory on sys.path: imported as ``LSVRG_so
 
 def LSVRGmethod(X, y, weight_function, loss, l2_reg=None, l1_reg=None, lossB=None,
                 max_iter=20, lr=0.01, train_loss=None, test_loss=None, uniform=None, verbose=True, args=None):
-    X = np.asarray(X.detach().cpu().numpy() if hasattr(X, "detach") else X, dtype=np.float64)
+    X = _baselines._solver._as_matrix(X)            # (sparse X is densified: the competitors work on dense rows)
     n, d = X.shape
     if weight_function not in ("erm", "ehrm") and args is None:
         raise ValueError("args for framework is None")                            # LSVRG_solver.py:31-32

@@ -18,7 +18,7 @@ except ImportError:      # package directory on sys.path: imported as ``SGD_solv
 
 def SGDmethod(X, y, weight_function, loss, l2_reg=None, l1_reg=None, lossB=None,
               max_iter=20, batch_size=64, lr=0.01, train_loss=None, test_loss=None, verbose=True, args=None):
-    X = np.asarray(X.detach().cpu().numpy() if hasattr(X, "detach") else X, dtype=np.float64)
+    X = _baselines._solver._as_matrix(X)            # (sparse X is densified: the competitors work on dense rows)
     n, d = X.shape
     ab, bb = _baselines.competitor_weights(weight_function, batch_size, args)     # objective.py:72-75: b-sample weights
     if weight_function != "ehrm":

@@ -23,6 +23,9 @@ SOURCE_DTYPE = {np.dtype(np.float64): DTYPE_F64, np.dtype(np.float32): DTYPE_F32
 MEM_HOST, MEM_DEVICE = 0, 1
 SCALING = {"none": 0, "fit": 1, "apply": 2}
 DATA_ONES_COLUMN = 1
+# rbl_set_data_csr: the type of indptr and indices
+INDEX_I32, INDEX_I64 = 0, 1
+INDEX_DTYPE = {np.dtype(np.int32): INDEX_I32, np.dtype(np.int64): INDEX_I64}
 
 
 def storage_ld(d, storage):
@@ -116,6 +119,7 @@ SIGNATURES = {
     "rbl_set_stream": (C.c_int, [_P, _P]),
     "rbl_set_data": (C.c_int, [_P, _P, _P, C.c_int64]),
     "rbl_set_data_from": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int64, _P, C.c_int, C.c_int]),
+    "rbl_set_data_csr": (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_int]),
     "rbl_set_scaling": (C.c_int, [_P, _P, _P]),
     "rbl_get_scaling": (C.c_int, [_P, _P, _P, C.POINTER(C.c_int)]),
     "rbl_generate_synthetic": (C.c_int, [_P, C.c_uint64, C.c_double, C.c_double]),

@@ -3,6 +3,7 @@ argument checking with the reference's error messages, buffer marshalling, and t
 per-phase calls.  Every number is computed by the HIP library."""
 import ctypes as C
 import math
+import sys
 
 import numpy as np
 
@@ -113,8 +114,23 @@ def add_intercept_column(X):
     return np.ascontiguousarray(np.hstack([X, np.ones((X.shape[0], 1))]))
 
 
+def _is_scipy_sparse(X):
+    """a scipy.sparse matrix or array (SciPy is looked at only if the caller has imported it)"""
+    sp = sys.modules.get("scipy.sparse")
+    return sp is not None and sp.issparse(X)
+
+
+def _is_torch_sparse(X):
+    return hasattr(X, "detach") and hasattr(X, "layout") and "sparse" in str(X.layout)
+
+
 def _as_matrix(X):
-    """X as a C-contiguous float64 host array (the baselines' path, and what as_source falls back to)"""
+    """X as a C-contiguous float64 host array (the baselines' path, and what as_source falls back to); sparse input is
+    densified - the baselines mirror the reference, which works on dense rows"""
+    if _is_scipy_sparse(X):
+        X = X.toarray()
+    elif _is_torch_sparse(X):
+        X = X.detach().to_dense()
     X = X.detach().cpu().numpy() if hasattr(X, "detach") else np.asarray(X)
     if X.ndim != 2:
         raise ValueError("X must be a 2-D array")
@@ -134,6 +150,83 @@ class Source:
         self.ptr, self.dtype, self.mem, self.ldx, self.shape, self.keep = int(ptr), dtype, mem, int(ldx), tuple(shape), keep
 
 
+class CsrSource:
+    """A sparse data matrix as rbl_set_data_csr takes it: ``shape``, ``dtype`` (_lib.DTYPE_* of the values), ``mem``
+    (_lib.MEM_HOST / MEM_DEVICE, of all three arrays), ``index_type`` (_lib.INDEX_*, of indptr and indices), ``nnz``,
+    the integer addresses ``indptr`` / ``indices`` / ``values`` and ``keep`` - the objects that own the memory (the
+    caller's own arrays when they are used in place)."""
+    __slots__ = ("shape", "dtype", "mem", "index_type", "nnz", "indptr", "indices", "values", "keep")
+
+    def __init__(self, shape, dtype, mem, index_type, nnz, indptr, indices, values, keep):
+        self.shape, self.dtype, self.mem, self.index_type, self.nnz = tuple(int(v) for v in shape), dtype, mem, index_type, int(nnz)
+        self.indptr, self.indices, self.values, self.keep = int(indptr), int(indices), int(values), keep
+
+
+def _host_array(a, dtype):
+    """a as a native, aligned, C-contiguous 1-D array of dtype - a itself when it already is one"""
+    if isinstance(a, np.ndarray) and a.dtype == dtype and a.dtype.isnative and a.ndim == 1 and a.flags["C_CONTIGUOUS"] \
+            and a.flags["ALIGNED"]:
+        return a
+    return np.ascontiguousarray(a, dtype=dtype).reshape(-1)
+
+
+def _csr_from_scipy(X):
+    """SciPy sparse -> CsrSource.  A canonical csr_matrix / csr_array with float64 / float32 data is used in place; other
+    formats go through tocsr(), a non-canonical matrix is copied and sum_duplicates() runs on the copy (the caller's
+    object is never modified); integer / bool data become float64; indptr and indices of different widths, or of a type
+    other than int32 / int64, become int64."""
+    A = X
+    if A.ndim != 2:
+        raise ValueError("X must be a 2-D array")
+    if A.dtype.kind == "c":
+        raise ValueError(f"X has dtype {A.dtype}: the supported element types are {_SOURCE_TYPES}")
+    if A.format != "csr":
+        A = A.tocsr()
+    if not A.has_canonical_format:
+        if A is X:
+            A = A.copy()
+        A.sum_duplicates()
+    vt = A.data.dtype if A.data.dtype in (np.dtype(np.float64), np.dtype(np.float32)) else np.dtype(np.float64)
+    it = A.indptr.dtype if A.indptr.dtype == A.indices.dtype and A.indptr.dtype in _lib.INDEX_DTYPE else np.dtype(np.int64)
+    indptr, indices, data = _host_array(A.indptr, it), _host_array(A.indices, it), _host_array(A.data, vt)
+    return CsrSource(A.shape, _lib.SOURCE_DTYPE[vt], _lib.MEM_HOST, _lib.INDEX_DTYPE[it], data.shape[0], indptr.ctypes.data,
+                     indices.ctypes.data, data.ctypes.data, (A, indptr, indices, data))
+
+
+def _csr_from_torch(X, device):
+    """torch sparse tensor -> CsrSource.  A sparse_csr tensor with float64 / float32 / float16 values is used in place, on
+    the CPU or on the solver's GPU (its current stream is synchronised first); COO and CSC go through to_sparse_csr();
+    integer / bool values become float64.  bfloat16, complex, batched or hybrid tensors and tensors on another device are
+    a ValueError.  The rows of a device tensor are checked by the library (canonical CSR)."""
+    import torch
+    t = X.detach()
+    if t.dim() != 2 or t.dense_dim() != 0:
+        raise ValueError("X must be a 2-D array (a batched or hybrid sparse tensor has no instance)")
+    kinds = {torch.float64: _lib.DTYPE_F64, torch.float32: _lib.DTYPE_F32, torch.float16: _lib.DTYPE_F16}
+    if t.dtype not in kinds and (t.dtype.is_floating_point or t.dtype.is_complex):
+        raise ValueError(f"X has dtype {t.dtype}: the supported element types are {_SOURCE_TYPES}")
+    if t.device.type not in ("cpu", "cuda"):
+        raise ValueError(f"X lives on {t.device}: host memory or the solver's GPU (element types {_SOURCE_TYPES})")
+    if t.device.type == "cuda" and device is not None and t.device.index != int(device):
+        raise ValueError(f"X lives on {t.device}, the solver on device {int(device)}: move it there (supported "
+                         f"element types: {_SOURCE_TYPES})")
+    if t.layout != torch.sparse_csr:
+        if t.layout == torch.sparse_coo:
+            t = t.coalesce()
+        t = t.to_sparse_csr()
+    if t.dtype not in kinds:
+        t = t.to(torch.float64)
+    crow, col, val = t.crow_indices(), t.col_indices(), t.values()
+    if crow.dtype != col.dtype or crow.dtype not in (torch.int32, torch.int64):
+        crow, col = crow.to(torch.int64), col.to(torch.int64)
+    crow, col, val = crow.contiguous(), col.contiguous(), val.contiguous()
+    if t.device.type == "cuda":
+        torch.cuda.current_stream(t.device).synchronize()          # X's writes are complete before the library reads it
+    return CsrSource(t.shape, kinds[t.dtype], _lib.MEM_DEVICE if t.device.type == "cuda" else _lib.MEM_HOST,
+                     _lib.INDEX_I32 if crow.dtype == torch.int32 else _lib.INDEX_I64, val.shape[0], crow.data_ptr(),
+                     col.data_ptr(), val.data_ptr(), (t, crow, col, val))
+
+
 def _row_stride(shape, strides, itemsize):
     """row stride in elements if the rows are contiguous and the stride a positive multiple of the item size, else None"""
     n, d = shape
@@ -149,7 +242,8 @@ def _row_stride(shape, strides, itemsize):
 
 
 def as_source(X, device=None):
-    """X in the type it has and from where it lives (include/rbl.h: rbl_set_data_from) -> Source.
+    """X in the type it has and from where it lives (include/rbl.h: rbl_set_data_from) -> Source; a scipy.sparse
+    matrix / array or a torch sparse tensor -> CsrSource (rbl_set_data_csr: _csr_from_scipy, _csr_from_torch).
 
     No copy for NumPy float64 / float32 / float16 arrays with contiguous rows (a column slice of a wider array is used
     in place with its row stride), for torch CPU tensors of those types (a view) and for torch tensors on the handle's
@@ -158,8 +252,12 @@ def as_source(X, device=None):
     in its own type, for the duration of the call - for a tensor of tens of GB pass contiguous rows.  Integer / bool data, Fortran
     order, negative strides and lists are converted to a C-contiguous float64 host array.  A tensor on another device,
     or of a type the library has no instance for (bfloat16, complex), is a ValueError."""
-    if isinstance(X, Source):
+    if isinstance(X, (Source, CsrSource)):
         return X
+    if _is_scipy_sparse(X):
+        return _csr_from_scipy(X)
+    if _is_torch_sparse(X):
+        return _csr_from_torch(X, device)
     if hasattr(X, "detach") and hasattr(X, "data_ptr"):
         import torch
         t = X.detach()
@@ -265,7 +363,7 @@ class Solver:
     # ---------------------------------------------------------------------- data
     def set_data(self, X, y, scaling="none", ones_column=False):
         """D = -y * X from X as it is (as_source: float64 / float32 / float16, host or this handle's GPU; include/rbl.h:
-        rbl_set_data_from).  scaling: "none", "fit" (standardise the columns on the device, keep the vectors:
+        rbl_set_data_from; sparse X: CSR arrays expanded on the device, rbl_set_data_csr).  scaling: "none", "fit" (standardise the columns on the device, keep the vectors:
         get_scaling) or "apply" (the vectors of set_scaling).  ones_column: X has d - 1 columns, column d - 1 of D is
         -y * 1 (the intercept's), never scaled.  Labels are a host float64 vector (a device y is copied, 8 bytes a row)."""
         if scaling not in _lib.SCALING:
@@ -275,8 +373,14 @@ class Solver:
         shape = (src.shape[0], src.shape[1] + (1 if ones_column else 0))
         if shape != (self.n, self.d):
             raise ValueError(f"X is {shape}, expected {(self.n, self.d)}")
+        flags = _lib.DATA_ONES_COLUMN if ones_column else 0
+        if isinstance(src, CsrSource):      # expanded on the device (include/rbl.h: rbl_set_data_csr)
+            _lib.check(self.lib.rbl_set_data_csr(self._h, C.c_void_p(src.indptr), C.c_void_p(src.indices),
+                                                 C.c_void_p(src.values), src.nnz, src.index_type, src.dtype, src.mem,
+                                                 _lib.ptr(y), _lib.SCALING[scaling], flags))
+            return
         _lib.check(self.lib.rbl_set_data_from(self._h, C.c_void_p(src.ptr), src.dtype, src.mem, src.ldx, _lib.ptr(y),
-                                              _lib.SCALING[scaling], _lib.DATA_ONES_COLUMN if ones_column else 0))
+                                              _lib.SCALING[scaling], flags))
 
     def set_data_f64(self, X, y):
         """the float64 host route (include/rbl.h: rbl_set_data): X is converted to a C-contiguous float64 host array"""

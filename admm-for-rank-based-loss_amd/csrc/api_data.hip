@@ -2,6 +2,7 @@
 // or device memory, optional column scaling), the synthetic generator's host side, penalties, labels, the one-vs-rest
 // decision, the Gram matrix and rbl_get_D.
 #include "api_internal.h"
+#include "csr_plan.h"
 
 // ---- rbl_set_data_from: X in the caller's type, from host or device memory ------------------------------------------
 static inline size_t src_esz(int dtype) { return dtype == RBL_DTYPE_F16 ? 2 : dtype == RBL_DTYPE_F32 ? 4 : 8; }
@@ -12,33 +13,48 @@ static inline double src_host_widen(const void* p, int dtype) {
 }
 // first and last byte of the claimed range must be device memory of the handle's device (a host pointer must fail here,
 // with a message, not fault in a kernel)
-static int src_check_device_range(const void* X, size_t bytes, int device) {
+static int src_check_device_range(const void* X, size_t bytes, int device, const char* who = "set_data_from",
+                                  const char* what = "X") {
     const char* ends[2] = {(const char*)X, (const char*)X + (bytes ? bytes - 1 : 0)};
     for (const char* p : ends) {
         hipPointerAttribute_t a;
         const hipError_t e = hipPointerGetAttributes(&a, p);
         if (e != hipSuccess) (void)hipGetLastError();
         if (e != hipSuccess || a.type != hipMemoryTypeDevice) {
-            rbl_set_error("set_data_from: X was passed as RBL_MEM_DEVICE but %p is not device memory (a host array goes "
-                          "with RBL_MEM_HOST)", (const void*)p);
+            rbl_set_error("%s: %s was passed as RBL_MEM_DEVICE but %p is not device memory (a host array goes "
+                          "with RBL_MEM_HOST)", who, what, (const void*)p);
             return RBL_ERR_INVALID;
         }
         if (a.device != device) {
-            rbl_set_error("set_data_from: X lives on device %d, the handle on device %d", a.device, device);
+            rbl_set_error("%s: %s lives on device %d, the handle on device %d", who, what, a.device, device);
             return RBL_ERR_INVALID;
         }
     }
     return RBL_OK;
 }
+// A CSR source as rbl_set_data_csr got it, with the host copy of indptr that plans the chunks
+struct CsrView {
+    const void *indptr = nullptr, *indices = nullptr, *values = nullptr;
+    int64_t nnz = 0;
+    int index_type = RBL_INDEX_I32, dtype = RBL_DTYPE_F64, mem = RBL_MEM_HOST;
+    size_t isz = 4, esz = 8;
+    const int64_t* ip = nullptr;   // n + 1 entries, checked (csr_check_indptr)
+    int64_t ds = 0, ldc = 0;       // source columns; row stride of the dense staging chunk (elements, 16-byte rows)
+    u64* err = nullptr;            // device: {entries refused by the expand kernel, smallest row that has one}
+};
 // The upload pipeline of a host source of any element type: the caller's rows are pinned in place and go over
 // PCIe untouched, chunk by chunk, into two staging buffers (the copy of chunk k + 1 runs on a second stream while the
-// kernels of chunk k read staging buffer k & 1).  A device source is one "chunk": the caller's own memory.
+// kernels of chunk k read staging buffer k & 1).  A device source is one "chunk": the caller's own memory.  A CSR source
+// (pass_csr) of either memory kind is expanded chunk by chunk into ONE dense staging buffer; of a host source the slices of
+// its three arrays take the place of the rows in the double-buffered copies.
 struct SrcPipe {
     DevArena tmp;
     unsigned char* Xd[2] = {nullptr, nullptr};
     hipStream_t stream = nullptr, copy_stream = nullptr;
     hipEvent_t copied[2] = {nullptr, nullptr}, formed[2] = {nullptr, nullptr};
-    void* registered = nullptr;
+    void* registered[3] = {nullptr, nullptr, nullptr};   // (a CSR source: three arrays)
+    // a CSR source: one dense staging chunk, and for a host source two sets of slices of the three arrays
+    unsigned char *stage = nullptr, *ipd[2] = {nullptr, nullptr}, *idx[2] = {nullptr, nullptr}, *val[2] = {nullptr, nullptr};
     ~SrcPipe() {   // (the arena's buffers are freed after this body: nothing may still be running on them)
         if (copy_stream) (void)hipStreamSynchronize(copy_stream);
         (void)hipStreamSynchronize(stream);
@@ -47,14 +63,22 @@ struct SrcPipe {
             if (formed[k]) (void)hipEventDestroy(formed[k]);
         }
         if (copy_stream) (void)hipStreamDestroy(copy_stream);
-        if (registered) (void)hipHostUnregister(registered);
+        for (void* r : registered)
+            if (r) (void)hipHostUnregister(r);
         (void)hipGetLastError();
     }
-    int open_host(const void* X, size_t xbytes, size_t chunk_bytes) {
-        if (hipHostRegister(const_cast<void*>(X), xbytes, hipHostRegisterDefault) == hipSuccess) registered = const_cast<void*>(X);
+    void pin(const void* X, size_t xbytes, int slot) {
+        if (!X || !xbytes) return;
+        if (hipHostRegister(const_cast<void*>(X), xbytes, hipHostRegisterDefault) == hipSuccess) registered[slot] = const_cast<void*>(X);
         else (void)hipGetLastError();   // pageable copies instead: slower, same result
+    }
+    int open_host(const void* X, size_t xbytes, size_t chunk_bytes) {
+        pin(X, xbytes, 0);
         RBL_TRY(tmp.alloc(&Xd[0], chunk_bytes));
         RBL_TRY(tmp.alloc(&Xd[1], chunk_bytes));
+        return open_copy_stream();
+    }
+    int open_copy_stream() {
         RBL_HIP(hipStreamCreateWithFlags(&copy_stream, hipStreamNonBlocking));
         for (int k = 0; k < 2; ++k) {
             RBL_HIP(hipEventCreateWithFlags(&copied[k], hipEventDisableTiming));
@@ -66,14 +90,9 @@ struct SrcPipe {
     // with both streams idle
     int pass(const void* X, int mem, size_t esz, int64_t ldx, int64_t ds, int64_t n, int64_t chunk,
              const std::function<int(const void*, int64_t, int64_t)>& fn, double* ms = nullptr) {
-        int rc = RBL_OK;
-        hipEvent_t t0 = nullptr, t1 = nullptr;   // the pass on the handle's stream, first kernel to last (host source: the
-                                                 // copies it waits for in between included)
-        if (ms && (hipEventCreate(&t0) != hipSuccess || hipEventCreate(&t1) != hipSuccess || hipEventRecord(t0, stream) != hipSuccess))
-            ms = nullptr;
-        if (mem == RBL_MEM_DEVICE) {
-            rc = fn(X, (int64_t)0, n);
-        } else {
+        return timed(ms, [&]() {
+            if (mem == RBL_MEM_DEVICE) return fn(X, (int64_t)0, n);
+            int rc = RBL_OK;
             int64_t k = 0;
             for (int64_t r0 = 0; r0 < n && rc == RBL_OK; r0 += chunk, ++k) {
                 const int64_t rows = n - r0 < chunk ? n - r0 : chunk;
@@ -95,7 +114,60 @@ struct SrcPipe {
                 if (rc == RBL_OK && hipEventRecord(formed[b], stream) != hipSuccess) rc = RBL_ERR_HIP;
             }
             if (hipStreamSynchronize(copy_stream) != hipSuccess && rc == RBL_OK) rc = RBL_ERR_HIP;
-        }
+            return rc;
+        });
+    }
+    // The CSR sibling: the same fn is handed dense rows.  Chunk by chunk the source's rows are expanded into the one
+    // staging buffer (expansion and fn run on `stream`, in order) - a device source straight from the caller's arrays, a
+    // host source from slices of the three arrays that the copy stream brings over one chunk ahead.
+    int pass_csr(const CsrView& v, int64_t n, int64_t chunk, int num_cu, const std::function<int(const void*, int64_t, int64_t)>& fn,
+                 double* ms = nullptr) {
+        return timed(ms, [&]() {
+            int rc = RBL_OK;
+            const int64_t nk = csr_chunk_count(n, chunk);
+            for (int64_t k = 0; k < nk && rc == RBL_OK; ++k) {
+                const CsrChunk c = csr_chunk(v.ip, n, chunk, k);
+                const int b = (int)(k & 1);
+                if (v.mem == RBL_MEM_DEVICE) {
+                    rc = launch_csr_expand(v.dtype, v.index_type, stage, v.ldc, c.rows, v.ds, (const unsigned char*)v.indptr + (size_t)c.r0 * v.isz,
+                                           v.indices, v.values, 0, v.nnz, c.r0, v.err, num_cu, stream);
+                    if (rc == RBL_OK) rc = fn((const void*)stage, c.r0, c.rows);
+                    continue;
+                }
+                hipError_t e = hipSuccess;
+                if (k >= 2) e = hipStreamWaitEvent(copy_stream, formed[b], 0);   // slices b have been expanded
+                if (e == hipSuccess)
+                    e = hipMemcpyAsync(ipd[b], (const unsigned char*)v.indptr + (size_t)c.r0 * v.isz, (size_t)(c.rows + 1) * v.isz,
+                                       hipMemcpyHostToDevice, copy_stream);
+                if (e == hipSuccess && c.cnt > 0)
+                    e = hipMemcpyAsync(idx[b], (const unsigned char*)v.indices + (size_t)c.base * v.isz, (size_t)c.cnt * v.isz,
+                                       hipMemcpyHostToDevice, copy_stream);
+                if (e == hipSuccess && c.cnt > 0)
+                    e = hipMemcpyAsync(val[b], (const unsigned char*)v.values + (size_t)c.base * v.esz, (size_t)c.cnt * v.esz,
+                                       hipMemcpyHostToDevice, copy_stream);
+                if (e == hipSuccess) e = hipEventRecord(copied[b], copy_stream);
+                if (e == hipSuccess) e = hipStreamWaitEvent(stream, copied[b], 0);
+                if (e != hipSuccess) {
+                    rbl_set_error("set_data_csr: upload failed: %s", hipGetErrorString(e));
+                    rc = RBL_ERR_HIP;
+                    break;
+                }
+                rc = launch_csr_expand(v.dtype, v.index_type, stage, v.ldc, c.rows, v.ds, ipd[b], idx[b], val[b], c.base, c.cnt, c.r0,
+                                       v.err, num_cu, stream);
+                if (rc == RBL_OK && hipEventRecord(formed[b], stream) != hipSuccess) rc = RBL_ERR_HIP;
+                if (rc == RBL_OK) rc = fn((const void*)stage, c.r0, c.rows);
+            }
+            if (copy_stream && hipStreamSynchronize(copy_stream) != hipSuccess && rc == RBL_OK) rc = RBL_ERR_HIP;
+            return rc;
+        });
+    }
+    // body() enqueues one pass; timed on the handle's stream, first kernel to last (host source: the copies it waits for in
+    // between included); returns with the stream idle
+    int timed(double* ms, const std::function<int()>& body) {
+        hipEvent_t t0 = nullptr, t1 = nullptr;
+        if (ms && (hipEventCreate(&t0) != hipSuccess || hipEventCreate(&t1) != hipSuccess || hipEventRecord(t0, stream) != hipSuccess))
+            ms = nullptr;
+        int rc = body();
         if (ms && hipEventRecord(t1, stream) != hipSuccess) ms = nullptr;
         if (hipStreamSynchronize(stream) != hipSuccess && rc == RBL_OK) rc = RBL_ERR_HIP;
         float el = 0.f;
@@ -110,8 +182,68 @@ struct SrcPipe {
     }
 };
 
+// the raw value at (r, c) of a CSR source, for a message: 0 for an implicit entry
+static int csr_value_at(const CsrView& v, int64_t r, int64_t c, double* out) {
+    *out = 0.0;
+    const int64_t a = v.ip[r], len = v.ip[r + 1] - a;
+    if (len <= 0) return RBL_OK;
+    std::vector<unsigned char> ib((size_t)len * v.isz);
+    const hipMemcpyKind kind = v.mem == RBL_MEM_DEVICE ? hipMemcpyDeviceToHost : hipMemcpyHostToHost;
+    RBL_HIP(hipMemcpy(ib.data(), (const unsigned char*)v.indices + (size_t)a * v.isz, ib.size(), kind));
+    for (int64_t k = 0; k < len; ++k) {
+        const int64_t ck = v.index_type == RBL_INDEX_I64 ? ((const int64_t*)ib.data())[k] : (int64_t)((const int32_t*)ib.data())[k];
+        if (ck != c) continue;
+        unsigned char tmp8[8] = {0};
+        RBL_HIP(hipMemcpy(tmp8, (const unsigned char*)v.values + (size_t)(a + k) * v.esz, v.esz, kind));
+        *out = src_host_widen(tmp8, v.dtype);
+        break;
+    }
+    return RBL_OK;
+}
+
+// what the expand kernel refused, read after a pass: RBL_ERR_INVALID with the first offending entry of the smallest
+// offending row (looked up in the source) in the message
+static int csr_verdict(const CsrView& v) {
+    u64 got[2] = {0ull, 0ull};
+    RBL_HIP(hipMemcpy(got, v.err, sizeof(got), hipMemcpyDeviceToHost));
+    if (got[0] == 0) return RBL_OK;
+    const int64_t r = (int64_t)got[1], a = v.ip[r], len = v.ip[r + 1] - a;
+    std::vector<unsigned char> ib((size_t)(len > 0 ? len : 1) * v.isz);
+    RBL_HIP(hipMemcpy(ib.data(), (const unsigned char*)v.indices + (size_t)a * v.isz, (size_t)len * v.isz,
+                      v.mem == RBL_MEM_DEVICE ? hipMemcpyDeviceToHost : hipMemcpyHostToHost));
+    static const char* fix = "canonical CSR is required: sort the indices of every row and sum duplicates first (SciPy: "
+                             "sum_duplicates(); torch: coalesce() the COO tensor before to_sparse_csr())";
+    int64_t prev = -1;
+    for (int64_t k = 0; k < len; ++k) {
+        const int64_t c = v.index_type == RBL_INDEX_I64 ? ((const int64_t*)ib.data())[k] : (int64_t)((const int32_t*)ib.data())[k];
+        if (c < 0 || c >= v.ds) {
+            rbl_set_error("set_data_csr: %llu entries refused, first in row %lld: column index %lld (entry %lld of the row) is "
+                          "outside [0, %lld)", got[0], (long long)r, (long long)c, (long long)k, (long long)v.ds);
+            return RBL_ERR_INVALID;
+        }
+        if (k > 0 && c == prev) {
+            rbl_set_error("set_data_csr: %llu entries refused, first in row %lld: column index %lld is repeated (entries %lld "
+                          "and %lld of the row) - duplicates are not summed; %s", got[0], (long long)r, (long long)c,
+                          (long long)(k - 1), (long long)k, fix);
+            return RBL_ERR_INVALID;
+        }
+        if (k > 0 && c < prev) {
+            rbl_set_error("set_data_csr: %llu entries refused, first in row %lld: column index %lld follows %lld (entries %lld "
+                          "and %lld of the row) - the indices of a row must be strictly increasing; %s", got[0], (long long)r,
+                          (long long)c, (long long)prev, (long long)(k - 1), (long long)k, fix);
+            return RBL_ERR_INVALID;
+        }
+        prev = c;
+    }
+    rbl_set_error("set_data_csr: %llu entries refused, first in row %lld (the arrays changed during the call?)", got[0],
+                  (long long)r);
+    return RBL_ERR_INVALID;
+}
+
+// cs == NULL: the dense source X / ldx.  cs != NULL: the CSR source *cs (X is NULL), expanded chunk by chunk into dense
+// staging rows of stride cs->ldc that the same kernels read.
 static int set_data_from_impl(rbl_solver* h, const void* X, int dtype, int mem, int64_t ldx, const double* y, int scaling,
-                              int64_t ds) {
+                              int64_t ds, CsrView* cs = nullptr) {
     const int64_t n = h->n, d = h->d, ld = h->ld;
     const size_t esz = src_esz(dtype);
     {
@@ -125,12 +257,30 @@ static int set_data_from_impl(rbl_solver* h, const void* X, int dtype, int mem, 
     h->src_timed[0] = h->src_timed[1] = 0;
     const int64_t SB = src_stat_rows();
     int64_t chunk = n;
-    if (mem == RBL_MEM_HOST) {
-        long long cb = 64LL << 20;
-        if (const char* e = getenv("RBL_UPLOAD_CHUNK_BYTES")) {   // test hook: several chunks at small sizes
-            const long long v = atoll(e);
-            if (v > 0) cb = v;
+    long long cb = 64LL << 20;
+    if (const char* e = getenv("RBL_UPLOAD_CHUNK_BYTES")) {   // test hook: several chunks at small sizes
+        const long long v = atoll(e);
+        if (v > 0) cb = v;
+    }
+    if (cs) {   // a device source is chunked as well: the dense staging buffer stays at chunk size
+        cs->ldc = round_up(ds, (int64_t)(16 / esz));
+        ldx = cs->ldc;
+        chunk = csr_chunk_rows((int64_t)cb, (int64_t)(esz * (size_t)ldx), n, scaling == RBL_SCALE_FIT ? SB : 0);
+        RBL_TRY(p.tmp.alloc(&p.stage, (size_t)chunk * (size_t)ldx * esz));
+        RBL_TRY(p.tmp.alloc(&cs->err, 2));
+        if (mem == RBL_MEM_HOST) {
+            const size_t cap = (size_t)csr_max_chunk_nnz(cs->ip, n, chunk);
+            p.pin(cs->indptr, (size_t)(n + 1) * cs->isz, 0);
+            p.pin(cs->indices, (size_t)cs->nnz * cs->isz, 1);
+            p.pin(cs->values, (size_t)cs->nnz * esz, 2);
+            for (int b = 0; b < 2; ++b) {
+                RBL_TRY(p.tmp.alloc(&p.ipd[b], (size_t)(chunk + 1) * cs->isz));
+                RBL_TRY(p.tmp.alloc(&p.idx[b], cap * cs->isz));
+                RBL_TRY(p.tmp.alloc(&p.val[b], cap * esz));
+            }
+            RBL_TRY(p.open_copy_stream());
         }
+    } else if (mem == RBL_MEM_HOST) {
         chunk = (int64_t)(cb / (long long)(esz * (size_t)ldx));
         if (scaling == RBL_SCALE_FIT) {   // whole row blocks of the statistics (the other modes: 64 MB)
             chunk = chunk / SB * SB;
@@ -141,11 +291,18 @@ static int set_data_from_impl(rbl_solver* h, const void* X, int dtype, int mem, 
         const size_t xbytes = ((size_t)(n - 1) * (size_t)ldx + (size_t)ds) * esz;
         RBL_TRY(p.open_host(X, xbytes, (size_t)chunk * (size_t)ldx * esz));
     }
+    const u64 pair0[2] = {0ull, ~0ull};   // {count, smallest position}
+    // one pass over the source, whichever kind; a CSR source's entry checks are read when the pass has ended
+    auto run_pass = [&](const std::function<int(const void*, int64_t, int64_t)>& fn, double* ms) -> int {
+        if (!cs) return p.pass(X, mem, esz, ldx, ds, n, chunk, fn, ms);
+        RBL_HIP(hipMemcpy(cs->err, pair0, sizeof(pair0), hipMemcpyHostToDevice));
+        RBL_TRY(p.pass_csr(*cs, n, chunk, h->num_cu, fn, ms));
+        return csr_verdict(*cs);
+    };
     u64* ovf = nullptr;   // RBL_STORE_F16: {entries that do not fit, first of them} written by the forming kernel
     if (h->storage == RBL_STORE_F16) {
-        const u64 ovf0[2] = {0ull, ~0ull};
         RBL_TRY(p.tmp.alloc(&ovf, 2));
-        RBL_HIP(hipMemcpy(ovf, ovf0, sizeof(ovf0), hipMemcpyHostToDevice));
+        RBL_HIP(hipMemcpy(ovf, pair0, sizeof(pair0), hipMemcpyHostToDevice));
     }
     double *dmean = nullptr, *dinv = nullptr;
     std::vector<double> fit_mean, fit_scale;   // RBL_SCALE_FIT: kept in the handle after the forming pass has succeeded
@@ -157,7 +314,23 @@ static int set_data_from_impl(rbl_solver* h, const void* X, int dtype, int mem, 
         RBL_TRY(p.tmp.alloc(&sums, (size_t)ld * 2));
         RBL_HIP(hipMemsetAsync(slab, 0, sizeof(double) * (size_t)nb * ld * 2, h->stream));
         std::vector<double> sh((size_t)ld, 0.0), st((size_t)ld * 2, 0.0);
-        if (mem == RBL_MEM_HOST) {   // the shift: the column's first row, widened
+        if (cs) {   // row 0 expanded into the staging buffer (its refused entries are counted by the pass)
+            const void *ipc = cs->indptr, *idc = cs->indices, *vlc = cs->values;
+            const int64_t cnt0 = cs->ip[1];
+            if (mem == RBL_MEM_HOST) {
+                RBL_HIP(hipMemcpyAsync(p.ipd[0], cs->indptr, 2 * cs->isz, hipMemcpyHostToDevice, h->stream));
+                if (cnt0 > 0) {
+                    RBL_HIP(hipMemcpyAsync(p.idx[0], cs->indices, (size_t)cnt0 * cs->isz, hipMemcpyHostToDevice, h->stream));
+                    RBL_HIP(hipMemcpyAsync(p.val[0], cs->values, (size_t)cnt0 * esz, hipMemcpyHostToDevice, h->stream));
+                }
+                ipc = p.ipd[0], idc = p.idx[0], vlc = p.val[0];
+            }
+            RBL_HIP(hipMemcpy(cs->err, pair0, sizeof(pair0), hipMemcpyHostToDevice));
+            RBL_TRY(launch_csr_expand(dtype, cs->index_type, p.stage, ldx, 1, ds, ipc, idc, vlc, 0, cnt0, 0, cs->err, h->num_cu, h->stream));
+            RBL_HIP(hipMemsetAsync(shift, 0, sizeof(double) * ld, h->stream));
+            RBL_TRY(launch_src_row(dtype, p.stage, ds, shift, h->stream));
+            RBL_HIP(hipStreamSynchronize(h->stream));
+        } else if (mem == RBL_MEM_HOST) {   // the shift: the column's first row, widened
             for (int64_t j = 0; j < ds; ++j) sh[(size_t)j] = src_host_widen((const unsigned char*)X + (size_t)j * esz, dtype);
             RBL_HIP(hipMemcpyAsync(shift, sh.data(), sizeof(double) * ld, hipMemcpyHostToDevice, h->stream));
             RBL_HIP(hipStreamSynchronize(h->stream));
@@ -166,7 +339,7 @@ static int set_data_from_impl(rbl_solver* h, const void* X, int dtype, int mem, 
             RBL_TRY(launch_src_row(dtype, X, ds, shift, h->stream));
         }
         double* slab2 = slab + (size_t)nb * ld;
-        RBL_TRY(p.pass(X, mem, esz, ldx, ds, n, chunk, [&](const void* Xc, int64_t r0, int64_t rows) {
+        RBL_TRY(run_pass([&](const void* Xc, int64_t r0, int64_t rows) {
             return launch_src_colstats(dtype, Xc, ldx, rows, ds, shift, slab, slab2, ld, r0 / SB, h->stream);
         }, &h->src_ms[0]));
         h->src_timed[0] = 1;
@@ -208,7 +381,7 @@ static int set_data_from_impl(rbl_solver* h, const void* X, int dtype, int mem, 
         dinv = h->colstats + 3 * ld;
         RBL_HIP(hipMemcpy(dmean, mi.data(), sizeof(double) * ld * 2, hipMemcpyHostToDevice));
     }
-    RBL_TRY(p.pass(X, mem, esz, ldx, ds, n, chunk, [&](const void* Xc, int64_t r0, int64_t rows) {
+    RBL_TRY(run_pass([&](const void* Xc, int64_t r0, int64_t rows) {
         return launch_form_src(dtype, h->storage, h->D, ld, r0, Xc, ldx, h->ysign + r0, rows, ds, d, dmean, dinv, h->num_cu,
                                h->stream, ovf);
     }, &h->src_ms[1]));
@@ -220,7 +393,9 @@ static int set_data_from_impl(rbl_solver* h, const void* X, int dtype, int mem, 
             const long long r = (long long)(got[1] / (u64)d), c = (long long)(got[1] % (u64)d);
             double raw = 0.0;
             const unsigned char* at = (const unsigned char*)X + ((size_t)r * (size_t)ldx + (size_t)c) * esz;
-            if (mem == RBL_MEM_HOST) {
+            if (cs) {
+                RBL_TRY(csr_value_at(*cs, r, c, &raw));
+            } else if (mem == RBL_MEM_HOST) {
                 raw = src_host_widen(at, dtype);
             } else {
                 unsigned char tmp8[8] = {0};
@@ -251,27 +426,50 @@ static int check_labels(const char* who, const double* y, int64_t n) {
     return RBL_OK;
 }
 
+// the argument checks the dense and the CSR entry share (`who`: the entry point's name in the message)
+static int check_source_args(rbl_solver* h, const char* who, int dtype, int mem, int scaling, int flags) {
+    if (dtype != RBL_DTYPE_F64 && dtype != RBL_DTYPE_F32 && dtype != RBL_DTYPE_F16) {
+        rbl_set_error("%s: unknown dtype %d (RBL_DTYPE_F64 / F32 / F16)", who, dtype);
+        return RBL_ERR_INVALID;
+    }
+    if (mem != RBL_MEM_HOST && mem != RBL_MEM_DEVICE) {
+        rbl_set_error("%s: unknown memory kind %d (RBL_MEM_HOST / RBL_MEM_DEVICE)", who, mem);
+        return RBL_ERR_INVALID;
+    }
+    if (scaling != RBL_SCALE_NONE && scaling != RBL_SCALE_FIT && scaling != RBL_SCALE_APPLY) {
+        rbl_set_error("%s: unknown scaling %d (RBL_SCALE_NONE / FIT / APPLY)", who, scaling);
+        return RBL_ERR_INVALID;
+    }
+    if (flags & ~RBL_DATA_ONES_COLUMN) {
+        rbl_set_error("%s: unknown flags 0x%x", who, (unsigned)flags);
+        return RBL_ERR_INVALID;
+    }
+    return RBL_OK;
+}
+static int check_scaling_state(rbl_solver* h, const char* who, int scaling) {
+    if (scaling == RBL_SCALE_FIT && h->nt != h->n) {
+        rbl_set_error("%s: RBL_SCALE_FIT on a row-sharded handle (n = %lld of n_total = %lld) - reduce the column "
+                      "sums over the ranks in the driver, hand every rank the same vectors (rbl_set_scaling) and use "
+                      "RBL_SCALE_APPLY", who, (long long)h->n, (long long)h->nt);
+        return RBL_ERR_INVALID;
+    }
+    if (scaling == RBL_SCALE_FIT && h->n < 1) {
+        rbl_set_error("%s: RBL_SCALE_FIT needs at least one row", who);
+        return RBL_ERR_INVALID;
+    }
+    if (scaling == RBL_SCALE_APPLY && !h->sc_set) {
+        rbl_set_error("%s: RBL_SCALE_APPLY without a scaling - call rbl_set_scaling first", who);
+        return RBL_ERR_STATE;
+    }
+    return RBL_OK;
+}
+
 extern "C" {
 
 int rbl_set_data_from(rbl_solver* h, const void* X, int dtype, int mem, int64_t ldx, const double* y, int scaling, int flags) {
     RBL_ENTER(h);
     RBL_NOT_BORROWER(h, "set_data_from");
-    if (dtype != RBL_DTYPE_F64 && dtype != RBL_DTYPE_F32 && dtype != RBL_DTYPE_F16) {
-        rbl_set_error("set_data_from: unknown dtype %d (RBL_DTYPE_F64 / F32 / F16)", dtype);
-        return RBL_ERR_INVALID;
-    }
-    if (mem != RBL_MEM_HOST && mem != RBL_MEM_DEVICE) {
-        rbl_set_error("set_data_from: unknown memory kind %d (RBL_MEM_HOST / RBL_MEM_DEVICE)", mem);
-        return RBL_ERR_INVALID;
-    }
-    if (scaling != RBL_SCALE_NONE && scaling != RBL_SCALE_FIT && scaling != RBL_SCALE_APPLY) {
-        rbl_set_error("set_data_from: unknown scaling %d (RBL_SCALE_NONE / FIT / APPLY)", scaling);
-        return RBL_ERR_INVALID;
-    }
-    if (flags & ~RBL_DATA_ONES_COLUMN) {
-        rbl_set_error("set_data_from: unknown flags 0x%x", (unsigned)flags);
-        return RBL_ERR_INVALID;
-    }
+    RBL_TRY(check_source_args(h, "set_data_from", dtype, mem, scaling, flags));
     const int64_t n = h->n, d = h->d;
     const int64_t ds = d - ((flags & RBL_DATA_ONES_COLUMN) ? 1 : 0);
     if (!X || !y || ds < 1 || ldx < ds) {
@@ -284,25 +482,87 @@ int rbl_set_data_from(rbl_solver* h, const void* X, int dtype, int mem, int64_t 
         return RBL_ERR_INVALID;
     }
     RBL_TRY(check_labels("set_data_from", y, n));
-    if (scaling == RBL_SCALE_FIT && h->nt != h->n) {
-        rbl_set_error("set_data_from: RBL_SCALE_FIT on a row-sharded handle (n = %lld of n_total = %lld) - reduce the column "
-                      "sums over the ranks in the driver, hand every rank the same vectors (rbl_set_scaling) and use "
-                      "RBL_SCALE_APPLY", (long long)h->n, (long long)h->nt);
-        return RBL_ERR_INVALID;
-    }
-    if (scaling == RBL_SCALE_FIT && n < 1) {
-        rbl_set_error("set_data_from: RBL_SCALE_FIT needs at least one row");
-        return RBL_ERR_INVALID;
-    }
-    if (scaling == RBL_SCALE_APPLY && !h->sc_set) {
-        rbl_set_error("set_data_from: RBL_SCALE_APPLY without a scaling - call rbl_set_scaling first");
-        return RBL_ERR_STATE;
-    }
+    RBL_TRY(check_scaling_state(h, "set_data_from", scaling));
     if (n > 0) {
         if (mem == RBL_MEM_DEVICE)
             RBL_TRY(src_check_device_range(X, ((size_t)(n - 1) * (size_t)ldx + (size_t)ds) * src_esz(dtype), h->cfg.device));
         h->data_ready = false;   // a failed upload leaves the handle without data
         RBL_TRY(set_data_from_impl(h, X, dtype, mem, ldx, y, scaling, ds));
+    }
+    h->data_ready = true;
+    h->gram_ready = h->gram_local_done = false;
+    h->v_valid = false;
+    return RBL_OK;
+}
+
+int rbl_set_data_csr(rbl_solver* h, const void* indptr, const void* indices, const void* values, int64_t nnz, int index_type,
+                     int dtype, int mem, const double* y, int scaling, int flags) {
+    RBL_ENTER(h);
+    RBL_NOT_BORROWER(h, "set_data_csr");
+    RBL_TRY(check_source_args(h, "set_data_csr", dtype, mem, scaling, flags));
+    if (index_type != RBL_INDEX_I32 && index_type != RBL_INDEX_I64) {
+        rbl_set_error("set_data_csr: unknown index type %d (RBL_INDEX_I32 / RBL_INDEX_I64)", index_type);
+        return RBL_ERR_INVALID;
+    }
+    const int64_t n = h->n, d = h->d;
+    const int64_t ds = d - ((flags & RBL_DATA_ONES_COLUMN) ? 1 : 0);
+    if (!indptr || !y || ds < 1 || nnz < 0 || (nnz > 0 && (!indices || !values))) {
+        rbl_set_error("set_data_csr: bad arguments (indptr %s, indices %s, values %s, y %s, nnz=%lld, source columns=%lld)",
+                      indptr ? "given" : "NULL", indices ? "given" : "NULL", values ? "given" : "NULL", y ? "given" : "NULL",
+                      (long long)nnz, (long long)ds);
+        return RBL_ERR_INVALID;
+    }
+    CsrView v;
+    v.indptr = indptr, v.indices = nnz ? indices : nullptr, v.values = nnz ? values : nullptr;
+    v.nnz = nnz, v.index_type = index_type, v.dtype = dtype, v.mem = mem, v.ds = ds;
+    v.isz = index_type == RBL_INDEX_I64 ? 8 : 4, v.esz = src_esz(dtype);
+    if ((size_t)(uintptr_t)indptr % v.isz != 0 || (size_t)(uintptr_t)v.indices % v.isz != 0 || (size_t)(uintptr_t)v.values % v.esz != 0) {
+        rbl_set_error("set_data_csr: indptr / indices / values are not aligned to their element sizes (%zu / %zu / %zu bytes)",
+                      v.isz, v.isz, v.esz);
+        return RBL_ERR_INVALID;
+    }
+    RBL_TRY(check_labels("set_data_csr", y, n));
+    RBL_TRY(check_scaling_state(h, "set_data_csr", scaling));
+    if (mem == RBL_MEM_DEVICE) {
+        RBL_TRY(src_check_device_range(indptr, (size_t)(n + 1) * v.isz, h->cfg.device, "set_data_csr", "indptr"));
+        if (nnz > 0) {
+            RBL_TRY(src_check_device_range(indices, (size_t)nnz * v.isz, h->cfg.device, "set_data_csr", "indices"));
+            RBL_TRY(src_check_device_range(values, (size_t)nnz * v.esz, h->cfg.device, "set_data_csr", "values"));
+        }
+    }
+    // the structure of indptr, on the host, before anything is enqueued: a device indptr is copied once, and the 64-bit
+    // copy plans the chunks
+    std::vector<int64_t> ip((size_t)n + 1);
+    {
+        std::vector<unsigned char> raw;
+        const void* src = indptr;
+        if (mem == RBL_MEM_DEVICE) {
+            raw.resize((size_t)(n + 1) * v.isz);
+            RBL_HIP(hipStreamSynchronize(h->stream));
+            RBL_HIP(hipMemcpy(raw.data(), indptr, raw.size(), hipMemcpyDeviceToHost));
+            src = raw.data();
+        }
+        int64_t row = 0, got = 0;
+        int bad;
+        if (index_type == RBL_INDEX_I64) {
+            bad = csr_check_indptr((const int64_t*)src, n, nnz, &row, &got);
+            csr_widen_indptr((const int64_t*)src, n, ip.data());
+        } else {
+            bad = csr_check_indptr((const int32_t*)src, n, nnz, &row, &got);
+            csr_widen_indptr((const int32_t*)src, n, ip.data());
+        }
+        if (bad == CSR_PLAN_FIRST) rbl_set_error("set_data_csr: indptr[0] is %lld, not 0", (long long)got);
+        if (bad == CSR_PLAN_DECREASING)
+            rbl_set_error("set_data_csr: indptr decreases at row %lld (indptr[%lld] = %lld < indptr[%lld] = %lld)", (long long)row,
+                          (long long)(row + 1), (long long)got, (long long)row, (long long)ip[(size_t)row]);
+        if (bad == CSR_PLAN_LAST)
+            rbl_set_error("set_data_csr: indptr[n] is %lld, nnz is %lld (n = %lld rows)", (long long)got, (long long)nnz, (long long)n);
+        if (bad != CSR_PLAN_OK) return RBL_ERR_INVALID;
+    }
+    v.ip = ip.data();
+    if (n > 0) {
+        h->data_ready = false;   // a failed upload leaves the handle without data
+        RBL_TRY(set_data_from_impl(h, nullptr, dtype, mem, 0, y, scaling, ds, &v));
     }
     h->data_ready = true;
     h->gram_ready = h->gram_local_done = false;

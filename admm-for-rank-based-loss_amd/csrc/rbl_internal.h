@@ -200,6 +200,13 @@ int launch_src_colstats(int dtype, const void* X, int64_t ldx, int64_t rows, int
                         double* slab2, int64_t ld, int64_t blk0, hipStream_t s);
 int launch_src_colreduce(const double* slab, int64_t nb, int64_t ld, double* out, hipStream_t s);
 int launch_src_row(int dtype, const void* X, int64_t ds, double* out, hipStream_t s);
+// CSR source (rbl_set_data_csr) -> `rows` dense rows of stride ldc elements of type dtype in Xc (zeroed here first), which
+// the launchers above then read.  indptr: the rows + 1 entries of these rows, of index_type (RBL_INDEX_*); entry positions
+// in indices / values are indptr[r] - base, clamped to [0, cnt).  A column index outside [0, ds) or not above the entry
+// before it is not written: err[0] += 1, err[1] = min(err[1], row0 + r).
+int launch_csr_expand(int dtype, int index_type, void* Xc, int64_t ldc, int64_t rows, int64_t ds, const void* indptr,
+                      const void* indices, const void* values, int64_t base, int64_t cnt, int64_t row0, u64* err, int num_cu,
+                      hipStream_t s);
 
 // ---- elementwise.hip --------------------------------------------------------------------
 // rs (optional, in the launchers below): the sign vector of a handle with labels of its own on a borrowed D

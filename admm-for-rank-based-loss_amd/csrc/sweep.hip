@@ -638,6 +638,51 @@ __global__ void k_src_row(const S* __restrict__ X, long long ds, double* __restr
     if (j < ds) out[j] = src_widen(X[j]);
 }
 
+// CSR source -> dense staging rows (already zeroed) of the caller's element type: one wave per row, the lanes stride over
+// the row's entries (index and value loads are coalesced), every lane stores one element.  V types the values by size
+// only (the bits are copied: -0.0 stays -0.0), I = int / long long.  Entry positions are indptr[r] - base, clamped to
+// [0, cnt) in 64 bits before anything is indexed with them; a column index is compared in 64 bits with [0, ds) and with
+// the entry before it (canonical CSR: strictly increasing) BEFORE it reaches an address.  An entry that fails is not
+// written: err[0] counts them, err[1] keeps the smallest row (row0 + r) that has one.
+template <typename V, typename I>
+__global__ __launch_bounds__(256) void k_csr_expand(V* __restrict__ Xc, long long ldc, long long rows, long long ds,
+                                                     const I* __restrict__ indptr, const I* __restrict__ indices,
+                                                     const V* __restrict__ values, long long base, long long cnt,
+                                                     long long row0, u64* err) {
+    const int lane = (int)threadIdx.x & (RBL_WAVE - 1);
+    constexpr int WPB = 256 / RBL_WAVE;
+    for (long long r = (long long)blockIdx.x * WPB + ((int)threadIdx.x / RBL_WAVE); r < rows; r += (long long)gridDim.x * WPB) {
+        long long a = (long long)indptr[r] - base, b = (long long)indptr[r + 1] - base;
+        a = a < 0 ? 0 : (a > cnt ? cnt : a);
+        b = b < 0 ? 0 : (b > cnt ? cnt : b);
+        for (long long k = a + lane; k < b; k += RBL_WAVE) {
+            const long long c = (long long)indices[k];
+            const long long prev = k > a ? (long long)indices[k - 1] : -1;
+            if (c >= 0 && c < ds && c > prev) {
+                Xc[r * ldc + c] = values[k];
+            } else {
+                atomicAdd(&err[0], 1ull);
+                atomicMin(&err[1], (u64)(row0 + r));
+            }
+        }
+    }
+}
+
+template <typename V>
+int csr_expand_V(int index_type, void* Xc, long long ldc, long long rows, long long ds, const void* indptr, const void* indices,
+                 const void* values, long long base, long long cnt, long long row0, u64* err, int num_cu, hipStream_t s) {
+    long long grid = (rows + 3) / 4;
+    if (grid > (long long)num_cu * 32) grid = (long long)num_cu * 32;
+    if (index_type == RBL_INDEX_I64)
+        hipLaunchKernelGGL((k_csr_expand<V, long long>), dim3((unsigned)grid), dim3(256), 0, s, (V*)Xc, ldc, rows, ds,
+                           (const long long*)indptr, (const long long*)indices, (const V*)values, base, cnt, row0, err);
+    else
+        hipLaunchKernelGGL((k_csr_expand<V, int>), dim3((unsigned)grid), dim3(256), 0, s, (V*)Xc, ldc, rows, ds,
+                           (const int*)indptr, (const int*)indices, (const V*)values, base, cnt, row0, err);
+    RBL_HIP(hipGetLastError());
+    return RBL_OK;
+}
+
 template <typename S, typename T>
 int form_src_T(void* D, long long ld, long long row0, const void* X, long long ldx, const signed char* ysign, long long rows,
                long long ds, long long d, const double* mean, const double* inv, int num_cu, hipStream_t s, u64* ovf) {
@@ -718,6 +763,20 @@ int launch_src_row(int dtype, const void* X, int64_t ds, double* out, hipStream_
     else hipLaunchKernelGGL(k_src_row<double>, dim3(grid), dim3(256), 0, s, (const double*)X, (long long)ds, out);
     RBL_HIP(hipGetLastError());
     return RBL_OK;
+}
+
+int launch_csr_expand(int dtype, int index_type, void* Xc, int64_t ldc, int64_t rows, int64_t ds, const void* indptr,
+                      const void* indices, const void* values, int64_t base, int64_t cnt, int64_t row0, u64* err, int num_cu,
+                      hipStream_t s) {
+    if (rows <= 0) return RBL_OK;
+    const size_t esz = dtype == RBL_DTYPE_F16 ? 2 : dtype == RBL_DTYPE_F32 ? 4 : 8;
+    RBL_HIP(hipMemsetAsync(Xc, 0, (size_t)rows * (size_t)ldc * esz, s));   // the implicit entries: +0.0
+    if (cnt <= 0) return RBL_OK;
+    if (dtype == RBL_DTYPE_F16)
+        return csr_expand_V<unsigned short>(index_type, Xc, ldc, rows, ds, indptr, indices, values, base, cnt, row0, err, num_cu, s);
+    if (dtype == RBL_DTYPE_F32)
+        return csr_expand_V<unsigned int>(index_type, Xc, ldc, rows, ds, indptr, indices, values, base, cnt, row0, err, num_cu, s);
+    return csr_expand_V<u64>(index_type, Xc, ldc, rows, ds, indptr, indices, values, base, cnt, row0, err, num_cu, s);
 }
 
 int gemvt_slab_rows(int num_cu) { return num_cu * GEMVT_BLOCKS_PER_CU; }

@@ -205,6 +205,33 @@ enum { RBL_SCALE_NONE = 0, RBL_SCALE_FIT = 1, RBL_SCALE_APPLY = 2 };
 enum { RBL_DATA_ONES_COLUMN = 1 };                                   /* flags */
 int  rbl_set_data_from(rbl_solver* h, const void* X, int dtype, int mem, int64_t ldx /* in elements */,
                        const double* y /* n host doubles, +-1 */, int scaling, int flags);
+/* A sparse X in CSR form, expanded on the device: D itself stays dense.  indptr (n + 1 entries) and indices (nnz) are
+ * int32 or int64 (index_type, both the same), values (nnz) has element type dtype; all three live in the same memory kind
+ * mem and are naturally aligned.  With nnz == 0, indices and values may be NULL.  By definition the call equals
+ *     rbl_set_data_from(h, A, dtype, mem, ds, y, scaling, flags)
+ * on the dense expansion A of the same element type (ds = d, or d - 1 with RBL_DATA_ONES_COLUMN; implicit entries are
+ * +0.0, stored entries keep their bits, -0.0 and explicit zeros included): the same D bit for bit, the same scaling
+ * vectors, the same checks and the same messages - the fp16-overflow refusal names row, column and the value found in the
+ * source.  dtype, mem, scaling and flags mean what they mean there; borrowers: RBL_ERR_STATE; RBL_SCALE_FIT on a
+ * row-sharded handle: RBL_ERR_INVALID.  The arrays are read, never modified and never adopted.
+ *   Structure, checked on the host before anything is enqueued (a device indptr is copied to the host once, and that copy
+ * plans the chunks): indptr[0] == 0, indptr non-decreasing, indptr[n] == nnz; device arrays must be memory of the handle's
+ * device.  Anything else is RBL_ERR_INVALID.
+ *   Entries, checked by the expanding kernel before it stores: 0 <= column < ds, and the columns of a row strictly
+ * increasing (canonical CSR: duplicates and unsorted rows are refused, never summed).  An offending entry is not written;
+ * after the first pass over the source (the statistics pass under RBL_SCALE_FIT, else the forming pass) the call fails
+ * with RBL_ERR_INVALID, the message names the smallest offending row, the index and the rule it breaks, and the handle is
+ * left without data (a later valid call works).  No index reaches an address before its range test; int64 indices are
+ * compared in 64 bits; a row's entry range is clamped to [0, nnz).
+ *   Rows are processed in chunks whose DENSE size is 64 MB (RBL_UPLOAD_CHUNK_BYTES overrides it; whole blocks of 1024 rows
+ * under RBL_SCALE_FIT) for host and device sources alike: the staging buffer never grows to n x ds.  A host source is
+ * pinned in place and only indptr, indices and values cross PCIe (twice under RBL_SCALE_FIT), the next chunk's slices
+ * while the current chunk is expanded and consumed.  rbl_kernel_time(RBL_KERNEL_SRC_STATS / RBL_KERNEL_SRC_FORM) report
+ * the passes, expansion included.  The presence of this symbol is the capability probe (RBL_VERSION is unchanged). */
+enum { RBL_INDEX_I32 = 0, RBL_INDEX_I64 = 1 };
+int  rbl_set_data_csr(rbl_solver* h, const void* indptr /* n + 1 */, const void* indices /* nnz */,
+                      const void* values /* nnz, element type dtype */, int64_t nnz, int index_type,
+                      int dtype, int mem, const double* y, int scaling, int flags);
 /* the column means and scales RBL_SCALE_APPLY uses: d host doubles each (finite, scale > 0); both NULL clears them */
 int  rbl_set_scaling(rbl_solver* h, const double* mean, const double* scale);
 /* the vectors of RBL_SCALE_FIT / rbl_set_scaling (either may be NULL); *is_set = 0, means 0 and scales 1 when there are none */
