@@ -182,6 +182,7 @@ SIGNATURES = {
     "rbl_k_sort": (C.c_int, [C.c_int64, _P, _P, _P]),
     "rbl_k_sort32": (C.c_int, [C.c_int64, _P, C.c_uint32, _P, _P, C.POINTER(C.c_int)]),
     "rbl_zband_status": (C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "rbl_risk_path": (C.c_int, [_P, C.POINTER(C.c_int)]),
     "rbl_k_pav": (C.c_int, [C.c_int, C.c_int64, _P, C.c_double, _P, _P, _I64]),
     "rbl_k_pav_ehrm": (C.c_int, [C.c_int64, _P, _P, C.c_double, C.c_double, _P, C.c_int, _P, C.POINTER(C.c_int)]),
     "rbl_k_pav_seq": (C.c_int, [C.c_int, C.c_int64, _P, _P, C.c_double, C.c_double, C.c_int, _P, C.c_int, _P, _P, _P]),

@@ -693,6 +693,13 @@ class Solver:
         _lib.check(self.lib.rbl_zband_status(self._h, C.byref(st), C.byref(split)))
         return st.value, split.value
 
+    def risk_path(self):
+        """which kernels computed the handle's last risk (include/rbl.h: rbl_risk_path): 0 none yet, 1 mean (erm),
+        2 sort + dot, 3 banded select"""
+        p = C.c_int(0)
+        _lib.check(self.lib.rbl_risk_path(self._h, C.byref(p)))
+        return p.value
+
     def pending_reduce(self):
         m = C.c_int(0)
         _lib.check(self.lib.rbl_pending_reduce(self._h, C.byref(m)))

@@ -175,13 +175,18 @@ int zb_setup(rbl_solver* h) {
 // sum_i sigma_i * loss_(i) from n_total values of v (device) -> *out_dev
 int risk_from_v(rbl_solver* h, const double* v_all, double* out_dev) {
     hipStream_t s = h->stream;
-    if (h->cfg.weight_function == RBL_W_ERM)
+    if (h->cfg.weight_function == RBL_W_ERM) {
+        h->risk_path = 1;
         return launch_loss_sum(h->cfg.loss, h->nt, v_all, 1.0 / (double)h->nt, h->partials, out_dev, s, h->rs);
+    }
     h->keys_ready = false;   // the sort workspace is reused: keys left by rbl_phase_m are gone
     RBL_TRY(launch_loss_keys(h->nt, v_all, h->sw.keys[0], s, h->rs));   // (own labels: the losses are taken at r * v)
     // piecewise-constant weights: the band sums of the losses need a select, not a sort (zband.hip; exact for any v)
-    if (h->zb.enabled)
+    if (h->zb.enabled) {
+        h->risk_path = 3;
         return launch_zband_risk(h->cfg.loss, h->zb.cfg, h->nt, h->sw.keys[0], h->zb.st, h->zb.hist, h->zb.part, out_dev, s);
+    }
+    h->risk_path = 2;
     RBL_TRY(launch_radix_sort(h->sw, h->nt, false, s));
     return launch_sorted_loss_dot(h->cfg.loss, h->nt, h->sw.keys[0], h->sigma_a, h->partials, out_dev, s);
 }
@@ -888,6 +893,16 @@ int rbl_zband_status(rbl_solver* h, int* status, int* split) {
     const bool have = h->zb.pin && h->zb.seq > 0 && h->zb.pin[0] == h->zb.seq;
     if (status) *status = have ? h->zb.pin[1] : -1;
     if (split) *split = have ? h->zb.pin[2] : -1;
+    return RBL_OK;
+}
+
+// which kernels the handle's last risk went through (risk_from_v records it; read-only)
+int rbl_risk_path(rbl_solver* h, int* path) {
+    if (!h || !path) {
+        rbl_set_error("risk_path: NULL argument");
+        return RBL_ERR_INVALID;
+    }
+    *path = h->risk_path;
     return RBL_OK;
 }
 

@@ -446,6 +446,10 @@ int  rbl_zbd_apply(rbl_solver* h, int* status);
  * sharded path, which has no such pass.  It changes nothing in the iterate, but like every entry it is a call between
  * phases: a w-step computed ahead of time is discarded (w_prev is copied back, the stream is synchronised). */
 int  rbl_zband_status(rbl_solver* h, int* status, int* split);
+/* read-only (tests, diagnostics): which kernels computed this handle's last risk sum_i sigma_i loss_(i) (rbl_objective,
+ * rbl_risk_from_v, the objective of a step) - 0 none yet, 1 the mean (erm), 2 sort + dot with sigma, 3 the banded select
+ * (no sort; only after the handle's first rank-weighted z-step has classified sigma).  Nothing is dispatched on it. */
+int  rbl_risk_path(rbl_solver* h, int* path);
 
 /* RBL_BUF_Q is the whole exchange buffer [q (ld) | D^T lambda seed (ld) | ||z||^2 | primal^2 |
  * sum loss]; RBL_BUF_RED is its 2-double tail.  After rbl_phase_q and after rbl_phase_dual this

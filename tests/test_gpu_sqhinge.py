@@ -238,7 +238,7 @@ def test_fused_erm_at_every_instance_shape(R, storage, d, inst):
 
 # ------------------------------------------------------------------------------------------------ 5. objective, accuracy
 @pytest.mark.parametrize("wf,args,n", [("erm", None, 3001), ("superquantile", [0.5], 6000), ("aorr", [0.2, 0.8], 6000),
-                                       ("extremile", [2.0], 3001)], ids=["erm", "superquantile_banded", "aorr_banded", "extremile"])
+                                       ("extremile", [2.0], 3001)], ids=["erm", "superquantile_sorted", "aorr_sorted", "extremile"])
 def test_objective_and_accuracy(R, wf, args, n):
     from oracle import problems, weights
     acc_mod = __import__("admm_for_rank_based_loss_amd.src.util.calculate_acc", fromlist=["calculate_accuracy"])
@@ -254,8 +254,11 @@ def test_objective_and_accuracy(R, wf, args, n):
         v = (-y.reshape(-1, 1) * X) @ w
         F = sq.objective_from_v(sigma, v, w, l2_reg=0.02)
         got = o.get_arrogate_loss(w)
-        print(f"objective {wf} scale {scale}: {got:.15g} vs {F:.15g}")
+        print(f"objective {wf} scale {scale}: {got:.15g} vs {F:.15g} risk_path={o._s.risk_path()}")
         assert abs(got - F) <= 1e-12 * max(1.0, abs(F)), (wf, scale)
+        # an objective-only handle never runs a z-step, so its banded weights are never classified: the risk sorts
+        # (the select on the same families: tests/test_gpu_risk.py, path C)
+        assert o._s.risk_path() == (1 if wf == "erm" else 2)
         # the documented rule: predict +1 iff x.w >= 0, whatever the threshold
         want = float(np.mean(np.where(X @ w >= 0.0, 1, -1) == y.reshape(-1)))
         for thr in (0.5, 0.9):

@@ -351,9 +351,9 @@ class GpuRank:
         rec["status"] = self.s.zband_status()
 
 
-def run_sharded(rank_cls, fam, loss, n, world, banded, injections, timeout=120):
-    """injections: [(m0, rho, iter)].  Every rank thread runs all of them through ShardedADMM.step on its rows.
-    -> [per injection: dict(m, z = concatenated, recs = [per rank: banded / distributed / totals / mode / status])]"""
+def run_ranks(rank_cls, fam, loss, n, world, banded, body, timeout=120, what="sharded z-step"):
+    """`world` rank threads on the rows of one problem, each with its engine and a ShardedADMM on the hub's collectives
+    (set up: data, Gram matrix); every thread runs body(rk, drv) -> [per rank: what body returned]"""
     from admm_for_rank_based_loss_amd.dist import ShardedADMM
     hub, out, errs = Hub(world), [None] * world, []
 
@@ -363,23 +363,7 @@ def run_sharded(rank_cls, fam, loss, n, world, banded, injections, timeout=120):
             drv = make_thread_driver(ShardedADMM, hub, rk.sync)(rk.engine, world=world, rank=rank)
             drv.banded_z = bool(banded)
             rk.setup(drv)
-            e, res = rk.engine, []
-            plain = e.phase_m
-            seen = {}
-
-            def phase_m():                       # m as the z-step is about to see it (the device path reuses the buffer)
-                plain()
-                rk.sync()
-                seen["m"] = e.buf("m").cpu().numpy().copy()
-
-            e.phase_m = phase_m
-            for m0, rho, it in injections:
-                rk.set(m0[rk.lo:rk.lo + rk.cnt], rho, it)
-                drv.rec = dict(banded=None, distributed=False)
-                st = drv.step(False)
-                rk.report(st, drv.rec)
-                res.append(dict(m=seen["m"], z=rk.z(), rec=drv.rec))
-            out[rank] = res
+            out[rank] = body(rk, drv)
         except BaseException as ex:              # a dead thread must not leave the others in a barrier forever
             errs.append((rank, repr(ex)))
             hub.bar.abort()
@@ -392,10 +376,36 @@ def run_sharded(rank_cls, fam, loss, n, world, banded, injections, timeout=120):
     if any(t.is_alive() for t in ts):
         # ranks stuck in a collective or on the device keep their handles open: no further device work in this process
         import pytest
-        pytest.exit(f"sharded z-step hung: {fam} {loss} n={n} world={world} banded={banded} {errs}", returncode=1)
+        pytest.exit(f"{what} hung: {fam} {loss} n={n} world={world} banded={banded} {errs}", returncode=1)
     real = [e for e in errs if "BrokenBarrierError" not in e[1]] or errs
     assert not errs, real
     assert all(o is not None for o in out)
+    return out
+
+
+def run_sharded(rank_cls, fam, loss, n, world, banded, injections, timeout=120):
+    """injections: [(m0, rho, iter)].  Every rank thread runs all of them through ShardedADMM.step on its rows.
+    -> [per injection: dict(m, z = concatenated, recs = [per rank: banded / distributed / totals / mode / status])]"""
+    def body(rk, drv):
+        e, res = rk.engine, []
+        plain = e.phase_m
+        seen = {}
+
+        def phase_m():                       # m as the z-step is about to see it (the device path reuses the buffer)
+            plain()
+            rk.sync()
+            seen["m"] = e.buf("m").cpu().numpy().copy()
+
+        e.phase_m = phase_m
+        for m0, rho, it in injections:
+            rk.set(m0[rk.lo:rk.lo + rk.cnt], rho, it)
+            drv.rec = dict(banded=None, distributed=False)
+            st = drv.step(False)
+            rk.report(st, drv.rec)
+            res.append(dict(m=seen["m"], z=rk.z(), rec=drv.rec))
+        return res
+
+    out = run_ranks(rank_cls, fam, loss, n, world, banded, body, timeout)
     return [dict(m=np.concatenate([out[r][k]["m"] for r in range(world)]),
                  z=np.concatenate([out[r][k]["z"] for r in range(world)]),
                  recs=[out[r][k]["rec"] for r in range(world)]) for k in range(len(injections))]
