@@ -15,8 +15,10 @@ RBL_OK, RBL_ERR_INVALID, RBL_ERR_NO_DEVICE, RBL_ERR_HIP, RBL_ERR_STATE, RBL_ERR_
 LOSS = {"binary_cross_entropy": 0, "hinge": 1, "squared_hinge": 2}
 WEIGHT = {"erm": 0, "extremile": 1, "superquantile": 2, "esrm": 3, "aorr": 4, "aorr_dc": 5, "ehrm": 6}
 WSTEP_L1, WSTEP_L2, WSTEP_SMOOTH_L1 = 1, 2, 3
-STORAGE = {"f32": 0, "float32": 0, "f64": 1, "float64": 1, "fp16": 2, "float16": 2}
-_STORAGE_DTYPE = {0: np.float32, 1: np.float64, 2: np.float16}
+# "csr" (RBL_STORE_CSR): D stays sparse on the device - its entries as float64, so nothing is rounded
+STORAGE = {"f32": 0, "float32": 0, "f64": 1, "float64": 1, "fp16": 2, "float16": 2, "csr": 3}
+STORE_CSR = 3
+_STORAGE_DTYPE = {0: np.float32, 1: np.float64, 2: np.float16, 3: np.float64}
 # rbl_set_data_from: element type of the caller's X, where it lives, column scaling, flags
 DTYPE_F64, DTYPE_F32, DTYPE_F16 = 0, 1, 2
 SOURCE_DTYPE = {np.dtype(np.float64): DTYPE_F64, np.dtype(np.float32): DTYPE_F32, np.dtype(np.float16): DTYPE_F16}
@@ -30,7 +32,7 @@ INDEX_DTYPE = {np.dtype(np.int32): INDEX_I32, np.dtype(np.int64): INDEX_I64}
 
 def storage_ld(d, storage):
     """Row stride (elements) of the stored matrix: rows are whole 16-byte packets, zero padded - a multiple of 8 elements
-    with fp16 storage, of 4 with f32 / f64."""
+    with fp16 storage, of 4 with f32 / f64.  "csr" stores no rows; its vectors of length ld follow the f64 rule."""
     e = 8 if STORAGE[storage] == 2 else 4
     return (int(d) + e - 1) // e * e
 
@@ -191,6 +193,9 @@ SIGNATURES = {
     "rbl_k_gemv_multi": (C.c_int, [C.c_int, C.c_int64, C.c_int64, C.c_int, _P, _P, _P]),
     "rbl_k_gemvt_multi": (C.c_int, [C.c_int, C.c_int64, C.c_int64, C.c_int, _P, _P, _P]),
     "rbl_k_gram": (C.c_int, [C.c_int, C.c_int64, C.c_int64, _P, _P]),
+    "rbl_k_csr_gemv": (C.c_int, [C.c_int64, C.c_int64, _P, _P, _P, _P, _P]),
+    "rbl_k_csr_gemvt": (C.c_int, [C.c_int64, C.c_int64, _P, _P, _P, _P, _P]),
+    "rbl_k_csr_gram": (C.c_int, [C.c_int64, C.c_int64, _P, _P, _P, _P]),
     "rbl_k_wstep": (C.c_int, [C.c_int, C.c_int64, _P, _P, C.c_double, C.c_double, C.c_double, _P, C.c_double, _P,
                               C.POINTER(C.c_int)]),
     "rbl_k_wstep_pen": (C.c_int, [C.c_int64, _P, _P, C.c_double, _P, _P, _P, C.c_double, _P, C.POINTER(C.c_int),
@@ -381,6 +386,39 @@ def k_gram(D, storage="f32"):
     D = f64(D)
     G = np.empty((D.shape[1], D.shape[1]))
     check(load().rbl_k_gram(STORAGE[storage], D.shape[0], D.shape[1], ptr(D), ptr(G)))
+    return G
+
+
+def _csr_arrays(A):
+    """(n, d, indptr int64, indices int32, values float64) of a canonical scipy.sparse CSR matrix holding D itself"""
+    n, d = A.shape
+    return (n, d, np.ascontiguousarray(A.indptr, dtype=np.int64), np.ascontiguousarray(A.indices, dtype=np.int32),
+            np.ascontiguousarray(A.data, dtype=np.float64))
+
+
+def k_csr_gemv(A, w):
+    """v = A w through the sparse pass of storage "csr" (A: canonical scipy.sparse CSR, explicit zeros kept)"""
+    n, d, ip, ix, va = _csr_arrays(A)
+    w = f64(w).reshape(-1)
+    v = np.empty(n)
+    check(load().rbl_k_csr_gemv(n, d, ptr(ip), ptr(ix), ptr(va), ptr(w), ptr(v)))
+    return v
+
+
+def k_csr_gemvt(A, c):
+    """q = A^T c through the column form of storage "csr"; q has storage_ld(d, "csr") entries, the padding included"""
+    n, d, ip, ix, va = _csr_arrays(A)
+    c = f64(c).reshape(-1)
+    q = np.empty(storage_ld(d, "csr"))
+    check(load().rbl_k_csr_gemvt(n, d, ptr(ip), ptr(ix), ptr(va), ptr(c), ptr(q)))
+    return q
+
+
+def k_csr_gram(A):
+    """G = A^T A by the route of storage "csr": row chunks expanded through the fp64 MFMA kernel"""
+    n, d, ip, ix, va = _csr_arrays(A)
+    G = np.empty((d, d))
+    check(load().rbl_k_csr_gram(n, d, ptr(ip), ptr(ix), ptr(va), ptr(G)))
     return G
 
 

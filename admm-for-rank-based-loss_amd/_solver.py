@@ -292,6 +292,19 @@ def as_source(X, device=None):
     return Source(A.ctypes.data, dt, _lib.MEM_HOST, ldx, A.shape, A)
 
 
+def check_csr_storage(src, storage, standardize=False, what="X"):
+    """storage="csr" keeps D sparse: it takes a sparse matrix as it is and no standardisation (centring makes the
+    columns dense).  Raises ValueError - before any device call - for a dense ``src`` (a Source) or standardize=True."""
+    if storage != "csr":
+        return
+    if standardize:
+        raise ValueError('standardize=True with storage="csr": centring the columns makes D dense - scale the sparse '
+                         "matrix yourself (scaling without centring keeps it sparse) or use a dense storage type")
+    if not isinstance(src, CsrSource):
+        raise ValueError(f'storage="csr" needs a sparse {what} (scipy.sparse matrix / array or torch sparse tensor); '
+                         f"this one is dense - pass scipy.sparse.csr_matrix({what}), or use storage f32 / f64 / fp16")
+
+
 def as_scaling(mean, scale, d, ones_column=False):
     """(mean, scale) for d coordinates as float64; with ones_column the vectors of the d - 1 features are accepted and
     the unscaled column's (0, 1) appended"""
@@ -369,6 +382,8 @@ class Solver:
         if scaling not in _lib.SCALING:
             raise ValueError(f"scaling must be one of {sorted(_lib.SCALING)}")
         src = as_source(X, self.cfg.device)
+        if self.cfg.storage == _lib.STORE_CSR:
+            check_csr_storage(src, "csr", scaling != "none")
         y = _as_labels(y, src.shape[0])
         shape = (src.shape[0], src.shape[1] + (1 if ones_column else 0))
         if shape != (self.n, self.d):
@@ -384,6 +399,8 @@ class Solver:
 
     def set_data_f64(self, X, y):
         """the float64 host route (include/rbl.h: rbl_set_data): X is converted to a C-contiguous float64 host array"""
+        if self.cfg.storage == _lib.STORE_CSR:
+            raise ValueError('storage="csr" takes its data through set_data (a sparse X); set_data_f64 uploads a dense matrix')
         X = _as_matrix(X)
         y = _as_labels(y, X.shape[0])
         if X.shape != (self.n, self.d):

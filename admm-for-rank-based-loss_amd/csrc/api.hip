@@ -208,8 +208,17 @@ int validate(const rbl_config* c) {
             return RBL_ERR_INVALID;
         }
     }
-    if (c->storage != RBL_STORE_F32 && c->storage != RBL_STORE_F64 && c->storage != RBL_STORE_F16) {
-        rbl_set_error("storage must be RBL_STORE_F32, RBL_STORE_F64 or RBL_STORE_F16");
+    if (c->storage != RBL_STORE_F32 && c->storage != RBL_STORE_F64 && c->storage != RBL_STORE_F16 && c->storage != RBL_STORE_CSR) {
+        rbl_set_error("storage must be RBL_STORE_F32, RBL_STORE_F64, RBL_STORE_F16 or RBL_STORE_CSR");
+        return RBL_ERR_INVALID;
+    }
+    if (c->storage == RBL_STORE_CSR && c->n != c->n_total) {
+        rbl_set_error("RBL_STORE_CSR: row-sharded handles (n = %lld of n_total = %lld) are not supported - sparse storage runs "
+                      "on one device", (long long)c->n, (long long)c->n_total);
+        return RBL_ERR_INVALID;
+    }
+    if (c->storage == RBL_STORE_CSR && c->n > 0x7fffffffLL) {
+        rbl_set_error("RBL_STORE_CSR: n = %lld exceeds 2^31 - 1 (row indices are 32 bits)", (long long)c->n);
         return RBL_ERR_INVALID;
     }
     if (c->n_total >= (1LL << 32)) {
@@ -297,7 +306,14 @@ static int create_setup(rbl_solver* h, rbl_solver* owner = nullptr) {
     } else {
         h->shared = std::make_shared<DevArena>();
         const size_t dbytes = (size_t)(n > 0 ? n : 1) * ld * h->esz;
-        if (h->shared->alloc((unsigned char**)&h->D, dbytes) != RBL_OK) {
+        if (h->storage == RBL_STORE_CSR) {
+            // no n x ld matrix: D is the descriptor (stable - borrowers copy the pointer; read by the host alone, it only
+            // shares the arena's life); the entry buffers it points at are allocated by rbl_set_data_csr, once nnz is known
+            CsrStore* st = nullptr;
+            RBL_TRY(h->shared->pinned(&st, 1, hipHostMallocDefault));
+            memset(st, 0, sizeof(CsrStore));
+            h->D = st;
+        } else if (h->shared->alloc((unsigned char**)&h->D, dbytes) != RBL_OK) {
             rbl_set_error("hipMalloc of the %lld x %lld matrix (%zu bytes) failed: %s", (long long)n, (long long)ld, dbytes,
                           hipGetErrorString(hipGetLastError()));
             return RBL_ERR_NOMEM;
@@ -316,6 +332,8 @@ static int create_setup(rbl_solver* h, rbl_solver* owner = nullptr) {
     if (cfg->objective_only) RBL_TRY(mem.alloc(&h->red, 8));
     RBL_TRY(mem.alloc(&h->red2, 8));
     h->slab_bytes = (size_t)gemvt_slab_rows(h->num_cu) * ld * sizeof(double) * 2;
+    if (owner && h->storage == RBL_STORE_CSR)   // q = D^T c keeps one partial sum per segment in the handle's own slab
+        h->slab_bytes = std::max(h->slab_bytes, sizeof(double) * (size_t)((const CsrStore*)owner->D)->nseg);
     if (!cfg->objective_only) {
         size_t gb = owner ? 0 : gram_slab_bytes(ld, h->num_cu, n > 0 ? n : 1);   // (a borrower never forms G)
         if (gb > h->slab_bytes) h->slab_bytes = gb;

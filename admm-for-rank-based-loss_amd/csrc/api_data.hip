@@ -120,14 +120,21 @@ struct SrcPipe {
     // The CSR sibling: the same fn is handed dense rows.  Chunk by chunk the source's rows are expanded into the one
     // staging buffer (expansion and fn run on `stream`, in order) - a device source straight from the caller's arrays, a
     // host source from slices of the three arrays that the copy stream brings over one chunk ahead.
+    // `sparse` (RBL_STORE_CSR): nothing is expanded - the chunk's slices of indices / values (entries [base, base + cnt) of
+    // the source) go to sparse(indices, values, chunk, base, cnt) instead, and fn is not called.
+    typedef std::function<int(const void*, const void*, const CsrChunk&, int64_t, int64_t)> SparseFn;
     int pass_csr(const CsrView& v, int64_t n, int64_t chunk, int num_cu, const std::function<int(const void*, int64_t, int64_t)>& fn,
-                 double* ms = nullptr) {
+                 double* ms = nullptr, const SparseFn* sparse = nullptr) {
         return timed(ms, [&]() {
             int rc = RBL_OK;
             const int64_t nk = csr_chunk_count(n, chunk);
             for (int64_t k = 0; k < nk && rc == RBL_OK; ++k) {
                 const CsrChunk c = csr_chunk(v.ip, n, chunk, k);
                 const int b = (int)(k & 1);
+                if (v.mem == RBL_MEM_DEVICE && sparse) {
+                    rc = (*sparse)(v.indices, v.values, c, 0, v.nnz);
+                    continue;
+                }
                 if (v.mem == RBL_MEM_DEVICE) {
                     rc = launch_csr_expand(v.dtype, v.index_type, stage, v.ldc, c.rows, v.ds, (const unsigned char*)v.indptr + (size_t)c.r0 * v.isz,
                                            v.indices, v.values, 0, v.nnz, c.r0, v.err, num_cu, stream);
@@ -151,6 +158,11 @@ struct SrcPipe {
                     rbl_set_error("set_data_csr: upload failed: %s", hipGetErrorString(e));
                     rc = RBL_ERR_HIP;
                     break;
+                }
+                if (sparse) {
+                    rc = (*sparse)(idx[b], val[b], c, c.base, c.cnt);
+                    if (rc == RBL_OK && hipEventRecord(formed[b], stream) != hipSuccess) rc = RBL_ERR_HIP;
+                    continue;
                 }
                 rc = launch_csr_expand(v.dtype, v.index_type, stage, v.ldc, c.rows, v.ds, ipd[b], idx[b], val[b], c.base, c.cnt, c.r0,
                                        v.err, num_cu, stream);
@@ -416,6 +428,75 @@ static int set_data_from_impl(rbl_solver* h, const void* X, int dtype, int mem, 
     return RBL_OK;
 }
 
+// RBL_STORE_CSR: the CSR source *cs becomes the handle's D as it comes - no dense chunk, no forming kernel.  The chunks,
+// the pinned double-buffered copies of a host source and the verdict are those of the dense route; the entries go through
+// launch_csr_store (spmv.hip), then the column form is built on the device.
+static int set_data_csr_sparse(rbl_solver* h, const double* y, int64_t ds, int ones, CsrView* cs) {
+    const int64_t n = h->n, ld = h->ld;
+    CsrStore* st = (CsrStore*)h->D;
+    st->lanes = 0;
+    {
+        std::vector<signed char> ys((size_t)n);
+        for (int64_t i = 0; i < n; ++i) ys[(size_t)i] = y[i] > 0 ? 1 : -1;
+        RBL_HIP(hipMemcpy(h->ysign, ys.data(), (size_t)n, hipMemcpyHostToDevice));
+    }
+    // nothing reads the entry buffers while they are regrown: this handle's stream, and with borrowers (each on a stream
+    // of its own) the whole device.  A borrower's slab follows the new segment count at its next q pass (api_iter.hip)
+    if (h->shared.use_count() > 1) RBL_HIP(hipDeviceSynchronize());
+    RBL_HIP(hipStreamSynchronize(h->stream));
+    const bool columns = !h->cfg.objective_only;
+    RBL_TRY(csr_store_reserve(*h->shared, st, n, ld, cs->nnz + (ones ? n : 0), columns));
+    {   // D's own indptr: the source's, plus one slot per row with the column of ones
+        std::vector<int64_t> op((size_t)n + 1);
+        for (int64_t r = 0; r <= n; ++r) op[(size_t)r] = cs->ip[r] + (ones ? r : 0);
+        RBL_HIP(hipMemcpy(st->indptr, op.data(), sizeof(int64_t) * (size_t)(n + 1), hipMemcpyHostToDevice));
+    }
+    SrcPipe p;
+    p.stream = h->stream;
+    h->src_ms[0] = h->src_ms[1] = 0.0;
+    h->src_timed[0] = h->src_timed[1] = 0;
+    long long cb = 64LL << 20;
+    if (const char* e = getenv("RBL_UPLOAD_CHUNK_BYTES")) {   // test hook: several chunks at small sizes
+        const long long v = atoll(e);
+        if (v > 0) cb = v;
+    }
+    // rows of a chunk: as many as an average row's share of the source arrays fits the chunk size
+    const int64_t per_row = (int64_t)cs->isz + (int64_t)(cs->isz + cs->esz) * ((cs->nnz + n - 1) / n);
+    const int64_t chunk = csr_chunk_rows((int64_t)cb, per_row, n, 0);
+    RBL_TRY(p.tmp.alloc(&cs->err, 2));
+    if (cs->mem == RBL_MEM_HOST) {
+        const size_t cap = (size_t)csr_max_chunk_nnz(cs->ip, n, chunk);
+        p.pin(cs->indptr, (size_t)(n + 1) * cs->isz, 0);
+        p.pin(cs->indices, (size_t)cs->nnz * cs->isz, 1);
+        p.pin(cs->values, (size_t)cs->nnz * cs->esz, 2);
+        for (int b = 0; b < 2; ++b) {
+            RBL_TRY(p.tmp.alloc(&p.ipd[b], (size_t)(chunk + 1) * cs->isz));
+            RBL_TRY(p.tmp.alloc(&p.idx[b], cap * cs->isz));
+            RBL_TRY(p.tmp.alloc(&p.val[b], cap * cs->esz));
+        }
+        RBL_TRY(p.open_copy_stream());
+    }
+    const u64 pair0[2] = {0ull, ~0ull};   // {count, smallest position}
+    RBL_HIP(hipMemcpy(cs->err, pair0, sizeof(pair0), hipMemcpyHostToDevice));
+    const SrcPipe::SparseFn store = [&](const void* idx, const void* val, const CsrChunk& c, int64_t base, int64_t cnt) {
+        return launch_csr_store(cs->dtype, cs->index_type, st, c.rows, c.r0, ds, ones, idx, val, base, cnt, h->ysign, cs->err,
+                                h->num_cu, h->stream);
+    };
+    RBL_TRY(p.pass_csr(*cs, n, chunk, h->num_cu, nullptr, &h->src_ms[1], &store));
+    h->src_timed[1] = 1;
+    RBL_TRY(csr_verdict(*cs));
+    RBL_TRY(csr_store_finish(st, ld, columns, h->num_cu, h->stream));
+    return RBL_OK;   // (the slab of the q pass follows the segment count where the pass is launched: api_iter.hip)
+}
+
+// what a handle with RBL_STORE_CSR takes no part in (`who`: the entry point): RBL_ERR_INVALID, the handle without data
+static int refuse_on_csr(rbl_solver* h, const char* who, const char* why) {
+    if (h->storage != RBL_STORE_CSR) return RBL_OK;
+    if (!h->borrower) h->data_ready = false;
+    rbl_set_error("%s: %s", who, why);
+    return RBL_ERR_INVALID;
+}
+
 // labels are +1 / -1, nothing else (`who`: the entry point's name in the message)
 static int check_labels(const char* who, const double* y, int64_t n) {
     for (int64_t i = 0; i < n; ++i)
@@ -470,6 +551,8 @@ int rbl_set_data_from(rbl_solver* h, const void* X, int dtype, int mem, int64_t 
     RBL_ENTER(h);
     RBL_NOT_BORROWER(h, "set_data_from");
     RBL_TRY(check_source_args(h, "set_data_from", dtype, mem, scaling, flags));
+    RBL_TRY(refuse_on_csr(h, "set_data_from", "a dense source on a handle with RBL_STORE_CSR - sparse storage takes its data "
+                                               "through rbl_set_data_csr (a dense matrix belongs in storage f32 / f64 / fp16)"));
     const int64_t n = h->n, d = h->d;
     const int64_t ds = d - ((flags & RBL_DATA_ONES_COLUMN) ? 1 : 0);
     if (!X || !y || ds < 1 || ldx < ds) {
@@ -506,6 +589,17 @@ int rbl_set_data_csr(rbl_solver* h, const void* indptr, const void* indices, con
     }
     const int64_t n = h->n, d = h->d;
     const int64_t ds = d - ((flags & RBL_DATA_ONES_COLUMN) ? 1 : 0);
+    if (h->storage == RBL_STORE_CSR) {
+        if (scaling != RBL_SCALE_NONE)
+            return refuse_on_csr(h, "set_data_csr", "RBL_SCALE_FIT / RBL_SCALE_APPLY on a handle with RBL_STORE_CSR - centring the "
+                                                    "columns makes D dense; scale the source yourself or use a dense storage type");
+        if (nnz > 0x7fffffffLL || (nnz >= 0 && nnz + ((flags & RBL_DATA_ONES_COLUMN) ? n : 0) > 0x7fffffffLL)) {   // (n <= 2^31 - 1)
+            char why[256];
+            snprintf(why, sizeof(why), "nnz = %lld%s exceeds the 2^31 - 1 entries a handle with RBL_STORE_CSR holds", (long long)nnz,
+                     (flags & RBL_DATA_ONES_COLUMN) ? " (plus n for the column of ones)" : "");
+            return refuse_on_csr(h, "set_data_csr", why);
+        }
+    }
     if (!indptr || !y || ds < 1 || nnz < 0 || (nnz > 0 && (!indices || !values))) {
         rbl_set_error("set_data_csr: bad arguments (indptr %s, indices %s, values %s, y %s, nnz=%lld, source columns=%lld)",
                       indptr ? "given" : "NULL", indices ? "given" : "NULL", values ? "given" : "NULL", y ? "given" : "NULL",
@@ -562,7 +656,8 @@ int rbl_set_data_csr(rbl_solver* h, const void* indptr, const void* indices, con
     v.ip = ip.data();
     if (n > 0) {
         h->data_ready = false;   // a failed upload leaves the handle without data
-        RBL_TRY(set_data_from_impl(h, nullptr, dtype, mem, 0, y, scaling, ds, &v));
+        if (h->storage == RBL_STORE_CSR) RBL_TRY(set_data_csr_sparse(h, y, ds, (flags & RBL_DATA_ONES_COLUMN) ? 1 : 0, &v));
+        else RBL_TRY(set_data_from_impl(h, nullptr, dtype, mem, 0, y, scaling, ds, &v));
     }
     h->data_ready = true;
     h->gram_ready = h->gram_local_done = false;
@@ -612,6 +707,7 @@ int rbl_get_scaling(rbl_solver* h, double* mean, double* scale, int* is_set) {
 int rbl_synth_local(rbl_solver* h, uint64_t seed, double class_sep, double flip_y) {
     RBL_ENTER(h);
     RBL_NOT_BORROWER(h, "synth_local");
+    RBL_TRY(refuse_on_csr(h, "synth_local", "the synthetic generator writes a dense matrix - not available with RBL_STORE_CSR"));
     // positions of the 2 informative + 2 redundant columns, the 2x2 mixing matrix of the redundant ones, the four
     // clusters' covariance matrices A_k (entries uniform in (-1, 1)) and which hypercube vertex each cluster sits on
     // (a random permutation; cluster k belongs to class k % 2) - make_classification's geometry draws - from a small
@@ -673,6 +769,7 @@ int rbl_synth_local(rbl_solver* h, uint64_t seed, double class_sep, double flip_
 int rbl_synth_finish(rbl_solver* h) {
     RBL_ENTER(h);
     RBL_NOT_BORROWER(h, "synth_finish");
+    RBL_TRY(refuse_on_csr(h, "synth_finish", "the synthetic generator writes a dense matrix - not available with RBL_STORE_CSR"));
     // preprocessing.scale (load_data.py:115): (x - mean) / std with the population std
     const int64_t ld = h->ld;
     std::vector<double> st((size_t)ld * 4, 0.0);
@@ -708,6 +805,7 @@ int rbl_synth_finish(rbl_solver* h) {
 int rbl_generate_synthetic(rbl_solver* h, uint64_t seed, double class_sep, double flip_y) {
     RBL_ENTER(h);
     RBL_NOT_BORROWER(h, "generate_synthetic");
+    RBL_TRY(refuse_on_csr(h, "generate_synthetic", "the synthetic generator writes a dense matrix - not available with RBL_STORE_CSR"));
     if (h->nt != h->n) {
         rbl_set_error("generate_synthetic: sharded problem - use rbl_synth_local, sum RBL_BUF_COLSTATS, rbl_synth_finish");
         return RBL_ERR_STATE;
@@ -985,7 +1083,10 @@ int rbl_get_D(rbl_solver* h, double* out) {
     RBL_TRY(mem.alloc(&tmp, (size_t)chunk * d));
     for (int64_t r0 = 0; r0 < n; r0 += chunk) {
         const int64_t rows = n - r0 < chunk ? n - r0 : chunk;
-        RBL_TRY(launch_D_to_f64(h->storage, (const char*)h->D + (size_t)r0 * h->ld * h->esz, h->ld, rows, d, tmp, h->stream));
+        if (h->storage == RBL_STORE_CSR)   // implicit entries: +0.0
+            RBL_TRY(launch_csr_dense((const CsrStore*)h->D, r0, rows, d, tmp, h->num_cu, h->stream));
+        else
+            RBL_TRY(launch_D_to_f64(h->storage, (const char*)h->D + (size_t)r0 * h->ld * h->esz, h->ld, rows, d, tmp, h->stream));
         if (hipMemcpyAsync(out + r0 * d, tmp, sizeof(double) * rows * d, hipMemcpyDeviceToHost, h->stream) != hipSuccess ||
             hipStreamSynchronize(h->stream) != hipSuccess)
             return RBL_ERR_HIP;

@@ -3,6 +3,24 @@
 // what evaluates an iterate: objective, accuracy, fairness statistics, risk.
 #include "api_internal.h"
 
+// q = D^T c of a handle.  Sparse storage keeps one partial sum per segment in the handle's own slab: it is regrown here
+// when the data have more segments than it holds (a second upload on the owner of a borrowed D), and the launcher
+// refuses a slab that is too small.
+static int gemvt_h(rbl_solver* h, const double* c, double* q, hipEvent_t main_done = nullptr) {
+    if (h->storage == RBL_STORE_CSR) {
+        const size_t need = sizeof(double) * (size_t)((const CsrStore*)h->D)->nseg;
+        if (need > h->slab_bytes) {
+            unsigned char* grown = nullptr;   // the new one first: a failed allocation leaves the handle its slab
+            RBL_TRY(h->mem.alloc(&grown, need));
+            RBL_HIP(hipStreamSynchronize(h->stream));
+            h->mem.release(h->slab);
+            h->slab = (double*)grown;
+            h->slab_bytes = need;
+        }
+    }
+    return launch_gemvt(h->storage, h->D, h->n, h->ld, c, h->slab, q, h->num_cu, h->stream, main_done, h->slab_bytes / sizeof(double));
+}
+
 int ensure_v(rbl_solver* h) {
     if (h->v_valid) return RBL_OK;
     h->nd_launches += 1;
@@ -217,7 +235,7 @@ int zb_resolve(rbl_solver* h, bool* redone) {
             RBL_TRY(z_step_sorted(h, h->m, h->step_rho, false));
             if (q_done) {
                 RBL_TRY(launch_make_c(h->n, h->z, h->lam, h->step_rho, h->c, h->stream));
-                RBL_TRY(launch_gemvt(h->storage, h->D, h->n, h->ld, h->c, h->slab, h->q, h->num_cu, h->stream));
+                RBL_TRY(gemvt_h(h, h->c, h->q));
                 h->nd_launches += 1;
             }
             if (redone) *redone = true;
@@ -245,7 +263,7 @@ int zb_resolve(rbl_solver* h, bool* redone) {
     RBL_TRY(z_step_sorted(h, h->m, h->step_rho, false));
     if (q_done) {
         RBL_TRY(launch_make_c(h->n, h->z, h->lam, h->step_rho, h->c, h->stream));
-        RBL_TRY(launch_gemvt(h->storage, h->D, h->n, h->ld, h->c, h->slab, h->q, h->num_cu, h->stream));
+        RBL_TRY(gemvt_h(h, h->c, h->q));
         h->nd_launches += 1;
     }
     if (redone) *redone = true;
@@ -436,13 +454,12 @@ int rbl_phase_q(rbl_solver* h) {
         h->zb.c_ready = false;
         h->zb.q_done = h->zb.used;   // q of an unsettled sort-free z-step (zb_resolve redoes it with the z-step)
         h->s32.q_done = h->s32.used; // ... and of an unsettled 32-bit sort
-        RBL_TRY(launch_gemvt(h->storage, h->D, h->n, h->ld, h->c, h->slab, h->q, h->num_cu, h->stream,
-                             prof_now(h) ? h->kev[3] : nullptr));
+        RBL_TRY(gemvt_h(h, h->c, h->q, prof_now(h) ? h->kev[3] : nullptr));
         h->nd_launches += 1;
         if (prof_now(h)) h->kev_pending[1] = h->n > 0;
         if (h->fused_ok && !h->p_valid) {
             // D^T lambda seeds the d-space recurrence used to predict the primal residual
-            RBL_TRY(launch_gemvt(h->storage, h->D, h->n, h->ld, h->lam, h->slab, q_pinit(h), h->num_cu, h->stream));
+            RBL_TRY(gemvt_h(h, h->lam, q_pinit(h)));
             h->nd_launches += 1;
             h->p_pending = true;
         }

@@ -1,5 +1,6 @@
 // api_kernels.hip - the kernel-level entry points (rbl_k_*) of the parity tests: host buffers in, host buffers out.
 #include "api_internal.h"
+#include "csr_plan.h"
 
 // =================================================== kernel-level entry points (host buffers)
 // They run on the same workspace allocators as the solver handle (alloc_sort, alloc_pav, alloc_prefix, alloc_wstep).
@@ -33,6 +34,10 @@ int scratch_begin(Scratch& sc, int* num_cu) {
 
 // D (host fp64 n x d) -> device storage with ld padding
 int upload_matrix(Scratch& sc, int storage, int64_t n, int64_t d, const double* D, void** Dd, int64_t* ld_out) {
+    if (storage != RBL_STORE_F32 && storage != RBL_STORE_F64 && storage != RBL_STORE_F16) {   // (sparse: the rbl_k_csr_* entries)
+        rbl_set_error("kernel-level entry: storage must be RBL_STORE_F32, RBL_STORE_F64 or RBL_STORE_F16 (got %d)", storage);
+        return RBL_ERR_INVALID;
+    }
     const int64_t ld = rbl_storage_ld(storage, d);
     const size_t esz = rbl_storage_esz(storage);
     std::vector<unsigned char> host((size_t)n * ld * esz, 0);
@@ -43,6 +48,50 @@ int upload_matrix(Scratch& sc, int storage, int64_t n, int64_t d, const double* 
             else ((double*)host.data())[r * ld + j] = D[r * d + j];
         }
     RBL_TRY(sc.upload((unsigned char**)Dd, host.data(), host.size()));
+    *ld_out = ld;
+    return RBL_OK;
+}
+
+// A host CSR matrix that holds D itself -> a CsrStore in the call's arena, through the launches rbl_set_data_csr runs on a
+// handle with RBL_STORE_CSR: the forming kernel (labels -1, so -y x = x; one chunk), then the lane group and, with
+// `columns`, the column form and its segment table.
+int upload_csr(Scratch& sc, const char* who, int64_t n, int64_t d, const int64_t* indptr, const int32_t* indices, const double* values,
+               bool columns, int num_cu, CsrStore* st, int64_t* ld_out) {
+    if (n < 1 || n > 0x7fffffffLL || d < 1 || !indptr) {
+        rbl_set_error("%s: 1 <= n <= 2^31 - 1, d >= 1 and indptr are needed (n = %lld, d = %lld)", who, (long long)n, (long long)d);
+        return RBL_ERR_INVALID;
+    }
+    int64_t row = 0, got = 0;
+    const int64_t nnz = indptr[n];
+    if (nnz < 0 || nnz > 0x7fffffffLL || csr_check_indptr(indptr, n, nnz, &row, &got) != CSR_PLAN_OK || (nnz > 0 && (!indices || !values))) {
+        rbl_set_error("%s: indptr must start at 0, not decrease and end at nnz <= 2^31 - 1 (indices / values given)", who);
+        return RBL_ERR_INVALID;
+    }
+    const int64_t ld = rbl_storage_ld(RBL_STORE_CSR, d);
+    memset(st, 0, sizeof(CsrStore));
+    RBL_TRY(csr_store_reserve(sc.mem, st, n, ld, nnz, columns));
+    RBL_HIP(hipMemcpy(st->indptr, indptr, sizeof(int64_t) * (size_t)(n + 1), hipMemcpyHostToDevice));
+    int32_t* di = nullptr;
+    double* dv = nullptr;
+    signed char* ys = nullptr;
+    u64* err = nullptr;
+    RBL_TRY(sc.upload(&di, indices, (size_t)nnz));
+    RBL_TRY(sc.upload(&dv, values, (size_t)nnz));
+    RBL_TRY(sc.mem.alloc(&ys, (size_t)n));
+    RBL_TRY(sc.mem.alloc(&err, 2));
+    const u64 pair0[2] = {0ull, ~0ull};
+    RBL_HIP(hipMemcpy(err, pair0, sizeof(pair0), hipMemcpyHostToDevice));
+    RBL_HIP(hipMemsetAsync(ys, 0xff, (size_t)n, sc.s));   // y = -1
+    RBL_TRY(launch_csr_store(RBL_DTYPE_F64, RBL_INDEX_I32, st, n, 0, d, 0, di, dv, 0, nnz, ys, err, num_cu, sc.s));
+    u64 bad[2] = {0ull, 0ull};
+    RBL_HIP(hipMemcpyAsync(bad, err, sizeof(bad), hipMemcpyDeviceToHost, sc.s));
+    RBL_HIP(hipStreamSynchronize(sc.s));
+    if (bad[0] > 0) {
+        rbl_set_error("%s: %llu entries refused, first in row %llu - the columns of a row must lie in [0, d) and increase strictly",
+                      who, bad[0], bad[1]);
+        return RBL_ERR_INVALID;
+    }
+    RBL_TRY(csr_store_finish(st, ld, columns, num_cu, sc.s));
     *ld_out = ld;
     return RBL_OK;
 }
@@ -352,6 +401,65 @@ int rbl_k_gram(int storage, int64_t n, int64_t d, const double* D, double* G) {
     RBL_TRY(sc.mem.alloc((unsigned char**)&slab, gram_slab_bytes(ld, num_cu, n > 0 ? n : 1)));
     RBL_TRY(sc.mem.alloc(&dG, (size_t)ld * ld));
     RBL_TRY(launch_gram(storage, Dd, n, ld, d, slab, dG, num_cu, sc.s));
+    std::vector<double> hG((size_t)ld * ld);
+    RBL_HIP(hipMemcpyAsync(hG.data(), dG, sizeof(double) * ld * ld, hipMemcpyDeviceToHost, sc.s));
+    RBL_HIP(hipStreamSynchronize(sc.s));
+    for (int64_t i = 0; i < d; ++i)
+        for (int64_t j = 0; j < d; ++j) G[i * d + j] = hG[(size_t)(i * ld + j)];
+    return RBL_OK;
+}
+
+int rbl_k_csr_gemv(int64_t n, int64_t d, const int64_t* indptr, const int32_t* indices, const double* values, const double* w,
+                   double* v) {
+    Scratch sc;
+    int num_cu = 256;
+    RBL_TRY(scratch_begin(sc, &num_cu));
+    if (n <= 0) return RBL_OK;
+    CsrStore st;
+    int64_t ld = 0;
+    RBL_TRY(upload_csr(sc, "rbl_k_csr_gemv", n, d, indptr, indices, values, false, num_cu, &st, &ld));
+    std::vector<double> wp((size_t)ld, 0.0);
+    for (int64_t j = 0; j < d; ++j) wp[(size_t)j] = w[j];
+    double *dw = nullptr, *dv = nullptr;
+    RBL_TRY(sc.upload(&dw, wp.data(), (size_t)ld));
+    RBL_TRY(sc.mem.alloc(&dv, (size_t)n));
+    RBL_TRY(launch_gemv(RBL_STORE_CSR, &st, n, ld, dw, dv, num_cu, sc.s));
+    RBL_HIP(hipMemcpyAsync(v, dv, sizeof(double) * n, hipMemcpyDeviceToHost, sc.s));
+    RBL_HIP(hipStreamSynchronize(sc.s));
+    return RBL_OK;
+}
+
+// q has ld = storage_ld(d) entries here: the padding [d, ld) is part of what the pass writes (+0.0)
+int rbl_k_csr_gemvt(int64_t n, int64_t d, const int64_t* indptr, const int32_t* indices, const double* values, const double* c,
+                    double* q) {
+    Scratch sc;
+    int num_cu = 256;
+    RBL_TRY(scratch_begin(sc, &num_cu));
+    CsrStore st;
+    int64_t ld = 0;
+    RBL_TRY(upload_csr(sc, "rbl_k_csr_gemvt", n, d, indptr, indices, values, true, num_cu, &st, &ld));
+    double *dc = nullptr, *part = nullptr, *dq = nullptr;
+    RBL_TRY(sc.upload(&dc, c, (size_t)n));
+    RBL_TRY(sc.mem.alloc(&part, (size_t)st.nseg));
+    RBL_TRY(sc.mem.alloc(&dq, (size_t)ld));
+    RBL_HIP(hipMemsetAsync(dq, 0xff, sizeof(double) * ld, sc.s));   // (NaN: every entry must be written by the pass)
+    RBL_TRY(launch_gemvt(RBL_STORE_CSR, &st, n, ld, dc, part, dq, num_cu, sc.s, nullptr, (size_t)st.nseg));
+    RBL_HIP(hipMemcpyAsync(q, dq, sizeof(double) * ld, hipMemcpyDeviceToHost, sc.s));
+    RBL_HIP(hipStreamSynchronize(sc.s));
+    return RBL_OK;
+}
+
+int rbl_k_csr_gram(int64_t n, int64_t d, const int64_t* indptr, const int32_t* indices, const double* values, double* G) {
+    Scratch sc;
+    int num_cu = 256;
+    RBL_TRY(scratch_begin(sc, &num_cu));
+    CsrStore st;
+    int64_t ld = 0;
+    RBL_TRY(upload_csr(sc, "rbl_k_csr_gram", n, d, indptr, indices, values, false, num_cu, &st, &ld));
+    double *slab = nullptr, *dG = nullptr;
+    RBL_TRY(sc.mem.alloc((unsigned char**)&slab, gram_slab_bytes(ld, num_cu, n)));
+    RBL_TRY(sc.mem.alloc(&dG, (size_t)ld * ld));
+    RBL_TRY(launch_gram(RBL_STORE_CSR, &st, n, ld, d, slab, dG, num_cu, sc.s));
     std::vector<double> hG((size_t)ld * ld);
     RBL_HIP(hipMemcpyAsync(hG.data(), dG, sizeof(double) * ld * ld, hipMemcpyDeviceToHost, sc.s));
     RBL_HIP(hipStreamSynchronize(sc.s));

@@ -177,8 +177,10 @@ int launch_gemv(int storage, const void* D, int64_t n, int64_t ld, const double*
                 int num_cu, hipStream_t s);
 // q = D^T c : partial column sums go to slab (gemvt_slab_rows() x ld doubles), then q
 int gemvt_slab_rows(int num_cu);
+// RBL_STORE_CSR: the slab holds one partial sum per segment; slab_doubles is what it has room for (a slab too small is
+// RBL_ERR_STATE, never a write past its end)
 int launch_gemvt(int storage, const void* D, int64_t n, int64_t ld, const double* c, double* slab,
-                 double* q, int num_cu, hipStream_t s, hipEvent_t main_done = nullptr);
+                 double* q, int num_cu, hipStream_t s, hipEvent_t main_done = nullptr, size_t slab_doubles = 0);
 int launch_D_to_f64(int storage, const void* D, int64_t ld, int64_t n, int64_t d, double* out,
                     hipStream_t s);
 // column sums / sums of squares (slab-reduced, deterministic) and in-place standardisation
@@ -459,6 +461,46 @@ int launch_ridge_eig(const double* G, const double* Vt, const double* V, const d
 size_t gram_slab_bytes(int64_t d, int num_cu, int64_t n);
 int launch_gram(int storage, const void* D, int64_t n, int64_t ld, int64_t d, double* slab, double* G,
                 int num_cu, hipStream_t s);
+
+// ---- spmv.hip: RBL_STORE_CSR - D as its non-zero entries --------------------------------------------------------
+// The descriptor a handle's D points at (launch_gemv / launch_gemvt / launch_gram take it as `D` with storage
+// RBL_STORE_CSR).  Host memory owned by the arena that owns the buffers (only the host reads it); it never moves:
+// borrowers copy the pointer.  Row form: indptr (n + 1), col / val (nnz).  Column form (NULL on an objective-only handle): colptr (ld + 1),
+// row / cval (nnz) - every column's entries in ascending row order - and segptr (ld + 1, csc_plan.h).
+struct CsrStore {
+    int64_t* indptr;
+    int* col;
+    double* val;
+    int64_t* colptr;
+    int* row;
+    double* cval;
+    int64_t* segptr;
+    int64_t n, nnz, nseg, cap;   // cap: entries the entry buffers were allocated for
+    int lanes;                   // lanes per row of v = D w (csr_lanes), 0 = no data yet
+    int seg;                     // entries per segment of q = D^T c
+};
+int csr_lanes(int64_t nnz, int64_t n);   // 4 .. 64, from the average row length alone
+// (re)allocates the buffers for n rows / nnz entries in mem; the caller then fills indptr and runs launch_csr_store over
+// the source's chunks
+int csr_store_reserve(DevArena& mem, CsrStore* st, int64_t n, int64_t ld, int64_t nnz, bool columns);
+// rows [row0, row0 + rows): the entries at indptr[R] - (ones ? R : 0) - base of indices / values (cnt of them, types as
+// launch_csr_expand) are checked (err as there) and stored as (column, -y_R x); ones: the slot (d - 1 = ds, -y_R) as well.
+// ysign: the signs of all n rows
+int launch_csr_store(int dtype, int index_type, const CsrStore* st, int64_t rows, int64_t row0, int64_t ds, int ones,
+                     const void* indices, const void* values, int64_t base, int64_t cnt, const signed char* ysign, u64* err,
+                     int num_cu, hipStream_t s);
+// after the last chunk: the lane group, and with columns the column form and its segment table; returns with s idle
+int csr_store_finish(CsrStore* st, int64_t ld, bool columns, int num_cu, hipStream_t s);
+int launch_csr_gemv(const CsrStore* st, int64_t n, const double* w, double* v, int num_cu, hipStream_t s);
+// part: the segments' partial sums, part_doubles >= st->nseg of them (fewer: RBL_ERR_STATE before anything is launched)
+int launch_csr_gemvt(const CsrStore* st, int64_t ld, const double* c, double* part, size_t part_doubles, double* q, int num_cu,
+                     hipStream_t s, hipEvent_t main_done);
+// rows [row0, row0 + rows) as dense fp64 rows of stride ldo (implicit entries +0.0)
+int launch_csr_dense(const CsrStore* st, int64_t row0, int64_t rows, int64_t ldo, double* out, int num_cu, hipStream_t s);
+// G = D^T D: chunks of csr_gram_chunk_rows(n, ld) rows expanded into a transient staging buffer (<= 256 MB), each through
+// launch_gram(RBL_STORE_F64), added in chunk order; returns with s idle
+int64_t csr_gram_chunk_rows(int64_t n, int64_t ld);
+int launch_csr_gram(const CsrStore* st, int64_t n, int64_t ld, int64_t d, double* slab, double* G, int num_cu, hipStream_t s);
 
 // ---- synth.hip --------------------------------------------------------------------------
 int launch_synth(int storage, void* D, int64_t n, int64_t ld, int64_t d, int64_t row_offset, u64 seed,

@@ -784,17 +784,20 @@ int gemvt_slab_rows(int num_cu) { return num_cu * GEMVT_BLOCKS_PER_CU; }
 int launch_gemv(int storage, const void* D, int64_t n, int64_t ld, const double* w, double* v, int num_cu,
                 hipStream_t s) {
     if (n <= 0) return RBL_OK;
+    if (storage == RBL_STORE_CSR) return launch_csr_gemv((const CsrStore*)D, n, w, v, num_cu, s);   // spmv.hip
     if (storage == RBL_STORE_F32) return gemv_T<float>((const float*)D, n, ld, w, v, num_cu, s);
     if (storage == RBL_STORE_F16) return gemv_T<rbl_half>((const rbl_half*)D, n, ld, w, v, num_cu, s);
     return gemv_T<double>((const double*)D, n, ld, w, v, num_cu, s);
 }
 
 int launch_gemvt(int storage, const void* D, int64_t n, int64_t ld, const double* c, double* slab, double* q,
-                 int num_cu, hipStream_t s, hipEvent_t main_done) {
+                 int num_cu, hipStream_t s, hipEvent_t main_done, size_t slab_doubles) {
     if (n <= 0) {
         RBL_HIP(hipMemsetAsync(q, 0, sizeof(double) * ld, s));
         return RBL_OK;
     }
+    // spmv.hip: the slab holds the segments' partial sums
+    if (storage == RBL_STORE_CSR) return launch_csr_gemvt((const CsrStore*)D, ld, c, slab, slab_doubles, q, num_cu, s, main_done);
     if (sweep_v_supported(storage, ld)) return launch_sweep_q(storage, D, n, ld, c, slab, q, num_cu, s, main_done);
     int nb = gemvt_blocks(num_cu, n);
     if (storage == RBL_STORE_F32)
@@ -830,6 +833,10 @@ int launch_colstats(int storage, const void* D, int64_t n, int64_t ld, double* s
 int launch_D_to_f64(int storage, const void* D, int64_t ld, int64_t n, int64_t d, double* out, hipStream_t s) {
     long long total = n * d;
     if (total <= 0) return RBL_OK;
+    if (storage == RBL_STORE_CSR) {   // D is a descriptor, not rows: rbl_get_D expands chunks with launch_csr_dense
+        rbl_set_error("D_to_f64: not available for RBL_STORE_CSR");
+        return RBL_ERR_INVALID;
+    }
     unsigned grid = (unsigned)((total + 255) / 256);
     if (storage == RBL_STORE_F32)
         hipLaunchKernelGGL(k_D_to_f64<float>, dim3(grid), dim3(256), 0, s, (const float*)D, (long long)ld,

@@ -687,6 +687,7 @@ int launch_T(const T* D, long long n, long long ld, const double* w, const doubl
 }  // namespace
 
 bool sweep_erm_supported(int storage, int64_t ld) {
+    if (storage == RBL_STORE_CSR) return false;   // sparse storage runs the two-pass iteration (spmv.hip)
     const int64_t PK = ld / rbl_storage_packet(storage);
     // wave-per-row kernel up to 4 (fp32) / 8 (fp64) passes of 64 packets, workgroup-per-row
     // kernel up to 8 packets per thread: d <= 16384 (fp32) / 8192 (fp64).  fp16: 4 packets per thread (w in LDS is
@@ -767,6 +768,7 @@ int launch_v_T(const T* D, long long n, long long ld, const double* w, const dou
 // rank-weighted problems: v = D w, lambda += rho (z - v), red[0] = sum (z - v)^2 in one pass
 // (replaces k_gemv + k_dual when the row width fits the wave-per-row kernel)
 bool sweep_v_supported(int storage, int64_t ld) {
+    if (storage == RBL_STORE_CSR) return false;   // sparse storage: launch_gemv / launch_gemvt dispatch to spmv.hip
     const int64_t PK = ld / rbl_storage_packet(storage);   // (fp16: 256 < ld <= 4096)
     return PK > 32 && PK <= 512;
 }

@@ -453,6 +453,7 @@ int launch_qm_T(const T* D, long long n, long long ld, const MultiQ& a, double* 
 // registers that 8 packets are with fp32 storage, so the shared range ends at the same width in ELEMENTS and begins, as
 // everywhere, above 32 packets per row (ld > 256); wider fp16 rows run each member's own passes
 bool sweep_multi_supported(int storage, int64_t ld) {
+    if (storage == RBL_STORE_CSR) return false;   // no shared multi-column sparse passes: every member runs its own
     if (storage == RBL_STORE_F16) return sweep_v_supported(storage, ld) && ld <= 2048;
     return sweep_v_supported(storage, ld);
 }

@@ -7,7 +7,8 @@ the reference (citations: reference ``src/optim/algorithms.py``), so ``run_SRM.p
 directory on ``PYTHONPATH``.  State (w, z, lambda) lives on the GPU; the ``w`` / ``z`` /
 ``lagrangian`` attributes download it on access.  All arithmetic is done by librbl.so
 (include/rbl.h); this file is host glue.  Extra keyword arguments (after the reference's
-own): ``storage`` ("f32" default | "f64" strict | "fp16" half the bytes of D, data rounded once to float16), ``device``;
+own): ``storage`` ("f32" default | "f64" strict | "fp16" half the bytes of D, data rounded once to float16 | "csr" a sparse
+X stays sparse on the device: float64 entries, sparse passes, no standardize), ``device``;
 ``l1_weights`` / ``l2_weights`` (a scalar or one value per feature: the regulariser becomes
 1/2 sum_j (l1_j |w_j| + l2_j w_j^2) - elastic net, penalty factors, unpenalised coordinates) and ``fit_intercept``
 (an unpenalised bias: the library forms the column -y * 1 itself, no host copy of X; the solver has d + 1 coordinates,
@@ -53,6 +54,7 @@ class Optimizer:
         if weight_function == "ehrm" and B is None:
             raise ValueError("ehrm needs the reference point B")
         src = _solver.as_source(X, device)              # X in its own type, where it lives: no host copy
+        _solver.check_csr_storage(src, storage, standardize)          # storage="csr": a sparse X, no standardisation
         # per-coordinate penalties / intercept: validated on the host before any device call; None = the scalar path
         pen = _solver.resolve_penalty(src.shape[1], l1_reg, l2_reg, l1_weights, l2_weights, fit_intercept)
         self.fit_intercept = bool(fit_intercept)
@@ -521,6 +523,7 @@ class OneVsRest:
         W = self._current_W()
         if d != W.shape[0]:
             raise ValueError(f"X_test has {d} features, the model {W.shape[0]}")
+        _solver.check_csr_storage(Xt, self._storage, what="X_test")
         if self._test is None or self._test[1] is not X_test:
             if self._test is not None:
                 self._test[0].close()

@@ -87,6 +87,7 @@ class rankbasedObjective:
             # X as it is (_solver.as_source).  scaling: (mean, scale) of a solver (its scale_mean_ / scale_scale_, or
             # Solver.get_scaling()) - this matrix is standardised with them on the device; _ones_column: the intercept's
             Xm = _solver.as_source(X, device)
+            _solver.check_csr_storage(Xm, storage, scaling is not None, what="X_test")
             self.n, self.d = Xm.shape[0], Xm.shape[1] + (1 if _ones_column else 0)
             # _share_data: another objective on the same (X, y) whose device matrix this one borrows (ADMMgroup)
             share = None if _share_data is None else _share_data._s

@@ -56,6 +56,12 @@ enum { RBL_WSTEP_L1 = 1, RBL_WSTEP_L2 = 2, RBL_WSTEP_SMOOTH_L1 = 3 };
  * to a multiple of 8 elements (f32 / f64: of 4), the upload rounds to nearest even once, and a finite entry that does not
  * fit the format (|x| >= 65520) is rejected by rbl_set_data / rbl_set_data_from (RBL_ERR_INVALID), never clipped. */
 enum { RBL_STORE_F32 = 0, RBL_STORE_F64 = 1, RBL_STORE_F16 = 2 };
+/* RBL_STORE_CSR: D lives on the device as its non-zero entries only (row form: int64 indptr, int32 columns, fp64 values
+ * -y_r * x widened exactly from the source; column form of the same entries for q = D^T c: 24 bytes per entry in all, no
+ * n x ld matrix is ever allocated).  The data come through rbl_set_data_csr alone, with RBL_SCALE_NONE; at most 2^31 - 1
+ * entries (the column of ones included); row-sharded handles (n != n_total) are refused by rbl_create.  ld follows the
+ * f64 rule.  The iteration runs the two-pass form (fused = 0) on sparse passes; see DESIGN.md, "Sparse storage". */
+enum { RBL_STORE_CSR = 3 };
 
 /* Constructor arguments of Optimizer.__init__ (src/optim/algorithms.py:20-75). */
 typedef struct rbl_config {
@@ -228,6 +234,13 @@ int  rbl_set_data_from(rbl_solver* h, const void* X, int dtype, int mem, int64_t
  * pinned in place and only indptr, indices and values cross PCIe (twice under RBL_SCALE_FIT), the next chunk's slices
  * while the current chunk is expanded and consumed.  rbl_kernel_time(RBL_KERNEL_SRC_STATS / RBL_KERNEL_SRC_FORM) report
  * the passes, expansion included.  The presence of this symbol is the capability probe (RBL_VERSION is unchanged). */
+/* On a handle with storage RBL_STORE_CSR nothing is expanded: the entries are checked by the same rules (same messages)
+ * and stored as they come, value -y_r * x, explicit zeros and -0.0 included; RBL_DATA_ONES_COLUMN appends the entry
+ * (d - 1, -y_r) to every row.  Refused with RBL_ERR_INVALID (the handle is left without data): RBL_SCALE_FIT / APPLY
+ * (centring makes D dense), nnz (plus n with the column of ones) above 2^31 - 1.  rbl_set_data / rbl_set_data_from and
+ * the generator are RBL_ERR_INVALID there.  A second upload regrows the entry buffers under the handles that borrow the
+ * data (the device is waited for first; their D pointer stays); after an upload that failed they answer RBL_ERR_STATE
+ * until a valid one. */
 enum { RBL_INDEX_I32 = 0, RBL_INDEX_I64 = 1 };
 int  rbl_set_data_csr(rbl_solver* h, const void* indptr /* n + 1 */, const void* indices /* nnz */,
                       const void* values /* nnz, element type dtype */, int64_t nnz, int index_type,
@@ -527,6 +540,14 @@ int  rbl_k_gemv_multi(int storage, int64_t n, int64_t d, int k, const double* D,
 int  rbl_k_gemvt_multi(int storage, int64_t n, int64_t d, int k, const double* D, const double* C, double* Q);
 /* G = D^T D (MFMA f64) */
 int  rbl_k_gram(int storage, int64_t n, int64_t d, const double* D, double* G);
+/* the passes of RBL_STORE_CSR on a host CSR matrix that holds D itself (no label sign): int64 indptr (n + 1), int32
+ * indices and fp64 values (indptr[n] entries each, canonical rows).  They run the launches a handle runs: the forming
+ * kernel, the column-form build, the pass.  q has ld entries (d rounded up to a multiple of 4): the padding is written too. */
+int  rbl_k_csr_gemv(int64_t n, int64_t d, const int64_t* indptr, const int32_t* indices, const double* values,
+                    const double* w, double* v);
+int  rbl_k_csr_gemvt(int64_t n, int64_t d, const int64_t* indptr, const int32_t* indices, const double* values,
+                     const double* c, double* q);
+int  rbl_k_csr_gram(int64_t n, int64_t d, const int64_t* indptr, const int32_t* indices, const double* values, double* G);
 /* w-steps in Gram space: lasso / ridge / smoothed-l1 */
 int  rbl_k_wstep(int wstep, int64_t d, const double* G, const double* q, double rho, double reg,
                  double smooth_t, const double* w0, double tol, double* w_out, int* iters);
