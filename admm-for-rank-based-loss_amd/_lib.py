@@ -192,6 +192,12 @@ SIGNATURES = {
     "rbl_k_gemvt": (C.c_int, [C.c_int, C.c_int64, C.c_int64, _P, _P, _P]),
     "rbl_k_gemv_multi": (C.c_int, [C.c_int, C.c_int64, C.c_int64, C.c_int, _P, _P, _P]),
     "rbl_k_gemvt_multi": (C.c_int, [C.c_int, C.c_int64, C.c_int64, C.c_int, _P, _P, _P]),
+    "rbl_k_sweep_erm": (C.c_int, [C.c_int, C.c_int, C.c_int64, C.c_int64, _P, _P, _P, _P, C.c_double, C.c_double, C.c_double,
+                                  C.c_int, C.c_int, _P, _P, _P, _P, _D, _D, _P]),
+    "rbl_k_sweep_v": (C.c_int, [C.c_int, C.c_int64, C.c_int64, _P, _P, _P, _P, C.c_double, C.c_int, _P, _P, _D, _P]),
+    "rbl_k_sweep_q": (C.c_int, [C.c_int, C.c_int64, C.c_int64, _P, _P, C.c_int, _P, _P]),
+    "rbl_k_sweep_v_multi": (C.c_int, [C.c_int, C.c_int64, C.c_int64, C.c_int, _P, _P, _P, _P, _P, C.c_int, _P, _P, _P, _P]),
+    "rbl_k_sweep_q_multi": (C.c_int, [C.c_int, C.c_int64, C.c_int64, C.c_int, _P, _P, C.c_int, _P, _P]),
     "rbl_k_gram": (C.c_int, [C.c_int, C.c_int64, C.c_int64, _P, _P]),
     "rbl_k_csr_gemv": (C.c_int, [C.c_int64, C.c_int64, _P, _P, _P, _P, _P]),
     "rbl_k_csr_gemvt": (C.c_int, [C.c_int64, C.c_int64, _P, _P, _P, _P, _P]),
@@ -380,6 +386,80 @@ def k_gemvt_multi(D, Cm, storage="f32"):
     Q = np.empty((Cm.shape[0], D.shape[1]))
     check(load().rbl_k_gemvt_multi(STORAGE[storage], D.shape[0], D.shape[1], Cm.shape[0], ptr(D), ptr(Cm), ptr(Q)))
     return Q
+
+
+MULTI_KMAX = 4
+SWEEP_KIND = {0: "wave", 1: "wide"}
+
+
+def _instance(a):
+    """(kind, P | PT, R, S, blocks) of the kernel instance a rbl_k_sweep_* call ran"""
+    return (SWEEP_KIND[int(a[0])], int(a[1]), int(a[2]), int(a[3]), int(a[4]))
+
+
+def k_sweep_erm(D, w, z_old, lam, sigma0, rho, rho_next, loss, storage="f32", num_cu=1, want_v=True):
+    """The single-sweep pass on prescribed inputs with the grid of `num_cu` compute units (include/rbl.h:
+    rbl_k_sweep_erm).  Returns a dict: lam, v (all NaN when want_v is False), z, q, primal2, zz, instance."""
+    D, w, z_old, lam = f64(D), f64(w).reshape(-1), f64(z_old).reshape(-1), f64(lam).reshape(-1)
+    n, d = D.shape
+    lam_out, v, z_new, q = np.empty(n), np.empty(n), np.empty(n), np.empty(d)
+    p2, zz = C.c_double(0.0), C.c_double(0.0)
+    inst = np.zeros(5, dtype=np.int32)
+    check(load().rbl_k_sweep_erm(STORAGE[storage], LOSS[loss], n, d, ptr(D), ptr(w), ptr(z_old), ptr(lam), float(sigma0),
+                                 float(rho), float(rho_next), int(num_cu), 1 if want_v else 0, ptr(lam_out), ptr(v),
+                                 ptr(z_new), ptr(q), C.byref(p2), C.byref(zz), ptr(inst)))
+    return dict(lam=lam_out, v=v, z=z_new, q=q, primal2=p2.value, zz=zz.value, instance=_instance(inst))
+
+
+def k_sweep_v(D, w, z, lam, rho, storage="f32", num_cu=1):
+    """The V-only pass: v = D w, lam + rho (z - v), sum (z - v)^2 (include/rbl.h: rbl_k_sweep_v)"""
+    D, w, z, lam = f64(D), f64(w).reshape(-1), f64(z).reshape(-1), f64(lam).reshape(-1)
+    n, d = D.shape
+    lam_out, v = np.empty(n), np.empty(n)
+    p2 = C.c_double(0.0)
+    inst = np.zeros(5, dtype=np.int32)
+    check(load().rbl_k_sweep_v(STORAGE[storage], n, d, ptr(D), ptr(w), ptr(z), ptr(lam), float(rho), int(num_cu),
+                               ptr(lam_out), ptr(v), C.byref(p2), ptr(inst)))
+    return dict(lam=lam_out, v=v, primal2=p2.value, instance=_instance(inst))
+
+
+def k_sweep_q(D, c, storage="f32", num_cu=1):
+    """q = D^T c through the Q-only pass, its widths only (include/rbl.h: rbl_k_sweep_q)"""
+    D, c = f64(D), f64(c).reshape(-1)
+    n, d = D.shape
+    q = np.empty(d)
+    inst = np.zeros(5, dtype=np.int32)
+    check(load().rbl_k_sweep_q(STORAGE[storage], n, d, ptr(D), ptr(c), int(num_cu), ptr(q), ptr(inst)))
+    return dict(q=q, instance=_instance(inst))
+
+
+def k_sweep_v_multi(D, W, Z, LAM, rho, storage="f32", num_cu=1):
+    """k = 1..4 columns of the V pass with the lambda update in one launch; W: (k, d), Z, LAM: (k, n), rho: (k,).
+    lam and v come back as (4, n): the rows behind k are buffers of the entry point that no launch was told about; they
+    stay NaN unless a column was written past its n rows (include/rbl.h)."""
+    D, W = f64(D), f64(W)
+    n, d = D.shape
+    W = np.ascontiguousarray(W.reshape(-1, d))
+    k = W.shape[0]
+    Z, LAM, rho = f64(Z).reshape(k, n), f64(LAM).reshape(k, n), f64(rho).reshape(k)
+    lam_out, V = np.empty((MULTI_KMAX, n)), np.empty((MULTI_KMAX, n))
+    p2 = np.zeros(k)
+    inst = np.zeros(5, dtype=np.int32)
+    check(load().rbl_k_sweep_v_multi(STORAGE[storage], n, d, k, ptr(D), ptr(W), ptr(Z), ptr(LAM), ptr(rho), int(num_cu),
+                                     ptr(lam_out), ptr(V), ptr(p2), ptr(inst)))
+    return dict(lam=lam_out, v=V, primal2=p2, instance=_instance(inst))
+
+
+def k_sweep_q_multi(D, Cm, storage="f32", num_cu=1):
+    """Q = D^T [c_1 .. c_k] in one launch of the multi-column Q pass, k = 1..4; Cm: (k, n) -> q: (k, d)"""
+    D, Cm = f64(D), f64(Cm)
+    n, d = D.shape
+    Cm = np.ascontiguousarray(Cm.reshape(-1, n))
+    k = Cm.shape[0]
+    Q = np.empty((k, d))
+    inst = np.zeros(5, dtype=np.int32)
+    check(load().rbl_k_sweep_q_multi(STORAGE[storage], n, d, k, ptr(D), ptr(Cm), int(num_cu), ptr(Q), ptr(inst)))
+    return dict(q=Q, instance=_instance(inst))
 
 
 def k_gram(D, storage="f32"):

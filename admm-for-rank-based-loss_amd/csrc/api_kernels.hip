@@ -390,6 +390,259 @@ int rbl_k_gemvt_multi(int storage, int64_t n, int64_t d, int k, const double* D,
     return RBL_OK;
 }
 
+// ---- the row-streaming passes on prescribed inputs with a caller-chosen grid (rbl_k_sweep_*): the launchers of a solve,
+// unchanged, with num_cu in the place of the device's CU count; buffers sized by the launchers' own rules for that num_cu
+namespace {
+constexpr int SWEEP_GUARD = 64;   // doubles behind row n of every row-wise array, preset like the rows
+
+// the checks that come before any device work; ld of the stored matrix
+int sweep_begin(Scratch& sc, const char* who, int storage, int64_t n, int64_t d, int num_cu, int64_t* ld) {
+    if (storage != RBL_STORE_F32 && storage != RBL_STORE_F64 && storage != RBL_STORE_F16) {
+        rbl_set_error("%s: storage must be RBL_STORE_F32, RBL_STORE_F64 or RBL_STORE_F16 (got %d)", who, storage);
+        return RBL_ERR_INVALID;
+    }
+    if (n < 1 || d < 1) {
+        rbl_set_error("%s: n >= 1 and d >= 1 are needed (n = %lld, d = %lld)", who, (long long)n, (long long)d);
+        return RBL_ERR_INVALID;
+    }
+    int cus = 0;
+    RBL_TRY(scratch_begin(sc, &cus));
+    if (num_cu < 1 || num_cu > cus) {
+        rbl_set_error("%s: num_cu = %d outside 1..%d (the device's compute units)", who, num_cu, cus);
+        return RBL_ERR_INVALID;
+    }
+    *ld = rbl_storage_ld(storage, d);
+    return RBL_OK;
+}
+
+// rows x (n + SWEEP_GUARD) doubles on the device, every byte 0xff (a NaN); init (rows_init x n, host) fills the first rows
+int rows_alloc(Scratch& sc, double** p, int64_t n, int rows, const double* init, int rows_init) {
+    const size_t stride = (size_t)n + SWEEP_GUARD;
+    std::vector<double> host(stride * rows);
+    memset(host.data(), 0xff, host.size() * sizeof(double));
+    for (int r = 0; r < rows_init; ++r) memcpy(host.data() + r * stride, init + (size_t)r * n, sizeof(double) * (size_t)n);
+    return sc.upload(p, host.data(), host.size());
+}
+
+// back to the host (out: rows x n, may be NULL); a guard that no longer holds 0xff is a write past row n
+int rows_fetch(Scratch& sc, const char* who, const char* what, const double* p, int64_t n, int rows, double* out) {
+    const size_t stride = (size_t)n + SWEEP_GUARD;
+    std::vector<double> host(stride * rows);
+    RBL_HIP(hipMemcpyAsync(host.data(), p, host.size() * sizeof(double), hipMemcpyDeviceToHost, sc.s));
+    RBL_HIP(hipStreamSynchronize(sc.s));
+    for (int r = 0; r < rows; ++r) {
+        const unsigned char* g = (const unsigned char*)(host.data() + r * stride + n);
+        for (size_t b = 0; b < SWEEP_GUARD * sizeof(double); ++b)
+            if (g[b] != 0xff) {
+                rbl_set_error("%s: %s (column %d) was written past row n = %lld", who, what, r, (long long)n);
+                return RBL_ERR_STATE;
+            }
+        if (out) memcpy(out + (size_t)r * n, host.data() + r * stride, sizeof(double) * (size_t)n);
+    }
+    return RBL_OK;
+}
+
+// vectors over the columns (k x d, host) padded to k x ld on the device
+int cols_upload(Scratch& sc, double** p, const double* host, int k, int64_t d, int64_t ld) {
+    std::vector<double> wp((size_t)ld * k, 0.0);
+    for (int j = 0; j < k; ++j)
+        for (int64_t i = 0; i < d; ++i) wp[(size_t)j * ld + i] = host[(size_t)j * d + i];
+    return sc.upload(p, wp.data(), wp.size());
+}
+
+void instance_out(int* instance, const SweepInstance& in) {
+    if (!instance) return;
+    instance[0] = in.kind;
+    instance[1] = in.p;
+    instance[2] = in.r;
+    instance[3] = in.s;
+    instance[4] = in.blocks;
+}
+}  // namespace
+
+int rbl_k_sweep_erm(int storage, int loss, int64_t n, int64_t d, const double* D, const double* w, const double* z_old,
+                    const double* lam, double sigma0, double rho, double rho_next, int num_cu, int want_v, double* lam_out,
+                    double* v, double* z_new, double* q, double* primal2, double* zz, int* instance) {
+    const char* who = "rbl_k_sweep_erm";
+    RBL_TRY(k_check_loss(who, loss));
+    Scratch sc;
+    int64_t ld = 0;
+    RBL_TRY(sweep_begin(sc, who, storage, n, d, num_cu, &ld));
+    if (!sweep_erm_supported(storage, ld)) {
+        rbl_set_error("%s: d = %lld (ld = %lld) is outside the single-sweep kernels' widths for this storage", who, (long long)d,
+                      (long long)ld);
+        return RBL_ERR_INVALID;
+    }
+    void* Dd = nullptr;
+    RBL_TRY(upload_matrix(sc, storage, n, d, D, &Dd, &ld));
+    double *dw = nullptr, *dz = nullptr, *dlam = nullptr, *dv = nullptr, *dzn = nullptr, *pred = nullptr, *slab = nullptr,
+           *partials = nullptr, *dq = nullptr, *red = nullptr;
+    RBL_TRY(cols_upload(sc, &dw, w, 1, d, ld));
+    RBL_TRY(sc.upload(&dz, z_old, (size_t)n));
+    RBL_TRY(rows_alloc(sc, &dlam, n, 1, lam, 1));
+    RBL_TRY(rows_alloc(sc, &dv, n, 1, nullptr, 0));
+    RBL_TRY(rows_alloc(sc, &dzn, n, 1, nullptr, 0));
+    const double pred_h[2] = {rho_next, 0.0};
+    RBL_TRY(sc.upload(&pred, pred_h, 2));
+    RBL_TRY(sc.mem.alloc(&slab, (size_t)sweep_erm_slab_rows(num_cu) * ld));
+    RBL_TRY(sc.mem.alloc(&partials, std::max((size_t)sweep_erm_blocks(num_cu) * 3, (size_t)reduce_blocks() * 4)));
+    RBL_TRY(sc.mem.alloc(&dq, (size_t)ld));
+    RBL_TRY(sc.mem.alloc(&red, 8));
+    SweepInstance inst{};
+    RBL_TRY(launch_sweep_erm(storage, loss, Dd, n, ld, dw, dz, dlam, dv, dzn, sigma0, rho, pred, slab, partials, dq, red, red + 4,
+                             num_cu, sc.s, nullptr, want_v ? 1 : 0, &inst));
+    RBL_TRY(rows_fetch(sc, who, "lambda", dlam, n, 1, lam_out));
+    RBL_TRY(rows_fetch(sc, who, "v", dv, n, 1, v));
+    RBL_TRY(rows_fetch(sc, who, "z_new", dzn, n, 1, z_new));
+    double redh[8];
+    RBL_HIP(hipMemcpyAsync(q, dq, sizeof(double) * d, hipMemcpyDeviceToHost, sc.s));
+    RBL_HIP(hipMemcpyAsync(redh, red, sizeof(redh), hipMemcpyDeviceToHost, sc.s));
+    RBL_HIP(hipStreamSynchronize(sc.s));
+    if (primal2) *primal2 = redh[0];
+    if (zz) *zz = redh[4];
+    instance_out(instance, inst);
+    return RBL_OK;
+}
+
+int rbl_k_sweep_v(int storage, int64_t n, int64_t d, const double* D, const double* w, const double* z, const double* lam,
+                  double rho, int num_cu, double* lam_out, double* v, double* primal2, int* instance) {
+    const char* who = "rbl_k_sweep_v";
+    Scratch sc;
+    int64_t ld = 0;
+    RBL_TRY(sweep_begin(sc, who, storage, n, d, num_cu, &ld));
+    if (!sweep_v_supported(storage, ld)) {
+        rbl_set_error("%s: d = %lld (ld = %lld) is outside the V-only pass' widths for this storage", who, (long long)d, (long long)ld);
+        return RBL_ERR_INVALID;
+    }
+    void* Dd = nullptr;
+    RBL_TRY(upload_matrix(sc, storage, n, d, D, &Dd, &ld));
+    double *dw = nullptr, *dz = nullptr, *dlam = nullptr, *dv = nullptr, *partials = nullptr, *red = nullptr;
+    RBL_TRY(cols_upload(sc, &dw, w, 1, d, ld));
+    RBL_TRY(sc.upload(&dz, z, (size_t)n));
+    RBL_TRY(rows_alloc(sc, &dlam, n, 1, lam, 1));
+    RBL_TRY(rows_alloc(sc, &dv, n, 1, nullptr, 0));
+    RBL_TRY(sc.mem.alloc(&partials, (size_t)num_cu * 3));
+    RBL_TRY(sc.mem.alloc(&red, 8));
+    SweepInstance inst{};
+    RBL_TRY(launch_sweep_v(storage, Dd, n, ld, dw, dz, dlam, dv, rho, partials, red, num_cu, sc.s, nullptr, &inst));
+    RBL_TRY(rows_fetch(sc, who, "lambda", dlam, n, 1, lam_out));
+    RBL_TRY(rows_fetch(sc, who, "v", dv, n, 1, v));
+    double redh[2];
+    RBL_HIP(hipMemcpyAsync(redh, red, sizeof(redh), hipMemcpyDeviceToHost, sc.s));
+    RBL_HIP(hipStreamSynchronize(sc.s));
+    if (primal2) *primal2 = redh[0];
+    instance_out(instance, inst);
+    return RBL_OK;
+}
+
+int rbl_k_sweep_q(int storage, int64_t n, int64_t d, const double* D, const double* c, int num_cu, double* q, int* instance) {
+    const char* who = "rbl_k_sweep_q";
+    Scratch sc;
+    int64_t ld = 0;
+    RBL_TRY(sweep_begin(sc, who, storage, n, d, num_cu, &ld));
+    if (!sweep_v_supported(storage, ld)) {
+        rbl_set_error("%s: d = %lld (ld = %lld) is outside the Q-only pass' widths for this storage", who, (long long)d, (long long)ld);
+        return RBL_ERR_INVALID;
+    }
+    void* Dd = nullptr;
+    RBL_TRY(upload_matrix(sc, storage, n, d, D, &Dd, &ld));
+    double *dc = nullptr, *slab = nullptr, *dq = nullptr;
+    RBL_TRY(sc.upload(&dc, c, (size_t)n));
+    RBL_TRY(sc.mem.alloc(&slab, (size_t)sweep_erm_slab_rows(num_cu) * ld));
+    RBL_TRY(sc.mem.alloc(&dq, (size_t)ld));
+    SweepInstance inst{};
+    RBL_TRY(launch_sweep_q(storage, Dd, n, ld, dc, slab, dq, num_cu, sc.s, nullptr, &inst));
+    RBL_HIP(hipMemcpyAsync(q, dq, sizeof(double) * d, hipMemcpyDeviceToHost, sc.s));
+    RBL_HIP(hipStreamSynchronize(sc.s));
+    instance_out(instance, inst);
+    return RBL_OK;
+}
+
+int rbl_k_sweep_v_multi(int storage, int64_t n, int64_t d, int k, const double* D, const double* W, const double* Z,
+                        const double* LAM, const double* rho, int num_cu, double* LAM_out, double* V, double* primal2,
+                        int* instance) {
+    const char* who = "rbl_k_sweep_v_multi";
+    if (k < 1 || k > RBL_MULTI_KMAX) {
+        rbl_set_error("%s: %d columns (1..%d)", who, k, RBL_MULTI_KMAX);
+        return RBL_ERR_INVALID;
+    }
+    Scratch sc;
+    int64_t ld = 0;
+    RBL_TRY(sweep_begin(sc, who, storage, n, d, num_cu, &ld));
+    if (!sweep_multi_supported(storage, ld)) {
+        rbl_set_error("%s: d = %lld (ld = %lld) is outside the multi-column passes' widths for this storage", who, (long long)d,
+                      (long long)ld);
+        return RBL_ERR_INVALID;
+    }
+    void* Dd = nullptr;
+    RBL_TRY(upload_matrix(sc, storage, n, d, D, &Dd, &ld));
+    double *dw = nullptr, *dz = nullptr, *dlam = nullptr, *dv = nullptr, *partials = nullptr, *red = nullptr;
+    RBL_TRY(cols_upload(sc, &dw, W, k, d, ld));
+    RBL_TRY(sc.upload(&dz, Z, (size_t)n * k));
+    // the slots behind column k - 1 have buffers too, which no launch is told about: they keep their NaN
+    RBL_TRY(rows_alloc(sc, &dlam, n, RBL_MULTI_KMAX, LAM, k));
+    RBL_TRY(rows_alloc(sc, &dv, n, RBL_MULTI_KMAX, nullptr, 0));
+    RBL_TRY(sc.mem.alloc(&partials, (size_t)num_cu * 3 * k));
+    RBL_TRY(sc.mem.alloc(&red, (size_t)2 * k));
+    const size_t stride = (size_t)n + SWEEP_GUARD;
+    const double *pw[RBL_MULTI_KMAX], *pz[RBL_MULTI_KMAX];
+    double *pl[RBL_MULTI_KMAX], *pv[RBL_MULTI_KMAX], *pp[RBL_MULTI_KMAX], *pr[RBL_MULTI_KMAX];
+    for (int j = 0; j < k; ++j) {
+        pw[j] = dw + (size_t)j * ld;
+        pz[j] = dz + (size_t)j * n;
+        pl[j] = dlam + j * stride;
+        pv[j] = dv + j * stride;
+        pp[j] = partials + (size_t)j * num_cu * 3;
+        pr[j] = red + 2 * j;
+    }
+    SweepInstance inst{};
+    RBL_TRY(launch_sweep_v_multi(storage, Dd, n, ld, k, pw, pz, pl, pv, rho, pp, pr, num_cu, sc.s, &inst));
+    RBL_TRY(rows_fetch(sc, who, "lambda", dlam, n, RBL_MULTI_KMAX, LAM_out));
+    RBL_TRY(rows_fetch(sc, who, "v", dv, n, RBL_MULTI_KMAX, V));
+    double redh[2 * RBL_MULTI_KMAX];
+    RBL_HIP(hipMemcpyAsync(redh, red, sizeof(double) * 2 * k, hipMemcpyDeviceToHost, sc.s));
+    RBL_HIP(hipStreamSynchronize(sc.s));
+    for (int j = 0; primal2 && j < k; ++j) primal2[j] = redh[2 * j];
+    instance_out(instance, inst);
+    return RBL_OK;
+}
+
+int rbl_k_sweep_q_multi(int storage, int64_t n, int64_t d, int k, const double* D, const double* Cm, int num_cu, double* Q,
+                        int* instance) {
+    const char* who = "rbl_k_sweep_q_multi";
+    if (k < 1 || k > RBL_MULTI_KMAX) {
+        rbl_set_error("%s: %d columns (1..%d)", who, k, RBL_MULTI_KMAX);
+        return RBL_ERR_INVALID;
+    }
+    Scratch sc;
+    int64_t ld = 0;
+    RBL_TRY(sweep_begin(sc, who, storage, n, d, num_cu, &ld));
+    if (!sweep_multi_supported(storage, ld)) {
+        rbl_set_error("%s: d = %lld (ld = %lld) is outside the multi-column passes' widths for this storage", who, (long long)d,
+                      (long long)ld);
+        return RBL_ERR_INVALID;
+    }
+    void* Dd = nullptr;
+    RBL_TRY(upload_matrix(sc, storage, n, d, D, &Dd, &ld));
+    double *dc = nullptr, *slab = nullptr, *dq = nullptr;
+    RBL_TRY(sc.upload(&dc, Cm, (size_t)n * k));
+    RBL_TRY(sc.mem.alloc(&slab, sweep_multi_slab_doubles(ld, num_cu)));
+    RBL_TRY(sc.mem.alloc(&dq, (size_t)ld * k));
+    const double* pc[RBL_MULTI_KMAX];
+    double* pq[RBL_MULTI_KMAX];
+    for (int j = 0; j < k; ++j) {
+        pc[j] = dc + (size_t)j * n;
+        pq[j] = dq + (size_t)j * ld;
+    }
+    SweepInstance inst{};
+    RBL_TRY(launch_sweep_q_multi(storage, Dd, n, ld, k, pc, slab, pq, num_cu, sc.s, &inst));
+    for (int j = 0; j < k; ++j)
+        RBL_HIP(hipMemcpyAsync(Q + (size_t)j * d, dq + (size_t)j * ld, sizeof(double) * d, hipMemcpyDeviceToHost, sc.s));
+    RBL_HIP(hipStreamSynchronize(sc.s));
+    instance_out(instance, inst);
+    return RBL_OK;
+}
+
 int rbl_k_gram(int storage, int64_t n, int64_t d, const double* D, double* G) {
     Scratch sc;
     int num_cu = 256;

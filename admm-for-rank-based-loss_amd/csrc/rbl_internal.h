@@ -414,13 +414,26 @@ int launch_lasso_fs_pen(const double* G, int64_t ld, int64_t d, const double* q,
                         double* w_prev_out = nullptr, double* Gw_out = nullptr);
 int launch_soft_threshold(int64_t d, double* w, double t, hipStream_t s);
 
+// which kernel instance a row-streaming launcher ran (optional out-parameter of the launch_sweep_* functions: the
+// rbl_k_sweep_* entry points report it, the solver passes NULL).  kind: the wave-per-row kernels (p = P packets per
+// lane) or the workgroup-per-row kernel (p = PT packets per thread); r rows per sub-batch, s sub-batches per
+// super-batch, blocks launched.
+enum { SWEEP_KIND_WAVE = 0, SWEEP_KIND_WIDE = 1 };
+struct SweepInstance {
+    int kind, p, r, s, blocks;
+};
+inline void sweep_report(SweepInstance* inst, int kind, int p, int r, int s, int blocks) {
+    if (inst) *inst = SweepInstance{kind, p, r, s, blocks};
+}
+
 // ---- sweep_erm.hip: one pass over D per iteration for erm (fused dual update + next z-step + D^T c)
 bool sweep_erm_supported(int storage, int64_t ld);
 int sweep_erm_blocks(int num_cu);
+int sweep_erm_slab_rows(int num_cu);
 int launch_sweep_erm(int storage, int loss, const void* D, int64_t n, int64_t ld, const double* w, const double* z_old,
                      double* lam, double* v, double* z_new, double sigma0, double rho, const double* pred_dev,
                      double* slab, double* partials, double* q, double* red, double* zz_out, int num_cu, hipStream_t s,
-                     hipEvent_t main_done, int want_obj);
+                     hipEvent_t main_done, int want_obj, SweepInstance* inst = nullptr);
 // rho_{k+1} prediction + the w statistics (||w - w_prev||^2, sum w^2, ||w||_1 -> wstats[0..2]); p_out != p
 // rho_dev != NULL: rho is read from rho_dev[0] on the device (may alias pred)
 int launch_predict_rho(int64_t ld, const double* q, const double* p, double* p_out, const double* w, const double* w_prev,
@@ -432,9 +445,10 @@ bool sweep_v_supported(int storage, int64_t ld);
 // q = D^T c with the single-sweep kernel's row-streaming loads (sweep_erm.hip: SE_QONLY) for the widths of
 // sweep_v_supported; launch_gemvt routes to it
 int launch_sweep_q(int storage, const void* D, int64_t n, int64_t ld, const double* c, double* slab, double* q, int num_cu,
-                   hipStream_t s, hipEvent_t main_done);
+                   hipStream_t s, hipEvent_t main_done, SweepInstance* inst = nullptr);
 int launch_sweep_v(int storage, const void* D, int64_t n, int64_t ld, const double* w, const double* z, double* lam,
-                   double* v, double rho, double* partials, double* red, int num_cu, hipStream_t s, hipEvent_t main_done);
+                   double* v, double rho, double* partials, double* red, int num_cu, hipStream_t s, hipEvent_t main_done,
+                   SweepInstance* inst = nullptr);
 // ---- sweep_multi.hip: the two passes for up to RBL_MULTI_KMAX problems on one D per launch (widths of sweep_v_supported)
 #define RBL_MULTI_KMAX 4
 bool sweep_multi_supported(int storage, int64_t ld);
@@ -444,10 +458,10 @@ size_t sweep_multi_slab_doubles(int64_t ld, int num_cu);         // slab of laun
 // (partials_j: 3 doubles per CU).  Arrays of k host-side pointers / values, 1 <= k <= RBL_MULTI_KMAX.
 int launch_sweep_v_multi(int storage, const void* D, int64_t n, int64_t ld, int k, const double* const* w, const double* const* z,
                          double* const* lam, double* const* v, const double* rho, double* const* partials, double* const* red,
-                         int num_cu, hipStream_t s);
+                         int num_cu, hipStream_t s, SweepInstance* inst = nullptr);
 // q_j = D^T c_j
 int launch_sweep_q_multi(int storage, const void* D, int64_t n, int64_t ld, int k, const double* const* c, double* slab,
-                         double* const* q, int num_cu, hipStream_t s);
+                         double* const* q, int num_cu, hipStream_t s, SweepInstance* inst = nullptr);
 int launch_symv(const double* G, int64_t ld, const double* x, double* y, hipStream_t s);
 int launch_symv_ab(const double* G, int64_t ld, const double* x, double* y, double alpha, double beta, hipStream_t s);   // y = alpha G x + beta x
 

@@ -603,7 +603,7 @@ int launch_one(const T* D, long long n, long long ld, const double* w, const dou
 template <typename T, int LOSS>
 int launch_T(const T* D, long long n, long long ld, const double* w, const double* z_old, double* lam, double* v,
              double* z_new, double sigma0, double rho, const double* pred, double* slab, double* partials, int grid,
-             int num_cu, int* used, hipStream_t s) {
+             int num_cu, int* used, SweepInstance* inst, hipStream_t s) {
     const long long PK = ld / Pk<T>::E;
     const long long passes = (PK + 63) / 64;
     *used = grid;
@@ -617,6 +617,7 @@ int launch_T(const T* D, long long n, long long ld, const double* w, const doubl
 #define RBL_ONE(P_, R_, S_, WL_)                                                                                              \
     do {                                                                                                                      \
         *used = num_cu;                                                                                                       \
+        sweep_report(inst, SWEEP_KIND_WAVE, P_, R_, S_, num_cu);                                                              \
         return launch_one<T, LOSS, P_, R_, S_, WL_, 1>(D, n, ld, w, z_old, lam, v, z_new, sigma0, rho, pred, slab, partials, \
                                                        num_cu, s);                                                            \
     } while (0)
@@ -624,8 +625,10 @@ int launch_T(const T* D, long long n, long long ld, const double* w, const doubl
     // lane) weighs most, more waves hide it - 16 rows per sub-batch, still two blocks per CU: 24M x 250 201.5 -> 224 it/s
     // (one block per CU: 184-189).  Two packets: 8 rows per sub-batch, super-batches of 64 rows (512-byte row-wise
     // segments), one block per CU: 12M x 500 255.5 -> 269 (profiles/r03_sweep_shapes.txt block 8).
-    if (passes == 1)
+    if (passes == 1) {
+        sweep_report(inst, SWEEP_KIND_WAVE, 1, 16, 2, grid);
         return launch_one<T, LOSS, 1, 16, 2, false, 2>(D, n, ld, w, z_old, lam, v, z_new, sigma0, rho, pred, slab, partials, grid, s);
+    }
     if (passes == 2) RBL_ONE(2, 8, 8, false);
     if (passes <= 4) RBL_ONE(4, 4, 4, true);
     // 5-8 packets per lane and row (fp64 storage d <= 1024, fp32 storage d <= 2048).  fp64, d = 1000: four rows of 8
@@ -656,6 +659,7 @@ int launch_T(const T* D, long long n, long long ld, const double* w, const doubl
         hipLaunchKernelGGL(kfn, dim3(wgrid), dim3(SEW_THREADS), lds, s, D, n, ld, w, z_old, lam, v, z_new, sigma0, rho,  \
                            pred, slab, partials);                                                                      \
         RBL_HIP(hipGetLastError());                                                                                    \
+        sweep_report(inst, SWEEP_KIND_WIDE, PT_, R_, S_, wgrid);                                                       \
         return RBL_OK;                                                                                                 \
     } while (0)
     // Rows per sub-batch: as many as the 256 registers of a wave (8 waves per workgroup, one workgroup per CU) hold in two
@@ -701,7 +705,7 @@ int sweep_erm_slab_rows(int num_cu) { return sweep_erm_blocks(num_cu) + CR_SLICE
 int launch_sweep_erm(int storage, int loss, const void* D, int64_t n, int64_t ld, const double* w, const double* z_old,
                      double* lam, double* v, double* z_new, double sigma0, double rho, const double* pred_dev,
                      double* slab, double* partials, double* q, double* red, double* zz_out, int num_cu, hipStream_t s,
-                     hipEvent_t main_done, int want_obj) {
+                     hipEvent_t main_done, int want_obj, SweepInstance* inst) {
     const int grid = sweep_erm_blocks(num_cu);
     int nrows = grid;   // slab rows / partial triples produced = blocks launched
     double* const v_for_loss = v;
@@ -710,11 +714,11 @@ int launch_sweep_erm(int storage, int loss, const void* D, int64_t n, int64_t ld
     // the fused instances exist per loss and storage type, with the same (P, R, S, WL, OCC) / (PT, R, S) tables (launch_T)
     RBL_LOSS_SWITCH(loss, L_,
                     if (storage == RBL_STORE_F16)
-                        rc = launch_T<rbl_half, L_>((const rbl_half*)D, n, ld, w, z_old, lam, v, z_new, sigma0, rho, pred_dev, slab, partials, grid, num_cu, &nrows, s);
+                        rc = launch_T<rbl_half, L_>((const rbl_half*)D, n, ld, w, z_old, lam, v, z_new, sigma0, rho, pred_dev, slab, partials, grid, num_cu, &nrows, inst, s);
                     else if (storage == RBL_STORE_F32)
-                        rc = launch_T<float, L_>((const float*)D, n, ld, w, z_old, lam, v, z_new, sigma0, rho, pred_dev, slab, partials, grid, num_cu, &nrows, s);
+                        rc = launch_T<float, L_>((const float*)D, n, ld, w, z_old, lam, v, z_new, sigma0, rho, pred_dev, slab, partials, grid, num_cu, &nrows, inst, s);
                     else
-                        rc = launch_T<double, L_>((const double*)D, n, ld, w, z_old, lam, v, z_new, sigma0, rho, pred_dev, slab, partials, grid, num_cu, &nrows, s));
+                        rc = launch_T<double, L_>((const double*)D, n, ld, w, z_old, lam, v, z_new, sigma0, rho, pred_dev, slab, partials, grid, num_cu, &nrows, inst, s));
     RBL_TRY(rc);
     if (main_done) RBL_HIP(hipEventRecord(main_done, s));
     double* part = slab + (size_t)grid * ld;   // CR_SLICES rows behind the grid rows of the slab
@@ -743,7 +747,7 @@ __global__ __launch_bounds__(256) void k_finish_v(const double* __restrict__ par
 
 template <typename T>
 int launch_v_T(const T* D, long long n, long long ld, const double* w, const double* z, double* lam, double* v, double rho,
-               double* partials, int grid, hipStream_t s) {
+               double* partials, int grid, SweepInstance* inst, hipStream_t s) {
     const long long PK = ld / Pk<T>::E;
     const long long passes = (PK + 63) / 64;
 #define RBL_V(P_, R_, S_, WL_, OCC_)                                                                                \
@@ -752,6 +756,7 @@ int launch_v_T(const T* D, long long n, long long ld, const double* w, const dou
                            ld, w, z, lam, v, (double*)nullptr, 0.0, rho, (const double*)nullptr, (double*)nullptr,  \
                            partials);                                                                               \
         RBL_HIP(hipGetLastError());                                                                                 \
+        sweep_report(inst, SWEEP_KIND_WAVE, P_, R_, S_, grid);                                                      \
         return RBL_OK;                                                                                              \
     } while (0)
     if (passes == 1) RBL_V(1, 8, 2, false, 2);
@@ -777,14 +782,15 @@ bool sweep_v_supported(int storage, int64_t ld) {
 // on one box C2sq 134.6 -> 137.4 it/s (the fused pass with two rows per sub-batch the other way round, 270 it/s with two
 // blocks and 236 with one; with four rows per sub-batch it too runs best with one block, launch_T)
 int launch_sweep_v(int storage, const void* D, int64_t n, int64_t ld, const double* w, const double* z, double* lam,
-                   double* v, double rho, double* partials, double* red, int num_cu, hipStream_t s, hipEvent_t main_done) {
+                   double* v, double rho, double* partials, double* red, int num_cu, hipStream_t s, hipEvent_t main_done,
+                   SweepInstance* inst) {
     const int grid = num_cu;
     if (storage == RBL_STORE_F32)
-        RBL_TRY(launch_v_T<float>((const float*)D, n, ld, w, z, lam, v, rho, partials, grid, s));
+        RBL_TRY(launch_v_T<float>((const float*)D, n, ld, w, z, lam, v, rho, partials, grid, inst, s));
     else if (storage == RBL_STORE_F16)
-        RBL_TRY(launch_v_T<rbl_half>((const rbl_half*)D, n, ld, w, z, lam, v, rho, partials, grid, s));
+        RBL_TRY(launch_v_T<rbl_half>((const rbl_half*)D, n, ld, w, z, lam, v, rho, partials, grid, inst, s));
     else
-        RBL_TRY(launch_v_T<double>((const double*)D, n, ld, w, z, lam, v, rho, partials, grid, s));
+        RBL_TRY(launch_v_T<double>((const double*)D, n, ld, w, z, lam, v, rho, partials, grid, inst, s));
     if (main_done) RBL_HIP(hipEventRecord(main_done, s));
     hipLaunchKernelGGL(k_finish_v, dim3(1), dim3(256), 0, s, partials, grid, red);
     RBL_HIP(hipGetLastError());
@@ -802,7 +808,7 @@ __global__ __launch_bounds__(256) void k_finish_q(const double* __restrict__ par
 }
 
 template <typename T>
-int launch_q_T(const T* D, long long n, long long ld, const double* c, double* slab, int grid, hipStream_t s) {
+int launch_q_T(const T* D, long long n, long long ld, const double* c, double* slab, int grid, SweepInstance* inst, hipStream_t s) {
     const long long PK = ld / Pk<T>::E;
     const long long passes = (PK + 63) / 64;
 #define RBL_Q(P_, R_, S_, OCC_)                                                                                      \
@@ -811,6 +817,7 @@ int launch_q_T(const T* D, long long n, long long ld, const double* c, double* s
                            ld, (const double*)nullptr, c, (double*)nullptr, (double*)nullptr, (double*)nullptr, 0.0, 1.0,     \
                            (const double*)nullptr, slab, (double*)nullptr);                                          \
         RBL_HIP(hipGetLastError());                                                                                  \
+        sweep_report(inst, SWEEP_KIND_WAVE, P_, R_, S_, grid);                                                       \
         return RBL_OK;                                                                                               \
     } while (0)
     if (passes == 1) RBL_Q(1, 8, 2, 2);
@@ -824,14 +831,14 @@ int launch_q_T(const T* D, long long n, long long ld, const double* c, double* s
 
 // q = D^T c through the single-sweep kernel's loads (SE_QONLY); same widths as launch_sweep_v
 int launch_sweep_q(int storage, const void* D, int64_t n, int64_t ld, const double* c, double* slab, double* q, int num_cu,
-                   hipStream_t s, hipEvent_t main_done) {
+                   hipStream_t s, hipEvent_t main_done, SweepInstance* inst) {
     const int grid = num_cu;   // one block per CU (see launch_sweep_v)
     if (storage == RBL_STORE_F32)
-        RBL_TRY(launch_q_T<float>((const float*)D, n, ld, c, slab, grid, s));
+        RBL_TRY(launch_q_T<float>((const float*)D, n, ld, c, slab, grid, inst, s));
     else if (storage == RBL_STORE_F16)
-        RBL_TRY(launch_q_T<rbl_half>((const rbl_half*)D, n, ld, c, slab, grid, s));
+        RBL_TRY(launch_q_T<rbl_half>((const rbl_half*)D, n, ld, c, slab, grid, inst, s));
     else
-        RBL_TRY(launch_q_T<double>((const double*)D, n, ld, c, slab, grid, s));
+        RBL_TRY(launch_q_T<double>((const double*)D, n, ld, c, slab, grid, inst, s));
     if (main_done) RBL_HIP(hipEventRecord(main_done, s));
     double* part = slab + (size_t)grid * ld;
     hipLaunchKernelGGL(k_colreduce2, dim3((unsigned)((ld + 63) / 64), CR_SLICES), dim3(256), 0, s, slab, grid, (long long)ld, part);

@@ -400,7 +400,7 @@ __global__ __launch_bounds__(256) void k_finish_qm(const double* __restrict__ sl
 
 // shapes (P, R, S) of launch_v_T / launch_q_T (sweep_erm.hip); every multi-column kernel runs one block per CU
 template <typename T, int KC>
-int launch_vm_T(const T* D, long long n, long long ld, const MultiV& a, int grid, hipStream_t s) {
+int launch_vm_T(const T* D, long long n, long long ld, const MultiV& a, int grid, SweepInstance* inst, hipStream_t s) {
     const long long passes = (ld / Pk<T>::E + 63) / 64;
 #define RBL_VM(P_, R_, S_)                                                                                               \
     do {                                                                                                                 \
@@ -414,6 +414,7 @@ int launch_vm_T(const T* D, long long n, long long ld, const MultiV& a, int grid
         }                                                                                                                \
         hipLaunchKernelGGL(kfn, dim3(grid), dim3(SM_THREADS), lds, s, D, n, ld, a);                                      \
         RBL_HIP(hipGetLastError());                                                                                      \
+        sweep_report(inst, SWEEP_KIND_WAVE, P_, R_, S_, grid);                                                           \
         return RBL_OK;                                                                                                   \
     } while (0)
     if (passes == 1) RBL_VM(1, 8, 2);
@@ -428,12 +429,14 @@ int launch_vm_T(const T* D, long long n, long long ld, const MultiV& a, int grid
 }
 
 template <typename T, int KC>
-int launch_qm_T(const T* D, long long n, long long ld, const MultiQ& a, double* slab, long long plane, int grid, hipStream_t s) {
+int launch_qm_T(const T* D, long long n, long long ld, const MultiQ& a, double* slab, long long plane, int grid, SweepInstance* inst,
+                hipStream_t s) {
     const long long passes = (ld / Pk<T>::E + 63) / 64;
 #define RBL_QM(P_, R_, S_)                                                                                              \
     do {                                                                                                                \
         hipLaunchKernelGGL((k_sweep_qm<T, P_, R_, S_, KC>), dim3(grid), dim3(SM_THREADS), 0, s, D, n, ld, a, slab, plane); \
         RBL_HIP(hipGetLastError());                                                                                     \
+        sweep_report(inst, SWEEP_KIND_WAVE, P_, R_, S_, grid);                                                          \
         return RBL_OK;                                                                                                  \
     } while (0)
     if (passes == 1) RBL_QM(1, 8, 2);
@@ -470,7 +473,7 @@ size_t sweep_multi_slab_doubles(int64_t ld, int num_cu) { return (size_t)RBL_MUL
 
 int launch_sweep_v_multi(int storage, const void* D, int64_t n, int64_t ld, int k, const double* const* w, const double* const* z,
                          double* const* lam, double* const* v, const double* rho, double* const* partials, double* const* red,
-                         int num_cu, hipStream_t s) {
+                         int num_cu, hipStream_t s, SweepInstance* inst) {
     if (k < 1 || k > RBL_MULTI_KMAX) {
         rbl_set_error("multi-column V pass: %d columns in one launch (1..%d)", k, RBL_MULTI_KMAX);
         return RBL_ERR_INVALID;
@@ -495,11 +498,11 @@ int launch_sweep_v_multi(int storage, const void* D, int64_t n, int64_t ld, int 
     const int grid = num_cu;
     int rc;
     if (storage == RBL_STORE_F32)
-        rc = k <= 2 ? launch_vm_T<float, 2>((const float*)D, n, ld, a, grid, s) : launch_vm_T<float, 4>((const float*)D, n, ld, a, grid, s);
+        rc = k <= 2 ? launch_vm_T<float, 2>((const float*)D, n, ld, a, grid, inst, s) : launch_vm_T<float, 4>((const float*)D, n, ld, a, grid, inst, s);
     else if (storage == RBL_STORE_F16)
-        rc = k <= 2 ? launch_vm_T<rbl_half, 2>((const rbl_half*)D, n, ld, a, grid, s) : launch_vm_T<rbl_half, 4>((const rbl_half*)D, n, ld, a, grid, s);
+        rc = k <= 2 ? launch_vm_T<rbl_half, 2>((const rbl_half*)D, n, ld, a, grid, inst, s) : launch_vm_T<rbl_half, 4>((const rbl_half*)D, n, ld, a, grid, inst, s);
     else
-        rc = k <= 2 ? launch_vm_T<double, 2>((const double*)D, n, ld, a, grid, s) : launch_vm_T<double, 4>((const double*)D, n, ld, a, grid, s);
+        rc = k <= 2 ? launch_vm_T<double, 2>((const double*)D, n, ld, a, grid, inst, s) : launch_vm_T<double, 4>((const double*)D, n, ld, a, grid, inst, s);
     RBL_TRY(rc);
     if (update) {
         hipLaunchKernelGGL(k_finish_vm, dim3(k), dim3(256), 0, s, r, grid);
@@ -509,7 +512,7 @@ int launch_sweep_v_multi(int storage, const void* D, int64_t n, int64_t ld, int 
 }
 
 int launch_sweep_q_multi(int storage, const void* D, int64_t n, int64_t ld, int k, const double* const* c, double* slab,
-                         double* const* q, int num_cu, hipStream_t s) {
+                         double* const* q, int num_cu, hipStream_t s, SweepInstance* inst) {
     if (k < 1 || k > RBL_MULTI_KMAX) {
         rbl_set_error("multi-column Q pass: %d columns in one launch (1..%d)", k, RBL_MULTI_KMAX);
         return RBL_ERR_INVALID;
@@ -528,14 +531,14 @@ int launch_sweep_q_multi(int storage, const void* D, int64_t n, int64_t ld, int 
     const long long plane = (long long)(grid + SM_SLICES) * ld;
     int rc;
     if (storage == RBL_STORE_F32)
-        rc = k <= 2 ? launch_qm_T<float, 2>((const float*)D, n, ld, a, slab, plane, grid, s)
-                    : launch_qm_T<float, 4>((const float*)D, n, ld, a, slab, plane, grid, s);
+        rc = k <= 2 ? launch_qm_T<float, 2>((const float*)D, n, ld, a, slab, plane, grid, inst, s)
+                    : launch_qm_T<float, 4>((const float*)D, n, ld, a, slab, plane, grid, inst, s);
     else if (storage == RBL_STORE_F16)
-        rc = k <= 2 ? launch_qm_T<rbl_half, 2>((const rbl_half*)D, n, ld, a, slab, plane, grid, s)
-                    : launch_qm_T<rbl_half, 4>((const rbl_half*)D, n, ld, a, slab, plane, grid, s);
+        rc = k <= 2 ? launch_qm_T<rbl_half, 2>((const rbl_half*)D, n, ld, a, slab, plane, grid, inst, s)
+                    : launch_qm_T<rbl_half, 4>((const rbl_half*)D, n, ld, a, slab, plane, grid, inst, s);
     else
-        rc = k <= 2 ? launch_qm_T<double, 2>((const double*)D, n, ld, a, slab, plane, grid, s)
-                    : launch_qm_T<double, 4>((const double*)D, n, ld, a, slab, plane, grid, s);
+        rc = k <= 2 ? launch_qm_T<double, 2>((const double*)D, n, ld, a, slab, plane, grid, inst, s)
+                    : launch_qm_T<double, 4>((const double*)D, n, ld, a, slab, plane, grid, inst, s);
     RBL_TRY(rc);
     hipLaunchKernelGGL(k_colreduce_m, dim3((unsigned)((ld + 63) / 64), SM_SLICES, (unsigned)k), dim3(256), 0, s, slab, plane, grid,
                        (long long)ld);

@@ -538,6 +538,38 @@ int  rbl_k_gemvt(int storage, int64_t n, int64_t d, const double* D, const doubl
  * column) - algorithms.py:89,132 / :192 for k problems at once */
 int  rbl_k_gemv_multi(int storage, int64_t n, int64_t d, int k, const double* D, const double* W, double* V);
 int  rbl_k_gemvt_multi(int storage, int64_t n, int64_t d, int k, const double* D, const double* C, double* Q);
+/* The row-streaming passes on prescribed inputs, with a caller-chosen grid: the launchers a solve runs, unchanged, with
+ * `num_cu` in the place of the device's CU count (1 <= num_cu <= that count, else RBL_ERR_INVALID).  A wave (a
+ * workgroup of the wide kernel) takes the super-batches gw, gw + GW, ... of S*R rows, so with num_cu = 1 it loops after
+ * a few hundred (about fifty) rows.  Host fp64 in and out; D is rounded to `storage` (RBL_STORE_F32 / F64 / F16).
+ * instance (5 ints, optional) receives which kernel instance ran: kind (0 wave-per-row, 1 workgroup-per-row), P (packets
+ * per lane) or PT (packets per thread), R rows per sub-batch, S sub-batches per super-batch, blocks launched.
+ * Every row-wise output is preset to NaN on the device and has a guard behind row n: a row the pass does not write comes
+ * back as NaN, a write past n is RBL_ERR_STATE.
+ *   rbl_k_sweep_erm      the single-sweep pass (sweep_erm.hip lines 5-9): lam_out = lam + rho (z_old - D w), z_new =
+ *                        prox(sigma0, rho_next, v - lam_out / rho_next), q = D^T (z_new + lam_out / rho_next), *primal2
+ *                        = sum (z_old - v)^2, *zz = sum z_new^2.  rho_next is what the solver predicts on the device
+ *                        (pred[0]).  want_v = 0: the pass without the store of v (no objective logging); v may be NULL.
+ *                        Widths outside the single-sweep kernels' range are RBL_ERR_INVALID.
+ *   rbl_k_sweep_v        v = D w, lam_out = lam + rho (z - v), *primal2 = sum (z - v)^2 (the V-only mode)
+ *   rbl_k_sweep_q        q = D^T c through the Q-only mode - its widths only (rbl_k_gemvt takes every width and says
+ *                        nothing about the kernel that ran)
+ *   rbl_k_sweep_v_multi  k = 1..4 columns in one launch (W: k x d, Z, LAM: k x n, rho[k]); primal2[k].  LAM_out and V
+ *                        are 4 x n: rows >= k are buffers of this entry that no launch is told about (the launcher gives
+ *                        the kernel's unused slots column 0's pointers), so their NaN says only that no column was
+ *                        written past its n rows - not that the kernel skipped the stores of the slots >= k
+ *   rbl_k_sweep_q_multi  Q = D^T [c_1 .. c_k], C: k x n, Q: k x d, k = 1..4 */
+int  rbl_k_sweep_erm(int storage, int loss, int64_t n, int64_t d, const double* D, const double* w, const double* z_old,
+                     const double* lam, double sigma0, double rho, double rho_next, int num_cu, int want_v,
+                     double* lam_out, double* v, double* z_new, double* q, double* primal2, double* zz, int* instance);
+int  rbl_k_sweep_v(int storage, int64_t n, int64_t d, const double* D, const double* w, const double* z, const double* lam,
+                   double rho, int num_cu, double* lam_out, double* v, double* primal2, int* instance);
+int  rbl_k_sweep_q(int storage, int64_t n, int64_t d, const double* D, const double* c, int num_cu, double* q, int* instance);
+int  rbl_k_sweep_v_multi(int storage, int64_t n, int64_t d, int k, const double* D, const double* W, const double* Z,
+                         const double* LAM, const double* rho, int num_cu, double* LAM_out, double* V, double* primal2,
+                         int* instance);
+int  rbl_k_sweep_q_multi(int storage, int64_t n, int64_t d, int k, const double* D, const double* C, int num_cu, double* Q,
+                         int* instance);
 /* G = D^T D (MFMA f64) */
 int  rbl_k_gram(int storage, int64_t n, int64_t d, const double* D, double* G);
 /* the passes of RBL_STORE_CSR on a host CSR matrix that holds D itself (no label sign): int64 indptr (n + 1), int32
