@@ -89,6 +89,22 @@ class RblStats(C.Structure):
     ]
 
 
+class RblWstepReport(C.Structure):
+    """rbl_wstep_report of include/rbl.h: what one step of rbl_k_wstep_seq ran"""
+    _fields_ = [
+        ("form", C.c_int32), ("status", C.c_int32), ("iters", C.c_int32),
+        ("glds", C.c_int32), ("per", C.c_int32), ("nblocks", C.c_int32), ("lds_bytes", C.c_int32),
+        ("phase_a", C.c_int32),
+        ("fs", C.c_int32 * 4),
+        ("fell_back", C.c_int32), ("gw_valid", C.c_int32),
+        ("last_iters", C.c_int32), ("last_fista", C.c_int32), ("ncg_skip", C.c_int32), ("ncg_backoff", C.c_int32),
+        ("launch_seq", C.c_int32), ("live_handles", C.c_int32),
+    ]
+
+
+KW_WANT_GW, KW_W_PREV, KW_RHO_DEV, KW_TWO_CALL = 1, 2, 4, 8
+
+
 class RblError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f"librbl error {code}: {msg}")
@@ -206,6 +222,8 @@ SIGNATURES = {
                               C.POINTER(C.c_int)]),
     "rbl_k_wstep_pen": (C.c_int, [C.c_int64, _P, _P, C.c_double, _P, _P, _P, C.c_double, _P, C.POINTER(C.c_int),
                                   C.POINTER(C.c_int)]),
+    "rbl_k_wstep_seq": (C.c_int, [C.c_int, C.c_int64, _P, C.c_int, _P, C.c_double, C.c_double, C.c_double, _P, _P, _P,
+                                  C.c_double, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P]),
     "rbl_k_weights": (C.c_int, [C.c_int, C.c_int64, _P, C.c_int, _P, _P]),
     "rbl_bl_create": (C.c_int, [C.c_int64, C.c_int64, _P, _P, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_int,
                                 C.POINTER(_P)]),
@@ -254,7 +272,7 @@ def load():
             fn = getattr(lib, name)
             fn.restype = res
             fn.argtypes = args
-        for which, cls in ((0, RblConfig), (1, RblStats)):
+        for which, cls in ((0, RblConfig), (1, RblStats), (2, RblWstepReport)):
             if lib.rbl_sizeof(which) != C.sizeof(cls):
                 raise ImportError(f"{LIB_PATH}: sizeof({cls.__name__}) is {lib.rbl_sizeof(which)} in the library and "
                                   f"{C.sizeof(cls)} in this binding (include/rbl.h and _lib.py out of step: rebuild)")
@@ -525,6 +543,30 @@ def k_wstep_pen(G, q, rho, l1=None, l2=None, w0=None, tol=1e-13):
     check(load().rbl_k_wstep_pen(d, ptr(G), ptr(q), float(rho), ptr(l1), ptr(l2), ptr(w0), float(tol), ptr(out),
                                  C.byref(it), C.byref(form)))
     return out, it.value, form.value
+
+
+def k_wstep_seq(wstep, G, Q, rho, reg, w0=None, smooth_t=1.0, tol=1e-13, max_inner=100000, l1=None, l2=None, route=0,
+                launch_seq0=0, want_Gw=False, w_prev=False, rho_dev=False, two_call=False):
+    """K w-steps one after another on one workspace, each warm-started from the previous w (include/rbl.h:
+    rbl_k_wstep_seq).  Q: (K, d) or (d,).  Returns dict(w (K, d), Gw (K, d; NaN rows where the step left no valid G w),
+    w_prev (K, d; NaN where nothing was saved), reports: K dicts of the fields of rbl_wstep_report)."""
+    G = f64(G)
+    d = G.shape[0]
+    Q = np.ascontiguousarray(f64(Q).reshape(-1, d))
+    K = Q.shape[0]
+    l1 = None if l1 is None else f64(np.broadcast_to(np.asarray(l1, dtype=np.float64), (d,)))
+    l2 = None if l2 is None else f64(np.broadcast_to(np.asarray(l2, dtype=np.float64), (d,)))
+    w0 = None if w0 is None else f64(w0).reshape(-1)
+    flags = (KW_WANT_GW if want_Gw else 0) | (KW_W_PREV if w_prev else 0) | (KW_RHO_DEV if rho_dev else 0) | \
+            (KW_TWO_CALL if two_call else 0)
+    W, Gw, Wp = np.empty((K, d)), np.empty((K, d)), np.empty((K, d))
+    rep = (RblWstepReport * K)()
+    check(load().rbl_k_wstep_seq(int(wstep), d, ptr(G), K, ptr(Q), float(rho), float(reg), float(smooth_t), ptr(l1), ptr(l2),
+                                 ptr(w0), float(tol), int(max_inner), int(route), int(launch_seq0), flags, ptr(W), ptr(Gw),
+                                 ptr(Wp), C.cast(rep, C.c_void_p)))
+    reports = [{name: (list(getattr(r, name)) if name == "fs" else int(getattr(r, name))) for name, _ in RblWstepReport._fields_}
+               for r in rep]
+    return dict(w=W, Gw=Gw, w_prev=Wp, reports=reports)
 
 
 def k_weights(weight_function, n, args=None):

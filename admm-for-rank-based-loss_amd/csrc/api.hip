@@ -242,7 +242,9 @@ extern "C" {
 
 int rbl_version(void) { return RBL_VERSION; }
 
-int rbl_sizeof(int which) { return which == 0 ? (int)sizeof(rbl_config) : which == 1 ? (int)sizeof(rbl_stats) : -1; }
+int rbl_sizeof(int which) {
+    return which == 0 ? (int)sizeof(rbl_config) : which == 1 ? (int)sizeof(rbl_stats) : which == 2 ? (int)sizeof(rbl_wstep_report) : -1;
+}
 
 const char* rbl_last_error(void) { return g_err.c_str(); }
 

@@ -805,6 +805,147 @@ int rbl_k_wstep_pen(int64_t d, const double* G, const double* q, double rho, con
     return RBL_OK;
 }
 
+int rbl_k_wstep_seq(int wstep, int64_t d, const double* G, int K, const double* Q, double rho, double reg, double smooth_t,
+                    const double* l1, const double* l2, const double* w0, double tol, int max_inner, int route,
+                    int launch_seq0, int flags, double* W, double* Gw, double* Wprev, rbl_wstep_report* reports) {
+    const char* who = "rbl_k_wstep_seq";
+    const bool pen = l1 || l2;
+    if (wstep != RBL_WSTEP_L1 && wstep != RBL_WSTEP_L2 && wstep != RBL_WSTEP_SMOOTH_L1) {
+        rbl_set_error("%s: wstep must be 1 (lasso), 2 (ridge) or 3 (smoothed l1), got %d", who, wstep);
+        return RBL_ERR_INVALID;
+    }
+    if (d < 1 || d > 16384 || K < 1 || !G || !Q || !W) {
+        rbl_set_error("%s: 1 <= d <= 16384, K >= 1, G, Q and W are needed (d = %lld, K = %d)", who, (long long)d, K);
+        return RBL_ERR_INVALID;
+    }
+    if (!(rho > 0.0) || !std::isfinite(rho) || !(reg >= 0.0) || !std::isfinite(reg) || !(tol > 0.0) || !(tol < 1.0) ||
+        max_inner < 1 || (wstep == RBL_WSTEP_SMOOTH_L1 && (!(smooth_t > 0.0) || !std::isfinite(smooth_t)))) {
+        rbl_set_error("%s: rho > 0, reg >= 0, 0 < tol < 1, max_inner >= 1 and smooth_t > 0 are needed (rho = %g, reg = %g, "
+                      "tol = %g, max_inner = %d, smooth_t = %g)", who, rho, reg, tol, max_inner, smooth_t);
+        return RBL_ERR_INVALID;
+    }
+    if ((route != 0 && route != 1) || launch_seq0 < 0 || launch_seq0 > 0xfffff ||
+        (flags & ~(RBL_KW_WANT_GW | RBL_KW_W_PREV | RBL_KW_RHO_DEV | RBL_KW_TWO_CALL)) != 0) {
+        rbl_set_error("%s: route is 0 or 1, 0 <= launch_seq0 <= 0xfffff, flags are RBL_KW_* (route = %d, launch_seq0 = %d, "
+                      "flags = %d)", who, route, launch_seq0, flags);
+        return RBL_ERR_INVALID;
+    }
+    if (pen && wstep == RBL_WSTEP_SMOOTH_L1) {
+        rbl_set_error("%s: per-coordinate penalties go with wstep 1 or 2", who);
+        return RBL_ERR_INVALID;
+    }
+    if (wstep != RBL_WSTEP_L1 && (flags & (RBL_KW_W_PREV | RBL_KW_RHO_DEV | RBL_KW_TWO_CALL)) != 0) {
+        rbl_set_error("%s: RBL_KW_W_PREV, RBL_KW_RHO_DEV and RBL_KW_TWO_CALL are call forms of the lasso (wstep 1)", who);
+        return RBL_ERR_INVALID;
+    }
+    if (((flags & RBL_KW_WANT_GW) && !Gw) || ((flags & RBL_KW_W_PREV) && !Wprev)) {
+        rbl_set_error("%s: RBL_KW_WANT_GW needs Gw, RBL_KW_W_PREV needs Wprev", who);
+        return RBL_ERR_INVALID;
+    }
+    double l2max = 0.0;
+    for (int k = 0; k < 2; ++k) {
+        const double* v = k ? l2 : l1;
+        for (int64_t j = 0; v && j < d; ++j) {
+            if (!(v[j] >= 0.0) || !std::isfinite(v[j])) {
+                rbl_set_error("%s: %s[%lld] = %g - penalties must be finite and >= 0", who, k ? "l2" : "l1", (long long)j, v[j]);
+                return RBL_ERR_INVALID;
+            }
+            if (k && v[j] > l2max) l2max = v[j];
+        }
+    }
+    const bool want_Gw = (flags & RBL_KW_WANT_GW) != 0, want_prev = (flags & RBL_KW_W_PREV) != 0;
+    const bool rho_on_dev = (flags & RBL_KW_RHO_DEV) != 0, two_call = rho_on_dev || (flags & RBL_KW_TWO_CALL) != 0;
+
+    Scratch sc;
+    RBL_TRY(scratch_begin(sc, nullptr));
+    const int64_t ld = round_up(d, 4);
+    std::vector<double> hG((size_t)ld * ld, 0.0), hq((size_t)ld, 0.0), hw((size_t)ld, 0.0), hp((size_t)(2 * ld), 0.0);
+    for (int64_t i = 0; i < d; ++i) {
+        for (int64_t j = 0; j < d; ++j) hG[(size_t)(i * ld + j)] = G[i * d + j];
+        hw[(size_t)i] = w0 ? w0[i] : 0.0;
+        hp[(size_t)i] = l1 ? l1[i] : 0.0;
+        hp[(size_t)(ld + i)] = l2 ? l2[i] : 0.0;
+    }
+    double *dG = nullptr, *dq = nullptr, *dw = nullptr, *dp = nullptr, *dprev = nullptr, *drho = nullptr;
+    RBL_TRY(sc.upload(&dG, hG.data(), hG.size()));
+    RBL_TRY(sc.mem.alloc(&dq, (size_t)ld));
+    RBL_TRY(sc.upload(&dw, hw.data(), hw.size()));
+    RBL_TRY(sc.upload(&dp, hp.data(), hp.size()));
+    RBL_TRY(sc.mem.alloc(&dprev, (size_t)ld));
+    RBL_TRY(sc.upload(&drho, &rho, 1));
+    WstepWorkspace ww{};
+    RBL_TRY(alloc_wstep(sc.mem, ww, ld, sc.s));
+    if (pen) {
+        ww.pen_l1 = dp;
+        ww.pen_l2 = dp + ld;
+        ww.pen_l2max = l2max;
+    }
+    if (route == 1) ww.bar = nullptr, ww.xch = nullptr;   // run_wstep takes the persistent route only with both
+    ww.launch_seq = launch_seq0;
+    WstepInstance inst{};
+    ww.inst = &inst;
+    double lam = 0.0;
+    RBL_TRY(launch_power_iteration(dG, ld, ww.yk, ww.Gy, ww.scal, 100, &lam, sc.s));
+    double L = 1.02 * lam;
+    if (!(L > 0.0)) L = 1.0;
+    int dev = 0;
+    RBL_HIP(hipGetDevice(&dev));
+    const size_t row = sizeof(double) * (size_t)d;
+    for (int k = 0; k < K; ++k) {
+        for (int64_t i = 0; i < d; ++i) hq[(size_t)i] = Q[(size_t)k * d + i];
+        RBL_HIP(hipMemcpyAsync(dq, hq.data(), sizeof(double) * ld, hipMemcpyHostToDevice, sc.s));
+        RBL_HIP(hipMemsetAsync(dprev, 0xff, sizeof(double) * ld, sc.s));   // NaN: what the kernel does not save stays so
+        RBL_HIP(hipStreamSynchronize(sc.s));                              // (hq is reused)
+        inst = WstepInstance{};
+        int it = 0;
+        bool fs_pending = false, fell_back = false;
+        RBL_TRY(run_wstep(wstep, dG, ld, dq, rho_on_dev ? 1.0 : rho, reg, smooth_t, L, tol, max_inner, dw, ww, &it, sc.s,
+                          two_call ? &fs_pending : nullptr, rho_on_dev ? drho : nullptr, want_prev ? dprev : nullptr, want_Gw));
+        if (fs_pending)
+            RBL_TRY(finish_wstep_l1(dG, ld, dq, rho, pen ? 0.0 : reg, L, tol, max_inner, dw, ww, &it, sc.s, &fell_back));
+        RBL_HIP(hipStreamSynchronize(sc.s));
+        const volatile int* pin = ww.pin;
+        const bool lasso = wstep == RBL_WSTEP_L1;
+        if (lasso && !two_call) fell_back = ww.form != 2;
+        const bool gw_ok = want_Gw && (lasso ? (pin[0] == 0 && ww.form == 2) : ww.gw_valid);
+        RBL_HIP(hipMemcpy(W + (size_t)k * d, dw, row, hipMemcpyDeviceToHost));
+        if (Gw) {
+            if (gw_ok) RBL_HIP(hipMemcpy(Gw + (size_t)k * d, ww.Gy, row, hipMemcpyDeviceToHost));
+            else memset(Gw + (size_t)k * d, 0xff, row);
+        }
+        if (Wprev) RBL_HIP(hipMemcpy(Wprev + (size_t)k * d, dprev, row, hipMemcpyDeviceToHost));
+        if (reports) {
+            rbl_wstep_report& r = reports[k];
+            memset(&r, 0, sizeof(r));
+            r.form = ww.form;
+            r.iters = it;
+            r.phase_a = -1;
+            if (lasso) {
+                for (int i = 0; i < 4; ++i) r.fs[i] = pin[i];
+                r.status = pin[0];
+            } else {
+                r.status = wstep == RBL_WSTEP_L2 ? pin[4] : pin[8];
+            }
+            if (inst.nblocks > 0) {   // a persistent launch ran (form 0 with one: its iteration cap handed over to FISTA)
+                r.glds = inst.glds;
+                r.per = inst.per;
+                r.nblocks = inst.nblocks;
+                r.lds_bytes = inst.lds_bytes;
+                if (wstep == RBL_WSTEP_SMOOTH_L1) r.phase_a = pin[10];
+            }
+            r.fell_back = fell_back ? 1 : 0;
+            r.gw_valid = gw_ok ? 1 : 0;
+            r.last_iters = ww.last_iters;
+            r.last_fista = ww.last_fista;
+            r.ncg_skip = ww.ncg_skip;
+            r.ncg_backoff = ww.ncg_backoff;
+            r.launch_seq = ww.launch_seq;
+            r.live_handles = rbl_live_handles(dev);
+        }
+    }
+    return RBL_OK;
+}
+
 int rbl_k_weights(int weight_function, int64_t n, const double* args, int n_args, double* alphas, double* betas) {
     Scratch sc;
     RBL_TRY(scratch_begin(sc, nullptr));

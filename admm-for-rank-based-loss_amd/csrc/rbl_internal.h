@@ -352,6 +352,11 @@ int launch_scatter_z(int64_t n, const double* u, const u32* perm, const int* bra
                      hipStream_t s, const signed char* rs = nullptr);
 
 // ---- wstep.hip --------------------------------------------------------------------------
+// which persistent kernel instance a w-step launched (wp_run fills it through WstepWorkspace::inst: the rbl_k_wstep_seq
+// entry reports it, the solver leaves the pointer NULL, as with SweepInstance)
+struct WstepInstance {
+    int glds, per, nblocks, lds_bytes;   // G rows in LDS, vector elements per thread, blocks launched, dynamic LDS
+};
 struct WstepWorkspace {
     double* yk;     // d
     double* Gy;     // d
@@ -366,9 +371,10 @@ struct WstepWorkspace {
     bool eig_ok;
     int last_iters; // CG iterations of the previous w-step (sizes the next batch)
     int last_fista; // the same for FISTA; pin[6..7] = its (done, iterations)
-    // persistent one-launch w-steps (wstep.hip: k_cg_persist / k_ncg_persist): two sets of barrier counters used
-    // alternately (a launch clears the set of the next one), pin[4..5] / pin[8..9] = their (status, iterations)
-    unsigned* bar;  // [0]: abort word of the persistent kernels (a block that gave up waiting)
+    // persistent one-launch w-steps (wstep.hip: k_cg_persist / k_ncg_persist): pin[4..5] / pin[8..9] = their (status,
+    // iterations), pin[10] = what became of the nonlinear CG's linear first phase.  The blocks meet through the tagged
+    // granules of xch alone (wp_exchange): there are no barrier counters, and nothing is cleared between launches
+    unsigned* bar;  // only [0] is used: the abort word of the persistent kernels (a block that gave up waiting)
     double* xch;    // the two exchange buffers of the matrix-vector products: 8-byte granules {tag | 32 bits}, two per double
     int launch_seq; // launches so far (the tags of a launch: launch_seq << 12 | exchange number)
     bool gw_valid;  // ws.Gy holds G w of the w the last run_wstep returned
@@ -378,6 +384,7 @@ struct WstepWorkspace {
     // pen_l2max = max_j l2_j (FISTA's step constant)
     const double *pen_l1, *pen_l2;
     double pen_l2max;
+    WstepInstance* inst;   // NULL in the solver; the test entry's report of the persistent launch
 };
 constexpr int WSTEP_BAR_UINTS = 2 * 10 * 32;
 constexpr int WSTEP_PERSIST_MAX_LD = 2048;                                  // 8 vector elements per thread of a 256-thread block

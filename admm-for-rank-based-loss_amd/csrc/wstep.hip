@@ -1241,6 +1241,7 @@ int wp_run(const WpPlan& pl, int64_t ld, K const (&kern)[2][2], int* pin, int ma
     double* gw = want_Gw ? ws.Gy : nullptr;
     unsigned long long *x0 = reinterpret_cast<unsigned long long*>(ws.xch), *x1 = x0 + WSTEP_XCH_GRANULES;
     const int g = pl.glds ? 1 : 0, wide = ld <= 4 * WP_THREADS ? 0 : 1;
+    if (ws.inst) *ws.inst = WstepInstance{g, wide ? 8 : 4, pl.nblocks, (int)pl.lds_bytes};
     static size_t lds_set[2][2] = {};   // (one attribute call per instantiation and size, not per launch)
     if (lds_set[g][wide] < pl.lds_bytes) {
         RBL_TRY(wp_set_lds(kern[g][wide], pl.lds_bytes));

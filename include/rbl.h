@@ -119,7 +119,7 @@ typedef struct rbl_solver rbl_solver;
 
 /* ---- lifetime ------------------------------------------------------------------ */
 int  rbl_version(void);
-/* sizeof(rbl_config) (which = 0) / sizeof(rbl_stats) (which = 1) as THIS library was compiled: a binding whose
+/* sizeof(rbl_config) (which = 0) / sizeof(rbl_stats) (which = 1) / sizeof(rbl_wstep_report) (which = 2) as THIS library was compiled: a binding whose
  * structure definitions are older or newer than the library checks them at load time instead of letting rbl_step
  * write past its buffer; -1 for any other `which` */
 int  rbl_sizeof(int which);
@@ -587,6 +587,42 @@ int  rbl_k_wstep(int wstep, int64_t d, const double* G, const double* q, double 
  * else CG; *form as rbl_stats.wstep_form reports it (2 active-set kernel, 0 / 1 CG or FISTA) */
 int  rbl_k_wstep_pen(int64_t d, const double* G, const double* q, double rho, const double* l1, const double* l2,
                      const double* w0, double tol, double* w_out, int* iters, int* form);
+/* K >= 1 w-steps one after another on ONE workspace, as consecutive ADMM iterations run them: step k solves for the
+ * right-hand side Q[k] (K x d), warm-started from the w of step k - 1 (step 0 from w0, NULL = 0), through run_wstep
+ * unchanged - the batch sizes, the back-off of the nonlinear CG's linear phase, the exchange tags and the uncleared
+ * exchange buffers all carry over from step to step.  l1 / l2 (d each, either may be NULL) are per-coordinate penalties
+ * as in rbl_k_wstep_pen (wstep 1 or 2 only; reg is then not used).
+ *   route        0: as the solver runs with one live handle (the persistent kernels where the width allows them);
+ *                1: the batched launches - the workspace has no exchange buffers, the test a second live handle fails too
+ *   launch_seq0  the workspace's launch counter before the first step (0 .. 0xfffff)
+ *   flags        RBL_KW_WANT_GW  ask for G w of the solution (want_Gw);
+ *                RBL_KW_W_PREV   let the lasso kernel save its warm start (w_prev_out);
+ *                RBL_KW_RHO_DEV  the lasso kernel reads rho on the device (the host passes 1.0 in its place, as the
+ *                                speculative w-step does; implies RBL_KW_TWO_CALL, whose second call knows rho);
+ *                RBL_KW_TWO_CALL the lasso as run_wstep(fs_pending) followed by finish_wstep_l1
+ * Outputs, K rows each: W (K x d); Gw (K x d, optional): the workspace's G w where the step declared it valid (the
+ * persistent kernels with RBL_KW_WANT_GW, the lasso kernel when its status is 0), NaN elsewhere; Wprev (K x d, optional):
+ * what the lasso kernel saved, NaN where nothing was; reports (K, optional).
+ * Every argument is checked before anything is allocated (RBL_ERR_INVALID). */
+enum { RBL_KW_WANT_GW = 1, RBL_KW_W_PREV = 2, RBL_KW_RHO_DEV = 4, RBL_KW_TWO_CALL = 8 };
+typedef struct rbl_wstep_report {
+    int32_t form;           /* rbl_stats.wstep_form: 0 batched launches, 1 one persistent launch, 2 active-set lasso kernel */
+    int32_t status;         /* CG / nonlinear CG: 1 converged, 0 iteration cap (the kernel's own word); lasso: fs[0] */
+    int32_t iters;          /* as run_wstep / finish_wstep_l1 return them */
+    int32_t glds, per, nblocks, lds_bytes;   /* the persistent instance the step launched (G rows in LDS, elements per
+                                                thread, blocks, dynamic LDS bytes), 0 when none ran.  form 1 has one; so
+                                                has form 0 with status 0 under wstep 3: the nonlinear CG reached its
+                                                iteration cap and FISTA finished the step */
+    int32_t phase_a;        /* persistent nonlinear CG: linear first phase -1 not tried, 0 dropped, 1 accepted; else -1 */
+    int32_t fs[4];          /* lasso kernel: status (0 converged, 1 overflow, 2 cap), outer iterations, steps, support */
+    int32_t fell_back;      /* lasso: FISTA took over */
+    int32_t gw_valid;       /* Gw[k] holds G w */
+    int32_t last_iters, last_fista, ncg_skip, ncg_backoff, launch_seq;   /* the workspace after the step */
+    int32_t live_handles;   /* solver handles of this process alive on the device during the step */
+} rbl_wstep_report;
+int  rbl_k_wstep_seq(int wstep, int64_t d, const double* G, int K, const double* Q, double rho, double reg, double smooth_t,
+                     const double* l1, const double* l2, const double* w0, double tol, int max_inner, int route,
+                     int launch_seq0, int flags, double* W, double* Gw, double* Wprev, rbl_wstep_report* reports);
 /* sigma generators (src/optim/objective.py:97-164) */
 int  rbl_k_weights(int weight_function, int64_t n, const double* args, int n_args,
                    double* alphas, double* betas);

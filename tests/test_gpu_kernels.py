@@ -289,7 +289,18 @@ def test_persistent_d_space_wsteps_are_optimal(L, d):
     its linear first phase) at widths the iterate tests do not reach, judged by their optimality conditions
     (w_LBFGS.py:11-62): cold start, warm start from the solution of a slightly different right-hand side (the case the
     linear phase is made for), a start far from the solution's Huber pattern, and a Gram matrix with two exactly collinear
-    columns (a wrong pattern then makes the linear system singular)."""
+    columns (a wrong pattern then makes the linear system singular).  Through rbl_k_wstep_seq, which reports what ran:
+    a batched launch in the persistent kernels' place (a second live solver handle makes wp_plan choose it) fails here.
+    At t = 1e-4 the nonlinear CG can reach its cap of 600 iterations (status 0); FISTA then finishes the step from the
+    point reached and the form is 0 although the persistent kernel ran - at t = 1 and 1e-2 that must not happen."""
+    def k_wstep(wstep, G, q, rho, reg, w0, smooth_t=1.0):
+        out = L.k_wstep_seq(wstep, G, q, rho, reg, w0=w0, smooth_t=smooth_t)
+        rep = out["reports"][0]
+        launched = (rep["nblocks"], rep["per"], rep["glds"])
+        assert launched == ((d + 15) // 16, 4 if d <= 1024 else 8, 1 if d <= 1168 else 0), ("no persistent launch", rep)
+        capped = wstep == 3 and smooth_t < 1e-2 and rep["status"] == 0 and rep["iters"] > 600
+        assert (rep["form"] == 1 and rep["status"] == 1) or (capped and rep["form"] == 0), rep
+        return out["w"][0], rep["iters"]
     rng = np.random.default_rng(d)
     n = 3000
     D = rng.standard_normal((n, d))
@@ -301,15 +312,15 @@ def test_persistent_d_space_wsteps_are_optimal(L, d):
     hub = lambda w, t: np.where(np.abs(w) <= t, reg * w / (2 * t), 0.5 * reg * np.sign(w))
     for trial, t in enumerate((1.0, 1e-2, 1e-4)):
         q = D.T @ (c + 0.1 * trial)
-        w_r, _ = L.k_wstep(2, G, q, rho, reg, np.zeros(d))
+        w_r, _ = k_wstep(2, G, q, rho, reg, np.zeros(d))
         assert np.max(np.abs(rho * (G @ w_r - q) + reg * w_r)) <= 1e-10 * np.max(np.abs(rho * q)), ("ridge", d, t)
         scale = max(np.max(np.abs(rho * q)), 0.5 * reg)
-        w_c, it_c = L.k_wstep(3, G, q, rho, reg, np.zeros(d), smooth_t=t)                       # cold
+        w_c, it_c = k_wstep(3, G, q, rho, reg, np.zeros(d), smooth_t=t)                       # cold
         assert np.max(np.abs(rho * (G @ w_c - q) + hub(w_c, t))) <= 1e-10 * scale, ("cold", d, t, it_c)
         q2 = q + 1e-4 * np.max(np.abs(q)) * rng.standard_normal(d)
-        w_w, it_w = L.k_wstep(3, G, q2, rho, reg, w_c, smooth_t=t)                               # warm: pattern (nearly) stable
+        w_w, it_w = k_wstep(3, G, q2, rho, reg, w_c, smooth_t=t)                               # warm: pattern (nearly) stable
         assert np.max(np.abs(rho * (G @ w_w - q2) + hub(w_w, t))) <= 1e-10 * scale, ("warm", d, t, it_w)
-        w_f, it_f = L.k_wstep(3, G, q, rho, reg, 50.0 * rng.standard_normal(d), smooth_t=t)      # far: every sign assumed wrong
+        w_f, it_f = k_wstep(3, G, q, rho, reg, 50.0 * rng.standard_normal(d), smooth_t=t)      # far: every sign assumed wrong
         assert np.max(np.abs(rho * (G @ w_f - q) + hub(w_f, t))) <= 1e-10 * scale, ("far", d, t, it_f)
         # (with collinear columns the minimiser need not be unique outside the quadratic zone: compare the objective)
         phi = lambda w: (0.5 * rho * w @ (G @ w) - rho * q @ w
