@@ -39,7 +39,7 @@ def SGDmethod(X, y, weight_function, loss, l2_reg=None, l1_reg=None, lossB=None,
     for it in range(max_iter):
         order = torch.randperm(n).numpy()                                         # start_epoch, algorithms.py:80-82
         rands = np.array([float(torch.rand(1)) for _ in range(steps)], dtype=np.float32) if l1_reg else None
-        opt.sgd_epoch(order[: min(n, steps * batch_size)], steps, batch_size, ab, bb, lr, rands)   # :84-93 x epoch_len
+        opt.sgd_epoch(order[: steps * batch_size], steps, batch_size, ab, bb, lr, rands)   # :84-93 x epoch_len
         if train_loss is not None:
             train_losses.append(train_loss(wt()))
         test_losses.append(test_loss(wt()))

@@ -79,9 +79,8 @@ __global__ __launch_bounds__(BL_SGD_THREADS) void k_bl_sgd_epoch(const double* _
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     constexpr int NW = BL_SGD_THREADS / 64;
     for (int s = 0; s < steps; ++s) {
-        long long b0 = (long long)s * batch, b1 = b0 + batch;
-        if (b1 > n) b1 = n;
-        const int b = (int)(b1 - b0);                        // rows of this mini-batch (algorithms.py:85-88)
+        const long long b0 = (long long)s * batch;
+        const int b = batch;                                 // rows of this mini-batch: always whole (rbl_bl_sgd_epoch)
         if (tid < b) s_off[tid] = (long long)order[b0 + tid] * ld;
         __syncthreads();
         for (int r0 = wave * 4; r0 < b; r0 += NW * 4) {      // logits: 4 rows per wave at a time
@@ -321,15 +320,22 @@ int rbl_bl_sgd_epoch(rbl_baseline* h, const int32_t* order, int steps, int batch
         rbl_set_error("sgd_epoch: bad arguments (batch must be 1..%d)", BL_MAX_BATCH);
         return RBL_ERR_INVALID;
     }
-    if ((long long)(steps - 1) * batch >= h->n && steps > 0) {
-        rbl_set_error("sgd_epoch: %d mini-batches of %d rows exceed the %lld rows", steps, batch, (long long)h->n);
+    const long long cnt = (long long)steps * batch;
+    if (cnt > h->n) {
+        // the call carries the `batch`-sample weights; the reference weights a short last mini-batch of b < batch rows
+        // with weight_function(b) (objective.py:72-77), which this call does not have
+        rbl_set_error("sgd_epoch: %d mini-batches of %d rows exceed the %lld rows: a short last mini-batch takes the weights "
+                      "of its own length, and alphas_b / betas_b are the %d-sample weights",
+                      steps, batch, (long long)h->n, batch);
+        return RBL_ERR_INVALID;
+    }
+    if (steps > 0 && h->l1 != 0.0 && !rands) {
+        rbl_set_error("sgd_epoch: rands is NULL on a handle with l1_reg != 0 (one torch.rand(1) per step)");
         return RBL_ERR_INVALID;
     }
     RBL_HIP(hipSetDevice(h->device));
     if (steps == 0) return RBL_OK;
     hipStream_t s = h->stream;
-    long long cnt = (long long)steps * batch;
-    if (cnt > h->n) cnt = h->n;
     for (long long i = 0; i < cnt; ++i)
         if (order[i] < 0 || order[i] >= h->n) {
             rbl_set_error("sgd_epoch: row index %d out of range", order[i]);
@@ -364,6 +370,10 @@ int rbl_bl_lsvrg_epoch(rbl_baseline* h, const double* alphas, const double* beta
             rbl_set_error("lsvrg_epoch: sample %d out of range", samples[i]);
             return RBL_ERR_INVALID;
         }
+    if (steps > 0 && h->l1 != 0.0 && !rands) {
+        rbl_set_error("lsvrg_epoch: rands is NULL on a handle with l1_reg != 0 (one torch.rand(1) per step)");
+        return RBL_ERR_INVALID;
+    }
     RBL_HIP(hipSetDevice(h->device));
     hipStream_t s = h->stream;
     const long long n = h->n, ld = h->ld;

@@ -642,8 +642,12 @@ int  rbl_bl_destroy(rbl_baseline* h);
 int  rbl_bl_set_w(rbl_baseline* h, const double* w);
 int  rbl_bl_get_w(rbl_baseline* h, double* w);
 /* StochasticSubgradientMethod.start_epoch + `steps` x step (algorithms.py:80-93): mini-batch s = rows
- * order[s*batch .. min(n, (s+1)*batch)); alphas_b / betas_b: the `batch`-sample weights (objective.py:72-75;
- * betas_b NULL unless EHRM); rands: one torch.rand(1) per step for the l1 subgradient at 0 (NULL without l1_reg) */
+ * order[s*batch .. (s+1)*batch); alphas_b / betas_b: the `batch`-sample weights (objective.py:72-75;
+ * betas_b NULL unless EHRM); rands: one torch.rand(1) per step for the l1 subgradient at 0 (NULL without l1_reg).
+ * Every mini-batch is whole: steps * batch > n is RBL_ERR_INVALID, because the reference weights a short last
+ * mini-batch of b < batch rows with the b-sample weights (objective.py:72-77), which this call does not carry
+ * (SGDmethod never makes one: steps = min(100, n / batch)).  rands == NULL on a handle created with l1_reg != 0 is
+ * RBL_ERR_INVALID when steps > 0, here and in rbl_bl_lsvrg_epoch.  A refused call leaves w as it was. */
 int  rbl_bl_sgd_epoch(rbl_baseline* h, const int32_t* order, int steps, int batch, const double* alphas_b,
                       const double* betas_b, double lr, const float* rands);
 /* LSVRG.start_epoch + `steps` x step (algorithms.py:183-253): alphas / betas are the n-sample weights; samples[s]
