@@ -214,6 +214,10 @@ SIGNATURES = {
     "rbl_k_sweep_q": (C.c_int, [C.c_int, C.c_int64, C.c_int64, _P, _P, C.c_int, _P, _P]),
     "rbl_k_sweep_v_multi": (C.c_int, [C.c_int, C.c_int64, C.c_int64, C.c_int, _P, _P, _P, _P, _P, C.c_int, _P, _P, _P, _P]),
     "rbl_k_sweep_q_multi": (C.c_int, [C.c_int, C.c_int64, C.c_int64, C.c_int, _P, _P, C.c_int, _P, _P]),
+    "rbl_k_pass_v": (C.c_int, [C.c_int, C.c_int64, C.c_int64, _P, _P, C.c_int, _P, _P]),
+    "rbl_k_pass_q": (C.c_int, [C.c_int, C.c_int64, C.c_int64, _P, _P, C.c_int, _P, _P]),
+    "rbl_k_pass_colstats": (C.c_int, [C.c_int, C.c_int64, C.c_int64, _P, C.c_int, _P, _P, _P]),
+    "rbl_k_gram_full": (C.c_int, [C.c_int, C.c_int64, C.c_int64, _P, C.c_int, _P, _P]),
     "rbl_k_gram": (C.c_int, [C.c_int, C.c_int64, C.c_int64, _P, _P]),
     "rbl_k_csr_gemv": (C.c_int, [C.c_int64, C.c_int64, _P, _P, _P, _P, _P]),
     "rbl_k_csr_gemvt": (C.c_int, [C.c_int64, C.c_int64, _P, _P, _P, _P, _P]),
@@ -478,6 +482,59 @@ def k_sweep_q_multi(D, Cm, storage="f32", num_cu=1):
     inst = np.zeros(5, dtype=np.int32)
     check(load().rbl_k_sweep_q_multi(STORAGE[storage], n, d, k, ptr(D), ptr(Cm), int(num_cu), ptr(Q), ptr(inst)))
     return dict(q=Q, instance=_instance(inst))
+
+
+def _pass_instance(a):
+    """what a rbl_k_pass_* call reports: ("gemv", LPR, P, U, blocks), ("gemvt", TPR, PJ, U, row blocks, column tiles) or,
+    where launch_gemvt handed the pass to the Q-only kernel, ("sweep_q", P, R, S, blocks)"""
+    a = [int(x) for x in a]
+    if a[0] == 1:
+        return ("sweep_q", a[1], a[2], a[3], a[4])
+    return tuple(a[1:])
+
+
+def k_pass_v(D, w, storage="f32", num_cu=1):
+    """v = D w through launch_gemv with the grid of `num_cu` compute units (include/rbl.h: rbl_k_pass_v); rows the pass
+    did not write come back NaN.  Returns a dict: v, instance = (LPR, P, U, blocks)."""
+    D, w = f64(D), f64(w).reshape(-1)
+    n, d = D.shape
+    v = np.empty(n)
+    inst = np.zeros(6, dtype=np.int32)
+    check(load().rbl_k_pass_v(STORAGE[storage], n, d, ptr(D), ptr(w), int(num_cu), ptr(v), ptr(inst)))
+    return dict(v=v, instance=_pass_instance(inst)[:4])
+
+
+def k_pass_q(D, c, storage="f32", num_cu=1):
+    """q = D^T c through launch_gemvt; q has storage_ld(d) entries, the pad included (rbl_k_pass_q).  instance =
+    (TPR, PJ, U, row blocks, column tiles), or ("sweep_q", P, R, S, blocks) at the widths of the Q-only pass."""
+    D, c = f64(D), f64(c).reshape(-1)
+    n, d = D.shape
+    q = np.empty(storage_ld(d, storage))
+    inst = np.zeros(6, dtype=np.int32)
+    check(load().rbl_k_pass_q(STORAGE[storage], n, d, ptr(D), ptr(c), int(num_cu), ptr(q), ptr(inst)))
+    return dict(q=q, instance=_pass_instance(inst))
+
+
+def k_pass_colstats(D, storage="f32", num_cu=1):
+    """column sums and sums of squares through launch_colstats, ld entries each (rbl_k_pass_colstats)"""
+    D = f64(D)
+    n, d = D.shape
+    ld = storage_ld(d, storage)
+    s1, s2 = np.empty(ld), np.empty(ld)
+    inst = np.zeros(6, dtype=np.int32)
+    check(load().rbl_k_pass_colstats(STORAGE[storage], n, d, ptr(D), int(num_cu), ptr(s1), ptr(s2), ptr(inst)))
+    return dict(sum=s1, sumsq=s2, instance=_pass_instance(inst))
+
+
+def k_gram_full(D, storage="f32", num_cu=1):
+    """G = D^T D through launch_gram, all ld x ld entries; plan = (ntiles, npairs, ksplit, rows_per_split)"""
+    D = f64(D)
+    n, d = D.shape
+    ld = storage_ld(d, storage)
+    G = np.empty((ld, ld))
+    plan = np.zeros(4, dtype=np.int64)
+    check(load().rbl_k_gram_full(STORAGE[storage], n, d, ptr(D), int(num_cu), ptr(G), ptr(plan)))
+    return dict(G=G, plan=tuple(int(x) for x in plan))
 
 
 def k_gram(D, storage="f32"):

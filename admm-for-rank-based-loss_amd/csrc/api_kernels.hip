@@ -643,6 +643,110 @@ int rbl_k_sweep_q_multi(int storage, int64_t n, int64_t d, int k, const double* 
     return RBL_OK;
 }
 
+// ---- the plain passes (sweep.hip: k_gemv, k_gemvt, its column-statistics variant, k_colreduce) and the Gram kernels on
+// prescribed inputs with a caller-chosen grid (rbl_k_pass_*, rbl_k_gram_full): the launchers of a solve, unchanged
+namespace {
+void pass_out(int* instance, const PassInstance& in) {
+    if (!instance) return;
+    instance[0] = in.route;
+    instance[1] = in.a;
+    instance[2] = in.p;
+    instance[3] = in.u;
+    instance[4] = in.blocks;
+    instance[5] = in.tiles;
+}
+}  // namespace
+
+int rbl_k_pass_v(int storage, int64_t n, int64_t d, const double* D, const double* w, int num_cu, double* v, int* instance) {
+    const char* who = "rbl_k_pass_v";
+    Scratch sc;
+    int64_t ld = 0;
+    RBL_TRY(sweep_begin(sc, who, storage, n, d, num_cu, &ld));
+    void* Dd = nullptr;
+    RBL_TRY(upload_matrix(sc, storage, n, d, D, &Dd, &ld));
+    double *dw = nullptr, *dv = nullptr;
+    RBL_TRY(cols_upload(sc, &dw, w, 1, d, ld));
+    RBL_TRY(rows_alloc(sc, &dv, n, 1, nullptr, 0));
+    PassInstance inst{};
+    RBL_TRY(launch_gemv(storage, Dd, n, ld, dw, dv, num_cu, sc.s, &inst));
+    RBL_TRY(rows_fetch(sc, who, "v", dv, n, 1, v));
+    pass_out(instance, inst);
+    return RBL_OK;
+}
+
+int rbl_k_pass_q(int storage, int64_t n, int64_t d, const double* D, const double* c, int num_cu, double* q_ld, int* instance) {
+    const char* who = "rbl_k_pass_q";
+    Scratch sc;
+    int64_t ld = 0;
+    RBL_TRY(sweep_begin(sc, who, storage, n, d, num_cu, &ld));
+    void* Dd = nullptr;
+    RBL_TRY(upload_matrix(sc, storage, n, d, D, &Dd, &ld));
+    double *dc = nullptr, *slab = nullptr, *dq = nullptr;
+    RBL_TRY(sc.upload(&dc, c, (size_t)n));
+    // gemvt_slab_rows(num_cu) rows; where launch_gemvt hands the pass to launch_sweep_q, that launcher's own rule (with the
+    // device's CU count the first covers the second, with num_cu = 1 it does not)
+    size_t slab_rows = (size_t)gemvt_slab_rows(num_cu);
+    if (sweep_v_supported(storage, ld)) slab_rows = std::max(slab_rows, (size_t)sweep_erm_slab_rows(num_cu));
+    RBL_TRY(sc.mem.alloc(&slab, slab_rows * ld));
+    RBL_TRY(sc.mem.alloc(&dq, (size_t)ld));
+    RBL_HIP(hipMemsetAsync(dq, 0xff, sizeof(double) * ld, sc.s));   // (NaN: every entry, the pad included, must be written)
+    PassInstance inst{};
+    RBL_TRY(launch_gemvt(storage, Dd, n, ld, dc, slab, dq, num_cu, sc.s, nullptr, 0, &inst));
+    RBL_HIP(hipMemcpyAsync(q_ld, dq, sizeof(double) * ld, hipMemcpyDeviceToHost, sc.s));
+    RBL_HIP(hipStreamSynchronize(sc.s));
+    pass_out(instance, inst);
+    return RBL_OK;
+}
+
+int rbl_k_pass_colstats(int storage, int64_t n, int64_t d, const double* D, int num_cu, double* sum_ld, double* sumsq_ld,
+                        int* instance) {
+    const char* who = "rbl_k_pass_colstats";
+    Scratch sc;
+    int64_t ld = 0;
+    RBL_TRY(sweep_begin(sc, who, storage, n, d, num_cu, &ld));
+    if (storage == RBL_STORE_F16) {   // refused before anything is uploaded; launch_colstats refuses it as well
+        rbl_set_error("%s: colstats: not available for RBL_STORE_F16", who);
+        return RBL_ERR_INVALID;
+    }
+    void* Dd = nullptr;
+    RBL_TRY(upload_matrix(sc, storage, n, d, D, &Dd, &ld));
+    double *slab = nullptr, *ds = nullptr;
+    RBL_TRY(sc.mem.alloc(&slab, (size_t)gemvt_slab_rows(num_cu) * ld * 2));   // (sums | sums of squares, as a handle's slab)
+    RBL_TRY(sc.mem.alloc(&ds, (size_t)ld * 2));
+    RBL_HIP(hipMemsetAsync(ds, 0xff, sizeof(double) * ld * 2, sc.s));
+    PassInstance inst{};
+    RBL_TRY(launch_colstats(storage, Dd, n, ld, slab, ds, ds + ld, num_cu, sc.s, &inst));
+    RBL_HIP(hipMemcpyAsync(sum_ld, ds, sizeof(double) * ld, hipMemcpyDeviceToHost, sc.s));
+    RBL_HIP(hipMemcpyAsync(sumsq_ld, ds + ld, sizeof(double) * ld, hipMemcpyDeviceToHost, sc.s));
+    RBL_HIP(hipStreamSynchronize(sc.s));
+    pass_out(instance, inst);
+    return RBL_OK;
+}
+
+int rbl_k_gram_full(int storage, int64_t n, int64_t d, const double* D, int num_cu, double* G_ld, int64_t* plan) {
+    const char* who = "rbl_k_gram_full";
+    Scratch sc;
+    int64_t ld = 0;
+    RBL_TRY(sweep_begin(sc, who, storage, n, d, num_cu, &ld));
+    void* Dd = nullptr;
+    RBL_TRY(upload_matrix(sc, storage, n, d, D, &Dd, &ld));
+    double *slab = nullptr, *dG = nullptr;
+    RBL_TRY(sc.mem.alloc((unsigned char**)&slab, gram_slab_bytes(ld, num_cu, n)));
+    RBL_TRY(sc.mem.alloc(&dG, (size_t)ld * ld));
+    RBL_HIP(hipMemsetAsync(dG, 0xff, sizeof(double) * ld * ld, sc.s));
+    GramPlanOut g{};
+    RBL_TRY(launch_gram(storage, Dd, n, ld, d, slab, dG, num_cu, sc.s, &g));
+    RBL_HIP(hipMemcpyAsync(G_ld, dG, sizeof(double) * ld * ld, hipMemcpyDeviceToHost, sc.s));
+    RBL_HIP(hipStreamSynchronize(sc.s));
+    if (plan) {
+        plan[0] = g.ntiles;
+        plan[1] = g.npairs;
+        plan[2] = g.ksplit;
+        plan[3] = g.rows_per_split;
+    }
+    return RBL_OK;
+}
+
 int rbl_k_gram(int storage, int64_t n, int64_t d, const double* D, double* G) {
     Scratch sc;
     int num_cu = 256;

@@ -200,11 +200,12 @@ size_t gram_slab_bytes(int64_t ld, int num_cu, int64_t n) {
 }
 
 int launch_gram(int storage, const void* D, int64_t n, int64_t ld, int64_t d, double* slab, double* G, int num_cu,
-                hipStream_t s) {
+                hipStream_t s, GramPlanOut* plan) {
     if (storage == RBL_STORE_CSR) return launch_csr_gram((const CsrStore*)D, n, ld, d, slab, G, num_cu, s);   // spmv.hip
     RBL_HIP(hipMemsetAsync(G, 0, sizeof(double) * ld * ld, s));
     if (n <= 0) return RBL_OK;
     GramPlan g = gram_plan(ld, n, num_cu);
+    if (plan) *plan = GramPlanOut{g.ntiles, g.npairs, g.ksplit, g.rows_per_split};
     dim3 grid(g.npairs, g.ksplit);
     if (storage == RBL_STORE_F32)
         hipLaunchKernelGGL(k_gram<float>, grid, dim3(256), 0, s, (const float*)D, (long long)n, (long long)ld,

@@ -172,20 +172,36 @@ struct SeamRec {
 };
 
 // ---- sweep.hip ------------------------------------------------------------------------
+// which kernel instance launch_gemv / launch_gemvt / launch_colstats ran (optional trailing out-parameter: the
+// rbl_k_pass_* entry points report it, the solver leaves it NULL; RBL_STORE_CSR does not fill it).
+//   route PASS_ROUTE_PLAIN, k_gemv:   a = LPR lanes per row, p = P passes (0: w staged in LDS), u = U row groups in flight,
+//                                     blocks launched, tiles = 1
+//   route PASS_ROUTE_PLAIN, k_gemvt:  a = TPR threads per row, p = PJ packets per thread, u = U steps in flight, blocks =
+//                                     row blocks nb (slab rows), tiles = column tiles (gridDim.y)
+//   route PASS_ROUTE_SWEEP_Q:         launch_gemvt handed the pass to launch_sweep_q: a, p, u, blocks = the SweepInstance's
+//                                     p, r, s, blocks; tiles = 0
+enum { PASS_ROUTE_PLAIN = 0, PASS_ROUTE_SWEEP_Q = 1 };
+struct PassInstance {
+    int route, a, p, u, blocks, tiles;
+};
+inline void pass_report(PassInstance* inst, int route, int a, int p, int u, int blocks, int tiles) {
+    if (inst) *inst = PassInstance{route, a, p, u, blocks, tiles};
+}
 // v = D w : D is n x ld row-major (ld % 4 == 0, fp16 storage: ld % 8 == 0; columns >= d are zero)
 int launch_gemv(int storage, const void* D, int64_t n, int64_t ld, const double* w, double* v,
-                int num_cu, hipStream_t s);
+                int num_cu, hipStream_t s, PassInstance* inst = nullptr);
 // q = D^T c : partial column sums go to slab (gemvt_slab_rows() x ld doubles), then q
 int gemvt_slab_rows(int num_cu);
 // RBL_STORE_CSR: the slab holds one partial sum per segment; slab_doubles is what it has room for (a slab too small is
 // RBL_ERR_STATE, never a write past its end)
 int launch_gemvt(int storage, const void* D, int64_t n, int64_t ld, const double* c, double* slab,
-                 double* q, int num_cu, hipStream_t s, hipEvent_t main_done = nullptr, size_t slab_doubles = 0);
+                 double* q, int num_cu, hipStream_t s, hipEvent_t main_done = nullptr, size_t slab_doubles = 0,
+                 PassInstance* inst = nullptr);
 int launch_D_to_f64(int storage, const void* D, int64_t ld, int64_t n, int64_t d, double* out,
                     hipStream_t s);
 // column sums / sums of squares (slab-reduced, deterministic) and in-place standardisation
 int launch_colstats(int storage, const void* D, int64_t n, int64_t ld, double* slab, double* sum,
-                    double* sumsq, int num_cu, hipStream_t s);
+                    double* sumsq, int num_cu, hipStream_t s, PassInstance* inst = nullptr);
 int launch_standardize_negy(int storage, void* D, int64_t n, int64_t ld, int64_t d, const double* mean,
                             const double* inv_std, const signed char* ysign, hipStream_t s);
 // typed sources (rbl_set_data_from): X of element type dtype (RBL_DTYPE_*) already on the device, ds source columns.
@@ -480,8 +496,14 @@ int launch_ridge_eig(const double* G, const double* Vt, const double* V, const d
 
 // ---- gram.hip ---------------------------------------------------------------------------
 size_t gram_slab_bytes(int64_t d, int num_cu, int64_t n);
+// the launch plan of the dense path (optional out-parameter of launch_gram: rbl_k_gram_full reports it): tiles of 128
+// columns, tile pairs ti <= tj, row splits (slab tiles per pair) and rows per split
+struct GramPlanOut {
+    int ntiles, npairs, ksplit;
+    long long rows_per_split;
+};
 int launch_gram(int storage, const void* D, int64_t n, int64_t ld, int64_t d, double* slab, double* G,
-                int num_cu, hipStream_t s);
+                int num_cu, hipStream_t s, GramPlanOut* plan = nullptr);
 
 // ---- spmv.hip: RBL_STORE_CSR - D as its non-zero entries --------------------------------------------------------
 // The descriptor a handle's D points at (launch_gemv / launch_gemvt / launch_gram take it as `D` with storage

@@ -193,7 +193,8 @@ __global__ __launch_bounds__(256) void k_gemv(const T* __restrict__ D, long long
 }
 
 template <typename T, int LPR>
-int gemv_dispatch(const T* D, long long n, long long ld, const double* w, double* v, int num_cu, hipStream_t s) {
+int gemv_dispatch(const T* D, long long n, long long ld, const double* w, double* v, int num_cu, hipStream_t s,
+                  PassInstance* inst) {
     constexpr int E = Pkt<T>::E;
     const long long PK = ld / E;
     const long long passes = (PK + LPR - 1) / LPR;
@@ -204,16 +205,21 @@ int gemv_dispatch(const T* D, long long n, long long ld, const double* w, double
     if constexpr (LPR < 64) {
         // a row fits one pass of its lane group
         hipLaunchKernelGGL((k_gemv<T, LPR, 1, 4>), dim3(grid), dim3(256), 0, s, D, n, ld, w, v);
+        pass_report(inst, PASS_ROUTE_PLAIN, LPR, 1, 4, grid, 1);
     } else {
-        if (passes == 1)
+        if (passes == 1) {
             hipLaunchKernelGGL((k_gemv<T, LPR, 1, 4>), dim3(grid), dim3(256), 0, s, D, n, ld, w, v);
-        else if (passes == 2)
+            pass_report(inst, PASS_ROUTE_PLAIN, LPR, 1, 4, grid, 1);
+        } else if (passes == 2) {
             hipLaunchKernelGGL((k_gemv<T, LPR, 2, 4>), dim3(grid), dim3(256), 0, s, D, n, ld, w, v);
-        else if (passes <= 4)
+            pass_report(inst, PASS_ROUTE_PLAIN, LPR, 2, 4, grid, 1);
+        } else if (passes <= 4) {
             hipLaunchKernelGGL((k_gemv<T, LPR, 4, 2>), dim3(grid), dim3(256), 0, s, D, n, ld, w, v);
-        else if (passes <= 8)
+            pass_report(inst, PASS_ROUTE_PLAIN, LPR, 4, 2, grid, 1);
+        } else if (passes <= 8) {
             hipLaunchKernelGGL((k_gemv<T, LPR, 8, 1>), dim3(grid), dim3(256), 0, s, D, n, ld, w, v);
-        else {
+            pass_report(inst, PASS_ROUTE_PLAIN, LPR, 8, 1, grid, 1);
+        } else {
             size_t lds = (size_t)ld * sizeof(double);
             if (lds > 150 * 1024) {
                 rbl_set_error("gemv: d too large for the LDS-staged path (ld=%lld)", ld);
@@ -224,6 +230,7 @@ int gemv_dispatch(const T* D, long long n, long long ld, const double* w, double
                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
             }
             hipLaunchKernelGGL((k_gemv<T, LPR, 0, 4>), dim3(grid), dim3(256), lds, s, D, n, ld, w, v);
+            pass_report(inst, PASS_ROUTE_PLAIN, LPR, 0, 4, grid, 1);
         }
     }
     RBL_HIP(hipGetLastError());
@@ -231,15 +238,15 @@ int gemv_dispatch(const T* D, long long n, long long ld, const double* w, double
 }
 
 template <typename T>
-int gemv_T(const T* D, long long n, long long ld, const double* w, double* v, int num_cu, hipStream_t s) {
+int gemv_T(const T* D, long long n, long long ld, const double* w, double* v, int num_cu, hipStream_t s, PassInstance* inst) {
     const long long PK = ld / Pkt<T>::E;
-    if (PK > 32) return gemv_dispatch<T, 64>(D, n, ld, w, v, num_cu, s);
-    if (PK > 16) return gemv_dispatch<T, 32>(D, n, ld, w, v, num_cu, s);
-    if (PK > 8) return gemv_dispatch<T, 16>(D, n, ld, w, v, num_cu, s);
-    if (PK > 4) return gemv_dispatch<T, 8>(D, n, ld, w, v, num_cu, s);
-    if (PK > 2) return gemv_dispatch<T, 4>(D, n, ld, w, v, num_cu, s);
-    if (PK > 1) return gemv_dispatch<T, 2>(D, n, ld, w, v, num_cu, s);
-    return gemv_dispatch<T, 1>(D, n, ld, w, v, num_cu, s);
+    if (PK > 32) return gemv_dispatch<T, 64>(D, n, ld, w, v, num_cu, s, inst);
+    if (PK > 16) return gemv_dispatch<T, 32>(D, n, ld, w, v, num_cu, s, inst);
+    if (PK > 8) return gemv_dispatch<T, 16>(D, n, ld, w, v, num_cu, s, inst);
+    if (PK > 4) return gemv_dispatch<T, 8>(D, n, ld, w, v, num_cu, s, inst);
+    if (PK > 2) return gemv_dispatch<T, 4>(D, n, ld, w, v, num_cu, s, inst);
+    if (PK > 1) return gemv_dispatch<T, 2>(D, n, ld, w, v, num_cu, s, inst);
+    return gemv_dispatch<T, 1>(D, n, ld, w, v, num_cu, s, inst);
 }
 
 // ---------------------------------------------------------------------------- q = D^T c
@@ -384,7 +391,7 @@ constexpr int GEMVT_BLOCKS_PER_CU = RBL_GEMVT_BPC;
 
 template <typename T, int TPR, bool SQ>
 int gemvt_dispatch(const T* D, long long n, long long ld, const double* c, double* slab, double* slab2,
-                   int nblocks, hipStream_t s) {
+                   int nblocks, hipStream_t s, PassInstance* inst) {
     constexpr int E = Pkt<T>::E;
     const long long PK = ld / E;
     long long pj = (PK + TPR - 1) / TPR;
@@ -396,15 +403,21 @@ int gemvt_dispatch(const T* D, long long n, long long ld, const double* c, doubl
     dim3 grid(nblocks, ytiles);
     if constexpr (TPR < 256) {
         hipLaunchKernelGGL((k_gemvt<T, TPR, 1, 8, SQ>), grid, dim3(256), 0, s, D, n, ld, c, slab, slab2);
+        pass_report(inst, PASS_ROUTE_PLAIN, TPR, 1, 8, nblocks, ytiles);
     } else {
-        if (pj == 1)
+        if (pj == 1) {
             hipLaunchKernelGGL((k_gemvt<T, TPR, 1, RBL_GEMVT_U, SQ>), grid, dim3(256), 0, s, D, n, ld, c, slab, slab2);
-        else if (pj == 2)
+            pass_report(inst, PASS_ROUTE_PLAIN, TPR, 1, RBL_GEMVT_U, nblocks, ytiles);
+        } else if (pj == 2) {
             hipLaunchKernelGGL((k_gemvt<T, TPR, 2, 4, SQ>), grid, dim3(256), 0, s, D, n, ld, c, slab, slab2);
-        else if (pj <= 4)
+            pass_report(inst, PASS_ROUTE_PLAIN, TPR, 2, 4, nblocks, ytiles);
+        } else if (pj <= 4) {
             hipLaunchKernelGGL((k_gemvt<T, TPR, 4, 2, SQ>), grid, dim3(256), 0, s, D, n, ld, c, slab, slab2);
-        else
+            pass_report(inst, PASS_ROUTE_PLAIN, TPR, 4, 2, nblocks, ytiles);
+        } else {
             hipLaunchKernelGGL((k_gemvt<T, TPR, 8, 1, SQ>), grid, dim3(256), 0, s, D, n, ld, c, slab, slab2);
+            pass_report(inst, PASS_ROUTE_PLAIN, TPR, 8, 1, nblocks, ytiles);
+        }
     }
     RBL_HIP(hipGetLastError());
     return RBL_OK;
@@ -412,17 +425,17 @@ int gemvt_dispatch(const T* D, long long n, long long ld, const double* c, doubl
 
 template <typename T, bool SQ>
 int gemvt_T(const T* D, long long n, long long ld, const double* c, double* slab, double* slab2, int nblocks,
-            hipStream_t s) {
+            hipStream_t s, PassInstance* inst) {
     const long long PK = ld / Pkt<T>::E;
-    if (PK > 128) return gemvt_dispatch<T, 256, SQ>(D, n, ld, c, slab, slab2, nblocks, s);
-    if (PK > 64) return gemvt_dispatch<T, 128, SQ>(D, n, ld, c, slab, slab2, nblocks, s);
-    if (PK > 32) return gemvt_dispatch<T, 64, SQ>(D, n, ld, c, slab, slab2, nblocks, s);
-    if (PK > 16) return gemvt_dispatch<T, 32, SQ>(D, n, ld, c, slab, slab2, nblocks, s);
-    if (PK > 8) return gemvt_dispatch<T, 16, SQ>(D, n, ld, c, slab, slab2, nblocks, s);
-    if (PK > 4) return gemvt_dispatch<T, 8, SQ>(D, n, ld, c, slab, slab2, nblocks, s);
-    if (PK > 2) return gemvt_dispatch<T, 4, SQ>(D, n, ld, c, slab, slab2, nblocks, s);
-    if (PK > 1) return gemvt_dispatch<T, 2, SQ>(D, n, ld, c, slab, slab2, nblocks, s);
-    return gemvt_dispatch<T, 1, SQ>(D, n, ld, c, slab, slab2, nblocks, s);
+    if (PK > 128) return gemvt_dispatch<T, 256, SQ>(D, n, ld, c, slab, slab2, nblocks, s, inst);
+    if (PK > 64) return gemvt_dispatch<T, 128, SQ>(D, n, ld, c, slab, slab2, nblocks, s, inst);
+    if (PK > 32) return gemvt_dispatch<T, 64, SQ>(D, n, ld, c, slab, slab2, nblocks, s, inst);
+    if (PK > 16) return gemvt_dispatch<T, 32, SQ>(D, n, ld, c, slab, slab2, nblocks, s, inst);
+    if (PK > 8) return gemvt_dispatch<T, 16, SQ>(D, n, ld, c, slab, slab2, nblocks, s, inst);
+    if (PK > 4) return gemvt_dispatch<T, 8, SQ>(D, n, ld, c, slab, slab2, nblocks, s, inst);
+    if (PK > 2) return gemvt_dispatch<T, 4, SQ>(D, n, ld, c, slab, slab2, nblocks, s, inst);
+    if (PK > 1) return gemvt_dispatch<T, 2, SQ>(D, n, ld, c, slab, slab2, nblocks, s, inst);
+    return gemvt_dispatch<T, 1, SQ>(D, n, ld, c, slab, slab2, nblocks, s, inst);
 }
 
 int gemvt_blocks(int num_cu, long long n) {
@@ -782,30 +795,35 @@ int launch_csr_expand(int dtype, int index_type, void* Xc, int64_t ldc, int64_t 
 int gemvt_slab_rows(int num_cu) { return num_cu * GEMVT_BLOCKS_PER_CU; }
 
 int launch_gemv(int storage, const void* D, int64_t n, int64_t ld, const double* w, double* v, int num_cu,
-                hipStream_t s) {
+                hipStream_t s, PassInstance* inst) {
     if (n <= 0) return RBL_OK;
     if (storage == RBL_STORE_CSR) return launch_csr_gemv((const CsrStore*)D, n, w, v, num_cu, s);   // spmv.hip
-    if (storage == RBL_STORE_F32) return gemv_T<float>((const float*)D, n, ld, w, v, num_cu, s);
-    if (storage == RBL_STORE_F16) return gemv_T<rbl_half>((const rbl_half*)D, n, ld, w, v, num_cu, s);
-    return gemv_T<double>((const double*)D, n, ld, w, v, num_cu, s);
+    if (storage == RBL_STORE_F32) return gemv_T<float>((const float*)D, n, ld, w, v, num_cu, s, inst);
+    if (storage == RBL_STORE_F16) return gemv_T<rbl_half>((const rbl_half*)D, n, ld, w, v, num_cu, s, inst);
+    return gemv_T<double>((const double*)D, n, ld, w, v, num_cu, s, inst);
 }
 
 int launch_gemvt(int storage, const void* D, int64_t n, int64_t ld, const double* c, double* slab, double* q,
-                 int num_cu, hipStream_t s, hipEvent_t main_done, size_t slab_doubles) {
+                 int num_cu, hipStream_t s, hipEvent_t main_done, size_t slab_doubles, PassInstance* inst) {
     if (n <= 0) {
         RBL_HIP(hipMemsetAsync(q, 0, sizeof(double) * ld, s));
         return RBL_OK;
     }
     // spmv.hip: the slab holds the segments' partial sums
     if (storage == RBL_STORE_CSR) return launch_csr_gemvt((const CsrStore*)D, ld, c, slab, slab_doubles, q, num_cu, s, main_done);
-    if (sweep_v_supported(storage, ld)) return launch_sweep_q(storage, D, n, ld, c, slab, q, num_cu, s, main_done);
+    if (sweep_v_supported(storage, ld)) {
+        SweepInstance sq{};
+        RBL_TRY(launch_sweep_q(storage, D, n, ld, c, slab, q, num_cu, s, main_done, inst ? &sq : nullptr));
+        pass_report(inst, PASS_ROUTE_SWEEP_Q, sq.p, sq.r, sq.s, sq.blocks, 0);
+        return RBL_OK;
+    }
     int nb = gemvt_blocks(num_cu, n);
     if (storage == RBL_STORE_F32)
-        RBL_TRY((gemvt_T<float, false>((const float*)D, n, ld, c, slab, nullptr, nb, s)));
+        RBL_TRY((gemvt_T<float, false>((const float*)D, n, ld, c, slab, nullptr, nb, s, inst)));
     else if (storage == RBL_STORE_F16)
-        RBL_TRY((gemvt_T<rbl_half, false>((const rbl_half*)D, n, ld, c, slab, nullptr, nb, s)));
+        RBL_TRY((gemvt_T<rbl_half, false>((const rbl_half*)D, n, ld, c, slab, nullptr, nb, s, inst)));
     else
-        RBL_TRY((gemvt_T<double, false>((const double*)D, n, ld, c, slab, nullptr, nb, s)));
+        RBL_TRY((gemvt_T<double, false>((const double*)D, n, ld, c, slab, nullptr, nb, s, inst)));
     if (main_done) RBL_HIP(hipEventRecord(main_done, s));  // the sweep kernel alone (roofline timing)
     hipLaunchKernelGGL(k_colreduce, dim3((unsigned)((ld + 63) / 64)), dim3(1024), 0, s, slab, nb, (long long)ld, q);
     RBL_HIP(hipGetLastError());
@@ -813,7 +831,7 @@ int launch_gemvt(int storage, const void* D, int64_t n, int64_t ld, const double
 }
 
 int launch_colstats(int storage, const void* D, int64_t n, int64_t ld, double* slab, double* sum,
-                    double* sumsq, int num_cu, hipStream_t s) {
+                    double* sumsq, int num_cu, hipStream_t s, PassInstance* inst) {
     if (storage == RBL_STORE_F16) {   // the generator takes them from the unrounded draws (synth.hip: launch_synth_stats)
         rbl_set_error("colstats: not available for RBL_STORE_F16");
         return RBL_ERR_INVALID;
@@ -821,9 +839,9 @@ int launch_colstats(int storage, const void* D, int64_t n, int64_t ld, double* s
     int nb = gemvt_blocks(num_cu, n);
     double* slab2 = slab + (size_t)gemvt_slab_rows(num_cu) * ld;
     if (storage == RBL_STORE_F32)
-        RBL_TRY((gemvt_T<float, true>((const float*)D, n, ld, nullptr, slab, slab2, nb, s)));
+        RBL_TRY((gemvt_T<float, true>((const float*)D, n, ld, nullptr, slab, slab2, nb, s, inst)));
     else
-        RBL_TRY((gemvt_T<double, true>((const double*)D, n, ld, nullptr, slab, slab2, nb, s)));
+        RBL_TRY((gemvt_T<double, true>((const double*)D, n, ld, nullptr, slab, slab2, nb, s, inst)));
     hipLaunchKernelGGL(k_colreduce, dim3((unsigned)((ld + 63) / 64)), dim3(1024), 0, s, slab, nb, (long long)ld, sum);
     hipLaunchKernelGGL(k_colreduce, dim3((unsigned)((ld + 63) / 64)), dim3(1024), 0, s, slab2, nb, (long long)ld, sumsq);
     RBL_HIP(hipGetLastError());

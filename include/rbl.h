@@ -570,6 +570,27 @@ int  rbl_k_sweep_v_multi(int storage, int64_t n, int64_t d, int k, const double*
                          int* instance);
 int  rbl_k_sweep_q_multi(int storage, int64_t n, int64_t d, int k, const double* D, const double* C, int num_cu, double* Q,
                          int* instance);
+/* The plain passes (sweep.hip) and the Gram kernels (gram.hip) on prescribed inputs with a caller-chosen grid: the
+ * launchers a solve runs, unchanged, with `num_cu` (1 .. the device's count, else RBL_ERR_INVALID) in the place of the
+ * device's CU count and buffers sized by the launchers' own rules for that num_cu.  Host fp64 in and out; D is rounded
+ * to `storage`; ld = d rounded up to the storage's row stride.  Outputs over the columns come back at full length ld
+ * and are preset to 0xff bytes on the device: the pad [d, ld) is part of what a pass must write (+0.0).
+ *   rbl_k_pass_v         v = D w through launch_gemv.  v is preset to NaN with a guard behind row n, as in rbl_k_sweep_*.
+ *                        instance (6 ints): 0, LPR lanes per row, P passes (0: w staged in LDS), U, blocks, 1.
+ *                        A row wider than the LDS-staged path takes (ld x 8 > 150 KiB) is RBL_ERR_INVALID.
+ *   rbl_k_pass_q         q = D^T c through launch_gemvt, its routing to the Q-only pass at 33..512 packets per row
+ *                        included.  instance: 0, TPR threads per row, PJ packets per thread, U, row blocks, column tiles -
+ *                        or 1, P, R, S, blocks, 0 when the Q-only pass ran (rbl_k_sweep_q tests that one).
+ *   rbl_k_pass_colstats  column sums and sums of squares through launch_colstats (RBL_STORE_F32 / F64; F16 is
+ *                        RBL_ERR_INVALID); instance as rbl_k_pass_q's first form, at every width.
+ *   rbl_k_gram_full      G = D^T D through launch_gram, all ld x ld entries; plan (4 x int64): column tiles, tile pairs,
+ *                        row splits, rows per split. */
+int  rbl_k_pass_v(int storage, int64_t n, int64_t d, const double* D, const double* w, int num_cu, double* v, int* instance);
+int  rbl_k_pass_q(int storage, int64_t n, int64_t d, const double* D, const double* c, int num_cu, double* q_ld,
+                  int* instance);
+int  rbl_k_pass_colstats(int storage, int64_t n, int64_t d, const double* D, int num_cu, double* sum_ld, double* sumsq_ld,
+                         int* instance);
+int  rbl_k_gram_full(int storage, int64_t n, int64_t d, const double* D, int num_cu, double* G_ld, int64_t* plan);
 /* G = D^T D (MFMA f64) */
 int  rbl_k_gram(int storage, int64_t n, int64_t d, const double* D, double* G);
 /* the passes of RBL_STORE_CSR on a host CSR matrix that holds D itself (no label sign): int64 indptr (n + 1), int32
