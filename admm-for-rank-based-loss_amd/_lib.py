@@ -142,6 +142,8 @@ SIGNATURES = {
     "rbl_set_labels": (C.c_int, [_P, _P]),
     "rbl_set_penalty": (C.c_int, [_P, _P, _P]),
     "rbl_get_penalty": (C.c_int, [_P, _P, _P, C.POINTER(C.c_int)]),
+    "rbl_set_row_weights": (C.c_int, [_P, _P]),
+    "rbl_get_row_weights": (C.c_int, [_P, _P, C.POINTER(C.c_int)]),
     "rbl_decide_multi": (C.c_int, [_P, C.c_int, _P, _P]),
     "rbl_group_create": (C.c_int, [C.POINTER(_P), C.c_int, C.POINTER(_P)]),
     "rbl_group_destroy": (C.c_int, [_P]),
@@ -224,6 +226,8 @@ SIGNATURES = {
     "rbl_k_gemvt_multi": (C.c_int, [C.c_int, C.c_int64, C.c_int64, C.c_int, _P, _P, _P]),
     "rbl_k_sweep_erm": (C.c_int, [C.c_int, C.c_int, C.c_int64, C.c_int64, _P, _P, _P, _P, C.c_double, C.c_double, C.c_double,
                                   C.c_int, C.c_int, _P, _P, _P, _P, _D, _D, _P]),
+    "rbl_k_sweep_erm_w": (C.c_int, [C.c_int, C.c_int, C.c_int64, C.c_int64, _P, _P, _P, _P, _P, C.c_double, C.c_double,
+                                    C.c_int, C.c_int, _P, _P, _P, _P, _D, _D, _P]),
     "rbl_k_sweep_v": (C.c_int, [C.c_int, C.c_int64, C.c_int64, _P, _P, _P, _P, C.c_double, C.c_int, _P, _P, _D, _P]),
     "rbl_k_sweep_q": (C.c_int, [C.c_int, C.c_int64, C.c_int64, _P, _P, C.c_int, _P, _P]),
     "rbl_k_sweep_v_multi": (C.c_int, [C.c_int, C.c_int64, C.c_int64, C.c_int, _P, _P, _P, _P, _P, C.c_int, _P, _P, _P, _P]),
@@ -447,6 +451,23 @@ def k_sweep_erm(D, w, z_old, lam, sigma0, rho, rho_next, loss, storage="f32", nu
     check(load().rbl_k_sweep_erm(STORAGE[storage], LOSS[loss], n, d, ptr(D), ptr(w), ptr(z_old), ptr(lam), float(sigma0),
                                  float(rho), float(rho_next), int(num_cu), 1 if want_v else 0, ptr(lam_out), ptr(v),
                                  ptr(z_new), ptr(q), C.byref(p2), C.byref(zz), ptr(inst)))
+    return dict(lam=lam_out, v=v, z=z_new, q=q, primal2=p2.value, zz=zz.value, instance=_instance(inst))
+
+
+def k_sweep_erm_w(D, w, z_old, lam, sigma, rho, rho_next, loss, storage="f32", num_cu=1, want_v=True):
+    """k_sweep_erm with one sigma per row (n values) in the place of sigma0: the row-weighted twins (include/rbl.h:
+    rbl_k_sweep_erm_w).  Same dict."""
+    D, w, z_old, lam = f64(D), f64(w).reshape(-1), f64(z_old).reshape(-1), f64(lam).reshape(-1)
+    n, d = D.shape
+    sigma = f64(sigma).reshape(-1)
+    if sigma.shape[0] != n:
+        raise ValueError(f"k_sweep_erm_w: sigma has {sigma.shape[0]} entries, D has {n} rows")
+    lam_out, v, z_new, q = np.empty(n), np.empty(n), np.empty(n), np.empty(d)
+    p2, zz = C.c_double(0.0), C.c_double(0.0)
+    inst = np.zeros(5, dtype=np.int32)
+    check(load().rbl_k_sweep_erm_w(STORAGE[storage], LOSS[loss], n, d, ptr(D), ptr(w), ptr(z_old), ptr(lam), ptr(sigma),
+                                   float(rho), float(rho_next), int(num_cu), 1 if want_v else 0, ptr(lam_out), ptr(v),
+                                   ptr(z_new), ptr(q), C.byref(p2), C.byref(zz), ptr(inst)))
     return dict(lam=lam_out, v=v, z=z_new, q=q, primal2=p2.value, zz=zz.value, instance=_instance(inst))
 
 

@@ -109,6 +109,68 @@ def resolve_penalty(d, l1_reg=None, l2_reg=None, l1_weights=None, l2_weights=Non
     return dict(l1=l1, l2=l2, wstep=_lib.WSTEP_L1 if any_l1 else _lib.WSTEP_L2, reg=reg)
 
 
+def as_row_weights(c, n, what="sample_weight"):
+    """Row weights: n values, finite and >= 0, at least one > 0 -> float64 (n,); anything else is a ValueError naming
+    `what` and the first offending row.  Checked on the host, before any device call."""
+    a = np.asarray(c.detach().cpu().numpy() if hasattr(c, "detach") else c)
+    try:
+        a = np.ascontiguousarray(np.asarray(a, dtype=np.float64).reshape(-1))
+    except (TypeError, ValueError):
+        raise ValueError(f"{what}: expected {n} numbers") from None
+    if a.shape[0] != n:
+        raise ValueError(f"{what}: has {a.shape[0]} entries for {n} rows")
+    if not np.all(np.isfinite(a)):
+        bad = int(np.flatnonzero(~np.isfinite(a))[0])
+        raise ValueError(f"{what}: weights must be finite (row {bad} is {a[bad]!r})")
+    if np.any(a < 0):
+        bad = int(np.flatnonzero(a < 0)[0])
+        raise ValueError(f"{what}: weights must be >= 0 (row {bad} is {a[bad]!r})")
+    if n > 0 and not np.any(a > 0):
+        raise ValueError(f"{what}: all {n} weights are zero - at least one must be > 0")
+    return a
+
+
+def resolve_row_weights(y_pm1, sample_weight=None, class_weight=None, weight_function="erm"):
+    """The row weights c of F(w) = (1/n) sum_i c_i loss_i(w) + R(w) (include/rbl.h: rbl_set_row_weights) from the two
+    keywords, or None when neither is given (the unweighted path, exactly as before).
+
+    class_weight: "balanced" gives c_i = n / (2 n_{y_i}); a dict {+1: a, -1: b} is taken as given.  sample_weight (n
+    values) multiplies in.  No normalisation.  Everything is checked here, on the host, before any device call; a
+    rank-weighted family is refused: with weights the sigma of a rank depends on the cumulative weight in sorted order,
+    so it is not fixed per rank and the PAV z-step does not apply."""
+    if sample_weight is None and class_weight is None:
+        return None
+    if weight_function != "erm":
+        raise ValueError(f'sample_weight / class_weight need weight_function="erm" (got {weight_function!r}): with row '
+                         "weights the sigma of a rank depends on the cumulative weight in sorted order, so it is not "
+                         "fixed per rank and the PAV z-step does not apply")
+    y = np.asarray(y_pm1, dtype=np.float64).reshape(-1)
+    n = y.shape[0]
+    c = np.ones(n)
+    if class_weight is not None:
+        pos = y > 0
+        if isinstance(class_weight, str):
+            if class_weight != "balanced":
+                raise ValueError(f'class_weight must be "balanced" or a dict {{+1: a, -1: b}} (got {class_weight!r})')
+            n_pos, n_neg = int(np.count_nonzero(pos)), int(n - np.count_nonzero(pos))
+            if n_pos == 0 or n_neg == 0:
+                raise ValueError('class_weight="balanced": both classes must be present')
+            a, b = n / (2.0 * n_pos), n / (2.0 * n_neg)
+        elif isinstance(class_weight, dict):
+            if set(class_weight) != {1, -1}:
+                raise ValueError(f"class_weight: the dict must have exactly the keys +1 and -1 (got {sorted(class_weight, key=repr)})")
+            a, b = float(class_weight[1]), float(class_weight[-1])
+            for k, v in ((1, a), (-1, b)):
+                if not np.isfinite(v) or v < 0:
+                    raise ValueError(f"class_weight[{k:+d}] must be finite and >= 0 (got {v!r})")
+        else:
+            raise ValueError(f'class_weight must be "balanced" or a dict {{+1: a, -1: b}} (got {class_weight!r})')
+        c = np.where(pos, a, b).astype(np.float64)
+    if sample_weight is not None:
+        c = c * as_row_weights(sample_weight, n)
+    return as_row_weights(c, n, "sample_weight * class_weight" if class_weight is not None else "sample_weight")
+
+
 def add_intercept_column(X):
     """[X | 1]: a host copy of X with a column of ones appended (fit_intercept=True)"""
     return np.ascontiguousarray(np.hstack([X, np.ones((X.shape[0], 1))]))
@@ -453,6 +515,21 @@ class Solver:
         l1, l2, flag = np.empty(self.d), np.empty(self.d), C.c_int(0)
         _lib.check(self.lib.rbl_get_penalty(self._h, _lib.ptr(l1), _lib.ptr(l2), C.byref(flag)))
         return (l1, l2) if flag.value else None
+
+    def set_row_weights(self, c):
+        """Row weights of an erm problem (include/rbl.h: rbl_set_row_weights): n values >= 0, at least one > 0, or None
+        for the unweighted path.  Allowed between iterations.  Shape, finiteness and sign are checked here first."""
+        if c is None:
+            _lib.check(self.lib.rbl_set_row_weights(self._h, None))
+            return
+        c = as_row_weights(c, self.n)
+        _lib.check(self.lib.rbl_set_row_weights(self._h, _lib.ptr(c)))
+
+    def get_row_weights(self):
+        """the weights of set_row_weights, or None when the handle has none"""
+        c, flag = np.empty(self.n), C.c_int(0)
+        _lib.check(self.lib.rbl_get_row_weights(self._h, _lib.ptr(c), C.byref(flag)))
+        return c if flag.value else None
 
     def decide_multi(self, W):
         """argmax_j x_i . w_j over the rows of this handle's data (ties: lowest j); W: (k, d) -> int32 (n,)

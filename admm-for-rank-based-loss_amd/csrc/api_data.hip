@@ -946,6 +946,63 @@ int rbl_set_labels(rbl_solver* h, const double* y) {
     return RBL_OK;
 }
 
+// Row weights of an erm problem: F(w) = (1/n) sum_i c_i loss_i(w) + R(w).  Only the z-step (sigma_i = c_i * sigma0) and
+// the logged losses see them; D, G, the w-step, the dual update, the residuals and the rho schedule do not.
+int rbl_set_row_weights(rbl_solver* h, const double* c) {
+    RBL_ENTER(h);   // like rbl_set_state: a w-step enqueued ahead is put back
+    if (h->cfg.weight_function != RBL_W_ERM) {
+        rbl_set_error("set_row_weights: row weights need weight_function erm - with weights the sigma of a rank depends on the "
+                      "cumulative weight in sorted order, so it is not fixed per rank and the PAV z-step does not apply");
+        return RBL_ERR_INVALID;
+    }
+    if (h->nt != h->n) {
+        rbl_set_error("set_row_weights: row-sharded handle (n=%lld of %lld) - row weights are single-device problems",
+                      (long long)h->n, (long long)h->nt);
+        return RBL_ERR_INVALID;
+    }
+    const int64_t n = h->n;
+    if (c) {
+        bool any = false;
+        for (int64_t i = 0; i < n; ++i) {
+            if (!std::isfinite(c[i]) || c[i] < 0.0) {
+                rbl_set_error("set_row_weights: c[%lld] = %g - weights are finite and >= 0", (long long)i, c[i]);
+                return RBL_ERR_INVALID;
+            }
+            any = any || c[i] > 0.0;
+        }
+        if (!any) {
+            rbl_set_error("set_row_weights: all %lld weights are zero - at least one must be > 0", (long long)n);
+            return RBL_ERR_INVALID;
+        }
+    }
+    RBL_HIP(hipStreamSynchronize(h->stream));
+    if (!c) {   // back to the unweighted path; the handle's own buffers alone are freed
+        if (h->cw) h->mem.release(h->cw);
+        if (h->sigw) h->mem.release(h->sigw);
+        h->cw = h->sigw = nullptr;
+        h->cw_host.clear();
+    } else {
+        if (!h->cw) RBL_TRY(h->mem.alloc(&h->cw, (size_t)(n > 0 ? n : 1)));
+        if (!h->sigw) RBL_TRY(h->mem.alloc(&h->sigw, (size_t)(n > 0 ? n : 1)));
+        std::vector<double> sg((size_t)n);
+        for (int64_t i = 0; i < n; ++i) sg[(size_t)i] = c[i] * h->sigma0;   // the ONE product: c == 1.0 gives sigma0's bits
+        h->cw_host.assign(c, c + n);
+        RBL_HIP(hipMemcpy(h->cw, c, sizeof(double) * n, hipMemcpyHostToDevice));
+        RBL_HIP(hipMemcpy(h->sigw, sg.data(), sizeof(double) * n, hipMemcpyHostToDevice));
+    }
+    // whatever was computed ahead with the old weights is void: the next z-step runs with the new ones
+    h->z_ready = h->pred_valid = false;
+    return RBL_OK;
+}
+
+int rbl_get_row_weights(rbl_solver* h, double* c, int* is_set) {
+    RBL_ENTER_ITER(h);
+    if (is_set) *is_set = h->cw ? 1 : 0;
+    if (c)
+        for (int64_t i = 0; i < h->n; ++i) c[i] = h->cw ? h->cw_host[(size_t)i] : 1.0;
+    return RBL_OK;
+}
+
 // One-vs-rest decision on the rows of `data`: cls[i] = argmax_j x_i . w_j (ties: the lowest j).  D = -y X, so the
 // scores are -y_i (D w_j)_i: the multi-column V product of the groups (sweep_multi.hip), ceil(k / k_per_pass) passes
 // over D, each followed by the row-wise comparison against the best score so far.

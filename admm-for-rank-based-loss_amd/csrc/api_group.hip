@@ -192,7 +192,7 @@ int rbl_group_step(rbl_group* g, int want_objective, rbl_stats* out) {
                 RBL_TRY(risk_from_v(h, h->v, h->red + 1));
                 h->obj_is_risk = true;
             } else if (want_objective) {
-                RBL_TRY(launch_loss_sum(h->cfg.loss, h->n, h->v, 1.0, h->partials, h->red + 1, s, h->rs));   // objective.py:11-24
+                RBL_TRY(launch_loss_sum(h->cfg.loss, h->n, h->v, 1.0, h->partials, h->red + 1, s, h->rs, h->cw));   // objective.py:11-24
             }
         }
     } else {

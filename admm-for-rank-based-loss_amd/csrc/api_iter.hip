@@ -195,7 +195,7 @@ int risk_from_v(rbl_solver* h, const double* v_all, double* out_dev) {
     hipStream_t s = h->stream;
     if (h->cfg.weight_function == RBL_W_ERM) {
         h->risk_path = 1;
-        return launch_loss_sum(h->cfg.loss, h->nt, v_all, 1.0 / (double)h->nt, h->partials, out_dev, s, h->rs);
+        return launch_loss_sum(h->cfg.loss, h->nt, v_all, 1.0 / (double)h->nt, h->partials, out_dev, s, h->rs, h->cw);
     }
     h->keys_ready = false;   // the sort workspace is reused: keys left by rbl_phase_m are gone
     RBL_TRY(launch_loss_keys(h->nt, v_all, h->sw.keys[0], s, h->rs));   // (own labels: the losses are taken at r * v)
@@ -351,7 +351,7 @@ int rbl_phase_z(rbl_solver* h, const void* m_all_dev) {
     if (h->fused_ok && h->z_ready) {
         std::swap(h->z, h->z_next);  // the z-step of this iteration was done by the previous pass
     } else if (!h->sorted_path) {
-        RBL_TRY(launch_erm_zc(h->cfg.loss, h->n, h->sigma0, rho, h->v, h->lam, h->m, h->z, h->c, h->stream, h->rs));
+        RBL_TRY(launch_erm_zc(h->cfg.loss, h->n, h->sigma0, rho, h->v, h->lam, h->m, h->z, h->c, h->stream, h->rs, h->sigw));
         if (h->fused_ok) RBL_TRY(launch_sumsq(h->n, h->z, h->partials, q_zz(h), h->stream));
     } else {
         const double* msrc = (const double*)m_all_dev;
@@ -566,7 +566,8 @@ int rbl_phase_dual(rbl_solver* h, int want_objective) {
         if (prof_now(h)) RBL_HIP(hipEventRecord(h->kev[4], h->stream));
         RBL_TRY(launch_sweep_erm(h->storage, h->cfg.loss, h->D, h->n, h->ld, h->w, h->z, h->lam, h->v, h->z_next,
                                  h->sigma0, h->step_rho, h->pred, h->slab, h->partials, h->q, h->red, q_zz(h),
-                                 h->num_cu, h->stream, prof_now(h) ? h->kev[5] : nullptr, want_objective));
+                                 h->num_cu, h->stream, prof_now(h) ? h->kev[5] : nullptr, want_objective, nullptr, h->sigw,
+                                 h->cw));
         if (prof_now(h)) h->kev_pending[2] = h->n > 0;
         h->fused_ran = true;
         h->v_valid = want_objective != 0;   // without objective logging the pass does not store v (ensure_v recomputes it if a misprediction asks)
@@ -591,9 +592,10 @@ int rbl_phase_dual(rbl_solver* h, int want_objective) {
         if (h->phase_timing) RBL_HIP(hipEventRecord(h->ev[4], h->stream));
         RBL_TRY(launch_dual(h->cfg.loss, h->n, h->step_rho, h->z, h->v, h->lam, h->partials, h->red, h->stream));
     }
-    // own labels: k_dual summed the losses at v as the pass left it - the handle's own are at r * v
-    if (h->rs && want_objective && !h->sorted_path)
-        RBL_TRY(launch_loss_sum(h->cfg.loss, h->n, h->v, 1.0, h->partials, h->red + 1, h->stream, h->rs));
+    // own labels: k_dual summed the losses at v as the pass left it - the handle's own are at r * v; row weights: k_dual
+    // sums unweighted losses (the single-sweep pass' own loss sum took the weights already)
+    if ((h->rs || (h->cw && !h->fused_ran)) && want_objective && !h->sorted_path)
+        RBL_TRY(launch_loss_sum(h->cfg.loss, h->n, h->v, 1.0, h->partials, h->red + 1, h->stream, h->rs, h->cw));
     h->pending_mask = 2 | (h->fused_ran ? 1 : 0);
     h->want_obj = want_objective;
     h->obj_is_risk = false;

@@ -462,10 +462,12 @@ void instance_out(int* instance, const SweepInstance& in) {
 }
 }  // namespace
 
-int rbl_k_sweep_erm(int storage, int loss, int64_t n, int64_t d, const double* D, const double* w, const double* z_old,
-                    const double* lam, double sigma0, double rho, double rho_next, int num_cu, int want_v, double* lam_out,
-                    double* v, double* z_new, double* q, double* primal2, double* zz, int* instance) {
-    const char* who = "rbl_k_sweep_erm";
+// rbl_k_sweep_erm (sigma == NULL) and rbl_k_sweep_erm_w (sigma: n host doubles, one per row): one body, the same presets,
+// guards and reporting
+static int k_sweep_erm_any(const char* who, int storage, int loss, int64_t n, int64_t d, const double* D, const double* w,
+                           const double* z_old, const double* lam, double sigma0, const double* sigma, double rho,
+                           double rho_next, int num_cu, int want_v, double* lam_out, double* v, double* z_new, double* q,
+                           double* primal2, double* zz, int* instance) {
     RBL_TRY(k_check_loss(who, loss));
     Scratch sc;
     int64_t ld = 0;
@@ -490,9 +492,11 @@ int rbl_k_sweep_erm(int storage, int loss, int64_t n, int64_t d, const double* D
     RBL_TRY(sc.mem.alloc(&partials, std::max((size_t)sweep_erm_blocks(num_cu) * 3, (size_t)reduce_blocks() * 4)));
     RBL_TRY(sc.mem.alloc(&dq, (size_t)ld));
     RBL_TRY(sc.mem.alloc(&red, 8));
+    double* dsig = nullptr;
+    if (sigma) RBL_TRY(sc.upload(&dsig, sigma, (size_t)n));
     SweepInstance inst{};
     RBL_TRY(launch_sweep_erm(storage, loss, Dd, n, ld, dw, dz, dlam, dv, dzn, sigma0, rho, pred, slab, partials, dq, red, red + 4,
-                             num_cu, sc.s, nullptr, want_v ? 1 : 0, &inst));
+                             num_cu, sc.s, nullptr, want_v ? 1 : 0, &inst, dsig));
     RBL_TRY(rows_fetch(sc, who, "lambda", dlam, n, 1, lam_out));
     RBL_TRY(rows_fetch(sc, who, "v", dv, n, 1, v));
     RBL_TRY(rows_fetch(sc, who, "z_new", dzn, n, 1, z_new));
@@ -504,6 +508,24 @@ int rbl_k_sweep_erm(int storage, int loss, int64_t n, int64_t d, const double* D
     if (zz) *zz = redh[4];
     instance_out(instance, inst);
     return RBL_OK;
+}
+
+int rbl_k_sweep_erm(int storage, int loss, int64_t n, int64_t d, const double* D, const double* w, const double* z_old,
+                    const double* lam, double sigma0, double rho, double rho_next, int num_cu, int want_v, double* lam_out,
+                    double* v, double* z_new, double* q, double* primal2, double* zz, int* instance) {
+    return k_sweep_erm_any("rbl_k_sweep_erm", storage, loss, n, d, D, w, z_old, lam, sigma0, nullptr, rho, rho_next, num_cu,
+                           want_v, lam_out, v, z_new, q, primal2, zz, instance);
+}
+
+int rbl_k_sweep_erm_w(int storage, int loss, int64_t n, int64_t d, const double* D, const double* w, const double* z_old,
+                      const double* lam, const double* sigma, double rho, double rho_next, int num_cu, int want_v,
+                      double* lam_out, double* v, double* z_new, double* q, double* primal2, double* zz, int* instance) {
+    if (!sigma) {
+        rbl_set_error("rbl_k_sweep_erm_w: sigma is NULL");
+        return RBL_ERR_INVALID;
+    }
+    return k_sweep_erm_any("rbl_k_sweep_erm_w", storage, loss, n, d, D, w, z_old, lam, 0.0, sigma, rho, rho_next, num_cu, want_v,
+                           lam_out, v, z_new, q, primal2, zz, instance);
 }
 
 int rbl_k_sweep_v(int storage, int64_t n, int64_t d, const double* D, const double* w, const double* z, const double* lam,

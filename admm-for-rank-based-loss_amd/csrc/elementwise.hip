@@ -4,6 +4,7 @@
 // with a fixed summation order (deterministic, no float atomics).
 #include "rbl_internal.h"
 #include "device_math.h"
+#include <type_traits>
 
 namespace {
 
@@ -31,8 +32,15 @@ __device__ __forceinline__ double rs_flip(double x, const signed char* __restric
     return x;
 }
 
-template <int LOSS, bool RS>
-__global__ __launch_bounds__(EW_THREADS) void k_erm_zc(long long n, double sigma0, double rho,
+// SG: double (sigma0) or const double* (row weights: one sigma per row) - two compile-time forms, as RS
+template <typename SG>
+__device__ __forceinline__ double sigma_at(SG sigma, long long i) {
+    if constexpr (std::is_pointer<SG>::value) return sigma[i];
+    else return sigma;
+}
+
+template <int LOSS, bool RS, typename SG>
+__global__ __launch_bounds__(EW_THREADS) void k_erm_zc(long long n, SG sigma0, double rho,
                                                         const double* __restrict__ v,
                                                         const double* __restrict__ lam, double* __restrict__ m,
                                                         double* __restrict__ z, double* __restrict__ c,
@@ -42,7 +50,7 @@ __global__ __launch_bounds__(EW_THREADS) void k_erm_zc(long long n, double sigma
          i += (long long)gridDim.x * EW_THREADS) {
         double lr = lam[i] / rho;
         double mi = rs_flip<RS>(v[i] - lr, rs, i);
-        double zi = rs_flip<RS>(rbl::prox<LOSS>(sigma0, rho, mi), rs, i);
+        double zi = rs_flip<RS>(rbl::prox<LOSS>(sigma_at(sigma0, i), rho, mi), rs, i);
         m[i] = mi;
         z[i] = zi;
         c[i] = zi + lr;
@@ -256,15 +264,18 @@ __global__ __launch_bounds__(EW_THREADS) void k_sorted_loss_dot(long long n, con
     if (threadIdx.x == 0) partials[blockIdx.x] = acc[0];
 }
 
-template <int LOSS, bool RS>
+// W: row weights - every loss is multiplied by cw[i] before it is added (cw == 1.0 leaves its bits)
+template <int LOSS, bool RS, bool W>
 __global__ __launch_bounds__(EW_THREADS) void k_loss_sum(long long n, const double* __restrict__ v, double scale,
-                                                          double* __restrict__ partials,
+                                                          double* __restrict__ partials, const double* __restrict__ cw,
                                                           const signed char* __restrict__ rs) {
     __shared__ double smem[EW_THREADS / 64];
     double acc[1] = {0.0};
     for (long long i = (long long)blockIdx.x * EW_THREADS + threadIdx.x; i < n;
-         i += (long long)gridDim.x * EW_THREADS)
-        acc[0] += rbl::sample_loss<LOSS>(rs_flip<RS>(v[i], rs, i));
+         i += (long long)gridDim.x * EW_THREADS) {
+        const double l = rbl::sample_loss<LOSS>(rs_flip<RS>(v[i], rs, i));
+        acc[0] += W ? cw[i] * l : l;
+    }
     acc[0] *= scale;
     rbl::block_sum<1, EW_THREADS>(acc, smem);
     if (threadIdx.x == 0) partials[blockIdx.x] = acc[0];
@@ -437,10 +448,19 @@ int reduce_blocks() { return RED_BLOCKS; }
         else hipLaunchKernelGGL((KERN<false>), dim3(grid), dim3(block), 0, stream, __VA_ARGS__, rs);     \
     } while (0)
 
+// kernels with a further compile-time form behind <LOSS, RS>: X is a type or a constant
+#define LAUNCH_LOSS_RS_X(KERN, X, loss, rs, grid, block, stream, ...)                                                   \
+    RBL_LOSS_SWITCH(loss, L_,                                                                                           \
+                    if (rs) hipLaunchKernelGGL((KERN<L_, true, X>), dim3(grid), dim3(block), 0, stream, __VA_ARGS__, rs); \
+                    else hipLaunchKernelGGL((KERN<L_, false, X>), dim3(grid), dim3(block), 0, stream, __VA_ARGS__, rs))
+
 int launch_erm_zc(int loss, int64_t n, double sigma0, double rho, const double* v, const double* lam, double* m,
-                  double* z, double* c, hipStream_t s, const signed char* rs) {
+                  double* z, double* c, hipStream_t s, const signed char* rs, const double* sigma_rows) {
     if (n <= 0) return RBL_OK;
-    LAUNCH_LOSS_RS(k_erm_zc, loss, rs, ew_grid(n), EW_THREADS, s, (long long)n, sigma0, rho, v, lam, m, z, c);
+    if (sigma_rows)
+        LAUNCH_LOSS_RS_X(k_erm_zc, const double*, loss, rs, ew_grid(n), EW_THREADS, s, (long long)n, sigma_rows, rho, v, lam, m, z, c);
+    else
+        LAUNCH_LOSS_RS_X(k_erm_zc, double, loss, rs, ew_grid(n), EW_THREADS, s, (long long)n, sigma0, rho, v, lam, m, z, c);
     RBL_HIP(hipGetLastError());
     return RBL_OK;
 }
@@ -525,8 +545,11 @@ int launch_sorted_loss_dot(int loss, int64_t n, const u64* sorted_keys, const do
 }
 
 int launch_loss_sum(int loss, int64_t n, const double* v, double scale, double* partials, double* out,
-                    hipStream_t s, const signed char* rs) {
-    LAUNCH_LOSS_RS(k_loss_sum, loss, rs, RED_BLOCKS, EW_THREADS, s, (long long)n, v, scale, partials);
+                    hipStream_t s, const signed char* rs, const double* cw) {
+    if (cw)
+        LAUNCH_LOSS_RS_X(k_loss_sum, true, loss, rs, RED_BLOCKS, EW_THREADS, s, (long long)n, v, scale, partials, cw);
+    else
+        LAUNCH_LOSS_RS_X(k_loss_sum, false, loss, rs, RED_BLOCKS, EW_THREADS, s, (long long)n, v, scale, partials, cw);
     RBL_HIP(hipGetLastError());
     return launch_sum_partials(partials, RED_BLOCKS, 1, out, s);
 }

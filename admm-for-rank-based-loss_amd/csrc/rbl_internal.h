@@ -229,8 +229,10 @@ int launch_csr_expand(int dtype, int index_type, void* Xc, int64_t ldc, int64_t 
 // ---- elementwise.hip --------------------------------------------------------------------
 // rs (optional, in the launchers below): the sign vector of a handle with labels of its own on a borrowed D
 // (rbl_set_labels): r_i = y_i * y_owner_i.  v, z, lambda, c are then in the owner's sign convention, m is the true m.
+// sigma_rows != NULL (row weights): the prox of row i runs with sigma_rows[i] in the place of sigma0
 int launch_erm_zc(int loss, int64_t n, double sigma0, double rho, const double* v, const double* lam,
-                  double* m, double* z, double* c, hipStream_t s, const signed char* rs = nullptr);
+                  double* m, double* z, double* c, hipStream_t s, const signed char* rs = nullptr,
+                  const double* sigma_rows = nullptr);
 // m = v - lambda/rho together with the sort's input: keys[i] = order-preserving transform of m[i], idx[i] = i + idx_off
 int launch_make_m_keys(int64_t n, double rho, const double* v, const double* lam, double* m, u64* keys, u32* idx,
                        u32 idx_off, hipStream_t s, const signed char* rs = nullptr);
@@ -263,8 +265,9 @@ int launch_sum_partials(const double* partials, int nblocks, int K, double* out,
 int launch_loss_keys(int64_t n, const double* v, u64* keys, hipStream_t s, const signed char* rs = nullptr);
 int launch_sorted_loss_dot(int loss, int64_t n, const u64* sorted_keys, const double* sigma,
                            double* partials, double* out, hipStream_t s);
+// cw != NULL (row weights): scale * sum_i cw[i] * loss_i, the same two stages in the same order
 int launch_loss_sum(int loss, int64_t n, const double* v, double scale, double* partials, double* out,
-                    hipStream_t s, const signed char* rs = nullptr);
+                    hipStream_t s, const signed char* rs = nullptr, const double* cw = nullptr);
 
 // ---- sort.hip -------------------------------------------------------------------------
 struct SortWorkspace {
@@ -456,7 +459,14 @@ int sweep_erm_slab_rows(int num_cu);
 int launch_sweep_erm(int storage, int loss, const void* D, int64_t n, int64_t ld, const double* w, const double* z_old,
                      double* lam, double* v, double* z_new, double sigma0, double rho, const double* pred_dev,
                      double* slab, double* partials, double* q, double* red, double* zz_out, int num_cu, hipStream_t s,
-                     hipEvent_t main_done, int want_obj, SweepInstance* inst = nullptr);
+                     hipEvent_t main_done, int want_obj, SweepInstance* inst = nullptr,
+                     const double* sigma_rows = nullptr /* n: the row-weighted twins, sigma0 unused */,
+                     const double* loss_w = nullptr /* n: row weights of the logged loss sum */);
+// the same pass with one sigma per row (sweep_erm_w.hip); called by launch_sweep_erm
+int launch_sweep_erm_w(int storage, int loss, const void* D, int64_t n, int64_t ld, const double* w, const double* z_old,
+                       double* lam, double* v, double* z_new, const double* sigma_rows, double rho, const double* pred_dev,
+                       double* slab, double* partials, double* q, double* red, double* zz_out, int num_cu, hipStream_t s,
+                       hipEvent_t main_done, int want_obj, SweepInstance* inst, const double* loss_w);
 // rho_{k+1} prediction + the w statistics (||w - w_prev||^2, sum w^2, ||w||_1 -> wstats[0..2]); p_out != p
 // rho_dev != NULL: rho is read from rho_dev[0] on the device (may alias pred)
 int launch_predict_rho(int64_t ld, const double* q, const double* p, double* p_out, const double* w, const double* w_prev,

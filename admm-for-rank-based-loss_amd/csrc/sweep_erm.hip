@@ -20,6 +20,7 @@
 // simply recomputes the z-step / q with the unfused kernels (api_iter.hip).
 // Algorithmic bytes = n*ld*sizeof(T): half of the unfused iteration's.
 #include "rbl_internal.h"
+#include <type_traits>
 #ifndef RBL_D_AUX
 #define RBL_D_AUX 2   // cache policy of the streaming loads of D: 2 = nt (non-temporal) on gfx950; 0 = default policy
 #endif
@@ -83,14 +84,22 @@ __device__ inline void opaque(u32x4 (&buf)[R][P]) {
 // residual sums; the same loads in the same order, the same accumulation into per-lane column sums, one slab row per
 // block.  The thread-per-column-packet k_gemvt reads the same bytes at 6.0 TB/s, this kernel at the single-sweep
 // kernel's 6.2-6.5 (buffer loads through scalar row descriptors, a whole sub-batch of rows in flight per wave).
-enum : int { SE_FUSED = 0, SE_VONLY = 1, SE_QONLY = 2 };
+//   SE_FUSED_W  SE_FUSED with row weights: sigma_i = c_i * sigma0 is READ per row (n doubles in the place of the scalar) as a
+//             third row-wise load beside z_old and lambda, 8 more bytes per row.  A compile-time twin: the instances of
+//             the three modes above contain no trace of it.
+// (a NAMED enum: SigArg<MODE == SE_FUSED_W> puts its type into the kernels' mangled names, and an unnamed type is numbered
+// differently by the host and the device compilation - the launch then finds no such kernel)
+enum SweepMode : int { SE_FUSED = 0, SE_VONLY = 1, SE_QONLY = 2, SE_FUSED_W = 3 };
+// the sigma argument of the fused kernels: the scalar sigma0, or (WT) one sigma per row
+template <bool WT> struct SigArg { typedef double type; };
+template <> struct SigArg<true> { typedef const double* __restrict__ type; };
 template <typename T, int LOSS, int P, int R, int S, bool WL, int MODE, int OCC>
 __global__ __launch_bounds__(SE_THREADS, OCC) void k_sweep_erm(
     const T* __restrict__ D, long long n, long long ld, const double* __restrict__ w, const double* __restrict__ z_old,
-    double* __restrict__ lam, double* __restrict__ v, double* __restrict__ z_new, double sigma0, double rho,
-    const double* __restrict__ pred, double* __restrict__ slab, double* __restrict__ partials) {
+    double* __restrict__ lam, double* __restrict__ v, double* __restrict__ z_new, typename SigArg<MODE == SE_FUSED_W>::type sigma0,
+    double rho, const double* __restrict__ pred, double* __restrict__ slab, double* __restrict__ partials) {
     constexpr int E = Pk<T>::E;
-    constexpr bool VONLY = MODE == SE_VONLY, QONLY = MODE == SE_QONLY;
+    constexpr bool VONLY = MODE == SE_VONLY, QONLY = MODE == SE_QONLY, WT = MODE == SE_FUSED_W;
     // The wave index goes through readfirstlane: super-batch numbers, row numbers and the row
     // descriptors are then scalar registers, and a load is buffer_load(SGPR descriptor, 32-bit
     // per-lane offset) - no 64-bit per-lane addresses, which is what keeps two R x P packet
@@ -142,12 +151,13 @@ __global__ __launch_bounds__(SE_THREADS, OCC) void k_sweep_erm(
     // Loads are issued in the order they are consumed: s_waitcnt vmcnt counts in issue order,
     // so waiting for sub-batch t then leaves the whole of sub-batch t+1 in flight (a row-wise
     // load issued later than the prefetch would drain it).
-    auto load_side = [&](int q, double& zo, double& lm) {
+    auto load_side = [&](int q, double& zo, double& lm, double& sg) {
         const int live = q == nsuper - 1 ? live_last : SR;
         const bool mine = lane < live;
         const long long myrow = (long long)q * SR + lane;
         zo = mine ? z_old[myrow] : 0.0;
         lm = (mine && !QONLY) ? lam[myrow] : 0.0;
+        if constexpr (WT) sg = mine ? sigma0[myrow] : 0.0;   // row weights: the third row-wise load, still ahead of load_rows
     };
     auto load_rows = [&](int q, int sub, u32x4 (&buf)[R][P]) {
         const int live = q == nsuper - 1 ? live_last : SR;
@@ -164,7 +174,10 @@ __global__ __launch_bounds__(SE_THREADS, OCC) void k_sweep_erm(
     };
 
     double l_out = 0.0, v_out = 0.0, z_out = 0.0;   // this lane's row of the current super-batch
-    auto process = [&](int live, int sub, u32x4 (&buf)[R][P], double zo, double lm) {
+    auto process = [&](int live, int sub, u32x4 (&buf)[R][P], double zo, double lm, double sg) {
+        double sig;   // sigma of this lane's row
+        if constexpr (WT) sig = sg;
+        else sig = sigma0;
         double dot[R];
 #pragma unroll
         for (int r = 0; r < R; ++r) dot[r] = QONLY ? Pk<T>::at(buf[r][0], 0) : 0.0;
@@ -199,7 +212,7 @@ __global__ __launch_bounds__(SE_THREADS, OCC) void k_sweep_erm(
             const double lr = l / rho_next;
             const double m = myv - lr;                             // algorithms.py:89 (next iteration)
             // (squared hinge: the closed form, no warm start)
-            const double zn = VONLY ? m : ((LOSS == 0) ? rbl::prox_bce_warm(sigma0, rho_next, m, zo) : rbl::prox<LOSS>(sigma0, rho_next, m));
+            const double zn = VONLY ? m : ((LOSS == 0) ? rbl::prox_bce_warm(sig, rho_next, m, zo) : rbl::prox<LOSS>(sig, rho_next, m));
             s_zz += zn * zn;
             l_out = l;
             v_out = myv;
@@ -223,13 +236,14 @@ __global__ __launch_bounds__(SE_THREADS, OCC) void k_sweep_erm(
 
     u32x4 bufA[R][P], bufB[R][P];
     double zo = 0.0, lm = 0.0, zoN = 0.0, lmN = 0.0;
+    double sg = 0.0, sgN = 0.0;   // (WT) sigma of the lane's row, handed over with zoN / lmN
     int q = gw, sub = 0;
     // One copy of the row-wise code, as in k_sweep_erm_wide: every load lands in bufB; at the top of
     // an iteration bufB (issued one whole process() earlier) is moved to bufA, the next sub-batch is
     // requested into bufB and the arithmetic runs on bufA, whose registers are never the target of a
     // load - nothing in process() waits for the prefetch in flight.
     if (q < nsuper) {
-        load_side(q, zoN, lmN);
+        load_side(q, zoN, lmN, sgN);
         load_rows(q, 0, bufB);
     }
 #pragma clang loop unroll(disable)
@@ -242,17 +256,18 @@ __global__ __launch_bounds__(SE_THREADS, OCC) void k_sweep_erm(
         if (sub == 0) {
             zo = zoN;
             lm = lmN;
+            if constexpr (WT) sg = sgN;
         }
         const bool last = sub + 1 == S;
         const int qn = last ? q + GW : q;
         const int subn = last ? 0 : sub + 1;
         __builtin_amdgcn_sched_barrier(0);
         if (qn < nsuper) {
-            if (last) load_side(qn, zoN, lmN);
+            if (last) load_side(qn, zoN, lmN, sgN);
             load_rows(qn, subn, bufB);
         }
         __builtin_amdgcn_sched_barrier(0);   // the prefetch stays above the arithmetic
-        process(live, sub, bufA, zo, lm);
+        process(live, sub, bufA, zo, lm, sg);
         if (last && lane < live && !QONLY) {
             const long long row = (long long)q * SR + lane;
             row_store(lam, row, l_out);
@@ -305,10 +320,11 @@ __global__ __launch_bounds__(SE_THREADS, OCC) void k_sweep_erm(
 // the column sums: R is the largest number of rows whose two buffers fit (launch_T).
 constexpr int SEW_THREADS = 512;
 
-template <typename T, int LOSS, int PT, int R, int S>
+// WT: the row-weighted twin (SE_FUSED_W of the wave-per-row kernel) - sigma0 is one sigma per row, kept in one more LDS slot
+template <typename T, int LOSS, int PT, int R, int S, bool WT>
 __global__ __launch_bounds__(SEW_THREADS, 1) void k_sweep_erm_wide(
     const T* __restrict__ D, long long n, long long ld, const double* __restrict__ w, const double* __restrict__ z_old,
-    double* __restrict__ lam, double* __restrict__ v, double* __restrict__ z_new, double sigma0, double rho,
+    double* __restrict__ lam, double* __restrict__ v, double* __restrict__ z_new, typename SigArg<WT>::type sigma0, double rho,
     const double* __restrict__ pred, double* __restrict__ slab, double* __restrict__ partials) {
     constexpr int E = Pk<T>::E;
     constexpr int NT = SEW_THREADS;
@@ -350,17 +366,19 @@ __global__ __launch_bounds__(SEW_THREADS, 1) void k_sweep_erm_wide(
     // sub-batch fit without a spill (three rows of 5 packets in flight per wave instead of two: C5shard 124.6 -> 132
     // it/s); the LDS round trips on the owner's path between the two barriers cost ~1.5 % at equal R.
     __shared__ double rw_zo[SR], rw_lm[SR], rw_l[SR], rw_v[SR], rw_z[SR], rw_prim[SR], rw_zz[SR];
+    __shared__ double rw_sg[WT ? SR : 1];   // (WT) sigma of the row, beside rw_zo / rw_lm
     if (tid < SR) {
         rw_prim[tid] = 0.0;
         rw_zz[tid] = 0.0;
     }
 
-    auto load_side = [&](int q, double& zo, double& lm) {
+    auto load_side = [&](int q, double& zo, double& lm, double& sg) {
         const int live = q == nsuper - 1 ? live_last : SR;
         const bool mine = tid < live;
         const long long myrow = (long long)q * SR + tid;
         zo = mine ? z_old[myrow] : 0.0;
         lm = mine ? lam[myrow] : 0.0;
+        if constexpr (WT) sg = mine ? sigma0[myrow] : 0.0;
     };
     auto load_rows = [&](int q, int sub, u32x4 (&buf)[R][PT]) {
         const int live = q == nsuper - 1 ? live_last : SR;
@@ -406,12 +424,15 @@ __global__ __launch_bounds__(SEW_THREADS, 1) void k_sweep_erm_wide(
 #pragma unroll
             for (int wv = 0; wv < NW; ++wv) myv += part[wv][r];
             const double zo = rw_zo[tid];
+            double sig;
+            if constexpr (WT) sig = rw_sg[tid];
+            else sig = sigma0;
             const double res = zo - myv;
             const double l = rw_lm[tid] + rho * res;               // algorithms.py:132
             rw_prim[tid] += res * res;                             // algorithms.py:135
             const double lr = l / rho_next;
             const double m = myv - lr;                             // algorithms.py:89 (next iteration)
-            const double zn = (LOSS == 0) ? rbl::prox_bce_warm(sigma0, rho_next, m, zo) : rbl::prox<LOSS>(sigma0, rho_next, m);
+            const double zn = (LOSS == 0) ? rbl::prox_bce_warm(sig, rho_next, m, zo) : rbl::prox<LOSS>(sig, rho_next, m);
             rw_zz[tid] += zn * zn;
             rw_l[tid] = l;
             rw_v[tid] = myv;
@@ -437,10 +458,10 @@ __global__ __launch_bounds__(SEW_THREADS, 1) void k_sweep_erm_wide(
     // NEXT sub-batch is requested into bufB, and the arithmetic runs on bufA, whose registers are
     // never the target of a load (so nothing in process() waits for the prefetch in flight).
     u32x4 bufA[R][PT], bufB[R][PT];
-    double zoN = 0.0, lmN = 0.0;
+    double zoN = 0.0, lmN = 0.0, sgN = 0.0;
     int q = (int)blockIdx.x, sub = 0;
     if (q < nsuper) {
-        load_side(q, zoN, lmN);
+        load_side(q, zoN, lmN, sgN);
         load_rows(q, 0, bufB);
     }
 #pragma clang loop unroll(disable)
@@ -453,13 +474,14 @@ __global__ __launch_bounds__(SEW_THREADS, 1) void k_sweep_erm_wide(
         if (sub == 0 && tid < SR) {
             rw_zo[tid] = zoN;
             rw_lm[tid] = lmN;
+            if constexpr (WT) rw_sg[tid] = sgN;
         }
         const bool last = sub + 1 == S;
         const int qn = last ? q + GW : q;
         const int subn = last ? 0 : sub + 1;
         __builtin_amdgcn_sched_barrier(0);
         if (qn < nsuper) {
-            if (last) load_side(qn, zoN, lmN);
+            if (last) load_side(qn, zoN, lmN, sgN);
             load_rows(qn, subn, bufB);
         }
         __builtin_amdgcn_sched_barrier(0);   // the prefetch stays above the arithmetic
@@ -590,19 +612,21 @@ __global__ __launch_bounds__(256) void k_sumsq(long long n, const double* __rest
     if (threadIdx.x == 0) partials[blockIdx.x] = a[0];
 }
 
-template <typename T, int LOSS, int P, int R, int S, bool WL, int OCC>
+// SG: double (sigma0, the unweighted instances) or const double* (one sigma per row: their SE_FUSED_W twins)
+template <typename T, int LOSS, int P, int R, int S, bool WL, int OCC, typename SG>
 int launch_one(const T* D, long long n, long long ld, const double* w, const double* z_old, double* lam, double* v,
-               double* z_new, double sigma0, double rho, const double* pred, double* slab, double* partials, int grid,
+               double* z_new, SG sigma0, double rho, const double* pred, double* slab, double* partials, int grid,
                hipStream_t s) {
-    hipLaunchKernelGGL((k_sweep_erm<T, LOSS, P, R, S, WL, SE_FUSED, OCC>), dim3(grid), dim3(SE_THREADS), 0, s, D, n, ld, w, z_old,
+    constexpr int MODE = std::is_pointer<SG>::value ? SE_FUSED_W : SE_FUSED;
+    hipLaunchKernelGGL((k_sweep_erm<T, LOSS, P, R, S, WL, MODE, OCC>), dim3(grid), dim3(SE_THREADS), 0, s, D, n, ld, w, z_old,
                        lam, v, z_new, sigma0, rho, pred, slab, partials);
     RBL_HIP(hipGetLastError());
     return RBL_OK;
 }
 
-template <typename T, int LOSS>
+template <typename T, int LOSS, typename SG>
 int launch_T(const T* D, long long n, long long ld, const double* w, const double* z_old, double* lam, double* v,
-             double* z_new, double sigma0, double rho, const double* pred, double* slab, double* partials, int grid,
+             double* z_new, SG sigma0, double rho, const double* pred, double* slab, double* partials, int grid,
              int num_cu, int* used, SweepInstance* inst, hipStream_t s) {
     const long long PK = ld / Pk<T>::E;
     const long long passes = (PK + 63) / 64;
@@ -648,7 +672,7 @@ int launch_T(const T* D, long long n, long long ld, const double* w, const doubl
     *used = wgrid;
 #define RBL_WIDE(PT_, R_, S_)                                                                                          \
     do {                                                                                                               \
-        auto kfn = k_sweep_erm_wide<T, LOSS, PT_, R_, S_>;                                                             \
+        auto kfn = k_sweep_erm_wide<T, LOSS, PT_, R_, S_, std::is_pointer<SG>::value>;                                  \
         const size_t lds = (size_t)PT_ * SEW_THREADS * Pk<T>::E * sizeof(double);                                      \
         static bool attr_set = false;                                                                                  \
         if (!attr_set) {                                                                                               \
@@ -690,22 +714,13 @@ int launch_T(const T* D, long long n, long long ld, const double* w, const doubl
 
 }  // namespace
 
-bool sweep_erm_supported(int storage, int64_t ld) {
-    if (storage == RBL_STORE_CSR) return false;   // sparse storage runs the two-pass iteration (spmv.hip)
-    const int64_t PK = ld / rbl_storage_packet(storage);
-    // wave-per-row kernel up to 4 (fp32) / 8 (fp64) passes of 64 packets, workgroup-per-row
-    // kernel up to 8 packets per thread: d <= 16384 (fp32) / 8192 (fp64).  fp16: 4 packets per thread (w in LDS is
-    // 8 doubles per packet: 128 KB at 4), which is the same d <= 16384; rows of <= 32 packets are ld <= 256
-    return PK > 32 && PK <= (storage == RBL_STORE_F16 ? 4 : 8) * SEW_THREADS;
-}
-// upper bound of the blocks a single-sweep launch uses (slab rows, partial triples): 2 per CU; the shapes that run one
-// block per CU (launch_T) use the first half
-int sweep_erm_blocks(int num_cu) { return num_cu * 2; }
-int sweep_erm_slab_rows(int num_cu) { return sweep_erm_blocks(num_cu) + CR_SLICES; }
-int launch_sweep_erm(int storage, int loss, const void* D, int64_t n, int64_t ld, const double* w, const double* z_old,
-                     double* lam, double* v, double* z_new, double sigma0, double rho, const double* pred_dev,
-                     double* slab, double* partials, double* q, double* red, double* zz_out, int num_cu, hipStream_t s,
-                     hipEvent_t main_done, int want_obj, SweepInstance* inst) {
+// the pass and what follows it, for the scalar sigma0 (SG = double) and for one sigma per row (SG = const double*);
+// loss_w: row weights of the logged loss sum (NULL: none)
+template <typename SG>
+static int sweep_erm_any(int storage, int loss, const void* D, int64_t n, int64_t ld, const double* w, const double* z_old,
+                         double* lam, double* v, double* z_new, SG sigma0, double rho, const double* pred_dev, double* slab,
+                         double* partials, double* q, double* red, double* zz_out, int num_cu, hipStream_t s,
+                         hipEvent_t main_done, int want_obj, SweepInstance* inst, const double* loss_w) {
     const int grid = sweep_erm_blocks(num_cu);
     int nrows = grid;   // slab rows / partial triples produced = blocks launched
     double* const v_for_loss = v;
@@ -728,8 +743,42 @@ int launch_sweep_erm(int storage, int loss, const void* D, int64_t n, int64_t ld
     RBL_HIP(hipGetLastError());
     // objective.py:11-24: the per-sample losses are summed from v in a pass of their own (8 B per
     // row) - exp/log1p inside the sweep cost registers on its critical path
-    if (want_obj) RBL_TRY(launch_loss_sum(loss, n, v_for_loss, 1.0, partials, red + 1, s));
+    if (want_obj) RBL_TRY(launch_loss_sum(loss, n, v_for_loss, 1.0, partials, red + 1, s, nullptr, loss_w));
     return RBL_OK;
+}
+
+#ifdef RBL_SWEEP_ERM_W_UNIT
+// sweep_erm_w.hip: this file again, for the SE_FUSED_W instantiations alone - they double the fused kernels, and one
+// translation unit with both is what the whole build would wait for
+int launch_sweep_erm_w(int storage, int loss, const void* D, int64_t n, int64_t ld, const double* w, const double* z_old,
+                       double* lam, double* v, double* z_new, const double* sigma_rows, double rho, const double* pred_dev,
+                       double* slab, double* partials, double* q, double* red, double* zz_out, int num_cu, hipStream_t s,
+                       hipEvent_t main_done, int want_obj, SweepInstance* inst, const double* loss_w) {
+    return sweep_erm_any(storage, loss, D, n, ld, w, z_old, lam, v, z_new, sigma_rows, rho, pred_dev, slab, partials, q, red,
+                         zz_out, num_cu, s, main_done, want_obj, inst, loss_w);
+}
+#else
+bool sweep_erm_supported(int storage, int64_t ld) {
+    if (storage == RBL_STORE_CSR) return false;   // sparse storage runs the two-pass iteration (spmv.hip)
+    const int64_t PK = ld / rbl_storage_packet(storage);
+    // wave-per-row kernel up to 4 (fp32) / 8 (fp64) passes of 64 packets, workgroup-per-row
+    // kernel up to 8 packets per thread: d <= 16384 (fp32) / 8192 (fp64).  fp16: 4 packets per thread (w in LDS is
+    // 8 doubles per packet: 128 KB at 4), which is the same d <= 16384; rows of <= 32 packets are ld <= 256
+    return PK > 32 && PK <= (storage == RBL_STORE_F16 ? 4 : 8) * SEW_THREADS;
+}
+// upper bound of the blocks a single-sweep launch uses (slab rows, partial triples): 2 per CU; the shapes that run one
+// block per CU (launch_T) use the first half
+int sweep_erm_blocks(int num_cu) { return num_cu * 2; }
+int sweep_erm_slab_rows(int num_cu) { return sweep_erm_blocks(num_cu) + CR_SLICES; }
+int launch_sweep_erm(int storage, int loss, const void* D, int64_t n, int64_t ld, const double* w, const double* z_old,
+                     double* lam, double* v, double* z_new, double sigma0, double rho, const double* pred_dev,
+                     double* slab, double* partials, double* q, double* red, double* zz_out, int num_cu, hipStream_t s,
+                     hipEvent_t main_done, int want_obj, SweepInstance* inst, const double* sigma_rows, const double* loss_w) {
+    if (sigma_rows)   // row weights: the SE_FUSED_W twins (sweep_erm_w.hip), sigma0 unused
+        return launch_sweep_erm_w(storage, loss, D, n, ld, w, z_old, lam, v, z_new, sigma_rows, rho, pred_dev, slab, partials, q,
+                                  red, zz_out, num_cu, s, main_done, want_obj, inst, loss_w);
+    return sweep_erm_any(storage, loss, D, n, ld, w, z_old, lam, v, z_new, sigma0, rho, pred_dev, slab, partials, q, red, zz_out,
+                         num_cu, s, main_done, want_obj, inst, loss_w);
 }
 
 namespace {
@@ -862,3 +911,4 @@ int launch_sumsq(int64_t n, const double* x, double* partials, double* out, hipS
     RBL_HIP(hipGetLastError());
     return launch_sum_partials(partials, nb, 1, out, s);
 }
+#endif  // RBL_SWEEP_ERM_W_UNIT

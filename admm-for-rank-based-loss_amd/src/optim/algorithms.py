@@ -17,7 +17,10 @@ columns of X are centred and scaled to unit population variance on the device, o
 ``scale_mean_`` / ``scale_scale_`` hold the vectors, every later matrix of the object - the test set of ``start_store`` -
 gets the same scaling, ``unscaled()`` gives the coefficients for raw features).  X is taken as it is: a NumPy array or
 torch CPU tensor of float64 / float32 / float16 is uploaded in its own type without a host copy, a torch tensor on the
-solver's GPU is read where it lives (_solver.as_source).
+solver's GPU is read where it lives (_solver.as_source).  ``sample_weight`` (n values >= 0) and ``class_weight``
+("balanced": c_i = n / (2 n_{y_i}), or a dict {+1: a, -1: b}) weigh the rows of an erm problem: F(w) = (1/n) sum_i c_i
+loss_i(w) + R(w) (include/rbl.h: rbl_set_row_weights); ``sample_weight_`` holds the resolved vector (None without
+weights), ``set_sample_weight(c)`` replaces it between ``main_loop`` calls or iterations.
 """
 import time
 
@@ -44,7 +47,7 @@ class Optimizer:
     def __init__(self, X, y, weight_function="erm", loss="binary_cross_entropy", l2_reg=None, l1_reg=None,
                  B=None, n_class=None, args=None, w0=None, max_iter=200, tol=1e-4, storage="f32", device=0,
                  _wstep=None, _smooth_t=1.0, share_data=None, l1_weights=None, l2_weights=None, fit_intercept=False,
-                 standardize=False):
+                 standardize=False, sample_weight=None, class_weight=None):
         # argument checks in the reference's order (objective first :22, then :55-68)
         _solver.check_problem(weight_function, loss, B, args)
         if l1_reg is None and l2_reg is None and l1_weights is None and l2_weights is None:
@@ -87,6 +90,14 @@ class Optimizer:
                 raise ValueError("share_data was built with another storage type or device")
             if y is not None:
                 y_own = _solver.as_pm1_labels(y, self.num_row)      # shape / +-1 before any device call
+        # row weights (erm only): validated on the host before any device call; None = the unweighted path
+        self.sample_weight_ = None
+        if sample_weight is not None or class_weight is not None:
+            if y is None and share is not None:
+                y_w = share.labels()                # the labels of the solver whose data are borrowed
+            else:
+                y_w = y_own if y_own is not None else _solver.as_pm1_labels(y, self.num_row)
+            self.sample_weight_ = _solver.resolve_row_weights(y_w, sample_weight, class_weight, weight_function)
         self._s = _solver.Solver(self.num_row, self.num_feature, weight_function, loss, reg=self.reg, wstep=wstep,
                                  B=B, args=args, smooth_t=_smooth_t, tol=tol, max_iter=max_iter, storage=storage,
                                  device=device, share=share)
@@ -108,6 +119,8 @@ class Optimizer:
         self.scale_scale_ = None if sc is None else sc[1][:nf].copy()
         if pen:
             self._s.set_penalty(pen["l1"], pen["l2"])
+        if self.sample_weight_ is not None:
+            self._s.set_row_weights(self.sample_weight_)
         if w0 is not None:                                                                    # :39-40
             w0 = np.asarray(w0, dtype=np.float64).reshape(-1)
             if self.fit_intercept and w0.size == self.num_feature - 1:
@@ -197,13 +210,23 @@ class Optimizer:
         return D.T @ D
 
     # ---- logging (:77-86) ------------------------------------------------------------------
+    def set_sample_weight(self, c):
+        """Replace the row weights (n values >= 0, at least one > 0; None: back to the unweighted problem) - between
+        main_loop calls or between iterations; the next z-step uses them.  The logged objective follows."""
+        if c is not None:
+            c = _solver.resolve_row_weights(np.ones(self.num_row), c, None, self.weight_function)
+        self._s.set_row_weights(c)
+        self.sample_weight_ = c
+
     def start_store(self, X, y, weight_function="erm", loss="binary_cross_entropy", B=None, l2_reg=None,
-                    l1_reg=None, n_class=None, args=None, _share_data=None):
-        # the test matrix as it is, with the training scaling and the library's own column of ones
+                    l1_reg=None, n_class=None, args=None, _share_data=None, sample_weight_test=None):
+        # the test matrix as it is, with the training scaling and the library's own column of ones; the test objective is
+        # unweighted unless it gets weights of its own
         self.test_objective = rankbasedObjective(X, y, weight_function, loss, l2_reg, l1_reg, B, n_class, args,
                                                  storage=self._storage, device=self._device, _share_data=_share_data,
                                                  scaling=self._scaling, _ones_column=self.fit_intercept,
-                                                 _penalty=(self._pen["l1"], self._pen["l2"]) if self._pen else None)
+                                                 _penalty=(self._pen["l1"], self._pen["l2"]) if self._pen else None,
+                                                 sample_weight=sample_weight_test)
         w = self.w
         self._s.profile_kernels(2)     # z_time / w_time below come from HIP events around the phases
         self.w_time = [0]
@@ -272,15 +295,18 @@ class Optimizer:
 class ADMMmethod(Optimizer):
     def __init__(self, X, y, weight_function="erm", loss="binary_cross_entropy", l2_reg=None, l1_reg=None, B=None,
                  n_class=None, args=None, w0=None, max_iter=200, tol=1e-4, storage="f32", device=0,
-                 l1_weights=None, l2_weights=None, fit_intercept=False, standardize=False, share_data=None):
-        # (share_data stays the trailing keyword; the four before it are meant to be given by name)
+                 l1_weights=None, l2_weights=None, fit_intercept=False, standardize=False, sample_weight=None,
+                 class_weight=None, share_data=None):
+        # (share_data stays the trailing keyword; the six before it are meant to be given by name)
         super().__init__(X, y, weight_function, loss, l2_reg, l1_reg, B, n_class, args, w0, max_iter, tol,
                          storage=storage, device=device, share_data=share_data, l1_weights=l1_weights,
-                         l2_weights=l2_weights, fit_intercept=fit_intercept, standardize=standardize)
+                         l2_weights=l2_weights, fit_intercept=fit_intercept, standardize=standardize,
+                         sample_weight=sample_weight, class_weight=class_weight)
 
     def start_store(self, X, y, weight_function="erm", loss="binary_cross_entropy", B=None, l2_reg=None,
-                    l1_reg=None, n_class=None, args=None):
-        super().start_store(X, y, weight_function, loss, B, l2_reg, l1_reg, n_class, args)
+                    l1_reg=None, n_class=None, args=None, sample_weight_test=None):
+        super().start_store(X, y, weight_function, loss, B, l2_reg, l1_reg, n_class, args,
+                            sample_weight_test=sample_weight_test)
 
     def main_loop(self, verbose=True):                                                    # :209-216
         t_start = time.time()
@@ -296,14 +322,15 @@ class ADMMmethod(Optimizer):
 class smoothADMMmethod(Optimizer):
     def __init__(self, X, y, weight_function="erm", loss="binary_cross_entropy", B=None, l2_reg=None, l1_reg=None,
                  n_class=None, args=None, w0=None, t=1, max_iter=200, tol=1e-4, storage="f32", device=0,
-                 l1_weights=None, l2_weights=None, fit_intercept=False, standardize=False, share_data=None):
+                 l1_weights=None, l2_weights=None, fit_intercept=False, standardize=False, sample_weight=None,
+                 class_weight=None, share_data=None):
         if l1_weights is not None or l2_weights is not None or fit_intercept:
             raise ValueError("smoothADMMmethod has no per-coordinate penalties: l1_weights, l2_weights and fit_intercept "
                              "belong to ADMMmethod (the smoothed-l1 w-step smooths one scalar l1 norm)")
         wstep = _lib.WSTEP_SMOOTH_L1 if l1_reg is not None else None
         super().__init__(X, y, weight_function, loss, l2_reg, l1_reg, B, n_class, args, w0, max_iter, tol,
                          storage=storage, device=device, _wstep=wstep, _smooth_t=float(t), share_data=share_data,
-                         standardize=standardize)
+                         standardize=standardize, sample_weight=sample_weight, class_weight=class_weight)
 
     @property
     def t(self):
@@ -314,8 +341,9 @@ class smoothADMMmethod(Optimizer):
         self._s.set_state(smooth_t=float(value))
 
     def start_store(self, X, y, weight_function="erm", loss="binary_cross_entropy", B=None, l2_reg=None,
-                    l1_reg=None, n_class=None, args=None):
-        super().start_store(X, y, weight_function, loss, B, l2_reg, l1_reg, n_class, args)
+                    l1_reg=None, n_class=None, args=None, sample_weight_test=None):
+        super().start_store(X, y, weight_function, loss, B, l2_reg, l1_reg, n_class, args,
+                            sample_weight_test=sample_weight_test)
 
     def main_loop(self, verbose=True):                                                    # :248-260
         t_start = time.time()
@@ -345,7 +373,7 @@ class ADMMgroup:
     the columns of X on the device.  X is taken as it is (_solver.as_source)."""
 
     _KEYS = ("weight_function", "loss", "l2_reg", "l1_reg", "B", "args", "w0", "smooth", "t", "y", "l1_weights",
-             "l2_weights", "fit_intercept", "standardize")
+             "l2_weights", "fit_intercept", "standardize", "sample_weight", "class_weight")
 
     def __init__(self, X, y, problems, storage="f32", device=0, max_iter=200, tol=1e-4):
         if not isinstance(problems, (list, tuple)) or len(problems) == 0:
@@ -384,6 +412,9 @@ class ADMMgroup:
                     raise ValueError("t is the smoothing parameter of smooth=True members")
                 if pr.get("y") is not None:
                     pr["y"] = _solver.as_pm1_labels(pr["y"], X.shape[0])
+                if pr.get("sample_weight") is not None or pr.get("class_weight") is not None:   # row weights: on the host, now
+                    _solver.resolve_row_weights(_solver.as_pm1_labels(pr["y"] if pr.get("y") is not None else y, X.shape[0]),
+                                                pr.get("sample_weight"), pr.get("class_weight"), pr["weight_function"])
             except ValueError as e:
                 raise ValueError(f"problem {k}: {e}") from None
             self.problems.append(pr)
@@ -392,7 +423,7 @@ class ADMMgroup:
         self.max_iter, self.tol = max_iter, tol
         self.solvers = []
         for pr in self.problems:
-            kw = {k: pr.get(k) for k in ("l2_reg", "l1_reg", "B", "args", "w0")}
+            kw = {k: pr.get(k) for k in ("l2_reg", "l1_reg", "B", "args", "w0", "sample_weight", "class_weight")}
             share = self.solvers[0] if self.solvers else None
             yk = pr["y"] if pr.get("y") is not None else y
             if pr.get("smooth"):
@@ -492,7 +523,9 @@ class OneVsRest:
 
     def __init__(self, X, labels, weight_function="erm", loss="binary_cross_entropy", l2_reg=None, l1_reg=None, B=None,
                  args=None, storage="f32", device=0, max_iter=200, tol=1e-4, l1_weights=None, l2_weights=None,
-                 fit_intercept=False, standardize=False):
+                 fit_intercept=False, standardize=False, sample_weight=None, class_weight=None):
+        # class_weight="balanced": every member gets the balanced weights of its OWN +-1 labels (one class against the
+        # rest is imbalanced by construction); a common sample_weight multiplies into all of them
         Xm = _solver.as_source(X, device)
         self.fit_intercept = bool(fit_intercept)
         lab = np.asarray(labels.detach().cpu().numpy() if hasattr(labels, "detach") else labels).reshape(-1)
@@ -506,7 +539,8 @@ class OneVsRest:
         ys = [np.where(lab == c, 1.0, -1.0) for c in self.classes_]
         problems = [dict(weight_function=weight_function, loss=loss, l2_reg=l2_reg, l1_reg=l1_reg, B=B, args=args, y=yk,
                          l1_weights=l1_weights, l2_weights=l2_weights, fit_intercept=self.fit_intercept,
-                         standardize=bool(standardize)) for yk in ys]
+                         standardize=bool(standardize), sample_weight=sample_weight, class_weight=class_weight)
+                    for yk in ys]
         self._storage, self._device = storage, device
         self.group = ADMMgroup(Xm, ys[0], problems, storage=storage, device=device, max_iter=max_iter, tol=tol)
         first = self.group.solvers[0]

@@ -70,7 +70,8 @@ class rankbasedObjective:
 
     def __init__(self, X, y, weight_function="erm", loss="binary_cross_entropy", l2_reg=None, l1_reg=None,
                  B=None, n_class=None, args=None, storage="f32", device=0, _shared_solver=None, _share_data=None,
-                 _penalty=None, scaling=None, _ones_column=False):
+                 _penalty=None, scaling=None, _ones_column=False, sample_weight=None, class_weight=None):
+        # sample_weight / class_weight (erm only): F(w) = (1/n) sum_i c_i loss_i(w) + R(w), _solver.resolve_row_weights
         _solver.check_problem(weight_function, loss, B, args, need_prox=False)
         if loss == "multinomial_cross_entropy":
             raise ValueError("multinomial_cross_entropy is outside the ADMM hot path (binary losses only)")
@@ -80,9 +81,12 @@ class rankbasedObjective:
         self.B = B
         self.lossB = None if B is None else float(np.logaddexp(0.0, B))     # objective.py:59-63
         self.n_class = n_class
+        self.sample_weight_ = None
         if _shared_solver is not None:
             self._s = _shared_solver
             self.n, self.d = self._s.n_total, self._s.d
+            if sample_weight is not None or class_weight is not None:
+                raise ValueError("a shared solver carries its own row weights: give them to the solver")
         else:
             # X as it is (_solver.as_source).  scaling: (mean, scale) of a solver (its scale_mean_ / scale_scale_, or
             # Solver.get_scaling()) - this matrix is standardised with them on the device; _ones_column: the intercept's
@@ -94,6 +98,9 @@ class rankbasedObjective:
             if share is not None and (share.n, share.d) != (self.n, self.d):
                 raise ValueError(f"shared data is {(share.n, share.d)}, X is {(self.n, self.d)}")
             y_own = _solver.as_pm1_labels(y, self.n) if share is not None and y is not None else None
+            if sample_weight is not None or class_weight is not None:      # on the host, before any device call
+                y_w = share.labels() if (y is None and share is not None) else _solver.as_pm1_labels(y, self.n)
+                self.sample_weight_ = _solver.resolve_row_weights(y_w, sample_weight, class_weight, weight_function)
             self._s = _solver.Solver(self.n, self.d, weight_function, loss, args=args, B=B, storage=storage,
                                      device=device, objective_only=True, share=share)
             if share is None:
@@ -102,6 +109,8 @@ class rankbasedObjective:
                 self._s.set_data(Xm, y, scaling="none" if scaling is None else "apply", ones_column=_ones_column)
             elif y_own is not None:
                 self._s.set_labels(y_own)      # labels of its own on the borrowed matrix (rbl_set_labels)
+            if self.sample_weight_ is not None:
+                self._s.set_row_weights(self.sample_weight_)
         # per-coordinate penalties (l1, l2) of the solver (ADMMmethod's l1_weights / l2_weights / fit_intercept): the
         # regulariser is then evaluated by the library on this handle (rbl_objective), an own handle is given the vectors
         self._penalty = _penalty

@@ -172,6 +172,26 @@ int  rbl_set_labels(rbl_solver* h, const double* y);
 int  rbl_set_penalty(rbl_solver* h, const double* l1, const double* l2);
 /* the vectors of rbl_set_penalty (d doubles each, either may be NULL); *is_set = 0 and zeros when none were set */
 int  rbl_get_penalty(rbl_solver* h, double* l1, double* l2, int* is_set);
+/* Row weights of an erm problem: F(w) = (1/n) sum_i c_i loss_i(w) + R(w).  c: n host doubles in the row order of X, each
+ * finite and >= 0, at least one > 0; no normalisation is applied.  The weights enter the z-step alone: the element prox
+ * of row i runs with sigma_i = c_i * sigma0 (one product; sigma0 = 1.0 / n_total, so c == 1.0 computes the unweighted
+ * path's bits) - in the single-sweep pass (rbl_stats.fused stays 1: sigma_i is a third row-wise load, 8 more bytes per
+ * row) and in the two-pass z-step.  D, G, the w-step, the dual update, the residuals, the rho schedule and its
+ * prediction never see them, so borrowers of one D carry different weights (cross-validation folds as 0/1 weights).  A
+ * row with c_i = 0 leaves the problem: z_i = m_i and its multiplier goes to 0.  rbl_objective, rbl_risk_from_v and the
+ * logged objective use the weights; rbl_accuracy, rbl_fair_statistics and rbl_decide_multi do not.
+ *   c == NULL returns the handle to the unweighted path (its own two n-vectors are freed, nothing shared is).  May be
+ * called whenever rbl_set_state may, also between iterations: the next z-step uses the new weights, and what was
+ * computed ahead (the z-step of the previous pass, the w-step enqueued ahead of time) is dropped.  rbl_set_labels and a
+ * new upload leave the weights as they are (n is fixed per handle).  Works on owners, borrowers (relabelled ones too),
+ * group members and objective_only handles.  RBL_ERR_INVALID, with the reason: a weight that is negative or not finite
+ * (the message names the first such row), all weights zero, a weight function other than RBL_W_ERM (with weights the
+ * sigma of a rank depends on the cumulative weight in sorted order: the PAV z-step does not apply), a row-sharded handle
+ * (n != n_total: several devices are out of scope).  The presence of these symbols is the capability probe
+ * (RBL_VERSION is unchanged). */
+int  rbl_set_row_weights(rbl_solver* h, const double* c /* n, or NULL */);
+/* the weights of rbl_set_row_weights (n doubles, may be NULL); *is_set = 0 and ones when none are set */
+int  rbl_get_row_weights(rbl_solver* h, double* c, int* is_set);
 /* run the library's kernels on this hipStream_t: NULL is the (legacy) default stream,
  * (void*)-1 goes back to the handle's own non-blocking stream (the initial setting) */
 int  rbl_set_stream(rbl_solver* h, void* hip_stream);
@@ -576,6 +596,13 @@ int  rbl_k_gemvt_multi(int storage, int64_t n, int64_t d, int k, const double* D
 int  rbl_k_sweep_erm(int storage, int loss, int64_t n, int64_t d, const double* D, const double* w, const double* z_old,
                      const double* lam, double sigma0, double rho, double rho_next, int num_cu, int want_v,
                      double* lam_out, double* v, double* z_new, double* q, double* primal2, double* zz, int* instance);
+/* rbl_k_sweep_erm with one sigma per row (sigma: n host doubles, sigma_i = c_i * sigma0 of rbl_set_row_weights) in the
+ * place of sigma0: the row-weighted twin of whichever instance rbl_k_sweep_erm runs at that width - same launcher, same
+ * num_cu and instance reporting, same NaN presets and guard behind row n.  sigma_i == sigma0 for all i gives
+ * rbl_k_sweep_erm's bits.  sigma NULL is RBL_ERR_INVALID. */
+int  rbl_k_sweep_erm_w(int storage, int loss, int64_t n, int64_t d, const double* D, const double* w, const double* z_old,
+                       const double* lam, const double* sigma /* n */, double rho, double rho_next, int num_cu, int want_v,
+                       double* lam_out, double* v, double* z_new, double* q, double* primal2, double* zz, int* instance);
 int  rbl_k_sweep_v(int storage, int64_t n, int64_t d, const double* D, const double* w, const double* z, const double* lam,
                    double rho, int num_cu, double* lam_out, double* v, double* primal2, int* instance);
 int  rbl_k_sweep_q(int storage, int64_t n, int64_t d, const double* D, const double* c, int num_cu, double* q, int* instance);
