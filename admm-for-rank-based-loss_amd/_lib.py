@@ -25,6 +25,7 @@ SOURCE_DTYPE = {np.dtype(np.float64): DTYPE_F64, np.dtype(np.float32): DTYPE_F32
 MEM_HOST, MEM_DEVICE = 0, 1
 SCALING = {"none": 0, "fit": 1, "apply": 2}
 DATA_ONES_COLUMN = 1
+GROUP_SHARE_SPARSE = 1          # rbl_group_create_opts: shared multi-column passes on storage "csr"
 # rbl_set_data_csr: the type of indptr and indices
 INDEX_I32, INDEX_I64 = 0, 1
 INDEX_DTYPE = {np.dtype(np.int32): INDEX_I32, np.dtype(np.int64): INDEX_I64}
@@ -146,6 +147,9 @@ SIGNATURES = {
     "rbl_get_row_weights": (C.c_int, [_P, _P, C.POINTER(C.c_int)]),
     "rbl_decide_multi": (C.c_int, [_P, C.c_int, _P, _P]),
     "rbl_group_create": (C.c_int, [C.POINTER(_P), C.c_int, C.POINTER(_P)]),
+    "rbl_group_create_opts": (C.c_int, [C.POINTER(_P), C.c_int, C.c_int, C.POINTER(_P)]),
+    "rbl_group_profile": (C.c_int, [_P, C.c_int]),
+    "rbl_group_pass_times": (C.c_int, [_P, _D, _I64]),
     "rbl_group_destroy": (C.c_int, [_P]),
     "rbl_group_step": (C.c_int, [_P, C.c_int, C.POINTER(RblStats)]),
     "rbl_group_solve": (C.c_int, [_P, C.c_int, C.c_int, C.POINTER(RblStats), _P, _P, _P, _P, _I64, C.c_int64]),
@@ -239,6 +243,8 @@ SIGNATURES = {
     "rbl_k_gram": (C.c_int, [C.c_int, C.c_int64, C.c_int64, _P, _P]),
     "rbl_k_csr_gemv": (C.c_int, [C.c_int64, C.c_int64, _P, _P, _P, _P, _P]),
     "rbl_k_csr_gemvt": (C.c_int, [C.c_int64, C.c_int64, _P, _P, _P, _P, _P]),
+    "rbl_k_csr_gemv_multi": (C.c_int, [C.c_int64, C.c_int64, _P, _P, _P, C.c_int, _P, C.c_int, _P, C.POINTER(C.c_int)]),
+    "rbl_k_csr_gemvt_multi": (C.c_int, [C.c_int64, C.c_int64, _P, _P, _P, C.c_int, _P, C.c_int, _P, C.POINTER(C.c_int64)]),
     "rbl_k_csr_gram": (C.c_int, [C.c_int64, C.c_int64, _P, _P, _P, _P]),
     "rbl_k_csr_gram_route": (C.c_int, [C.c_int64, C.c_int64, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P, C.POINTER(RblGramReport)]),
     "rbl_gram_info": (C.c_int, [_P, C.POINTER(RblGramReport)]),
@@ -605,6 +611,28 @@ def k_csr_gemvt(A, c):
     q = np.empty(storage_ld(d, "csr"))
     check(load().rbl_k_csr_gemvt(n, d, ptr(ip), ptr(ix), ptr(va), ptr(c), ptr(q)))
     return q
+
+
+def k_csr_gemv_multi(A, W, num_cu=1):
+    """(V, lanes): row j of V = A w_j for the k <= 4 rows of W (k x d) through the groups' multi-column sparse pass on a
+    grid sized for num_cu; lanes: the lane group of the pass"""
+    n, d, ip, ix, va = _csr_arrays(A)
+    W = f64(W).reshape(-1, d)
+    V = np.empty((W.shape[0], n))
+    lanes = C.c_int(0)
+    check(load().rbl_k_csr_gemv_multi(n, d, ptr(ip), ptr(ix), ptr(va), W.shape[0], ptr(W), int(num_cu), ptr(V), C.byref(lanes)))
+    return V, lanes.value
+
+
+def k_csr_gemvt_multi(A, Cm, num_cu=1):
+    """(Q, nseg): row j of Q = A^T c_j (storage_ld(d, "csr") entries, the padding included) for the k <= 4 rows of Cm
+    (k x n) through the groups' multi-column sparse pass; nseg: the segments of the column form"""
+    n, d, ip, ix, va = _csr_arrays(A)
+    Cm = f64(Cm).reshape(-1, n)
+    Q = np.empty((Cm.shape[0], storage_ld(d, "csr")))
+    nseg = C.c_int64(0)
+    check(load().rbl_k_csr_gemvt_multi(n, d, ptr(ip), ptr(ix), ptr(va), Cm.shape[0], ptr(Cm), int(num_cu), ptr(Q), C.byref(nseg)))
+    return Q, nseg.value
 
 
 def k_csr_gram(A):

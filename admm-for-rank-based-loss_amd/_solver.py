@@ -838,12 +838,21 @@ class Solver:
         return ms.value, cnt.value
 
 
+def check_share_sparse(value):
+    """``share_sparse`` of Group / ADMMgroup / OneVsRest is a bool: anything else is an argument error (no device call)"""
+    if not isinstance(value, (bool, np.bool_)):
+        raise ValueError(f"share_sparse must be True or False, got {value!r}")
+
+
 class Group:
     """Several Solvers on one data matrix iterated together, the two passes over D shared (include/rbl.h:
-    rbl_group_*).  The solvers stay usable on their own after close()."""
+    rbl_group_*).  The solvers stay usable on their own after close().  ``share_sparse=True`` opts a group on
+    storage "csr" into the shared multi-column sparse passes (RBL_GROUP_SHARE_SPARSE: same iterates bit for bit, the
+    entries of D read once per four members); on dense storage it has no effect."""
 
-    def __init__(self, solvers):
+    def __init__(self, solvers, share_sparse=False):
         self._g = None
+        check_share_sparse(share_sparse)
         self.solvers = list(solvers)
         if not self.solvers:
             raise ValueError("Group needs at least one solver")
@@ -853,7 +862,8 @@ class Group:
         self.k = len(self.solvers)
         arr = (C.c_void_p * self.k)(*[s._h.value for s in self.solvers])
         g = C.c_void_p()
-        _lib.check(self.lib.rbl_group_create(arr, self.k, C.byref(g)))
+        flags = _lib.GROUP_SHARE_SPARSE if share_sparse else 0
+        _lib.check(self.lib.rbl_group_create_opts(arr, self.k, flags, C.byref(g)))
         self._g = g
 
     def close(self):
@@ -883,6 +893,18 @@ class Group:
                                             _lib.ptr(hist["primal"]), _lib.ptr(hist["dual"]), _lib.ptr(hist["rho"]),
                                             iters.ctypes.data_as(C.POINTER(C.c_int64)), cap))
         return list(st), [{name: a[i, :int(iters[i])].copy() for name, a in hist.items()} for i in range(self.k)]
+
+    def profile(self, on=True):
+        """HIP events around the shared sparse passes of every step (rbl_group_profile); clears the sums"""
+        _lib.check(self.lib.rbl_group_profile(self._g, 1 if on else 0))
+
+    def pass_times(self):
+        """per-step milliseconds of the shared sparse passes since profile(): dict(v, q, pack, steps)"""
+        ms = (C.c_double * 3)()
+        steps = C.c_int64(0)
+        _lib.check(self.lib.rbl_group_pass_times(self._g, ms, C.byref(steps)))
+        n = max(1, steps.value)
+        return dict(v=ms[0] / n, q=ms[1] / n, pack=ms[2] / n, steps=steps.value)
 
     def counters(self):
         kpp = C.c_int(0)

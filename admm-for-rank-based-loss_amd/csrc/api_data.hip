@@ -1019,8 +1019,9 @@ int rbl_decide_multi(rbl_solver* h, int k, const double* W, int32_t* cls) {
     const int64_t n = h->n, ld = h->ld, d = h->d;
     if (n <= 0) return RBL_OK;
     hipStream_t s = h->stream;
-    const bool multi = sweep_multi_supported(h->storage, ld);
-    const int kpp = multi ? sweep_multi_k(h->storage, ld) : 1;
+    const bool sparse = h->storage == RBL_STORE_CSR;   // spmv.hip's multi-column pass: the scores keep the single-column bits
+    const bool multi = sparse || sweep_multi_supported(h->storage, ld);
+    const int kpp = sparse ? RBL_MULTI_KMAX : multi ? sweep_multi_k(h->storage, ld) : 1;
     DevArena mem;   // scratch of this call, freed on return (after the stream wait)
     double *dw = nullptr, *dv = nullptr, *best = nullptr;
     int* dcls = nullptr;
@@ -1044,7 +1045,8 @@ int rbl_decide_multi(rbl_solver* h, int k, const double* W, int32_t* cls) {
                 w[j] = dw + (size_t)(j0 + j) * ld;
                 v[j] = dv + (size_t)j * n;
             }
-            rc = launch_sweep_v_multi(h->storage, h->D, n, ld, kk, w, nullptr, nullptr, v, nullptr, nullptr, nullptr, h->num_cu, s);
+            rc = sparse ? launch_csr_gemv_multi((const CsrStore*)h->D, n, kk, w, v, h->num_cu, s)
+                        : launch_sweep_v_multi(h->storage, h->D, n, ld, kk, w, nullptr, nullptr, v, nullptr, nullptr, nullptr, h->num_cu, s);
         }
         if (rc == RBL_OK) rc = launch_decide_rows(n, kk, j0, dv, h->ysign, best, dcls, s);
     }

@@ -1,15 +1,42 @@
 // api_group.hip - groups: K problems on one D, one ADMM iteration of every live member per rbl_group_step with the two
-// n x d passes shared (sweep_multi.hip).  struct rbl_group: api_internal.h.
+// n x d passes shared (sweep_multi.hip; on RBL_STORE_CSR with RBL_GROUP_SHARE_SPARSE the multi-column passes of
+// spmv.hip).  struct rbl_group: api_internal.h.
 #include "api_internal.h"
 
 extern "C" {
 
-int rbl_group_create(rbl_solver* const* members, int k, rbl_group** out) {
+// The arena buffers of the shared sparse passes follow the store: the owner may have uploaded again since the last step
+// (more rows cannot come, more segments can).  The new buffer first: a failed allocation leaves the group its old one.
+static int group_sparse_room(rbl_group* g, const CsrStore* st) {
+    const size_t want[2] = {(size_t)st->nseg * RBL_MULTI_KMAX, (size_t)st->n * RBL_MULTI_KMAX};
+    double** buf[2] = {&g->slab, &g->cpack};
+    size_t* have[2] = {&g->slab_doubles, &g->cpack_doubles};
+    for (int i = 0; i < 2; ++i) {
+        if (*buf[i] && want[i] <= *have[i]) continue;
+        double* grown = nullptr;
+        RBL_TRY(g->mem.alloc(&grown, want[i]));
+        if (*buf[i]) {
+            RBL_HIP(hipStreamSynchronize(g->stream));
+            g->mem.release(*buf[i]);
+        }
+        *buf[i] = grown;
+        *have[i] = want[i] > 0 ? want[i] : 1;
+    }
+    return RBL_OK;
+}
+
+int rbl_group_create(rbl_solver* const* members, int k, rbl_group** out) { return rbl_group_create_opts(members, k, 0, out); }
+
+int rbl_group_create_opts(rbl_solver* const* members, int k, int flags, rbl_group** out) {
     if (!out) {
         rbl_set_error("group_create: out is NULL");
         return RBL_ERR_INVALID;
     }
     *out = nullptr;
+    if (flags & ~RBL_GROUP_SHARE_SPARSE) {
+        rbl_set_error("group_create: unknown flag bits 0x%x (RBL_GROUP_SHARE_SPARSE is the only flag)", flags & ~RBL_GROUP_SHARE_SPARSE);
+        return RBL_ERR_INVALID;
+    }
     if (!members || k < 1 || k > 64) {
         rbl_set_error("group_create: 1..64 members (got %d)", k);
         return RBL_ERR_INVALID;
@@ -57,11 +84,17 @@ int rbl_group_create(rbl_solver* const* members, int k, rbl_group** out) {
     g->shared_passes = h0->n > 0 && sweep_multi_supported(h0->storage, h0->ld);
     g->kpp = g->shared_passes ? sweep_multi_k(h0->storage, h0->ld) : 1;
     if (g->shared_passes) {
-        const int rc = g->mem.alloc(&g->slab, sweep_multi_slab_doubles(h0->ld, h0->num_cu));
+        g->slab_doubles = sweep_multi_slab_doubles(h0->ld, h0->num_cu);
+        const int rc = g->mem.alloc(&g->slab, g->slab_doubles);
         if (rc != RBL_OK) {
             (void)hipStreamDestroy(g->stream);
             return rc;
         }
+    } else if ((flags & RBL_GROUP_SHARE_SPARSE) && h0->storage == RBL_STORE_CSR && h0->n > 0 && ((const CsrStore*)h0->D)->colptr) {
+        // the opt-in: spmv.hip's multi-column passes, RBL_MULTI_KMAX members per read of the entries (on dense storage the
+        // flag changes nothing: sweep_multi_supported alone decides there).  The buffers come with the first shared pass
+        g->shared_passes = g->sparse = true;
+        g->kpp = RBL_MULTI_KMAX;
     }
     rbl_stats zero;
     std::memset(&zero, 0, sizeof(zero));
@@ -99,6 +132,8 @@ int rbl_group_destroy(rbl_group* g) {
         (void)hipStreamSynchronize(g->stream);
         (void)hipStreamDestroy(g->stream);
     }
+    for (hipEvent_t e : g->pev)
+        if (e) (void)hipEventDestroy(e);
     delete g;   // g->mem frees the slab
     return RBL_OK;
 }
@@ -130,6 +165,8 @@ int rbl_group_step(rbl_group* g, int want_objective, rbl_stats* out) {
             h->zb.q_done = h->zb.used;     // an unsettled z-step's q is redone with it, by the member alone (zb_resolve)
             h->s32.q_done = h->s32.used;
         }
+        const bool timed = g->profile && !idx.empty();
+        if (timed) RBL_HIP(hipEventRecord(g->pev[0], s));
         for (size_t b = 0; b < idx.size(); b += (size_t)g->kpp) {
             const int kk = (int)std::min(idx.size() - b, (size_t)g->kpp);
             const double* c[RBL_MULTI_KMAX];
@@ -139,9 +176,18 @@ int rbl_group_step(rbl_group* g, int want_objective, rbl_stats* out) {
                 q[j] = g->m[idx[b + j]]->q;
             }
             rbl_solver* h0 = g->m[idx[b]];
-            RBL_TRY(launch_sweep_q_multi(h0->storage, h0->D, h0->n, h0->ld, kk, c, g->slab, q, h0->num_cu, s));
+            if (g->sparse) {
+                const CsrStore* st = (const CsrStore*)h0->D;
+                RBL_TRY(group_sparse_room(g, st));
+                RBL_TRY(launch_csr_gemvt_multi(st, h0->n, h0->ld, kk, c, g->cpack, g->cpack_doubles, g->slab, g->slab_doubles, q,
+                                               h0->num_cu, s, timed && b == 0 && kk > 1 ? g->pev[2] : nullptr));
+                if (b == 0) g->pack_timed = timed && kk > 1;
+            } else {
+                RBL_TRY(launch_sweep_q_multi(h0->storage, h0->D, h0->n, h0->ld, kk, c, g->slab, q, h0->num_cu, s));
+            }
             g->shared_q += 1;
         }
+        if (timed) RBL_HIP(hipEventRecord(g->pev[1], s));
         for (int i : idx) {
             rbl_solver* h = g->m[i];
             h->pending_mask = 1;
@@ -160,7 +206,29 @@ int rbl_group_step(rbl_group* g, int want_objective, rbl_stats* out) {
         RBL_TRY(rbl_phase_w(g->m[i]));
     }
     // E: v_k = D w_k, lambda_k += rho_k (z_k - v_k), the primal residuals - D read once per kpp members
-    if (g->shared_passes) {
+    if (g->sparse) {
+        // the sparse pass carries v alone: every member's dual update is rbl_phase_dual's unfused one behind it
+        const bool timed = g->profile && !idx.empty();
+        if (timed) RBL_HIP(hipEventRecord(g->pev[3], s));
+        for (size_t b = 0; b < idx.size(); b += (size_t)g->kpp) {
+            const int kk = (int)std::min(idx.size() - b, (size_t)g->kpp);
+            const double* w[RBL_MULTI_KMAX];
+            double* v[RBL_MULTI_KMAX];
+            for (int j = 0; j < kk; ++j) {
+                w[j] = g->m[idx[b + j]]->w;
+                v[j] = g->m[idx[b + j]]->v;
+            }
+            rbl_solver* h0 = g->m[idx[b]];
+            RBL_TRY(launch_csr_gemv_multi((const CsrStore*)h0->D, h0->n, kk, w, v, h0->num_cu, s));
+            g->shared_v += 1;
+        }
+        if (timed) RBL_HIP(hipEventRecord(g->pev[4], s));
+        for (int i : idx) {
+            rbl_solver* h = g->m[i];
+            h->fused_ran = h->fused_v_ran = false;
+            RBL_TRY(dual_after_v(h, want_objective));
+        }
+    } else if (g->shared_passes) {
         for (size_t b = 0; b < idx.size(); b += (size_t)g->kpp) {
             const int kk = (int)std::min(idx.size() - b, (size_t)g->kpp);
             const double *w[RBL_MULTI_KMAX], *z[RBL_MULTI_KMAX];
@@ -215,6 +283,17 @@ int rbl_group_step(rbl_group* g, int want_objective, rbl_stats* out) {
         if (g->last[i].converged) g->live[i] = 0;   // frozen where its own rbl_solve would have stopped
     }
     g_host_syncs = 0;
+    if (g->profile && g->sparse && !idx.empty()) {   // the statistics are in: the events before them have completed
+        float q = 0.f, v = 0.f, pk = 0.f;
+        if (hipEventElapsedTime(&q, g->pev[0], g->pev[1]) == hipSuccess && hipEventElapsedTime(&v, g->pev[3], g->pev[4]) == hipSuccess &&
+            (!g->pack_timed || hipEventElapsedTime(&pk, g->pev[0], g->pev[2]) == hipSuccess)) {
+            g->pass_ms[0] += v;
+            g->pass_ms[1] += q;
+            g->pass_ms[2] += pk;
+            g->pass_steps += 1;
+        }
+        (void)hipGetLastError();
+    }
     if (out)
         for (int i = 0; i < K; ++i) out[i] = g->last[i];
     return RBL_OK;
@@ -252,6 +331,31 @@ int rbl_group_solve(rbl_group* g, int max_iter, int want_objective, rbl_stats* l
         if (iters) iters[i] = done[i];
         if (last) last[i] = g->last[i];
     }
+    return RBL_OK;
+}
+
+int rbl_group_profile(rbl_group* g, int on) {
+    if (!g) {
+        rbl_set_error("group handle is NULL");
+        return RBL_ERR_INVALID;
+    }
+    RBL_HIP(hipSetDevice(g->device));
+    if (on)
+        for (hipEvent_t& e : g->pev)
+            if (!e) RBL_HIP(hipEventCreate(&e));
+    g->profile = on != 0;
+    g->pass_ms[0] = g->pass_ms[1] = g->pass_ms[2] = 0.0;
+    g->pass_steps = 0;
+    return RBL_OK;
+}
+
+int rbl_group_pass_times(rbl_group* g, double* ms3, int64_t* steps) {
+    if (!g || !ms3 || !steps) {
+        rbl_set_error("group_pass_times: group, ms3 and steps must not be NULL");
+        return RBL_ERR_INVALID;
+    }
+    for (int i = 0; i < 3; ++i) ms3[i] = g->pass_ms[i];
+    *steps = g->pass_steps;
     return RBL_OK;
 }
 

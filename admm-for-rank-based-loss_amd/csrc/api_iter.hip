@@ -312,6 +312,33 @@ static inline double* q_zz(rbl_solver* h) { return h->q + 2 * h->ld; }     // ||
 // kernel events in this iteration?  (every profile_every-th one: an event record costs ~5 us of stream time)
 static inline bool prof_now(const rbl_solver* h) { return h->profile && (h->iter % h->profile_every) == 0; }
 
+// what every form of the dual update ends with: the logged loss sum where k_dual's is not the handle's own, the flags of
+// the exchange buffer, the rank-weighted risk
+static int dual_epilogue(rbl_solver* h, int want_objective) {
+    // own labels: k_dual summed the losses at v as the pass left it - the handle's own are at r * v; row weights: k_dual
+    // sums unweighted losses (the single-sweep pass' own loss sum took the weights already)
+    if ((h->rs || (h->cw && !h->fused_ran)) && want_objective && !h->sorted_path)
+        RBL_TRY(launch_loss_sum(h->cfg.loss, h->n, h->v, 1.0, h->partials, h->red + 1, h->stream, h->rs, h->cw));
+    h->pending_mask = 2 | (h->fused_ran ? 1 : 0);
+    h->want_obj = want_objective;
+    h->obj_is_risk = false;
+    if (want_objective && h->sorted_path && h->nt == h->n) {
+        RBL_TRY(risk_from_v(h, h->v, h->red + 1));
+        h->obj_is_risk = true;
+    }
+    return RBL_OK;
+}
+
+// The unfused dual update behind a plain v = D w that is already in the stream - rbl_phase_dual's own launch_gemv, or a
+// group's shared sparse pass (api_group.hip): lambda += rho (z - v) with the residual, then the epilogue.  The caller
+// has cleared fused_ran / fused_v_ran.
+int dual_after_v(rbl_solver* h, int want_objective) {
+    h->v_valid = true;
+    if (h->phase_timing) RBL_HIP(hipEventRecord(h->ev[4], h->stream));
+    RBL_TRY(launch_dual(h->cfg.loss, h->n, h->step_rho, h->z, h->v, h->lam, h->partials, h->red, h->stream));
+    return dual_epilogue(h, want_objective);
+}
+
 extern "C" {
 
 int rbl_phase_m(rbl_solver* h) {
@@ -588,22 +615,9 @@ int rbl_phase_dual(rbl_solver* h, int want_objective) {
             RBL_HIP(hipEventRecord(h->kev[1], h->stream));
             h->kev_pending[0] = true;
         }
-        h->v_valid = true;
-        if (h->phase_timing) RBL_HIP(hipEventRecord(h->ev[4], h->stream));
-        RBL_TRY(launch_dual(h->cfg.loss, h->n, h->step_rho, h->z, h->v, h->lam, h->partials, h->red, h->stream));
+        return dual_after_v(h, want_objective);
     }
-    // own labels: k_dual summed the losses at v as the pass left it - the handle's own are at r * v; row weights: k_dual
-    // sums unweighted losses (the single-sweep pass' own loss sum took the weights already)
-    if ((h->rs || (h->cw && !h->fused_ran)) && want_objective && !h->sorted_path)
-        RBL_TRY(launch_loss_sum(h->cfg.loss, h->n, h->v, 1.0, h->partials, h->red + 1, h->stream, h->rs, h->cw));
-    h->pending_mask = 2 | (h->fused_ran ? 1 : 0);
-    h->want_obj = want_objective;
-    h->obj_is_risk = false;
-    if (want_objective && h->sorted_path && h->nt == h->n) {
-        RBL_TRY(risk_from_v(h, h->v, h->red + 1));
-        h->obj_is_risk = true;
-    }
-    return RBL_OK;
+    return dual_epilogue(h, want_objective);
 }
 
 // One thread gathers the iteration's scalars into the pinned host block: the host then needs a

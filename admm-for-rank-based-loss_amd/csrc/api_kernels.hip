@@ -830,6 +830,73 @@ int rbl_k_csr_gemvt(int64_t n, int64_t d, const int64_t* indptr, const int32_t* 
     return RBL_OK;
 }
 
+// the checks of the two multi-column entries that come before any upload
+static int csr_multi_begin(Scratch& sc, const char* who, int k, const void* in, const void* out, int num_cu) {
+    if (k < 1 || k > RBL_MULTI_KMAX || !in || !out) {
+        rbl_set_error("%s: 1..%d columns (got %d), input and output not NULL", who, RBL_MULTI_KMAX, k);
+        return RBL_ERR_INVALID;
+    }
+    int cus = 0;
+    RBL_TRY(scratch_begin(sc, &cus));
+    if (num_cu < 1 || num_cu > cus) {
+        rbl_set_error("%s: num_cu = %d outside 1..%d (the device's compute units)", who, num_cu, cus);
+        return RBL_ERR_INVALID;
+    }
+    return RBL_OK;
+}
+
+int rbl_k_csr_gemv_multi(int64_t n, int64_t d, const int64_t* indptr, const int32_t* indices, const double* values, int k,
+                         const double* W, int num_cu, double* V, int* lanes_out) {
+    const char* who = "rbl_k_csr_gemv_multi";
+    Scratch sc;
+    RBL_TRY(csr_multi_begin(sc, who, k, W, V, num_cu));
+    CsrStore st;
+    int64_t ld = 0;
+    RBL_TRY(upload_csr(sc, who, n, d, indptr, indices, values, false, num_cu, &st, &ld));
+    double *dw = nullptr, *dv = nullptr;
+    RBL_TRY(cols_upload(sc, &dw, W, k, d, ld));
+    RBL_TRY(rows_alloc(sc, &dv, n, k, nullptr, 0));
+    const double* w[RBL_MULTI_KMAX];
+    double* v[RBL_MULTI_KMAX];
+    for (int j = 0; j < k; ++j) {
+        w[j] = dw + (size_t)j * ld;
+        v[j] = dv + (size_t)j * (n + SWEEP_GUARD);
+    }
+    RBL_TRY(launch_csr_gemv_multi(&st, n, k, w, v, num_cu, sc.s));
+    RBL_TRY(rows_fetch(sc, who, "v", dv, n, k, V));
+    if (lanes_out) *lanes_out = st.lanes;
+    return RBL_OK;
+}
+
+int rbl_k_csr_gemvt_multi(int64_t n, int64_t d, const int64_t* indptr, const int32_t* indices, const double* values, int k,
+                          const double* C, int num_cu, double* Q, int64_t* nseg_out) {
+    const char* who = "rbl_k_csr_gemvt_multi";
+    Scratch sc;
+    RBL_TRY(csr_multi_begin(sc, who, k, C, Q, num_cu));
+    CsrStore st;
+    int64_t ld = 0;
+    RBL_TRY(upload_csr(sc, who, n, d, indptr, indices, values, true, num_cu, &st, &ld));
+    const size_t ks = (size_t)csr_multi_stride(k), part_doubles = (size_t)st.nseg * ks, cp_doubles = (size_t)n * ks;
+    double *dc = nullptr, *cp = nullptr, *part = nullptr, *dq = nullptr;
+    RBL_TRY(sc.upload(&dc, C, (size_t)n * k));
+    RBL_TRY(sc.mem.alloc(&cp, cp_doubles));
+    RBL_TRY(sc.mem.alloc(&part, part_doubles));
+    RBL_TRY(sc.mem.alloc(&dq, (size_t)ld * k));
+    RBL_HIP(hipMemsetAsync(dq, 0xff, sizeof(double) * ld * k, sc.s));   // (NaN: every entry, the pad included, must be written)
+    RBL_HIP(hipMemsetAsync(part, 0xff, sizeof(double) * (part_doubles > 0 ? part_doubles : 1), sc.s));
+    const double* c[RBL_MULTI_KMAX];
+    double* q[RBL_MULTI_KMAX];
+    for (int j = 0; j < k; ++j) {
+        c[j] = dc + (size_t)j * n;
+        q[j] = dq + (size_t)j * ld;
+    }
+    RBL_TRY(launch_csr_gemvt_multi(&st, n, ld, k, c, cp, cp_doubles, part, part_doubles, q, num_cu, sc.s));
+    RBL_HIP(hipMemcpyAsync(Q, dq, sizeof(double) * ld * k, hipMemcpyDeviceToHost, sc.s));
+    RBL_HIP(hipStreamSynchronize(sc.s));
+    if (nseg_out) *nseg_out = st.nseg;
+    return RBL_OK;
+}
+
 int rbl_k_csr_gram(int64_t n, int64_t d, const int64_t* indptr, const int32_t* indices, const double* values, double* G) {
     Scratch sc;
     int num_cu = 256;

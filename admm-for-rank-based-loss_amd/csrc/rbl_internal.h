@@ -549,6 +549,17 @@ int launch_csr_gemv(const CsrStore* st, int64_t n, const double* w, double* v, i
 // part: the segments' partial sums, part_doubles >= st->nseg of them (fewer: RBL_ERR_STATE before anything is launched)
 int launch_csr_gemvt(const CsrStore* st, int64_t ld, const double* c, double* part, size_t part_doubles, double* q, int num_cu,
                      hipStream_t s, hipEvent_t main_done);
+// The two passes for k problems (1 <= k <= RBL_MULTI_KMAX) per read of the entries; arrays of k host-side pointers.  Column
+// j has the bits of the single-column launcher on w[j] / c[j] alone (k = 1 is that launcher); k = 3 runs three chains, on
+// the q side over packed rows of four.  v_j = D w_j:
+int launch_csr_gemv_multi(const CsrStore* st, int64_t n, int k, const double* const* w, double* const* v, int num_cu, hipStream_t s);
+// q_j = D^T c_j (ld entries each).  Cp: the c_j interleaved row by row, written here (k_pack_cols) - csr_multi_stride(k)
+// doubles per row, cp_doubles of room; part: csr_multi_stride(k) partial sums per segment, part_doubles of room.  Too little
+// of either is RBL_ERR_STATE before anything is launched.  pack_done (optional) is recorded behind the interleaving.
+int csr_multi_stride(int k);   // 2 for k <= 2, else 4
+int launch_csr_gemvt_multi(const CsrStore* st, int64_t n, int64_t ld, int k, const double* const* c, double* Cp, size_t cp_doubles,
+                           double* part, size_t part_doubles, double* const* q, int num_cu, hipStream_t s,
+                           hipEvent_t pack_done = nullptr);
 // rows [row0, row0 + rows) as dense fp64 rows of stride ldo (implicit entries +0.0)
 int launch_csr_dense(const CsrStore* st, int64_t row0, int64_t rows, int64_t ldo, double* out, int num_cu, hipStream_t s);
 // G = D^T D by one of two routes (route: 0 = the rule csr_gram_route of csr_gram_plan.h on st->pair_products, 2, 3);

@@ -1,6 +1,6 @@
 // spmv.hip - RBL_STORE_CSR: D = -y X kept as its non-zero entries.  The forming kernel of rbl_set_data_csr (checks and
 // stores the entries of a chunk), the column-form build, v = D w on the row form, q = D^T c on the column form without
-// float atomics, the dense expansion of row chunks (rbl_get_D, the Gram matrix) and G = D^T D - through the fp64 MFMA
+// float atomics, both for up to four problems per read of the entries (groups), the dense expansion of row chunks (rbl_get_D, the Gram matrix) and G = D^T D - through the fp64 MFMA
 // kernel of gram.hip, or from the entries (spgram.hip) where the rule of csr_gram_plan.h says so.  Every sum has a fixed order that depends on the data and on (n, ld) alone ("Sparse
 // storage").
 #include "rbl_internal.h"
@@ -107,6 +107,125 @@ __global__ __launch_bounds__(SP_THREADS) void k_csc_columns(const int64_t* __res
 #pragma unroll
     for (int off = SP_QL / 2; off >= 1; off >>= 1) acc += __shfl_xor(acc, off, SP_QL);
     if (l == 0) q[j] = acc;
+}
+
+// ---- the two passes for up to RBL_MULTI_KMAX problems per read of the entries (groups, rbl_decide_multi).  Column k of
+// a launch runs the chain of the single-column kernel above on its own accumulator - the same entries in the same order,
+// the same butterfly - so it has that kernel's bits; only the loads of (col, val) / (row, cval) are shared.
+template <int KC>
+struct SpIn {
+    const double* p[KC];
+};
+template <int KC>
+struct SpOut {
+    double* p[KC];
+};
+
+// v_k = D w_k, k < KC: the w_k are gathered through their own pointers (ld doubles each: they stay in L2)
+template <int L, int KC>
+__global__ __launch_bounds__(SP_THREADS) void k_csr_gemv_multi(const int64_t* __restrict__ indptr, const int* __restrict__ col,
+                                                               const double* __restrict__ val, SpIn<KC> w, SpOut<KC> v, long long n) {
+    const int l = (int)threadIdx.x & (L - 1);
+    constexpr int GPB = SP_THREADS / L;
+    for (long long r = (long long)blockIdx.x * GPB + ((int)threadIdx.x / L); r < n; r += (long long)gridDim.x * GPB) {
+        const long long a = indptr[r], b = indptr[r + 1];
+        double acc[KC];
+#pragma unroll
+        for (int k = 0; k < KC; ++k) acc[k] = 0.0;
+        for (long long e = a + l; e < b; e += L) {
+            const double x = val[e];
+            const int j = col[e];
+#pragma unroll
+            for (int k = 0; k < KC; ++k) acc[k] = fma(x, w.p[k][j], acc[k]);
+        }
+#pragma unroll
+        for (int k = 0; k < KC; ++k) {
+#pragma unroll
+            for (int off = L / 2; off >= 1; off >>= 1) acc[k] += __shfl_xor(acc[k], off, L);
+        }
+        if (l == 0) {
+#pragma unroll
+            for (int k = 0; k < KC; ++k) v.p[k][r] = acc[k];
+        }
+    }
+}
+
+// Cp[i * KS + k] = c_k[i], k < KC: the members' c interleaved row by row with stride KS (2 or 4), so that the line the
+// q pass gathers for an entry carries every column.  KC = 3 runs at KS = 4: the fourth slot is written +0.0 (whole
+// 32-byte rows) and never enters a sum.
+template <int KS, int KC>
+__global__ void k_pack_cols(SpIn<KC> c, double* __restrict__ Cp, long long n) {
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
+        double x[KS];
+#pragma unroll
+        for (int k = 0; k < KS; ++k) x[k] = k < KC ? c.p[k < KC ? k : 0][i] : 0.0;
+        double2* out = reinterpret_cast<double2*>(Cp + i * KS);
+#pragma unroll
+        for (int k = 0; k < KS; k += 2) out[k / 2] = make_double2(x[k], x[k + 1]);
+    }
+}
+
+// q_k = D^T c_k, first kernel: k_csc_segments with KC chains per lane; the KC values of a row come from one (KS = 2) or
+// two (KS = 4) aligned 16-byte loads of the packed c.  part[s * KS + k]: segment s of member k.
+template <int KS, int KC>
+__global__ __launch_bounds__(SP_THREADS) void k_csc_segments_multi(const int64_t* __restrict__ colptr, const int64_t* __restrict__ segptr,
+                                                                   const int* __restrict__ row, const double* __restrict__ cval,
+                                                                   const double* __restrict__ Cp, double* __restrict__ part,
+                                                                   long long ld, long long nseg, int T) {
+    const int lane = (int)threadIdx.x & (RBL_WAVE - 1);
+    for (long long s = (long long)blockIdx.x * SP_WPB + ((int)threadIdx.x / RBL_WAVE); s < nseg; s += (long long)gridDim.x * SP_WPB) {
+        const CscSegment g = csc_segment(colptr, segptr, ld, s, T);
+        double acc[KC];
+#pragma unroll
+        for (int k = 0; k < KC; ++k) acc[k] = 0.0;
+        for (long long e = g.begin + lane; e < g.end; e += RBL_WAVE) {
+            const double x = cval[e];
+            const double2* cr = reinterpret_cast<const double2*>(Cp + (long long)row[e] * KS);
+            double c[KS];
+#pragma unroll
+            for (int k = 0; k < KS; k += 2) {
+                const double2 t = cr[k / 2];
+                c[k] = t.x;
+                c[k + 1] = t.y;
+            }
+#pragma unroll
+            for (int k = 0; k < KC; ++k) acc[k] = fma(x, c[k], acc[k]);
+        }
+#pragma unroll
+        for (int k = 0; k < KC; ++k) {
+#pragma unroll
+            for (int off = RBL_WAVE / 2; off >= 1; off >>= 1) acc[k] += __shfl_xor(acc[k], off, RBL_WAVE);
+        }
+        if (lane == 0) {
+#pragma unroll
+            for (int k = 0; k < KC; ++k) part[s * KS + k] = acc[k];
+        }
+    }
+}
+
+// second kernel: k_csc_columns per member - q_k[j] for every j < ld, the padding included
+template <int KS, int KC>
+__global__ __launch_bounds__(SP_THREADS) void k_csc_columns_multi(const int64_t* __restrict__ segptr, const double* __restrict__ part,
+                                                                  SpOut<KC> q, long long ld) {
+    const int l = (int)threadIdx.x & (SP_QL - 1);
+    const long long j = ((long long)blockIdx.x * SP_THREADS + (int)threadIdx.x) / SP_QL;
+    if (j >= ld) return;   // (whole groups leave together)
+    double acc[KC];
+#pragma unroll
+    for (int k = 0; k < KC; ++k) acc[k] = 0.0;
+    for (long long s = segptr[j] + l; s < segptr[j + 1]; s += SP_QL) {
+#pragma unroll
+        for (int k = 0; k < KC; ++k) acc[k] += part[s * KS + k];
+    }
+#pragma unroll
+    for (int k = 0; k < KC; ++k) {
+#pragma unroll
+        for (int off = SP_QL / 2; off >= 1; off >>= 1) acc[k] += __shfl_xor(acc[k], off, SP_QL);
+    }
+    if (l == 0) {
+#pragma unroll
+        for (int k = 0; k < KC; ++k) q.p[k][j] = acc[k];
+    }
 }
 
 // ---- column form: a stable sort of (column, entry id) puts every column's entries in ascending row order
@@ -337,6 +456,111 @@ int launch_csr_gemvt(const CsrStore* st, int64_t ld, const double* c, double* pa
                        (const int64_t*)st->segptr, (const double*)part, q, (long long)ld);
     RBL_HIP(hipGetLastError());
     return RBL_OK;
+}
+
+namespace {
+
+template <int KC>
+int csr_gemv_multi_K(const CsrStore* st, int64_t n, const double* const* w, double* const* v, int num_cu, hipStream_t s) {
+    SpIn<KC> wi;
+    SpOut<KC> vo;
+    for (int k = 0; k < KC; ++k) {
+        wi.p[k] = w[k];
+        vo.p[k] = v[k];
+    }
+#define RBL_CSR_GEMV_MULTI(L_)                                                                                           \
+    hipLaunchKernelGGL((k_csr_gemv_multi<L_, KC>), dim3(sp_grid(n, SP_THREADS / L_, num_cu)), dim3(SP_THREADS), 0, s,        \
+                       (const int64_t*)st->indptr, (const int*)st->col, (const double*)st->val, wi, vo, (long long)n)
+    switch (st->lanes) {
+        case 4: RBL_CSR_GEMV_MULTI(4); break;
+        case 8: RBL_CSR_GEMV_MULTI(8); break;
+        case 16: RBL_CSR_GEMV_MULTI(16); break;
+        case 32: RBL_CSR_GEMV_MULTI(32); break;
+        case 64: RBL_CSR_GEMV_MULTI(64); break;
+        default: rbl_set_error("csr gemv multi: the data are not complete (no upload, or the last one failed)"); return RBL_ERR_STATE;
+    }
+#undef RBL_CSR_GEMV_MULTI
+    RBL_HIP(hipGetLastError());
+    return RBL_OK;
+}
+
+template <int KS, int KC>
+int csr_gemvt_multi_K(const CsrStore* st, int64_t n, int64_t ld, const double* const* c, double* Cp, double* part, double* const* q,
+                      int num_cu, hipStream_t s, hipEvent_t pack_done) {
+    SpIn<KC> ci;
+    SpOut<KC> qo;
+    for (int k = 0; k < KC; ++k) {
+        ci.p[k] = c[k];
+        qo.p[k] = q[k];
+    }
+    hipLaunchKernelGGL((k_pack_cols<KS, KC>), dim3(sp_grid(n, 256, num_cu)), dim3(256), 0, s, ci, Cp, (long long)n);
+    if (pack_done) RBL_HIP(hipEventRecord(pack_done, s));   // the interleaving alone (tools/csr_group_bench.py)
+    if (st->nseg > 0)
+        hipLaunchKernelGGL((k_csc_segments_multi<KS, KC>), dim3(sp_grid(st->nseg, SP_WPB, num_cu)), dim3(SP_THREADS), 0, s,
+                           (const int64_t*)st->colptr, (const int64_t*)st->segptr, (const int*)st->row, (const double*)st->cval,
+                           (const double*)Cp, part, (long long)ld, (long long)st->nseg, st->seg);
+    hipLaunchKernelGGL((k_csc_columns_multi<KS, KC>), dim3((unsigned)((ld * SP_QL + SP_THREADS - 1) / SP_THREADS)), dim3(SP_THREADS), 0, s,
+                       (const int64_t*)st->segptr, (const double*)part, qo, (long long)ld);
+    RBL_HIP(hipGetLastError());
+    return RBL_OK;
+}
+
+}  // namespace
+
+int csr_multi_stride(int k) { return k <= 2 ? 2 : 4; }
+
+int launch_csr_gemv_multi(const CsrStore* st, int64_t n, int k, const double* const* w, double* const* v, int num_cu, hipStream_t s) {
+    if (k < 1 || k > RBL_MULTI_KMAX) {
+        rbl_set_error("csr gemv multi: 1..%d columns per launch (got %d)", RBL_MULTI_KMAX, k);
+        return RBL_ERR_INVALID;
+    }
+    if (n <= 0) return RBL_OK;
+    if (!st->lanes) {
+        rbl_set_error("csr gemv multi: the data are not complete (no upload, or the last one failed)");
+        return RBL_ERR_STATE;
+    }
+    switch (k) {
+        case 1: return launch_csr_gemv(st, n, w[0], v[0], num_cu, s);
+        case 2: return csr_gemv_multi_K<2>(st, n, w, v, num_cu, s);
+        case 3: return csr_gemv_multi_K<3>(st, n, w, v, num_cu, s);
+        default: return csr_gemv_multi_K<4>(st, n, w, v, num_cu, s);
+    }
+}
+
+int launch_csr_gemvt_multi(const CsrStore* st, int64_t n, int64_t ld, int k, const double* const* c, double* Cp, size_t cp_doubles,
+                           double* part, size_t part_doubles, double* const* q, int num_cu, hipStream_t s, hipEvent_t pack_done) {
+    if (k < 1 || k > RBL_MULTI_KMAX) {
+        rbl_set_error("csr gemvt multi: 1..%d columns per launch (got %d)", RBL_MULTI_KMAX, k);
+        return RBL_ERR_INVALID;
+    }
+    if (!st->colptr || !st->segptr) {
+        rbl_set_error("csr gemvt multi: the handle holds the row form only (objective-only)");
+        return RBL_ERR_STATE;
+    }
+    if (!st->lanes) {
+        rbl_set_error("csr gemvt multi: the data are not complete (the last upload failed)");
+        return RBL_ERR_STATE;
+    }
+    if (k == 1) {
+        if (n <= 0) return RBL_OK;
+        return launch_csr_gemvt(st, ld, c[0], part, part_doubles, q[0], num_cu, s, nullptr);
+    }
+    const size_t ks = (size_t)csr_multi_stride(k);
+    if ((size_t)st->nseg * ks > part_doubles) {
+        rbl_set_error("csr gemvt multi: the slab holds %zu partial sums, the data have %lld segments of %zu columns", part_doubles,
+                      (long long)st->nseg, ks);
+        return RBL_ERR_STATE;
+    }
+    if (n > 0 && (size_t)(n > st->n ? n : st->n) * ks > cp_doubles) {   // (the entries' row ids index it)
+        rbl_set_error("csr gemvt multi: the packed c holds %zu doubles, %lld rows of %zu columns are needed", cp_doubles, (long long)n, ks);
+        return RBL_ERR_STATE;
+    }
+    if (n <= 0) return RBL_OK;
+    switch (k) {
+        case 2: return csr_gemvt_multi_K<2, 2>(st, n, ld, c, Cp, part, q, num_cu, s, pack_done);
+        case 3: return csr_gemvt_multi_K<4, 3>(st, n, ld, c, Cp, part, q, num_cu, s, pack_done);
+        default: return csr_gemvt_multi_K<4, 4>(st, n, ld, c, Cp, part, q, num_cu, s, pack_done);
+    }
 }
 
 int launch_csr_dense(const CsrStore* st, int64_t row0, int64_t rows, int64_t ldo, double* out, int num_cu, hipStream_t s) {

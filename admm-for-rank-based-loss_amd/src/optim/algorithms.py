@@ -370,10 +370,13 @@ class ADMMgroup:
     on the shared X - one-vs-rest, multi-label - default: the group's ``y``).  ``solvers`` are ordinary ADMMmethod /
     smoothADMMmethod objects; start_store / main_loop / final_res mirror the single-solver calls and return lists in
     the order of ``problems``.  ``standardize=True`` (in every problem, like ``fit_intercept``: one data matrix) standardises
-    the columns of X on the device.  X is taken as it is (_solver.as_source)."""
+    the columns of X on the device.  X is taken as it is (_solver.as_source).  ``share_sparse=True`` (in every problem, like
+    ``standardize``: one set of passes; storage "csr"): the members share multi-column sparse passes, four per read of the
+    entries, with bit-identical iterates (default off: every member runs its own sparse passes); it has no effect on dense
+    storage."""
 
     _KEYS = ("weight_function", "loss", "l2_reg", "l1_reg", "B", "args", "w0", "smooth", "t", "y", "l1_weights",
-             "l2_weights", "fit_intercept", "standardize", "sample_weight", "class_weight")
+             "l2_weights", "fit_intercept", "standardize", "sample_weight", "class_weight", "share_sparse")
 
     def __init__(self, X, y, problems, storage="f32", device=0, max_iter=200, tol=1e-4):
         if not isinstance(problems, (list, tuple)) or len(problems) == 0:
@@ -381,6 +384,12 @@ class ADMMgroup:
         if len(problems) > 64:
             raise ValueError("ADMMgroup: at most 64 problems in one group")
         self.problems = []
+        for k, pr in enumerate(problems):            # before anything can touch the device (a tensor X)
+            if isinstance(pr, dict) and "share_sparse" in pr:
+                try:
+                    _solver.check_share_sparse(pr["share_sparse"])
+                except ValueError as e:
+                    raise ValueError(f"problem {k}: {e}") from None
         X = _solver.as_source(X, device)             # once for all members: no copy, or one conversion
         for k, pr in enumerate(problems):            # every argument error before any device call
             if not isinstance(pr, dict):
@@ -402,6 +411,8 @@ class ADMMgroup:
                     raise ValueError("fit_intercept must be the same for every problem of a group (one data matrix)")
                 if bool(pr.get("standardize")) != bool(problems[0].get("standardize")):
                     raise ValueError("standardize must be the same for every problem of a group (one data matrix)")
+                if bool(pr.get("share_sparse")) != bool(problems[0].get("share_sparse")):
+                    raise ValueError("share_sparse must be the same for every problem of a group (one set of passes)")
                 _solver.resolve_penalty(X.shape[1], pr.get("l1_reg"), pr.get("l2_reg"), pr.get("l1_weights"),
                                         pr.get("l2_weights"), bool(pr.get("fit_intercept")))
                 if pr.get("B") is not None and pr["weight_function"] != "ehrm":
@@ -435,7 +446,7 @@ class ADMMgroup:
                                l2_weights=pr.get("l2_weights"), fit_intercept=bool(pr.get("fit_intercept")),
                                standardize=bool(pr.get("standardize")), **kw)
             self.solvers.append(s)
-        self._group = _solver.Group([s._s for s in self.solvers])
+        self._group = _solver.Group([s._s for s in self.solvers], share_sparse=bool(self.problems[0].get("share_sparse")))
         self.store = False
         self.last = [None] * len(self.solvers)
         self.iterations = [0] * len(self.solvers)
@@ -519,11 +530,13 @@ class OneVsRest:
     iteration reads D once for several classes in each of its two passes (ADMMgroup with per-member labels,
     include/rbl.h: rbl_set_labels).  The reference's ``n_class`` / multinomial loss has no z-step (its prox is missing),
     so this is the multi-class route of the ADMM.  ``predict`` takes the arg-max of x . w_k over the classes on the
-    GPU (rbl_decide_multi)."""
+    GPU (rbl_decide_multi).  ``share_sparse=True`` (storage "csr"): the classes share multi-column sparse
+    passes (ADMMgroup's ``share_sparse``); default off."""
 
     def __init__(self, X, labels, weight_function="erm", loss="binary_cross_entropy", l2_reg=None, l1_reg=None, B=None,
                  args=None, storage="f32", device=0, max_iter=200, tol=1e-4, l1_weights=None, l2_weights=None,
-                 fit_intercept=False, standardize=False, sample_weight=None, class_weight=None):
+                 fit_intercept=False, standardize=False, sample_weight=None, class_weight=None, share_sparse=False):
+        _solver.check_share_sparse(share_sparse)     # before anything touches the device
         # class_weight="balanced": every member gets the balanced weights of its OWN +-1 labels (one class against the
         # rest is imbalanced by construction); a common sample_weight multiplies into all of them
         Xm = _solver.as_source(X, device)
@@ -539,7 +552,8 @@ class OneVsRest:
         ys = [np.where(lab == c, 1.0, -1.0) for c in self.classes_]
         problems = [dict(weight_function=weight_function, loss=loss, l2_reg=l2_reg, l1_reg=l1_reg, B=B, args=args, y=yk,
                          l1_weights=l1_weights, l2_weights=l2_weights, fit_intercept=self.fit_intercept,
-                         standardize=bool(standardize), sample_weight=sample_weight, class_weight=class_weight)
+                         standardize=bool(standardize), sample_weight=sample_weight, class_weight=class_weight,
+                         share_sparse=share_sparse)
                     for yk in ys]
         self._storage, self._device = storage, device
         self.group = ADMMgroup(Xm, ys[0], problems, storage=storage, device=device, max_iter=max_iter, tol=tol)

@@ -8,7 +8,11 @@ test row is the arg-max of x . w_k, taken on the GPU.
 One CSV row per class (class, rows of the class, iterations, final train loss, final test loss, one-vs-rest test
 accuracy), then the multi-class test accuracy.
 
-    python examples/run_ovr.py [--rows 9000] [--cols 400] [--iters 200] [--out rows.csv]
+    python examples/run_ovr.py [--rows 9000] [--cols 400] [--iters 200] [--out rows.csv] [--sparse]
+
+``--sparse``: the same problem on a SciPy CSR matrix (70 % of the entries dropped) with ``storage="csr",
+share_sparse=True``: D stays sparse on the device and the three classes share its multi-column sparse passes - the entries
+are read once per pass for all three, with the iterates of three separate sparse solves bit for bit.
 """
 import argparse
 import csv
@@ -42,6 +46,7 @@ def main():
     ap.add_argument("--level", type=float, default=0.5, help="superquantile level")
     ap.add_argument("--seed", type=int, default=17)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--sparse", action="store_true", help='a SciPy CSR matrix with storage="csr", share_sparse=True')
     a = ap.parse_args()
 
     from admm_for_rank_based_loss_amd import OneVsRest
@@ -50,8 +55,14 @@ def main():
     ntr = int(0.6 * a.rows)
     X_train, l_train, X_test, l_test = X[:ntr], labels[:ntr], X[ntr:], labels[ntr:]
 
+    extra = {}
+    if a.sparse:
+        import scipy.sparse as sp
+        keep = np.random.default_rng(a.seed + 1).random(X.shape) < 0.3
+        X_train, X_test = sp.csr_matrix(X_train * keep[:ntr]), sp.csr_matrix(X_test * keep[ntr:])
+        extra = dict(storage="csr", share_sparse=True)
     ovr = OneVsRest(X_train, l_train, weight_function="superquantile", loss="binary_cross_entropy", l2_reg=0.01,
-                    args=[a.level], max_iter=a.iters)
+                    args=[a.level], max_iter=a.iters, **extra)
     ovr.group.start_store(X_test, [np.where(l_test == c, 1.0, -1.0) for c in ovr.classes_])
     W = ovr.main_loop(verbose=False)
     cnt = ovr.group.counters()

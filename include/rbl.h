@@ -336,6 +336,15 @@ int  rbl_finalize_smooth(rbl_solver* h);
  *  - the shared passes exist for 32 < packets per row <= 512 (128 < ld <= 2048 with fp32 storage, 64 < ld <= 1024 with
  *    fp64, 256 < ld <= 2048 with fp16: the Q pass' column sums bound the width in elements); outside that range a group runs each member's own passes (shared_v == shared_q == 0, counted in
  *    single_passes).  Column k of a shared pass is bit-identical to the member's own single-column pass.
+ *  - RBL_STORE_CSR: by default a group on sparse storage runs every member's own two passes (k_per_pass == 1).
+ *    rbl_group_create_opts with RBL_GROUP_SHARE_SPARSE opts into shared sparse passes: the entries of D are read once
+ *    for up to 4 members - V = D [w_1 .. w_4] with one FMA chain per member and entry, Q = D^T [c_1 .. c_4] on the
+ *    members' c interleaved row by row, so that the line gathered for an entry carries every member's value - and every
+ *    member's lambda update, residual and logged loss then run as on its own (rbl_phase_dual's unfused kernels).  Every
+ *    fp64 sum keeps the order of the single-column sparse pass, so a group with shared sparse passes reproduces the
+ *    standalone RBL_STORE_CSR iterates bit for bit, as the dense group does.  k_per_pass is then 4 at every width; the
+ *    packed c (4 n doubles) and the segments' partial sums (4 per segment) live in the group and follow a second upload.
+ *    On dense storage the flag has no effect: the width rule above alone decides there.
  *  - a member whose z-step was not certified redoes it and its own q with the single-column pass (counted in
  *    single_passes, as is the v = D w a member needs before its first z-step); the others are not disturbed.
  *  - a member that converges (its own tol) is frozen exactly where rbl_solve would have stopped and drops out of the
@@ -347,6 +356,9 @@ int  rbl_finalize_smooth(rbl_solver* h);
  * may be NULL; iters: iterations each member ran in this call. */
 typedef struct rbl_group rbl_group;
 int  rbl_group_create(rbl_solver* const* members, int k, rbl_group** out);
+/* rbl_group_create with flags (rbl_group_create is flags == 0); a bit that is not listed here is RBL_ERR_INVALID */
+#define RBL_GROUP_SHARE_SPARSE 1   /* RBL_STORE_CSR: shared multi-column sparse passes (above) */
+int  rbl_group_create_opts(rbl_solver* const* members, int k, int flags, rbl_group** out);
 int  rbl_group_destroy(rbl_group* g);
 int  rbl_group_step(rbl_group* g, int want_objective, rbl_stats* out);
 int  rbl_group_solve(rbl_group* g, int max_iter, int want_objective, rbl_stats* last,
@@ -355,10 +367,18 @@ int  rbl_group_solve(rbl_group* g, int max_iter, int want_objective, rbl_stats* 
 /* k_per_pass: members one shared launch carries (1: no shared passes at this width); shared_v / shared_q: shared
  * launches so far; single_passes[k]: n x d launches each member ran on its own since the group was created */
 int  rbl_group_counters(rbl_group* g, int* k_per_pass, int64_t* shared_v, int64_t* shared_q, int64_t* single_passes);
+/* Measuring aid (tools/csr_group_bench.py): with on != 0 a group with shared sparse passes puts HIP events around the
+ * shared launches of every step; on == 0 stops that; either call clears the sums.  rbl_group_pass_times: ms3 = the
+ * summed milliseconds of [the V batches, the Q batches (interleaving included), the first Q batch's interleaving] and
+ * the steps they were summed over. */
+int  rbl_group_profile(rbl_group* g, int on);
+int  rbl_group_pass_times(rbl_group* g, double* ms3, int64_t* steps);
 /* The decision of k one-vs-rest classifiers on the rows of `data` (typically an objective_only handle holding a test
  * matrix): cls[i] = argmax_j x_i . w_j, ties to the lowest j.  W: k x d host doubles (row j = w_j), cls: n host int32,
  * 1 <= k <= 64.  The scores come from the groups' multi-column V product (ceil(k / k_per_pass) passes over data's D,
- * the label sign in D = -y*X taken out), each pass followed by a row-wise comparison against the best score so far. */
+ * the label sign in D = -y*X taken out), each pass followed by a row-wise comparison against the best score so far.
+ * A handle with RBL_STORE_CSR takes the multi-column sparse pass, 4 columns per read of the entries: the scores have
+ * the bits of the single-column pass, so the classes are the same. */
 int  rbl_decide_multi(rbl_solver* data, int k, const double* W, int32_t* cls);
 /* rankbasedObjective.get_arrogate_loss(w) (objective.py:71-87); w: d host doubles */
 int  rbl_objective(rbl_solver* h, const double* w, int include_reg, double* out);
@@ -641,6 +661,15 @@ int  rbl_k_csr_gemv(int64_t n, int64_t d, const int64_t* indptr, const int32_t* 
                     const double* w, double* v);
 int  rbl_k_csr_gemvt(int64_t n, int64_t d, const int64_t* indptr, const int32_t* indices, const double* values,
                      const double* c, double* q);
+/* the multi-column sparse passes of the groups (RBL_GROUP_SHARE_SPARSE) through their launchers, on a grid sized for
+ * num_cu (1 .. the device's count, else RBL_ERR_INVALID); 1 <= k <= 4, k == 1 is the single-column pass.  W: k x d,
+ * V: k x n (row j = D w_j; from a buffer preset to NaN with a guard behind row n that the entry checks); C: k x n,
+ * Q: k x ld (row j = D^T c_j, the padding included; Q and the segments' partial sums are preset to 0xff).  lanes_out:
+ * the lane group of v = D w (4 .. 64); nseg_out: the segments of q = D^T c.  Either may be NULL. */
+int  rbl_k_csr_gemv_multi(int64_t n, int64_t d, const int64_t* indptr, const int32_t* indices, const double* values, int k,
+                          const double* W, int num_cu, double* V, int* lanes_out);
+int  rbl_k_csr_gemvt_multi(int64_t n, int64_t d, const int64_t* indptr, const int32_t* indices, const double* values, int k,
+                           const double* C, int num_cu, double* Q, int64_t* nseg_out);
 int  rbl_k_csr_gram(int64_t n, int64_t d, const int64_t* indptr, const int32_t* indices, const double* values, double* G);
 /* rbl_k_csr_gram with the route (0 = the rule's, 2, 3), the grid and the tile width (0 = the plan's) chosen by the
  * caller - launcher arguments like num_cu elsewhere, not switches; G_ld: all ld x ld entries, from a buffer the entry
