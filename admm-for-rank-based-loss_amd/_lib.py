@@ -255,6 +255,7 @@ SIGNATURES = {
                                   C.POINTER(C.c_int)]),
     "rbl_k_wstep_seq": (C.c_int, [C.c_int, C.c_int64, _P, C.c_int, _P, C.c_double, C.c_double, C.c_double, _P, _P, _P,
                                   C.c_double, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P]),
+    "rbl_k_eig": (C.c_int, [C.c_int64, _P, _P, _P, _P, _I64, C.POINTER(C.c_int)]),
     "rbl_k_weights": (C.c_int, [C.c_int, C.c_int64, _P, C.c_int, _P, _P]),
     "rbl_bl_create": (C.c_int, [C.c_int64, C.c_int64, _P, _P, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_int,
                                 C.POINTER(_P)]),
@@ -708,6 +709,22 @@ def k_wstep_seq(wstep, G, Q, rho, reg, w0=None, smooth_t=1.0, tol=1e-13, max_inn
     reports = [{name: (list(getattr(r, name)) if name == "fs" else int(getattr(r, name))) for name, _ in RblWstepReport._fields_}
                for r in rep]
     return dict(w=W, Gw=Gw, w_prev=Wp, reports=reports)
+
+
+def k_eig(G):
+    """The one-time Jacobi eigendecomposition of the eigendecomposition ridge on a prescribed G (include/rbl.h:
+    rbl_k_eig).  Returns dict(Vt (ld x ld, rows = eigenvectors), V (its transpose), lam (ld), ld, sweeps; 0 sweeps = not
+    converged: V and lam are then NaN)."""
+    G = f64(G)
+    d = G.shape[0]
+    if G.ndim != 2 or G.shape[1] != d:
+        raise ValueError(f"k_eig: G must be square, got shape {G.shape}")
+    n = (max(d, 1) + 3) // 4 * 4
+    Vt, V, lam = np.empty((n, n)), np.empty((n, n)), np.empty(n)
+    ld, sweeps = C.c_int64(0), C.c_int(0)
+    check(load().rbl_k_eig(d, ptr(G), ptr(Vt), ptr(V), ptr(lam), C.byref(ld), C.byref(sweeps)))
+    assert ld.value == n, (ld.value, n)
+    return dict(Vt=Vt, V=V, lam=lam, ld=int(ld.value), sweeps=int(sweeps.value))
 
 
 def k_weights(weight_function, n, args=None):

@@ -1126,7 +1126,7 @@ int rbl_gram_finish(rbl_solver* h) {
     h->L = 1.02 * lam;
     if (!(h->L > 0.0)) h->L = 1.0;
     // l2 w-step: RBL_RIDGE_EIG=1 replaces the warm-started CG by a one-time eigendecomposition of G (eig.hip).
-    // Opt-in: it makes an iteration 0.13 ms shorter at d = 1000 (14 CG iterations -> 5 small launches) but the
+    // Opt-in: it makes an iteration 0.13 ms shorter at d = 1000 (14 CG iterations -> 5 small launches when measured, 8 now) but the
     // Jacobi sweeps cost 0.8 s of setup there - 6000 iterations to break even, and a solve runs a few hundred
     h->ww.eig_ok = false;
     static const bool ridge_eig = [] {

@@ -1043,10 +1043,14 @@ int rbl_k_wstep_seq(int wstep, int64_t d, const double* G, int K, const double* 
                       "tol = %g, max_inner = %d, smooth_t = %g)", who, rho, reg, tol, max_inner, smooth_t);
         return RBL_ERR_INVALID;
     }
-    if ((route != 0 && route != 1) || launch_seq0 < 0 || launch_seq0 > 0xfffff ||
+    if (route < 0 || route > 2 || launch_seq0 < 0 || launch_seq0 > 0xfffff ||
         (flags & ~(RBL_KW_WANT_GW | RBL_KW_W_PREV | RBL_KW_RHO_DEV | RBL_KW_TWO_CALL)) != 0) {
-        rbl_set_error("%s: route is 0 or 1, 0 <= launch_seq0 <= 0xfffff, flags are RBL_KW_* (route = %d, launch_seq0 = %d, "
+        rbl_set_error("%s: route is 0, 1 or 2, 0 <= launch_seq0 <= 0xfffff, flags are RBL_KW_* (route = %d, launch_seq0 = %d, "
                       "flags = %d)", who, route, launch_seq0, flags);
+        return RBL_ERR_INVALID;
+    }
+    if (route == 2 && wstep != RBL_WSTEP_L2) {
+        rbl_set_error("%s: route 2 (the eigendecomposition ridge) goes with wstep 2, got wstep %d", who, wstep);
         return RBL_ERR_INVALID;
     }
     if (pen && wstep == RBL_WSTEP_SMOOTH_L1) {
@@ -1107,6 +1111,24 @@ int rbl_k_wstep_seq(int wstep, int64_t d, const double* G, int K, const double* 
     RBL_TRY(launch_power_iteration(dG, ld, ww.yk, ww.Gy, ww.scal, 100, &lam, sc.s));
     double L = 1.02 * lam;
     if (!(L > 0.0)) L = 1.0;
+    if (route == 2 && ld <= 2048) {   // the decomposition as rbl_gram_finish runs it
+        const size_t nn = (size_t)ld * (size_t)ld;
+        RBL_TRY(sc.mem.alloc(&ww.eig_Vt, nn));
+        RBL_TRY(sc.mem.alloc(&ww.eig_V, nn));
+        RBL_TRY(sc.mem.alloc(&ww.eig_lambda, (size_t)ld));
+        int rc = RBL_OK, sweeps = 0;
+        {
+            DevArena tmp;   // Jacobi scratch, freed after the stream wait
+            double* Bt = nullptr;
+            unsigned long long* off = nullptr;
+            RBL_TRY(tmp.alloc(&Bt, nn));
+            RBL_TRY(tmp.alloc(&off, 1));
+            rc = launch_eig_jacobi(dG, ld, d, Bt, ww.eig_Vt, ww.eig_V, ww.eig_lambda, off, sc.s, &sweeps);
+            (void)hipStreamSynchronize(sc.s);
+        }
+        RBL_TRY(rc);
+        ww.eig_ok = sweeps > 0;
+    }
     int dev = 0;
     RBL_HIP(hipGetDevice(&dev));
     const size_t row = sizeof(double) * (size_t)d;
@@ -1162,6 +1184,43 @@ int rbl_k_wstep_seq(int wstep, int64_t d, const double* G, int K, const double* 
             r.live_handles = rbl_live_handles(dev);
         }
     }
+    return RBL_OK;
+}
+
+int rbl_k_eig(int64_t d, const double* G, double* Vt_ld, double* V_ld, double* lambda_ld, int64_t* ld_out, int* sweeps_out) {
+    const char* who = "rbl_k_eig";
+    if (d < 1 || d > 2048 || !G || !Vt_ld || !V_ld || !lambda_ld || !ld_out || !sweeps_out) {
+        rbl_set_error("%s: 1 <= d <= 2048 (the width up to which the solver decomposes G), G, Vt_ld, V_ld, lambda_ld, ld and "
+                      "sweeps are needed (d = %lld)", who, (long long)d);
+        return RBL_ERR_INVALID;
+    }
+    Scratch sc;
+    RBL_TRY(scratch_begin(sc, nullptr));
+    const int64_t ld = round_up(d, 4);
+    const size_t nn = (size_t)ld * (size_t)ld;
+    std::vector<double> hG(nn, 0.0);
+    for (int64_t i = 0; i < d; ++i)
+        for (int64_t j = 0; j < d; ++j) hG[(size_t)(i * ld + j)] = G[i * d + j];
+    double *dG = nullptr, *Bt = nullptr, *Vt = nullptr, *V = nullptr, *lambda = nullptr;
+    unsigned long long* off = nullptr;
+    RBL_TRY(sc.upload(&dG, hG.data(), hG.size()));
+    RBL_TRY(sc.mem.alloc(&Bt, nn));
+    RBL_TRY(sc.mem.alloc(&Vt, nn));
+    RBL_TRY(sc.mem.alloc(&V, nn));
+    RBL_TRY(sc.mem.alloc(&lambda, (size_t)ld));
+    RBL_TRY(sc.mem.alloc(&off, 1));
+    RBL_HIP(hipMemsetAsync(Vt, 0xff, sizeof(double) * nn, sc.s));   // (NaN: what the decomposition does not write stays so)
+    RBL_HIP(hipMemsetAsync(V, 0xff, sizeof(double) * nn, sc.s));
+    RBL_HIP(hipMemsetAsync(lambda, 0xff, sizeof(double) * ld, sc.s));
+    int sweeps = 0;
+    const int rc = launch_eig_jacobi(dG, ld, d, Bt, Vt, V, lambda, off, sc.s, &sweeps);
+    (void)hipStreamSynchronize(sc.s);
+    RBL_TRY(rc);
+    RBL_HIP(hipMemcpy(Vt_ld, Vt, sizeof(double) * nn, hipMemcpyDeviceToHost));
+    RBL_HIP(hipMemcpy(V_ld, V, sizeof(double) * nn, hipMemcpyDeviceToHost));
+    RBL_HIP(hipMemcpy(lambda_ld, lambda, sizeof(double) * ld, hipMemcpyDeviceToHost));
+    *ld_out = ld;
+    *sweeps_out = sweeps;
     return RBL_OK;
 }
 

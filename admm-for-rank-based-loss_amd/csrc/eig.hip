@@ -5,8 +5,9 @@
 // iteration (src/optim/algorithms.py:154-157), so a factorisation of the system matrix cannot be kept - but
 // G = D^T D (algorithms.py:24) never changes, and with G = V diag(lambda) V^T
 //     w = V diag(rho / (rho lambda_j + reg)) V^T q
-// is two d x d mat-vecs for ANY rho (plus one step of iterative refinement against the unfactored matrix):
-// 5 small launches instead of the 28 of a 14-iteration warm-started CG (152 -> 30 us per iteration at d = 1000).
+// is two d x d mat-vecs for ANY rho (plus two steps of iterative refinement against the unfactored matrix):
+// 8 small launches instead of the 28 of a 14-iteration warm-started CG (152 -> 30 us per iteration at d = 1000 was
+// measured with one refinement step, 5 launches; the second adds three launches of the same kind).
 // OPT-IN (RBL_RIDGE_EIG=1), not the default: measured on MI355X (round 2) it lifts C2sq from 109.2 to 112.4 it/s,
 // C3 from 66.6 to 68.8 and C4shard from 100.3 to 103.5, but the one-row-pair-per-block Jacobi below needs
 // ~0.8 s of setup at d = 1000 - the 0.13 ms it saves per iteration pay that back after 6000 iterations, and a
@@ -111,12 +112,25 @@ __global__ __launch_bounds__(EJ_THREADS) void k_eig_finish(const double* __restr
 }
 
 // out_i = (row i of Vt) . (a1 x1 + a2 x2) / (rho lambda_i + reg): the coefficients of the solution of
-// (rho G + reg I) y = a1 x1 + a2 x2 in the eigenbasis.  One row per wave.
+// (rho G + reg I) y = a1 x1 + a2 x2 in the eigenbasis.  One row per wave.  reg == 0 leaves rho lambda_i alone in the
+// denominator: exactly 0 on the padding rows and on clamped rows, rounding level (1e-13 where 0 is meant) on the other
+// rows of the null space of a singular G.  Those rows get the coefficient 0 (the pseudo-inverse, with the cut
+// numpy.linalg.pinv uses: lambda_i at most EJ_NULL_CUT ld max lambda) - 0 / 0 would be NaN in all of w, and x / 1e-13
+// puts 1e4 ||w|| into the null space, whose image under G is rounding level times that.
+constexpr double EJ_NULL_CUT = 1e-13;
 __global__ __launch_bounds__(256) void k_eig_coef(const double* __restrict__ Vt, long long ld, const double* __restrict__ x1,
                                                    double a1, const double* __restrict__ x2, double a2,
                                                    const double* __restrict__ lambda, double rho, double reg,
                                                    double* __restrict__ out) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    double cut = -1.0;                        // reg > 0: every row is solved (lambda >= 0 > cut)
+    if (reg == 0.0) {
+        double mx = 0.0;
+        for (long long j = lane; j < ld; j += 64) mx = fmax(mx, lambda[j]);
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) mx = fmax(mx, __shfl_xor(mx, off, 64));
+        cut = EJ_NULL_CUT * (double)ld * mx;
+    }
     for (long long row = (long long)blockIdx.x * 4 + wave; row < ld; row += (long long)gridDim.x * 4) {
         const double* v = Vt + row * ld;
         double acc = 0.0;
@@ -127,7 +141,7 @@ __global__ __launch_bounds__(256) void k_eig_coef(const double* __restrict__ Vt,
         }
 #pragma unroll
         for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off, 64);
-        if (lane == 0) out[row] = acc / (rho * lambda[row] + reg);
+        if (lane == 0) out[row] = lambda[row] > cut ? acc / (rho * lambda[row] + reg) : 0.0;
     }
 }
 
@@ -201,18 +215,25 @@ int launch_eig_jacobi(const double* G, int64_t ld, int64_t d, double* Bt, double
     return RBL_OK;   // *sweeps_out stays 0: no decomposition, the caller keeps the CG w-step
 }
 
-// (rho G + reg I) w = rho q through the decomposition, one step of iterative refinement against G itself.
+// (rho G + reg I) w = rho q through the decomposition, EJ_REFINE steps of iterative refinement against G itself:
+// 2 + 3 EJ_REFINE = 8 launches.  One step is not enough on a singular G late in a solve: a null vector is only as good
+// as the threshold that left its row alone (||G v|| up to 1e-13 d max diag), and at the cap of the rho schedule
+// (217 d) with reg = 1e-4 rho ||G v|| is no longer small beside reg - each step gains one to two digits there, the
+// true residual after one is 5 - 300 x ridge_bound(1e-13, 2) at d = 63 .. 260, after two at most 0.04 x.
 // tmp1, tmp2: ld doubles each.
+constexpr int EJ_REFINE = 2;
 int launch_ridge_eig(const double* G, const double* Vt, const double* V, const double* lambda, int64_t ld, const double* q,
                      double rho, double reg, double* w, double* tmp1, double* tmp2, hipStream_t s) {
     const unsigned g = ej_rows_grid(ld);
     hipLaunchKernelGGL(k_eig_coef, dim3(g), dim3(256), 0, s, Vt, (long long)ld, q, rho, (const double*)nullptr, 0.0, lambda, rho,
                        reg, tmp1);
     hipLaunchKernelGGL(k_eig_apply, dim3(g), dim3(256), 0, s, V, (long long)ld, tmp1, w, 0);
-    // residual r = rho q - (rho G + reg I) w, correction through the same decomposition
-    RBL_TRY(launch_symv_ab(G, ld, w, tmp2, rho, reg, s));
-    hipLaunchKernelGGL(k_eig_coef, dim3(g), dim3(256), 0, s, Vt, (long long)ld, q, rho, tmp2, -1.0, lambda, rho, reg, tmp1);
-    hipLaunchKernelGGL(k_eig_apply, dim3(g), dim3(256), 0, s, V, (long long)ld, tmp1, w, 1);
+    for (int k = 0; k < EJ_REFINE; ++k) {
+        // residual r = rho q - (rho G + reg I) w, correction through the same decomposition
+        RBL_TRY(launch_symv_ab(G, ld, w, tmp2, rho, reg, s));
+        hipLaunchKernelGGL(k_eig_coef, dim3(g), dim3(256), 0, s, Vt, (long long)ld, q, rho, tmp2, -1.0, lambda, rho, reg, tmp1);
+        hipLaunchKernelGGL(k_eig_apply, dim3(g), dim3(256), 0, s, V, (long long)ld, tmp1, w, 1);
+    }
     RBL_HIP(hipGetLastError());
     return RBL_OK;
 }

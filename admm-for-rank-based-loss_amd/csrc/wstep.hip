@@ -1328,7 +1328,7 @@ int run_wstep(int wstep, const double* G, int64_t ld, const double* q, double rh
     if (pen) reg = 0.0;
     if (wstep == RBL_WSTEP_L2 && ws.eig_ok && !pen) {
         // (rho G + reg I) w = rho q through the one-time eigendecomposition of G (eig.hip): two mat-vecs for any rho,
-        // plus one step of iterative refinement against G itself
+        // plus two steps of iterative refinement against G itself
         if (iters_host) *iters_host = 1;
         ws.form = 3;
         return launch_ridge_eig(G, ws.eig_Vt, ws.eig_V, ws.eig_lambda, ld, q, rho, reg, w, ws.Gy, ws.r, s);

@@ -690,6 +690,10 @@ int  rbl_k_wstep_pen(int64_t d, const double* G, const double* q, double rho, co
  * as in rbl_k_wstep_pen (wstep 1 or 2 only; reg is then not used).
  *   route        0: as the solver runs with one live handle (the persistent kernels where the width allows them);
  *                1: the batched launches - the workspace has no exchange buffers, the test a second live handle fails too
+ *                2: (wstep 2 only) the eigendecomposition ridge: G is decomposed once on the workspace as rbl_gram_finish
+ *                   does under RBL_RIDGE_EIG=1 (no environment variable is read here), with its ld <= 2048 rule; where
+ *                   the Jacobi converged every step reports form 3 and iters 1, where it did not (or ld > 2048, or with
+ *                   l1 / l2) the steps run as under route 0 - the report's form says which
  *   launch_seq0  the workspace's launch counter before the first step (0 .. 0xfffff)
  *   flags        RBL_KW_WANT_GW  ask for G w of the solution (want_Gw);
  *                RBL_KW_W_PREV   let the lasso kernel save its warm start (w_prev_out);
@@ -702,7 +706,8 @@ int  rbl_k_wstep_pen(int64_t d, const double* G, const double* q, double rho, co
  * Every argument is checked before anything is allocated (RBL_ERR_INVALID). */
 enum { RBL_KW_WANT_GW = 1, RBL_KW_W_PREV = 2, RBL_KW_RHO_DEV = 4, RBL_KW_TWO_CALL = 8 };
 typedef struct rbl_wstep_report {
-    int32_t form;           /* rbl_stats.wstep_form: 0 batched launches, 1 one persistent launch, 2 active-set lasso kernel */
+    int32_t form;           /* rbl_stats.wstep_form: 0 batched launches, 1 one persistent launch, 2 active-set lasso kernel,
+                               3 eigendecomposition ridge (route 2) */
     int32_t status;         /* CG / nonlinear CG: 1 converged, 0 iteration cap (the kernel's own word); lasso: fs[0] */
     int32_t iters;          /* as run_wstep / finish_wstep_l1 return them */
     int32_t glds, per, nblocks, lds_bytes;   /* the persistent instance the step launched (G rows in LDS, elements per
@@ -719,6 +724,14 @@ typedef struct rbl_wstep_report {
 int  rbl_k_wstep_seq(int wstep, int64_t d, const double* G, int K, const double* Q, double rho, double reg, double smooth_t,
                      const double* l1, const double* l2, const double* w0, double tol, int max_inner, int route,
                      int launch_seq0, int flags, double* W, double* Gw, double* Wprev, rbl_wstep_report* reports);
+/* The one-time Jacobi eigendecomposition behind the eigendecomposition ridge (form 3), on a prescribed symmetric PSD G
+ * (d x d host doubles, 1 <= d, round_up(d, 4) <= 2048): G is zero-padded to ld = round_up(d, 4) as rbl_k_wstep_seq pads
+ * it and decomposed on a scratch stream.  Outputs (host): Vt_ld (ld x ld, row j = eigenvector j), V_ld (ld x ld, its
+ * transpose), lambda_ld (ld), *ld, *sweeps = the Jacobi sweeps run, 0 = not converged within the cap - the solver then
+ * keeps the CG, and V_ld / lambda_ld are NaN (only a converged run writes them; Vt_ld holds the last iterate).
+ * Every argument is checked before anything is allocated (RBL_ERR_INVALID).  The presence of this symbol is the
+ * capability probe (RBL_VERSION is unchanged). */
+int  rbl_k_eig(int64_t d, const double* G, double* Vt_ld, double* V_ld, double* lambda_ld, int64_t* ld, int* sweeps);
 /* sigma generators (src/optim/objective.py:97-164) */
 int  rbl_k_weights(int weight_function, int64_t n, const double* args, int n_args,
                    double* alphas, double* betas);

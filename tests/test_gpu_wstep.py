@@ -97,8 +97,9 @@ def check_huber(ratios, key, m, q, rep, w, ws=None, rho=RHO, reg=REG, t=T, tol=T
 def test_arguments_are_checked_before_anything_runs(L):
     G, q = np.eye(4), np.ones(4)
     ok = dict(wstep=2, G=G, Q=q, rho=1.0, reg=1.0)
-    for bad in (dict(wstep=4), dict(rho=0.0), dict(reg=-1.0), dict(tol=0.0), dict(max_inner=0), dict(route=2),
-                dict(launch_seq0=1 << 20), dict(launch_seq0=-1), dict(l2=-np.ones(4)), dict(l1=np.full(4, np.nan), wstep=1),
+    for bad in (dict(wstep=4), dict(rho=0.0), dict(reg=-1.0), dict(tol=0.0), dict(max_inner=0), dict(route=3),
+                dict(route=2, wstep=1), dict(route=2, wstep=3),        # (route 2 is the ridge's: tests/test_gpu_eig.py)
+dict(launch_seq0=1 << 20), dict(launch_seq0=-1), dict(l2=-np.ones(4)), dict(l1=np.full(4, np.nan), wstep=1),
                 dict(wstep=3, l2=np.ones(4)), dict(wstep=2, two_call=True), dict(wstep=3, rho_dev=True),
                 dict(wstep=3, smooth_t=0.0)):
         with pytest.raises(ValueError):

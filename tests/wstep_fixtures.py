@@ -1,6 +1,8 @@
 """Matrices, planted minimisers, bounds and the instance table for the d-space w-steps (csrc/wstep.hip, csrc/lasso_fs.hip)
 run through rbl_k_wstep_seq (a helper, not a conftest).  Nothing here calls the library; tests/test_wstep_host.py checks
-this file on the CPU, tests/test_gpu_wstep.py uses it against the kernels.
+this file on the CPU, tests/test_gpu_wstep.py uses it against the kernels.  The fixtures, widths and the two bounds of the
+eigendecomposition ridge (csrc/eig.hip, route 2 of the entry) are in the section of that name; tests/test_eig_host.py
+checks them and tests/test_gpu_eig.py uses them.
 
 Instance table.  A persistent w-step launches ceil(ld / WP_RPB) blocks of WP_THREADS threads.  A block keeps ld + 48
 doubles (the vector, 16 block sums, WP_RPB + 16 for its rows of the product) and, when they fit the LDS budget beside
@@ -134,6 +136,121 @@ def collinear(d, n=None):
     G = D.T @ D                                                     # integers below 2^53: exact in any order
     assert np.array_equal(G, (D.astype(np.int64).T @ D.astype(np.int64)).astype(np.float64))
     return Mat(G, np.zeros(d), D, 0.0, float(np.sum(D * D)), "collinear"), D
+
+
+# ------------------------------------------------------------- the eigendecomposition ridge (csrc/eig.hip), route 2
+# Widths: the smallest at which each loop shape of eig.hip changes.  1: one player and the dummy, nothing rotates; 2, 3: 3 is
+# odd (a dummy player) with ld = 4; 5: padded past one packet (ld = 8); 63, 64, 65: the 64-lane stride of k_eig_coef /
+# k_eig_apply; 255, 256, 257, 260: one trip against two of the EJ_THREADS = 256 loops, with ld = d and ld > d.
+EIG_WIDTHS = [1, 2, 3, 5, 63, 64, 65, 255, 256, 257, 260]
+EIG_EXACT = ["identity", "diagzero", "zero", "rankone"]
+EIG_ILL_D = [3, 5, 24, 63, 64, 65, 132]          # "ill" where the Jacobi converges within its 30 sweeps ...
+EIG_ILL_STALLS_D = 257                           # ... and where the restatement does not
+EIG_COLLINEAR_D = [w for w in EIG_WIDTHS if w >= 8]
+EIG_WIDE_D = [1000, 2048]                        # "well" only: the benchmark's width and the limit of the route
+EIG_MAX_LD = 2048                                # rbl_gram_finish decomposes up to here; beyond, the CG runs
+EIG_BEYOND_D = 2052
+# every decomposition the GPU tests run and tests/test_eig_host.py restates (the two wide ones are restated once, by hand:
+# EIG_REF_WIDE below)
+EIG_CASES = ([("well", d) for d in EIG_WIDTHS] + [("ill", d) for d in EIG_ILL_D] + [("collinear", d) for d in EIG_COLLINEAR_D]
+             + [(k, d) for k in EIG_EXACT for d in EIG_WIDTHS])
+# ridge through the basis: planted minimisers on these, at the four (rho, reg) of eig_rho_reg(d)
+EIG_RIDGE_CASES = [c for c in EIG_CASES if c[0] in ("well", "ill", "collinear")]
+
+
+def eig_rho_reg(d):
+    """(rho, reg): the w-step tests' own pair, a small rho, and the cap of the rho schedule (217 d) with reg = 0.01 and
+    with the reference default 1e-4"""
+    return [(1.0, 0.5), (2.0 ** -12, 0.5), (217.0 * d, 0.01), (217.0 * d, 1e-4)]
+
+
+def eig_matrix(kind, d):
+    """the Mat of an EIG_CASES entry.  The exact kinds: "identity" 3 I; "diagzero" diag(1 + j mod 7) with entry d // 2
+    zero (a null row before any rotation); "zero"; "rankone" u u^T with integer u, every third entry zero (null rows from
+    the start) - all exact in fp64, mv through the factors in longdouble as for the others."""
+    if kind in ("well", "ill"):
+        return matrix(d, kind)
+    if kind == "collinear":
+        return collinear(d)[0]
+    j = np.arange(d)
+    none = np.zeros((1, d))
+    if kind == "identity":
+        return Mat(3.0 * np.eye(d), np.full(d, 3.0), none, 3.0, 3.0, kind)
+    if kind == "diagzero":
+        s = 1.0 + j % 7
+        s[d // 2] = 0.0
+        return Mat(np.diag(s), s, none, 0.0, float(np.max(s)), kind)
+    if kind == "zero":
+        return Mat(np.zeros((d, d)), np.zeros(d), none, 0.0, 0.0, kind)
+    if kind == "rankone":
+        u = np.where(j % 3 == 2, 0.0, (j % 5 + 1.0) * np.where(j % 2, -1.0, 1.0))
+        return Mat(np.outer(u, u), np.zeros(d), u[None, :], 0.0, float(u @ u), kind)
+    raise ValueError(kind)
+
+
+def eig_null_rows(kind, d):
+    """rows of G that are zero from the start: the Jacobi must leave them (and their columns of V) alone"""
+    j = np.arange(d)
+    return {"diagzero": j[j == d // 2], "zero": j, "rankone": j[j % 3 == 2]}.get(kind, j[:0])
+
+
+# The two bounds the project did not have, both K d eps:
+#   EIG_ORTH_K   max |Vt Vt^T - I| <= EIG_ORTH_K d eps
+#   EIG_RES_K    max_j ||G v_j - lambda_j v_j||_2 <= EIG_RES_K d eps lam_hi   (and |lambda - eigvalsh| the same)
+# K = 4 x the largest value the NumPy restatement (tests/eig_ref.py) reaches over EIG_CASES and EIG_REF_WIDE; the device
+# sums a row in a block tree where NumPy sums pairwise, 4 covers the order.  Restatement, in units of d eps:
+#   orthogonality   largest 3.01 (ill, d = 132); ill 0.46 - 3.01, collinear 1.17 - 1.59, well 0.15 - 1.10, rank one <= 0.21
+#   residual        largest 31.3 (collinear, d = 63: a null vector is only as good as the threshold that leaves its row
+#                   alone, 1e-13 d max diag); collinear 1.4 - 31.3, ill 0.12 - 2.71, well 0.19 - 0.80, rank one <= 0.23
+# (tests/test_eig_host.py prints the table, holds every case to half its bound and the constants to 4 x the largest)
+EIG_ORTH_K = 12.1
+EIG_RES_K = 126.0
+# the restatement on the wide matrices (minutes on a CPU, so run once and kept as data; measured on 64 sampled rows):
+# d -> (sweeps, orthogonality and residual in units of d eps)
+EIG_REF_WIDE = {1000: (6, 1.10, 0.77), 2048: (6, 1.15, 0.89)}
+# sweeps the restatement needs per fixture (the host test allows its live count one either way); the GPU tests print
+# them beside the device's and assert no equality
+EIG_REF_SWEEPS = {("well", 1): 1, ("well", 2): 2, ("well", 3): 4, ("well", 5): 4, ("well", 63): 5, ("well", 64): 6,
+                  ("well", 65): 6, ("well", 255): 6, ("well", 256): 6, ("well", 257): 6, ("well", 260): 6,
+                  ("well", 1000): 6, ("well", 2048): 6,
+                  ("ill", 3): 4, ("ill", 5): 5, ("ill", 24): 10, ("ill", 63): 18, ("ill", 64): 19, ("ill", 65): 18,
+                  ("ill", 132): 27,
+                  ("collinear", 63): 11, ("collinear", 64): 11, ("collinear", 65): 11, ("collinear", 255): 15,
+                  ("collinear", 256): 15, ("collinear", 257): 16, ("collinear", 260): 15}
+EIG_REF_SWEEPS.update({("identity", d): 1 for d in EIG_WIDTHS})
+EIG_REF_SWEEPS.update({("diagzero", d): 1 for d in EIG_WIDTHS})
+EIG_REF_SWEEPS.update({("zero", d): 1 for d in EIG_WIDTHS})
+EIG_REF_SWEEPS.update({("rankone", d): (1 if d == 1 else 2) for d in EIG_WIDTHS})
+
+
+def drifting_rhs_in_range(m, q0, K=3, seed=0):
+    """K right-hand sides that drift inside range(G): q_k = q_{k-1} + 1e-3 x (G u_k scaled to unit RMS), rounded to fp64.
+    This is all a solver's right-hand side can do - q = D^T c lies in range(D^T) = range(G) - and on a singular G it is
+    what keeps the problem the solver's: a component of q in the null space is divided by reg alone, ||w|| = rho 1e-3 /
+    reg (1e5 - 1e6 at the rho cap with reg = 1e-4, which no iterate has), and with reg = 0 the system has no solution."""
+    rng = np.random.default_rng([m.d, 67, seed])
+    Q = np.empty((K, m.d))
+    q = np.array(q0, dtype=np.float64)
+    for k in range(K):
+        if k:
+            t = np.asarray(m.mv(rng.standard_normal(m.d)), dtype=np.float64)
+            q = q + 1e-3 * t / float(np.sqrt(np.mean(t * t)))
+        Q[k] = q
+    return Q
+
+
+def eig_drift(m, q0, K=3):
+    """the drifting right-hand sides of the route 2 tests: drifting_rhs without jumps where G is non-singular (any
+    direction is in range), drifting_rhs_in_range where it is singular"""
+    return drifting_rhs(q0, K=K, jumps=()) if m.lam_lo > 0 else drifting_rhs_in_range(m, q0, K)
+
+
+def eig_orth_bound(d):
+    return EIG_ORTH_K * d * EPS
+
+
+def eig_res_bound(m):
+    return EIG_RES_K * m.d * EPS * m.lam_hi
 
 
 # ---------------------------------------------------------------------------------------------- planted minimisers
