@@ -42,6 +42,18 @@ void rbl_spin_wait(const volatile int* word, int sentinel, hipStream_t stream) {
     }
 }
 
+// RBL_NO_FUSE=1 (tests, comparisons): the two-pass iteration with plain passes - no single-sweep erm pass, no fused V pass
+static bool no_fuse() {
+    const char* nf = getenv("RBL_NO_FUSE");
+    return nf && nf[0] == '1';
+}
+
+// The single-sweep erm pass: erm problems at the widths it has instances for.  The sign of a handle's own labels is not
+// part of its in-pass prox, so such a handle runs the two-pass iteration.
+bool single_sweep_allowed(const rbl_solver* h) {
+    return !h->rs && !h->sorted_path && !no_fuse() && sweep_erm_supported(h->storage, h->ld);
+}
+
 int alloc_sort(DevArena& mem, SortWorkspace& sw, int64_t n, bool with_vals, hipStream_t s) {
     RBL_TRY(mem.alloc(&sw.keys[0], (size_t)n));
     RBL_TRY(mem.alloc(&sw.keys[1], (size_t)n));
@@ -298,6 +310,7 @@ static int create_setup(rbl_solver* h, rbl_solver* owner = nullptr) {
     for (auto& e : h->ev_spec) RBL_HIP(hipEventCreate(&e));
     DevArena& mem = h->mem;
     RBL_TRY(mem.pinned(&h->hstat, 16, hipHostMallocCoherent));
+    h->fin.pin = reinterpret_cast<int*>(h->hstat + 15);
     const int64_t n = h->n, ld = h->ld, nt = h->nt;
     if (owner) {
         h->shared = owner->shared;
@@ -359,8 +372,8 @@ static int create_setup(rbl_solver* h, rbl_solver* owner = nullptr) {
             RBL_TRY(alloc_pav(mem, h->pw, nt, h->stream));
             RBL_TRY(mem.alloc(&h->s32.mm, (size_t)s32_range_words()));
             RBL_TRY(mem.alloc(&h->s32.flag, 1));
-            RBL_TRY(mem.pinned(&h->s32.pin, 16, hipHostMallocDefault));
-            for (int i = 0; i < 16; ++i) h->s32.pin[i] = 0;
+            RBL_TRY(mem.pinned(&h->s32.v.pin, 16, hipHostMallocDefault));
+            for (int i = 0; i < 16; ++i) h->s32.v.pin[i] = 0;
             RBL_TRY(alloc_prefix(mem, h->pfx_a, nt));
             h->pfx_b = h->pfx_a;
             if (cfg->weight_function == RBL_W_EHRM) RBL_TRY(alloc_prefix(mem, h->pfx_b, nt));
@@ -379,9 +392,8 @@ static int create_setup(rbl_solver* h, rbl_solver* owner = nullptr) {
         RBL_TRY(fill_const(h->z, n, 0.1 * reg / (double)nt, h->stream));
         RBL_TRY(fill_const(h->w, h->d, 0.001 * reg / (double)h->d / (double)nt, h->stream));
         RBL_HIP(hipMemsetAsync(h->q, 0, sizeof(double) * (ld * 2 + 3), h->stream));
-        const char* nf = getenv("RBL_NO_FUSE");
-        h->fused_ok = !h->sorted_path && !(nf && nf[0] == '1') && sweep_erm_supported(h->storage, ld);
-        h->fuse_v = !h->fused_ok && !(nf && nf[0] == '1') && n > 0 && sweep_v_supported(h->storage, ld);
+        h->fused_ok = single_sweep_allowed(h);
+        h->fuse_v = !h->fused_ok && !no_fuse() && n > 0 && sweep_v_supported(h->storage, ld);
         if (h->fused_ok) {
             RBL_TRY(mem.alloc(&h->z_next, (size_t)n));
             RBL_TRY(mem.alloc(&h->p, (size_t)ld));

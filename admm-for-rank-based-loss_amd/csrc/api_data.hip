@@ -936,12 +936,8 @@ int rbl_set_labels(rbl_solver* h, const double* y) {
         RBL_TRY(upload_rows(h, h->z, zh.data()));
         RBL_TRY(upload_rows(h, h->lam, lh.data()));
     }
-    if (!h->cfg.objective_only) {
-        // the sign is not part of the single-sweep erm pass' in-pass prox: such a handle runs the two-pass iteration
-        const char* nf = getenv("RBL_NO_FUSE");
-        h->fused_ok = !h->rs && !h->sorted_path && !(nf && nf[0] == '1') && sweep_erm_supported(h->storage, h->ld);
-    }
-    h->z_ready = h->p_valid = h->p_pending = h->pred_valid = false;
+    if (!h->cfg.objective_only) h->fused_ok = single_sweep_allowed(h);   // (not with labels of its own)
+    drop_look_ahead(h);
     h->keys_ready = h->s32.m_ready = false;
     return RBL_OK;
 }

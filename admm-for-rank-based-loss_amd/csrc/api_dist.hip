@@ -297,18 +297,10 @@ int rbl_zbd_decide(rbl_solver* h, int k, int last, int* settled) {
     if (!settled) return launch_zbd_decide(h->cfg.loss, h->zb.cfg, h->zb.st, k, h->step_rho, h->zb.tot, last, h->stream);
     // the verdict of this pass through pinned memory (one host wait): every rank reads the same answer, the driver stops
     // issuing root passes (and their all-reduces) for this cluster after the pass that settles it
-    volatile int* pin = h->zb.pin + 4;
-    h->zb.dseq = (h->zb.dseq & 0x3fffffff) + 1;
-    pin[0] = 0;
-    RBL_TRY(launch_zbd_decide(h->cfg.loss, h->zb.cfg, h->zb.st, k, h->step_rho, h->zb.tot, last, h->stream, h->zb.pin + 4,
-                              h->zb.dseq));
-    rbl_spin_wait(pin, 0, h->stream);
-    if (pin[0] != h->zb.dseq) {
-        rbl_set_error("zbd_decide: the verdict of the root pass was never written");
-        (void)hipGetLastError();
-        return RBL_ERR_HIP;
-    }
-    *settled = pin[1];
+    const int seq = h->zb.dv.arm();
+    RBL_TRY(launch_zbd_decide(h->cfg.loss, h->zb.cfg, h->zb.st, k, h->step_rho, h->zb.tot, last, h->stream, h->zb.dv.pin, seq));
+    RBL_TRY(h->zb.dv.wait(h->stream, "zbd_decide: the verdict of the root pass was never written"));
+    *settled = h->zb.dv.word(1);
     return RBL_OK;
 }
 int rbl_zbd_root_passes(void) { return ZB_ROOT_PASSES; }
@@ -327,29 +319,20 @@ int rbl_zbd_finish(rbl_solver* h, int k, const void* packs_all_dev, int world) {
 int rbl_zbd_apply(rbl_solver* h, int* status) {
     RBL_ENTER_ITER(h);
     RBL_TRY(zbd_ready(h));
-    h->zb.seq = (h->zb.seq & 0x3fffffff) + 1;
-    h->zb.pin[0] = 0;
-    RBL_TRY(launch_zbd_apply(h->cfg.loss, h->zb.cfg, h->n, h->step_rho, h->m, h->z, h->lam, h->c, h->zb.st, h->zb.pin, h->zb.seq,
+    const int seq = h->zb.v.arm();
+    RBL_TRY(launch_zbd_apply(h->cfg.loss, h->zb.cfg, h->n, h->step_rho, h->m, h->z, h->lam, h->c, h->zb.st, h->zb.v.pin, seq,
                              h->pw.counters, h->stream));
     // every rank holds the same state, so every rank reads the same verdict and takes the same branch afterwards
-    volatile int* pin = h->zb.pin;
-    rbl_spin_wait(pin, 0, h->stream);
-    if (pin[0] != h->zb.seq) {
-        rbl_set_error("banded z-step: its status word was never written");
-        (void)hipGetLastError();
-        return RBL_ERR_HIP;
-    }
-    if (status) *status = pin[1];
-    if (pin[1] == ZB_OK) {
+    RBL_TRY(h->zb.v.wait(h->stream, "banded z-step: its status word was never written"));
+    if (status) *status = h->zb.v.word(1);
+    if (h->zb.v.word(1) == ZB_OK) {
         h->zb.backoff = 0;
         h->zb.c_ready = true;
         h->zb.mode = 1;
         h->keys_ready = false;
         if (h->phase_timing) RBL_HIP(hipEventRecord(h->ev[1], h->stream));
     } else {
-        h->zb.backoff = h->zb.backoff < 2 ? 2 : (h->zb.backoff >= 32 ? 64 : 2 * h->zb.backoff);
-        h->zb.skip_until = h->iter + 1 + h->zb.backoff;
-        h->zb.mode = 2;   // the caller runs the sort-based distributed z-step (rbl_zd_*) for this iteration
+        zb_back_off(h);   // mode 2: the caller runs the sort-based distributed z-step (rbl_zd_*) for this iteration
     }
     return RBL_OK;
 }

@@ -111,7 +111,7 @@ int rbl_group_create_opts(rbl_solver* const* members, int k, int flags, rbl_grou
         h->stream = g->stream;
         // two-pass structure for every member: whatever a single-sweep erm pass prepared ahead is dropped
         h->fused_ok = false;
-        h->z_ready = h->p_valid = h->p_pending = h->pred_valid = false;
+        drop_look_ahead(h);
     }
     *out = g.release();
     return RBL_OK;
@@ -158,13 +158,7 @@ int rbl_group_step(rbl_group* g, int want_objective, rbl_stats* out) {
     }
     // C: q_k = D^T c_k, D read once per kpp members
     if (g->shared_passes) {
-        for (int i : idx) {
-            rbl_solver* h = g->m[i];
-            if (h->sorted_path && !h->zb.c_ready) RBL_TRY(launch_make_c(h->n, h->z, h->lam, h->step_rho, h->c, s));
-            h->zb.c_ready = false;
-            h->zb.q_done = h->zb.used;     // an unsettled z-step's q is redone with it, by the member alone (zb_resolve)
-            h->s32.q_done = h->s32.used;
-        }
+        for (int i : idx) RBL_TRY(q_prologue(g->m[i]));   // (an unsettled z-step's q is redone with it, by the member alone)
         const bool timed = g->profile && !idx.empty();
         if (timed) RBL_HIP(hipEventRecord(g->pev[0], s));
         for (size_t b = 0; b < idx.size(); b += (size_t)g->kpp) {
@@ -188,12 +182,7 @@ int rbl_group_step(rbl_group* g, int want_objective, rbl_stats* out) {
             g->shared_q += 1;
         }
         if (timed) RBL_HIP(hipEventRecord(g->pev[1], s));
-        for (int i : idx) {
-            rbl_solver* h = g->m[i];
-            h->pending_mask = 1;
-            h->z_ready = false;
-            if (h->phase_timing) RBL_HIP(hipEventRecord(h->ev[2], s));
-        }
+        for (int i : idx) RBL_TRY(q_epilogue(g->m[i]));
     } else {
         for (int i : idx) {
             SyncBook book(g->syncs[i]);
@@ -250,18 +239,9 @@ int rbl_group_step(rbl_group* g, int want_objective, rbl_stats* out) {
         for (int i : idx) {
             rbl_solver* h = g->m[i];
             h->fused_ran = false;
-            h->fused_v_ran = true;
-            h->v_valid = true;
-            h->pending_mask = 2;
-            h->want_obj = want_objective;
-            h->obj_is_risk = false;
+            h->fused_v_ran = h->v_valid = true;
             if (h->phase_timing) RBL_HIP(hipEventRecord(h->ev[4], s));
-            if (want_objective && h->sorted_path) {
-                RBL_TRY(risk_from_v(h, h->v, h->red + 1));
-                h->obj_is_risk = true;
-            } else if (want_objective) {
-                RBL_TRY(launch_loss_sum(h->cfg.loss, h->n, h->v, 1.0, h->partials, h->red + 1, s, h->rs, h->cw));   // objective.py:11-24
-            }
+            RBL_TRY(dual_epilogue(h, want_objective, false));   // the pass carries no loss sum
         }
     } else {
         for (int i : idx) {
@@ -273,9 +253,8 @@ int rbl_group_step(rbl_group* g, int want_objective, rbl_stats* out) {
     // stop tests and schedules
     for (int i : idx) RBL_TRY(phase_finish_part(g->m[i], nullptr, FIN_ENQUEUE));
     if (!idx.empty()) {
-        rbl_solver* hl = g->m[idx.back()];
         SyncBook book(g->syncs[idx[0]]);
-        rbl_spin_wait(reinterpret_cast<volatile int*>(hl->hstat + 15), 0, s);
+        RBL_TRY(g->m[idx.back()]->fin.wait(s, FIN_NEVER));
     }
     for (int i : idx) {
         g_host_syncs = g->syncs[i];

@@ -55,9 +55,8 @@ int z_step_sorted(rbl_solver* h, const double* msrc, double rho, bool allow32 = 
         RBL_TRY(launch_keys32(nt, h->m, h->s32.mm, k32, h->sw.vals[0], (u32)h->off, s));
         RBL_TRY(launch_radix_sort32(h->sw, nt, s));
         RBL_TRY(launch_sort32_fix(nt, k32, h->sw.vals[0], h->m, (u32)h->off, h->pw.ms, h->sw.vals[1], h->s32.flag, s));
-        h->s32.seq = (h->s32.seq & 0x3fffffff) + 1;
-        h->s32.pin[0] = 0;
-        hipLaunchKernelGGL(k_publish_flag, dim3(1), dim3(64), 0, s, (const int*)h->s32.flag, h->s32.pin, h->s32.seq);
+        const int seq = h->s32.v.arm();
+        hipLaunchKernelGGL(k_publish_flag, dim3(1), dim3(64), 0, s, (const int*)h->s32.flag, h->s32.v.pin, seq);
         RBL_HIP(hipGetLastError());
         h->s32.used = true;
         h->s32.q_done = false;
@@ -184,8 +183,9 @@ int zb_setup(rbl_solver* h) {
     RBL_TRY(h->mem.alloc((unsigned char**)&h->zb.part, zb_partials_bytes()));
     RBL_TRY(h->mem.alloc(&h->zb.tot, (size_t)(4 * ZB_C)));
     RBL_TRY(h->mem.alloc(&h->zb.pack, (size_t)(ZB_GCAP + 1)));
-    RBL_TRY(h->mem.pinned(&h->zb.pin, 16, hipHostMallocDefault));
-    for (int i = 0; i < 16; ++i) h->zb.pin[i] = 0;
+    RBL_TRY(h->mem.pinned(&h->zb.v.pin, 16, hipHostMallocDefault));
+    for (int i = 0; i < 16; ++i) h->zb.v.pin[i] = 0;
+    h->zb.dv.pin = h->zb.v.pin + 4;
     h->zb.enabled = true;   // set last: the buffers above are all there
     return RBL_OK;
 }
@@ -209,59 +209,46 @@ int risk_from_v(rbl_solver* h, const double* v_all, double* out_dev) {
     return launch_sorted_loss_dot(h->cfg.loss, h->nt, h->sw.keys[0], h->sigma_a, h->partials, out_dev, s);
 }
 
-// The sort-free z-step (zband.hip) reports through a pinned word whether it could certify its result.  Whoever is about
-// to look at z (or at the q formed from it) before rbl_phase_w has done so settles it here: wait for the word; not
-// certified -> the z-step (and q, if rbl_phase_q has run) is redone with the sort + merge-tree PAV, and the fast path
-// pauses for 2, 4, ... 64 iterations (the first iterations pool most of the rows in one block; that passes).
-// *redone (optional): tells rbl_phase_w that its w-step has to be repeated.
-int zb_resolve(rbl_solver* h, bool* redone) {
-    if (redone) *redone = false;
-    if (h->s32.used) {
-        // z-step with 32-bit sort keys: a run of equal keys too long for the fix-up (many m within range / 2^32 of each
-        // other: ties on a grid, a degenerate range) - redo this iteration's z-step (and q) with 64-bit keys, and stay on
-        // them for the next 64 iterations
-        h->s32.used = false;
-        volatile int* pin = h->s32.pin;
-        if (pin[0] != h->s32.seq) rbl_spin_wait(pin, 0, h->stream);
-        if (pin[0] != h->s32.seq) {
-            rbl_set_error("z-step: the verdict of the 32-bit sort was never written");
-            (void)hipGetLastError();
-            return RBL_ERR_HIP;
-        }
-        if (pin[1] != 0) {
-            h->s32.skip_until = h->iter + 1 + 64;
-            const bool q_done = h->s32.q_done;
-            h->s32.q_done = false;
-            RBL_TRY(z_step_sorted(h, h->m, h->step_rho, false));
-            if (q_done) {
-                RBL_TRY(launch_make_c(h->n, h->z, h->lam, h->step_rho, h->c, h->stream));
-                RBL_TRY(gemvt_h(h, h->c, h->q));
-                h->nd_launches += 1;
-            }
-            if (redone) *redone = true;
-        }
-        return RBL_OK;
-    }
-    if (!h->zb.used) return RBL_OK;
-    h->zb.used = false;
-    volatile int* pin = h->zb.pin;
-    if (pin[0] != h->zb.seq) rbl_spin_wait(pin, 0, h->stream);
-    if (pin[0] != h->zb.seq) {
-        rbl_set_error("banded z-step: its status word was never written");
-        (void)hipGetLastError();
-        return RBL_ERR_HIP;
-    }
-    if (pin[1] == ZB_OK) {
-        h->zb.backoff = 0;
-        return RBL_OK;
-    }
+// an uncertified sort-free z-step (here, and the sharded rbl_zbd_apply): the path pauses for 2, 4, ... 64 iterations
+void zb_back_off(rbl_solver* h) {
     h->zb.backoff = h->zb.backoff < 2 ? 2 : (h->zb.backoff >= 32 ? 64 : 2 * h->zb.backoff);
     h->zb.skip_until = h->iter + 1 + h->zb.backoff;
     h->zb.mode = 2;
-    const bool q_done = h->zb.q_done;
-    h->zb.c_ready = h->zb.q_done = false;
+}
+
+// The fast z-steps - the sort-free one (zband.hip) and the sort with 32-bit keys - report through pinned words
+// (PinVerdict) whether they could certify their result.  Whoever is about to look at z (or at the q formed from it)
+// before rbl_phase_w has done so settles it here: wait for the word; not certified -> the z-step (and q, if the q phase
+// has run) is redone with the 64-bit sort + merge-tree PAV, and the fast path pauses (the sort-free one for 2, 4, ... 64
+// iterations: the first iterations pool most of the rows in one block, that passes; 32-bit keys for 64).
+// *redone (optional): tells rbl_phase_w that its w-step has to be repeated.
+int zb_resolve(rbl_solver* h, bool* redone) {
+    if (redone) *redone = false;
+    bool q_done = false;
+    if (h->s32.used) {
+        // a run of equal keys too long for the fix-up (many m within range / 2^32 of each other: ties on a grid, a
+        // degenerate range)
+        h->s32.used = false;
+        RBL_TRY(h->s32.v.settle(h->stream, "z-step: the verdict of the 32-bit sort was never written"));
+        if (h->s32.v.word(1) == 0) return RBL_OK;
+        h->s32.skip_until = h->iter + 1 + 64;
+        q_done = h->s32.q_done;
+        h->s32.q_done = false;
+    } else if (h->zb.used) {
+        h->zb.used = false;
+        RBL_TRY(h->zb.v.settle(h->stream, "banded z-step: its status word was never written"));
+        if (h->zb.v.word(1) == ZB_OK) {
+            h->zb.backoff = 0;
+            return RBL_OK;
+        }
+        zb_back_off(h);
+        q_done = h->zb.q_done;
+        h->zb.c_ready = h->zb.q_done = false;
+    } else {
+        return RBL_OK;
+    }
     RBL_TRY(z_step_sorted(h, h->m, h->step_rho, false));
-    if (q_done) {
+    if (q_done) {   // whichever pass formed it - the handle's own or a group's shared one - the redo is the handle's alone
         RBL_TRY(launch_make_c(h->n, h->z, h->lam, h->step_rho, h->c, h->stream));
         RBL_TRY(gemvt_h(h, h->c, h->q));
         h->nd_launches += 1;
@@ -312,13 +299,14 @@ static inline double* q_zz(rbl_solver* h) { return h->q + 2 * h->ld; }     // ||
 // kernel events in this iteration?  (every profile_every-th one: an event record costs ~5 us of stream time)
 static inline bool prof_now(const rbl_solver* h) { return h->profile && (h->iter % h->profile_every) == 0; }
 
-// what every form of the dual update ends with: the logged loss sum where k_dual's is not the handle's own, the flags of
-// the exchange buffer, the rank-weighted risk
-static int dual_epilogue(rbl_solver* h, int want_objective) {
-    // own labels: k_dual summed the losses at v as the pass left it - the handle's own are at r * v; row weights: k_dual
-    // sums unweighted losses (the single-sweep pass' own loss sum took the weights already)
-    if ((h->rs || (h->cw && !h->fused_ran)) && want_objective && !h->sorted_path)
-        RBL_TRY(launch_loss_sum(h->cfg.loss, h->n, h->v, 1.0, h->partials, h->red + 1, h->stream, h->rs, h->cw));
+// What every form of the dual update ends with: the logged loss sum of an erm handle where the pass did not leave it, the
+// flags of the exchange buffer, the rank-weighted risk.  own_loss_in_red: red[1] holds the handle's own loss sum already -
+// the single-sweep pass' does (weights included; it never runs with own labels), k_dual's does unless the handle has own
+// labels (k_dual sums the losses at v as the pass left it, the handle's own are at r * v) or row weights (k_dual sums
+// unweighted losses); the V-only passes (launch_sweep_v, a group's launch_sweep_v_multi) leave none
+int dual_epilogue(rbl_solver* h, int want_objective, bool own_loss_in_red) {
+    if (!own_loss_in_red && want_objective && !h->sorted_path)
+        RBL_TRY(launch_loss_sum(h->cfg.loss, h->n, h->v, 1.0, h->partials, h->red + 1, h->stream, h->rs, h->cw));   // objective.py:11-24
     h->pending_mask = 2 | (h->fused_ran ? 1 : 0);
     h->want_obj = want_objective;
     h->obj_is_risk = false;
@@ -336,7 +324,26 @@ int dual_after_v(rbl_solver* h, int want_objective) {
     h->v_valid = true;
     if (h->phase_timing) RBL_HIP(hipEventRecord(h->ev[4], h->stream));
     RBL_TRY(launch_dual(h->cfg.loss, h->n, h->step_rho, h->z, h->v, h->lam, h->partials, h->red, h->stream));
-    return dual_epilogue(h, want_objective);
+    return dual_epilogue(h, want_objective, !(h->rs || h->cw));
+}
+
+// Before q = D^T c in any form (the handle's own pass, a group's shared one).  Rank-weighted problems: the z-step's
+// scatter writes z alone (one random access per row); c = z + lambda/rho (algorithms.py:192) is a streaming pass here.
+// (Forming it inside the sweep was tried: the per-row division on the sweep's critical path costs 0.9 ms, the streaming
+// pass 30 us.)  The q of an unsettled fast z-step is owed a redo with it (zb_resolve).
+int q_prologue(rbl_solver* h) {
+    if (h->sorted_path && !h->zb.c_ready) RBL_TRY(launch_make_c(h->n, h->z, h->lam, h->step_rho, h->c, h->stream));
+    h->zb.c_ready = false;
+    h->zb.q_done = h->zb.used;
+    h->s32.q_done = h->s32.used;
+    return RBL_OK;
+}
+
+int q_epilogue(rbl_solver* h, bool q_ahead) {
+    h->pending_mask = q_ahead ? 0 : 1;  // a fused pass' q was already summed with its residuals
+    h->z_ready = false;  // consumed: q (and zz) now belong to the iteration in flight
+    if (h->phase_timing) RBL_HIP(hipEventRecord(h->ev[2], h->stream));
+    return RBL_OK;
 }
 
 extern "C" {
@@ -353,7 +360,7 @@ int rbl_phase_m(rbl_solver* h) {
         // which z-step will follow on a single handle: the sort-free one (banded weights), else the sort - with 32-bit
         // keys from the second iteration on (iteration 0 starts from equal m: one run) unless a step was not certified
         const bool banded_next = h->zb.enabled && h->nt == h->n && h->iter > 0 && h->iter >= h->zb.skip_until;
-        const bool s32 = h->s32.pin && !h->s32.off && h->nt == h->n && h->n >= 2 && h->iter > 0 &&
+        const bool s32 = h->s32.v.pin && !h->s32.off && h->nt == h->n && h->n >= 2 && h->iter > 0 &&
                          h->iter >= h->s32.skip_until && !banded_next;
         h->s32.m_ready = false;
         if (s32) {
@@ -393,10 +400,9 @@ int rbl_phase_z(rbl_solver* h, const void* m_all_dev) {
         h->zb.mode = 0;
         // iteration 0 starts from w = 0, lambda = 0: every m is equal, the keys tie across every band edge
         if (h->zb.enabled && h->nt == h->n && h->keys_ready && msrc == h->m && h->iter > 0 && h->iter >= h->zb.skip_until) {
-            h->zb.seq = (h->zb.seq & 0x3fffffff) + 1;
-            h->zb.pin[0] = 0;
+            const int seq = h->zb.v.arm();
             RBL_TRY(launch_zband(h->cfg.loss, h->zb.cfg, h->n, rho, h->sw.keys[0], h->m, h->z, h->lam, h->c, h->zb.st, h->zb.hist,
-                                 h->zb.part, h->zb.pin, h->zb.seq, h->pw.counters, h->stream, h->rs));
+                                 h->zb.part, h->zb.v.pin, seq, h->pw.counters, h->stream, h->rs));
             h->zb.used = true;
             h->zb.q_done = false;
             h->zb.c_ready = true;   // the element-wise pass wrote c = z + lambda/rho as well
@@ -472,15 +478,10 @@ int rbl_phase_w_external(rbl_solver* h, const double* w) {
 
 int rbl_phase_q(rbl_solver* h) {
     RBL_ENTER_ITER(h);
-    if (!(h->fused_ok && h->z_ready)) {
+    const bool q_ahead = h->fused_ok && h->z_ready;
+    if (!q_ahead) {
         if (prof_now(h)) RBL_HIP(hipEventRecord(h->kev[2], h->stream));
-        // rank-weighted problems: the z-step's scatter writes z alone (one random access per row); c = z +
-        // lambda/rho (algorithms.py:192) is a streaming pass here.  (Forming it inside the sweep was tried:
-        // the per-row division on the sweep's critical path costs 0.9 ms, the streaming pass 30 us.)
-        if (h->sorted_path && !h->zb.c_ready) RBL_TRY(launch_make_c(h->n, h->z, h->lam, h->step_rho, h->c, h->stream));
-        h->zb.c_ready = false;
-        h->zb.q_done = h->zb.used;   // q of an unsettled sort-free z-step (zb_resolve redoes it with the z-step)
-        h->s32.q_done = h->s32.used; // ... and of an unsettled 32-bit sort
+        RBL_TRY(q_prologue(h));
         RBL_TRY(gemvt_h(h, h->c, h->q, prof_now(h) ? h->kev[3] : nullptr));
         h->nd_launches += 1;
         if (prof_now(h)) h->kev_pending[1] = h->n > 0;
@@ -491,10 +492,7 @@ int rbl_phase_q(rbl_solver* h) {
             h->p_pending = true;
         }
     }
-    h->pending_mask = (h->fused_ok && h->z_ready) ? 0 : 1;  // a fused pass' q was already summed with its residuals
-    h->z_ready = false;  // consumed: q (and zz) now belong to the iteration in flight
-    if (h->phase_timing) RBL_HIP(hipEventRecord(h->ev[2], h->stream));
-    return RBL_OK;
+    return q_epilogue(h, q_ahead);
 }
 
 // the single-sweep iteration's statistics kernel (launch_predict_rho) knows the two norms only: the weighted sums
@@ -599,7 +597,9 @@ int rbl_phase_dual(rbl_solver* h, int want_objective) {
         h->fused_ran = true;
         h->v_valid = want_objective != 0;   // without objective logging the pass does not store v (ensure_v recomputes it if a misprediction asks)
         if (h->phase_timing) RBL_HIP(hipEventRecord(h->ev[4], h->stream));
-    } else if (h->fuse_v) {
+        return dual_epilogue(h, want_objective, true);
+    }
+    if (h->fuse_v) {
         // v = D w and the lambda update in one pass (timed as the gemv of the iteration)
         if (prof_now(h)) RBL_HIP(hipEventRecord(h->kev[0], h->stream));
         RBL_TRY(launch_sweep_v(h->storage, h->D, h->n, h->ld, h->w, h->z, h->lam, h->v, h->step_rho, h->partials, h->red,
@@ -608,16 +608,15 @@ int rbl_phase_dual(rbl_solver* h, int want_objective) {
         h->v_valid = true;
         h->fused_v_ran = true;
         if (h->phase_timing) RBL_HIP(hipEventRecord(h->ev[4], h->stream));
-    } else {
-        if (prof_now(h)) RBL_HIP(hipEventRecord(h->kev[0], h->stream));
-        RBL_TRY(launch_gemv(h->storage, h->D, h->n, h->ld, h->w, h->v, h->num_cu, h->stream));
-        if (prof_now(h)) {
-            RBL_HIP(hipEventRecord(h->kev[1], h->stream));
-            h->kev_pending[0] = true;
-        }
-        return dual_after_v(h, want_objective);
+        return dual_epilogue(h, want_objective, false);
     }
-    return dual_epilogue(h, want_objective);
+    if (prof_now(h)) RBL_HIP(hipEventRecord(h->kev[0], h->stream));
+    RBL_TRY(launch_gemv(h->storage, h->D, h->n, h->ld, h->w, h->v, h->num_cu, h->stream));
+    if (prof_now(h)) {
+        RBL_HIP(hipEventRecord(h->kev[1], h->stream));
+        h->kev_pending[0] = true;
+    }
+    return dual_after_v(h, want_objective);
 }
 
 // One thread gathers the iteration's scalars into the pinned host block: the host then needs a
@@ -660,10 +659,8 @@ int phase_finish_part(rbl_solver* h, rbl_stats* out, int part) {
     if (h->spec_timed) (void)hipEventElapsedTime(&spec_ms, h->ev_spec[0], h->ev_spec[1]);
     h->spec_timed = false;
     if (h->phase_timing && part != FIN_DIGEST) RBL_HIP(hipEventRecord(h->ev[5], h->stream));
-    volatile int* seq_word = reinterpret_cast<volatile int*>(h->hstat + 15);
-    const int pack_seq = (int)((h->iter & 0x3fffffff) + 1);
     if (part != FIN_DIGEST) {
-        *seq_word = 0;
+        const int pack_seq = h->fin.arm();
         hipLaunchKernelGGL(k_pack_stats, dim3(1), dim3(64), 0, h->stream, h->red, h->red2,
                            h->fused_ran ? h->pred : (const double*)nullptr,
                            (h->sorted_path && h->cfg.weight_function == RBL_W_EHRM) ? h->pw.branch : (const int*)nullptr,
@@ -691,12 +688,7 @@ int phase_finish_part(rbl_solver* h, rbl_stats* out, int part) {
         RBL_TRY(pen_terms_after_predict(h));
         if (h->phase_timing) RBL_HIP(hipEventRecord(h->ev_spec[1], h->stream));
     }
-    if (part == FIN_ALL) rbl_spin_wait(seq_word, 0, h->stream);
-    if (*seq_word != pack_seq) {
-        rbl_set_error("phase_finish: the statistics kernel did not complete");
-        (void)hipGetLastError();
-        return RBL_ERR_HIP;
-    }
+    RBL_TRY(part == FIN_ALL ? h->fin.wait(h->stream, FIN_NEVER) : h->fin.check(FIN_NEVER));   // FIN_DIGEST: the group has waited
     const volatile double* hs = h->hstat;
     const double r[2] = {hs[0], hs[1]}, r2[3] = {hs[2], hs[3], hs[4]}, pr[2] = {hs[5], hs[6]};
     const int br = (int)hs[7];
@@ -923,9 +915,9 @@ int rbl_accuracy(rbl_solver* h, const double* w, double threshold, double* out) 
 // why the last sort-free z-step was (not) certified: the pinned status word stays as written until the next one is launched
 int rbl_zband_status(rbl_solver* h, int* status, int* split) {
     RBL_ENTER(h);
-    const bool have = h->zb.pin && h->zb.seq > 0 && h->zb.pin[0] == h->zb.seq;
-    if (status) *status = have ? h->zb.pin[1] : -1;
-    if (split) *split = have ? h->zb.pin[2] : -1;
+    const bool have = h->zb.v.pin && h->zb.v.seq > 0 && h->zb.v.there();
+    if (status) *status = have ? h->zb.v.word(1) : -1;
+    if (split) *split = have ? h->zb.v.word(2) : -1;
     return RBL_OK;
 }
 

@@ -450,6 +450,77 @@ def test_admmgroup_matches_separate_solvers(R):
     grp.close()
 
 
+# ------------------------------------------------- 8. an uncertified z-step of a member behind the shared passes
+# path -> (family of both members, the m the fast path must refuse, environment read at each handle's first z-step)
+UNCERTIFIED = {
+    "banded": ("superq_0.5", "all_equal", {"RBL_NO_ZBAND": "0", "RBL_NO_SORT32": "0", "RBL_ZBAND_MIN_N": "16"}),
+    "sort32": ("extremile", "two_values", {"RBL_NO_ZBAND": "1", "RBL_NO_SORT32": "0"}),
+}
+
+
+@pytest.mark.parametrize("path,storage", [("banded", "f32"), ("sort32", "f32"), ("banded", "csr")])
+def test_uncertified_z_step_of_a_member_behind_shared_passes(R, monkeypatch, path, storage):
+    """Two rank-weighted members on one X with a prescribed m each (tests/zstep_inject.py: set_state(w = 0,
+    lam = -rho m0, rho = 2^-4, iter = 200)): member A's m is benign, member B's is one its fast z-step cannot certify
+    (keys tied across the band edge; a run of equal 32-bit keys).  B's q came out of the shared Q pass; its rbl_phase_w
+    settles the verdict and redoes z and q for B alone.  Each member's z equals, bit for bit, the z of a handle of its
+    own with the same state after rbl_step; the shared passes ran once each; B cost one n x d launch more than A.
+    132 columns: the narrowest width the dense multi-column passes take; storage="csr": the opt-in sparse ones."""
+    import torch
+    import zstep_inject as Z
+    fam, bad, env = UNCERTIFIED[path]
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    n, d, rho, it = 4096, 132, 2.0 ** -4, 200
+    wf, args, B, _, _ = Z.family(fam, n)
+    X, y = Z.make_problem(n, d)
+    if storage == "csr":
+        X = torch.from_numpy(X).to_sparse_csr()          # every entry stored
+    m0 = [Z.pattern("gaussian", n, 2, fam), Z.pattern(bad, n, 1, fam)]
+
+    def handle(share=None):
+        s = R.Solver(n, d, wf, Z.BCE, reg=0.01, wstep=2, args=args, B=B, tol=0.0, storage=storage, share=share)
+        if share is None:
+            s.set_data(X, y)
+            s.gram()
+        return s
+
+    def inject(s, m):
+        s.set_state(w=np.zeros(d), lam=-rho * m, rho=rho, iter=it)
+
+    members = [handle()]
+    members.append(handle(share=members[0]))
+    g = R._solver.Group(members, share_sparse=storage == "csr")
+    for s, m in zip(members, m0):
+        inject(s, m)
+    c0 = g.counters()
+    a, b = g.step(False)
+    c1 = g.counters()
+    zg = [s.get_state(want_lam=False)["z"].copy() for s in members]
+    print(f"{path} {storage}: k_per_pass={c0['k_per_pass']} A zband={a.zband} passes={a.sort_passes} "
+          f"B zband={b.zband} passes={b.sort_passes} counters {c0} -> {c1}")
+    assert c0["k_per_pass"] >= 2 and (storage != "csr" or c0["k_per_pass"] == 4), c0     # the shared passes are on
+    if path == "banded":
+        assert (a.zband, b.zband) == (1, 2), (a.zband, b.zband)
+    else:
+        assert (a.zband, a.sort_passes, b.zband, b.sort_passes) == (0, 4, 0, 12), (a.sort_passes, b.sort_passes)
+    assert c1["shared_q"] - c0["shared_q"] == 1 and c1["shared_v"] - c0["shared_v"] == 1, (c0, c1)
+    own = [c1["single_passes"][k] - c0["single_passes"][k] for k in (0, 1)]
+    assert own[1] == own[0] + 1, own                      # the q redone for B alone
+    # the group's handles stay alive beside the standalone ones: the same form of the w-step on both sides
+    for k, m in enumerate(m0):
+        s = handle()
+        inject(s, m)
+        st = s.step(False)
+        z = s.get_state(want_lam=False)["z"]
+        s.close()
+        assert (st.zband, st.sort_passes) == ((a, b)[k].zband, (a, b)[k].sort_passes), k
+        assert np.array_equal(zg[k].view(np.uint64), z.view(np.uint64)), (path, storage, k, float(np.max(np.abs(zg[k] - z))))
+    g.close()
+    for s in members:
+        s.close()
+
+
 def test_run_group_example():
     env = dict(os.environ, RBL_EXAMPLE_FAST="1")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "examples", "run_group.py")], capture_output=True, text=True,
