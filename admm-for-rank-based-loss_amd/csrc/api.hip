@@ -315,6 +315,7 @@ static int create_setup(rbl_solver* h, rbl_solver* owner = nullptr) {
     if (owner) {
         h->shared = owner->shared;
         h->gram_rep = owner->gram_rep;
+        h->sd = owner->sd;
         h->borrower = true;
         h->D = owner->D;
         h->G = owner->G;
@@ -323,6 +324,7 @@ static int create_setup(rbl_solver* h, rbl_solver* owner = nullptr) {
     } else {
         h->shared = std::make_shared<DevArena>();
         h->gram_rep = std::make_shared<rbl_gram_report>();
+        h->sd = std::make_shared<SharedData>();
         const size_t dbytes = (size_t)(n > 0 ? n : 1) * ld * h->esz;
         if (h->storage == RBL_STORE_CSR) {
             // no n x ld matrix: D is the descriptor (stable - borrowers copy the pointer; read by the host alone, it only
@@ -404,14 +406,10 @@ static int create_setup(rbl_solver* h, rbl_solver* owner = nullptr) {
         h->smooth_t = cfg->smooth_t > 0.0 ? cfg->smooth_t : 1.0;
     }
     if (owner) {
-        // everything rbl_gram_finish derives from G alone
-        h->L = owner->L;
-        h->ww.eig_Vt = owner->ww.eig_Vt;
-        h->ww.eig_V = owner->ww.eig_V;
-        h->ww.eig_lambda = owner->ww.eig_lambda;
-        h->ww.eig_ok = owner->ww.eig_ok;
-        h->eig_sweeps = owner->eig_sweeps;
-        h->data_ready = h->gram_local_done = h->gram_ready = true;
+        h->data_ready = true;
+        RBL_TRY(sync_data_epoch(h));   // a new handle is behind every epoch: it takes what the owner derived from G alone
+    } else {
+        h->epoch = h->sd->epoch;
     }
     RBL_HIP(hipStreamSynchronize(h->stream));
     return RBL_OK;
@@ -443,7 +441,7 @@ int rbl_create_shared(const rbl_config* cfg, rbl_solver* owner, rbl_solver** out
         rbl_set_error("create_shared: the owner has no data yet (rbl_set_data / rbl_generate_synthetic first)");
         return RBL_ERR_STATE;
     }
-    if (!cfg->objective_only && (!owner->gram_ready || !owner->G)) {
+    if (!cfg->objective_only && (!owner->der.gram_ready || !owner->G)) {
         rbl_set_error("create_shared: the owner's Gram matrix is not ready (rbl_gram_local + rbl_gram_finish first)");
         return RBL_ERR_STATE;
     }
@@ -529,21 +527,19 @@ int rbl_set_state(rbl_solver* h, const double* w, const double* z, const double*
     RBL_HIP(hipStreamSynchronize(h->stream));
     if (w) {
         RBL_HIP(hipMemcpy(h->w, w, sizeof(double) * h->d, hipMemcpyHostToDevice));
-        h->v_valid = false;
-        h->z_ready = false;
+        w_changed(h->der);
     }
     if (z && h->z) {
         RBL_TRY(upload_rows(h, h->z, z));
-        h->z_ready = false;
+        z_replaced(h->der);
     }
     if (lam && h->lam) {
         RBL_TRY(upload_rows(h, h->lam, lam));
-        h->z_ready = false;
-        h->p_valid = h->p_pending = false;
+        lambda_changed(h->der);
     }
     if (rho) {
         h->rho = *rho;
-        h->z_ready = false;
+        rho_changed(h->der);
     }
     if (iter) h->iter = *iter;
     if (smooth_t) h->smooth_t = *smooth_t;

@@ -441,9 +441,8 @@ static int set_data_csr_sparse(rbl_solver* h, const double* y, int64_t ds, int o
         for (int64_t i = 0; i < n; ++i) ys[(size_t)i] = y[i] > 0 ? 1 : -1;
         RBL_HIP(hipMemcpy(h->ysign, ys.data(), (size_t)n, hipMemcpyHostToDevice));
     }
-    // nothing reads the entry buffers while they are regrown: this handle's stream, and with borrowers (each on a stream
-    // of its own) the whole device.  A borrower's slab follows the new segment count at its next q pass (api_iter.hip)
-    if (h->shared.use_count() > 1) RBL_HIP(hipDeviceSynchronize());
+    // nothing reads the entry buffers while they are regrown (data_write_begins has waited for the borrowers).  A borrower's
+    // slab follows the new segment count at its next q pass (api_iter.hip)
     RBL_HIP(hipStreamSynchronize(h->stream));
     const bool columns = !h->cfg.objective_only;
     RBL_TRY(csr_store_reserve(*h->shared, st, n, ld, cs->nnz + (ones ? n : 0), columns));
@@ -489,6 +488,26 @@ static int set_data_csr_sparse(rbl_solver* h, const double* y, int64_t ds, int o
     RBL_TRY(csr_verdict(*cs));
     RBL_TRY(csr_store_finish(st, ld, columns, h->num_cu, h->stream));
     return RBL_OK;   // (the slab of the q pass follows the segment count where the pass is launched: api_iter.hip)
+}
+
+// In front of every write to D or the labels beside it: the data epoch moves, so that whoever holds something computed
+// from the old D - this handle, its borrowers - drops it (sync_data_epoch), whether the write completes or not.  With
+// borrowers, each on a stream of its own, the whole device is waited for: no pass of theirs still streams what is
+// overwritten (dense storage) or freed and regrown (sparse storage).  A handle on its own never pays that wait.
+static int data_write_begins(rbl_solver* h) {
+    h->sd->epoch += 1;
+    h->sd->complete = false;
+    if (h->shared.use_count() > 1) RBL_HIP(hipDeviceSynchronize());
+    return RBL_OK;
+}
+
+// ... and behind it, once D stands
+static int data_written(rbl_solver* h) {
+    h->data_ready = true;
+    h->sd->complete = true;
+    data_changed(h->der);
+    h->epoch = h->sd->epoch;
+    return RBL_OK;
 }
 
 // what a handle with RBL_STORE_CSR takes no part in (`who`: the entry point): RBL_ERR_INVALID, the handle without data
@@ -572,12 +591,10 @@ int rbl_set_data_from(rbl_solver* h, const void* X, int dtype, int mem, int64_t 
         if (mem == RBL_MEM_DEVICE)
             RBL_TRY(src_check_device_range(X, ((size_t)(n - 1) * (size_t)ldx + (size_t)ds) * src_esz(dtype), h->cfg.device));
         h->data_ready = false;   // a failed upload leaves the handle without data
+        RBL_TRY(data_write_begins(h));
         RBL_TRY(set_data_from_impl(h, X, dtype, mem, ldx, y, scaling, ds));
     }
-    h->data_ready = true;
-    h->gram_ready = h->gram_local_done = false;
-    h->v_valid = false;
-    return RBL_OK;
+    return data_written(h);
 }
 
 int rbl_set_data_csr(rbl_solver* h, const void* indptr, const void* indices, const void* values, int64_t nnz, int index_type,
@@ -658,13 +675,11 @@ int rbl_set_data_csr(rbl_solver* h, const void* indptr, const void* indices, con
     v.ip = ip.data();
     if (n > 0) {
         h->data_ready = false;   // a failed upload leaves the handle without data
+        RBL_TRY(data_write_begins(h));
         if (h->storage == RBL_STORE_CSR) RBL_TRY(set_data_csr_sparse(h, y, ds, (flags & RBL_DATA_ONES_COLUMN) ? 1 : 0, &v));
         else RBL_TRY(set_data_from_impl(h, nullptr, dtype, mem, 0, y, scaling, ds, &v));
     }
-    h->data_ready = true;
-    h->gram_ready = h->gram_local_done = false;
-    h->v_valid = false;
-    return RBL_OK;
+    return data_written(h);
 }
 
 // the float64 host route is the typed one (include/rbl.h)
@@ -741,6 +756,7 @@ int rbl_synth_local(rbl_solver* h, uint64_t seed, double class_sep, double flip_
         const int j = (int)(next() % (uint32_t)(i + 1));
         std::swap(vertex[i], vertex[j]);
     }
+    RBL_TRY(data_write_begins(h));   // (the labels now; D here or, fp16 storage, in rbl_synth_finish)
     if (h->storage == RBL_STORE_F16) {
         // the statistics of the unrounded draws; the matrix itself is written by rbl_synth_finish, in one rounding
         h->synth.pending = true;
@@ -798,10 +814,7 @@ int rbl_synth_finish(rbl_solver* h) {
                                         h->ysign, h->stream));
     }
     RBL_HIP(hipStreamSynchronize(h->stream));
-    h->data_ready = true;
-    h->gram_ready = h->gram_local_done = false;
-    h->v_valid = false;
-    return RBL_OK;
+    return data_written(h);
 }
 
 int rbl_generate_synthetic(rbl_solver* h, uint64_t seed, double class_sep, double flip_y) {
@@ -936,9 +949,9 @@ int rbl_set_labels(rbl_solver* h, const double* y) {
         RBL_TRY(upload_rows(h, h->z, zh.data()));
         RBL_TRY(upload_rows(h, h->lam, lh.data()));
     }
+    labels_changed(h->der);
     if (!h->cfg.objective_only) h->fused_ok = single_sweep_allowed(h);   // (not with labels of its own)
-    drop_look_ahead(h);
-    h->keys_ready = h->s32.m_ready = false;
+    drop_look_ahead(h->der);
     return RBL_OK;
 }
 
@@ -987,7 +1000,7 @@ int rbl_set_row_weights(rbl_solver* h, const double* c) {
         RBL_HIP(hipMemcpy(h->sigw, sg.data(), sizeof(double) * n, hipMemcpyHostToDevice));
     }
     // whatever was computed ahead with the old weights is void: the next z-step runs with the new ones
-    h->z_ready = h->pred_valid = false;
+    row_weights_changed(h->der);
     return RBL_OK;
 }
 
@@ -1004,6 +1017,7 @@ int rbl_get_row_weights(rbl_solver* h, double* c, int* is_set) {
 // over D, each followed by the row-wise comparison against the best score so far.
 int rbl_decide_multi(rbl_solver* h, int k, const double* W, int32_t* cls) {
     RBL_ENTER(h);
+    RBL_TRY(sync_data_epoch(h));
     if (!h->data_ready) {
         rbl_set_error("decide_multi: no data");
         return RBL_ERR_STATE;
@@ -1093,8 +1107,7 @@ int rbl_gram_local(rbl_solver* h) {
     }
     RBL_HIP(hipStreamSynchronize(h->stream));
     *h->gram_rep = rep;
-    h->gram_local_done = true;
-    h->ww.eig_ok = false;
+    gram_formed(h->der);
     return RBL_OK;
 }
 
@@ -1113,32 +1126,34 @@ int rbl_csr_gram_route(int64_t n, int64_t ld, int64_t pair_products) { return cs
 int rbl_gram_finish(rbl_solver* h) {
     RBL_ENTER(h);
     RBL_NOT_BORROWER(h, "gram_finish");
-    if (!h->gram_local_done) {
+    if (!h->der.gram_local_done) {
         rbl_set_error("gram_finish before gram_local");
         return RBL_ERR_STATE;
     }
     double lam = 0.0;
     RBL_TRY(launch_power_iteration(h->G, h->ld, h->ww.yk, h->ww.Gy, h->ww.scal, 100, &lam, h->stream));
-    h->L = 1.02 * lam;
-    if (!(h->L > 0.0)) h->L = 1.0;
+    gram_changed(h->der);   // G is whole only now (a row shard's was summed over the ranks since rbl_gram_local)
+    SharedData& r = *h->sd;   // what comes from G alone goes into the shared record: the borrowers read it there
+    r.eig_ok = false;
+    r.L = 1.02 * lam;
+    if (!(r.L > 0.0)) r.L = 1.0;
     // l2 w-step: RBL_RIDGE_EIG=1 replaces the warm-started CG by a one-time eigendecomposition of G (eig.hip).
     // Opt-in: it makes an iteration 0.13 ms shorter at d = 1000 (14 CG iterations -> 5 small launches when measured, 8 now) but the
     // Jacobi sweeps cost 0.8 s of setup there - 6000 iterations to break even, and a solve runs a few hundred
-    h->ww.eig_ok = false;
     static const bool ridge_eig = [] {
         const char* e = getenv("RBL_RIDGE_EIG");
         return e && e[0] == '1';
     }();
     if (h->cfg.wstep == RBL_WSTEP_L2 && h->ld <= 2048 && ridge_eig) {
         const size_t nn = (size_t)h->ld * (size_t)h->ld;
-        if (!h->ww.eig_Vt) {
+        if (!r.eig_Vt) {
             double *Vt = nullptr, *V = nullptr, *lambda = nullptr;
             RBL_TRY(h->shared->alloc(&Vt, nn));   // derived from G alone: shared with the borrowers
             RBL_TRY(h->shared->alloc(&V, nn));
             RBL_TRY(h->shared->alloc(&lambda, (size_t)h->ld));
-            h->ww.eig_V = V;
-            h->ww.eig_lambda = lambda;
-            h->ww.eig_Vt = Vt;   // set last: it says the basis buffers are there
+            r.eig_V = V;
+            r.eig_lambda = lambda;
+            r.eig_Vt = Vt;   // set last: it says the basis buffers are there
         }
         int rc = RBL_OK, sweeps = 0;
         {
@@ -1147,19 +1162,20 @@ int rbl_gram_finish(rbl_solver* h) {
             unsigned long long* off = nullptr;
             RBL_TRY(tmp.alloc(&Bt, nn));
             RBL_TRY(tmp.alloc(&off, 1));
-            rc = launch_eig_jacobi(h->G, h->ld, h->d, Bt, h->ww.eig_Vt, h->ww.eig_V, h->ww.eig_lambda, off, h->stream, &sweeps);
+            rc = launch_eig_jacobi(h->G, h->ld, h->d, Bt, r.eig_Vt, r.eig_V, r.eig_lambda, off, h->stream, &sweeps);
             (void)hipStreamSynchronize(h->stream);
         }
         RBL_TRY(rc);
-        h->ww.eig_ok = sweeps > 0;
-        h->eig_sweeps = sweeps;
+        r.eig_ok = sweeps > 0;
+        r.eig_sweeps = sweeps;
     }
-    h->gram_ready = true;
+    take_gram(h);
     return RBL_OK;
 }
 
 int rbl_get_D(rbl_solver* h, double* out) {
     RBL_ENTER(h);
+    RBL_TRY(sync_data_epoch(h));
     if (!h->data_ready) {
         rbl_set_error("get_D: no data");
         return RBL_ERR_STATE;

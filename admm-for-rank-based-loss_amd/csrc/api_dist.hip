@@ -46,11 +46,11 @@ int rbl_zd_sort_local(rbl_solver* h, int nsamples) {
     }
     hipStream_t s = h->stream;
     // keys of the local m, payload = GLOBAL row id
-    if (!h->keys_ready) {
+    if (!h->der.keys_ready) {
         RBL_TRY(launch_keys_from_m(h->n, h->m, h->sw.keys[0], h->sw.vals[0], s));
         if (h->off != 0) RBL_TRY(launch_add_u32(h->n, h->sw.vals[0], (u32)h->off, s));
     }
-    h->keys_ready = false;
+    h->der.keys_ready = false;
     RBL_TRY(launch_radix_sort(h->sw, h->n, true, s));
     RBL_TRY(launch_zd_sample(h->sw.keys[0], h->n, nsamples, h->zd_small + ZD_OFF_SAMPLES, s));
     return RBL_OK;
@@ -67,7 +67,7 @@ int rbl_zd_sort_losses(rbl_solver* h, int nsamples) {
     }
     hipStream_t s = h->stream;
     RBL_TRY(ensure_v(h));
-    h->keys_ready = false;
+    h->der.keys_ready = false;
     RBL_TRY(launch_loss_keys(h->n, h->v, h->sw.keys[0], s));
     RBL_TRY(launch_radix_sort(h->sw, h->n, false, s));
     RBL_TRY(launch_zd_sample(h->sw.keys[0], h->n, nsamples, h->zd_small + ZD_OFF_SAMPLES, s));
@@ -252,7 +252,7 @@ int rbl_zd_scatter(rbl_solver* h, int64_t n_back) {
 
 // ---- sort-free z-step for banded rank weights, sharded rows (zband.hip step by step; the driver sums / gathers in between)
 static int zbd_ready(rbl_solver* h) {
-    if (!h->zb.enabled || !h->keys_ready) {
+    if (!h->zb.enabled || !h->der.keys_ready) {
         rbl_set_error("rbl_zbd_*: call rbl_phase_m and rbl_zbd_begin (applicable) first");
         return RBL_ERR_STATE;
     }
@@ -266,7 +266,7 @@ int rbl_zbd_begin(rbl_solver* h, int* applicable, int* root_clusters) {
     if (!h->zb.checked) RBL_TRY(zb_setup(h));
     h->zb.mode = 0;
     // iteration 0 (every m equal) and the pause after an uncertified z-step: the caller takes the sort path
-    if (!(h->zb.enabled && h->keys_ready && h->iter > 0 && h->iter >= h->zb.skip_until)) return RBL_OK;
+    if (!(h->zb.enabled && h->der.keys_ready && h->iter > 0 && h->iter >= h->zb.skip_until)) return RBL_OK;
     RBL_TRY(launch_zbd_init(h->zb.cfg, h->zb.st, h->zb.hist, h->stream));
     if (applicable) *applicable = 1;
     if (root_clusters) {
@@ -327,9 +327,9 @@ int rbl_zbd_apply(rbl_solver* h, int* status) {
     if (status) *status = h->zb.v.word(1);
     if (h->zb.v.word(1) == ZB_OK) {
         h->zb.backoff = 0;
-        h->zb.c_ready = true;
+        h->der.zb_c_ready = true;
         h->zb.mode = 1;
-        h->keys_ready = false;
+        h->der.keys_ready = false;
         if (h->phase_timing) RBL_HIP(hipEventRecord(h->ev[1], h->stream));
     } else {
         zb_back_off(h);   // mode 2: the caller runs the sort-based distributed z-step (rbl_zd_*) for this iteration

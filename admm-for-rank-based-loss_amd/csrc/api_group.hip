@@ -111,7 +111,7 @@ int rbl_group_create_opts(rbl_solver* const* members, int k, int flags, rbl_grou
         h->stream = g->stream;
         // two-pass structure for every member: whatever a single-sweep erm pass prepared ahead is dropped
         h->fused_ok = false;
-        drop_look_ahead(h);
+        drop_look_ahead(h->der);
     }
     *out = g.release();
     return RBL_OK;
@@ -239,7 +239,7 @@ int rbl_group_step(rbl_group* g, int want_objective, rbl_stats* out) {
         for (int i : idx) {
             rbl_solver* h = g->m[i];
             h->fused_ran = false;
-            h->fused_v_ran = h->v_valid = true;
+            h->fused_v_ran = h->der.v_valid = true;
             if (h->phase_timing) RBL_HIP(hipEventRecord(h->ev[4], s));
             RBL_TRY(dual_epilogue(h, want_objective, false));   // the pass carries no loss sum
         }

@@ -22,10 +22,10 @@ static int gemvt_h(rbl_solver* h, const double* c, double* q, hipEvent_t main_do
 }
 
 int ensure_v(rbl_solver* h) {
-    if (h->v_valid) return RBL_OK;
+    if (h->der.v_valid) return RBL_OK;
     h->nd_launches += 1;
     RBL_TRY(launch_gemv(h->storage, h->D, h->n, h->ld, h->w, h->v, h->num_cu, h->stream));
-    h->v_valid = true;
+    h->der.v_valid = true;
     return RBL_OK;
 }
 
@@ -40,14 +40,14 @@ static __global__ void k_publish_flag(const int* __restrict__ flag, int* __restr
 }
 
 // Sorted-path z-step over the n_total values in msrc (device), writing the local slice.
-// allow32: the 32-bit-key sort may be used when rbl_phase_m prepared it (h->s32.m_ready) - its verdict is settled later
+// allow32: the 32-bit-key sort may be used when rbl_phase_m prepared it (h->der.s32_m_ready) - its verdict is settled later
 // (zb_resolve); false: 64-bit keys (the redo of an uncertified step, gathered m of the replicated distributed form).
 int z_step_sorted(rbl_solver* h, const double* msrc, double rho, bool allow32 = true) {
     hipStream_t s = h->stream;
     const int64_t nt = h->nt;
     const u32* perm = h->sw.vals[0];
-    const bool use32 = allow32 && h->s32.m_ready && msrc == h->m && nt == h->n;
-    h->s32.m_ready = false;
+    const bool use32 = allow32 && h->der.s32_m_ready && msrc == h->m && nt == h->n;
+    h->der.s32_m_ready = false;
     if (use32) {
         // fixed-point 32-bit keys of m: 4 radix passes over 8 bytes per row instead of 8 over 12, then one pass that gathers
         // the sorted m through the row ids and repairs the short runs the 32 bits cannot tell apart
@@ -58,19 +58,19 @@ int z_step_sorted(rbl_solver* h, const double* msrc, double rho, bool allow32 = 
         const int seq = h->s32.v.arm();
         hipLaunchKernelGGL(k_publish_flag, dim3(1), dim3(64), 0, s, (const int*)h->s32.flag, h->s32.v.pin, seq);
         RBL_HIP(hipGetLastError());
-        h->s32.used = true;
-        h->s32.q_done = false;
+        h->der.s32_used = true;
+        h->der.s32_q_done = false;
         RBL_TRY(launch_prefix(h->pw.ms, nt, h->pw.pm, s));
         perm = h->sw.vals[1];
         h->sort_passes += 4;
     } else {
         // rbl_phase_m already formed the keys with m when it covers the whole problem (one pass instead of two)
-        if (!(h->keys_ready && msrc == h->m && nt == h->n)) RBL_TRY(launch_keys_from_m(nt, msrc, h->sw.keys[0], h->sw.vals[0], s));
+        if (!(h->der.keys_ready && msrc == h->m && nt == h->n)) RBL_TRY(launch_keys_from_m(nt, msrc, h->sw.keys[0], h->sw.vals[0], s));
         RBL_TRY(launch_radix_sort(h->sw, nt, true, s));
         RBL_TRY(launch_unflip_prefix(h->sw.keys[0], nt, h->pw.ms, h->pw.pm, s));
         h->sort_passes += 8;
     }
-    h->keys_ready = false;   // the sort consumes its input
+    h->der.keys_ready = false;   // the sort consumes its input
     const bool ehrm = h->cfg.weight_function == RBL_W_EHRM;
     // EHRM: the branch of the previous iteration is speculated and the exact test rides on the bottom kernel
     // (pav.hip: k_pav_bottom<0, true>).  RBL_EHRM_SPEC=0 / 1: the first speculation (tests force a wrong one);
@@ -197,7 +197,7 @@ int risk_from_v(rbl_solver* h, const double* v_all, double* out_dev) {
         h->risk_path = 1;
         return launch_loss_sum(h->cfg.loss, h->nt, v_all, 1.0 / (double)h->nt, h->partials, out_dev, s, h->rs, h->cw);
     }
-    h->keys_ready = false;   // the sort workspace is reused: keys left by rbl_phase_m are gone
+    h->der.keys_ready = false;   // the sort workspace is reused: keys left by rbl_phase_m are gone
     RBL_TRY(launch_loss_keys(h->nt, v_all, h->sw.keys[0], s, h->rs));   // (own labels: the losses are taken at r * v)
     // piecewise-constant weights: the band sums of the losses need a select, not a sort (zband.hip; exact for any v)
     if (h->zb.enabled) {
@@ -225,25 +225,25 @@ void zb_back_off(rbl_solver* h) {
 int zb_resolve(rbl_solver* h, bool* redone) {
     if (redone) *redone = false;
     bool q_done = false;
-    if (h->s32.used) {
+    if (h->der.s32_used) {
         // a run of equal keys too long for the fix-up (many m within range / 2^32 of each other: ties on a grid, a
         // degenerate range)
-        h->s32.used = false;
+        h->der.s32_used = false;
         RBL_TRY(h->s32.v.settle(h->stream, "z-step: the verdict of the 32-bit sort was never written"));
         if (h->s32.v.word(1) == 0) return RBL_OK;
         h->s32.skip_until = h->iter + 1 + 64;
-        q_done = h->s32.q_done;
-        h->s32.q_done = false;
-    } else if (h->zb.used) {
-        h->zb.used = false;
+        q_done = h->der.s32_q_done;
+        h->der.s32_q_done = false;
+    } else if (h->der.zb_used) {
+        h->der.zb_used = false;
         RBL_TRY(h->zb.v.settle(h->stream, "banded z-step: its status word was never written"));
         if (h->zb.v.word(1) == ZB_OK) {
             h->zb.backoff = 0;
             return RBL_OK;
         }
         zb_back_off(h);
-        q_done = h->zb.q_done;
-        h->zb.c_ready = h->zb.q_done = false;
+        q_done = h->der.zb_q_done;
+        h->der.zb_c_ready = h->der.zb_q_done = false;
     } else {
         return RBL_OK;
     }
@@ -268,17 +268,43 @@ int cancel_spec(rbl_solver* h) {
     return RBL_OK;
 }
 
+// L and the eigenbasis of G as rbl_gram_finish left them in the shared record: the owner behind its own rbl_gram_finish, a
+// borrower whenever it catches up with the data epoch - it has no Gram calls of its own and takes the owner's word for G
+void take_gram(rbl_solver* h) {
+    const SharedData& r = *h->sd;
+    h->L = r.L;
+    h->ww.eig_Vt = r.eig_Vt;
+    h->ww.eig_V = r.eig_V;
+    h->ww.eig_lambda = r.eig_lambda;
+    h->eig_sweeps = r.eig_sweeps;
+    gram_finished(h->der, r.eig_ok);
+}
+
+// The owner has written a new D since this handle last looked: whatever the handle computed from the old D falls, a w-step
+// enqueued ahead of time with it.  Run where a handle is about to iterate (require_ready) and by the evaluations that
+// read D.  While a write has begun and not completed - it failed half way - the handle stays as it is: there is no D to
+// compute anything from, and the call goes on to the refusals it met before (data_ready, the sparse launchers' guards).
+int sync_data_epoch(rbl_solver* h) {
+    if (h->epoch == h->sd->epoch || !h->sd->complete) return RBL_OK;
+    RBL_TRY(cancel_spec(h));
+    data_changed(h->der);
+    h->epoch = h->sd->epoch;
+    if (h->borrower) take_gram(h);
+    return RBL_OK;
+}
+
 // ------------------------------------------------------------------------------- phases
 int require_ready(rbl_solver* h) {
     if (h->cfg.objective_only) {
         rbl_set_error("objective-only handle cannot step");
         return RBL_ERR_STATE;
     }
+    RBL_TRY(sync_data_epoch(h));
     if (!h->data_ready) {
         rbl_set_error("step before set_data / generate_synthetic");
         return RBL_ERR_STATE;
     }
-    if (!h->gram_ready) {
+    if (!h->der.gram_ready) {
         if (h->nt != h->n) {
             rbl_set_error("sharded problem: call rbl_gram_local, sum RBL_BUF_G over ranks, rbl_gram_finish first");
             return RBL_ERR_STATE;
@@ -321,7 +347,7 @@ int dual_epilogue(rbl_solver* h, int want_objective, bool own_loss_in_red) {
 // group's shared sparse pass (api_group.hip): lambda += rho (z - v) with the residual, then the epilogue.  The caller
 // has cleared fused_ran / fused_v_ran.
 int dual_after_v(rbl_solver* h, int want_objective) {
-    h->v_valid = true;
+    h->der.v_valid = true;
     if (h->phase_timing) RBL_HIP(hipEventRecord(h->ev[4], h->stream));
     RBL_TRY(launch_dual(h->cfg.loss, h->n, h->step_rho, h->z, h->v, h->lam, h->partials, h->red, h->stream));
     return dual_epilogue(h, want_objective, !(h->rs || h->cw));
@@ -332,16 +358,16 @@ int dual_after_v(rbl_solver* h, int want_objective) {
 // (Forming it inside the sweep was tried: the per-row division on the sweep's critical path costs 0.9 ms, the streaming
 // pass 30 us.)  The q of an unsettled fast z-step is owed a redo with it (zb_resolve).
 int q_prologue(rbl_solver* h) {
-    if (h->sorted_path && !h->zb.c_ready) RBL_TRY(launch_make_c(h->n, h->z, h->lam, h->step_rho, h->c, h->stream));
-    h->zb.c_ready = false;
-    h->zb.q_done = h->zb.used;
-    h->s32.q_done = h->s32.used;
+    if (h->sorted_path && !h->der.zb_c_ready) RBL_TRY(launch_make_c(h->n, h->z, h->lam, h->step_rho, h->c, h->stream));
+    h->der.zb_c_ready = false;
+    h->der.zb_q_done = h->der.zb_used;
+    h->der.s32_q_done = h->der.s32_used;
     return RBL_OK;
 }
 
 int q_epilogue(rbl_solver* h, bool q_ahead) {
     h->pending_mask = q_ahead ? 0 : 1;  // a fused pass' q was already summed with its residuals
-    h->z_ready = false;  // consumed: q (and zz) now belong to the iteration in flight
+    h->der.z_ready = false;  // consumed: q (and zz) now belong to the iteration in flight
     if (h->phase_timing) RBL_HIP(hipEventRecord(h->ev[2], h->stream));
     return RBL_OK;
 }
@@ -353,7 +379,7 @@ int rbl_phase_m(rbl_solver* h) {
     RBL_TRY(require_ready(h));
     h->step_rho = h->rho;
     if (h->phase_timing) RBL_HIP(hipEventRecord(h->ev[0], h->stream));
-    if (h->fused_ok && h->z_ready) return RBL_OK;
+    if (h->fused_ok && h->der.z_ready) return RBL_OK;
     RBL_TRY(ensure_v(h));
     if (h->sorted_path) {
         if (!h->zb.checked) RBL_TRY(zb_setup(h));
@@ -362,18 +388,18 @@ int rbl_phase_m(rbl_solver* h) {
         const bool banded_next = h->zb.enabled && h->nt == h->n && h->iter > 0 && h->iter >= h->zb.skip_until;
         const bool s32 = h->s32.v.pin && !h->s32.off && h->nt == h->n && h->n >= 2 && h->iter > 0 &&
                          h->iter >= h->s32.skip_until && !banded_next;
-        h->s32.m_ready = false;
+        h->der.s32_m_ready = false;
         if (s32) {
             // m = D w - lambda/rho (algorithms.py:89) and its range (the 32-bit keys are a fixed-point image on it)
             RBL_TRY(launch_make_m_range(h->n, h->step_rho, h->v, h->lam, h->m, h->s32.mm, h->stream, h->rs));
-            h->s32.m_ready = true;
-            h->keys_ready = false;
+            h->der.s32_m_ready = true;
+            h->der.keys_ready = false;
         } else {
             // m and, in the same pass, the 64-bit sort's input for the z-step: keys of m with the GLOBAL row id as
             // payload (single GPU: off = 0; sharded: what rbl_zd_sort_local sorts)
             RBL_TRY(launch_make_m_keys(h->n, h->step_rho, h->v, h->lam, h->m, h->sw.keys[0], h->sw.vals[0], (u32)h->off,
                                        h->stream, h->rs));
-            h->keys_ready = true;
+            h->der.keys_ready = true;
         }
     }
     return RBL_OK;
@@ -382,7 +408,7 @@ int rbl_phase_m(rbl_solver* h) {
 int rbl_phase_z(rbl_solver* h, const void* m_all_dev) {
     RBL_ENTER_ITER(h);
     const double rho = h->step_rho;
-    if (h->fused_ok && h->z_ready) {
+    if (h->fused_ok && h->der.z_ready) {
         std::swap(h->z, h->z_next);  // the z-step of this iteration was done by the previous pass
     } else if (!h->sorted_path) {
         RBL_TRY(launch_erm_zc(h->cfg.loss, h->n, h->sigma0, rho, h->v, h->lam, h->m, h->z, h->c, h->stream, h->rs, h->sigw));
@@ -399,16 +425,16 @@ int rbl_phase_z(rbl_solver* h, const void* m_all_dev) {
         if (!h->zb.checked) RBL_TRY(zb_setup(h));
         h->zb.mode = 0;
         // iteration 0 starts from w = 0, lambda = 0: every m is equal, the keys tie across every band edge
-        if (h->zb.enabled && h->nt == h->n && h->keys_ready && msrc == h->m && h->iter > 0 && h->iter >= h->zb.skip_until) {
+        if (h->zb.enabled && h->nt == h->n && h->der.keys_ready && msrc == h->m && h->iter > 0 && h->iter >= h->zb.skip_until) {
             const int seq = h->zb.v.arm();
             RBL_TRY(launch_zband(h->cfg.loss, h->zb.cfg, h->n, rho, h->sw.keys[0], h->m, h->z, h->lam, h->c, h->zb.st, h->zb.hist,
                                  h->zb.part, h->zb.v.pin, seq, h->pw.counters, h->stream, h->rs));
-            h->zb.used = true;
-            h->zb.q_done = false;
-            h->zb.c_ready = true;   // the element-wise pass wrote c = z + lambda/rho as well
+            h->der.zb_used = true;
+            h->der.zb_q_done = false;
+            h->der.zb_c_ready = true;   // the element-wise pass wrote c = z + lambda/rho as well
             h->zb.mode = 1;
         } else {
-            h->zb.c_ready = false;
+            h->der.zb_c_ready = false;
             RBL_TRY(z_step_sorted(h, msrc, rho));
         }
     }
@@ -433,10 +459,7 @@ int rbl_phase_z_external(rbl_solver* h, const double* z) {
     rbl_note_host_sync();
     // a z-step the previous single-sweep pass did ahead of time (z_next, q, ||z||^2) is void: the unfused kernels
     // rebuild q in rbl_phase_q; erm keeps c = z + lambda/rho and ||z||^2 next to z (launch_erm_zc), rebuild both
-    h->z_ready = false;
-    h->keys_ready = false;
-    h->zb.used = h->zb.c_ready = false;   // whatever the library's own z-step left behind is void
-    h->s32.used = h->s32.m_ready = false;
+    z_replaced(h->der);   // with whatever the library's own z-step left behind: c, a verdict still unread
     h->zb.mode = 0;
     if (!h->sorted_path) {
         RBL_TRY(launch_make_c(h->n, h->z, h->lam, h->step_rho, h->c, h->stream));
@@ -465,11 +488,10 @@ int rbl_phase_w_external(rbl_solver* h, const double* w) {
     RBL_TRY(launch_w_stats(h->ld, h->w, h->w_prev, h->red2, h->stream, h->ww.pen_l1, h->ww.pen_l2,
                            pen_terms(h)));   // dual residual, regulariser terms
     // no rho prediction was made for this w: the dual update runs unfused, and the d-space recurrence for
-    // D^T lambda is re-seeded by the next rbl_phase_q
-    h->pred_valid = false;
-    h->p_valid = h->p_pending = false;
-    h->z_ready = false;        // (a caller that skipped rbl_phase_q: nothing of a previous pass is pending any more)
-    h->v_valid = false;
+    // D^T lambda is re-seeded by the next rbl_phase_q (a caller that skipped rbl_phase_q: nothing of a previous pass is
+    // pending any more)
+    w_changed(h->der);
+    drop_look_ahead(h->der);
     h->inner_iters = 0;
     h->ww.form = -1;
     if (h->phase_timing) RBL_HIP(hipEventRecord(h->ev[3], h->stream));
@@ -478,18 +500,18 @@ int rbl_phase_w_external(rbl_solver* h, const double* w) {
 
 int rbl_phase_q(rbl_solver* h) {
     RBL_ENTER_ITER(h);
-    const bool q_ahead = h->fused_ok && h->z_ready;
+    const bool q_ahead = h->fused_ok && h->der.z_ready;
     if (!q_ahead) {
         if (prof_now(h)) RBL_HIP(hipEventRecord(h->kev[2], h->stream));
         RBL_TRY(q_prologue(h));
         RBL_TRY(gemvt_h(h, h->c, h->q, prof_now(h) ? h->kev[3] : nullptr));
         h->nd_launches += 1;
         if (prof_now(h)) h->kev_pending[1] = h->n > 0;
-        if (h->fused_ok && !h->p_valid) {
+        if (h->fused_ok && !h->der.p_valid) {
             // D^T lambda seeds the d-space recurrence used to predict the primal residual
             RBL_TRY(gemvt_h(h, h->lam, q_pinit(h)));
             h->nd_launches += 1;
-            h->p_pending = true;
+            h->der.p_pending = true;
         }
     }
     return q_epilogue(h, q_ahead);
@@ -508,21 +530,22 @@ static int phase_w_body(rbl_solver* h) {
     int wstep = h->cfg.wstep;
     if (!spec && wstep != RBL_WSTEP_L1)   // the lasso kernel saves its warm start itself
         RBL_HIP(hipMemcpyAsync(h->w_prev, h->w, sizeof(double) * h->ld, hipMemcpyDeviceToDevice, h->stream));
-    if (h->p_pending) {
+    if (h->der.p_pending) {
         RBL_HIP(hipMemcpyAsync(h->p, q_pinit(h), sizeof(double) * h->ld, hipMemcpyDeviceToDevice, h->stream));
-        h->p_pending = false;
-        h->p_valid = true;
+        h->der.p_pending = false;
+        h->der.p_valid = true;
     }
     // The lasso's active-set kernel reports its status through pinned memory; the statistics of
     // the new w and the rho prediction are enqueued behind it before the host looks at the
     // status, so the device works through them while the host waits.  Only when the kernel did
     // not converge (FISTA then changes w again) are they enqueued a second time.
     bool fs_pending = spec;
-    const bool predict = h->fused_ok && h->p_valid;
+    const bool predict = h->fused_ok && h->der.p_valid;
     // the active-set lasso kernel leaves G w of its solution in ww.Gy (it needs the gradient for its
     // own optimality test): no d x d product for the rho prediction unless FISTA had to take over
     bool gw_ready = predict && wstep == RBL_WSTEP_L1;
     if (!spec) {
+        h->ww.eig_ok = h->der.eig_ok;   // (run_wstep's view of it)
         RBL_TRY(run_wstep(wstep, h->G, h->ld, h->q, h->step_rho, h->cfg.reg, h->smooth_t, h->L, h->cfg.w_tol, 100000,
                           h->w, h->ww, &h->inner_iters, h->stream, &fs_pending, nullptr, h->w_prev, predict));
         // the persistent CG / nonlinear-CG kernels leave G w of their solution in ww.Gy as well
@@ -549,7 +572,7 @@ static int phase_w_body(rbl_solver* h) {
             RBL_TRY(after_w());
         }
     }
-    h->pred_valid = false;
+    h->der.pred_valid = false;
     if (predict) {
         std::swap(h->p, h->p_alt);   // the recurrence's output becomes D^T lambda of the next iteration
         // test hook: RBL_DEBUG_MISPREDICT_EVERY=N corrupts every N-th prediction so that the
@@ -563,7 +586,7 @@ static int phase_w_body(rbl_solver* h) {
             RBL_HIP(hipMemcpyAsync(h->pred, &wrong, sizeof(double), hipMemcpyHostToDevice, h->stream));
             RBL_HIP(hipStreamSynchronize(h->stream));
         }
-        h->pred_valid = true;
+        h->der.pred_valid = true;
     }
     if (h->phase_timing) RBL_HIP(hipEventRecord(h->ev[3], h->stream));
     return RBL_OK;
@@ -587,7 +610,7 @@ int rbl_phase_dual(rbl_solver* h, int want_objective) {
     h->fused_ran = false;
     h->fused_v_ran = false;
     h->nd_launches += 1;
-    if (h->fused_ok && h->pred_valid) {
+    if (h->fused_ok && h->der.pred_valid) {
         if (prof_now(h)) RBL_HIP(hipEventRecord(h->kev[4], h->stream));
         RBL_TRY(launch_sweep_erm(h->storage, h->cfg.loss, h->D, h->n, h->ld, h->w, h->z, h->lam, h->v, h->z_next,
                                  h->sigma0, h->step_rho, h->pred, h->slab, h->partials, h->q, h->red, q_zz(h),
@@ -595,7 +618,7 @@ int rbl_phase_dual(rbl_solver* h, int want_objective) {
                                  h->cw));
         if (prof_now(h)) h->kev_pending[2] = h->n > 0;
         h->fused_ran = true;
-        h->v_valid = want_objective != 0;   // without objective logging the pass does not store v (ensure_v recomputes it if a misprediction asks)
+        h->der.v_valid = want_objective != 0;   // without objective logging the pass does not store v (ensure_v recomputes it if a misprediction asks)
         if (h->phase_timing) RBL_HIP(hipEventRecord(h->ev[4], h->stream));
         return dual_epilogue(h, want_objective, true);
     }
@@ -605,7 +628,7 @@ int rbl_phase_dual(rbl_solver* h, int want_objective) {
         RBL_TRY(launch_sweep_v(h->storage, h->D, h->n, h->ld, h->w, h->z, h->lam, h->v, h->step_rho, h->partials, h->red,
                                h->num_cu, h->stream, prof_now(h) ? h->kev[1] : nullptr));
         if (prof_now(h)) h->kev_pending[0] = h->n > 0;
-        h->v_valid = true;
+        h->der.v_valid = true;
         h->fused_v_ran = true;
         if (h->phase_timing) RBL_HIP(hipEventRecord(h->ev[4], h->stream));
         return dual_epilogue(h, want_objective, false);
@@ -677,7 +700,7 @@ int phase_finish_part(rbl_solver* h, rbl_stats* out, int part) {
         const char* e = getenv("RBL_NO_SPECULATE");
         return e && e[0] == '1';
     }();
-    const bool try_spec = part == FIN_ALL && h->fused_ran && h->p_valid && h->cfg.wstep == RBL_WSTEP_L1 && !no_spec;
+    const bool try_spec = part == FIN_ALL && h->fused_ran && h->der.p_valid && h->cfg.wstep == RBL_WSTEP_L1 && !no_spec;
     if (try_spec) {
         if (h->phase_timing) RBL_HIP(hipEventRecord(h->ev_spec[0], h->stream));
         bool fs_pending = false;
@@ -735,14 +758,14 @@ int phase_finish_part(rbl_solver* h, rbl_stats* out, int part) {
         fused = 1;
         // the pass already did iteration i+1's z-step with the predicted rho: keep it only if the
         // exact residual leads to exactly that rho (same double arithmetic on both sides)
-        h->z_ready = !conv && pr[0] == rho_next;
-        if (!conv && !h->z_ready) mispred = 1;
+        h->der.z_ready = !conv && pr[0] == rho_next;
+        if (!conv && !h->der.z_ready) mispred = 1;
         h->n_fused += 1;
         h->n_mispred += mispred;
     }
-    h->pred_valid = false;
+    h->der.pred_valid = false;
     if (try_spec) {
-        if (!conv && h->z_ready) {
+        if (!conv && h->der.z_ready) {
             h->spec_w = true;
             h->spec_timed = h->phase_timing;
         } else {
@@ -847,7 +870,7 @@ int rbl_finalize_smooth(rbl_solver* h) {
     RBL_ENTER(h);
     if (h->cfg.wstep != RBL_WSTEP_SMOOTH_L1) return RBL_OK;
     RBL_TRY(launch_soft_threshold(h->ld, h->w, h->smooth_t, h->stream));
-    h->v_valid = false;
+    w_changed(h->der);
     RBL_HIP(hipStreamSynchronize(h->stream));
     return RBL_OK;
 }
@@ -860,6 +883,7 @@ static int predict_into_m(rbl_solver* h, const double* w) {
 
 int rbl_objective(rbl_solver* h, const double* w, int include_reg, double* out) {
     RBL_ENTER(h);
+    RBL_TRY(sync_data_epoch(h));
     if (!h->data_ready || !w || !out) {
         rbl_set_error("objective: no data or NULL argument");
         return RBL_ERR_STATE;
@@ -894,6 +918,7 @@ int rbl_objective(rbl_solver* h, const double* w, int include_reg, double* out) 
 // fraction of correctly classified rows of this handle's data (src/util/calculate_acc.py:3-19)
 int rbl_accuracy(rbl_solver* h, const double* w, double threshold, double* out) {
     RBL_ENTER(h);
+    RBL_TRY(sync_data_epoch(h));
     if (!h->data_ready || !w || !out) {
         rbl_set_error("accuracy: no data or NULL argument");
         return RBL_ERR_STATE;
@@ -945,6 +970,7 @@ int rbl_risk_from_v(rbl_solver* h, const void* v_all_dev, double* out) {
 // (src/util/fair_metric.py:3-41); group: n doubles with values 0 / 1
 int rbl_fair_statistics(rbl_solver* h, const double* w, const double* group, double threshold, double* out6) {
     RBL_ENTER(h);
+    RBL_TRY(sync_data_epoch(h));
     if (!h->data_ready || !w || !group || !out6) {
         rbl_set_error("fair_statistics: no data or NULL argument");
         return RBL_ERR_STATE;

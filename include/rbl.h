@@ -202,7 +202,13 @@ int  rbl_set_stream(rbl_solver* h, void* hip_stream);
  * (below): the same checks, messages ("set_data_from: ..."), 64 MB chunks (RBL_UPLOAD_CHUNK_BYTES applies), and
  * rbl_kernel_time(RBL_KERNEL_SRC_FORM) reports its forming pass.  Of a strided source (ldx > d) nothing is read beyond
  * column d of the last row.  RBL_STORE_F16: a finite entry that rounds to +-inf fails the call with RBL_ERR_INVALID (the
- * message counts them and names the first one); the handle is then without data. */
+ * message counts them and names the first one); the handle is then without data.
+ *   A second upload (any of rbl_set_data*, the generator) keeps the iterate - w, z, lambda, rho, iter, smooth_t, penalties,
+ * row weights, own labels - and nothing that was computed from the old data: the Gram matrix and what derives from it have
+ * to be formed again, D w, the work a single-sweep pass did ahead for the next iteration and a w-step enqueued ahead of
+ * time are dropped, on the handle and on every handle that borrows its data (a borrower notices at its next iteration or
+ * evaluation).  The next iteration is the one a fresh handle on the new data runs from the same state.  With borrowers
+ * the call waits for the whole device before it writes: none of their passes still reads what is replaced. */
 int  rbl_set_data(rbl_solver* h, const double* X, const double* y, int64_t ldx);
 /* X in the type it has and from where it lives.  X: n rows of d columns (d - 1 with RBL_DATA_ONES_COLUMN: column d - 1 of
  * D is then -y * 1, never scaled, reported as mean 0 / scale 1), row stride ldx ELEMENTS, naturally aligned, element type
@@ -259,8 +265,8 @@ int  rbl_set_data_from(rbl_solver* h, const void* X, int dtype, int mem, int64_t
  * (d - 1, -y_r) to every row.  Refused with RBL_ERR_INVALID (the handle is left without data): RBL_SCALE_FIT / APPLY
  * (centring makes D dense), nnz (plus n with the column of ones) above 2^31 - 1.  rbl_set_data / rbl_set_data_from and
  * the generator are RBL_ERR_INVALID there.  A second upload regrows the entry buffers under the handles that borrow the
- * data (the device is waited for first; their D pointer stays); after an upload that failed they answer RBL_ERR_STATE
- * until a valid one. */
+ * data (the device is waited for first; their D pointer stays) and they drop what they computed from the old entries, as
+ * after any second upload (rbl_set_data); after an upload that failed they answer RBL_ERR_STATE until a valid one. */
 enum { RBL_INDEX_I32 = 0, RBL_INDEX_I64 = 1 };
 int  rbl_set_data_csr(rbl_solver* h, const void* indptr /* n + 1 */, const void* indices /* nnz */,
                       const void* values /* nnz, element type dtype */, int64_t nnz, int index_type,
@@ -300,7 +306,11 @@ int  rbl_gram_info(rbl_solver* h, rbl_gram_report* out);   /* the last rbl_gram_
 int  rbl_csr_gram_route(int64_t n, int64_t ld, int64_t pair_products);   /* the rule itself, no device: 2 or 3 */
 int  rbl_get_D(rbl_solver* h, double* out /* n x d */);
 
-/* ---- state: w, z, lambda, rho (algorithms.py:32-52); NULL pointers are skipped ---- */
+/* ---- state: w, z, lambda, rho (algorithms.py:32-52); NULL pointers are skipped ----
+ * rbl_set_state keeps whatever does not depend on the values it replaces and drops the rest: a new w voids D w, a new
+ * lambda the d-space copy of D^T lambda (it is formed again by the next iteration), any of w, z, lambda, rho the work a
+ * single-sweep pass did ahead for the next iteration; iter and smooth_t void nothing.  The next iteration is the one a
+ * fresh handle on the same data runs from that state. */
 int  rbl_get_state(rbl_solver* h, double* w, double* z, double* lam, double* rho, int64_t* iter, double* smooth_t);
 int  rbl_set_state(rbl_solver* h, const double* w, const double* z, const double* lam, const double* rho, const int64_t* iter, const double* smooth_t);
 int  rbl_get_sigma(rbl_solver* h, double* alphas, double* betas /* n_total each */);
@@ -316,7 +326,8 @@ int  rbl_step(rbl_solver* h, int want_objective, rbl_stats* out);
 int  rbl_solve(rbl_solver* h, int max_iter, int want_objective, rbl_stats* last,
                double* hist_objective, double* hist_primal, double* hist_dual, double* hist_rho,
                double* hist_time_s, int64_t cap);
-/* smoothADMMmethod's final soft-threshold of w by t (algorithms.py:257-258) */
+/* smoothADMMmethod's final soft-threshold of w by t (algorithms.py:257-258).  It changes w, and is treated like
+ * rbl_set_state(w): a handle that iterates on afterwards starts from the thresholded w. */
 int  rbl_finalize_smooth(rbl_solver* h);
 
 /* ---- groups: several problems on one data matrix, iterated together ------------------------------------------
