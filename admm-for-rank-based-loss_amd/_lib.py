@@ -26,6 +26,9 @@ MEM_HOST, MEM_DEVICE = 0, 1
 SCALING = {"none": 0, "fit": 1, "apply": 2}
 DATA_ONES_COLUMN = 1
 GROUP_SHARE_SPARSE = 1          # rbl_group_create_opts: shared multi-column passes on storage "csr"
+CREATE_NO_GRAM = 1              # rbl_create_opts: no Gram matrix, the operator w-step (storage "csr")
+GRAM_MAX_LD = 16384             # the widest ld of the Gram-space w-step (csrc/rbl_internal.h: RBL_GRAM_MAX_LD)
+GRAM_MODES = ("auto", "dense", "none")
 # rbl_set_data_csr: the type of indptr and indices
 INDEX_I32, INDEX_I64 = 0, 1
 INDEX_DTYPE = {np.dtype(np.int32): INDEX_I32, np.dtype(np.int64): INDEX_I64}
@@ -138,6 +141,7 @@ SIGNATURES = {
     "rbl_last_error": (C.c_char_p, []),
     "rbl_device_count": (C.c_int, []),
     "rbl_create": (C.c_int, [C.POINTER(RblConfig), C.POINTER(_P)]),
+    "rbl_create_opts": (C.c_int, [C.POINTER(RblConfig), C.c_uint32, C.POINTER(_P)]),
     "rbl_destroy": (C.c_int, [_P]),
     "rbl_create_shared": (C.c_int, [C.POINTER(RblConfig), _P, C.POINTER(_P)]),
     "rbl_set_labels": (C.c_int, [_P, _P]),
@@ -251,6 +255,8 @@ SIGNATURES = {
     "rbl_csr_gram_route": (C.c_int, [C.c_int64, C.c_int64, C.c_int64]),
     "rbl_k_wstep": (C.c_int, [C.c_int, C.c_int64, _P, _P, C.c_double, C.c_double, C.c_double, _P, C.c_double, _P,
                               C.POINTER(C.c_int)]),
+    "rbl_k_wstep_op": (C.c_int, [C.c_int, C.c_int64, C.c_int64, _P, _P, _P, _P, C.c_double, C.c_double, _P, _P, C.c_double,
+                                C.c_int, C.c_int, _P, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "rbl_k_wstep_pen": (C.c_int, [C.c_int64, _P, _P, C.c_double, _P, _P, _P, C.c_double, _P, C.POINTER(C.c_int),
                                   C.POINTER(C.c_int)]),
     "rbl_k_wstep_seq": (C.c_int, [C.c_int, C.c_int64, _P, C.c_int, _P, C.c_double, C.c_double, C.c_double, _P, _P, _P,
@@ -685,6 +691,24 @@ def k_wstep_pen(G, q, rho, l1=None, l2=None, w0=None, tol=1e-13):
     check(load().rbl_k_wstep_pen(d, ptr(G), ptr(q), float(rho), ptr(l1), ptr(l2), ptr(w0), float(tol), ptr(out),
                                  C.byref(it), C.byref(form)))
     return out, it.value, form.value
+
+
+def k_wstep_op(wstep, A, q, rho, reg=0.0, l1=None, l2=None, w0=None, tol=1e-13, max_inner=100000, num_cu=0):
+    """One operator w-step (include/rbl.h: rbl_k_wstep_op) on the canonical scipy.sparse CSR matrix A = D; returns
+    (w of storage_ld(d, "csr") entries - the padding included -, iterations, status: 1 converged / 0 cap reached)."""
+    n, d, ip, ix, va = _csr_arrays(A)
+    q = f64(q).reshape(-1)
+    if q.size != d:
+        raise ValueError(f"q has {q.size} entries for {d} columns")
+    l1 = None if l1 is None else f64(np.broadcast_to(np.asarray(l1, dtype=np.float64), (d,)))
+    l2 = None if l2 is None else f64(np.broadcast_to(np.asarray(l2, dtype=np.float64), (d,)))
+    w = np.zeros(storage_ld(d, "csr"))
+    if w0 is not None:
+        w[:d] = f64(w0).reshape(-1)
+    it, status = C.c_int(0), C.c_int(0)
+    check(load().rbl_k_wstep_op(int(wstep), n, d, ptr(ip), ptr(ix), ptr(va), ptr(q), float(rho), float(reg), ptr(l1), ptr(l2),
+                                float(tol), int(max_inner), int(num_cu), ptr(w), C.byref(it), C.byref(status)))
+    return w, it.value, status.value
 
 
 def k_wstep_seq(wstep, G, Q, rho, reg, w0=None, smooth_t=1.0, tol=1e-13, max_inner=100000, l1=None, l2=None, route=0,

@@ -367,6 +367,26 @@ def check_csr_storage(src, storage, standardize=False, what="X"):
                          f"this one is dense - pass scipy.sparse.csr_matrix({what}), or use storage f32 / f64 / fp16")
 
 
+def resolve_gram(gram, storage, d):
+    """The w-step route of a problem with d coordinates: "dense" (Gram space: G = D^T D is formed) or "none" (the
+    operator w-step of RBL_CREATE_NO_GRAM: no d x d matrix).  ``gram="auto"`` is "none" exactly where the Gram route
+    cannot run - storage "csr" with ld > 16 384 - and "dense" everywhere else.  "none" needs storage "csr"; "dense" on
+    "csr" needs ld <= 16 384.  Raises ValueError - before any device call - otherwise."""
+    if gram not in _lib.GRAM_MODES:
+        raise ValueError(f"gram must be one of {list(_lib.GRAM_MODES)}, got {gram!r}")
+    if storage not in _lib.STORAGE:
+        raise ValueError(f"storage must be one of {sorted(_lib.STORAGE)}")
+    wide = storage == "csr" and _lib.storage_ld(d, storage) > _lib.GRAM_MAX_LD
+    if gram == "auto":
+        return "none" if wide else "dense"
+    if gram == "none" and storage != "csr":
+        raise ValueError(f'gram="none" needs storage="csr" (the operator w-step runs on the sparse passes), got storage={storage!r}')
+    if gram == "dense" and wide:
+        raise ValueError(f'gram="dense" with storage="csr" and {d} coordinates: the Gram-space w-step stops at '
+                         f'{_lib.GRAM_MAX_LD} - use gram="none" (or "auto")')
+    return gram
+
+
 def as_scaling(mean, scale, d, ones_column=False):
     """(mean, scale) for d coordinates as float64; with ones_column the vectors of the d - 1 features are accepted and
     the unscaled column's (0, 1) appended"""
@@ -380,16 +400,25 @@ def as_scaling(mean, scale, d, ones_column=False):
 
 class Solver:
     """One librbl handle.  ``n`` local rows of an ``n_total``-row problem.  ``share``: another Solver whose device D and
-    Gram matrix this one borrows (include/rbl.h: rbl_create_shared) - no set_data / gram on this handle."""
+    Gram matrix this one borrows (include/rbl.h: rbl_create_shared) - no set_data / gram on this handle.  ``gram``: the
+    w-step's route (resolve_gram; ``gram_route`` holds "dense" or "none" - "none" creates the handle with
+    RBL_CREATE_NO_GRAM); with ``share`` it must be the owner's."""
 
     def __init__(self, n, d, weight_function="erm", loss="binary_cross_entropy", reg=0.0, wstep=_lib.WSTEP_L2,
                  B=None, args=None, smooth_t=1.0, rho0=0.0, tol=1e-4, w_tol=0.0, max_iter=200, storage="f32",
-                 device=0, objective_only=False, n_total=None, row_offset=0, share=None):
+                 device=0, objective_only=False, n_total=None, row_offset=0, share=None, gram="auto"):
         self._h = None
         self._share = share           # keeps the data's owner referenced (the library counts references itself)
-        self.lib = _lib.load()
         if storage not in _lib.STORAGE:
             raise ValueError(f"storage must be one of {sorted(_lib.STORAGE)}")
+        # "dense" or "none" (resolve_gram); a borrower is what its owner is - asking it for the other route is an error
+        self.gram_route = resolve_gram(gram, storage, d)
+        if not objective_only and self.gram_route == "none" and int(wstep) == _lib.WSTEP_SMOOTH_L1:
+            raise ValueError('the smoothed-l1 w-step needs the Gram matrix (its preconditioner is diag(G)): it has no '
+                             'gram="none" route' + (f" - and storage=\"csr\" with {d} coordinates has no other" if gram == "auto" else ""))
+        if isinstance(share, Solver) and not objective_only and not share.cfg.objective_only and share.gram_route != self.gram_route:
+            raise ValueError(f'gram={gram!r} on data shared with a gram="{share.gram_route}" solver: one data matrix, one route')
+        self.lib = _lib.load()
         cfg = _lib.RblConfig()
         cfg.n, cfg.d = int(n), int(d)
         cfg.n_total = int(n if n_total is None else n_total)
@@ -420,7 +449,8 @@ class Solver:
                 raise ValueError("share must be a live Solver")
             _lib.check(self.lib.rbl_create_shared(C.byref(cfg), share._h, C.byref(h)))
         else:
-            _lib.check(self.lib.rbl_create(C.byref(cfg), C.byref(h)))
+            flags = _lib.CREATE_NO_GRAM if self.gram_route == "none" and not objective_only else 0
+            _lib.check(self.lib.rbl_create_opts(C.byref(cfg), flags, C.byref(h)))
         self._h = h
 
     # ------------------------------------------------------------------ lifetime
@@ -553,7 +583,8 @@ class Solver:
 
     def gram_info(self):
         """how the handle's last Gram matrix was formed (include/rbl.h: rbl_gram_report; a borrower: its owner's):
-        route 0 none yet, 1 dense storage, 2 csr by dense expansion, 3 csr from the entries"""
+        route 0 none yet - or none at all (gram="none": the operator w-step) -, 1 dense storage, 2 csr by dense
+        expansion, 3 csr from the entries"""
         rep = _lib.RblGramReport()
         _lib.check(self.lib.rbl_gram_info(self._h, C.byref(rep)))
         return _lib._gram_report_dict(rep)
@@ -836,6 +867,12 @@ class Solver:
         ms, cnt = C.c_double(0), C.c_int64(0)
         _lib.check(self.lib.rbl_kernel_time(self._h, int(which), C.byref(ms), C.byref(cnt)))
         return ms.value, cnt.value
+
+
+def check_gram_mode(value):
+    """``gram`` of ADMMmethod / ADMMgroup / OneVsRest names a route: anything else is an argument error (no device call)"""
+    if value not in _lib.GRAM_MODES:
+        raise ValueError(f"gram must be one of {list(_lib.GRAM_MODES)}, got {value!r}")
 
 
 def check_share_sparse(value):

@@ -240,6 +240,33 @@ int validate(const rbl_config* c) {
     return RBL_OK;
 }
 
+// RBL_CREATE_NO_GRAM and what it asks of the problem; the late failure of a wide csr handle on the Gram route is refused here
+int validate_gram_route(const rbl_config* c, uint32_t flags, const char* who) {
+    if (flags & ~(uint32_t)RBL_CREATE_NO_GRAM) {
+        rbl_set_error("%s: unknown flag bits 0x%x (RBL_CREATE_NO_GRAM = %d is the only flag)", who, flags & ~(uint32_t)RBL_CREATE_NO_GRAM,
+                      RBL_CREATE_NO_GRAM);
+        return RBL_ERR_INVALID;
+    }
+    if (flags & RBL_CREATE_NO_GRAM) {
+        if (c->storage != RBL_STORE_CSR) {
+            rbl_set_error("%s: RBL_CREATE_NO_GRAM needs RBL_STORE_CSR (the operator w-step runs on the sparse passes; got storage %d)",
+                          who, c->storage);
+            return RBL_ERR_INVALID;
+        }
+        if (!c->objective_only && c->wstep == RBL_WSTEP_SMOOTH_L1) {
+            rbl_set_error("%s: RBL_CREATE_NO_GRAM has no smoothed-l1 w-step (RBL_WSTEP_SMOOTH_L1 preconditions with diag(G), and "
+                          "there is no Gram matrix on this route)", who);
+            return RBL_ERR_INVALID;
+        }
+    } else if (c->storage == RBL_STORE_CSR && !c->objective_only && rbl_storage_ld(c->storage, c->d) > RBL_GRAM_MAX_LD) {
+        rbl_set_error("%s: RBL_STORE_CSR with d = %lld: the Gram-space w-step holds a dense ld x ld matrix and stops at ld = %d - "
+                      "create the handle with rbl_create_opts(cfg, RBL_CREATE_NO_GRAM, ...) (the operator w-step)", who,
+                      (long long)c->d, RBL_GRAM_MAX_LD);
+        return RBL_ERR_INVALID;
+    }
+    return RBL_OK;
+}
+
 int build_sigma_prefix(rbl_solver* h) {
     // sigma is static: its prefix sums are built once (pav.hip uses them every iteration)
     RBL_TRY(launch_prefix(h->sigma_a, h->nt, h->pfx_a, h->stream));
@@ -340,7 +367,7 @@ static int create_setup(rbl_solver* h, rbl_solver* owner = nullptr) {
         }
         RBL_TRY(h->shared->alloc(&h->ysign, (size_t)n));
         RBL_TRY(h->shared->alloc(&h->colstats, (size_t)ld * 4));
-        if (!cfg->objective_only) RBL_TRY(h->shared->alloc(&h->G, (size_t)ld * ld));
+        if (!cfg->objective_only && !h->no_gram) RBL_TRY(h->shared->alloc(&h->G, (size_t)ld * ld));
     }
     RBL_TRY(mem.alloc(&h->w, (size_t)ld));
     RBL_TRY(mem.alloc(&h->w_tmp, (size_t)ld));
@@ -352,10 +379,13 @@ static int create_setup(rbl_solver* h, rbl_solver* owner = nullptr) {
     if (cfg->objective_only) RBL_TRY(mem.alloc(&h->red, 8));
     RBL_TRY(mem.alloc(&h->red2, 8));
     h->slab_bytes = (size_t)gemvt_slab_rows(h->num_cu) * ld * sizeof(double) * 2;
+    // no Gram matrix: the slab only ever holds the segments' partial sums (ensure_sparse_slab grows it to the data), not
+    // the dense passes' rows of ld - those are 800 MB at d = 200 000
+    if (h->no_gram) h->slab_bytes = sizeof(double) * (size_t)ld;
     if (owner && h->storage == RBL_STORE_CSR)   // q = D^T c keeps one partial sum per segment in the handle's own slab
         h->slab_bytes = std::max(h->slab_bytes, sizeof(double) * (size_t)((const CsrStore*)owner->D)->nseg);
     if (!cfg->objective_only) {
-        size_t gb = owner ? 0 : gram_slab_bytes(ld, h->num_cu, n > 0 ? n : 1);   // (a borrower never forms G)
+        size_t gb = owner || h->no_gram ? 0 : gram_slab_bytes(ld, h->num_cu, n > 0 ? n : 1);   // (a borrower never forms G)
         if (gb > h->slab_bytes) h->slab_bytes = gb;
         RBL_TRY(mem.alloc(&h->w_prev, (size_t)ld));
         // one exchange buffer, summed over ranks in at most one collective per iteration:
@@ -366,6 +396,10 @@ static int create_setup(rbl_solver* h, rbl_solver* owner = nullptr) {
         RBL_TRY(mem.alloc(&h->lam, (size_t)n));
         RBL_TRY(mem.alloc(&h->c, (size_t)n));
         RBL_TRY(alloc_wstep(mem, h->ww, ld, h->stream));
+        if (h->no_gram) {   // the operator's n-vector and the chunk partials of its d-space kernels
+            RBL_TRY(mem.alloc(&h->op_t, (size_t)(n > 0 ? n : 1)));
+            RBL_TRY(mem.alloc(&h->op_part, op_part_doubles(ld)));
+        }
     }
     RBL_TRY(mem.alloc((unsigned char**)&h->slab, h->slab_bytes));
     if (h->sorted_path) {
@@ -437,12 +471,19 @@ int rbl_create_shared(const rbl_config* cfg, rbl_solver* owner, rbl_solver** out
                       cfg->storage, oc.storage, cfg->device, oc.device);
         return RBL_ERR_INVALID;
     }
+    // a borrower of a no-Gram owner is a no-Gram handle: its cfg follows the rules of the flag
+    RBL_TRY(validate_gram_route(cfg, owner->no_gram ? RBL_CREATE_NO_GRAM : 0, "create_shared"));
     if (!owner->data_ready) {
         rbl_set_error("create_shared: the owner has no data yet (rbl_set_data / rbl_generate_synthetic first)");
         return RBL_ERR_STATE;
     }
-    if (!cfg->objective_only && (!owner->der.gram_ready || !owner->G)) {
+    if (!cfg->objective_only && !owner->no_gram && (!owner->der.gram_ready || !owner->G)) {
         rbl_set_error("create_shared: the owner's Gram matrix is not ready (rbl_gram_local + rbl_gram_finish first)");
+        return RBL_ERR_STATE;
+    }
+    if (!cfg->objective_only && owner->no_gram && (owner->cfg.objective_only || !owner->der.gram_ready)) {
+        rbl_set_error("create_shared: the owner's step constant is not ready (rbl_gram_local + rbl_gram_finish first; an "
+                      "objective-only owner has none)");
         return RBL_ERR_STATE;
     }
     RBL_TRY(check_device(nullptr));
@@ -450,6 +491,7 @@ int rbl_create_shared(const rbl_config* cfg, rbl_solver* owner, rbl_solver** out
     RBL_HIP(hipStreamSynchronize(owner->stream));   // D and G are complete before another stream reads them
     rbl_solver* h = new rbl_solver();
     h->cfg = *cfg;
+    h->no_gram = owner->no_gram;
     if (cfg->device < 64) {
         g_live[cfg->device].fetch_add(1, std::memory_order_relaxed);
         h->counted = true;
@@ -463,13 +505,14 @@ int rbl_create_shared(const rbl_config* cfg, rbl_solver* owner, rbl_solver** out
     return RBL_OK;
 }
 
-int rbl_create(const rbl_config* cfg, rbl_solver** out) {
+int rbl_create_opts(const rbl_config* cfg, uint32_t flags, rbl_solver** out) {
     if (!out) {
         rbl_set_error("out is NULL");
         return RBL_ERR_INVALID;
     }
     *out = nullptr;
     RBL_TRY(validate(cfg));
+    RBL_TRY(validate_gram_route(cfg, flags, flags ? "create_opts" : "create"));
     int cnt = 0;
     RBL_TRY(check_device(&cnt));
     if (cfg->device < 0 || cfg->device >= cnt) {
@@ -479,6 +522,7 @@ int rbl_create(const rbl_config* cfg, rbl_solver** out) {
     RBL_HIP(hipSetDevice(cfg->device));
     rbl_solver* h = new rbl_solver();
     h->cfg = *cfg;
+    h->no_gram = (flags & RBL_CREATE_NO_GRAM) != 0;
     if (cfg->device < 64) {
         g_live[cfg->device].fetch_add(1, std::memory_order_relaxed);
         h->counted = true;
@@ -491,6 +535,8 @@ int rbl_create(const rbl_config* cfg, rbl_solver** out) {
     *out = h;
     return RBL_OK;
 }
+
+int rbl_create(const rbl_config* cfg, rbl_solver** out) { return rbl_create_opts(cfg, 0, out); }
 
 int rbl_set_stream(rbl_solver* h, void* hip_stream) {
     RBL_ENTER(h);
@@ -562,7 +608,14 @@ int rbl_buffer(rbl_solver* h, int which, void** dev_ptr, int64_t* n_doubles) {
         case RBL_BUF_M: p = h->m; cnt = h->n; break;
         case RBL_BUF_Q: p = h->q; cnt = h->q ? 2 * h->ld + 3 : 0; break;  // whole exchange buffer (RED = its tail)
         case RBL_BUF_RED: p = h->red; cnt = 2; break;
-        case RBL_BUF_G: p = h->G; cnt = h->ld * h->ld; break;
+        case RBL_BUF_G:
+            if (h->no_gram) {
+                rbl_set_error("buffer(RBL_BUF_G): this handle has no Gram matrix (RBL_CREATE_NO_GRAM: the operator w-step)");
+                return RBL_ERR_STATE;
+            }
+            p = h->G;
+            cnt = h->ld * h->ld;
+            break;
         case RBL_BUF_V: p = h->v; cnt = h->n; break;
         case RBL_BUF_Z: p = h->z; cnt = h->n; break;
         case RBL_BUF_LAM: p = h->lam; cnt = h->n; break;

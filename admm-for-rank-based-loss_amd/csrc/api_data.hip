@@ -1086,7 +1086,9 @@ int rbl_gram_local(rbl_solver* h) {
         return RBL_ERR_STATE;
     }
     rbl_gram_report rep{};
-    if (h->storage == RBL_STORE_CSR) {   // the route is the rule's (csr_gram_plan.h); the launcher times itself
+    if (h->no_gram) {
+        // nothing is formed: the report stays route 0, "no Gram matrix"; rbl_gram_finish takes L through the operator
+    } else if (h->storage == RBL_STORE_CSR) {   // the route is the rule's (csr_gram_plan.h); the launcher times itself
         RBL_TRY(launch_csr_gram((const CsrStore*)h->D, h->n, h->ld, h->d, h->slab, h->G, h->num_cu, h->stream, 0, 0, &rep));
     } else {
         struct Ev {   // events of this call alone (the handle's belong to the iteration)
@@ -1131,7 +1133,13 @@ int rbl_gram_finish(rbl_solver* h) {
         return RBL_ERR_STATE;
     }
     double lam = 0.0;
-    RBL_TRY(launch_power_iteration(h->G, h->ld, h->ww.yk, h->ww.Gy, h->ww.scal, 100, &lam, h->stream));
+    if (h->no_gram) {   // lambda_max(D^T D) by the same 100 steps, D^T (D x) in the place of G x
+        OpData op;
+        RBL_TRY(op_data(h, &op));
+        RBL_TRY(launch_op_power_iteration(op, h->ld, h->d, h->ww.yk, h->ww.Gy, h->ww.scal, 100, &lam, h->stream));
+    } else {
+        RBL_TRY(launch_power_iteration(h->G, h->ld, h->ww.yk, h->ww.Gy, h->ww.scal, 100, &lam, h->stream));
+    }
     gram_changed(h->der);   // G is whole only now (a row shard's was summed over the ranks since rbl_gram_local)
     SharedData& r = *h->sd;   // what comes from G alone goes into the shared record: the borrowers read it there
     r.eig_ok = false;
@@ -1144,7 +1152,7 @@ int rbl_gram_finish(rbl_solver* h) {
         const char* e = getenv("RBL_RIDGE_EIG");
         return e && e[0] == '1';
     }();
-    if (h->cfg.wstep == RBL_WSTEP_L2 && h->ld <= 2048 && ridge_eig) {
+    if (h->cfg.wstep == RBL_WSTEP_L2 && h->ld <= 2048 && ridge_eig && !h->no_gram) {
         const size_t nn = (size_t)h->ld * (size_t)h->ld;
         if (!r.eig_Vt) {
             double *Vt = nullptr, *V = nullptr, *lambda = nullptr;

@@ -3,22 +3,32 @@
 // what evaluates an iterate: objective, accuracy, fairness statistics, risk.
 #include "api_internal.h"
 
-// q = D^T c of a handle.  Sparse storage keeps one partial sum per segment in the handle's own slab: it is regrown here
-// when the data have more segments than it holds (a second upload on the owner of a borrowed D), and the launcher
-// refuses a slab that is too small.
-static int gemvt_h(rbl_solver* h, const double* c, double* q, hipEvent_t main_done = nullptr) {
-    if (h->storage == RBL_STORE_CSR) {
-        const size_t need = sizeof(double) * (size_t)((const CsrStore*)h->D)->nseg;
-        if (need > h->slab_bytes) {
-            unsigned char* grown = nullptr;   // the new one first: a failed allocation leaves the handle its slab
-            RBL_TRY(h->mem.alloc(&grown, need));
-            RBL_HIP(hipStreamSynchronize(h->stream));
-            h->mem.release(h->slab);
-            h->slab = (double*)grown;
-            h->slab_bytes = need;
-        }
+// Sparse storage keeps one partial sum per segment in the handle's own slab: it is regrown here when the data have more
+// segments than it holds (a second upload on the owner of a borrowed D), and the launcher refuses a slab that is too small.
+int ensure_sparse_slab(rbl_solver* h) {
+    if (h->storage != RBL_STORE_CSR) return RBL_OK;
+    const size_t need = sizeof(double) * (size_t)((const CsrStore*)h->D)->nseg;
+    if (need > h->slab_bytes) {
+        unsigned char* grown = nullptr;   // the new one first: a failed allocation leaves the handle its slab
+        RBL_TRY(h->mem.alloc(&grown, need));
+        RBL_HIP(hipStreamSynchronize(h->stream));
+        h->mem.release(h->slab);
+        h->slab = (double*)grown;
+        h->slab_bytes = need;
     }
+    return RBL_OK;
+}
+
+// q = D^T c of a handle
+static int gemvt_h(rbl_solver* h, const double* c, double* q, hipEvent_t main_done = nullptr) {
+    RBL_TRY(ensure_sparse_slab(h));
     return launch_gemvt(h->storage, h->D, h->n, h->ld, c, h->slab, q, h->num_cu, h->stream, main_done, h->slab_bytes / sizeof(double));
+}
+
+int op_data(rbl_solver* h, OpData* op) {
+    RBL_TRY(ensure_sparse_slab(h));
+    *op = OpData{(const CsrStore*)h->D, h->n, h->op_t, h->slab, h->slab_bytes / sizeof(double), h->op_part, h->num_cu};
+    return RBL_OK;
 }
 
 int ensure_v(rbl_solver* h) {
@@ -528,7 +538,7 @@ static int phase_w_body(rbl_solver* h) {
     const bool spec = h->spec_w;   // this w-step (and what follows it) was enqueued by the previous rbl_phase_finish
     h->spec_w = false;
     int wstep = h->cfg.wstep;
-    if (!spec && wstep != RBL_WSTEP_L1)   // the lasso kernel saves its warm start itself
+    if (!spec && (wstep != RBL_WSTEP_L1 || h->no_gram))   // the lasso kernel saves its warm start itself
         RBL_HIP(hipMemcpyAsync(h->w_prev, h->w, sizeof(double) * h->ld, hipMemcpyDeviceToDevice, h->stream));
     if (h->der.p_pending) {
         RBL_HIP(hipMemcpyAsync(h->p, q_pinit(h), sizeof(double) * h->ld, hipMemcpyDeviceToDevice, h->stream));
@@ -544,7 +554,15 @@ static int phase_w_body(rbl_solver* h) {
     // the active-set lasso kernel leaves G w of its solution in ww.Gy (it needs the gradient for its
     // own optimality test): no d x d product for the rho prediction unless FISTA had to take over
     bool gw_ready = predict && wstep == RBL_WSTEP_L1;
-    if (!spec) {
+    if (!spec && h->no_gram) {
+        // no G: CG / FISTA on the operator rho D^T D + diag(.) (wstep_op.hip); csr never runs the single-sweep pass, so
+        // there is no rho prediction and the statistics of the new w follow as on the !predict branch
+        OpData op;
+        RBL_TRY(op_data(h, &op));
+        RBL_TRY(run_wstep_op(wstep, op, h->ld, h->q, h->step_rho, h->cfg.reg, h->L, h->cfg.w_tol, 100000, h->w, h->ww,
+                             &h->inner_iters, h->stream));
+        fs_pending = false;
+    } else if (!spec) {
         h->ww.eig_ok = h->der.eig_ok;   // (run_wstep's view of it)
         RBL_TRY(run_wstep(wstep, h->G, h->ld, h->q, h->step_rho, h->cfg.reg, h->smooth_t, h->L, h->cfg.w_tol, 100000,
                           h->w, h->ww, &h->inner_iters, h->stream, &fs_pending, nullptr, h->w_prev, predict));

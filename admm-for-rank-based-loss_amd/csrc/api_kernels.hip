@@ -1024,6 +1024,85 @@ int rbl_k_wstep_pen(int64_t d, const double* G, const double* q, double rho, con
     return RBL_OK;
 }
 
+// The operator w-step (wstep_op.hip) as a handle created with RBL_CREATE_NO_GRAM runs it: the entries are uploaded and both
+// forms built, L comes from the power iteration through the operator, then one run_wstep_op
+int rbl_k_wstep_op(int wstep, int64_t n, int64_t d, const int64_t* indptr, const int32_t* indices, const double* values,
+                   const double* q, double rho, double reg, const double* l1, const double* l2, double tol, int max_inner,
+                   int num_cu, double* w_inout, int* iters, int* status) {
+    const char* who = "rbl_k_wstep_op";
+    if (wstep == RBL_WSTEP_SMOOTH_L1) {
+        rbl_set_error("%s: no smoothed-l1 w-step on the operator route (RBL_WSTEP_SMOOTH_L1 preconditions with diag(G), and there "
+                      "is no Gram matrix)", who);
+        return RBL_ERR_INVALID;
+    }
+    if (wstep != RBL_WSTEP_L1 && wstep != RBL_WSTEP_L2) {
+        rbl_set_error("%s: wstep must be 1 (lasso / elastic net) or 2 (ridge), got %d", who, wstep);
+        return RBL_ERR_INVALID;
+    }
+    const bool pen = l1 || l2;
+    if (d < 1 || n < 1 || !indptr || !q || !w_inout || !(rho > 0.0) || !std::isfinite(rho) || max_inner < 1 || !std::isfinite(tol) ||
+        (!pen && (!(reg > 0.0) || !std::isfinite(reg)))) {
+        rbl_set_error("%s: bad argument (n >= 1, d >= 1, indptr, q, w_inout, finite rho > 0, max_inner >= 1, and a finite reg > 0 "
+                      "or l1 / l2 are needed; n = %lld, d = %lld)", who, (long long)n, (long long)d);
+        return RBL_ERR_INVALID;
+    }
+    double l2max = 0.0;
+    for (int k = 0; k < 2; ++k) {
+        const double* v = k ? l2 : l1;
+        for (int64_t j = 0; v && j < d; ++j) {
+            if (!(v[j] >= 0.0) || !std::isfinite(v[j])) {
+                rbl_set_error("%s: %s[%lld] = %g - penalties must be finite and >= 0", who, k ? "l2" : "l1", (long long)j, v[j]);
+                return RBL_ERR_INVALID;
+            }
+            if (k && v[j] > l2max) l2max = v[j];
+        }
+    }
+    Scratch sc;
+    int cus = 0;
+    RBL_TRY(scratch_begin(sc, &cus));
+    if (num_cu == 0) num_cu = cus;
+    if (num_cu < 1 || num_cu > cus) {
+        rbl_set_error("%s: num_cu = %d outside 1..%d (the device's compute units; 0 = all)", who, num_cu, cus);
+        return RBL_ERR_INVALID;
+    }
+    CsrStore st;
+    int64_t ld = 0;
+    RBL_TRY(upload_csr(sc, who, n, d, indptr, indices, values, true, num_cu, &st, &ld));
+    std::vector<double> hq((size_t)ld, 0.0), hw((size_t)ld, 0.0), hp((size_t)(2 * ld), 0.0);
+    for (int64_t i = 0; i < d; ++i) {
+        hq[(size_t)i] = q[i];
+        hw[(size_t)i] = w_inout[i];
+        hp[(size_t)i] = l1 ? l1[i] : 0.0;
+        hp[(size_t)(ld + i)] = l2 ? l2[i] : 0.0;
+    }
+    double *dq = nullptr, *dw = nullptr, *dp = nullptr;
+    RBL_TRY(sc.upload(&dq, hq.data(), hq.size()));
+    RBL_TRY(sc.upload(&dw, hw.data(), hw.size()));
+    WstepWorkspace ww{};
+    RBL_TRY(alloc_wstep(sc.mem, ww, ld, sc.s));
+    if (pen) {
+        RBL_TRY(sc.upload(&dp, hp.data(), hp.size()));
+        ww.pen_l1 = dp;
+        ww.pen_l2 = dp + ld;
+        ww.pen_l2max = l2max;
+    }
+    OpData op{&st, n, nullptr, nullptr, (size_t)(st.nseg > 0 ? st.nseg : 1), nullptr, num_cu};
+    RBL_TRY(sc.mem.alloc(&op.t, (size_t)n));
+    RBL_TRY(sc.mem.alloc(&op.slab, op.slab_doubles));
+    RBL_TRY(sc.mem.alloc(&op.part, op_part_doubles(ld)));
+    double lam = 0.0;
+    RBL_TRY(launch_op_power_iteration(op, ld, d, ww.yk, ww.Gy, ww.scal, 100, &lam, sc.s));
+    double L = 1.02 * lam;
+    if (!(L > 0.0)) L = 1.0;
+    int it = 0;
+    RBL_TRY(run_wstep_op(wstep, op, ld, dq, rho, reg, L, tol > 0.0 ? tol : 1e-13, max_inner, dw, ww, &it, sc.s));
+    RBL_HIP(hipMemcpyAsync(w_inout, dw, sizeof(double) * ld, hipMemcpyDeviceToHost, sc.s));
+    RBL_HIP(hipStreamSynchronize(sc.s));
+    if (iters) *iters = it;
+    if (status) *status = reinterpret_cast<const volatile int*>(ww.pin)[wstep == RBL_WSTEP_L2 ? 4 : 6] == 1 ? 1 : 0;
+    return RBL_OK;
+}
+
 int rbl_k_wstep_seq(int wstep, int64_t d, const double* G, int K, const double* Q, double rho, double reg, double smooth_t,
                     const double* l1, const double* l2, const double* w0, double tol, int max_inner, int route,
                     int launch_seq0, int flags, double* W, double* Gw, double* Wprev, rbl_wstep_report* reports) {

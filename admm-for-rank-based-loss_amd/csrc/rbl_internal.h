@@ -371,6 +371,7 @@ int launch_scatter_z(int64_t n, const double* u, const u32* perm, const int* bra
                      hipStream_t s, const signed char* rs = nullptr);
 
 // ---- wstep.hip --------------------------------------------------------------------------
+constexpr int RBL_GRAM_MAX_LD = 16384;   // the widest ld of the Gram-space w-step (its single-block update kernels)
 // which persistent kernel instance a w-step launched (wp_run fills it through WstepWorkspace::inst: the rbl_k_wstep_seq
 // entry reports it, the solver leaves the pointer NULL, as with SweepInstance)
 struct WstepInstance {
@@ -545,10 +546,11 @@ int launch_csr_store(int dtype, int index_type, const CsrStore* st, int64_t rows
                      int num_cu, hipStream_t s);
 // after the last chunk: the lane group, and with columns the column form and its segment table; returns with s idle
 int csr_store_finish(CsrStore* st, int64_t ld, bool columns, int num_cu, hipStream_t s);
-int launch_csr_gemv(const CsrStore* st, int64_t n, const double* w, double* v, int num_cu, hipStream_t s);
+// done (optional, both passes): a device flag - where it is set when a kernel starts, that kernel does nothing (output untouched)
+int launch_csr_gemv(const CsrStore* st, int64_t n, const double* w, double* v, int num_cu, hipStream_t s, const int* done = nullptr);
 // part: the segments' partial sums, part_doubles >= st->nseg of them (fewer: RBL_ERR_STATE before anything is launched)
 int launch_csr_gemvt(const CsrStore* st, int64_t ld, const double* c, double* part, size_t part_doubles, double* q, int num_cu,
-                     hipStream_t s, hipEvent_t main_done);
+                     hipStream_t s, hipEvent_t main_done, const int* done = nullptr);
 // The two passes for k problems (1 <= k <= RBL_MULTI_KMAX) per read of the entries; arrays of k host-side pointers.  Column
 // j has the bits of the single-column launcher on w[j] / c[j] alone (k = 1 is that launcher); k = 3 runs three chains, on
 // the q side over packed rows of four.  v_j = D w_j:
@@ -573,6 +575,26 @@ int launch_csr_gram(const CsrStore* st, int64_t n, int64_t ld, int64_t d, double
 int launch_csr_spgram(const CsrStore* st, int64_t n, int64_t ld, double* G, int num_cu, int tile_cols, hipStream_t s,
                       rbl_gram_report* rep);
 unsigned spgram_grid(int64_t items, int num_cu);   // blocks of four single-wave items, at most 32 per CU
+
+// ---- wstep_op.hip: the w-step of a handle without a Gram matrix (RBL_CREATE_NO_GRAM) ----------------------------
+// A = rho D^T D + diag(.) applied through the two sparse passes.  What the operator needs beside the WstepWorkspace:
+struct OpData {
+    const CsrStore* st;    // the owner's entries, both forms
+    int64_t n;
+    double* t;             // n: t = D p
+    double* slab;          // the segments' partial sums of y = D^T t, slab_doubles >= st->nseg of them
+    size_t slab_doubles;
+    double* part;          // op_part_doubles(ld): the chunks' partial sums and maxima of the d-space kernels
+    int num_cu;            // sizes the grids of the sparse passes only; no bit of a result depends on it
+};
+size_t op_part_doubles(int64_t ld);
+// launch_power_iteration through the operator: lambda_max(D^T D) after `iters` steps from the same start vector
+int launch_op_power_iteration(const OpData& op, int64_t ld, int64_t d, double* x, double* y, double* scal, int iters,
+                              double* lambda_host, hipStream_t s);
+// ridge by CG, lasso / elastic net by FISTA (ws.pen_l1 / ws.pen_l2 as in run_wstep); ws.form = 4.  RBL_WSTEP_SMOOTH_L1
+// is RBL_ERR_INVALID: its preconditioner is diag(G)
+int run_wstep_op(int wstep, const OpData& op, int64_t ld, const double* q, double rho, double reg, double L, double tol,
+                 int max_inner, double* w, WstepWorkspace& ws, int* iters_host, hipStream_t s);
 
 // ---- synth.hip --------------------------------------------------------------------------
 int launch_synth(int storage, void* D, int64_t n, int64_t ld, int64_t d, int64_t row_offset, u64 seed,

@@ -59,11 +59,13 @@ __global__ __launch_bounds__(SP_THREADS) void k_csr_store(const int64_t* __restr
 
 // v = D w: a group of L lanes owns a row.  Every lane runs an fp64 FMA chain over its entries k = a + l, a + l + L, ... in
 // entry order (col / val loads are coalesced, w is gathered), then a fixed butterfly over the L lanes; lane 0 stores.
-// An empty row gives +0.0.
+// An empty row gives +0.0.  done (optional): a device flag of the caller's - set, the launch is a no-op (the passes an
+// operator w-step has enqueued behind its convergence, wstep_op.hip).
 template <int L>
 __global__ __launch_bounds__(SP_THREADS) void k_csr_gemv(const int64_t* __restrict__ indptr, const int* __restrict__ col,
                                                          const double* __restrict__ val, const double* __restrict__ w,
-                                                         double* __restrict__ v, long long n) {
+                                                         double* __restrict__ v, long long n, const int* __restrict__ done) {
+    if (done && *done) return;
     const int l = (int)threadIdx.x & (L - 1);
     constexpr int GPB = SP_THREADS / L;
     for (long long r = (long long)blockIdx.x * GPB + ((int)threadIdx.x / L); r < n; r += (long long)gridDim.x * GPB) {
@@ -82,7 +84,8 @@ __global__ __launch_bounds__(SP_THREADS) void k_csr_gemv(const int64_t* __restri
 __global__ __launch_bounds__(SP_THREADS) void k_csc_segments(const int64_t* __restrict__ colptr, const int64_t* __restrict__ segptr,
                                                              const int* __restrict__ row, const double* __restrict__ cval,
                                                              const double* __restrict__ c, double* __restrict__ part,
-                                                             long long ld, long long nseg, int T) {
+                                                             long long ld, long long nseg, int T, const int* __restrict__ done) {
+    if (done && *done) return;   // (as in k_csr_gemv)
     const int lane = (int)threadIdx.x & (RBL_WAVE - 1);
     for (long long s = (long long)blockIdx.x * SP_WPB + ((int)threadIdx.x / RBL_WAVE); s < nseg; s += (long long)gridDim.x * SP_WPB) {
         const CscSegment g = csc_segment(colptr, segptr, ld, s, T);
@@ -98,7 +101,8 @@ __global__ __launch_bounds__(SP_THREADS) void k_csc_segments(const int64_t* __re
 // ... in segment order, then the butterfly.  Columns without entries and the padding [d, ld) give +0.0.
 constexpr int SP_QL = 16;
 __global__ __launch_bounds__(SP_THREADS) void k_csc_columns(const int64_t* __restrict__ segptr, const double* __restrict__ part,
-                                                            double* __restrict__ q, long long ld) {
+                                                            double* __restrict__ q, long long ld, const int* __restrict__ done) {
+    if (done && *done) return;   // (as in k_csr_gemv)
     const int l = (int)threadIdx.x & (SP_QL - 1);
     const long long j = ((long long)blockIdx.x * SP_THREADS + (int)threadIdx.x) / SP_QL;
     if (j >= ld) return;   // (whole groups leave together)
@@ -415,11 +419,11 @@ int csr_store_finish(CsrStore* st, int64_t ld, bool columns, int num_cu, hipStre
     return RBL_OK;
 }
 
-int launch_csr_gemv(const CsrStore* st, int64_t n, const double* w, double* v, int num_cu, hipStream_t s) {
+int launch_csr_gemv(const CsrStore* st, int64_t n, const double* w, double* v, int num_cu, hipStream_t s, const int* done) {
     if (n <= 0) return RBL_OK;
 #define RBL_CSR_GEMV(L_)                                                                                                      \
     hipLaunchKernelGGL(k_csr_gemv<L_>, dim3(sp_grid(n, SP_THREADS / L_, num_cu)), dim3(SP_THREADS), 0, s, (const int64_t*)st->indptr, \
-                       (const int*)st->col, (const double*)st->val, w, v, (long long)n)
+                       (const int*)st->col, (const double*)st->val, w, v, (long long)n, done)
     switch (st->lanes) {
         case 4: RBL_CSR_GEMV(4); break;
         case 8: RBL_CSR_GEMV(8); break;
@@ -434,7 +438,7 @@ int launch_csr_gemv(const CsrStore* st, int64_t n, const double* w, double* v, i
 }
 
 int launch_csr_gemvt(const CsrStore* st, int64_t ld, const double* c, double* part, size_t part_doubles, double* q, int num_cu,
-                     hipStream_t s, hipEvent_t main_done) {
+                     hipStream_t s, hipEvent_t main_done, const int* done) {
     if (!st->colptr || !st->segptr) {
         rbl_set_error("csr gemvt: the handle holds the row form only (objective-only)");
         return RBL_ERR_STATE;
@@ -450,10 +454,10 @@ int launch_csr_gemvt(const CsrStore* st, int64_t ld, const double* c, double* pa
     if (st->nseg > 0)
         hipLaunchKernelGGL(k_csc_segments, dim3(sp_grid(st->nseg, SP_WPB, num_cu)), dim3(SP_THREADS), 0, s, (const int64_t*)st->colptr,
                            (const int64_t*)st->segptr, (const int*)st->row, (const double*)st->cval, c, part, (long long)ld,
-                           (long long)st->nseg, st->seg);
+                           (long long)st->nseg, st->seg, done);
     if (main_done) RBL_HIP(hipEventRecord(main_done, s));   // the pass over the entries alone (roofline timing)
     hipLaunchKernelGGL(k_csc_columns, dim3((unsigned)((ld * SP_QL + SP_THREADS - 1) / SP_THREADS)), dim3(SP_THREADS), 0, s,
-                       (const int64_t*)st->segptr, (const double*)part, q, (long long)ld);
+                       (const int64_t*)st->segptr, (const double*)part, q, (long long)ld, done);
     RBL_HIP(hipGetLastError());
     return RBL_OK;
 }

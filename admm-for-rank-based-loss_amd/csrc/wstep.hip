@@ -50,6 +50,7 @@ __global__ __launch_bounds__(256) void k_symv(const double* __restrict__ G, long
 
 constexpr int UPD_THREADS = 1024;
 constexpr int UPD_PER = 16;  // d <= 16384 in the single-block update kernels
+static_assert(UPD_THREADS * UPD_PER == RBL_GRAM_MAX_LD, "rbl_create refuses what run_wstep would refuse");
 
 struct FistaParams {
     int mode;      // 0 lasso (soft threshold), 1 smoothed l1 (Huber prox)

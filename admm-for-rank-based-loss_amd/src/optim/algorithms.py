@@ -20,7 +20,11 @@ torch CPU tensor of float64 / float32 / float16 is uploaded in its own type with
 solver's GPU is read where it lives (_solver.as_source).  ``sample_weight`` (n values >= 0) and ``class_weight``
 ("balanced": c_i = n / (2 n_{y_i}), or a dict {+1: a, -1: b}) weigh the rows of an erm problem: F(w) = (1/n) sum_i c_i
 loss_i(w) + R(w) (include/rbl.h: rbl_set_row_weights); ``sample_weight_`` holds the resolved vector (None without
-weights), ``set_sample_weight(c)`` replaces it between ``main_loop`` calls or iterations.
+weights), ``set_sample_weight(c)`` replaces it between ``main_loop`` calls or iterations.  ``gram`` ("auto" | "dense" |
+"none"): the w-step's route.  "dense" forms G = D^T D and solves in Gram space; "none" (storage "csr" only) never forms it
+and applies rho D^T D + diag(.) through the sparse passes (CG for l2, FISTA for l1 / elastic net; include/rbl.h:
+RBL_CREATE_NO_GRAM) - the route for more than 16 384 columns, where "auto" picks it; everywhere else "auto" is "dense".
+A solver on borrowed data (``share_data``) must name the route of the solver that owns them.
 """
 import time
 
@@ -47,9 +51,10 @@ class Optimizer:
     def __init__(self, X, y, weight_function="erm", loss="binary_cross_entropy", l2_reg=None, l1_reg=None,
                  B=None, n_class=None, args=None, w0=None, max_iter=200, tol=1e-4, storage="f32", device=0,
                  _wstep=None, _smooth_t=1.0, share_data=None, l1_weights=None, l2_weights=None, fit_intercept=False,
-                 standardize=False, sample_weight=None, class_weight=None):
+                 standardize=False, sample_weight=None, class_weight=None, gram="auto"):
         # argument checks in the reference's order (objective first :22, then :55-68)
         _solver.check_problem(weight_function, loss, B, args)
+        _solver.check_gram_mode(gram)
         if l1_reg is None and l2_reg is None and l1_weights is None and l2_weights is None:
             raise ValueError("More arguments: l1_reg or l2_reg not l1_reg and l2_reg!")       # :62
         if B is not None and weight_function != "ehrm":
@@ -76,6 +81,8 @@ class Optimizer:
         self.weight_function = weight_function                                                # :73
         self.l1_reg, self.l2_reg = l1_reg, l2_reg
         wstep = _wstep if _wstep is not None else (_lib.WSTEP_L1 if self.w_flag == 1 else _lib.WSTEP_L2)
+        # the w-step's route: "dense" (Gram space) or "none" (operator w-step, storage "csr"); argument errors come now
+        self.gram = _solver.resolve_gram(gram, storage, self.num_feature)
         # share_data: another solver of this package built on the same X - its device D and DTD are borrowed; a y that
         # differs from that solver's becomes this solver's own labels (include/rbl.h: rbl_set_labels)
         share = None
@@ -90,6 +97,10 @@ class Optimizer:
                 raise ValueError("share_data was built with another storage type or device")
             if y is not None:
                 y_own = _solver.as_pm1_labels(y, self.num_row)      # shape / +-1 before any device call
+        if self.gram == "none" and wstep == _lib.WSTEP_SMOOTH_L1:
+            raise ValueError('smoothADMMmethod needs the Gram matrix (its w-step preconditions with diag(G)): it has no '
+                             'gram="none" route' + (f", and storage=\"csr\" with {self.num_feature} coordinates has no "
+                                                    "other - use ADMMmethod" if gram == "auto" else ""))
         # row weights (erm only): validated on the host before any device call; None = the unweighted path
         self.sample_weight_ = None
         if sample_weight is not None or class_weight is not None:
@@ -100,7 +111,7 @@ class Optimizer:
             self.sample_weight_ = _solver.resolve_row_weights(y_w, sample_weight, class_weight, weight_function)
         self._s = _solver.Solver(self.num_row, self.num_feature, weight_function, loss, reg=self.reg, wstep=wstep,
                                  B=B, args=args, smooth_t=_smooth_t, tol=tol, max_iter=max_iter, storage=storage,
-                                 device=device, share=share)
+                                 device=device, share=share, gram=self.gram)
         if share is None:
             self._s.set_data(src, y, scaling="fit" if self.standardize else "none",
                              ones_column=self.fit_intercept)                                  # :23 D = -y*X
@@ -206,6 +217,9 @@ class Optimizer:
 
     @property
     def DTD(self):
+        if self.gram == "none":
+            raise ValueError(f'DTD: this solver runs with gram="none" - it never forms the {self.num_feature} x '
+                             f'{self.num_feature} Gram matrix (the w-step applies D^T (D p) through the sparse passes)')
         D = self._s.get_D()
         return D.T @ D
 
@@ -296,12 +310,12 @@ class ADMMmethod(Optimizer):
     def __init__(self, X, y, weight_function="erm", loss="binary_cross_entropy", l2_reg=None, l1_reg=None, B=None,
                  n_class=None, args=None, w0=None, max_iter=200, tol=1e-4, storage="f32", device=0,
                  l1_weights=None, l2_weights=None, fit_intercept=False, standardize=False, sample_weight=None,
-                 class_weight=None, share_data=None):
-        # (share_data stays the trailing keyword; the six before it are meant to be given by name)
+                 class_weight=None, gram="auto", share_data=None):
+        # (share_data stays the trailing keyword; the seven before it are meant to be given by name)
         super().__init__(X, y, weight_function, loss, l2_reg, l1_reg, B, n_class, args, w0, max_iter, tol,
                          storage=storage, device=device, share_data=share_data, l1_weights=l1_weights,
                          l2_weights=l2_weights, fit_intercept=fit_intercept, standardize=standardize,
-                         sample_weight=sample_weight, class_weight=class_weight)
+                         sample_weight=sample_weight, class_weight=class_weight, gram=gram)
 
     def start_store(self, X, y, weight_function="erm", loss="binary_cross_entropy", B=None, l2_reg=None,
                     l1_reg=None, n_class=None, args=None, sample_weight_test=None):
@@ -323,14 +337,17 @@ class smoothADMMmethod(Optimizer):
     def __init__(self, X, y, weight_function="erm", loss="binary_cross_entropy", B=None, l2_reg=None, l1_reg=None,
                  n_class=None, args=None, w0=None, t=1, max_iter=200, tol=1e-4, storage="f32", device=0,
                  l1_weights=None, l2_weights=None, fit_intercept=False, standardize=False, sample_weight=None,
-                 class_weight=None, share_data=None):
+                 class_weight=None, gram="auto", share_data=None):
+        if gram not in ("auto", "dense"):
+            raise ValueError(f'smoothADMMmethod: gram must be "auto" or "dense", got {gram!r} (the smoothed-l1 w-step '
+                             "preconditions with diag(G): it needs the Gram matrix)")
         if l1_weights is not None or l2_weights is not None or fit_intercept:
             raise ValueError("smoothADMMmethod has no per-coordinate penalties: l1_weights, l2_weights and fit_intercept "
                              "belong to ADMMmethod (the smoothed-l1 w-step smooths one scalar l1 norm)")
         wstep = _lib.WSTEP_SMOOTH_L1 if l1_reg is not None else None
         super().__init__(X, y, weight_function, loss, l2_reg, l1_reg, B, n_class, args, w0, max_iter, tol,
                          storage=storage, device=device, _wstep=wstep, _smooth_t=float(t), share_data=share_data,
-                         standardize=standardize, sample_weight=sample_weight, class_weight=class_weight)
+                         standardize=standardize, sample_weight=sample_weight, class_weight=class_weight, gram=gram)
 
     @property
     def t(self):
@@ -376,7 +393,7 @@ class ADMMgroup:
     storage."""
 
     _KEYS = ("weight_function", "loss", "l2_reg", "l1_reg", "B", "args", "w0", "smooth", "t", "y", "l1_weights",
-             "l2_weights", "fit_intercept", "standardize", "sample_weight", "class_weight", "share_sparse")
+             "l2_weights", "fit_intercept", "standardize", "sample_weight", "class_weight", "share_sparse", "gram")
 
     def __init__(self, X, y, problems, storage="f32", device=0, max_iter=200, tol=1e-4):
         if not isinstance(problems, (list, tuple)) or len(problems) == 0:
@@ -413,6 +430,13 @@ class ADMMgroup:
                     raise ValueError("standardize must be the same for every problem of a group (one data matrix)")
                 if bool(pr.get("share_sparse")) != bool(problems[0].get("share_sparse")):
                     raise ValueError("share_sparse must be the same for every problem of a group (one set of passes)")
+                _solver.check_gram_mode(pr.get("gram", "auto"))
+                if pr.get("gram", "auto") != problems[0].get("gram", "auto"):
+                    raise ValueError("gram must be the same for every problem of a group (one data matrix, one route)")
+                if pr.get("smooth") and pr.get("gram", "auto") == "none":
+                    raise ValueError('smooth=True members have no gram="none" route (the smoothed-l1 w-step needs diag(G))')
+                if storage in _lib.STORAGE:
+                    _solver.resolve_gram(pr.get("gram", "auto"), storage, X.shape[1] + (1 if pr.get("fit_intercept") else 0))
                 _solver.resolve_penalty(X.shape[1], pr.get("l1_reg"), pr.get("l2_reg"), pr.get("l1_weights"),
                                         pr.get("l2_weights"), bool(pr.get("fit_intercept")))
                 if pr.get("B") is not None and pr["weight_function"] != "ehrm":
@@ -439,12 +463,13 @@ class ADMMgroup:
             yk = pr["y"] if pr.get("y") is not None else y
             if pr.get("smooth"):
                 s = smoothADMMmethod(X, yk, pr["weight_function"], pr["loss"], t=pr.get("t", 1), max_iter=max_iter, tol=tol,
-                                     storage=storage, device=device, share_data=share, standardize=bool(pr.get("standardize")), **kw)
+                                     storage=storage, device=device, share_data=share, standardize=bool(pr.get("standardize")),
+                                     gram=pr.get("gram", "auto"), **kw)
             else:
                 s = ADMMmethod(X, yk, pr["weight_function"], pr["loss"], max_iter=max_iter, tol=tol, storage=storage,
                                device=device, share_data=share, l1_weights=pr.get("l1_weights"),
                                l2_weights=pr.get("l2_weights"), fit_intercept=bool(pr.get("fit_intercept")),
-                               standardize=bool(pr.get("standardize")), **kw)
+                               standardize=bool(pr.get("standardize")), gram=pr.get("gram", "auto"), **kw)
             self.solvers.append(s)
         self._group = _solver.Group([s._s for s in self.solvers], share_sparse=bool(self.problems[0].get("share_sparse")))
         self.store = False
@@ -535,8 +560,10 @@ class OneVsRest:
 
     def __init__(self, X, labels, weight_function="erm", loss="binary_cross_entropy", l2_reg=None, l1_reg=None, B=None,
                  args=None, storage="f32", device=0, max_iter=200, tol=1e-4, l1_weights=None, l2_weights=None,
-                 fit_intercept=False, standardize=False, sample_weight=None, class_weight=None, share_sparse=False):
+                 fit_intercept=False, standardize=False, sample_weight=None, class_weight=None, share_sparse=False,
+                 gram="auto"):
         _solver.check_share_sparse(share_sparse)     # before anything touches the device
+        _solver.check_gram_mode(gram)
         # class_weight="balanced": every member gets the balanced weights of its OWN +-1 labels (one class against the
         # rest is imbalanced by construction); a common sample_weight multiplies into all of them
         Xm = _solver.as_source(X, device)
@@ -553,7 +580,7 @@ class OneVsRest:
         problems = [dict(weight_function=weight_function, loss=loss, l2_reg=l2_reg, l1_reg=l1_reg, B=B, args=args, y=yk,
                          l1_weights=l1_weights, l2_weights=l2_weights, fit_intercept=self.fit_intercept,
                          standardize=bool(standardize), sample_weight=sample_weight, class_weight=class_weight,
-                         share_sparse=share_sparse)
+                         share_sparse=share_sparse, gram=gram)
                     for yk in ys]
         self._storage, self._device = storage, device
         self.group = ADMMgroup(Xm, ys[0], problems, storage=storage, device=device, max_iter=max_iter, tol=tol)

@@ -9,20 +9,21 @@ except ImportError:      # package directory on sys.path: imported as ``src.util
     import _solver
 
 
-def calculate_accuracy(w, X_test, y_test, threshold=0.5, loss='binary_cross_entropy', scaling=None):
+def calculate_accuracy(w, X_test, y_test, threshold=0.5, loss='binary_cross_entropy', scaling=None, storage="f32"):
     """Fraction of rows with prediction == label (reference calculate_acc.py:3-19).
     binary_cross_entropy: predict +1 iff sigmoid(x.w) >= threshold.  hinge: the reference sets
     every prediction to +1 (calculate_acc.py:13-15); mirrored as is.  squared_hinge (not a loss of the reference):
     predict +1 iff x.w >= 0, ``threshold`` is ignored.  X_test is taken as it is (float64 / float32 / float16, host or
     GPU 0).  ``scaling``: (mean, scale) of a solver trained with standardize=True (``scale_mean_``, ``scale_scale_``) -
     X_test is standardised with them on the device; a w with one entry more than X_test has columns carries the
-    intercept last."""
+    intercept last.  ``storage``: how the test matrix is held on the device, as in ADMMmethod; "csr" keeps a sparse X_test
+    sparse (the dense passes stop at 19 200 columns, the sparse ones at none)."""
     if loss not in ('binary_cross_entropy', 'hinge', 'squared_hinge'):
         raise ValueError(f"loss '{loss}' is not supported! Options: ['binary_cross_entropy','hinge','squared_hinge']")
     X = _solver.as_source(X_test, 0)
     w = np.asarray(w, dtype=np.float64).reshape(-1)
     ones = scaling is not None and w.size == X.shape[1] + 1
-    s = _solver.Solver(X.shape[0], X.shape[1] + (1 if ones else 0), "erm", loss, objective_only=True)
+    s = _solver.Solver(X.shape[0], X.shape[1] + (1 if ones else 0), "erm", loss, objective_only=True, storage=storage)
     try:
         if scaling is not None:
             s.set_scaling(*_solver.as_scaling(scaling[0], scaling[1], s.d, ones))

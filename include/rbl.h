@@ -112,7 +112,9 @@ typedef struct rbl_stats {
                                 weights), 2 = banded path not certified, redone with the sort; -1 = n/a */
     int32_t wstep_form;      /* how the w-step ran: 0 = batches of launches (CG / nonlinear CG / FISTA), 1 = ONE persistent
                                 launch (k_cg_persist / k_ncg_persist), 2 = the exact active-set lasso kernel, 3 = the
-                                eigen-decomposition ridge, -1 = an overridden w_subproblem (rbl_phase_w_external) */
+                                eigen-decomposition ridge, 4 = the operator route of a handle without a Gram matrix
+                                (RBL_CREATE_NO_GRAM: CG / FISTA on rho D^T (D p) + diag(.) p, batches of launches),
+                                -1 = an overridden w_subproblem (rbl_phase_w_external) */
 } rbl_stats;
 
 typedef struct rbl_solver rbl_solver;
@@ -128,6 +130,27 @@ int  rbl_device_count(void);
 /* Optimizer.__init__ / rankbasedObjective.__init__ */
 int  rbl_create(const rbl_config* cfg, rbl_solver** out);
 int  rbl_destroy(rbl_solver* h);
+/* rbl_create with options; flags = 0 is rbl_create.
+ *   RBL_CREATE_NO_GRAM  (RBL_STORE_CSR only)  The handle never holds G = D^T D.  Every w-step applies
+ *     A = rho D^T D + reg I (or + diag(l2), rbl_set_penalty) as an operator, A p = rho D^T (D p) + ..., through the two
+ *     sparse passes: warm-started CG for RBL_WSTEP_L2, FISTA with gradient restart for RBL_WSTEP_L1 (per-coordinate
+ *     thresholds and free coordinates included; the exact active-set kernel needs G and is not used), with the stop rules
+ *     of the Gram route.  rbl_stats.wstep_form is 4.  Nothing of size d^2 is allocated - no G, no eigenbasis, no lasso
+ *     workspace - only one more n-vector and d-vectors, so d is not bounded by the Gram route's ld <= 16 384.  The
+ *     d-space sums run in a fixed order that depends on ld alone: the iterates do not depend on the grid.
+ *     rbl_gram_local forms nothing (rbl_gram_info reports route 0, "no Gram matrix"); rbl_gram_finish takes the step
+ *     constant L = 1.02 lambda_max(D^T D) from 100 power-iteration steps through the operator.  The call order is that
+ *     of every handle.  The z-step, the dual update, the residuals, the rho schedule, row weights and own labels do not
+ *     see G and are what they are elsewhere.  RBL_BUF_G is RBL_ERR_STATE on such a handle.  RBL_ERR_INVALID, with the
+ *     reason: a storage type other than RBL_STORE_CSR; RBL_WSTEP_SMOOTH_L1 on a handle that iterates (its preconditioner
+ *     is diag(G)); an unknown flag bit.
+ * rbl_create_shared on such an owner gives handles of the same kind (their cfg follows the same rules; D_k^T D_k = D^T D
+ * for own labels, so the operator is the owner's).
+ *   Without the flag, RBL_STORE_CSR with ld > 16 384 on a handle that iterates is RBL_ERR_INVALID at create (the message
+ * names RBL_CREATE_NO_GRAM): the Gram route would allocate ld^2 doubles and refuse the first w-step.
+ * The presence of this symbol is the capability probe (RBL_VERSION is unchanged). */
+#define RBL_CREATE_NO_GRAM 1
+int  rbl_create_opts(const rbl_config* cfg, uint32_t flags, rbl_solver** out);
 /* A second problem on the SAME (X, y): Optimizer.__init__ again with other weight_function / loss / regulariser / args
  * (examples/run_srm.py:57,68 builds ADMMmethod and smoothADMMmethod on one X_train), without algorithms.py:23-24 being
  * paid again.  The handle borrows the owner's device D = -y*X, G = D^T D and what derives from G alone (Lipschitz
@@ -694,6 +717,17 @@ int  rbl_k_wstep(int wstep, int64_t d, const double* G, const double* q, double 
  * else CG; *form as rbl_stats.wstep_form reports it (2 active-set kernel, 0 / 1 CG or FISTA) */
 int  rbl_k_wstep_pen(int64_t d, const double* G, const double* q, double rho, const double* l1, const double* l2,
                      const double* w0, double tol, double* w_out, int* iters, int* form);
+/* The operator w-step of RBL_CREATE_NO_GRAM over host buffers: the CSR arrays hold D itself (n x d, canonical rows, as
+ * rbl_k_csr_gemv takes them); both forms are built, L = 1.02 lambda_max(D^T D) comes from the power iteration through the
+ * operator as on a handle, then ONE w-step: wstep 2 solves (rho D^T D + reg I) w = rho q by CG, wstep 1 the lasso
+ * min 1/2 w'D^T D w - q'w + reg/(2 rho) ||w||_1 by FISTA; with l1 / l2 (d each, either may be NULL) the per-coordinate
+ * forms of rbl_set_penalty (reg is then not used).  w_inout: ld = d rounded up to 4 doubles - in: the warm start (the
+ * first d are read), out: all ld, the padding as the kernels left it (+0.0).  num_cu sizes the grids of the sparse
+ * passes (0: the device's); no bit of the result depends on it.  *status: 1 converged, 0 max_inner reached.
+ * RBL_WSTEP_SMOOTH_L1, NULL pointers, n or d < 1 are RBL_ERR_INVALID with a message. */
+int  rbl_k_wstep_op(int wstep, int64_t n, int64_t d, const int64_t* indptr, const int32_t* indices, const double* values,
+                    const double* q, double rho, double reg, const double* l1 /* NULL */, const double* l2 /* NULL */,
+                    double tol, int max_inner, int num_cu, double* w_inout, int* iters, int* status);
 /* K >= 1 w-steps one after another on ONE workspace, as consecutive ADMM iterations run them: step k solves for the
  * right-hand side Q[k] (K x d), warm-started from the w of step k - 1 (step 0 from w0, NULL = 0), through run_wstep
  * unchanged - the batch sizes, the back-off of the nonlinear CG's linear phase, the exchange tags and the uncleared
