@@ -27,6 +27,9 @@ SCALING = {"none": 0, "fit": 1, "apply": 2}
 DATA_ONES_COLUMN = 1
 GROUP_SHARE_SPARSE = 1          # rbl_group_create_opts: shared multi-column passes on storage "csr"
 CREATE_NO_GRAM = 1              # rbl_create_opts: no Gram matrix, the operator w-step (storage "csr")
+CREATE_WORKING_SET = 2          # ... and the exact working-set lasso as its l1 w-step (with CREATE_NO_GRAM, wstep l1)
+L1_SOLVERS = ("fista", "working_set")
+WS_CAP, WS_SELECT = 1024, 64    # csrc/wset_plan.h: slots of the working set, columns one scan adds at most
 GRAM_MAX_LD = 16384             # the widest ld of the Gram-space w-step (csrc/rbl_internal.h: RBL_GRAM_MAX_LD)
 GRAM_MODES = ("auto", "dense", "none")
 # rbl_set_data_csr: the type of indptr and indices
@@ -114,6 +117,19 @@ class RblGramReport(C.Structure):
         ("pair_products", C.c_int64), ("dense_products", C.c_int64), ("transient_bytes", C.c_int64),
         ("ms", C.c_float),
     ]
+
+
+class RblWsetReport(C.Structure):
+    """rbl_wset_report of include/rbl.h: the working set after the last w-step"""
+    _fields_ = [
+        ("slots", C.c_int32), ("support", C.c_int32), ("rounds", C.c_int32), ("pass_pairs", C.c_int32),
+        ("rows_last", C.c_int32), ("fista_on_gs", C.c_int32), ("left_route", C.c_int32), ("form", C.c_int32),
+        ("rows_total", C.c_int64), ("evictions", C.c_int64), ("bytes", C.c_int64),
+    ]
+
+
+def _wset_report_dict(r):
+    return {name: int(getattr(r, name)) for name, _ in RblWsetReport._fields_}
 
 
 def _gram_report_dict(r):
@@ -255,6 +271,11 @@ SIGNATURES = {
     "rbl_csr_gram_route": (C.c_int, [C.c_int64, C.c_int64, C.c_int64]),
     "rbl_k_wstep": (C.c_int, [C.c_int, C.c_int64, _P, _P, C.c_double, C.c_double, C.c_double, _P, C.c_double, _P,
                               C.POINTER(C.c_int)]),
+    "rbl_wset_info": (C.c_int, [_P, C.POINTER(RblWsetReport)]),
+    "rbl_k_wset_gram": (C.c_int, [C.c_int64, C.c_int64, _P, _P, _P, _P, C.c_int, _P, C.c_int, C.c_int, _P]),
+    "rbl_k_wset_scan": (C.c_int, [C.c_int64, C.c_int64, _P, _P, _P, _P, C.c_double, C.c_int, _P, C.POINTER(C.c_int)]),
+    "rbl_k_wstep_ws": (C.c_int, [C.c_int64, C.c_int64, _P, _P, _P, C.c_int, _P, C.c_double, C.c_double, _P, _P, C.c_double,
+                                 C.c_int, C.c_int, C.c_int, _P, _P, C.POINTER(RblWsetReport)]),
     "rbl_k_wstep_op": (C.c_int, [C.c_int, C.c_int64, C.c_int64, _P, _P, _P, _P, C.c_double, C.c_double, _P, _P, C.c_double,
                                 C.c_int, C.c_int, _P, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "rbl_k_wstep_pen": (C.c_int, [C.c_int64, _P, _P, C.c_double, _P, _P, _P, C.c_double, _P, C.POINTER(C.c_int),
@@ -709,6 +730,55 @@ def k_wstep_op(wstep, A, q, rho, reg=0.0, l1=None, l2=None, w0=None, tol=1e-13, 
     check(load().rbl_k_wstep_op(int(wstep), n, d, ptr(ip), ptr(ix), ptr(va), ptr(q), float(rho), float(reg), ptr(l1), ptr(l2),
                                 float(tol), int(max_inner), int(num_cu), ptr(w), C.byref(it), C.byref(status)))
     return w, it.value, status.value
+
+
+def k_wset_gram(A, cols, split=None, num_cu=0):
+    """The working set's sub-Gram matrix (include/rbl.h: rbl_k_wset_gram): the columns ``cols`` of the canonical
+    scipy.sparse CSR matrix A appended in that order - in calls of split[0], split[1], ... columns - -> Gs, WS_CAP x WS_CAP
+    (slot a = cols[a]; the unused slots zero)"""
+    n, d, ip, ix, va = _csr_arrays(A)
+    cols = np.ascontiguousarray(cols, dtype=np.int32).reshape(-1)
+    sp_ = None if split is None else np.ascontiguousarray(split, dtype=np.int32).reshape(-1)
+    Gs = np.empty((WS_CAP, WS_CAP))
+    check(load().rbl_k_wset_gram(n, d, ptr(ip), ptr(ix), ptr(va), ptr(cols), int(cols.size), ptr(sp_),
+                                 0 if sp_ is None else int(sp_.size), int(num_cu), ptr(Gs)))
+    return Gs
+
+
+def k_wset_scan(g, kappa, member, d=None, q=None, tol=1e-13, take=WS_SELECT):
+    """The scan's choice on prescribed vectors (include/rbl.h: rbl_k_wset_scan): g, kappa, member of ld entries (ld even),
+    the columns >= d never chosen -> the list of chosen columns, in the order they are chosen"""
+    g, kappa = f64(g).reshape(-1), f64(kappa).reshape(-1)
+    ld = g.size
+    member = np.ascontiguousarray(member, dtype=np.int32).reshape(-1)
+    q = None if q is None else f64(q).reshape(-1)
+    if kappa.size != ld or member.size != ld or (q is not None and q.size != ld):
+        raise ValueError(f"g has {ld} entries; kappa, member and q must have as many")
+    out, cnt = np.zeros(WS_SELECT, dtype=np.int32), C.c_int(0)
+    check(load().rbl_k_wset_scan(ld, ld if d is None else int(d), ptr(g), ptr(kappa), ptr(q), ptr(member), float(tol), int(take),
+                                 ptr(out), C.byref(cnt)))
+    return out[:cnt.value].tolist()
+
+
+def k_wstep_ws(A, Q, rho, reg=0.0, l1=None, l2=None, w0=None, tol=1e-13, max_inner=100000, num_cu=0, ws_cap=0):
+    """K working-set w-steps one after another on one workspace (include/rbl.h: rbl_k_wstep_ws) on the canonical
+    scipy.sparse CSR matrix A = D; Q: (K, d) or (d,).  Returns (W of shape (K, ld) - the padding included -, the K reports
+    as dicts of rbl_wset_report's fields)."""
+    n, d, ip, ix, va = _csr_arrays(A)
+    Q = f64(np.atleast_2d(Q))
+    if Q.shape[1] != d:
+        raise ValueError(f"Q has {Q.shape[1]} columns for {d} columns of A")
+    K = Q.shape[0]
+    l1 = None if l1 is None else f64(np.broadcast_to(np.asarray(l1, dtype=np.float64), (d,)))
+    l2 = None if l2 is None else f64(np.broadcast_to(np.asarray(l2, dtype=np.float64), (d,)))
+    w0 = None if w0 is None else f64(w0).reshape(-1)
+    if w0 is not None and w0.size != d:
+        raise ValueError(f"w0 has {w0.size} entries for {d} columns")
+    W = np.zeros((K, storage_ld(d, "csr")))
+    reps = (RblWsetReport * K)()
+    check(load().rbl_k_wstep_ws(n, d, ptr(ip), ptr(ix), ptr(va), K, ptr(Q), float(rho), float(reg), ptr(l1), ptr(l2), float(tol),
+                                int(max_inner), int(num_cu), int(ws_cap), ptr(w0), ptr(W), reps))
+    return W, [_wset_report_dict(r) for r in reps]
 
 
 def k_wstep_seq(wstep, G, Q, rho, reg, w0=None, smooth_t=1.0, tol=1e-13, max_inner=100000, l1=None, l2=None, route=0,

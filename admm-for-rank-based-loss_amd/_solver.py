@@ -387,6 +387,25 @@ def resolve_gram(gram, storage, d):
     return gram
 
 
+def resolve_l1_solver(l1_solver, has_l1, storage, gram_route):
+    """The l1 w-step of a gram="none" solver: "fista" (FISTA on the operator - the default, and the only value elsewhere)
+    or "working_set" (the exact working-set lasso, RBL_CREATE_WORKING_SET).  "working_set" needs an l1 penalty
+    (l1_reg / l1_weights), storage "csr" and the gram="none" route.  Raises ValueError - before any device call -
+    otherwise.  -> the create flag it adds (0 for "fista")."""
+    check_l1_solver(l1_solver)
+    if l1_solver == "fista":
+        return 0
+    if not has_l1:
+        raise ValueError('l1_solver="working_set" is the lasso / elastic-net w-step: it needs l1_reg or l1_weights')
+    if storage != "csr":
+        raise ValueError(f'l1_solver="working_set" needs storage="csr" (the working set is built from the sparse entries), '
+                         f"got storage={storage!r}")
+    if gram_route != "none":
+        raise ValueError('l1_solver="working_set" needs gram="none": with gram="dense" the l1 w-step is the exact active-set '
+                         "kernel on G already")
+    return _lib.CREATE_WORKING_SET
+
+
 def as_scaling(mean, scale, d, ones_column=False):
     """(mean, scale) for d coordinates as float64; with ones_column the vectors of the d - 1 features are accepted and
     the unscaled column's (0, 1) appended"""
@@ -406,7 +425,7 @@ class Solver:
 
     def __init__(self, n, d, weight_function="erm", loss="binary_cross_entropy", reg=0.0, wstep=_lib.WSTEP_L2,
                  B=None, args=None, smooth_t=1.0, rho0=0.0, tol=1e-4, w_tol=0.0, max_iter=200, storage="f32",
-                 device=0, objective_only=False, n_total=None, row_offset=0, share=None, gram="auto"):
+                 device=0, objective_only=False, n_total=None, row_offset=0, share=None, gram="auto", l1_solver="fista"):
         self._h = None
         self._share = share           # keeps the data's owner referenced (the library counts references itself)
         if storage not in _lib.STORAGE:
@@ -418,6 +437,13 @@ class Solver:
                              'gram="none" route' + (f" - and storage=\"csr\" with {d} coordinates has no other" if gram == "auto" else ""))
         if isinstance(share, Solver) and not objective_only and not share.cfg.objective_only and share.gram_route != self.gram_route:
             raise ValueError(f'gram={gram!r} on data shared with a gram="{share.gram_route}" solver: one data matrix, one route')
+        # "fista" or "working_set" (resolve_l1_solver); a borrower is what its owner is
+        ws_flag = 0 if objective_only else resolve_l1_solver(l1_solver, int(wstep) == _lib.WSTEP_L1, storage, self.gram_route)
+        self.l1_solver = "working_set" if ws_flag else "fista"
+        if isinstance(share, Solver) and not objective_only and not share.cfg.objective_only and \
+                getattr(share, "l1_solver", "fista") != self.l1_solver:
+            raise ValueError(f'l1_solver={l1_solver!r} on data shared with an l1_solver="{getattr(share, "l1_solver", "fista")}" '
+                             "solver: a borrower follows its owner")
         self.lib = _lib.load()
         cfg = _lib.RblConfig()
         cfg.n, cfg.d = int(n), int(d)
@@ -449,7 +475,7 @@ class Solver:
                 raise ValueError("share must be a live Solver")
             _lib.check(self.lib.rbl_create_shared(C.byref(cfg), share._h, C.byref(h)))
         else:
-            flags = _lib.CREATE_NO_GRAM if self.gram_route == "none" and not objective_only else 0
+            flags = (_lib.CREATE_NO_GRAM if self.gram_route == "none" and not objective_only else 0) | ws_flag
             _lib.check(self.lib.rbl_create_opts(C.byref(cfg), flags, C.byref(h)))
         self._h = h
 
@@ -588,6 +614,12 @@ class Solver:
         rep = _lib.RblGramReport()
         _lib.check(self.lib.rbl_gram_info(self._h, C.byref(rep)))
         return _lib._gram_report_dict(rep)
+
+    def wset_info(self):
+        """the working set after the last w-step (include/rbl.h: rbl_wset_report) of an l1_solver="working_set" solver"""
+        rep = _lib.RblWsetReport()
+        _lib.check(self.lib.rbl_wset_info(self._h, C.byref(rep)))
+        return _lib._wset_report_dict(rep)
 
     def get_D(self):
         out = np.empty((self.n, self.d))
@@ -873,6 +905,12 @@ def check_gram_mode(value):
     """``gram`` of ADMMmethod / ADMMgroup / OneVsRest names a route: anything else is an argument error (no device call)"""
     if value not in _lib.GRAM_MODES:
         raise ValueError(f"gram must be one of {list(_lib.GRAM_MODES)}, got {value!r}")
+
+
+def check_l1_solver(value):
+    """``l1_solver`` of ADMMmethod / ADMMgroup / OneVsRest names an l1 w-step: anything else is an argument error"""
+    if value not in _lib.L1_SOLVERS:
+        raise ValueError(f"l1_solver must be one of {list(_lib.L1_SOLVERS)}, got {value!r}")
 
 
 def check_share_sparse(value):

@@ -242,10 +242,25 @@ int validate(const rbl_config* c) {
 
 // RBL_CREATE_NO_GRAM and what it asks of the problem; the late failure of a wide csr handle on the Gram route is refused here
 int validate_gram_route(const rbl_config* c, uint32_t flags, const char* who) {
-    if (flags & ~(uint32_t)RBL_CREATE_NO_GRAM) {
-        rbl_set_error("%s: unknown flag bits 0x%x (RBL_CREATE_NO_GRAM = %d is the only flag)", who, flags & ~(uint32_t)RBL_CREATE_NO_GRAM,
-                      RBL_CREATE_NO_GRAM);
+    const uint32_t known = RBL_CREATE_NO_GRAM | RBL_CREATE_WORKING_SET;
+    if (flags & ~known) {
+        rbl_set_error("%s: unknown flag bits 0x%x (RBL_CREATE_NO_GRAM = %d and RBL_CREATE_WORKING_SET = %d are the flags)", who,
+                      flags & ~known, RBL_CREATE_NO_GRAM, RBL_CREATE_WORKING_SET);
         return RBL_ERR_INVALID;
+    }
+    if (flags & RBL_CREATE_WORKING_SET) {
+        if (!(flags & RBL_CREATE_NO_GRAM)) {
+            // (on a handle with a Gram matrix the bit means nothing: the message says so in the words of an unknown bit)
+            rbl_set_error("%s: unknown flag bits 0x%x on a handle with a Gram matrix: RBL_CREATE_WORKING_SET needs "
+                          "RBL_CREATE_NO_GRAM (the working set is the l1 w-step of a handle without a Gram matrix; the Gram "
+                          "route has its exact active-set kernel already)", who, RBL_CREATE_WORKING_SET);
+            return RBL_ERR_INVALID;
+        }
+        if (!c->objective_only && c->wstep != RBL_WSTEP_L1) {
+            rbl_set_error("%s: RBL_CREATE_WORKING_SET needs cfg.wstep == RBL_WSTEP_L1 (the lasso / elastic-net w-step; got wstep %d)",
+                          who, c->wstep);
+            return RBL_ERR_INVALID;
+        }
     }
     if (flags & RBL_CREATE_NO_GRAM) {
         if (c->storage != RBL_STORE_CSR) {
@@ -280,6 +295,21 @@ int build_sigma_prefix(rbl_solver* h) {
 extern "C" {
 
 int rbl_version(void) { return RBL_VERSION; }
+
+int rbl_wset_info(rbl_solver* h, rbl_wset_report* out) {
+    RBL_ENTER_ITER(h);
+    if (!out) {
+        rbl_set_error("wset_info: out is NULL");
+        return RBL_ERR_INVALID;
+    }
+    if (!h->wset) {
+        rbl_set_error("wset_info: this handle has no working set (rbl_create_opts with RBL_CREATE_WORKING_SET)");
+        return RBL_ERR_STATE;
+    }
+    *out = h->wset->rep;
+    out->bytes = h->wset->bytes + (h->wset->Gs2 ? (int64_t)sizeof(double) * WS_CAP * WS_CAP : 0);
+    return RBL_OK;
+}
 
 int rbl_sizeof(int which) {
     return which == 0 ? (int)sizeof(rbl_config) : which == 1 ? (int)sizeof(rbl_stats) : which == 2 ? (int)sizeof(rbl_wstep_report) :
@@ -399,6 +429,10 @@ static int create_setup(rbl_solver* h, rbl_solver* owner = nullptr) {
         if (h->no_gram) {   // the operator's n-vector and the chunk partials of its d-space kernels
             RBL_TRY(mem.alloc(&h->op_t, (size_t)(n > 0 ? n : 1)));
             RBL_TRY(mem.alloc(&h->op_part, op_part_doubles(ld)));
+            if (h->working_set) {
+                h->wset.reset(new WsetState());
+                RBL_TRY(alloc_wset(mem, *h->wset, ld, h->stream));
+            }
         }
     }
     RBL_TRY(mem.alloc((unsigned char**)&h->slab, h->slab_bytes));
@@ -472,7 +506,8 @@ int rbl_create_shared(const rbl_config* cfg, rbl_solver* owner, rbl_solver** out
         return RBL_ERR_INVALID;
     }
     // a borrower of a no-Gram owner is a no-Gram handle: its cfg follows the rules of the flag
-    RBL_TRY(validate_gram_route(cfg, owner->no_gram ? RBL_CREATE_NO_GRAM : 0, "create_shared"));
+    RBL_TRY(validate_gram_route(cfg, (owner->no_gram ? RBL_CREATE_NO_GRAM : 0) | (owner->working_set ? RBL_CREATE_WORKING_SET : 0),
+                                "create_shared"));
     if (!owner->data_ready) {
         rbl_set_error("create_shared: the owner has no data yet (rbl_set_data / rbl_generate_synthetic first)");
         return RBL_ERR_STATE;
@@ -492,6 +527,7 @@ int rbl_create_shared(const rbl_config* cfg, rbl_solver* owner, rbl_solver** out
     rbl_solver* h = new rbl_solver();
     h->cfg = *cfg;
     h->no_gram = owner->no_gram;
+    h->working_set = owner->working_set;
     if (cfg->device < 64) {
         g_live[cfg->device].fetch_add(1, std::memory_order_relaxed);
         h->counted = true;
@@ -523,6 +559,7 @@ int rbl_create_opts(const rbl_config* cfg, uint32_t flags, rbl_solver** out) {
     rbl_solver* h = new rbl_solver();
     h->cfg = *cfg;
     h->no_gram = (flags & RBL_CREATE_NO_GRAM) != 0;
+    h->working_set = (flags & RBL_CREATE_WORKING_SET) != 0;
     if (cfg->device < 64) {
         g_live[cfg->device].fetch_add(1, std::memory_order_relaxed);
         h->counted = true;
@@ -574,6 +611,7 @@ int rbl_set_state(rbl_solver* h, const double* w, const double* z, const double*
     if (w) {
         RBL_HIP(hipMemcpy(h->w, w, sizeof(double) * h->d, hipMemcpyHostToDevice));
         w_changed(h->der);
+        if (h->wset) h->wset->w_replaced();   // any S that holds the new support is valid: the next w-step finds it
     }
     if (z && h->z) {
         RBL_TRY(upload_rows(h, h->z, z));

@@ -873,6 +873,7 @@ int rbl_set_penalty(rbl_solver* h, const double* l1, const double* l2) {
     h->ww.pen_l1 = h->pen;
     h->ww.pen_l2 = h->pen + ld;
     h->ww.pen_l2max = l2max;
+    if (h->wset) h->wset->built = false;   // which coordinates are free may have changed: the working set is built again
     return RBL_OK;
 }
 

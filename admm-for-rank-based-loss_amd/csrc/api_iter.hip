@@ -274,6 +274,7 @@ int cancel_spec(rbl_solver* h) {
     h->spec_w = false;
     h->spec_timed = false;
     RBL_HIP(hipMemcpyAsync(h->w, h->w_prev, sizeof(double) * h->ld, hipMemcpyDeviceToDevice, h->stream));
+    if (h->wset) h->wset->w_replaced();
     RBL_HIP(hipStreamSynchronize(h->stream));
     return RBL_OK;
 }
@@ -501,6 +502,7 @@ int rbl_phase_w_external(rbl_solver* h, const double* w) {
     // D^T lambda is re-seeded by the next rbl_phase_q (a caller that skipped rbl_phase_q: nothing of a previous pass is
     // pending any more)
     w_changed(h->der);
+    if (h->wset) h->wset->w_replaced();
     drop_look_ahead(h->der);
     h->inner_iters = 0;
     h->ww.form = -1;
@@ -559,8 +561,18 @@ static int phase_w_body(rbl_solver* h) {
         // there is no rho prediction and the statistics of the new w follow as on the !predict branch
         OpData op;
         RBL_TRY(op_data(h, &op));
-        RBL_TRY(run_wstep_op(wstep, op, h->ld, h->q, h->step_rho, h->cfg.reg, h->L, h->cfg.w_tol, 100000, h->w, h->ww,
-                             &h->inner_iters, h->stream));
+        if (h->wset && wstep == RBL_WSTEP_L1) {
+            // the exact working-set lasso (wstep_ws.hip); Gs belongs to the data epoch it was formed in
+            if (h->wset->epoch != h->sd->epoch) {
+                h->wset->built = false;
+                h->wset->epoch = h->sd->epoch;
+            }
+            RBL_TRY(run_wstep_ws(op, h->ld, h->d, h->q, h->step_rho, h->cfg.reg, h->L, h->cfg.w_tol, 100000, h->w, h->ww, *h->wset,
+                                 WS_CAP, h->pen ? h->pen_host.data() : nullptr, &h->inner_iters, h->stream));
+        } else {
+            RBL_TRY(run_wstep_op(wstep, op, h->ld, h->q, h->step_rho, h->cfg.reg, h->L, h->cfg.w_tol, 100000, h->w, h->ww,
+                                 &h->inner_iters, h->stream));
+        }
         fs_pending = false;
     } else if (!spec) {
         h->ww.eig_ok = h->der.eig_ok;   // (run_wstep's view of it)
@@ -619,6 +631,8 @@ int rbl_phase_w(rbl_solver* h) {
     RBL_TRY(zb_resolve(h, &redone));
     if (!redone) return RBL_OK;
     RBL_HIP(hipMemcpyAsync(h->w, h->w_prev, sizeof(double) * h->ld, hipMemcpyDeviceToDevice, h->stream));
+    // the first pass may have changed S for the w it produced (a cold start, an eviction): w_prev's support is found again
+    if (h->wset) h->wset->w_replaced();
     return phase_w_body(h);
 }
 
@@ -788,6 +802,7 @@ int phase_finish_part(rbl_solver* h, rbl_stats* out, int part) {
             h->spec_timed = h->phase_timing;
         } else {
             RBL_HIP(hipMemcpyAsync(h->w, h->w_prev, sizeof(double) * h->ld, hipMemcpyDeviceToDevice, h->stream));
+            if (h->wset) h->wset->w_replaced();
         }
     }
     float ms[5] = {0, 0, 0, 0, 0};

@@ -1103,6 +1103,159 @@ int rbl_k_wstep_op(int wstep, int64_t n, int64_t d, const int64_t* indptr, const
     return RBL_OK;
 }
 
+// ---- the working-set lasso (wstep_ws.hip) piece by piece and as a handle runs it
+int rbl_k_wset_gram(int64_t n, int64_t d, const int64_t* indptr, const int32_t* indices, const double* values, const int32_t* cols,
+                    int ncols, const int32_t* split, int nsplit, int num_cu, double* Gs_out) {
+    const char* who = "rbl_k_wset_gram";
+    if (ncols < 0 || ncols > WS_CAP || (ncols > 0 && !cols) || !Gs_out || (split && nsplit < 1)) {
+        rbl_set_error("%s: bad argument (0 <= ncols <= %d, cols, Gs_out; split needs nsplit >= 1)", who, WS_CAP);
+        return RBL_ERR_INVALID;
+    }
+    std::vector<char> seen((size_t)(d > 0 ? d : 1), 0);
+    for (int i = 0; i < ncols; ++i) {
+        if (cols[i] < 0 || cols[i] >= d || seen[(size_t)cols[i]]) {
+            rbl_set_error("%s: cols[%d] = %d is outside [0, %lld) or appears twice", who, i, cols[i], (long long)d);
+            return RBL_ERR_INVALID;
+        }
+        seen[(size_t)cols[i]] = 1;
+    }
+    int64_t total = 0;
+    for (int k = 0; split && k < nsplit; ++k) {
+        if (split[k] < 0) total = -1;
+        if (total >= 0) total += split[k];
+    }
+    if (split && total != ncols) {
+        rbl_set_error("%s: the calls of split add up to %lld columns, ncols = %d", who, (long long)total, ncols);
+        return RBL_ERR_INVALID;
+    }
+    Scratch sc;
+    int cus = 0;
+    RBL_TRY(scratch_begin(sc, &cus));
+    if (num_cu == 0) num_cu = cus;
+    if (num_cu < 1 || num_cu > cus) {
+        rbl_set_error("%s: num_cu = %d outside 1..%d (the device's compute units; 0 = all)", who, num_cu, cus);
+        return RBL_ERR_INVALID;
+    }
+    CsrStore st;
+    int64_t ld = 0;
+    RBL_TRY(upload_csr(sc, who, n, d, indptr, indices, values, true, num_cu, &st, &ld));
+    WsetState W;
+    RBL_TRY(alloc_wset(sc.mem, W, ld, sc.s));
+    std::vector<int> c(cols, cols + ncols);
+    if (!split) {
+        RBL_TRY(wset_gram(&st, W, ld, c.data(), ncols, num_cu, sc.s));
+    } else {
+        int at = 0;
+        for (int k = 0; k < nsplit; ++k) {
+            RBL_TRY(wset_gram(&st, W, ld, c.data() + at, split[k], num_cu, sc.s));
+            at += split[k];
+        }
+    }
+    RBL_HIP(hipMemcpyAsync(Gs_out, W.Gs, sizeof(double) * (size_t)WS_CAP * WS_CAP, hipMemcpyDeviceToHost, sc.s));
+    RBL_HIP(hipStreamSynchronize(sc.s));
+    return RBL_OK;
+}
+
+int rbl_k_wset_scan(int64_t ld, int64_t d, const double* g, const double* kappa, const double* q, const int32_t* member, double tol,
+                    int take, int32_t* cols_out, int* count) {
+    const char* who = "rbl_k_wset_scan";
+    if (ld < 2 || (ld & 1) || d < 1 || d > ld || ld > 0x7fffffffLL || !g || !kappa || !member || !cols_out || !count || take < 0 ||
+        take > WS_SELECT || !std::isfinite(tol)) {
+        rbl_set_error("%s: bad argument (ld even, 1 <= d <= ld, g, kappa, member, cols_out, count, 0 <= take <= %d are needed)", who,
+                      WS_SELECT);
+        return RBL_ERR_INVALID;
+    }
+    Scratch sc;
+    RBL_TRY(scratch_begin(sc, nullptr));
+    WsetState W;
+    RBL_TRY(alloc_wset(sc.mem, W, ld, sc.s, true));
+    double *dg = nullptr, *dk = nullptr, *dq = nullptr;
+    RBL_TRY(sc.upload(&dg, g, (size_t)ld));
+    RBL_TRY(sc.upload(&dk, kappa, (size_t)ld));
+    if (q) RBL_TRY(sc.upload(&dq, q, (size_t)ld));
+    std::vector<int> pos((size_t)ld);
+    for (int64_t j = 0; j < ld; ++j) pos[(size_t)j] = member[j] ? 0 : -1;
+    int cnt = 0, sel[WS_SELECT];
+    RBL_TRY(wset_scan(W, ld, d, dg, dq, dk, pos.data(), tol, take, &cnt, sel, sc.s));
+    RBL_HIP(hipStreamSynchronize(sc.s));
+    for (int i = 0; i < cnt; ++i) cols_out[i] = sel[i];
+    *count = cnt;
+    return RBL_OK;
+}
+
+int rbl_k_wstep_ws(int64_t n, int64_t d, const int64_t* indptr, const int32_t* indices, const double* values, int K,
+                   const double* Q, double rho, double reg, const double* l1, const double* l2, double tol, int max_inner,
+                   int num_cu, int ws_cap, const double* w0, double* W_out, rbl_wset_report* reports) {
+    const char* who = "rbl_k_wstep_ws";
+    const bool pen = l1 || l2;
+    if (d < 1 || n < 1 || K < 1 || !indptr || !Q || !W_out || !reports || !(rho > 0.0) || !std::isfinite(rho) || max_inner < 1 ||
+        !std::isfinite(tol) || ws_cap < 0 || ws_cap > WS_CAP || (!pen && (!(reg > 0.0) || !std::isfinite(reg)))) {
+        rbl_set_error("%s: bad argument (n, d, K >= 1, indptr, Q, W_out, reports, finite rho > 0, max_inner >= 1, 0 <= ws_cap <= %d, "
+                      "and a finite reg > 0 or l1 / l2 are needed; n = %lld, d = %lld)", who, WS_CAP, (long long)n, (long long)d);
+        return RBL_ERR_INVALID;
+    }
+    double l2max = 0.0;
+    for (int k = 0; k < 2; ++k) {
+        const double* v = k ? l2 : l1;
+        for (int64_t j = 0; v && j < d; ++j) {
+            if (!(v[j] >= 0.0) || !std::isfinite(v[j])) {
+                rbl_set_error("%s: %s[%lld] = %g - penalties must be finite and >= 0", who, k ? "l2" : "l1", (long long)j, v[j]);
+                return RBL_ERR_INVALID;
+            }
+            if (k && v[j] > l2max) l2max = v[j];
+        }
+    }
+    Scratch sc;
+    int cus = 0;
+    RBL_TRY(scratch_begin(sc, &cus));
+    if (num_cu == 0) num_cu = cus;
+    if (num_cu < 1 || num_cu > cus) {
+        rbl_set_error("%s: num_cu = %d outside 1..%d (the device's compute units; 0 = all)", who, num_cu, cus);
+        return RBL_ERR_INVALID;
+    }
+    CsrStore st;
+    int64_t ld = 0;
+    RBL_TRY(upload_csr(sc, who, n, d, indptr, indices, values, true, num_cu, &st, &ld));
+    std::vector<double> hQ((size_t)(K * ld), 0.0), hw((size_t)ld, 0.0), hp((size_t)(2 * ld), 0.0), hl1((size_t)d, 0.0);
+    for (int k = 0; k < K; ++k)
+        for (int64_t i = 0; i < d; ++i) hQ[(size_t)(k * ld + i)] = Q[(size_t)k * d + i];
+    for (int64_t i = 0; i < d; ++i) {
+        hw[(size_t)i] = w0 ? w0[i] : 0.0;
+        hp[(size_t)i] = hl1[(size_t)i] = l1 ? l1[i] : 0.0;
+        hp[(size_t)(ld + i)] = l2 ? l2[i] : 0.0;
+    }
+    double *dQ = nullptr, *dw = nullptr, *dp = nullptr;
+    RBL_TRY(sc.upload(&dQ, hQ.data(), hQ.size()));
+    RBL_TRY(sc.upload(&dw, hw.data(), hw.size()));
+    WstepWorkspace ww{};
+    RBL_TRY(alloc_wstep(sc.mem, ww, ld, sc.s));
+    if (pen) {
+        RBL_TRY(sc.upload(&dp, hp.data(), hp.size()));
+        ww.pen_l1 = dp;
+        ww.pen_l2 = dp + ld;
+        ww.pen_l2max = l2max;
+    }
+    OpData op{&st, n, nullptr, nullptr, (size_t)(st.nseg > 0 ? st.nseg : 1), nullptr, num_cu};
+    RBL_TRY(sc.mem.alloc(&op.t, (size_t)n));
+    RBL_TRY(sc.mem.alloc(&op.slab, op.slab_doubles));
+    RBL_TRY(sc.mem.alloc(&op.part, op_part_doubles(ld)));
+    WsetState W;
+    RBL_TRY(alloc_wset(sc.mem, W, ld, sc.s));
+    double lam = 0.0;
+    RBL_TRY(launch_op_power_iteration(op, ld, d, ww.yk, ww.Gy, ww.scal, 100, &lam, sc.s));
+    double L = 1.02 * lam;
+    if (!(L > 0.0)) L = 1.0;
+    for (int k = 0; k < K; ++k) {
+        int it = 0;
+        RBL_TRY(run_wstep_ws(op, ld, d, dQ + (size_t)k * ld, rho, reg, L, tol > 0.0 ? tol : 1e-13, max_inner, dw, ww, W,
+                             ws_cap > 0 ? ws_cap : WS_CAP, pen ? hl1.data() : nullptr, &it, sc.s));
+        RBL_HIP(hipMemcpyAsync(W_out + (size_t)k * ld, dw, sizeof(double) * ld, hipMemcpyDeviceToHost, sc.s));
+        RBL_HIP(hipStreamSynchronize(sc.s));
+        reports[k] = W.rep;
+    }
+    return RBL_OK;
+}
+
 int rbl_k_wstep_seq(int wstep, int64_t d, const double* G, int K, const double* Q, double rho, double reg, double smooth_t,
                     const double* l1, const double* l2, const double* w0, double tol, int max_inner, int route,
                     int launch_seq0, int flags, double* W, double* Gw, double* Wprev, rbl_wstep_report* reports) {

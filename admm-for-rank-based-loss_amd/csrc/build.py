@@ -11,9 +11,9 @@ import sys
 from concurrent.futures import ThreadPoolExecutor
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-SOURCES = ["api.hip", "api_data.hip", "api_iter.hip", "api_dist.hip", "api_group.hip", "api_kernels.hip", "sweep.hip", "spmv.hip", "spgram.hip", "sweep_erm.hip", "sweep_erm_w.hip", "sweep_multi.hip", "elementwise.hip", "sort.hip", "pav.hip", "wstep.hip", "wstep_op.hip", "lasso_fs.hip", "gram.hip", "synth.hip", "eig.hip", "baselines.hip", "zband.hip"]
+SOURCES = ["api.hip", "api_data.hip", "api_iter.hip", "api_dist.hip", "api_group.hip", "api_kernels.hip", "sweep.hip", "spmv.hip", "spgram.hip", "sweep_erm.hip", "sweep_erm_w.hip", "sweep_multi.hip", "elementwise.hip", "sort.hip", "pav.hip", "wstep.hip", "wstep_op.hip", "wstep_ws.hip", "lasso_fs.hip", "gram.hip", "synth.hip", "eig.hip", "baselines.hip", "zband.hip"]
 # (sweep_erm.hip is also what sweep_erm_w.hip includes: listed with the headers so that a change rebuilds both)
-HEADERS = ["sweep_erm.hip", "rbl_internal.h", "api_internal.h", "derived_state.h", "csr_plan.h", "csc_plan.h", "csr_gram_plan.h", "wstep_op_plan.h", "device_math.h", os.path.join("..", "..", "include", "rbl.h")]
+HEADERS = ["sweep_erm.hip", "rbl_internal.h", "api_internal.h", "derived_state.h", "csr_plan.h", "csc_plan.h", "csr_gram_plan.h", "wstep_op_plan.h", "wset_plan.h", "device_math.h", os.path.join("..", "..", "include", "rbl.h")]
 OUT = os.path.join(HERE, "librbl.so")
 FLAGS = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function",
          "-ffp-contract=off"]

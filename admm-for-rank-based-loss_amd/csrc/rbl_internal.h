@@ -5,6 +5,7 @@
 #include <cstddef>
 #include <vector>
 #include "../../include/rbl.h"
+#include "wset_plan.h"
 
 void rbl_set_error(const char* fmt, ...);
 
@@ -410,6 +411,7 @@ constexpr int WSTEP_BAR_UINTS = 2 * 10 * 32;
 constexpr int WSTEP_PERSIST_MAX_LD = 2048;                                  // 8 vector elements per thread of a 256-thread block
 constexpr int WSTEP_XCH_GRANULES = 2 * (WSTEP_PERSIST_MAX_LD + 16);        // granules of one exchange buffer
 constexpr int WSTEP_XCH_DOUBLES = 2 * WSTEP_XCH_GRANULES;                 // two buffers
+int alloc_wstep(DevArena& mem, WstepWorkspace& ww, int64_t ld, hipStream_t s);   // api.hip
 int launch_power_iteration(const double* G, int64_t d, double* tmp1, double* tmp2, double* scal, int iters,
                            double* lambda_host, hipStream_t s);
 // lasso / smoothed-l1 by FISTA with restart, ridge by CG; w is updated in place.
@@ -595,6 +597,49 @@ int launch_op_power_iteration(const OpData& op, int64_t ld, int64_t d, double* x
 // is RBL_ERR_INVALID: its preconditioner is diag(G)
 int run_wstep_op(int wstep, const OpData& op, int64_t ld, const double* q, double rho, double reg, double L, double tol,
                  int max_inner, double* w, WstepWorkspace& ws, int* iters_host, hipStream_t s);
+
+// ---- wstep_ws.hip: the exact working-set lasso / elastic net on that route (RBL_CREATE_WORKING_SET) -----------------
+// The working set of one handle (a borrower has its own).  plan is the host's bookkeeping (wset_plan.h), S / pos its
+// device copies; Gs the WS_CAP-strided sub-Gram matrix; small the Gram-route workspace of the restricted problem.
+struct WsetState {
+    WsetPlan plan;
+    DevArena* mem = nullptr;     // where the spare Gs of a compaction is allocated when an eviction first needs it
+    double *Gs = nullptr, *Gs2 = nullptr;
+    int *pos = nullptr, *S = nullptr, *keep = nullptr;
+    double *qS = nullptr, *wS = nullptr, *l1S = nullptr, *l2S = nullptr;   // WS_CAP each
+    double *vpart = nullptr, *qpart = nullptr;   // per chunk: largest violation outside S, max |q|
+    int* ipart = nullptr;                        // ... and its column
+    int* info = nullptr;                         // device: [0] coefficients != 0 after the last scatter
+    int* pin = nullptr;                          // pinned: [0] sequence number (last), [1] columns chosen, [2] support, [3] candidate
+                                                 // chunks, [4 ..] the columns
+    int seq = 0;
+    int num_cu = 256;            // caps k_ws_gram_rows' grid (one block per unit); no bit of Gs depends on it
+    WstepWorkspace small{};
+    int64_t epoch = -1;          // the data epoch Gs belongs to
+    bool built = false;          // S / pos / Gs stand
+    bool resync = true;          // w may have coefficients outside S (set from outside, or a w-step left the route)
+    bool after_leave = false;    // ... the latter: w is what the operator FISTA left, and a support that still does not fit is
+                                 // not worth a cold start
+    void w_replaced() {          // w was written from outside the w-step (a state set, a w restored from w_prev)
+        resync = true;
+        after_leave = false;
+    }
+    int64_t bytes = 0;
+    rbl_wset_report rep{};
+};
+// scan_only: what wset_scan uses alone (no Gs, no restricted-problem workspace)
+int alloc_wset(DevArena& mem, WsetState& W, int64_t ld, hipStream_t s, bool scan_only = false);
+// One w-step (RBL_WSTEP_L1).  cap: the slots S may use (WS_CAP; the test entry shrinks it).  l1_host: the handle's l1 on
+// the host (d values) with per-coordinate penalties, for the free coordinates; ws.form = 5, or 4 when the w-step left
+// the route (run_wstep_op's FISTA from the current w)
+int run_wstep_ws(const OpData& op, int64_t ld, int64_t d, const double* q, double rho, double reg, double L, double tol,
+                 int max_inner, double* w, WstepWorkspace& ws, WsetState& W, int cap, const double* l1_host, int* iters_host,
+                 hipStream_t s);
+// the pieces alone (rbl_k_wset_gram / rbl_k_wset_scan): append cols to S and form their rows of Gs; the scan's choice on a
+// prescribed g (q may be NULL: zeros), kvec = kappa per column, member_pos = the host's pos (ld ints)
+int wset_gram(const CsrStore* st, WsetState& W, int64_t ld, const int* cols, int n, int num_cu, hipStream_t s);
+int wset_scan(WsetState& W, int64_t ld, int64_t d, const double* g, const double* q, const double* kvec, const int* member_pos,
+              double tol, int take, int* count, int* cols, hipStream_t s);
 
 // ---- synth.hip --------------------------------------------------------------------------
 int launch_synth(int storage, void* D, int64_t n, int64_t ld, int64_t d, int64_t row_offset, u64 seed,

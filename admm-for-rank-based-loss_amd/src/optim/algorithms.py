@@ -24,7 +24,11 @@ weights), ``set_sample_weight(c)`` replaces it between ``main_loop`` calls or it
 "none"): the w-step's route.  "dense" forms G = D^T D and solves in Gram space; "none" (storage "csr" only) never forms it
 and applies rho D^T D + diag(.) through the sparse passes (CG for l2, FISTA for l1 / elastic net; include/rbl.h:
 RBL_CREATE_NO_GRAM) - the route for more than 16 384 columns, where "auto" picks it; everywhere else "auto" is "dense".
-A solver on borrowed data (``share_data``) must name the route of the solver that owns them.
+A solver on borrowed data (``share_data``) must name the route of the solver that owns them.  ``l1_solver`` ("fista" |
+"working_set") of ADMMmethod: the l1 / elastic-net w-step of the "none" route.  "fista" (the default) is FISTA on the
+operator; "working_set" solves it exactly on a working set of at most 1024 columns whose sub-Gram matrix is formed from
+the entries and kept, and checks the KKT conditions on all columns with one D^T (D w) (include/rbl.h:
+RBL_CREATE_WORKING_SET; ``wset_info_`` reports it).  It needs an l1 penalty, storage "csr" and the "none" route.
 """
 import time
 
@@ -51,10 +55,11 @@ class Optimizer:
     def __init__(self, X, y, weight_function="erm", loss="binary_cross_entropy", l2_reg=None, l1_reg=None,
                  B=None, n_class=None, args=None, w0=None, max_iter=200, tol=1e-4, storage="f32", device=0,
                  _wstep=None, _smooth_t=1.0, share_data=None, l1_weights=None, l2_weights=None, fit_intercept=False,
-                 standardize=False, sample_weight=None, class_weight=None, gram="auto"):
+                 standardize=False, sample_weight=None, class_weight=None, gram="auto", l1_solver="fista"):
         # argument checks in the reference's order (objective first :22, then :55-68)
         _solver.check_problem(weight_function, loss, B, args)
         _solver.check_gram_mode(gram)
+        _solver.check_l1_solver(l1_solver)
         if l1_reg is None and l2_reg is None and l1_weights is None and l2_weights is None:
             raise ValueError("More arguments: l1_reg or l2_reg not l1_reg and l2_reg!")       # :62
         if B is not None and weight_function != "ehrm":
@@ -83,6 +88,9 @@ class Optimizer:
         wstep = _wstep if _wstep is not None else (_lib.WSTEP_L1 if self.w_flag == 1 else _lib.WSTEP_L2)
         # the w-step's route: "dense" (Gram space) or "none" (operator w-step, storage "csr"); argument errors come now
         self.gram = _solver.resolve_gram(gram, storage, self.num_feature)
+        # the l1 w-step of the gram="none" route: "fista" or "working_set"; its refusals come now, before any device call
+        _solver.resolve_l1_solver(l1_solver, wstep == _lib.WSTEP_L1, storage, self.gram)
+        self.l1_solver = l1_solver
         # share_data: another solver of this package built on the same X - its device D and DTD are borrowed; a y that
         # differs from that solver's becomes this solver's own labels (include/rbl.h: rbl_set_labels)
         share = None
@@ -111,7 +119,7 @@ class Optimizer:
             self.sample_weight_ = _solver.resolve_row_weights(y_w, sample_weight, class_weight, weight_function)
         self._s = _solver.Solver(self.num_row, self.num_feature, weight_function, loss, reg=self.reg, wstep=wstep,
                                  B=B, args=args, smooth_t=_smooth_t, tol=tol, max_iter=max_iter, storage=storage,
-                                 device=device, share=share, gram=self.gram)
+                                 device=device, share=share, gram=self.gram, l1_solver=l1_solver)
         if share is None:
             self._s.set_data(src, y, scaling="fit" if self.standardize else "none",
                              ones_column=self.fit_intercept)                                  # :23 D = -y*X
@@ -212,6 +220,11 @@ class Optimizer:
         return self._s.gram_info()
 
     @property
+    def wset_info_(self):
+        """the working set after the last w-step (include/rbl.h: rbl_wset_report; l1_solver="working_set" only)"""
+        return self._s.wset_info()
+
+    @property
     def D(self):
         return self._s.get_D()
 
@@ -310,12 +323,12 @@ class ADMMmethod(Optimizer):
     def __init__(self, X, y, weight_function="erm", loss="binary_cross_entropy", l2_reg=None, l1_reg=None, B=None,
                  n_class=None, args=None, w0=None, max_iter=200, tol=1e-4, storage="f32", device=0,
                  l1_weights=None, l2_weights=None, fit_intercept=False, standardize=False, sample_weight=None,
-                 class_weight=None, gram="auto", share_data=None):
-        # (share_data stays the trailing keyword; the seven before it are meant to be given by name)
+                 class_weight=None, gram="auto", l1_solver="fista", share_data=None):
+        # (share_data stays the trailing keyword; the eight before it are meant to be given by name)
         super().__init__(X, y, weight_function, loss, l2_reg, l1_reg, B, n_class, args, w0, max_iter, tol,
                          storage=storage, device=device, share_data=share_data, l1_weights=l1_weights,
                          l2_weights=l2_weights, fit_intercept=fit_intercept, standardize=standardize,
-                         sample_weight=sample_weight, class_weight=class_weight, gram=gram)
+                         sample_weight=sample_weight, class_weight=class_weight, gram=gram, l1_solver=l1_solver)
 
     def start_store(self, X, y, weight_function="erm", loss="binary_cross_entropy", B=None, l2_reg=None,
                     l1_reg=None, n_class=None, args=None, sample_weight_test=None):
@@ -393,7 +406,7 @@ class ADMMgroup:
     storage."""
 
     _KEYS = ("weight_function", "loss", "l2_reg", "l1_reg", "B", "args", "w0", "smooth", "t", "y", "l1_weights",
-             "l2_weights", "fit_intercept", "standardize", "sample_weight", "class_weight", "share_sparse", "gram")
+             "l2_weights", "fit_intercept", "standardize", "sample_weight", "class_weight", "share_sparse", "gram", "l1_solver")
 
     def __init__(self, X, y, problems, storage="f32", device=0, max_iter=200, tol=1e-4):
         if not isinstance(problems, (list, tuple)) or len(problems) == 0:
@@ -433,12 +446,20 @@ class ADMMgroup:
                 _solver.check_gram_mode(pr.get("gram", "auto"))
                 if pr.get("gram", "auto") != problems[0].get("gram", "auto"):
                     raise ValueError("gram must be the same for every problem of a group (one data matrix, one route)")
+                _solver.check_l1_solver(pr.get("l1_solver", "fista"))
+                if pr.get("l1_solver", "fista") != problems[0].get("l1_solver", "fista"):
+                    raise ValueError("l1_solver must be the same for every problem of a group (a borrower follows its owner)")
+                if pr.get("smooth") and pr.get("l1_solver", "fista") != "fista":
+                    raise ValueError("smooth=True members have no l1_solver (the smoothed-l1 w-step is not a lasso)")
                 if pr.get("smooth") and pr.get("gram", "auto") == "none":
                     raise ValueError('smooth=True members have no gram="none" route (the smoothed-l1 w-step needs diag(G))')
                 if storage in _lib.STORAGE:
-                    _solver.resolve_gram(pr.get("gram", "auto"), storage, X.shape[1] + (1 if pr.get("fit_intercept") else 0))
-                _solver.resolve_penalty(X.shape[1], pr.get("l1_reg"), pr.get("l2_reg"), pr.get("l1_weights"),
-                                        pr.get("l2_weights"), bool(pr.get("fit_intercept")))
+                    route = _solver.resolve_gram(pr.get("gram", "auto"), storage, X.shape[1] + (1 if pr.get("fit_intercept") else 0))
+                pen_k = _solver.resolve_penalty(X.shape[1], pr.get("l1_reg"), pr.get("l2_reg"), pr.get("l1_weights"),
+                                                pr.get("l2_weights"), bool(pr.get("fit_intercept")))
+                if storage in _lib.STORAGE:
+                    has_l1 = pen_k["wstep"] == _lib.WSTEP_L1 if pen_k else pr.get("l1_reg") is not None
+                    _solver.resolve_l1_solver(pr.get("l1_solver", "fista"), has_l1, storage, route)
                 if pr.get("B") is not None and pr["weight_function"] != "ehrm":
                     raise ValueError(f"Unrecognized weight_function '{pr['weight_function']}'! Options: ['ehrm']")
                 if pr["weight_function"] == "ehrm" and pr.get("B") is None:
@@ -469,7 +490,8 @@ class ADMMgroup:
                 s = ADMMmethod(X, yk, pr["weight_function"], pr["loss"], max_iter=max_iter, tol=tol, storage=storage,
                                device=device, share_data=share, l1_weights=pr.get("l1_weights"),
                                l2_weights=pr.get("l2_weights"), fit_intercept=bool(pr.get("fit_intercept")),
-                               standardize=bool(pr.get("standardize")), gram=pr.get("gram", "auto"), **kw)
+                               standardize=bool(pr.get("standardize")), gram=pr.get("gram", "auto"),
+                               l1_solver=pr.get("l1_solver", "fista"), **kw)
             self.solvers.append(s)
         self._group = _solver.Group([s._s for s in self.solvers], share_sparse=bool(self.problems[0].get("share_sparse")))
         self.store = False
@@ -561,9 +583,10 @@ class OneVsRest:
     def __init__(self, X, labels, weight_function="erm", loss="binary_cross_entropy", l2_reg=None, l1_reg=None, B=None,
                  args=None, storage="f32", device=0, max_iter=200, tol=1e-4, l1_weights=None, l2_weights=None,
                  fit_intercept=False, standardize=False, sample_weight=None, class_weight=None, share_sparse=False,
-                 gram="auto"):
+                 gram="auto", l1_solver="fista"):
         _solver.check_share_sparse(share_sparse)     # before anything touches the device
         _solver.check_gram_mode(gram)
+        _solver.check_l1_solver(l1_solver)
         # class_weight="balanced": every member gets the balanced weights of its OWN +-1 labels (one class against the
         # rest is imbalanced by construction); a common sample_weight multiplies into all of them
         Xm = _solver.as_source(X, device)
@@ -580,7 +603,7 @@ class OneVsRest:
         problems = [dict(weight_function=weight_function, loss=loss, l2_reg=l2_reg, l1_reg=l1_reg, B=B, args=args, y=yk,
                          l1_weights=l1_weights, l2_weights=l2_weights, fit_intercept=self.fit_intercept,
                          standardize=bool(standardize), sample_weight=sample_weight, class_weight=class_weight,
-                         share_sparse=share_sparse, gram=gram)
+                         share_sparse=share_sparse, gram=gram, l1_solver=l1_solver)
                     for yk in ys]
         self._storage, self._device = storage, device
         self.group = ADMMgroup(Xm, ys[0], problems, storage=storage, device=device, max_iter=max_iter, tol=tol)

@@ -114,6 +114,7 @@ typedef struct rbl_stats {
                                 launch (k_cg_persist / k_ncg_persist), 2 = the exact active-set lasso kernel, 3 = the
                                 eigen-decomposition ridge, 4 = the operator route of a handle without a Gram matrix
                                 (RBL_CREATE_NO_GRAM: CG / FISTA on rho D^T (D p) + diag(.) p, batches of launches),
+                                5 = the working set of RBL_CREATE_WORKING_SET (a w-step that left it reports 4),
                                 -1 = an overridden w_subproblem (rbl_phase_w_external) */
 } rbl_stats;
 
@@ -134,7 +135,8 @@ int  rbl_destroy(rbl_solver* h);
  *   RBL_CREATE_NO_GRAM  (RBL_STORE_CSR only)  The handle never holds G = D^T D.  Every w-step applies
  *     A = rho D^T D + reg I (or + diag(l2), rbl_set_penalty) as an operator, A p = rho D^T (D p) + ..., through the two
  *     sparse passes: warm-started CG for RBL_WSTEP_L2, FISTA with gradient restart for RBL_WSTEP_L1 (per-coordinate
- *     thresholds and free coordinates included; the exact active-set kernel needs G and is not used), with the stop rules
+ *     thresholds and free coordinates included; the exact active-set kernel needs G and is used on this route only
+ *     through the working set's sub-Gram matrix, RBL_CREATE_WORKING_SET below), with the stop rules
  *     of the Gram route.  rbl_stats.wstep_form is 4.  Nothing of size d^2 is allocated - no G, no eigenbasis, no lasso
  *     workspace - only one more n-vector and d-vectors, so d is not bounded by the Gram route's ld <= 16 384.  The
  *     d-space sums run in a fixed order that depends on ld alone: the iterates do not depend on the grid.
@@ -150,6 +152,20 @@ int  rbl_destroy(rbl_solver* h);
  * names RBL_CREATE_NO_GRAM): the Gram route would allocate ld^2 doubles and refuse the first w-step.
  * The presence of this symbol is the capability probe (RBL_VERSION is unchanged). */
 #define RBL_CREATE_NO_GRAM 1
+/*   RBL_CREATE_WORKING_SET  (with RBL_CREATE_NO_GRAM and cfg.wstep == RBL_WSTEP_L1 only; otherwise RBL_ERR_INVALID with a
+ *     message that says which)  The lasso / elastic-net w-step of such a handle (src/optim/algorithms.py:190-202,
+ *     src/util/fast_lasso.py) is solved exactly on a working set S of at most 1024 columns: the sub-Gram matrix of S is
+ *     formed from the entries once per column and kept (8 MB; dropped when the data change), the restricted problem goes
+ *     through the Gram route's active-set kernel (FISTA on the sub-Gram matrix when its active set outgrows the kernel),
+ *     and one D^T (D w) - two sparse passes - checks the KKT conditions on ALL columns: column j outside S joins S when
+ *     |g_j| - kappa_j > w_tol * max(1, max_j |q_j|), g = D^T D w + (l2/rho) w - q, the largest violation of each chunk of
+ *     2048 columns, at most 64 per round, in a fixed order.  rbl_stats.wstep_form is 5; a w-step that S cannot hold
+ *     (more than 1024 columns needed, free coordinates l1_j = 0 included) continues with the operator FISTA from where it stands and reports
+ *     4.  A warm start whose support does not fit S is replaced by w = 0 - unless the w-step before it left the route
+ *     already: then this one goes to the operator FISTA at once.  Without the flag nothing changes: FISTA.
+ *     rbl_create_shared on such an owner gives borrowers with a working set of their own under the same rule
+ *     (cfg.wstep == RBL_WSTEP_L1, or objective_only).  The presence of rbl_wset_info is the capability probe. */
+#define RBL_CREATE_WORKING_SET 2
 int  rbl_create_opts(const rbl_config* cfg, uint32_t flags, rbl_solver** out);
 /* A second problem on the SAME (X, y): Optimizer.__init__ again with other weight_function / loss / regulariser / args
  * (examples/run_srm.py:57,68 builds ADMMmethod and smoothADMMmethod on one X_train), without algorithms.py:23-24 being
@@ -728,6 +744,38 @@ int  rbl_k_wstep_pen(int64_t d, const double* G, const double* q, double rho, co
 int  rbl_k_wstep_op(int wstep, int64_t n, int64_t d, const int64_t* indptr, const int32_t* indices, const double* values,
                     const double* q, double rho, double reg, const double* l1 /* NULL */, const double* l2 /* NULL */,
                     double tol, int max_inner, int num_cu, double* w_inout, int* iters, int* status);
+/* ---- the working-set lasso of RBL_CREATE_WORKING_SET (wstep_ws.hip; src/optim/algorithms.py:190-202, src/util/fast_lasso.py) */
+typedef struct rbl_wset_report {
+    int32_t slots;        /* slots of the working set in use */
+    int32_t support;      /* coefficients != 0 after the last w-step (-1: it left the route) */
+    int32_t rounds;       /* solve + scan rounds of the last w-step */
+    int32_t pass_pairs;   /* D^T (D w) evaluations - two sparse passes each - of the last w-step */
+    int32_t rows_last;    /* rows of the sub-Gram matrix formed in the last w-step */
+    int32_t fista_on_gs;  /* 1: a restricted solve of the last w-step fell to FISTA on the sub-Gram matrix */
+    int32_t left_route;   /* 1: the last w-step left the route (operator FISTA, wstep_form 4) */
+    int32_t form;         /* rbl_stats.wstep_form of the last w-step, 0 = none yet */
+    int64_t rows_total;   /* rows formed since the working set was last emptied ... */
+    int64_t evictions;    /* ... and slots evicted */
+    int64_t bytes;        /* device bytes the working set holds */
+} rbl_wset_report;
+/* the working set of h; RBL_ERR_STATE on a handle created without RBL_CREATE_WORKING_SET */
+int  rbl_wset_info(rbl_solver* h, rbl_wset_report* out);
+/* k_ws_gram_rows over host buffers: the CSR arrays hold D (as rbl_k_wstep_op takes them); cols[0 .. ncols) are appended to
+ * an empty working set in that order, in calls of split[0], split[1], ... columns (nsplit >= 1, the sum is ncols; NULL:
+ * one call) -> Gs_out, 1024 x 1024 doubles, slot a = cols[a].  ncols <= 1024, the columns distinct and in [0, d). */
+int  rbl_k_wset_gram(int64_t n, int64_t d, const int64_t* indptr, const int32_t* indices, const double* values, const int32_t* cols,
+                     int ncols, const int32_t* split, int nsplit, int num_cu, double* Gs_out);
+/* k_ws_scan / k_ws_select on prescribed vectors of ld doubles (ld even): g, kappa (per column), q (NULL: zeros), member
+ * (ld ints, != 0: in S); columns >= d are never chosen.  cols_out: room for 64; *count the columns chosen (take <= 64). */
+int  rbl_k_wset_scan(int64_t ld, int64_t d, const double* g, const double* kappa, const double* q, const int32_t* member, double tol,
+                     int take, int32_t* cols_out, int* count);
+/* rbl_k_wstep_op's arguments for wstep 1, K right-hand sides Q (K x d) run one after another on ONE workspace as
+ * rbl_k_wstep_seq does (step k warm-started from step k - 1, step 0 from w_inout), through run_wstep_ws as a handle
+ * created with RBL_CREATE_WORKING_SET runs it.  ws_cap: the slots the working set may use (0 = 1024; a test argument).
+ * W_out: K x ld, reports: K. */
+int  rbl_k_wstep_ws(int64_t n, int64_t d, const int64_t* indptr, const int32_t* indices, const double* values, int K,
+                    const double* Q, double rho, double reg, const double* l1 /* NULL */, const double* l2 /* NULL */, double tol,
+                    int max_inner, int num_cu, int ws_cap, const double* w0 /* NULL = 0 */, double* W_out, rbl_wset_report* reports);
 /* K >= 1 w-steps one after another on ONE workspace, as consecutive ADMM iterations run them: step k solves for the
  * right-hand side Q[k] (K x d), warm-started from the w of step k - 1 (step 0 from w0, NULL = 0), through run_wstep
  * unchanged - the batch sizes, the back-off of the nonlinear CG's linear phase, the exchange tags and the uncleared
