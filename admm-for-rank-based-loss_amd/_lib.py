@@ -180,6 +180,8 @@ SIGNATURES = {
     "rbl_set_data_csr": (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_int]),
     "rbl_set_scaling": (C.c_int, [_P, _P, _P]),
     "rbl_get_scaling": (C.c_int, [_P, _P, _P, C.POINTER(C.c_int)]),
+    "rbl_set_centering": (C.c_int, [_P, C.c_int]),
+    "rbl_get_centering": (C.c_int, [_P, C.POINTER(C.c_int)]),
     "rbl_generate_synthetic": (C.c_int, [_P, C.c_uint64, C.c_double, C.c_double]),
     "rbl_synth_local": (C.c_int, [_P, C.c_uint64, C.c_double, C.c_double]),
     "rbl_synth_finish": (C.c_int, [_P]),

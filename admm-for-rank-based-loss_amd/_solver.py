@@ -354,14 +354,26 @@ def as_source(X, device=None):
     return Source(A.ctypes.data, dt, _lib.MEM_HOST, ldx, A.shape, A)
 
 
+def resolve_standardize(standardize):
+    """The ``standardize`` keyword -> False, True (centre and scale) or "scale" (unit-variance columns without centring:
+    the mean vector is all zeros, a sparse X stays sparse).  Any other string is a ValueError."""
+    if isinstance(standardize, str):
+        if standardize != "scale":
+            raise ValueError(f'standardize must be False, True or "scale", got {standardize!r}')
+        return "scale"
+    return bool(standardize)
+
+
 def check_csr_storage(src, storage, standardize=False, what="X"):
-    """storage="csr" keeps D sparse: it takes a sparse matrix as it is and no standardisation (centring makes the
-    columns dense).  Raises ValueError - before any device call - for a dense ``src`` (a Source) or standardize=True."""
+    """storage="csr" keeps D sparse: it takes a sparse matrix as it is and no centring (it makes the columns dense);
+    standardize="scale" scales without it.  Raises ValueError - before any device call - for a dense ``src`` (a Source)
+    or standardize=True."""
     if storage != "csr":
         return
-    if standardize:
+    if standardize and standardize != "scale":
         raise ValueError('standardize=True with storage="csr": centring the columns makes D dense - scale the sparse '
-                         "matrix yourself (scaling without centring keeps it sparse) or use a dense storage type")
+                         "matrix yourself (scaling without centring keeps it sparse) or use a dense storage type; "
+                         'standardize="scale" does that scaling on the device')
     if not isinstance(src, CsrSource):
         raise ValueError(f'storage="csr" needs a sparse {what} (scipy.sparse matrix / array or torch sparse tensor); '
                          f"this one is dense - pass scipy.sparse.csr_matrix({what}), or use storage f32 / f64 / fp16")
@@ -427,6 +439,7 @@ class Solver:
                  B=None, args=None, smooth_t=1.0, rho0=0.0, tol=1e-4, w_tol=0.0, max_iter=200, storage="f32",
                  device=0, objective_only=False, n_total=None, row_offset=0, share=None, gram="auto", l1_solver="fista"):
         self._h = None
+        self._center = True           # what set_centering last set (the library's default)
         self._share = share           # keeps the data's owner referenced (the library counts references itself)
         if storage not in _lib.STORAGE:
             raise ValueError(f"storage must be one of {sorted(_lib.STORAGE)}")
@@ -500,8 +513,8 @@ class Solver:
         if scaling not in _lib.SCALING:
             raise ValueError(f"scaling must be one of {sorted(_lib.SCALING)}")
         src = as_source(X, self.cfg.device)
-        if self.cfg.storage == _lib.STORE_CSR:
-            check_csr_storage(src, "csr", scaling != "none")
+        if self.cfg.storage == _lib.STORE_CSR:      # (scaling is allowed once centring is off: set_centering)
+            check_csr_storage(src, "csr", scaling != "none" and self._center)
         y = _as_labels(y, src.shape[0])
         shape = (src.shape[0], src.shape[1] + (1 if ones_column else 0))
         if shape != (self.n, self.d):
@@ -532,6 +545,17 @@ class Solver:
             return
         mean, scale = as_scaling(mean, scale, self.d)
         _lib.check(self.lib.rbl_set_scaling(self._h, _lib.ptr(mean), _lib.ptr(scale)))
+
+    def set_centering(self, center):
+        """False: scaling="fit" / "apply" of the next set_data scale the columns without centring them (the mean vector is
+        all zeros; include/rbl.h: rbl_set_centering) - the scaling a storage="csr" handle takes.  True: the default."""
+        _lib.check(self.lib.rbl_set_centering(self._h, 1 if center else 0))
+        self._center = bool(center)
+
+    def get_centering(self):
+        flag = C.c_int(1)
+        _lib.check(self.lib.rbl_get_centering(self._h, C.byref(flag)))
+        return bool(flag.value)
 
     def get_scaling(self):
         """(mean, scale) of scaling="fit" / set_scaling, or None when the handle has none"""

@@ -375,7 +375,7 @@ static int set_data_from_impl(rbl_solver* h, const void* X, int dtype, int mem, 
                 return RBL_ERR_INVALID;
             }
             if (!(var > 0.0)) var = 1.0;   // a constant column is left at x - mean = 0
-            mean[(size_t)j] = mu;
+            mean[(size_t)j] = h->center ? mu : 0.0;   // (centring off: the same scale, the forming pass subtracts zero)
             scale[(size_t)j] = std::sqrt(var);
         }
         fit_mean.swap(mean);
@@ -432,7 +432,84 @@ static int set_data_from_impl(rbl_solver* h, const void* X, int dtype, int mem, 
 // RBL_STORE_CSR: the CSR source *cs becomes the handle's D as it comes - no dense chunk, no forming kernel.  The chunks,
 // the pinned double-buffered copies of a host source and the verdict are those of the dense route; the entries go through
 // launch_csr_store (spmv.hip), then the column form is built on the device.
-static int set_data_csr_sparse(rbl_solver* h, const double* y, int64_t ds, int ones, CsrView* cs) {
+// body() enqueues kernels on s; *ms += what they took (HIP events); returns with s idle
+static int csr_timed(hipStream_t s, double* ms, const std::function<int()>& body) {
+    hipEvent_t t0 = nullptr, t1 = nullptr;
+    bool on = hipEventCreate(&t0) == hipSuccess && hipEventCreate(&t1) == hipSuccess && hipEventRecord(t0, s) == hipSuccess;
+    int rc = body();
+    if (on && hipEventRecord(t1, s) != hipSuccess) on = false;
+    if (hipStreamSynchronize(s) != hipSuccess && rc == RBL_OK) rc = RBL_ERR_HIP;
+    float el = 0.f;
+    if (on && rc == RBL_OK && hipEventElapsedTime(&el, t0, t1) == hipSuccess) *ms += (double)el;
+    if (t0) (void)hipEventDestroy(t0);
+    if (t1) (void)hipEventDestroy(t1);
+    if (rc == RBL_ERR_HIP) {
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) rbl_set_error("set_data_csr: %s", hipGetErrorString(e));
+    }
+    return rc;
+}
+
+// RBL_STORE_CSR with centring off: the entries stand unscaled in both forms (csr_store_finish has run).  RBL_SCALE_FIT
+// takes the columns' statistics from the column form - two passes (spmv.hip: launch_csr_colstats), the mean of the
+// shifted values formed on the host in between - then, as RBL_SCALE_APPLY does with the handle's vector, every stored
+// value is multiplied by fl(1.0 / scale) of its column.  -y_r x is exact, so scaling the stored values has the bits of
+// scaling at store time; both modes scale after the store.  The column of ones is never scaled (mean 0, scale 1).
+static int csr_scale_only(rbl_solver* h, CsrStore* st, int64_t ds, int scaling) {
+    const int64_t n = h->n, d = h->d, ld = h->ld;
+    DevArena tmp;   // freed on return: every launch below is waited for
+    double* dinv = nullptr;
+    RBL_TRY(tmp.alloc(&dinv, (size_t)ld));
+    std::vector<double> fit_scale;
+    if (scaling == RBL_SCALE_FIT) {
+        double *part = nullptr, *sums = nullptr, *mud = nullptr;
+        RBL_TRY(tmp.alloc(&part, (size_t)st->nseg));
+        RBL_TRY(tmp.alloc(&sums, (size_t)ld));
+        RBL_TRY(tmp.alloc(&mud, (size_t)ld));
+        std::vector<double> s1((size_t)ld, 0.0), s2((size_t)ld, 0.0), m1((size_t)ld, 0.0);
+        std::vector<int64_t> cp((size_t)ld + 1, 0);
+        const double nn = (double)n;
+        RBL_TRY(csr_timed(h->stream, &h->src_ms[0], [&]() {
+            return launch_csr_colstats(st, n, ld, h->ysign, 1, nullptr, part, sums, h->num_cu, h->stream);
+        }));
+        RBL_HIP(hipMemcpy(s1.data(), sums, sizeof(double) * (size_t)ld, hipMemcpyDeviceToHost));
+        RBL_HIP(hipMemcpy(cp.data(), st->colptr, sizeof(int64_t) * (size_t)(ld + 1), hipMemcpyDeviceToHost));
+        for (int64_t j = 0; j < ds; ++j) m1[(size_t)j] = s1[(size_t)j] / nn;
+        RBL_HIP(hipMemcpy(mud, m1.data(), sizeof(double) * (size_t)ld, hipMemcpyHostToDevice));
+        RBL_TRY(csr_timed(h->stream, &h->src_ms[0], [&]() {
+            return launch_csr_colstats(st, n, ld, h->ysign, 2, mud, part, sums, h->num_cu, h->stream);
+        }));
+        h->src_timed[0] = 1;
+        RBL_HIP(hipMemcpy(s2.data(), sums, sizeof(double) * (size_t)ld, hipMemcpyDeviceToHost));
+        fit_scale.assign((size_t)d, 1.0);
+        for (int64_t j = 0; j < ds; ++j) {
+            // x = sh + dl over the stored entries, 0 over the n - cnt others (sh = 0 unless the column is full):
+            // mean = sh + m1, m1 = sum dl / n;  var = (sum (dl - m1)^2 + (n - cnt) m1^2) / n
+            const double mu = m1[(size_t)j], rest = (double)(n - (cp[(size_t)j + 1] - cp[(size_t)j]));
+            double var = (s2[(size_t)j] + rest * (mu * mu)) / nn;
+            if (!std::isfinite(mu) || !std::isfinite(var)) {
+                rbl_set_error("set_data_csr: column %lld has a non-finite mean or variance (shifted mean %g, variance %g) - the "
+                              "source holds inf / nan or overflows fp64 sums", (long long)j, mu, var);
+                return RBL_ERR_INVALID;
+            }
+            if (!(var > 0.0)) var = 1.0;   // a constant column keeps its values
+            fit_scale[(size_t)j] = std::sqrt(var);
+        }
+    }
+    const std::vector<double>& use = scaling == RBL_SCALE_FIT ? fit_scale : h->sc_scale;
+    std::vector<double> inv((size_t)ld, 1.0);
+    for (int64_t j = 0; j < ds; ++j) inv[(size_t)j] = 1.0 / use[(size_t)j];
+    RBL_HIP(hipMemcpy(dinv, inv.data(), sizeof(double) * (size_t)ld, hipMemcpyHostToDevice));
+    RBL_TRY(csr_timed(h->stream, &h->src_ms[1], [&]() { return launch_csr_scale(st, ld, dinv, h->num_cu, h->stream); }));
+    if (scaling == RBL_SCALE_FIT) {   // the vectors are the handle's only once D stands
+        h->sc_mean.assign((size_t)d, 0.0);
+        h->sc_scale.swap(fit_scale);
+        h->sc_set = true;
+    }
+    return RBL_OK;
+}
+
+static int set_data_csr_sparse(rbl_solver* h, const double* y, int64_t ds, int ones, CsrView* cs, int scaling) {
     const int64_t n = h->n, ld = h->ld;
     CsrStore* st = (CsrStore*)h->D;
     st->lanes = 0;
@@ -487,6 +564,11 @@ static int set_data_csr_sparse(rbl_solver* h, const double* y, int64_t ds, int o
     h->src_timed[1] = 1;
     RBL_TRY(csr_verdict(*cs));
     RBL_TRY(csr_store_finish(st, ld, columns, h->num_cu, h->stream));
+    if (scaling != RBL_SCALE_NONE) {   // centring off (the entry point has refused everything else)
+        const int rc = csr_scale_only(h, st, ds, scaling);
+        if (rc != RBL_OK) st->lanes = 0;   // the values are not what the call promised: nothing reads them
+        RBL_TRY(rc);
+    }
     return RBL_OK;   // (the slab of the q pass follows the segment count where the pass is launched: api_iter.hip)
 }
 
@@ -563,6 +645,14 @@ static int check_scaling_state(rbl_solver* h, const char* who, int scaling) {
         rbl_set_error("%s: RBL_SCALE_APPLY without a scaling - call rbl_set_scaling first", who);
         return RBL_ERR_STATE;
     }
+    if (scaling == RBL_SCALE_APPLY && !h->center)
+        for (int64_t j = 0; j < h->d; ++j)
+            if (h->sc_mean[(size_t)j] != 0.0) {
+                rbl_set_error("%s: RBL_SCALE_APPLY with centring off (rbl_set_centering) takes an all-zero mean vector, mean[%lld] "
+                              "is %g - these vectors come from a centred fit: turn centring on, or set the means to zero", who,
+                              (long long)j, h->sc_mean[(size_t)j]);
+                return RBL_ERR_INVALID;
+            }
     return RBL_OK;
 }
 
@@ -609,9 +699,13 @@ int rbl_set_data_csr(rbl_solver* h, const void* indptr, const void* indices, con
     const int64_t n = h->n, d = h->d;
     const int64_t ds = d - ((flags & RBL_DATA_ONES_COLUMN) ? 1 : 0);
     if (h->storage == RBL_STORE_CSR) {
-        if (scaling != RBL_SCALE_NONE)
+        if (scaling != RBL_SCALE_NONE && h->center)
             return refuse_on_csr(h, "set_data_csr", "RBL_SCALE_FIT / RBL_SCALE_APPLY on a handle with RBL_STORE_CSR - centring the "
                                                     "columns makes D dense; scale the source yourself or use a dense storage type");
+        if (scaling == RBL_SCALE_FIT && h->cfg.objective_only)
+            return refuse_on_csr(h, "set_data_csr", "RBL_SCALE_FIT on an objective-only handle with RBL_STORE_CSR - the column "
+                                                    "statistics are taken from the column form, which such a handle does not "
+                                                    "build; give it the training vectors (rbl_set_scaling) and use RBL_SCALE_APPLY");
         if (nnz > 0x7fffffffLL || (nnz >= 0 && nnz + ((flags & RBL_DATA_ONES_COLUMN) ? n : 0) > 0x7fffffffLL)) {   // (n <= 2^31 - 1)
             char why[256];
             snprintf(why, sizeof(why), "nnz = %lld%s exceeds the 2^31 - 1 entries a handle with RBL_STORE_CSR holds", (long long)nnz,
@@ -676,7 +770,7 @@ int rbl_set_data_csr(rbl_solver* h, const void* indptr, const void* indices, con
     if (n > 0) {
         h->data_ready = false;   // a failed upload leaves the handle without data
         RBL_TRY(data_write_begins(h));
-        if (h->storage == RBL_STORE_CSR) RBL_TRY(set_data_csr_sparse(h, y, ds, (flags & RBL_DATA_ONES_COLUMN) ? 1 : 0, &v));
+        if (h->storage == RBL_STORE_CSR) RBL_TRY(set_data_csr_sparse(h, y, ds, (flags & RBL_DATA_ONES_COLUMN) ? 1 : 0, &v, scaling));
         else RBL_TRY(set_data_from_impl(h, nullptr, dtype, mem, 0, y, scaling, ds, &v));
     }
     return data_written(h);
@@ -708,6 +802,23 @@ int rbl_set_scaling(rbl_solver* h, const double* mean, const double* scale) {
     h->sc_mean.assign(mean, mean + h->d);
     h->sc_scale.assign(scale, scale + h->d);
     h->sc_set = true;
+    return RBL_OK;
+}
+
+int rbl_set_centering(rbl_solver* h, int center) {
+    RBL_ENTER(h);
+    RBL_NOT_BORROWER(h, "set_centering");
+    if (center != 0 && center != 1) {
+        rbl_set_error("set_centering: center must be 0 or 1 (got %d)", center);
+        return RBL_ERR_INVALID;
+    }
+    h->center = center != 0;
+    return RBL_OK;
+}
+
+int rbl_get_centering(rbl_solver* h, int* center) {
+    RBL_ENTER_ITER(h);
+    if (center) *center = h->center ? 1 : 0;
     return RBL_OK;
 }
 

@@ -548,6 +548,15 @@ int launch_csr_store(int dtype, int index_type, const CsrStore* st, int64_t rows
                      int num_cu, hipStream_t s);
 // after the last chunk: the lane group, and with columns the column form and its segment table; returns with s idle
 int csr_store_finish(CsrStore* st, int64_t ld, bool columns, int num_cu, hipStream_t s);
+// Scale-only standardisation of a complete store (rbl_set_centering(h, 0)).  Column sums of the source's x = -y_r * value
+// from the column form, per column: pass 1 sums[j] = sum (x - sh_j), pass 2 sums[j] = sum ((x - sh_j) - mu[j])^2 over the
+// stored entries (sh_j: the first stored x of a full column, else 0).  Two stages - one wave per segment into part
+// (st->nseg doubles), then the fold of q = D^T c - in an order that the column's entries and the segment length fix;
+// sums: ld doubles (columns without entries and the pad: +0.0); mu (ld doubles) is read by pass 2 alone.
+int launch_csr_colstats(const CsrStore* st, int64_t n, int64_t ld, const signed char* ysign, int pass, const double* mu,
+                        double* part, double* sums, int num_cu, hipStream_t s);
+// every stored value times inv[its column] (ld doubles), row form and - where the handle has one - column form
+int launch_csr_scale(const CsrStore* st, int64_t ld, const double* inv, int num_cu, hipStream_t s);
 // done (optional, both passes): a device flag - where it is set when a kernel starts, that kernel does nothing (output untouched)
 int launch_csr_gemv(const CsrStore* st, int64_t n, const double* w, double* v, int num_cu, hipStream_t s, const int* done = nullptr);
 // part: the segments' partial sums, part_doubles >= st->nseg of them (fewer: RBL_ERR_STATE before anything is launched)

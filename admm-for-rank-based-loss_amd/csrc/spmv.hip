@@ -283,6 +283,76 @@ __global__ void k_add_into(double* __restrict__ G, const double* __restrict__ Gc
     if (i < count) G[i] += Gc[i];
 }
 
+// ---- scale-only standardisation (rbl_set_centering(h, 0)): the column statistics from the entries, then the scaling
+// the source's x of slot p of the column form: the stored value is -y_r x, and -y_r (-y_r x) = x exactly
+__device__ inline double sp_source_x(const int* __restrict__ row, const double* __restrict__ cval,
+                                     const signed char* __restrict__ ysign, long long p) {
+    const double v = cval[p];
+    return ysign[row[p]] > 0 ? -v : v;
+}
+__device__ inline double sp_stat_term(double v, int r, const signed char* __restrict__ ysign, double sh, double mu, bool squares) {
+    double t = (ysign[r] > 0 ? -v : v) - sh;
+    if (!squares) return t;
+    t -= mu;
+    return t * t;
+}
+// One wave per segment of a column's entry list (csc_plan.h), as in k_csc_segments.  PASS 1: part[s] = sum (x - sh);
+// PASS 2: part[s] = sum ((x - sh) - mu[col])^2.  sh is the column's first stored x where the column is full (n entries:
+// the shift of the dense statistics, a constant column sums exact zeros) and 0 elsewhere.  Lane l runs one chain of plain
+// adds over the entries begin + 2l, begin + 2l + 1, begin + 2l + 128, ... in that order, then the butterfly over the wave:
+// the order is a function of the column's entries and T alone.  Where the segment begins on an even slot the pair comes
+// from one 16-byte load of cval and one 8-byte load of row; an odd beginning reads the same pair element by element.
+template <int PASS>
+__global__ __launch_bounds__(SP_THREADS) void k_csc_stat_segments(const int64_t* __restrict__ colptr, const int64_t* __restrict__ segptr,
+                                                                  const int* __restrict__ row, const double* __restrict__ cval,
+                                                                  const signed char* __restrict__ ysign, const double* __restrict__ mu,
+                                                                  double* __restrict__ part, long long ld, long long nseg, int T,
+                                                                  long long n) {
+    const int lane = (int)threadIdx.x & (RBL_WAVE - 1);
+    for (long long s = (long long)blockIdx.x * SP_WPB + ((int)threadIdx.x / RBL_WAVE); s < nseg; s += (long long)gridDim.x * SP_WPB) {
+        const CscSegment g = csc_segment(colptr, segptr, ld, s, T);
+        const long long c0 = colptr[g.col];
+        const double sh = colptr[g.col + 1] - c0 == n ? sp_source_x(row, cval, ysign, c0) : 0.0;
+        const double m = PASS == 2 ? mu[g.col] : 0.0;
+        const bool even = (g.begin & 1) == 0;
+        double acc = 0.0;
+        for (long long k = g.begin + 2 * lane; k < g.end; k += 2 * RBL_WAVE) {
+            const bool two = k + 1 < g.end;
+            double v0, v1 = 0.0;
+            int r0, r1 = 0;
+            if (even && two) {
+                const double2 tv = *reinterpret_cast<const double2*>(cval + k);
+                const int2 tr = *reinterpret_cast<const int2*>(row + k);
+                v0 = tv.x, v1 = tv.y, r0 = tr.x, r1 = tr.y;
+            } else {
+                v0 = cval[k], r0 = row[k];
+                if (two) v1 = cval[k + 1], r1 = row[k + 1];
+            }
+            acc += sp_stat_term(v0, r0, ysign, sh, m, PASS == 2);
+            if (two) acc += sp_stat_term(v1, r1, ysign, sh, m, PASS == 2);
+        }
+#pragma unroll
+        for (int off = RBL_WAVE / 2; off >= 1; off >>= 1) acc += __shfl_xor(acc, off, RBL_WAVE);
+        if (lane == 0) part[s] = acc;
+    }
+}
+// val[k] *= inv[col[k]] over the row form (inv: ld doubles, 1.0 for the column of ones and the pad: those keep their bits)
+__global__ void k_csr_scale_rows(const int* __restrict__ col, double* __restrict__ val, long long nnz, const double* __restrict__ inv) {
+    for (long long k = (long long)blockIdx.x * blockDim.x + threadIdx.x; k < nnz; k += (long long)gridDim.x * blockDim.x)
+        val[k] = val[k] * inv[col[k]];
+}
+// ... and over the column form: one wave per segment, the column's factor read once
+__global__ __launch_bounds__(SP_THREADS) void k_csc_scale_segments(const int64_t* __restrict__ colptr, const int64_t* __restrict__ segptr,
+                                                                   double* __restrict__ cval, const double* __restrict__ inv,
+                                                                   long long ld, long long nseg, int T) {
+    const int lane = (int)threadIdx.x & (RBL_WAVE - 1);
+    for (long long s = (long long)blockIdx.x * SP_WPB + ((int)threadIdx.x / RBL_WAVE); s < nseg; s += (long long)gridDim.x * SP_WPB) {
+        const CscSegment g = csc_segment(colptr, segptr, ld, s, T);
+        const double f = inv[g.col];
+        for (long long k = g.begin + lane; k < g.end; k += RBL_WAVE) cval[k] = cval[k] * f;
+    }
+}
+
 unsigned sp_grid(long long items, long long per_block, int num_cu) {
     long long g = (items + per_block - 1) / per_block;
     const long long cap = (long long)(num_cu > 0 ? num_cu : 256) * 64;
@@ -577,6 +647,50 @@ int launch_csr_dense(const CsrStore* st, int64_t row0, int64_t rows, int64_t ldo
     if (st->nnz <= 0) return RBL_OK;
     hipLaunchKernelGGL(k_csr_dense, dim3(sp_grid(rows, SP_WPB, num_cu)), dim3(SP_THREADS), 0, s, (const int64_t*)st->indptr,
                        (const int*)st->col, (const double*)st->val, (long long)row0, (long long)rows, (long long)ldo, out);
+    RBL_HIP(hipGetLastError());
+    return RBL_OK;
+}
+
+int launch_csr_colstats(const CsrStore* st, int64_t n, int64_t ld, const signed char* ysign, int pass, const double* mu,
+                        double* part, double* sums, int num_cu, hipStream_t s) {
+    if (!st->colptr || !st->segptr || !st->lanes) {
+        rbl_set_error("csr column statistics: the handle holds no complete column form");
+        return RBL_ERR_STATE;
+    }
+    if (pass != 1 && pass != 2) {
+        rbl_set_error("csr column statistics: pass must be 1 or 2 (got %d)", pass);
+        return RBL_ERR_INVALID;
+    }
+    if (st->nseg > 0) {
+        const dim3 grid(sp_grid(st->nseg, SP_WPB, num_cu)), block(SP_THREADS);
+        if (pass == 1)
+            hipLaunchKernelGGL(k_csc_stat_segments<1>, grid, block, 0, s, (const int64_t*)st->colptr, (const int64_t*)st->segptr,
+                               (const int*)st->row, (const double*)st->cval, ysign, mu, part, (long long)ld, (long long)st->nseg,
+                               st->seg, (long long)n);
+        else
+            hipLaunchKernelGGL(k_csc_stat_segments<2>, grid, block, 0, s, (const int64_t*)st->colptr, (const int64_t*)st->segptr,
+                               (const int*)st->row, (const double*)st->cval, ysign, mu, part, (long long)ld, (long long)st->nseg,
+                               st->seg, (long long)n);
+    }
+    // the segments' sums of a column, folded as q = D^T c folds them (16 lanes per column, then the butterfly)
+    hipLaunchKernelGGL(k_csc_columns, dim3((unsigned)((ld * SP_QL + SP_THREADS - 1) / SP_THREADS)), dim3(SP_THREADS), 0, s,
+                       (const int64_t*)st->segptr, (const double*)part, sums, (long long)ld, (const int*)nullptr);
+    RBL_HIP(hipGetLastError());
+    return RBL_OK;
+}
+
+int launch_csr_scale(const CsrStore* st, int64_t ld, const double* inv, int num_cu, hipStream_t s) {
+    if (!st->lanes) {
+        rbl_set_error("csr scale: the data are not complete (no upload, or the last one failed)");
+        return RBL_ERR_STATE;
+    }
+    if (st->nnz <= 0) return RBL_OK;
+    hipLaunchKernelGGL(k_csr_scale_rows, dim3(sp_grid(st->nnz, 256, num_cu)), dim3(256), 0, s, (const int*)st->col, st->val,
+                       (long long)st->nnz, inv);
+    if (st->colptr && st->segptr && st->cval && st->nseg > 0)
+        hipLaunchKernelGGL(k_csc_scale_segments, dim3(sp_grid(st->nseg, SP_WPB, num_cu)), dim3(SP_THREADS), 0, s,
+                           (const int64_t*)st->colptr, (const int64_t*)st->segptr, st->cval, inv, (long long)ld, (long long)st->nseg,
+                           st->seg);
     RBL_HIP(hipGetLastError());
     return RBL_OK;
 }

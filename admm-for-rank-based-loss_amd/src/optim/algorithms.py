@@ -8,14 +8,17 @@ directory on ``PYTHONPATH``.  State (w, z, lambda) lives on the GPU; the ``w`` /
 ``lagrangian`` attributes download it on access.  All arithmetic is done by librbl.so
 (include/rbl.h); this file is host glue.  Extra keyword arguments (after the reference's
 own): ``storage`` ("f32" default | "f64" strict | "fp16" half the bytes of D, data rounded once to float16 | "csr" a sparse
-X stays sparse on the device: float64 entries, sparse passes, no standardize), ``device``;
+X stays sparse on the device: float64 entries, sparse passes, of ``standardize`` only "scale"), ``device``;
 ``l1_weights`` / ``l2_weights`` (a scalar or one value per feature: the regulariser becomes
 1/2 sum_j (l1_j |w_j| + l2_j w_j^2) - elastic net, penalty factors, unpenalised coordinates) and ``fit_intercept``
 (an unpenalised bias: the library forms the column -y * 1 itself, no host copy of X; the solver has d + 1 coordinates,
 ``coef_`` / ``intercept_`` split the result while ``w`` and ``final_res()`` keep the full vector); ``standardize`` (the
 columns of X are centred and scaled to unit population variance on the device, one rounding into the storage type;
 ``scale_mean_`` / ``scale_scale_`` hold the vectors, every later matrix of the object - the test set of ``start_store`` -
-gets the same scaling, ``unscaled()`` gives the coefficients for raw features).  X is taken as it is: a NumPy array or
+gets the same scaling, ``unscaled()`` gives the coefficients for raw features; ``standardize="scale"`` divides the columns
+by the same standard deviation without centring them - ``scale_mean_`` is all zeros, a sparse X stays sparse, and with
+``fit_intercept`` it is the model of full standardisation, the intercept shifted by sum_j w_j mean_j / scale_j; the one
+value storage "csr" takes besides False).  X is taken as it is: a NumPy array or
 torch CPU tensor of float64 / float32 / float16 is uploaded in its own type without a host copy, a torch tensor on the
 solver's GPU is read where it lives (_solver.as_source).  ``sample_weight`` (n values >= 0) and ``class_weight``
 ("balanced": c_i = n / (2 n_{y_i}), or a dict {+1: a, -1: b}) weigh the rows of an erm problem: F(w) = (1/n) sum_i c_i
@@ -52,6 +55,8 @@ _ON_DEVICE = _OnDevice()
 
 
 class Optimizer:
+    standardize = False        # False, True or "scale" (set by __init__)
+
     def __init__(self, X, y, weight_function="erm", loss="binary_cross_entropy", l2_reg=None, l1_reg=None,
                  B=None, n_class=None, args=None, w0=None, max_iter=200, tol=1e-4, storage="f32", device=0,
                  _wstep=None, _smooth_t=1.0, share_data=None, l1_weights=None, l2_weights=None, fit_intercept=False,
@@ -66,12 +71,13 @@ class Optimizer:
             raise ValueError(f"Unrecognized weight_function '{weight_function}'! Options: ['ehrm']")  # :65-68
         if weight_function == "ehrm" and B is None:
             raise ValueError("ehrm needs the reference point B")
+        standardize = _solver.resolve_standardize(standardize)       # False, True or "scale"
         src = _solver.as_source(X, device)              # X in its own type, where it lives: no host copy
-        _solver.check_csr_storage(src, storage, standardize)          # storage="csr": a sparse X, no standardisation
+        _solver.check_csr_storage(src, storage, standardize)          # storage="csr": a sparse X, no centring
         # per-coordinate penalties / intercept: validated on the host before any device call; None = the scalar path
         pen = _solver.resolve_penalty(src.shape[1], l1_reg, l2_reg, l1_weights, l2_weights, fit_intercept)
         self.fit_intercept = bool(fit_intercept)
-        self.standardize = bool(standardize)
+        self.standardize = standardize
         self._pen = pen
         # (fit_intercept: the library forms the column of ones, RBL_DATA_ONES_COLUMN)
         self.num_row, self.num_feature = src.shape[0], src.shape[1] + (1 if self.fit_intercept else 0)   # :26-27
@@ -121,6 +127,8 @@ class Optimizer:
                                  B=B, args=args, smooth_t=_smooth_t, tol=tol, max_iter=max_iter, storage=storage,
                                  device=device, share=share, gram=self.gram, l1_solver=l1_solver)
         if share is None:
+            if self.standardize == "scale":
+                self._s.set_centering(False)         # unit-variance columns, no centring: the mean vector is zeros
             self._s.set_data(src, y, scaling="fit" if self.standardize else "none",
                              ones_column=self.fit_intercept)                                  # :23 D = -y*X
             self._s.gram()                                                                    # :24 DTD
@@ -129,9 +137,13 @@ class Optimizer:
         # the scaling of the data this solver runs on (its own, or the one of the solver it borrows from)
         sc = (share if share is not None else self._s).get_scaling() if self.standardize else None
         if self.standardize and sc is None:
-            raise ValueError("standardize=True, but share_data was built without it")
-        if share is not None and not self.standardize and share.get_scaling() is not None:
-            raise ValueError("standardize=False, but share_data holds standardised data: pass standardize=True")
+            raise ValueError(f"standardize={self.standardize!r}, but share_data was built without it")
+        if share is not None:                        # the mode, not just its truth value
+            held = False if share.get_scaling() is None else (True if share.get_centering() else "scale")
+            if not self.standardize and held:
+                raise ValueError(f"standardize=False, but share_data holds standardised data: pass standardize={held!r}")
+            if self.standardize != held:
+                raise ValueError(f"standardize={self.standardize!r}, but share_data was built with standardize={held!r}")
         self._scaling = sc
         nf = src.shape[1]
         self.scale_mean_ = None if sc is None else sc[0][:nf].copy()
@@ -251,7 +263,8 @@ class Optimizer:
         # unweighted unless it gets weights of its own
         self.test_objective = rankbasedObjective(X, y, weight_function, loss, l2_reg, l1_reg, B, n_class, args,
                                                  storage=self._storage, device=self._device, _share_data=_share_data,
-                                                 scaling=self._scaling, _ones_column=self.fit_intercept,
+                                                 scaling=self._scaling, _center=self.standardize != "scale",
+                                                 _ones_column=self.fit_intercept,
                                                  _penalty=(self._pen["l1"], self._pen["l2"]) if self._pen else None,
                                                  sample_weight=sample_weight_test)
         w = self.w
@@ -439,7 +452,8 @@ class ADMMgroup:
                     raise ValueError("smooth=True members have no l1_weights, l2_weights or fit_intercept")
                 if bool(pr.get("fit_intercept")) != bool(problems[0].get("fit_intercept")):
                     raise ValueError("fit_intercept must be the same for every problem of a group (one data matrix)")
-                if bool(pr.get("standardize")) != bool(problems[0].get("standardize")):
+                pr["standardize"] = _solver.resolve_standardize(pr.get("standardize", False))
+                if pr["standardize"] != _solver.resolve_standardize(problems[0].get("standardize", False)):
                     raise ValueError("standardize must be the same for every problem of a group (one data matrix)")
                 if bool(pr.get("share_sparse")) != bool(problems[0].get("share_sparse")):
                     raise ValueError("share_sparse must be the same for every problem of a group (one set of passes)")
@@ -484,13 +498,13 @@ class ADMMgroup:
             yk = pr["y"] if pr.get("y") is not None else y
             if pr.get("smooth"):
                 s = smoothADMMmethod(X, yk, pr["weight_function"], pr["loss"], t=pr.get("t", 1), max_iter=max_iter, tol=tol,
-                                     storage=storage, device=device, share_data=share, standardize=bool(pr.get("standardize")),
+                                     storage=storage, device=device, share_data=share, standardize=pr["standardize"],
                                      gram=pr.get("gram", "auto"), **kw)
             else:
                 s = ADMMmethod(X, yk, pr["weight_function"], pr["loss"], max_iter=max_iter, tol=tol, storage=storage,
                                device=device, share_data=share, l1_weights=pr.get("l1_weights"),
                                l2_weights=pr.get("l2_weights"), fit_intercept=bool(pr.get("fit_intercept")),
-                               standardize=bool(pr.get("standardize")), gram=pr.get("gram", "auto"),
+                               standardize=pr["standardize"], gram=pr.get("gram", "auto"),
                                l1_solver=pr.get("l1_solver", "fista"), **kw)
             self.solvers.append(s)
         self._group = _solver.Group([s._s for s in self.solvers], share_sparse=bool(self.problems[0].get("share_sparse")))
@@ -580,6 +594,8 @@ class OneVsRest:
     GPU (rbl_decide_multi).  ``share_sparse=True`` (storage "csr"): the classes share multi-column sparse
     passes (ADMMgroup's ``share_sparse``); default off."""
 
+    standardize = False        # False, True or "scale" (set by __init__)
+
     def __init__(self, X, labels, weight_function="erm", loss="binary_cross_entropy", l2_reg=None, l1_reg=None, B=None,
                  args=None, storage="f32", device=0, max_iter=200, tol=1e-4, l1_weights=None, l2_weights=None,
                  fit_intercept=False, standardize=False, sample_weight=None, class_weight=None, share_sparse=False,
@@ -587,6 +603,7 @@ class OneVsRest:
         _solver.check_share_sparse(share_sparse)     # before anything touches the device
         _solver.check_gram_mode(gram)
         _solver.check_l1_solver(l1_solver)
+        self.standardize = _solver.resolve_standardize(standardize)
         # class_weight="balanced": every member gets the balanced weights of its OWN +-1 labels (one class against the
         # rest is imbalanced by construction); a common sample_weight multiplies into all of them
         Xm = _solver.as_source(X, device)
@@ -602,7 +619,7 @@ class OneVsRest:
         ys = [np.where(lab == c, 1.0, -1.0) for c in self.classes_]
         problems = [dict(weight_function=weight_function, loss=loss, l2_reg=l2_reg, l1_reg=l1_reg, B=B, args=args, y=yk,
                          l1_weights=l1_weights, l2_weights=l2_weights, fit_intercept=self.fit_intercept,
-                         standardize=bool(standardize), sample_weight=sample_weight, class_weight=class_weight,
+                         standardize=self.standardize, sample_weight=sample_weight, class_weight=class_weight,
                          share_sparse=share_sparse, gram=gram, l1_solver=l1_solver)
                     for yk in ys]
         self._storage, self._device = storage, device
@@ -644,6 +661,8 @@ class OneVsRest:
                                device=self._device, objective_only=True)
             if self._scaling is not None:
                 t.set_scaling(*self._scaling)
+                if self.standardize == "scale":
+                    t.set_centering(False)
             t.set_data(Xt, np.ones(Xt.shape[0]), scaling="none" if self._scaling is None else "apply",
                        ones_column=self.fit_intercept)
             self._test = (t, X_test)

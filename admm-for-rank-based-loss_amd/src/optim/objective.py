@@ -70,7 +70,7 @@ class rankbasedObjective:
 
     def __init__(self, X, y, weight_function="erm", loss="binary_cross_entropy", l2_reg=None, l1_reg=None,
                  B=None, n_class=None, args=None, storage="f32", device=0, _shared_solver=None, _share_data=None,
-                 _penalty=None, scaling=None, _ones_column=False, sample_weight=None, class_weight=None):
+                 _penalty=None, scaling=None, _ones_column=False, sample_weight=None, class_weight=None, _center=True):
         # sample_weight / class_weight (erm only): F(w) = (1/n) sum_i c_i loss_i(w) + R(w), _solver.resolve_row_weights
         _solver.check_problem(weight_function, loss, B, args, need_prox=False)
         if loss == "multinomial_cross_entropy":
@@ -91,7 +91,11 @@ class rankbasedObjective:
             # X as it is (_solver.as_source).  scaling: (mean, scale) of a solver (its scale_mean_ / scale_scale_, or
             # Solver.get_scaling()) - this matrix is standardised with them on the device; _ones_column: the intercept's
             Xm = _solver.as_source(X, device)
-            _solver.check_csr_storage(Xm, storage, scaling is not None, what="X_test")
+            # _center=False: the vectors of a solver trained with standardize="scale" (an all-zero mean) - scaled, not centred
+            scale_only = scaling is not None and not _center
+            _solver.check_csr_storage(Xm, storage, "scale" if scale_only else scaling is not None, what="X_test")
+            if scale_only and np.any(np.asarray(scaling[0], dtype=np.float64) != 0.0):
+                raise ValueError('scaling without centring (standardize="scale") takes an all-zero mean vector')
             self.n, self.d = Xm.shape[0], Xm.shape[1] + (1 if _ones_column else 0)
             # _share_data: another objective on the same (X, y) whose device matrix this one borrows (ADMMgroup)
             share = None if _share_data is None else _share_data._s
@@ -106,6 +110,8 @@ class rankbasedObjective:
             if share is None:
                 if scaling is not None:
                     self._s.set_scaling(*_solver.as_scaling(scaling[0], scaling[1], self.d, _ones_column))
+                    if scale_only:
+                        self._s.set_centering(False)
                 self._s.set_data(Xm, y, scaling="none" if scaling is None else "apply", ones_column=_ones_column)
             elif y_own is not None:
                 self._s.set_labels(y_own)      # labels of its own on the borrowed matrix (rbl_set_labels)

@@ -58,7 +58,7 @@ enum { RBL_WSTEP_L1 = 1, RBL_WSTEP_L2 = 2, RBL_WSTEP_SMOOTH_L1 = 3 };
 enum { RBL_STORE_F32 = 0, RBL_STORE_F64 = 1, RBL_STORE_F16 = 2 };
 /* RBL_STORE_CSR: D lives on the device as its non-zero entries only (row form: int64 indptr, int32 columns, fp64 values
  * -y_r * x widened exactly from the source; column form of the same entries for q = D^T c: 24 bytes per entry in all, no
- * n x ld matrix is ever allocated).  The data come through rbl_set_data_csr alone, with RBL_SCALE_NONE; at most 2^31 - 1
+ * n x ld matrix is ever allocated).  The data come through rbl_set_data_csr alone, with RBL_SCALE_NONE (or scaled without centring: rbl_set_centering); at most 2^31 - 1
  * entries (the column of ones included); row-sharded handles (n != n_total) are refused by rbl_create.  ld follows the
  * f64 rule.  The iteration runs the two-pass form (fused = 0) on sparse passes; see DESIGN.md, "Sparse storage". */
 enum { RBL_STORE_CSR = 3 };
@@ -302,7 +302,7 @@ int  rbl_set_data_from(rbl_solver* h, const void* X, int dtype, int mem, int64_t
 /* On a handle with storage RBL_STORE_CSR nothing is expanded: the entries are checked by the same rules (same messages)
  * and stored as they come, value -y_r * x, explicit zeros and -0.0 included; RBL_DATA_ONES_COLUMN appends the entry
  * (d - 1, -y_r) to every row.  Refused with RBL_ERR_INVALID (the handle is left without data): RBL_SCALE_FIT / APPLY
- * (centring makes D dense), nnz (plus n with the column of ones) above 2^31 - 1.  rbl_set_data / rbl_set_data_from and
+ * with centring on (centring makes D dense; rbl_set_centering(h, 0) below scales without it), nnz (plus n with the column of ones) above 2^31 - 1.  rbl_set_data / rbl_set_data_from and
  * the generator are RBL_ERR_INVALID there.  A second upload regrows the entry buffers under the handles that borrow the
  * data (the device is waited for first; their D pointer stays) and they drop what they computed from the old entries, as
  * after any second upload (rbl_set_data); after an upload that failed they answer RBL_ERR_STATE until a valid one. */
@@ -314,6 +314,32 @@ int  rbl_set_data_csr(rbl_solver* h, const void* indptr /* n + 1 */, const void*
 int  rbl_set_scaling(rbl_solver* h, const double* mean, const double* scale);
 /* the vectors of RBL_SCALE_FIT / rbl_set_scaling (either may be NULL); *is_set = 0, means 0 and scales 1 when there are none */
 int  rbl_get_scaling(rbl_solver* h, double* mean, double* scale, int* is_set);
+/* Scale-only standardisation: center = 1 (the default) leaves RBL_SCALE_FIT / APPLY as described above, every bit and
+ * message; center = 0 makes them scale the columns WITHOUT centring, from the next upload on:
+ *   RBL_SCALE_FIT    scale_j is the same statistic - the population standard deviation about the mean (ddof 0, zero
+ *                    variance: 1) - the mean vector is stored as all zeros (rbl_get_scaling reports it so) and
+ *                    D = round_to_storage(-y * (widen(x) * (1.0 / scale))), one rounding.  On dense storage the statistics
+ *                    pass is the centred one: the scale vector has its bits.
+ *   RBL_SCALE_APPLY  the same formula with the scale vector of rbl_set_scaling; a mean vector that is not all zeros is
+ *                    RBL_ERR_INVALID at the upload.
+ * With fit_intercept this is the model of full standardisation: x_std.w + b = x_scaled.w + (b - sum_j w_j mean_j / s_j).
+ *   RBL_STORE_CSR accepts RBL_SCALE_FIT / APPLY when, and only when, centring is off; entries stay entries.  A stored
+ * value is fl((-y_r x) * fl(1.0 / scale_col)) in the row form and in the column form alike (both modes scale the stored
+ * values after the store: -y_r x is exact, so these are the bits of scaling at store time); explicit zeros and -0.0 keep
+ * their bits; the entry (d - 1, -y_r) of RBL_DATA_ONES_COLUMN is never scaled (mean 0, scale 1).  RBL_SCALE_FIT takes the
+ * statistics from the column form: per column, with cnt stored entries of n, sh = the first stored x if cnt == n (the
+ * shift of the dense statistics: a constant full column has variance exactly 0) else 0, m = sum (x - sh) / n and
+ * var = (sum ((x - sh) - m)^2 + (n - cnt) m^2) / n over the stored x = -y_r * value.  Every sum is two-stage - one wave
+ * per segment of 2048 entries of the column (lane l adds the entries 2l, 2l + 1, 2l + 128, ... of the segment in order, then
+ * a butterfly), then 16 lanes over the column's segments - so the vectors depend on the column's entries alone: not on
+ * the grid, the chunk size, the index or value type or where the source lives.  A non-finite statistic is
+ * RBL_ERR_INVALID (the column is named).  An objective-only handle builds no column form: RBL_SCALE_FIT is
+ * RBL_ERR_INVALID there, RBL_SCALE_APPLY works.  rbl_kernel_time(RBL_KERNEL_SRC_STATS) reports the statistics launches,
+ * RBL_KERNEL_SRC_FORM the store pass plus the scaling launches.
+ *   Borrowers: rbl_set_centering is RBL_ERR_STATE, as rbl_set_data* is.  The presence of these symbols is the capability
+ * probe (RBL_VERSION is unchanged). */
+int  rbl_set_centering(rbl_solver* h, int center);
+int  rbl_get_centering(rbl_solver* h, int* center);
 /* Synthetic two-class data generated on the device (statistics of
  * src/util/load_data.py:101-116), never materialised on the host. */
 int  rbl_generate_synthetic(rbl_solver* h, uint64_t seed, double class_sep, double flip_y);
